@@ -2,9 +2,17 @@
 """bench.py -- headline benchmark of the transport path (BASELINE.json):
 particle-scatter steps/s and wall time per iteration, 10^6 protons per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up and K timed steps and prints the result line: the headline, the roofline and
+load_balance of those steps.  --full adds what is measured beside the headline in runs of its own: cpu_baseline,
+overlapped_iterations, pipelined_pcuts and, with --mixed, photon_leg.  --dump-outputs DIR writes what the last timed
+step handed its caller (the merged tallies, ion_finalize's and iter_finalize's results; with --smooth the profile it left)
+as DIR/<name>.npy in float64, at most 64 MB in all.  The inputs depend on the arguments alone (a deterministic injection,
+counter-based RNG keyed by iteration, species, pcut and particle index), so two builds can be compared output for output; the fp64 tallies
+agree up to the order of their atomic adds.
 
 One "step" = one full iteration (`i_iter` body of src/main_loops.jl:52-391) of the
 workload: BASELINE config[1] -- 10^6 protons per GPU, single unmodified gamma0 = 5
@@ -22,17 +30,20 @@ Extra objects in the JSON line:
                is scalar fp64 arithmetic, neither HBM- nor MFMA-bound (SURVEY.md 8d);
                achieved = 400 algorithmic flop/step x steps / kernel time (HIP events on
                the kernel's stream, summed over the launches of the timed region).
-  cpu_baseline the CPU oracle (C++ restatement, glibc libm, OpenMP over particles on all
+  cpu_baseline (--full) the CPU oracle (C++ restatement, glibc libm, OpenMP over particles on all
                host cores) on a bounded sample of the same workload -- a surrogate for
                the Julia reference, which cannot run here; `single_thread` inside it is
                the same code on one core (the reference itself is serial), smaller sample.
   load_balance (N > 1) the largest local population over the mean, per pcut: worst and
                step-weighted mean over the timed iterations.
-  overlapped_iterations  (N = 1) a separate leg AFTER the timed region, never part of `value`: the same iterations
+  overlapped_iterations  (--full, N = 1) a separate leg AFTER the timed region, never part of `value`: the same iterations
                with two of them in flight on two contexts / streams (driver.run_overlapped) -- possible because the
                workload's shock profile is fixed, so its iterations are independent; --overlap 1 skips it.
+  pipelined_pcuts  (--full, N = 1) the same iterations with the pcuts pipelined (pipelined_leg); --long-draws 0 skips it.
+  photon_leg   (--full, --mixed, N = 1) the electron species' photon post-processing after the timed region.
 """
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -125,6 +136,50 @@ def pipelined_leg(mcs, prob, be, args, first_iter, sm):
             "note": "one iteration after the other, every pcut's long histories beside the next pcut; not the headline value"}
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE = 1 << 20          # elements kept of an array that has to be sampled to stay within the limit
+
+
+def step_outputs(prob, layout, res, n_itrs, smooth):
+    """What a caller of driver.run receives after the last timed step, as float64 arrays by name: the merged tallies (the
+    int64 counters as one array), ion_finalize's and iter_finalize's results of that iteration, and the profile it left
+    behind when the profile evolves."""
+    import numpy as np
+    out = {}
+    for name in layout.offsets:
+        a = layout.view(res.tallies_f64, name)
+        if name in ("px_esc_feb", "energy_esc_feb"):
+            a = a[:n_itrs]      # the rows of the iterations that ran (--full makes room for the iterations of its legs)
+        out["tally_" + name] = a
+    out["tally_i64"] = res.tallies_i64
+    _, it_fin, ion_fin = res.iter_finals[-1]
+    for obj, prefix in ((ion_fin, "ion_finalize_"), (it_fin, "iter_finalize_")):
+        for f in dataclasses.fields(obj):
+            out[prefix + f.name] = getattr(obj, f.name)
+    out["iter_state_Gamma_grid"] = res.iter_state.Gamma_grid
+    if smooth:
+        for name in ("ux", "gam_sf", "utot", "beta_ef", "gam_ef", "btot"):
+            out["profile_" + name] = getattr(prob, name)
+    return {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array; if they exceed DUMP_LIMIT_BYTES, arrays of more than DUMP_SAMPLE elements are cut to
+    the same seeded sample of DUMP_SAMPLE flat indices each, so that the files of two runs stay comparable."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            total -= a.nbytes - DUMP_SAMPLE * a.itemsize
+            arrays[name] = a.reshape(-1)[idx]
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes after sampling, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def workload_label(args):
     """What actually ran, built from the arguments: every kept bench line names its own workload."""
     n = args.particles
@@ -186,6 +241,9 @@ def main():
     ap.add_argument("--smooth", action="store_true", help="replace the shock profile after every iteration (smooth_grid_par): config[2]'s loop")
     ap.add_argument("--mixed", action="store_true", help="BASELINE config[4]'s species mix: protons + He + electrons, radiative losses, ion -> electron energy transfer (--particles per species)")
     ap.add_argument("--fp32", action="store_true", help="the fp32-state variant of the transport kernel (config[4]); tallies stay fp64")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: the CPU baseline, the overlapped and pipelined legs, --mixed's photon leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64, <= 64 MB in all)")
     args = ap.parse_args()
 
     import torch
@@ -222,9 +280,9 @@ def main():
     n_global = args.particles * world
     n_itrs = args.steps + args.warmup
     # (room in the per-iteration tallies for the iterations of the extra overlapped leg, which carry on the numbering)
-    overlap_leg = world == 1 and not force_comm and args.overlap > 1 and not args.smooth and not args.mixed and not args.fp32
+    overlap_leg = args.full and world == 1 and not force_comm and args.overlap > 1 and not args.smooth and not args.mixed and not args.fp32
     n_extra = (2 * args.overlap + args.steps) if overlap_leg else 0
-    pipe_leg = world == 1 and not force_comm and args.long_draws > 0 and not args.fp32 and not args.smooth
+    pipe_leg = args.full and world == 1 and not force_comm and args.long_draws > 0 and not args.fp32 and not args.smooth
     pipe_first = n_itrs + n_extra + 1
     if pipe_leg:
         n_extra += 1 + args.steps
@@ -335,7 +393,9 @@ def main():
             out["rehearsal"] = {"ranks_on_one_device": world, "backend": backend, "device_mem_used_gb_at_end": (total_b - free_b) / 1e9,
                                 "torch_peak_alloc_gb_rank0": torch.cuda.max_memory_allocated() / 1e9,
                                 "note": "all ranks share ONE GPU: rates say nothing about scaling; host-side cost and footprint of the multi-rank path only"}
-        if world == 1 and not args.no_cpu:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, step_outputs(prob, be.layout, res, n_itrs, args.smooth))
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(mcs, args.cpu_sample, n_sample_1t=args.cpu_sample_1t)
         if overlap_leg:
             out["overlapped_iterations"] = overlapped_leg(mcs, hip_backend, prob, be, local, args)
@@ -345,7 +405,7 @@ def main():
                 out["pipelined_pcuts"] = pipelined_leg(mcs, prob, be, args, pipe_first, sm)
             except Exception as e:      # noqa: BLE001
                 out["pipelined_pcuts"] = {"error": f"{type(e).__name__}: {e}"}
-        if args.mixed and world == 1:
+        if args.full and args.mixed and world == 1:
             # the photon leg of config[4] ("inverse-Compton/synch photon tallies"): ion_finalize's photon_calcs for the electron
             # species on the histograms the last iteration left on the device (K4 dN/dp, K5 synchrotron, K6 get_dNdp_2D + IC).
             # Reported beside the headline: it is O(bins) work per species, outside the particle loop the metric counts.

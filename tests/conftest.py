@@ -6,6 +6,10 @@ import sys
 
 import numpy as np
 import pytest
+# torch bundles its own HIP and ROCr runtimes, and libmcs_hip.so binds to whichever libamdhip64.so.7 the process has
+# loaded first.  Importing torch before any test loads the library keeps one runtime per process, as in bench.py and
+# smoke(); the other way round the process holds two, and torch then finds no GPU.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -2,9 +2,10 @@
 # Kernel trace of the bench line with the overlapped leg: how much of the time two K1 launches are resident at once.
 # usage (GPU box): tools/profile_overlap.sh <tag>  -> gpurun_out/<tag>/overlap_summary.txt
 set -e
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python $GRAFT_REPO_ROOT/bench.py --no-cpu --steps 4 > $OUT/trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python $ROOT/bench.py --full --no-cpu --steps 4 > $OUT/trace.log 2>&1
 python3 - <<PY
 import csv, glob
 rows = []
@@ -16,7 +17,7 @@ rows.sort()
 out = open("$OUT/overlap_summary.txt", "w")
 def P(*a):
     print(*a); print(*a, file=out)
-P(f"== rocprofv3 --kernel-trace of: python bench.py --no-cpu --steps 4   ({len(rows)} K1 launches on {len(set(r[2] for r in rows))} streams / queues)")
+P(f"== rocprofv3 --kernel-trace of: python bench.py --full --no-cpu --steps 4   ({len(rows)} K1 launches on {len(set(r[2] for r in rows))} streams / queues)")
 # sweep line: time with >= 1 and with >= 2 K1 launches resident, separately for the sequential part (one stream) and the overlapped leg
 ev = sorted([(s, 1) for s, e, q in rows] + [(e, -1) for s, e, q in rows])
 busy1 = busy2 = 0; depth = 0; last = ev[0][0]
