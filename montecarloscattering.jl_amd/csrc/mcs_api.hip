@@ -17,14 +17,12 @@
 #include <chrono>
 
 extern "C" {
-size_t mcs_transport_smem_bytes(int n_grid, int n_tcuts);
 int mcs_transport_max_entries(void);
-hipError_t mcs_launch_transport(const KArgs* a_dev, int kind, int blocks, int threads, hipStream_t st);
+hipError_t mcs_launch_transport(const KArgs* a_dev, int kernel, int blocks, int threads, hipStream_t st);
 int mcs_transport_ws_threads(void);
 hipError_t mcs_launch_finalize_split_dev(const uint8_t* l_save, long long cap_n, unsigned int* block_counts, unsigned long long* block_offsets,
                                          unsigned long long* scan_total, long long* src, PcutDev* pd, PcutDev* pd_next, unsigned long long* counters,
                                          long long n_target, unsigned long long* err, DevPop sv, DevPop out, int split_blocks, hipStream_t st);
-hipError_t mcs_launch_transport_f32(const KArgs* a_dev, int kind, int blocks, int threads, hipStream_t st);
 hipError_t mcs_launch_compact(const uint8_t* l_save, long long n, unsigned int* block_counts, unsigned long long* block_offsets,
                               unsigned long long* total_dev, long long* src, hipStream_t st);
 hipError_t mcs_launch_split(DevPop sv, DevPop out, const long long* src, long long n_new, long long i_mult, hipStream_t st);
@@ -106,9 +104,7 @@ struct mcs_ctx {
   // exports its live particles and ends; the host relaunches them, spread over the chip's waves, until none is left
   int tail_budget = 0;         // trips; 0 = one launch per pcut, run to the end
   int tail_rounds_last = 0;    // launches the last mcs_run_pcut* took
-  int claim_max_first = 64;    // MCS_CLAIM_MAX=<n> (environment): live particles per wave in the FIRST launch of a pcut (measurements of tau(L))
   double* d_strag[2] = {nullptr, nullptr}; long long strag_cap = 0;
-  int f32_blocks_per_cu = 3;   // MCS_F32_BLOCKS=<n>: resident workgroups per CU the organised fp32 kernel is launched for (its occupancy)
   bool f32_exact = false;      // MCS_F32_EXACT=1: the plain loop with the exact fp32 primitives (include/mcs_math_f32.h): the kernel the CPU restatement
                                // oracle/mcs_oracle_f32.inc reproduces bit for bit (tests)
   bool f32_loop = false;       // MCS_F32_LOOP=1: the fp32-state variant as a plain per-lane loop (the reference semantics of that variant; tests)
@@ -156,16 +152,12 @@ struct mcs_ctx {
   unsigned int* pp_bcounts = nullptr; unsigned long long* pp_boffs = nullptr; long long* pp_src = nullptr;
   unsigned long long* pp_dpc = nullptr; unsigned long long* pp_hpc = nullptr;
   KArgs* pp_hargs = nullptr; KArgs* pp_dargs = nullptr; PcutDev* pp_dpdl = nullptr; PcutDev* pp_hpdl = nullptr;
-  int pp_side_waves = 0;       // MCS_PIPE_SIDE_WAVES=<n>: waves the resumed long histories are spread over (0: one per SIMD of the chip)
-  int pp_side_max = 64;        // MCS_PIPE_SIDE_MAX=<n>: workgroups (of 2 per CU) the main launch leaves free for them at most
   int pp_waits_last = 0;       // pcuts of the last pipelined run whose i_mult had to wait for the long histories
   bool force_general = false;  // MCS_FORCE_GENERAL=1: always the general kernel (tests compare the two)
   int k1_ws = 2;               // the wave-specialised kernels (mcs_transport_ws.inc), where they apply: MCS_K1_WS=1 always, =0 never, default (2)
                                // for populations of at least ws_auto_min particles -- measured level with transport_body at 4e6 particles, 3.8 %
                                // faster at 1e7 and 7 % slower at 2e6, where its missing tail consolidation shows (profiles/r04_ws_kernel_ab.txt)
   long long ws_auto_min = 6000000;   // MCS_WS_AUTO_MIN=<n>
-  int ws_pop_max = 0;          // MCS_WS_POP=<n>: particles a block of the wave-specialised kernel holds at most (0: lanes + 160)
-  int ws_serve_min = 64;       // MCS_WS_SERVE=<n>: pending particles at which a wave serves them
   // consumers (K4): table staging, outputs, thermo scratch slab
   double* d_ctab = nullptr; double* d_cout = nullptr; double* d_cscratch = nullptr; unsigned long long* d_cdiag = nullptr;
   double* d_c2d = nullptr; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
@@ -321,19 +313,13 @@ int mcs_create(const mcs_params* p, int device, void* stream, mcs_ctx** out) {
   { const char* e = std::getenv("MCS_TAIL_MERGE"); c->tail_merge = !(e && e[0] == '0'); }
   { const char* e = std::getenv("MCS_K1_WS"); c->k1_ws = !e ? 2 : (e[0] == '1' ? 1 : (e[0] == '0' ? 0 : 2)); }
   { const char* e = std::getenv("MCS_WS_AUTO_MIN"); if (e && std::atoll(e) >= 0) c->ws_auto_min = std::atoll(e); }
-  { const char* e = std::getenv("MCS_WS_POP"); if (e && std::atoi(e) >= 64 && std::atoi(e) <= 4096) c->ws_pop_max = std::atoi(e); }
-  { const char* e = std::getenv("MCS_WS_SERVE"); if (e && std::atoi(e) >= 1 && std::atoi(e) <= 64) c->ws_serve_min = std::atoi(e); }
   { const char* e = std::getenv("MCS_PARK"); c->park = !(e && e[0] == '0'); }
   { const char* e = std::getenv("MCS_TAIL_RING"); c->tail_ring = !(e && e[0] == '0'); }
   { const char* e = std::getenv("MCS_TAIL_LOOP"); if (e && std::atoi(e) >= 0 && std::atoi(e) <= 32) c->tail_loop = std::atoi(e); }
   { const char* e = std::getenv("MCS_F32_LOOP"); c->f32_loop = e && e[0] == '1'; }
   { const char* e = std::getenv("MCS_F32_EXACT"); c->f32_exact = e && e[0] == '1'; }
-  { const char* e = std::getenv("MCS_F32_BLOCKS"); if (e && std::atoi(e) >= 1 && std::atoi(e) <= 8) c->f32_blocks_per_cu = std::atoi(e); }
   { const char* e = std::getenv("MCS_TAIL_BUDGET"); if (e && std::atoi(e) >= 0) c->tail_budget = std::atoi(e); }
-  { const char* e = std::getenv("MCS_CLAIM_MAX"); if (e && std::atoi(e) >= 1 && std::atoi(e) <= 64) c->claim_max_first = std::atoi(e); }
-  { const char* e = std::getenv("MCS_PIPE_SIDE_WAVES"); if (e && std::atoi(e) >= 1) c->pp_side_waves = std::atoi(e); }
   { const char* e = std::getenv("MCS_PIPE_SIDE_CUS"); if (e && std::atoi(e) >= 0 && std::atoi(e) <= 128) c->pp_side_cus = std::atoi(e); }
-  { const char* e = std::getenv("MCS_PIPE_SIDE_MAX"); if (e && std::atoi(e) >= 0 && std::atoi(e) <= 256) c->pp_side_max = std::atoi(e); }
   { const char* e = std::getenv("MCS_REFILL_MIN"); if (e && std::atoi(e) >= 1 && std::atoi(e) <= 48) c->refill_min = std::atoi(e); }
   { const char* e = std::getenv("MCS_DEFER_K"); if (e && std::atoi(e) >= 1 && std::atoi(e) <= 40) c->defer_k = std::atoi(e); }
   c->P = *p;
@@ -694,6 +680,75 @@ int mcs_run_pcut_indexed(mcs_ctx* c, int i_pcut, const int64_t* dev_gidx, int64_
   return run_pcut_impl(c, i_pcut, 0, 1, dev_gidx, n_saved);
 }
 
+// ---- K1 launches: which kernel, its geometry, the launch constants
+
+// The K1 kernel the context's current species runs, its block size and the workgroups of it a CU holds (2 for the fp64 kernels --
+// 78 KB of LDS each --, 1 for the wave-specialised ones, 3 for the fp32-state kernels -- the organised one: 168 VGPRs, 51 KB).
+// n: the population that decides the wave-specialised form (MCS_K1_WS, MCS_WS_AUTO_MIN).  sliced: a launch that suspends and resumes
+// particles -- the tail slicing of mcs_run_pcut* (mcs_set_tail_slicing) runs the general kernel's sliced form for every species, the
+// pipelined loop (which refuses tail slicing) the sliced form of the species' own kernel.
+struct K1Plan { int kernel, threads, per_cu; };
+static bool is_ws(int kernel) { return kernel == K1_WS || kernel == K1_WS_ETF; }
+static K1Plan k1_plan(const mcs_ctx* c, long long n, bool sliced) {
+  const mcs_params& P = c->P;
+  // the specialised kernel for the common configuration (see transport_body<PLAIN> in mcs_transport.hip)
+  const bool plain_but_etf = !c->force_general && c->all_parallel && !P.dont_scatter && !P.use_custom_epsB && !P.dont_DSA &&
+                             !(P.feb_downstream > 0) && c->aa >= 1 && c->tb.n_xspec == 0 && !(c->h_inj_fracs[c->i_ion - 1] < 1);
+  const bool plain = plain_but_etf && !(P.energy_transfer_frac > 0);
+  const bool plain_etf = plain_but_etf && !plain;      // the ions of a run with energy transfer: PLAIN with that one flag at run time
+  // the specialised kernel for electrons with radiative losses (transport_body<false, LOSSY>): the loss in line in the common pass
+  const bool lossy = !c->force_general && P.do_rad_losses && c->aa < 1 && !P.use_custom_epsB && !P.dont_scatter;
+  if (P.state_fp32) return {c->f32_exact ? K1_F32_LOOP_EXACT : (c->f32_loop ? K1_F32_LOOP : (lossy ? K1_F32_LOSSY : K1_F32)), 256, 3};
+  if (sliced && c->tail_budget > 0) return {K1_SLICED, 256, 2};
+  if (sliced) return {plain ? K1_PLAIN_SLICED : (lossy ? K1_LOSSY_SLICED : (plain_etf ? K1_PLAIN_ETF_SLICED : K1_SLICED)), 256, 2};
+  // the wave-specialised form of PLAIN / PLAIN_ETF (mcs_transport_ws.inc), not with an explicit launch geometry
+  if ((plain || plain_etf) && c->blocks <= 0 && (c->k1_ws == 1 || (c->k1_ws == 2 && n >= c->ws_auto_min)))
+    return {plain ? K1_WS : K1_WS_ETF, mcs_transport_ws_threads(), 1};
+  return {plain ? K1_PLAIN : (lossy ? K1_LOSSY : (plain_etf ? K1_PLAIN_ETF : K1_GENERAL)), 256, 2};
+}
+
+// persistent lanes: fill the chip (`full` workgroups), never launch more lanes than particles, at least one workgroup
+static int persistent_grid(long long n, int threads, long long full) {
+  return (int)std::max(1LL, std::min((n + threads - 1) / threads, full));
+}
+
+// live particles a wave holds at most (KArgs::claim_max) and the two flags that go with it: a sparse wave (fewer than 64) neither
+// defers its rare work nor waits for company nor consolidates
+static void set_claim(const mcs_ctx* c, KArgs& a, int claim_max) {
+  const bool dense = claim_max >= 64;
+  a.claim_max = claim_max;
+  // a wave whose live lanes all wait for company (fewer than defer_k of them) must be able to refill: with
+  // defer_k + refill_min <= 64 either defer_k lanes are live or refill_min are idle (see the deferral in transport_body)
+  a.defer_k = dense ? std::min(c->defer_k, 64 - c->refill_min) : 1;
+  a.wait_full = dense && c->park;
+  a.tail_merge = dense && c->tail_merge;
+}
+
+// A launch of n_x resumed particles spread over `waves` waves: a pass costs a wave the same with 1 live lane as with 64, but the rare
+// work of every live lane stalls all the others, so the fewer particles share a wave the faster each history advances -- and the
+// launch waits for its longest one.  Measured (profiles/r03_tau_vs_lanes.txt: 2048 particles, kernel time of 14 pcuts): 64 particles
+// per wave 45.6 ms, 32: 38.1, 16: 35.6, 8: 33.4, 4: 31.6, 2 (one wave per SIMD): 31.7, 1 (two waves per SIMD): 37.9 -- so as few
+// particles per wave as `waves` allow, and a dense launch when that would be more than 16.  Sets the claim of `a`; returns the
+// workgroups, at most `full`.
+static int sparse_claim(const mcs_ctx* c, KArgs& a, long long n_x, long long waves, int threads, long long full) {
+  long long cm = (n_x + waves - 1) / waves;
+  if (cm > 16) cm = 64;
+  set_claim(c, a, (int)cm);
+  const long long per_block = (long long)(threads / 64) * cm;
+  return (int)std::min((n_x + per_block - 1) / per_block, full);
+}
+
+// two export buffers of need_cap lane states each (sliced launches)
+static int ensure_strag(mcs_ctx* c, long long need_cap) {
+  if (need_cap <= c->strag_cap) return 0;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->strag_cap = 0;
+  for (double*& p : c->d_strag) { if (p) (void)hipFree(p); p = nullptr; }
+  for (double*& p : c->d_strag) HIPCHK(hipMalloc((void**)&p, (size_t)need_cap * MCS_STRAG_WORDS * sizeof(double)));
+  c->strag_cap = need_cap;
+  return 0;
+}
+
 // the launch constants of one pcut that do not depend on the kernel chosen (shared by mcs_run_pcut* and mcs_run_pcuts_fused)
 static void fill_kargs(mcs_ctx* c, KArgs& a, int i_pcut, long long n, long long i_prt_offset, long long i_prt_stride, const long long* dev_gidx, int budget) {
   std::memset(&a, 0, sizeof(a));
@@ -706,11 +761,8 @@ static void fill_kargs(mcs_ctx* c, KArgs& a, int i_pcut, long long n, long long 
   a.i_iter = c->i_iter; a.i_ion = c->i_ion; a.i_pcut = i_pcut;
   a.n = n; a.i_prt_offset = i_prt_offset; a.i_prt_stride = i_prt_stride; a.gidx = dev_gidx;
   a.retro_cap = c->retro_cap;
-  a.defer_k = c->defer_k;
   a.refill_min = c->refill_min;
-  // a wave whose live lanes all wait for company (fewer than defer_k of them) must be able to refill: with
-  // defer_k + refill_min <= 64 either defer_k lanes are live or refill_min are idle (see the deferral in transport_body)
-  if (a.defer_k > 64 - a.refill_min) a.defer_k = 64 - a.refill_min;
+  set_claim(c, a, 64);
   a.tail_ring = c->tail_ring ? 1 : 0;
   a.tail_loop = c->tail_ring ? c->tail_loop : 0;
   // iseed_mod - i_prt, src/particle_loop.jl:35-40
@@ -718,25 +770,12 @@ static void fill_kargs(mcs_ctx* c, KArgs& a, int i_pcut, long long n, long long 
                                      (long long)(c->i_ion - 1) * c->P.n_pts_max * c->tb.n_pcuts +
                                      (long long)(i_pcut - 1) * c->P.n_pts_max);
   a.work_counter = c->d_counters; a.n_saved = c->d_counters + 1;
-  a.tail_merge = c->tail_merge ? 1 : 0;
-  a.wait_full = c->park ? 1 : 0;
   a.tally_rep = c->d_tally_rep; a.rep_n = c->d_tally_rep ? c->rep_n : 0;
   if (c->debug_finals) { a.f_reason = c->f_reason; a.f_helix = c->f_helix; a.f_retro = c->f_retro; a.f_ptot = c->f_ptot; a.f_x = c->f_x; }
-  a.claim_max = 64; a.budget_trips = budget; a.strag_count = c->d_counters + 3;
+  a.budget_trips = budget; a.strag_count = c->d_counters + 3;
   a.strag_out = c->d_strag[0];
-}
-
-// which transport kernel a context's current species runs (mcs_launch_transport's `kind`), without the sliced / explicit-geometry cases
-static int species_kernel_kind(mcs_ctx* c, const KArgs& a, long long n, bool* ws_out) {
-  const bool plain_but_etf = !c->force_general && c->all_parallel && !c->P.dont_scatter && !c->P.use_custom_epsB &&
-                             !c->P.dont_DSA && !(c->P.feb_downstream > 0) && c->aa >= 1 && c->tb.n_xspec == 0 && !(a.inj_frac < 1);
-  const bool plain = plain_but_etf && !(c->P.energy_transfer_frac > 0);
-  const bool plain_etf = plain_but_etf && !plain;
-  const bool lossy = !c->force_general && c->P.do_rad_losses && c->aa < 1 && !c->P.use_custom_epsB && !c->P.dont_scatter;
-  const bool ws = (c->k1_ws == 1 || (c->k1_ws == 2 && n >= c->ws_auto_min)) && (plain || plain_etf) && !c->P.state_fp32;
-  if (ws_out) *ws_out = ws;
-  if (c->P.state_fp32) return c->f32_exact ? 3 : (c->f32_loop ? 1 : (lossy ? 2 : 0));
-  return ws ? (plain ? 7 : 8) : (plain ? 1 : (lossy ? 2 : (plain_etf ? 6 : 0)));
+  a.ws_pop_max = mcs_transport_ws_threads() + 160;      // (read by the wave-specialised kernels only)
+  a.ws_serve_min = 64;
 }
 
 static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i_prt_stride, const int64_t* dev_gidx, int64_t* n_saved) {
@@ -756,73 +795,35 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
     // one entry per lane a launch can hold: 2 workgroups of 256 threads per CU, or the geometry of mcs_set_launch if that is larger
     long long need_cap = (long long)2 * c->n_cu * 256;
     if (c->blocks > 0 && (long long)c->blocks * c->threads > need_cap) need_cap = (long long)c->blocks * c->threads;
-    if (need_cap > c->strag_cap) {
-      HIPCHK(hipStreamSynchronize(c->stream));
-      for (int b = 0; b < 2; ++b) { if (c->d_strag[b]) (void)hipFree(c->d_strag[b]); c->d_strag[b] = nullptr; }
-      c->strag_cap = need_cap;
-      for (int b = 0; b < 2; ++b) HIPCHK(hipMalloc((void**)&c->d_strag[b], (size_t)c->strag_cap * MCS_STRAG_WORDS * sizeof(double)));
-    }
+    if (ensure_strag(c, need_cap)) return 1;
   }
 
   KArgs& a = *c->h_args_pin;     // (every launch below is followed by a stream synchronisation before this is written again)
   fill_kargs(c, a, i_pcut, n, i_prt_offset, i_prt_stride, (const long long*)dev_gidx, budget);
 
-  const int threads = c->threads;
-  int blocks = c->blocks;
-  // two 256-thread blocks are resident per CU (78 KB of LDS each); the fp32-state kernel (27 KB, 119 VGPRs) fits four
-  // (resident workgroups per CU: 2 for the fp64 kernel -- 78 KB of LDS each --, 3 for the organised fp32 kernel -- 168 VGPRs, 51 KB --,
-  // 4 for its plain-loop form)
-  const long long full = (long long)c->n_cu * (c->P.state_fp32 ? ((c->f32_loop || c->f32_exact) ? 3 : c->f32_blocks_per_cu) : 2);
-  if (blocks <= 0) {
-    // persistent lanes: fill the chip, never launch more lanes than particles
-    const long long want = (n + threads - 1) / threads;
-    blocks = (int)(want < full ? want : full);
-    if (blocks < 1) blocks = 1;
-  }
-  if (c->claim_max_first < 64 && !c->P.state_fp32) {
-    a.claim_max = c->claim_max_first; a.defer_k = 1; a.wait_full = 0; a.tail_merge = 0;
-    const long long per_block = (long long)(threads / 64) * a.claim_max;
-    const long long nb = (n + per_block - 1) / per_block;
-    if (c->blocks <= 0) blocks = (int)(nb < full ? (nb > 0 ? nb : 1) : full);
-  }
+  const K1Plan k1 = k1_plan(c, n, budget > 0);
+  const bool ws = is_ws(k1.kernel);
+  // the geometry of mcs_set_launch, else the persistent grid (mcs_set_launch's block size sizes the grid of the fp32-state kernels
+  // too, which always run k1.threads)
+  const int threads = ws ? k1.threads : c->threads;
+  const int launch_threads = c->P.state_fp32 ? k1.threads : threads;
+  const long long full = (long long)c->n_cu * k1.per_cu;
+  int blocks = c->blocks > 0 ? c->blocks : persistent_grid(n, threads, full);
   if (budget > 0 && (long long)blocks * threads > c->strag_cap) return fail("mcs_run_pcut: launch geometry exceeds the export buffer of a sliced run");
-  // the specialised kernel for the common configuration (see transport_body<PLAIN> in mcs_transport.hip)
-  const bool plain_but_etf = !c->force_general && c->all_parallel && !c->P.dont_scatter && !c->P.use_custom_epsB &&
-                             !c->P.dont_DSA && !(c->P.feb_downstream > 0) && c->aa >= 1 && c->tb.n_xspec == 0 && !(a.inj_frac < 1);
-  const bool plain = plain_but_etf && !(c->P.energy_transfer_frac > 0);
-  const bool plain_etf = plain_but_etf && !plain;      // the ions of a run with energy transfer: PLAIN with that one flag at run time
-  // the specialised kernel for electrons with radiative losses (transport_body<false, LOSSY>): the loss in line in the common pass
-  const bool lossy = !c->force_general && c->P.do_rad_losses && c->aa < 1 && !c->P.use_custom_epsB && !c->P.dont_scatter;
-  // sliced launches (suspend / resume, fewer than 64 particles per wave) run the general kernel's SLICED form
-  const bool sliced = !c->P.state_fp32 && (budget > 0 || c->claim_max_first < 64);
-  // the wave-specialised form of those two (mcs_transport_ws.inc): 512-thread blocks, one per CU
-  const bool ws = (c->k1_ws == 1 || (c->k1_ws == 2 && n >= c->ws_auto_min)) && (plain || plain_etf) && !c->P.state_fp32 && budget == 0 &&
-                  c->claim_max_first == 64 && c->blocks <= 0;
-  int k1_threads = threads;
-  if (ws) {
-    k1_threads = mcs_transport_ws_threads();
-    const long long want = (n + k1_threads - 1) / k1_threads;
-    blocks = (int)(want < c->n_cu ? (want > 0 ? want : 1) : c->n_cu);
-    a.ws_pop_max = c->ws_pop_max > 0 ? c->ws_pop_max : k1_threads + 160;
-    a.ws_serve_min = c->ws_serve_min;
-  }
   double ms_total = 0.0;
   c->tail_rounds_last = 0;
-  c->kernel_last = c->P.state_fp32 ? (c->f32_exact ? 9 : (c->f32_loop ? 4 : (lossy ? 5 : 3))) : (sliced ? 10 : (ws ? (plain ? 7 : 8) : (plain ? 1 : (lossy ? 2 : (plain_etf ? 6 : 0)))));
+  c->kernel_last = k1.kernel;
   for (int round = 0;; ++round) {
     HIPCHK(hipMemcpyAsync(c->d_args, c->h_args_pin, sizeof(KArgs), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     if (n > 0) {
-      if (c->P.state_fp32) HIPCHK(mcs_launch_transport_f32(c->d_args, c->f32_exact ? 3 : (c->f32_loop ? 1 : (lossy ? 2 : 0)), blocks, 256, c->stream));
-      else HIPCHK(mcs_launch_transport(c->d_args, sliced ? 10 : (ws ? (plain ? 7 : 8) : (plain ? 1 : (lossy ? 2 : (plain_etf ? 6 : 0)))), blocks, k1_threads, c->stream));
+      HIPCHK(mcs_launch_transport(c->d_args, k1.kernel, blocks, launch_threads, c->stream));
       c->rep_dirty = true;
     }
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     ++c->tail_rounds_last;
     if (budget == 0) break;
-    // sliced run: how many particles did the launch export?  They are the next launch's queue, spread over the chip's waves:
-    // a pass costs a wave the same with 1 live lane as with 64, but the rare work of every live lane stalls all the others,
-    // so the fewer particles share a wave the faster each history advances -- and the launch waits for its longest one.
+    // sliced run: how many particles did the launch export?  They are the next launch's queue, spread over the chip's waves
     HIPCHK(hipMemcpyAsync(c->h_back + 2, c->d_counters + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     const unsigned long long n_x = c->h_back[2];
@@ -835,20 +836,9 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
     HIPCHK(hipMemsetAsync(c->d_counters + 3, 0, sizeof(unsigned long long), c->stream));    // export counter
     a.strag_in = c->d_strag[round & 1]; a.strag_out = c->d_strag[(round + 1) & 1];
     a.n_resume = (long long)n_x; a.fresh_lo = n;
-    // measured (profiles/r03_tau_vs_lanes.txt: 2048 particles, kernel time of 14 pcuts): 64 particles per wave 45.6 ms, 32: 38.1,
-    // 16: 35.6, 8: 33.4, 4: 31.6, 2 (one wave per SIMD): 31.7, 1 (two waves per SIMD): 37.9 -- so one wave per SIMD, as few
-    // particles per wave as that allows, and a dense launch when that would be more than 16
-    const long long waves1 = (long long)c->n_cu * (threads / 64);           // one wave per SIMD
-    long long cm = ((long long)n_x + waves1 - 1) / waves1;
-    if (cm > 16) cm = 64;
-    a.claim_max = (int)cm;
-    if (cm < 64) { a.defer_k = 1; a.wait_full = 0; a.tail_merge = 0; }
-    else { a.defer_k = c->defer_k > 64 - c->refill_min ? 64 - c->refill_min : c->defer_k; a.wait_full = c->park ? 1 : 0; a.tail_merge = c->tail_merge ? 1 : 0; }
-    const long long per_block = (long long)(threads / 64) * cm;
-    long long nb = ((long long)n_x + per_block - 1) / per_block;
-    blocks = (int)(nb < full ? nb : full);
+    blocks = sparse_claim(c, a, (long long)n_x, (long long)c->n_cu * (threads / 64), threads, full);     // one wave per SIMD
     // few particles per wave already: nothing left to gain from another slice
-    a.budget_trips = cm <= 4 ? 0 : budget;
+    a.budget_trips = a.claim_max <= 4 ? 0 : budget;
   }
   // the compaction half of new_pcut, queued behind the kernel: src[] for mcs_new_pcut / mcs_saved_export and an
   // independent count of the l_save flags next to the kernel's own n_saved counter, read back together
@@ -888,7 +878,7 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   if (!c->have_grid || !c->have_cuts) return fail("mcs_run_pcuts_fused: grid/cuts not set");
   if (i_pcut_first < 1 || i_pcut_last > c->tb.n_pcuts || i_pcut_last < i_pcut_first) return fail("mcs_run_pcuts_fused: pcut range");
   if (!n_target || !n_use_out || !n_saved_out || !i_mult_out) return fail("mcs_run_pcuts_fused: null argument");
-  if (c->tail_budget > 0 || c->claim_max_first < 64 || c->blocks > 0) return fail("mcs_run_pcuts_fused: not with sliced launches or an explicit launch geometry");
+  if (c->tail_budget > 0 || c->blocks > 0) return fail("mcs_run_pcuts_fused: not with sliced launches or an explicit launch geometry");
   const int npc = i_pcut_last - i_pcut_first + 1;
   long long cap_n = c->n;
   for (int k = 0; k < npc; ++k) { if (n_target[k] < 1) return fail("mcs_run_pcuts_fused: n_target < 1"); if (n_target[k] > cap_n) cap_n = n_target[k]; }
@@ -911,23 +901,15 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   }
   // launch constants of every pcut: the buffers rotate (cur -> saved -> spare -> cur) independently of the sizes
   PopBuf cur = c->cur, spare = c->spare;
-  int kind = 0, blocks = 0, threads = c->threads;
-  bool ws = false;
   for (int k = 0; k < npc; ++k) {
     KArgs& a = c->h_fargs[k];
     fill_kargs(c, a, i_pcut_first + k, 0, 0, 1, nullptr, 0);
     a.in = cur.d; a.sv = c->sav.d;
     a.n_dev = &c->d_pd[k].n_use;
-    if (k == 0) {
-      kind = species_kernel_kind(c, a, cap_n, &ws);
-      if (ws) { threads = mcs_transport_ws_threads(); blocks = c->n_cu; }
-      else { threads = 256; blocks = c->n_cu * (c->P.state_fp32 ? ((c->f32_loop || c->f32_exact) ? 3 : c->f32_blocks_per_cu) : 2); }
-      const long long want = (cap_n + threads - 1) / threads;
-      if (want < blocks) blocks = (int)(want > 0 ? want : 1);
-    }
-    if (ws) { a.ws_pop_max = c->ws_pop_max > 0 ? c->ws_pop_max : threads + 160; a.ws_serve_min = c->ws_serve_min; }
     PopBuf t = cur; cur = spare; spare = t;
   }
+  const K1Plan k1 = k1_plan(c, cap_n, false);
+  const int blocks = persistent_grid(cap_n, k1.threads, (long long)c->n_cu * k1.per_cu);
   std::memset(c->h_pd, 0, sizeof(PcutDev) * (size_t)(npc + 1));
   c->h_pd[0].n_use = c->n;
   HIPCHK(hipMemcpyAsync(c->d_fargs, c->h_fargs, sizeof(KArgs) * (size_t)npc, hipMemcpyHostToDevice, c->stream));
@@ -938,8 +920,7 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   for (int k = 0; k < npc; ++k) {
     HIPCHK(hipMemsetAsync(c->d_lsave, 0, (size_t)cap_n, c->stream));
     HIPCHK(hipEventRecord(c->f_ev[2 * k], c->stream));
-    if (c->P.state_fp32) HIPCHK(mcs_launch_transport_f32(c->d_fargs + k, kind, blocks, 256, c->stream));
-    else HIPCHK(mcs_launch_transport(c->d_fargs + k, kind, blocks, threads, c->stream));
+    HIPCHK(mcs_launch_transport(c->d_fargs + k, k1.kernel, blocks, k1.threads, c->stream));
     HIPCHK(hipEventRecord(c->f_ev[2 * k + 1], c->stream));
     HIPCHK(mcs_launch_finalize_split_dev(c->d_lsave, cap_n, c->d_bcounts, c->d_boffs, c->d_counters + 2, c->d_src, c->d_pd + k, c->d_pd + k + 1,
                                          c->d_counters, (long long)n_target[k], c->d_counters + 4, c->sav.d, spare.d, split_blocks, c->stream));
@@ -950,7 +931,7 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   HIPCHK(hipMemcpyAsync(c->h_back, c->d_counters + 3, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (c->h_back[1] != 0) return fail("mcs_run_pcuts_fused: the kernel's n_saved counter and the count of l_save flags differ");
-  if (ws && c->h_back[0] != 0) return fail("mcs_run_pcuts_fused: a bounded wait of the wave-specialised kernel ran out (a launch is incomplete)");
+  if (is_ws(k1.kernel) && c->h_back[0] != 0) return fail("mcs_run_pcuts_fused: a bounded wait of the wave-specialised kernel ran out (a launch is incomplete)");
   double ms_sum = 0.0;
   for (int k = 0; k < npc; ++k) {
     n_use_out[k] = c->h_pd[k].n_use; n_saved_out[k] = c->h_pd[k].n_saved; i_mult_out[k] = c->h_pd[k].i_mult;
@@ -963,9 +944,21 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   c->n = c->h_pd[npc].n_use;
   c->n_run_last = -1; c->n_saved_last = 0;
   c->last_ms = ms_sum; c->tail_rounds_last = npc;
-  c->kernel_last = c->P.state_fp32 ? (c->f32_exact ? 9 : (c->f32_loop ? 4 : (kind == 2 ? 5 : 3))) : kind;
+  c->kernel_last = k1.kernel;
   return 0;
 }
+
+// What the pcut loop of mcs_run_pcuts_pipelined leaves to its caller, which drains the streams and commits the buffers on every exit.
+struct PipeRun {
+  PopBuf cur, nxt;             // the population of the current pcut and the target of its split: c->cur / c->spare, rotated
+  hipStream_t s1, s2;          // the main stream of the CURRENT pcut (c->stream, or the masked one when the pcut has side work); the side stream
+  bool masked;                 // s1 and s2 have complementary CU masks (MCS_PIPE_SIDE_CUS)
+  int n_done;                  // pcuts whose population size is in n_use_out
+  double ms_sum;               // kernel time of the main launches
+};
+static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_first, int npc, long long cap_n, const int64_t* n_target,
+                           int64_t long_draws, int64_t long_imult_max, int64_t* n_use_out, int64_t* n_saved_out, int64_t* i_mult_out,
+                           double* kernel_ms_out, int64_t* strag_out);
 
 // ---- A species' pcuts with the long histories of pcut p finishing BESIDE pcut p + 1 (DESIGN.md "Pipelined pcuts").
 // A launch waits for its longest histories -- 10^4 passes of single particles while the chip idles (40 % of an iteration at 10^6
@@ -988,7 +981,7 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
   if (i_pcut_first < 1 || i_pcut_last > c->tb.n_pcuts || i_pcut_last < i_pcut_first) return fail("mcs_run_pcuts_pipelined: pcut range");
   if (!n_target || !n_use_out || !n_saved_out || !i_mult_out) return fail("mcs_run_pcuts_pipelined: null argument");
   if (c->P.state_fp32) return fail("mcs_run_pcuts_pipelined: not for the fp32-state variant");
-  if (c->tail_budget > 0 || c->claim_max_first < 64 || c->blocks > 0) return fail("mcs_run_pcuts_pipelined: not with sliced launches or an explicit launch geometry");
+  if (c->tail_budget > 0 || c->blocks > 0) return fail("mcs_run_pcuts_pipelined: not with sliced launches or an explicit launch geometry");
   if (long_draws < 64 || long_draws > 2000000000LL) return fail("mcs_run_pcuts_pipelined: long_draws out of range (64 .. 2e9)");
   const int npc = i_pcut_last - i_pcut_first + 1;
   long long cap_n = c->n;
@@ -1028,34 +1021,45 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
       }
     }
   }
-  const int threads = 256;
-  const long long full = (long long)c->n_cu * 2;            // resident workgroups of the fp64 kernels
-  {   // a wave exports at most its 64 lanes, once: room for the main and the late launch of one pcut
-    const long long need_cap = 2 * full * threads;
-    if (need_cap > c->strag_cap) {
-      HIPCHK(hipStreamSynchronize(c->stream));
-      for (int b = 0; b < 2; ++b) { if (c->d_strag[b]) (void)hipFree(c->d_strag[b]); c->d_strag[b] = nullptr; }
-      c->strag_cap = need_cap;
-      for (int b = 0; b < 2; ++b) HIPCHK(hipMalloc((void**)&c->d_strag[b], (size_t)c->strag_cap * MCS_STRAG_WORDS * sizeof(double)));
-    }
+  // the sliced form of the species' kernel (PLAIN, LOSSY, PLAIN_ETF, general); a wave exports at most its 64 lanes, once: room for the
+  // main and the late launch of one pcut
+  const K1Plan k1 = k1_plan(c, 0, true);
+  if (ensure_strag(c, 2 * (long long)c->n_cu * k1.per_cu * k1.threads)) return 1;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const bool masked = c->pp_s1m && c->pp_s2m;
+  PipeRun r{c->cur, c->spare, c->stream, masked ? c->pp_s2m : c->pp_s2, masked, 0, 0.0};
+  int rc = pipelined_pcuts(c, r, k1, i_pcut_first, npc, cap_n, n_target, long_draws, long_imult_max, n_use_out, n_saved_out, i_mult_out,
+                           kernel_ms_out, strag_out);
+  // every exit of the loop, a failed one too: no stream may still write the population, the saved arrays or the tallies
+  for (hipStream_t st : {r.s2, r.s1, c->stream}) {
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess && rc == 0) rc = fail(std::string("mcs_run_pcuts_pipelined: hipStreamSynchronize: ") + hipGetErrorString(e));
   }
+  c->cur = r.cur; c->spare = r.nxt;
+  // (after a failure the population is half-written: it is not run or split again before the next mcs_init_pop* / mcs_pop_upload)
+  c->n = rc ? 0 : (r.n_done > 0 ? n_use_out[r.n_done - 1] : c->n);
+  c->n_run_last = -1; c->n_saved_last = 0;
+  c->last_ms = r.ms_sum;
+  c->kernel_last = k1.kernel;
+  return rc;
+}
+
+// the pcut loop of mcs_run_pcuts_pipelined: on failure it returns at once, its caller drains and commits
+static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_first, int npc, long long cap_n, const int64_t* n_target,
+                           int64_t long_draws, int64_t long_imult_max, int64_t* n_use_out, int64_t* n_saved_out, int64_t* i_mult_out,
+                           double* kernel_ms_out, int64_t* strag_out) {
   // counters: [0] work, [1] n_saved of the main launch | [2] main scan total | [3 + q] particles exported by pcut parity q |
   // [5] work, [6] n_saved of the resumed long histories | [7] work, [8] n_saved of the late launch | [9] late scan total
   unsigned long long* const pc = c->pp_dpc;
-  const bool masked = c->pp_s1m && c->pp_s2m;
-  hipStream_t s1 = c->stream;                              // the main stream of the CURRENT pcut: c->stream, or the masked one when the pcut has side work
-  hipStream_t const s2 = masked ? c->pp_s2m : c->pp_s2;    // the side stream
+  const bool masked = r.masked;
+  hipStream_t& s1 = r.s1;
+  hipStream_t const s2 = r.s2;
   hipStream_t const s_alone = masked ? c->stream : c->pp_s2;   // long histories the pcut waits for: the whole chip
-  HIPCHK(hipStreamSynchronize(c->stream));
-  int kind;
-  {
-    KArgs t; fill_kargs(c, t, i_pcut_first, 0, 0, 1, nullptr, 0);
-    int kk = species_kernel_kind(c, t, 0, nullptr);
-    if (kk == 7) kk = 1;
-    if (kk == 8) kk = 6;
-    kind = kk == 1 ? 11 : (kk == 2 ? 12 : (kk == 6 ? 13 : 10));      // the sliced form of the species' kernel: PLAIN, LOSSY, PLAIN_ETF, general
-  }
-  PopBuf cur = c->cur, nxt = c->spare;
+  const int side_max = 64;     // workgroups (of 2 per CU) the main launch leaves free for the side stream at most
+  const int threads = k1.threads;
+  const long long full = (long long)c->n_cu * k1.per_cu;
+  PopBuf& cur = r.cur;
+  PopBuf& nxt = r.nxt;
   PopBuf savb[2] = {c->sav, c->pp_sav2};
   uint8_t* lsv[2] = {c->d_lsave, c->pp_lsave2};
   long long nA = c->n, nL = 0;
@@ -1066,15 +1070,12 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
   bool side_pending = false;
   int side_blocks = 0;               // workgroups the side stream's launches of this pcut need resident beside the main launch
   long long n1_prev = 0, sofar_prev = 0;
-  double ms_sum = 0.0;
-  int n_done = 0;
   c->pp_waits_last = 0;
   c->tail_rounds_last = 0;
   const bool dbg_pipe = std::getenv("MCS_PIPE_DEBUG") != nullptr;
   for (int k = 0; k < npc; ++k) { n_use_out[k] = 0; n_saved_out[k] = 0; i_mult_out[k] = 1; if (kernel_ms_out) kernel_ms_out[k] = 0.0; if (strag_out) { strag_out[2 * k] = 0; strag_out[2 * k + 1] = 0; } }
   HIPCHK(hipMemsetAsync(pc, 0, 16 * sizeof(unsigned long long), s1));
   if (nA > 0) HIPCHK(hipMemsetAsync(lsv[0], 0, (size_t)nA, s1));
-  auto blocks_for = [&](long long n) { const long long want = (n + threads - 1) / threads; return (int)(want < full ? (want > 0 ? want : 1) : full); };
   // the launch of the exported particles of pcut `i_pcut` (parity q), to their end, on `st`
   auto launch_resume = [&](int i_pcut, int q, long long n_pop, long long n_x, hipStream_t st, bool alone) -> int {
     KArgs& a = c->pp_hargs[1];
@@ -1082,23 +1083,16 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
     a.in = cur.d; a.sv = savb[q].d; a.l_save = lsv[q];
     a.work_counter = pc + 5; a.n_saved = pc + 6; a.strag_count = pc + 3 + (q ^ 1); a.strag_out = c->d_strag[q ^ 1];
     a.strag_in = c->d_strag[q]; a.n_resume = n_x; a.fresh_lo = n_pop; a.long_draws = (unsigned int)Bk; a.budget_trips = 0;
-    // few particles per wave (profiles/r03_tau_vs_lanes.txt), on at most one wave per SIMD of the chip
-    // (alone on the chip -- the pcut waits for them -- one wave per SIMD; beside a main launch every wave they hold is taken from it:
-    // 16 particles per wave cost 12 % on the longest history and 1 / 16 of the slots)
-    const long long waves1 = alone ? (long long)c->n_cu * (threads / 64) : (c->pp_side_waves > 0 ? c->pp_side_waves : (n_x + 15) / 16);
-    long long cm = (n_x + waves1 - 1) / waves1;
-    if (cm > 16) cm = 64;
-    a.claim_max = (int)cm;
-    if (cm < 64) { a.defer_k = 1; a.wait_full = 0; a.tail_merge = 0; }
-    const long long per_block = (long long)(threads / 64) * cm;
-    const long long nb = (n_x + per_block - 1) / per_block;
+    // few particles per wave (sparse_claim), on at most one wave per SIMD of the chip (alone on the chip -- the pcut waits for them --
+    // one wave per SIMD; beside a main launch every wave they hold is taken from it: 16 particles per wave cost 12 % on the longest
+    // history and 1 / 16 of the slots)
+    const int blocks = sparse_claim(c, a, n_x, alone ? (long long)c->n_cu * (threads / 64) : (n_x + 15) / 16, threads, full);
     HIPCHK(hipMemcpyAsync(c->pp_dargs + 1, &a, sizeof(KArgs), hipMemcpyHostToDevice, st));
-    HIPCHK(mcs_launch_transport(c->pp_dargs + 1, kind, (int)(nb < full ? nb : full), threads, st));
-    if (!alone) side_blocks += (int)(nb < full ? nb : full);
+    HIPCHK(mcs_launch_transport(c->pp_dargs + 1, k1.kernel, blocks, threads, st));
+    if (!alone) side_blocks += blocks;
     ++c->tail_rounds_last;
     return 0;
   };
-  int rc = 0;                        // (a failed cross-check ends the loop: the streams are drained below before the error is returned)
   for (int k = 0; k < npc; ++k) {
     const int i_pcut = i_pcut_first + k, q = k & 1;
     // ---- the main launch: particles 0 .. nA-1 of the population
@@ -1112,10 +1106,10 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
       HIPCHK(hipEventRecord(c->ev0, s1));
       // (the main launch is persistent and fills every slot of the chip: it leaves room for the side stream's workgroups, which would
       // otherwise wait for its workgroups to leave -- and run after it instead of beside it)
-      int blocks_a = blocks_for(nA);
+      int blocks_a = persistent_grid(nA, threads, full);
       if (masked) { if (s1 == c->pp_s1m && blocks_a > 2 * (c->n_cu - c->pp_side_cus)) blocks_a = 2 * (c->n_cu - c->pp_side_cus); }
       else if (side_blocks > 0 && blocks_a > full - side_blocks) blocks_a = (int)(full - side_blocks);
-      HIPCHK(mcs_launch_transport(c->pp_dargs, kind, blocks_a, threads, s1));
+      HIPCHK(mcs_launch_transport(c->pp_dargs, k1.kernel, blocks_a, threads, s1));
       HIPCHK(hipEventRecord(c->ev1, s1));
       ++c->tail_rounds_last;
     }
@@ -1133,7 +1127,7 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
     HIPCHK(hipStreamSynchronize(s1));
     const auto tj2 = std::chrono::steady_clock::now();
     float ms_main = 0.f;
-    if (nA > 0) { HIPCHK(hipEventElapsedTime(&ms_main, c->ev0, c->ev1)); if (kernel_ms_out) kernel_ms_out[k] = ms_main; ms_sum += ms_main; }
+    if (nA > 0) { HIPCHK(hipEventElapsedTime(&ms_main, c->ev0, c->ev1)); if (kernel_ms_out) kernel_ms_out[k] = ms_main; r.ms_sum += ms_main; }
     const unsigned long long* h = c->pp_hpc;
     double dbg_wait_ms = 0.0;
     if (side_pending) {
@@ -1145,21 +1139,21 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
         static char msg[256];
         std::snprintf(msg, sizeof msg, "mcs_run_pcuts_pipelined: pcut %d: the kernels' n_saved counters (%lld + %llu resumed) and the count of status bytes (%lld + %lld long) differ",
                       i_pcut - 1, sofar_prev, (unsigned long long)h[6], n1_prev, n5_prev);
-        rc = fail(msg); side_pending = false; break;
+        return fail(msg);
       }
     }
     side_pending = false;
     n_use_out[k] = nA + nL;
-    n_done = k + 1;
+    r.n_done = k + 1;
     const long long n1 = (long long)h[2], n_T = (long long)h[3 + q];
     long long sofar = (long long)h[1] + (long long)h[8];        // saved by the main and the late launch: not long, or long and already ended
     if (strag_out) strag_out[2 * k] = n_T;
-    if (n_T > c->strag_cap) { rc = fail("mcs_run_pcuts_pipelined: export buffer overrun"); break; }
+    if (n_T > c->strag_cap) return fail("mcs_run_pcuts_pipelined: export buffer overrun");
     if (sofar < n1) {
       static char msg[256];
       std::snprintf(msg, sizeof msg, "mcs_run_pcuts_pipelined: pcut %d: the kernels' n_saved counters (%llu main + %llu late) are below the count of status bytes (%lld)",
                     i_pcut, (unsigned long long)h[1], (unsigned long long)h[8], n1);
-      rc = fail(msg); break;
+      return fail(msg);
     }
     const long long target = (long long)n_target[k];
     const bool last = k == npc - 1;
@@ -1168,7 +1162,7 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
     const long long im_hi = target / (sofar + n_T) > 1 ? target / (sofar + n_T) : 1;
     const long long im_lo = sofar > 0 ? (target / sofar > 1 ? target / sofar : 1) : -1;
     // (more long histories than the side stream's CUs hold at 16 per wave, twice over: beside the main launch they would outlast it)
-    const long long side_cap = masked ? (long long)c->pp_side_cus * 8 * 16 * 2 : (long long)c->pp_side_max * 4 * 16 * 2;
+    const long long side_cap = masked ? (long long)c->pp_side_cus * 8 * 16 * 2 : (long long)side_max * 4 * 16 * 2;
     if ((last || im_lo != im_hi || n_T > side_cap) && n_T > 0) {
       // i_mult depends on how many of the long histories end saved (or this is the last pcut, or they are too many): they finish first
       HIPCHK(hipMemsetAsync(pc + 5, 0, 2 * sizeof(unsigned long long), s_alone));
@@ -1197,7 +1191,7 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
     const long long n5_max = sofar - n1 + n_open;               // long particles that are saved, or still running
     const long long nL_max = n5_max * i_mult;
     // ((sofar + n_open) * i_mult <= max(n_target, sofar + n_open) <= cap_n: every buffer holds it)
-    if (nA_next + nL_max > cap_n) { rc = fail("mcs_run_pcuts_pipelined: the next population exceeds the buffers"); break; }
+    if (nA_next + nL_max > cap_n) return fail("mcs_run_pcuts_pipelined: the next population exceeds the buffers");
     // (the long histories go first: their few waves must be resident before the next main launch fills every slot of the chip --
     // queued behind it they would start when its workgroups leave, i.e. run after it instead of beside it.  Their counters are the side
     // stream's own words; everything else is cleared on the main stream, and the late split / late launch wait for that.)
@@ -1229,9 +1223,10 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
       a.work_counter = pc + 7; a.n_saved = pc + 8; a.strag_count = pc + 3 + (q ^ 1); a.strag_out = c->d_strag[q ^ 1];
       a.long_draws = (unsigned int)B_next;
       HIPCHK(hipMemcpyAsync(c->pp_dargs + 2, &a, sizeof(KArgs), hipMemcpyHostToDevice, s2));
-      HIPCHK(mcs_launch_transport(c->pp_dargs + 2, kind, blocks_for(nL_max), threads, s2));
-      side_blocks += blocks_for(nL_max);
-      if (side_blocks > c->pp_side_max) side_blocks = c->pp_side_max;
+      const int blocks_l = persistent_grid(nL_max, threads, full);
+      HIPCHK(mcs_launch_transport(c->pp_dargs + 2, k1.kernel, blocks_l, threads, s2));
+      side_blocks += blocks_l;
+      if (side_blocks > side_max) side_blocks = side_max;
       ++c->tail_rounds_last;
       side_pending = true;
       nL = nL_max;
@@ -1242,15 +1237,7 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
     Bk = B_next;
     PopBuf t = cur; cur = nxt; nxt = t;
   }
-  HIPCHK(hipStreamSynchronize(s2));      // (idle already on every exit but a failed cross-check)
-  HIPCHK(hipStreamSynchronize(s1));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->cur = cur; c->spare = nxt;
-  c->n = n_done > 0 ? n_use_out[n_done - 1] : c->n;
-  c->n_run_last = -1; c->n_saved_last = 0;
-  c->last_ms = ms_sum;
-  c->kernel_last = kind;
-  return rc;
+  return 0;
 }
 
 int mcs_new_pcut(mcs_ctx* c, int64_t i_mult, int64_t* n_new_out) {

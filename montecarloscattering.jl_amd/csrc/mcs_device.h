@@ -92,6 +92,16 @@ struct KArgs {
 #define MCS_TALLY_REPLICAS 16
 #endif
 
+// The K1 transport kernels (mcs_transport.hip and its .inc files), numbered as mcs_last_kernel reports them (include/mcs.h):
+// the id mcs_launch_transport takes.  PLAIN / LOSSY / PLAIN_ETF are the specialisations of transport_body, WS its wave-specialised
+// form (mcs_transport_ws.inc), F32 the fp32-state kernels, *_SLICED the forms for sliced launches.
+enum K1Kernel {
+  K1_GENERAL = 0, K1_PLAIN = 1, K1_LOSSY = 2, K1_F32 = 3, K1_F32_LOOP = 4, K1_F32_LOSSY = 5, K1_PLAIN_ETF = 6,
+  K1_WS = 7, K1_WS_ETF = 8, K1_F32_LOOP_EXACT = 9,
+  K1_SLICED = 10, K1_PLAIN_SLICED = 11, K1_LOSSY_SLICED = 12, K1_PLAIN_ETF_SLICED = 13,
+  K1_COUNT
+};
+
 // One pcut of a fused species loop (mcs_run_pcuts_fused): what the host would have read back after every pcut
 struct PcutDev { long long n_use, n_saved, i_mult, n_new; };
 

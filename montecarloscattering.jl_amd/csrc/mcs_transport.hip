@@ -2467,21 +2467,16 @@ extern "C" int mcs_prof_read(unsigned long long* out, int reset) {
 #include "mcs_transport_ws.inc"
 #include "mcs_transport_f32.inc"
 
-extern "C" size_t mcs_transport_smem_bytes(int n_grid, int n_tcuts) { (void)n_grid; (void)n_tcuts; return 0; }   // static LDS
 extern "C" int mcs_transport_max_entries(void) { return MCS_MAXNE; }
 
-// `a_dev`: device copy of the launch constants (written by the caller on `st`).
-// `kind`: 0 the general kernel; 1 / 2 / 6: the host has checked the conditions of the PLAIN / LOSSY / PLAIN_ETF specialisation (see transport_body).
-extern "C" hipError_t mcs_launch_transport(const KArgs* a_dev, int kind, int blocks, int threads, hipStream_t st) {
-  if (kind == 1) hipLaunchKernelGGL(mcs_k_transport_plain, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 2) hipLaunchKernelGGL(mcs_k_transport_lossy, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 6) hipLaunchKernelGGL(mcs_k_transport_plain_etf, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 10) hipLaunchKernelGGL(mcs_k_transport_sliced, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 11) hipLaunchKernelGGL(mcs_k_transport_plain_sliced, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 12) hipLaunchKernelGGL(mcs_k_transport_lossy_sliced, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 13) hipLaunchKernelGGL(mcs_k_transport_plain_etf_sliced, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 7) hipLaunchKernelGGL(mcs_k_transport_ws, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 8) hipLaunchKernelGGL(mcs_k_transport_ws_etf, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else hipLaunchKernelGGL(mcs_k_transport, dim3(blocks), dim3(threads), 0, st, a_dev);
+// `a_dev`: device copy of the launch constants (written by the caller on `st`).  `kernel`: a K1Kernel (mcs_device.h); the host has
+// checked the conditions of the specialisation it names (see transport_body).
+extern "C" hipError_t mcs_launch_transport(const KArgs* a_dev, int kernel, int blocks, int threads, hipStream_t st) {
+  static void (*const k1[K1_COUNT])(const KArgs*) = {
+      mcs_k_transport, mcs_k_transport_plain, mcs_k_transport_lossy, mcs_k_transport_f32, mcs_k_transport_f32_loop,
+      mcs_k_transport_f32_lossy, mcs_k_transport_plain_etf, mcs_k_transport_ws, mcs_k_transport_ws_etf, mcs_k_transport_f32_loop_exact,
+      mcs_k_transport_sliced, mcs_k_transport_plain_sliced, mcs_k_transport_lossy_sliced, mcs_k_transport_plain_etf_sliced};
+  if (kernel < 0 || kernel >= K1_COUNT) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k1[kernel], dim3(blocks), dim3(threads), 0, st, a_dev);
   return hipGetLastError();
 }

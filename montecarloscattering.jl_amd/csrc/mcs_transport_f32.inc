@@ -467,13 +467,3 @@ extern "C" __global__ void __launch_bounds__(256) mcs_k_transport_f32_loop(const
 extern "C" __global__ void __launch_bounds__(256) mcs_k_transport_f32_loop_exact(const KArgs* __restrict__ ka) { f32_loop_body<true>(ka); }
 
 #include "mcs_transport_f32k.inc"
-
-// `kind` 1: the plain per-lane loop above (the reference semantics of the fp32 variant; tests compare the organised kernel with it);
-// 0 / 2: the organised kernel / its specialisation for electrons with radiative losses; 3: the plain loop with the exact primitives
-extern "C" hipError_t mcs_launch_transport_f32(const KArgs* a_dev, int kind, int blocks, int threads, hipStream_t st) {
-  if (kind == 1) hipLaunchKernelGGL(mcs_k_transport_f32_loop, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 3) hipLaunchKernelGGL(mcs_k_transport_f32_loop_exact, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else if (kind == 2) hipLaunchKernelGGL(mcs_k_transport_f32_lossy, dim3(blocks), dim3(threads), 0, st, a_dev);
-  else hipLaunchKernelGGL(mcs_k_transport_f32, dim3(blocks), dim3(threads), 0, st, a_dev);
-  return hipGetLastError();
-}

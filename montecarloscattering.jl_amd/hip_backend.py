@@ -105,7 +105,7 @@ class HipBackend:
 
     def last_kernel(self) -> int:
         """0 general, 1 plain, 2 lossy, 3 fp32, 4 fp32 plain loop, 5 fp32 lossy, 6 plain with energy transfer, 7 / 8 wave-specialised, 9 fp32 exact loop,
-        10 general sliced, 11 / 12 / 13 the sliced forms of 1 / 2 / 6 (mcs_last_kernel)"""
+        10 general sliced, 11 / 12 / 13 the sliced forms of 1 / 2 / 6 (mcs_last_kernel; the K1Kernel enum of csrc/mcs_device.h)"""
         return int(self.lib.mcs_last_kernel(self.h))
 
     # -- per iteration / species
