@@ -10,11 +10,12 @@ EVERY pcut the iteration reaches -- the late ones included, where the whole popu
 replicas of one or two saved particles piling onto single histogram bins.
 """
 import os
+import time
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, mcs, make_problem, oracle_backend, hip_backend, start_species, bits
+from conftest import ROOT, mcs, make_problem, oracle_backend, hip_backend, start_species, bits, assert_pop_equal, assert_tallies_close
 
 pytestmark = pytest.mark.gpu
 TALLY_RTOL = 1e-11
@@ -33,29 +34,26 @@ LONG_SUMS = ("pxx_flux", "pxz_flux", "energy_flux", "esc_flux", "px_esc_feb", "e
              "weight_coupled", "spectra_coupled_val", "scalars")
 
 
-def _load_reducer():
+def _fixture_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("make_golden_full", os.path.join(ROOT, "tests", "golden", "make_golden_full.py"))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
-    return m.reduce_tallies
+    return m
 
 
-def test_config1_full_size_vs_oracle_fixture():
-    fix = np.load(os.path.join(ROOT, "tests", "golden", "full_1e6.npz"))
-    N = 1_000_000
-    prob = make_problem(N)
-    hb = hip_backend(prob)
-    res = mcs.driver.run(prob, hb, None, n_itrs=1)
-    hb.destroy()
-    got = _load_reducer()(mcs.capi.Layout(prob.params), res.tallies_f64, res.tallies_i64, res.stats)
-    assert np.array_equal(got["stats"], fix["stats"])                 # n_pts_use, n_saved, i_mult of all pcuts
-    assert np.array_equal(got["tallies_i64"], fix["tallies_i64"])     # crossings per zone, exits by reason, steps, draws
-    assert int(fix["stats"][:, 2].min()) == 0 and len(fix["stats"]) >= 30
-    worst = ("", 0.0)
+def _load_reducer():
+    return _fixture_module().reduce_tallies
+
+
+def _binned_vs_fixture(got, fix, skip=()):
+    """Every binned array of a reduced run against the fixture's: *_idx equal, the rest within TALLY_RTOL of the array's
+    maximum (LONG_SUM_RTOL for LONG_SUMS).  Returns (worst array, its error) and the number of arrays compared."""
+    worst, n = ("", 0.0), 0
     for k in fix.files:
-        if k in ("stats", "tallies_i64", "meta"):
+        if k in ("stats", "tallies_i64", "meta") or k in skip:
             continue
+        n += 1
         a, b = got[k], fix[k]
         assert a.shape == b.shape, k
         if k.endswith("_idx"):
@@ -70,7 +68,22 @@ def test_config1_full_size_vs_oracle_fixture():
             worst = (k, err)
         tol = LONG_SUM_RTOL if k in LONG_SUMS else TALLY_RTOL
         assert err <= tol, f"{k}: max|gpu - oracle| / max|oracle| = {err:.3e}"
-    print(f"config[1] at 1e6: {len(fix.files) - 3} binned arrays within {TALLY_RTOL}; worst {worst[0]} {worst[1]:.2e}; {fix['meta']}")
+    return worst, n
+
+
+def test_config1_full_size_vs_oracle_fixture():
+    fix = np.load(os.path.join(ROOT, "tests", "golden", "full_1e6.npz"))
+    N = 1_000_000
+    prob = make_problem(N)
+    hb = hip_backend(prob)
+    res = mcs.driver.run(prob, hb, None, n_itrs=1)
+    hb.destroy()
+    got = _load_reducer()(mcs.capi.Layout(prob.params), res.tallies_f64, res.tallies_i64, res.stats)
+    assert np.array_equal(got["stats"], fix["stats"])                 # n_pts_use, n_saved, i_mult of all pcuts
+    assert np.array_equal(got["tallies_i64"], fix["tallies_i64"])     # crossings per zone, exits by reason, steps, draws
+    assert int(fix["stats"][:, 2].min()) == 0 and len(fix["stats"]) >= 30
+    worst, n = _binned_vs_fixture(got, fix)
+    print(f"config[1] at 1e6: {n} binned arrays within {TALLY_RTOL}; worst {worst[0]} {worst[1]:.2e}; {fix['meta']}")
 
 
 def test_long_sum_tolerance_is_the_gpu_add_order_noise(monkeypatch):
@@ -114,62 +127,132 @@ def test_long_sum_tolerance_is_the_gpu_add_order_noise(monkeypatch):
     print(f"long sums: GPU vs GPU (another add order) {worst_gg:.2e}, GPU vs oracle fixture {worst_go:.2e}, bound {LONG_SUM_RTOL}")
 
 
-def _property_run(N, n_prefix=4096, prefix_pcuts=5, prob=None, i_iter=1):
+def _begin(be, prob, i_iter, i_ion, pop=None):
+    """Start species i_ion of iteration i_iter as driver.run does: the first species opens the iteration (begin_iteration
+    clears the pools), a later one keeps what the earlier species left.  pop: a caller's population instead of the injection."""
+    if i_ion == 1:
+        start_species(be, prob, i_iter)
+    else:
+        cfg = prob.cfg
+        sp = cfg.species[i_ion - 1]
+        inj = mcs.inputs.init_pop_host(prob, i_ion)
+        pmax = mcs.inputs.get_pmax_cutoff(prob.Emax_keV, prob.Emax_per_aa_keV, prob.pmax, sp.aa)
+        ewf = 1.0 / cfg.species[-1].density if cfg.species[-1].density else float("inf")
+        be.begin_species(i_iter, i_ion, sp.aa, abs(sp.zz), pmax, sp.density, ewf)
+        be.set_fluxes(inj.pxx_flux, inj.pxz_flux, inj.energy_flux)
+        be.init_pop(inj, 0, inj.n_pts_use, inj.n_pts_use)
+    if pop is not None:
+        be.set_population(pop)
+
+
+def _property_run(N, n_prefix=4096, prefix_pcuts=5, prob=None, i_iter=1, i_ion=1, pop=None, hb=None, ob=None, twin=None,
+                  kernel=None, twin_kernel=None, min_pcuts=30):
     """One species through every pcut it reaches.  Per pcut: (i) every particle ends in exactly one way and the
-    saved flags are the reason-0 particles; (ii) the counters' exits equal the particles that ended; (iii) the first
-    n_prefix particles equal the oracle's bit for bit while the prefix stays aligned (pcuts 1-4 save everybody);
-    (iv) the split population is i_mult copies of each saved particle, in order, with weight / i_mult.  At the end:
-    weight is conserved through all splits, the upstream-escape tallies carry exactly the weight of the particles
-    that escaped upstream (LDS-staged and wave-reduced tallies at full size), no zone search failed."""
+    saved flags are the reason-0 particles; (ii) the counters' exits equal the particles that ended, the step counters
+    the finals; (iii) the first n_prefix particles equal the oracle's bit for bit while the prefix stays aligned (pcuts 1-4
+    save everybody); (iv) the split population is i_mult copies of each saved particle, in order, with weight / i_mult;
+    (v) `kernel`: the K1 kernel that ran (mcs_last_kernel).  At the end: weight is conserved through all splits, the
+    upstream-escape tallies of this species carry exactly the weight of the particles that escaped upstream (LDS-staged and
+    wave-reduced tallies at full size), no zone search failed.
+
+    Species i_ion of a multi-species problem: the caller passes the contexts (hb, and ob for the prefix) and runs the species
+    in order; the tallies are cumulative over the iteration, so the end checks take this species' deltas.  Before a later
+    species starts the oracle context gets the GPU's whole tally buffer: the electrons read energy_recv_pool, which
+    begin_species copies from the ions' energy_transfer_pool -- an fp64 atomic sum whose last bits depend on the order of the
+    adds --, and with both sides reading the same bits the electron prefix is compared bit for bit, not by luck.
+    pop: a caller's population (set_population) instead of the injection.  n_prefix = 0: no oracle.
+    twin: a second context (another kernel of the same statements, chosen by an environment knob at its creation) run in
+    lockstep: finals, saved arrays, l_save and the int64 tallies equal after every pcut, the binned tallies to TALLY_RTOL at
+    the species end; its energy_transfer_pool is pinned to hb's as the oracle's is.
+    state_fp32: the kernels hold the weight as a float (`p.w = (float)in.weight[k]`), so the weight they end, save and tally
+    is the population's rounded to fp32; the sums take those weights, and what the rounding removes at each pcut's load is
+    counted (w_round) -- the saved weights and the split must still account for every bit of the rest.
+    Returns the species' record: pcuts reached, exits, population, i_mult per split, exit reasons, int64 tally deltas."""
     prob = make_problem(N) if prob is None else prob      # (a caller's problem: e.g. one whose profile an iteration has updated)
-    hb = hip_backend(prob)
-    start_species(hb, prob, i_iter)
+    fp32 = bool(prob.params.state_fp32)
+    caller_pop = pop
+    own = hb is None
+    if own:
+        hb = hip_backend(prob)
+        ob = oracle_backend(prob, nthreads=8) if n_prefix > 0 else None
+    if ob is not None and i_ion > 1:
+        ob.write_tallies(*hb.read_tallies())
+    if twin is not None and i_ion > 1:
+        twin.write_tally("energy_transfer_pool", hb.layout.view(hb.read_tallies()[0], "energy_transfer_pool"))
+    _begin(hb, prob, i_iter, i_ion, caller_pop)
     ng, IC = prob.n_grid, mcs.capi.IC
+    L = hb.layout
     pop = hb.get_population()
+    n_in = pop.n
     w_in = float(pop.weight.sum())
-    ob = oracle_backend(prob, nthreads=8)
-    start_species(ob, prob, i_iter)
-    ob.set_population(pop.slice(0, n_prefix))
-    w_out = w_esc_up = 0.0
+    if ob is not None:
+        _begin(ob, prob, i_iter, i_ion)
+        ob.set_population(pop.slice(0, n_prefix))
+    if twin is not None:
+        _begin(twin, prob, i_iter, i_ion, caller_pop)
+    w_out = w_esc_up = w_round = 0.0
     n_done = n_up = 0
     reached = 0
     n_checked = []          # particles compared with the oracle in each of the first pcuts
-    I_prev = hb.read_tallies()[1]
+    mults = []
+    reasons = np.zeros(5, dtype=np.int64)
+    T0, I0 = hb.read_tallies()
+    I_prev = I0
     for ip in range(1, len(prob.pcuts) + 1):
         n_use = pop.n
         ns = hb.run_pcut(ip, 0)
         reached = ip
+        if kernel is not None:
+            assert hb.last_kernel() == kernel, f"ion {i_ion} pcut {ip}: K1 kernel {hb.last_kernel()}, expected {kernel}"
         f = hb.finals()
         saved, l_save = hb.get_saved()
         assert int(l_save.sum()) == ns and np.array_equal(f["reason"] == 0, l_save == 1), f"pcut {ip}"
         assert f["reason"].min() >= 0 and f["reason"].max() <= 4
+        reasons += np.bincount(f["reason"], minlength=5)
+        wk = pop.weight.astype(np.float32).astype(np.float64) if fp32 else pop.weight      # the weights the kernel held
+        w_round += float(pop.weight.sum()) - float(wk.sum())
+        assert np.array_equal(bits(saved.weight[l_save == 1]), bits(wk[l_save == 1])), f"pcut {ip}: saved weights"
         ended = f["reason"] != 0
-        w_out += float(pop.weight[ended].sum())
+        w_out += float(wk[ended].sum())
         up = f["reason"] == 2
-        w_esc_up += float(pop.weight[up].sum()); n_up += int(up.sum())
+        w_esc_up += float(wk[up].sum()); n_up += int(up.sum())
         n_done += int(ended.sum())
-        I = hb.read_tallies()[1]
+        I = hb.read_counters()
         d = I - I_prev; I_prev = I
         assert sum(int(d[ng + IC[f"REASON{r}"]]) for r in range(1, 5)) == int(ended.sum()), f"pcut {ip}"
         assert int(d[ng + IC["REASON0"]]) == ns and int(ended.sum()) + ns == n_use
         assert int(d[ng + IC["STEPS_HELIX"]]) == int(np.minimum(f["helix"], 10000).astype(np.int64).sum())
         assert int(d[ng + IC["STEPS_RETRO"]]) == int(f["retro"].astype(np.int64).sum())
+        if twin is not None:
+            assert twin.run_pcut(ip, 0) == ns, f"ion {i_ion} pcut {ip}: n_saved of the twin"
+            if twin_kernel is not None:
+                assert twin.last_kernel() == twin_kernel, f"ion {i_ion} pcut {ip}: twin's K1 kernel {twin.last_kernel()}, expected {twin_kernel}"
+            ft = twin.finals()
+            for k in f:
+                assert np.array_equal(bits(f[k]), bits(ft[k])), f"ion {i_ion} pcut {ip}: final {k} differs for {(f[k] != ft[k]).sum()} particles"
+            st, lt = twin.get_saved()
+            assert np.array_equal(l_save, lt), f"ion {i_ion} pcut {ip}: l_save"
+            assert_pop_equal(saved, st, f"ion {i_ion} pcut {ip}: saved arrays")
+            assert np.array_equal(twin.read_counters(), I), f"ion {i_ion} pcut {ip}: int64 tallies"
         nso = 0
         if ip <= prefix_pcuts and n_prefix > 0:
             nso = ob.run_pcut(ip, 0)
             fo = ob.finals()
             for k in fo:
-                assert np.array_equal(bits(f[k][:n_prefix]), bits(fo[k])), f"pcut {ip}: prefix {k}"
+                assert np.array_equal(bits(f[k][:n_prefix]), bits(fo[k])), f"ion {i_ion} pcut {ip}: prefix {k}"
             n_checked.append(n_prefix)
         if ns == 0:
             break
         im = max(N // ns, 1)
+        mults.append(im)
         if ip < prefix_pcuts and n_prefix > 0:
             # the children of the prefix's saved particles are the first nso * im particles of the next population, with the
             # same global indices (the split keeps the order): the oracle follows with ITS split of the prefix
             n_prefix = ob.new_pcut(im) if nso > 0 else 0
             assert n_prefix == nso * im
         assert hb.new_pcut(im) == ns * im
+        if twin is not None:
+            assert twin.new_pcut(im) == ns * im
         pop = hb.get_population()
         src = np.flatnonzero(l_save)
         o = np.unique(np.concatenate([np.arange(0, pop.n, 7), np.arange(max(pop.n - 1000, 0), pop.n)]))   # a sample of the new indices
@@ -179,30 +262,42 @@ def _property_run(N, n_prefix=4096, prefix_pcuts=5, prob=None, i_iter=1):
             if fld == "weight":
                 want = want / float(im)
             assert np.array_equal(bits(getattr(pop, fld)[o]), bits(want)), f"pcut {ip}: split field {fld} (i_mult {im}, {ns} parents)"
-    assert reached >= 30, "the iteration should run into the late pcuts"
-    assert len(n_checked) >= 3 and min(n_checked[:3]) >= 256, n_checked
+    assert reached >= min_pcuts, f"ion {i_ion}: {reached} pcuts reached, expected at least {min_pcuts}"
+    if n_checked:
+        assert len(n_checked) >= min(3, reached) and min(n_checked[:3]) >= 256, n_checked
     w_left = float(pop.weight.sum()) if ns else 0.0
-    assert abs(w_out + w_left - w_in) < 1e-9 * w_in
+    assert abs(w_out + w_left + w_round - w_in) < 1e-9 * w_in
     T, I = hb.read_tallies()
-    L = mcs.capi.Layout(prob.params)
+    dI = I - I0
     assert int(I[ng + IC["ZONE_FAIL"]]) == 0 and int(I[ng + IC["RETRO_CAP"]]) == 0
-    assert sum(int(I[ng + IC[f"REASON{r}"]]) for r in range(1, 5)) == n_done
-    assert int(I[ng + IC["REASON2"]]) == n_up
-    # reason-2 weight reaches esc_flux (LDS scalar staging) and esc_num_eff (LDS per-bin staging) exactly once
-    assert abs(float(L.view(T, "esc_flux")[0]) - w_esc_up) <= 1e-10 * max(w_esc_up, 1e-300)
-    assert abs(float(L.view(T, "esc_num_eff").sum()) - w_esc_up) <= 1e-10 * max(w_esc_up, 1e-300)
-    hb.destroy(); ob.destroy()
-    return reached, n_done
+    assert sum(int(dI[ng + IC[f"REASON{r}"]]) for r in range(1, 5)) == n_done
+    assert int(dI[ng + IC["REASON2"]]) == n_up
+    # reason-2 weight reaches esc_flux (LDS scalar staging) and esc_num_eff (LDS per-bin staging) exactly once, in this species' row
+    ion = i_ion - 1
+    d_flux = L.view(T, "esc_flux") - L.view(T0, "esc_flux")
+    d_num = L.view(T, "esc_num_eff") - L.view(T0, "esc_num_eff")
+    assert abs(float(d_flux[ion]) - w_esc_up) <= 1e-10 * max(w_esc_up, 1e-300)
+    assert abs(float(d_num[ion].sum()) - w_esc_up) <= 1e-10 * max(w_esc_up, 1e-300)
+    assert not np.any(np.delete(d_flux, ion)) and not np.any(np.delete(d_num, ion, axis=0)), f"ion {i_ion}: escape tallied in another species' row"
+    if twin is not None:
+        Tt, It = twin.read_tallies()
+        assert np.array_equal(It, I), f"ion {i_ion}: int64 tallies of the twin"
+        assert_tallies_close(L, Tt, T, TALLY_RTOL)
+    if own:
+        hb.destroy()
+        if ob is not None:
+            ob.destroy()
+    return dict(reached=reached, n_done=n_done, n_in=n_in, i_mult=mults, reasons=reasons, dI=dI)
 
 
 def test_config1_properties_every_pcut_1e6():
-    reached, n_done = _property_run(1_000_000)
-    print(f"1e6 protons: {reached} pcuts reached, {n_done} exits")
+    r = _property_run(1_000_000)
+    print(f"1e6 protons: {r['reached']} pcuts reached, {r['n_done']} exits")
 
 
 def test_config2_population_properties_every_pcut_1e7():
-    reached, n_done = _property_run(10_000_000)
-    print(f"1e7 protons: {reached} pcuts reached, {n_done} exits")
+    r = _property_run(10_000_000)
+    print(f"1e7 protons: {r['reached']} pcuts reached, {r['n_done']} exits")
 
 
 def test_config3_per_gpu_size_properties_5e7():
@@ -210,8 +305,8 @@ def test_config3_per_gpu_size_properties_5e7():
     per-pcut properties (every particle ends once, counters equal exits, splits are i_mult copies in order, weight conserved,
     the first 4096 particles equal the oracle's bit for bit) with 10 GB of population buffers resident.  The multi-GPU run
     itself cannot be tested on a one-GPU box; what a rank of it computes is this."""
-    reached, n_done = _property_run(50_000_000)
-    print(f"5e7 protons: {reached} pcuts reached, {n_done} exits")
+    r = _property_run(50_000_000)
+    print(f"5e7 protons: {r['reached']} pcuts reached, {r['n_done']} exits")
 
 
 def test_config2_1e7_second_iteration_on_the_updated_profile():
@@ -241,6 +336,191 @@ def test_config2_1e7_second_iteration_on_the_updated_profile():
     st = [(s.n_pts_use, s.n_saved, s.i_mult) for s in res.stats]
     assert all(b[0] == a[1] * a[2] for a, b in zip(st, st[1:])) and len(st) >= 30      # every population is the split of the previous one
     assert sum(int(I[ng + IC[f"REASON{r}"]]) for r in range(1, 5)) == sum(a[0] - a[1] for a in st)
-    reached, n_done = _property_run(N, prob=prob, i_iter=2)
+    r = _property_run(N, prob=prob, i_iter=2)
     print(f"config[2], 1e7 protons: iteration 1 {res.steps_helix + res.steps_retro} steps, profile updated "
-          f"(u_x at shock-3: {prob.ux[P.i_shock - 3] / P.u0:.4f} u0); iteration 2 on it: {reached} pcuts, {n_done} exits")
+          f"(u_x at shock-3: {prob.ux[P.i_shock - 3] / P.u0:.4f} u0); iteration 2 on it: {r['reached']} pcuts, {r['n_done']} exits")
+
+
+# ---- BASELINE config[4], the species mix of `bench.py --mixed` (protons + He + electrons, radiative losses, ion -> electron energy
+# transfer), at the bench's size: 10^6 particles per species.  K1 kernel per species (mcs_last_kernel, the K1Kernel enum): the ions
+# run PLAIN with the energy-transfer flag (6; its wave-specialised form 8), the electrons the lossy kernel (2); with state_fp32 the
+# organised fp32 kernels (3 for ions, 5 for electrons) and, under MCS_F32_LOOP=1, the plain per-lane loop (4) for every species.
+MIX_KERNELS = {False: (6, 6, 2), True: (3, 3, 5)}
+
+
+def _mixed_problem(N, **kw):
+    return _fixture_module().mixed_problem(N, **kw)
+
+
+def _check_transfer_pool(prob, hb, i_ion):
+    """After an ion species: the energy it handed the electrons is finite, >= 0, only in zones with eps_target > 0 and somewhere."""
+    pool = hb.layout.view(hb.read_tallies()[0], "energy_transfer_pool")
+    eps = np.asarray(prob.eps_target)
+    assert np.all(np.isfinite(pool)) and pool.min() >= 0.0, f"ion {i_ion}: energy_transfer_pool {pool}"
+    assert not np.any(pool[eps <= 0]), f"ion {i_ion}: energy transferred in zones {np.flatnonzero((pool != 0) & (eps <= 0)) + 1} without eps_target"
+    assert np.any(pool[eps > 0] > 0), f"ion {i_ion}: no energy transferred"
+    return pool
+
+
+def _thermal_electrons_q5(prob, r):
+    """Quirk Q5 at size: every thermal electron of the mix ends at the helix cap in its first pcut, nobody is saved."""
+    IC, ng = mcs.capi.IC, prob.n_grid
+    assert r["reached"] == 1 and r["i_mult"] == [] and r["n_done"] == r["n_in"], r
+    assert int(r["dI"][ng + IC["HELIX_CAP"]]) == r["n_in"]
+    assert int(r["dI"][ng + IC["REASON1"]]) == r["n_in"]
+
+
+def test_config4_species_properties_every_pcut_1e6(monkeypatch):
+    """The bench mix, fp64, 10^6 particles per species, each species through the per-pcut properties of _property_run in order:
+    protons and He on kernel 6 into the late pcuts (10^5..10^6 replicas of a few parents, the energy-transfer flag under the tail
+    loop, LDS-staged escape tallies of a Z = 2, A = 4 ion), the first 4096 particles against the oracle; the energy_transfer_pool
+    after each ion species; the thermal electrons on kernel 2 against the oracle with the ions' pool pinned (see _property_run),
+    and their Q5 outcome -- one pcut, nobody saved, every electron at the helix cap -- which is the bench's electron workload."""
+    t0 = time.perf_counter()
+    monkeypatch.delenv("MCS_K1_WS", raising=False)
+    N = 1_000_000
+    prob = _mixed_problem(N)
+    hb, ob = hip_backend(prob), oracle_backend(prob, nthreads=8)
+    rs = []
+    for i_ion, kernel in enumerate(MIX_KERNELS[False], 1):
+        ion = i_ion < 3
+        rs.append(_property_run(N, prob=prob, i_ion=i_ion, hb=hb, ob=ob, kernel=kernel, min_pcuts=30 if ion else 1))
+        if ion:
+            _check_transfer_pool(prob, hb, i_ion)
+    _thermal_electrons_q5(prob, rs[2])
+    hb.destroy(); ob.destroy()
+    print(f"config[4] fp64 at 1e6 per species: pcuts reached {[r['reached'] for r in rs]}, exits {[r['n_done'] for r in rs]}, "
+          f"max i_mult {[max(r['i_mult'], default=0) for r in rs]}; {time.perf_counter() - t0:.0f} s")
+
+
+def test_config4_fp32_organised_kernels_equal_plain_loop_1e6(monkeypatch):
+    """test_fp32_kernels_agree at the bench size: the fp32-state mix at 10^6 per species through the organised kernels (3, 3, 5)
+    and, in lockstep on a second context, through the plain per-lane loop (MCS_F32_LOOP=1: 4).  The hardware fp32 primitives have
+    no CPU equal, so the check at size is bit identity between the two forms -- particles, saved arrays, l_save and int64 tallies
+    in every pcut, binned tallies to TALLY_RTOL -- plus the per-pcut properties of _property_run (no oracle prefix)."""
+    t0 = time.perf_counter()
+    N = 1_000_000
+    prob = _mixed_problem(N, state_fp32=True)
+    monkeypatch.setenv("MCS_F32_LOOP", "0")
+    hb = hip_backend(prob)
+    monkeypatch.setenv("MCS_F32_LOOP", "1")
+    tw = hip_backend(prob)
+    rs = []
+    for i_ion, kernel in enumerate(MIX_KERNELS[True], 1):
+        ion = i_ion < 3
+        rs.append(_property_run(N, n_prefix=0, prob=prob, i_ion=i_ion, hb=hb, twin=tw, kernel=kernel, twin_kernel=4,
+                                min_pcuts=30 if ion else 1))
+        if ion:
+            _check_transfer_pool(prob, hb, i_ion)
+    _thermal_electrons_q5(prob, rs[2])
+    hb.destroy(); tw.destroy()
+    print(f"config[4] fp32 at 1e6 per species, organised == plain loop: pcuts reached {[r['reached'] for r in rs]}; "
+          f"{time.perf_counter() - t0:.0f} s")
+
+
+def test_config4_wave_specialised_ion_kernel_1e6(monkeypatch):
+    """The ions of the bench mix at 10^6 through the wave-specialised form of their kernel (MCS_K1_WS=1: 8) in lockstep with the
+    default choice (6 at this size): every particle, saved array and int64 tally bit for bit in every pcut, binned tallies to
+    TALLY_RTOL.  test_wave_specialised_kernel_is_bit_identical covers 8 at 4000 particles only."""
+    t0 = time.perf_counter()
+    N = 1_000_000
+    prob = _mixed_problem(N)
+    monkeypatch.delenv("MCS_K1_WS", raising=False)
+    hb = hip_backend(prob)
+    monkeypatch.setenv("MCS_K1_WS", "1")
+    tw = hip_backend(prob)
+    rs = [_property_run(N, n_prefix=0, prob=prob, i_ion=i_ion, hb=hb, twin=tw, kernel=6, twin_kernel=8) for i_ion in (1, 2)]
+    hb.destroy(); tw.destroy()
+    print(f"config[4] ions at 1e6, kernel 8 == kernel 6: pcuts reached {[r['reached'] for r in rs]}; {time.perf_counter() - t0:.0f} s")
+
+
+# The crafted relativistic electrons of the golden case electrons_crafted_n64 (make_golden.crafted_population) at 10^6, with the
+# stock momentum cuts but two changes, chosen on the oracle at N = 2000 and 20000: with the stock cuts every electron ends in pcut
+# 17 (1e5 m_p c: the losses in the 3 G field stop them below it), the largest split is i_mult 8 and no exit has reason 3.  Cut 17
+# lowered to 5.623e4 m_p c (between its neighbours 3.162e4 and 3.162e5): 1.5 % of pcut 17 is saved, i_mult ~66 there, 18 pcuts
+# reached.  maximum_age 3e5 s, inside the crafted ages (10^0..10^6 s): the oldest ~9 % leave by age (reason 3) in pcut 1.
+CRAFTED_CUT17 = 5.623e4
+CRAFTED_AGE_MAX = 3e5
+
+
+def _crafted_electron_problem(N, **kw):
+    from golden_common import make_golden
+    c = dict(make_golden.CASES["electrons_crafted_n64"]["cfg"])
+    c["species"] = [mcs.inputs.Species(**sp) for sp in c["species"]]
+    cuts = list(mcs.inputs.STOCK_PCUTS)
+    assert cuts[16] == 1e5
+    cuts[16] = CRAFTED_CUT17
+    c.update(momentum_cutoffs=tuple(cuts), maximum_age=CRAFTED_AGE_MAX, **kw)
+    return mcs.inputs.build_problem(mcs.inputs.Config(N_PTS_INJ=N, N_PTS_PCUT=N, N_PTS_PCUT_HI=N, **c)), make_golden
+
+
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+def test_crafted_electrons_lossy_kernel_every_pcut_1e6(monkeypatch, precision):
+    """Electrons that live: the lossy kernels' multi-pcut path at size -- splits of electrons up to i_mult ~66, PRP shortening,
+    losses inside the retro walk -- where the thermal electrons of the mix die in pcut 1 (Q5).  fp64: kernel 2 through the
+    per-pcut properties, the first 4096 particles against the oracle.  fp32: the organised lossy kernel (5) in lockstep with the
+    plain loop (4), bit for bit.  Both: at least 5 pcuts, a split by >= 10, exit reasons 0-3 all present, > 100 helix steps per
+    particle (the losses act in the helix loop)."""
+    t0 = time.perf_counter()
+    N = 1_000_000
+    fp32 = precision == "fp32"
+    prob, make_golden = _crafted_electron_problem(N, state_fp32=fp32)
+    pop = make_golden.crafted_population("electrons", prob, N)
+    if fp32:
+        monkeypatch.setenv("MCS_F32_LOOP", "0")
+        hb = hip_backend(prob)
+        monkeypatch.setenv("MCS_F32_LOOP", "1")
+        tw = hip_backend(prob)
+        r = _property_run(N, n_prefix=0, prob=prob, pop=pop, hb=hb, twin=tw, kernel=5, twin_kernel=4, min_pcuts=5)
+        tw.destroy()
+    else:
+        hb, ob = hip_backend(prob), oracle_backend(prob, nthreads=8)
+        r = _property_run(N, prob=prob, pop=pop, hb=hb, ob=ob, kernel=2, min_pcuts=5)
+        ob.destroy()
+    hb.destroy()
+    IC = mcs.capi.IC
+    ng = prob.n_grid
+    assert max(r["i_mult"]) >= 10, r["i_mult"]
+    assert np.all(r["reasons"][:4] > 0), r["reasons"]
+    assert int(r["dI"][ng + IC["STEPS_HELIX"]]) > 100 * N
+    print(f"crafted electrons {precision} at 1e6: {r['reached']} pcuts, i_mult {r['i_mult']}, reasons {r['reasons'].tolist()}, "
+          f"{int(r['dI'][ng + IC['STEPS_HELIX']]) / N:.0f} helix steps per particle; {time.perf_counter() - t0:.0f} s")
+
+
+def test_config4_mixed_iteration_vs_oracle_fixture():
+    """The bench mix at 10^5 per species, one whole iteration through driver.run, against the committed run of the oracle
+    (tests/golden/mixed_1e5.npz, make_golden_full.py --mixed): per-pcut populations of every species, int64 tallies at every
+    species end and at the end equal, every binned array of the reduction within TALLY_RTOL (LONG_SUM_RTOL for LONG_SUMS).  The
+    electrons read the ions' energy_transfer_pool, an fp64 atomic sum whose last bits depend on the add order: at each species end
+    the GPU's pool is compared with the oracle's to LONG_SUM_RTOL and then replaced by the oracle's bits, so that the electrons
+    start from the same pool as the oracle's did -- pinning, not a looser tolerance."""
+    t0 = time.perf_counter()
+    fix = np.load(os.path.join(ROOT, "tests", "golden", "mixed_1e5.npz"))
+    m = _fixture_module()
+    prob = m.mixed_problem(100_000)
+    hb = hip_backend(prob)
+    L = hb.layout
+    pools, ints = fix["species_energy_transfer_pool"], fix["species_tallies_i64"]
+    kernels, pool_err = [], []
+
+    def species_end(i_iter, i_ion, f, i):
+        kernels.append(hb.last_kernel())
+        assert np.array_equal(i, ints[i_ion - 1]), f"ion {i_ion}: int64 tallies at the species end"
+        got, want = L.view(f, "energy_transfer_pool"), pools[i_ion - 1]
+        err = float(np.max(np.abs(got - want))) / float(np.max(np.abs(want)))
+        assert err <= LONG_SUM_RTOL, f"ion {i_ion}: energy_transfer_pool off by {err:.3e}"
+        pool_err.append(err)
+        if i_ion < len(prob.cfg.species):
+            got[...] = want
+            hb.write_tallies(f, i)
+    res = mcs.driver.run(prob, hb, None, n_itrs=1, on_species_end=species_end)
+    hb.destroy()
+    assert kernels == list(MIX_KERNELS[False]), kernels
+    got = m.reduce_tallies(L, res.tallies_f64, res.tallies_i64, res.stats, with_ion=True)
+    assert np.array_equal(got["stats"], fix["stats"])                 # i_ion, i_pcut, n_pts_use, n_saved, i_mult of all pcuts
+    assert np.array_equal(got["tallies_i64"], fix["tallies_i64"])
+    assert sorted({int(s) for s in fix["stats"][:, 0]}) == [1, 2, 3]
+    worst, n = _binned_vs_fixture(got, fix, skip=("species_energy_transfer_pool", "species_tallies_i64"))
+    print(f"config[4] at 1e5 per species: kernels {kernels}, pools within {max(pool_err):.2e}; {n} binned arrays, worst "
+          f"{worst[0]} {worst[1]:.2e} (bound {LONG_SUM_RTOL if worst[0] in LONG_SUMS else TALLY_RTOL}); {fix['meta']}; "
+          f"{time.perf_counter() - t0:.0f} s")

@@ -793,9 +793,10 @@ def test_full_iteration_binned_spectra_vs_oracle():
 
 def test_config4_mixed_species_full_iteration_vs_oracle():
     """BASELINE config[4]'s species mix on one GPU, fp64: protons + He + electrons with radiative losses and ion ->
-    electron energy transfer (the general kernel: every_pass / odd_cfg paths), a whole iteration through driver.run
-    (three species, all pcuts, tallies accumulated across species as the reference does) against the oracle.  Same
-    bar as the proton iteration: integers and per-pcut populations equal, binned spectra to 1e-11."""
+    electron energy transfer, a whole iteration through driver.run (three species, all pcuts, tallies accumulated across
+    species as the reference does) against the oracle.  The ions run the plain kernel with the energy-transfer flag
+    (last_kernel 6), the electrons the lossy kernel (2), read at every species end.  Same bar as the proton iteration:
+    integers and per-pcut populations equal, binned spectra to 1e-11.  (At 10^6 per species: tests/test_gpu_full_size.py.)"""
     N = 8_000
     me_mp = mcs.constants.ME / mcs.constants.MP
     prob = make_problem(N, species=[mcs.inputs.Species(1.0, 1.0, 1e6, 1.0), mcs.inputs.Species(4.0, 2.0, 1e6, 0.1),
@@ -804,7 +805,9 @@ def test_config4_mixed_species_full_iteration_vs_oracle():
     ob = oracle_backend(prob, nthreads=32)
     hb = hip_backend(prob)
     ro = mcs.driver.run(prob, ob, n_itrs=1)
-    rg = mcs.driver.run(prob, hb, n_itrs=1)
+    kernels = []
+    rg = mcs.driver.run(prob, hb, n_itrs=1, on_species_end=lambda it, ion, f, i: kernels.append(hb.last_kernel()))
+    assert kernels == [6, 6, 2], kernels
     assert len({s.i_ion for s in rg.stats}) == 3
     assert np.array_equal(rg.tallies_i64, ro.tallies_i64)
     assert (rg.steps_helix, rg.steps_retro) == (ro.steps_helix, ro.steps_retro)
