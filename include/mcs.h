@@ -142,6 +142,21 @@ enum {
 
 static inline int64_t mcs_i64_total(const mcs_params* p) { return (int64_t)p->n_grid + MCS_IC_COUNT; }
 
+/* Two kinds of sections, by what happens to them between the species of an iteration:
+ *
+ *   buffer  words                                  kind            sections
+ *   fp64    [psd, esc_flux)                        per-species     psd, therm_sf, therm_pf, esc_psd_up, esc_psd_down,
+ *                                                                  pxx_flux, pxz_flux, energy_flux
+ *   fp64    [energy_recv_pool, scalars)            per-species     energy_recv_pool
+ *   int64   [0, n_grid)                            per-species     num_crossings
+ *   fp64    [esc_flux, energy_recv_pool)           running sum     esc_flux, px_esc_feb, energy_esc_feb, esc_energy_eff,
+ *                                                                  esc_num_eff, weight_coupled, spectra_coupled, spectra_sf,
+ *                                                                  spectra_pf, energy_transfer_pool
+ *   fp64    [scalars, total)                       running sum     scalars
+ *   int64   [n_grid, n_grid + MCS_IC_COUNT)        running sum     the event counters
+ *
+ * mcs_begin_species resets or sets the per-species sections; every later species adds to the running sums.
+ * mcs_accumulate_tallies moves the running sums of one context into another's. */
 static inline void mcs_tally_layout(const mcs_params* p, mcs_layout* L) {
   const int64_t nm = p->num_psd_mom_bins + 2, nt = p->num_psd_tht_bins + 2, ng = p->n_grid;
   const int64_t pm = MCS_PSD_MAX + 1;
@@ -300,6 +315,14 @@ int mcs_write_tallies(mcs_ctx* ctx, const double* host_f64, const int64_t* host_
  * host rewrites in place between iterations is small: tcut_print normalises spectra_coupled and floors weight_coupled
  * (src/io.jl:28-45, called at src/main_loops.jl:383-389). */
 int mcs_write_tallies_part(mcs_ctx* ctx, int64_t first, int64_t count, const double* host_f64);
+/* The running sums of src (the table beside mcs_tally_layout) added into dst's, word by word (each fp64 word is one plain
+ * dst + src), and then set to zero in src; the per-species sections of both contexts are left as they are.  For species that ran
+ * on a second context of the same problem (the ion species of an iteration do not depend on each other).
+ * Both contexts' tally replicas are folded in first.  Ordered on the two contexts' streams, with no host synchronisation: dst's
+ * stream waits for the work queued on src's, and src's stream waits for the add.  Refused, with nothing changed: a null
+ * context, dst == src, contexts on different devices, or layouts that differ (total, n_grid, n_ions, n_itrs).  The caller
+ * serialises the call with every other call on either context. */
+int mcs_accumulate_tallies(mcs_ctx* dst, mcs_ctx* src);
 
 /* ---- consumers of the tallies, on the device-resident histograms ----
  * Host-made tables (O(bins), O(n_grid)); the edges are cgs momenta and true cos(theta) in the
@@ -407,6 +430,10 @@ int mcs_last_kernel(mcs_ctx* ctx);
 /* compute units of the context's device (the default grid of mcs_run_pcut* is 2 workgroups per CU; a caller that keeps two
  * contexts busy on one device gives each of them one per CU: mcs_set_launch(ctx, mcs_num_cus(ctx), 256)) */
 int mcs_num_cus(mcs_ctx* ctx);
+/* workgroups of the current species' transport kernel that one CU holds under an explicit launch geometry (mcs_set_launch):
+ * 2 for the fp64 kernels, 3 for the fp32-state ones.  A caller that runs two species side by side splits
+ * mcs_num_cus * this between their launches.  0 before mcs_set_cuts. */
+int mcs_k1_blocks_per_cu(mcs_ctx* ctx);
 
 #ifdef __cplusplus
 }

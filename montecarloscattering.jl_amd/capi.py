@@ -163,6 +163,24 @@ class Layout:
         return flat[o:o + int(np.prod(shp))].reshape(shp)
 
 
+# The two kinds of tally sections (the table beside mcs_tally_layout in include/mcs.h): mcs_begin_species resets or sets the
+# per-species ones; later species add to the running sums, which mcs_accumulate_tallies moves from one context into another's.
+PER_SPECIES_F64 = ("psd", "therm_sf", "therm_pf", "esc_psd_up", "esc_psd_down", "pxx_flux", "pxz_flux", "energy_flux",
+                   "energy_recv_pool")
+RUNNING_F64 = ("esc_flux", "px_esc_feb", "energy_esc_feb", "esc_energy_eff", "esc_num_eff", "weight_coupled", "spectra_coupled",
+               "spectra_sf", "spectra_pf", "energy_transfer_pool", "scalars")
+
+
+def per_species_i64(L: "Layout") -> slice:
+    """num_crossings, [0, n_grid) of the int64 buffer."""
+    return slice(0, L.n_grid)
+
+
+def running_i64(L: "Layout") -> slice:
+    """The event counters, [n_grid, n_grid + IC_COUNT)."""
+    return slice(L.n_grid, L.n_grid + IC_COUNT)
+
+
 def _as_dp(a: np.ndarray):
     assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(c_double_p)
@@ -248,6 +266,8 @@ def load_library() -> ct.CDLL:
         "mcs_dndp_2d": (i32, [vp, ct.POINTER(McsConsumerIn), dbl, dbl, c_double_p]),
         "mcs_photon_ic": (i32, [vp, c_double_p, dbl, i32, i32, c_double_p, c_double_p, i32, dbl, dbl, dbl, c_double_p, c_double_p]),
         "mcs_photon_pion": (i32, [vp, c_double_p, c_double_p, dbl, dbl, c_double_p, dbl, i32, i32, dbl, dbl, c_double_p, c_double_p]),
+        "mcs_accumulate_tallies": (i32, [vp, vp]),
+        "mcs_k1_blocks_per_cu": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -267,4 +287,5 @@ EXPORTED_SYMBOLS = [
     "mcs_run_pcut_strided", "mcs_run_pcut_indexed", "mcs_saved_gidx", "mcs_init_pop_binned_strided", "mcs_saved_export", "mcs_split_import", "mcs_set_debug_finals", "mcs_set_retro_cap",
     "mcs_set_tail_slicing", "mcs_last_launches", "mcs_last_kernel", "mcs_write_tallies_part", "mcs_photon_synch",
     "mcs_dndp_2d", "mcs_photon_ic", "mcs_run_pcuts_fused", "mcs_photon_pion", "mcs_run_pcuts_pipelined",
+    "mcs_accumulate_tallies", "mcs_k1_blocks_per_cu",
 ]

@@ -43,6 +43,8 @@ hipError_t mcs_launch_init_pop(DevPop out, const double* ptot_in, const double* 
                                hipStream_t st);
 hipError_t mcs_launch_fill(double* p, long long n, double v, hipStream_t st);
 hipError_t mcs_launch_fold_replicas(double* dst, double* rep, long long n, int n_rep, hipStream_t st);
+hipError_t mcs_launch_accumulate_tallies(double* dT, double* sT, unsigned long long* dI, unsigned long long* sI, long long a_lo,
+                                         long long a_n, long long b_lo, long long b_n, long long i_lo, long long i_n, hipStream_t st);
 hipError_t mcs_launch_copy(double* dst, const double* src, long long n, hipStream_t st);
 hipError_t mcs_launch_eval(int fn, long long n, const double* a, const double* b, double* out, hipStream_t st);
 hipError_t mcs_launch_dndp_cr(const mcs_params* P, const double* psd, const double* gam_sf, const double* ux, const double* tabs,
@@ -164,6 +166,7 @@ struct mcs_ctx {
   // launch
   int blocks = 0, threads = 256;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t acc_ev = nullptr;  // mcs_accumulate_tallies: orders the two contexts' streams (no timing; ev0 / ev1 time K1)
   double last_ms = 0.0;
   int n_cu = 256;
 };
@@ -351,6 +354,7 @@ int mcs_create(const mcs_params* p, int device, void* stream, mcs_ctx** out) {
   CRCHK(hipMemsetAsync(c->d_I, 0, (size_t)mcs_i64_total(p) * sizeof(unsigned long long), c->stream));
   CRCHK(hipEventCreate(&c->ev0));
   CRCHK(hipEventCreate(&c->ev1));
+  CRCHK(hipEventCreateWithFlags(&c->acc_ev, hipEventDisableTiming));
 
   CRCHK(hipStreamSynchronize(c->stream));
 #undef CRCHK
@@ -387,6 +391,7 @@ int mcs_destroy(mcs_ctx* c) {
   for (auto e : c->f_ev) (void)hipEventDestroy(e);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
+  if (c->acc_ev) (void)hipEventDestroy(c->acc_ev);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return 0;
@@ -705,6 +710,17 @@ static K1Plan k1_plan(const mcs_ctx* c, long long n, bool sliced) {
   if ((plain || plain_etf) && c->blocks <= 0 && (c->k1_ws == 1 || (c->k1_ws == 2 && n >= c->ws_auto_min)))
     return {plain ? K1_WS : K1_WS_ETF, mcs_transport_ws_threads(), 1};
   return {plain ? K1_PLAIN : (lossy ? K1_LOSSY : (plain_etf ? K1_PLAIN_ETF : K1_GENERAL)), 256, 2};
+}
+
+// The workgroups of the current species' K1 kernel that one CU holds when the launch geometry is explicit (mcs_set_launch: never
+// the wave-specialised form).  0, with a message, before mcs_set_cuts.
+int mcs_k1_blocks_per_cu(mcs_ctx* c) {
+  if (!c || !c->have_cuts) { (void)fail("mcs_k1_blocks_per_cu: cuts not set"); return 0; }
+  const int blocks = c->blocks;
+  c->blocks = 1;
+  const int per_cu = k1_plan(c, c->n, false).per_cu;
+  c->blocks = blocks;
+  return per_cu;
 }
 
 // persistent lanes: fill the chip (`full` workgroups), never launch more lanes than particles, at least one workgroup
@@ -1334,6 +1350,27 @@ int mcs_write_tallies(mcs_ctx* c, const double* host_f64, const int64_t* host_i6
   if (host_f64) HIPCHK(hipMemcpyAsync(c->d_T, host_f64, (size_t)c->L.total * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (host_i64) HIPCHK(hipMemcpyAsync(c->d_I, host_i64, (size_t)mcs_i64_total(&c->P) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// The running sums of src added into dst's and cleared in src (the split of the layout: include/mcs.h, beside mcs_tally_layout).
+// Ordered on the two streams, no host synchronisation: dst's stream waits for what src's stream has queued, runs the kernel, and src's
+// stream waits for the kernel before anything else may add to the sums it clears.
+int mcs_accumulate_tallies(mcs_ctx* dst, mcs_ctx* src) {
+  if (!dst || !src) return fail("mcs_accumulate_tallies: null context");
+  if (dst == src) return fail("mcs_accumulate_tallies: dst and src are the same context");
+  if (dst->device != src->device) return fail("mcs_accumulate_tallies: the contexts are on different devices");
+  if (dst->L.total != src->L.total || dst->P.n_grid != src->P.n_grid || dst->P.n_ions != src->P.n_ions || dst->P.n_itrs != src->P.n_itrs)
+    return fail("mcs_accumulate_tallies: the contexts' tally layouts differ (total, n_grid, n_ions or n_itrs)");
+  HIPCHK(hipSetDevice(dst->device));
+  if (fold_replicas(src) || fold_replicas(dst)) return 1;
+  const mcs_layout& L = dst->L;
+  HIPCHK(hipEventRecord(src->acc_ev, src->stream));
+  HIPCHK(hipStreamWaitEvent(dst->stream, src->acc_ev, 0));
+  HIPCHK(mcs_launch_accumulate_tallies(dst->d_T, src->d_T, dst->d_I, src->d_I, L.esc_flux, L.energy_recv_pool - L.esc_flux, L.scalars, 4,
+                                       dst->P.n_grid, MCS_IC_COUNT, dst->stream));
+  HIPCHK(hipEventRecord(dst->acc_ev, dst->stream));
+  HIPCHK(hipStreamWaitEvent(src->stream, dst->acc_ev, 0));
   return 0;
 }
 

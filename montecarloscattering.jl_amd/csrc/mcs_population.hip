@@ -451,3 +451,32 @@ extern "C" hipError_t mcs_launch_fold_replicas(double* dst, double* rep, long lo
   mcs_k_fold_replicas<<<2048, 256, 0, st>>>(dst, rep, n, n_rep);
   return hipGetLastError();
 }
+
+// The running sums of one context's tallies added into another's and cleared at the source (mcs_accumulate_tallies; the split of
+// the layout is the table beside mcs_tally_layout in include/mcs.h): fp64 words [a_lo, a_lo + a_n) and [b_lo, b_lo + b_n), int64
+// words [i_lo, i_lo + i_n).  Each word is one plain add, so the sum is the one the host would form.
+extern "C" __global__ void mcs_k_accumulate_tallies(double* __restrict__ dT, double* __restrict__ sT, unsigned long long* __restrict__ dI,
+                                                    unsigned long long* __restrict__ sI, long long a_lo, long long a_n, long long b_lo,
+                                                    long long b_n, long long i_lo, long long i_n) {
+  const long long n = a_n + b_n + i_n;
+  for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
+    if (k < a_n + b_n) {
+      const long long j = k < a_n ? a_lo + k : b_lo + (k - a_n);
+      dT[j] = dT[j] + sT[j];
+      sT[j] = 0.0;
+    } else {
+      const long long j = i_lo + (k - a_n - b_n);
+      dI[j] = dI[j] + sI[j];
+      sI[j] = 0ULL;
+    }
+  }
+}
+extern "C" hipError_t mcs_launch_accumulate_tallies(double* dT, double* sT, unsigned long long* dI, unsigned long long* sI, long long a_lo,
+                                                    long long a_n, long long b_lo, long long b_n, long long i_lo, long long i_n, hipStream_t st) {
+  const long long n = a_n + b_n + i_n;
+  if (n <= 0) return hipSuccess;
+  long long blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  mcs_k_accumulate_tallies<<<(unsigned)blocks, 256, 0, st>>>(dT, sT, dI, sI, a_lo, a_n, b_lo, b_n, i_lo, i_n);
+  return hipGetLastError();
+}

@@ -32,12 +32,14 @@ from __future__ import annotations
 
 import dataclasses
 import os
+import threading
 import time
 from typing import Callable, List, Optional
 
 import numpy as np
 
 from . import inputs
+from .capi import RUNNING_F64, running_i64
 from .inputs import Problem
 
 
@@ -68,6 +70,8 @@ class RunResult:
     local_steps: list = dataclasses.field(default_factory=list)   # [(i_iter, i_ion, helix + retro steps made by THIS rank's kernels)]
     empty_launches: list = dataclasses.field(default_factory=list)   # [(i_iter, i_ion, i_pcut, kernel_ms)]: transport launches of a fused species
                                                                   # loop on an EMPTY population (the pcuts after the one that saved nobody)
+    species_spans: list = dataclasses.field(default_factory=list)    # [(i_iter, i_ion, context index, t_start, t_end)]: host times
+                                                                  # (time.perf_counter) around each species' transport, run(species_backends=...)
 
 
 class Comm:
@@ -130,13 +134,36 @@ def shard_range(n: int, rank: int, world: int):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def accumulate_tallies_host(L, dst, src):
+    """mcs_accumulate_tallies through the host, for backends without it (the CPU oracle): src's running sums (capi.RUNNING_F64 and
+    the event counters) added into dst's, then set to zero in src; the per-species sections of both stay as they are."""
+    df, di = dst.read_tallies()
+    sf, si = src.read_tallies()
+    for name in RUNNING_F64:
+        L.view(df, name)[...] += L.view(sf, name)
+        L.view(sf, name)[...] = 0.0
+    r = running_i64(L)
+    di[r] += si[r]
+    si[r] = 0
+    dst.write_tallies(df, di)
+    src.write_tallies(sf, si)
+
+
+def _launch_share(be, n_flight: int) -> int:
+    """Workgroups of one transport launch while n_flight species share the chip: an equal share of the workgroup slots the
+    species' kernel has (mcs_k1_blocks_per_cu per CU); 0, the automatic full-chip geometry, for a species alone."""
+    if n_flight <= 1:
+        return 0
+    return max(be.num_cus() * be.k1_blocks_per_cu() // n_flight, 1)
+
+
 def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[int] = None,
         max_pcuts: Optional[int] = None, on_species_end: Optional[Callable] = None,
         verbose: bool = False, gather_max: int = 1 << 17, skew_max: float = 1.1,
         finalize: bool = False, smoothing=None, on_iteration_end: Optional[Callable] = None,
         first_iter: int = 1, iter_state=None, species_tallies: str = "full", final_full_read: bool = True,
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: bool = True, long_draws: Optional[int] = None,
-        long_imult_max: Optional[int] = None) -> RunResult:
+        long_imult_max: Optional[int] = None, species_backends: Optional[list] = None) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -163,6 +190,20 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     first_iter / iter_state: run iterations first_iter .. first_iter + n_itrs - 1 (the iteration number enters the
     RNG keys and indexes the per-iteration tallies), carrying the iter_finalize state of an earlier call
     (RunResult.iter_state) -- lets a caller step through the loop one iteration at a time.
+    species_backends: further contexts of the same `prob` (created by the caller: each costs its own device memory) on which the
+    species of an iteration that depend on nothing run beside the others.  A species depends on every earlier one when it is a
+    receiver -- aa < 1 with energy_transfer_frac > 0: its begin_species copies what the earlier species deposited (include/mcs.h,
+    mcs_begin_species) -- and on nothing otherwise.  `backend` is the primary context: begin_iteration runs there only, and it holds
+    the iteration's running sums (the table beside mcs_tally_layout).  Species 1, every receiver and the last species run on the
+    primary, each after every earlier species has been merged into it; any other species runs on a secondary as soon as one is
+    free.  Species end in any order and are merged into the primary in species order (mcs_accumulate_tallies, or
+    accumulate_tallies_host); a secondary takes its next species only after its merge.  Species that run side by side take the
+    per-pcut loop, and before every launch each gets an equal share of the workgroup slots while others are in flight
+    (_launch_share).  What the caller sees is what the one-context run gives: stats, per_species, local_steps and the
+    on_species_end calls (calling thread, species order; for a species of a secondary after its merge, with the running sums of
+    species 1..k and species k's own per-species sections) are in species order, and what the hook writes back through
+    `backend.write_tallies` is what the later species start from.  RunResult.species_spans says what overlapped.  None or []:
+    the one-context loop.  Single process without a communicator, no long_draws and no before_pcut.
     """
     import torch
 
@@ -199,6 +240,23 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         steps_seen = int(_i0[i_h] + _i0[i_r])
     iter_finals = []
     empty_launches = []
+    species_spans = []
+    secondaries = list(species_backends or [])
+    if secondaries:
+        if comm.enabled:
+            raise ValueError("species_backends: one process without a communicator (the species' merges are not collectives)")
+        if long_draws:
+            raise ValueError("species_backends: not with long_draws (the pipelined pcut loop takes the whole chip)")
+        if before_pcut is not None:
+            raise ValueError("species_backends: the per-pcut hook sets the launch geometry of overlapping species; no before_pcut")
+        if len({id(be) for be in [backend] + secondaries}) != len(secondaries) + 1:
+            raise ValueError("species_backends: every context must be a different one, and none the primary")
+        for be in secondaries:
+            Lb = be.layout
+            if Lb.total != L.total or Lb.n_i64 != L.n_i64 or Lb.offsets != L.offsets:
+                raise ValueError("species_backends: a secondary context's tally layout differs from the primary's")
+            if getattr(be, "device", None) != getattr(backend, "device", None):
+                raise ValueError("species_backends: every context must be on the primary's device")
     if smoothing is not None:
         finalize = True
     if finalize:
@@ -210,6 +268,290 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         o = L.offsets[name]
         return t[o:o + int(np.prod(L.shapes[name]))]
 
+    def zero_running_sums(be):
+        f, i = be.read_tallies_light() if hasattr(be, "read_tallies_light") else be.read_tallies()
+        if any(np.any(L.view(f, name)) for name in RUNNING_F64) or np.any(i[running_i64(L)]):
+            f, i = be.read_tallies()
+            for name in RUNNING_F64:
+                L.view(f, name)[...] = 0.0
+            i[running_i64(L)] = 0
+            be.write_tallies(f, i)
+
+    def concurrent_species(i_iter):
+        """The species of iteration i_iter on the primary and the secondary contexts (run's species_backends)."""
+        nonlocal G_f, G_i, steps_seen
+        from concurrent.futures import ThreadPoolExecutor, wait, FIRST_COMPLETED
+        n_sp = len(cfg.species)
+        ctxs = [backend] + secondaries
+        etf = P.energy_transfer_frac > 0
+        on_primary = {k: k == 1 or k == n_sp or (etf and cfg.species[k - 1].aa < 1) for k in range(1, n_sp + 1)}
+        free = list(range(1, len(ctxs)))      # idle secondaries (context indices)
+        started = {}                          # i_ion -> (context index, future)
+        flight = {"n": 0}                     # species in flight on the chip (their launches share it)
+        lock = threading.Lock()
+        next_merge = 1                        # every species before this one is merged into the primary
+
+        def job(k, i_ion, overlapped):
+            be = ctxs[k]
+            out_stats, out_empty = [], []
+            geo = overlapped and hasattr(be, "set_launch")
+
+            def geometry(*_):
+                # decided before EVERY launch: a species left alone on the chip gets the automatic geometry back
+                if geo:
+                    blocks = _launch_share(be, flight["n"])
+                    be.set_launch(blocks, 256 if blocks else 0)
+            t0 = time.perf_counter()
+            try:
+                species_transport(be, i_iter, i_ion, geometry if overlapped else None, out_stats, out_empty)
+            finally:
+                t1 = time.perf_counter()
+                with lock:
+                    flight["n"] -= 1
+                if geo:
+                    be.set_launch(0, 0)          # back to the automatic geometry, also when the species raised
+            return out_stats, out_empty, t0, t1
+
+        def start_ready(primary_too):
+            for i_ion in range(1, n_sp + 1):
+                if i_ion in started:
+                    continue
+                if on_primary[i_ion]:
+                    if not (primary_too and i_ion == next_merge):
+                        continue
+                    k = 0
+                elif free:
+                    k = free.pop(0)
+                else:
+                    continue
+                # the primary's species overlap whatever species of a secondary has not ended yet (or is still to start); one that
+                # starts alone keeps the fused loop
+                overlapped = k > 0 or any(not on_primary[j] and not (j in started and started[j][1].done()) for j in range(1, n_sp + 1))
+                with lock:
+                    flight["n"] += 1
+                started[i_ion] = (k, pool.submit(job, k, i_ion, overlapped))
+
+        last_iter = first_iter + n_itrs - 1
+        with ThreadPoolExecutor(max_workers=len(ctxs)) as pool:   # (leaving the block waits for every thread, also on an exception)
+            start_ready(True)
+            while next_merge <= n_sp:
+                i_ion = next_merge
+                if i_ion in started and started[i_ion][1].done():
+                    k, fu = started[i_ion]
+                    out_stats, out_empty, t0, t1 = fu.result()            # (re-raises what the species raised)
+                    last_read = final_full_read and i_iter == last_iter and i_ion == n_sp
+                    be = ctxs[k]
+                    light = species_tallies == "light" and not last_read and hasattr(be, "read_tallies_light")
+                    if k > 0:
+                        if hasattr(backend, "accumulate_tallies_from") and type(be) is type(backend):
+                            backend.accumulate_tallies_from(be)
+                        else:
+                            accumulate_tallies_host(L, backend, be)
+                        # species k's own per-species sections (the secondary's) with the running sums of species 1..k (the primary's)
+                        f, i = be.read_tallies_light() if light else be.read_tallies()
+                        pf, pi = backend.read_tallies_light() if hasattr(backend, "read_tallies_light") else backend.read_tallies()
+                        for name in RUNNING_F64:
+                            L.view(f, name)[...] = L.view(pf, name)
+                        i[running_i64(L)] = pi[running_i64(L)]
+                        free.append(k)
+                        free.sort()
+                    else:
+                        f, i = backend.read_tallies_light() if light else backend.read_tallies()
+                    stats.extend(out_stats)
+                    empty_launches.extend(out_empty)
+                    species_spans.append((i_iter, i_ion, k, t0, t1))
+                    local_steps.append((i_iter, i_ion, int(i[i_h] + i[i_r]) - steps_seen))
+                    steps_seen = int(i[i_h] + i[i_r])
+                    G_f, G_i = f, i
+                    per_species.append((i_iter, i_ion, G_f, G_i))
+                    next_merge += 1
+                    start_ready(False)            # (a freed secondary takes its next species; the primary waits for the hook)
+                    if on_species_end is not None:
+                        on_species_end(i_iter, i_ion, G_f, G_i)
+                    start_ready(True)
+                    continue
+                running = [fu for _, fu in started.values() if not fu.done()]
+                wait(running, return_when=FIRST_COMPLETED)
+                for j in sorted(started):         # a species that raised: no more merges; the block's exit waits for the others
+                    if started[j][1].done() and started[j][1].exception() is not None:
+                        raise started[j][1].exception()
+
+    def species_transport(be, i_iter, i_ion, hook, out_stats, out_empty):
+        """begin_species .. the last pcut of species i_ion on context `be`; its pcuts go to out_stats / out_empty.  hook: the
+        before_pcut of this species (None: the fused loop where it applies)."""
+        sp = cfg.species[i_ion - 1]
+        pmax_cutoff = inputs.get_pmax_cutoff(prob.Emax_keV, prob.Emax_per_aa_keV, prob.pmax, sp.aa)
+        inj = inputs.init_pop_host(prob, i_ion)
+        zz = abs(sp.zz) if cfg.abs_charge else sp.zz
+        ewf = 1.0 / cfg.species[-1].density if cfg.species[-1].density != 0 else float("inf")
+        be.begin_species(i_iter, i_ion, sp.aa, zz, pmax_cutoff, sp.density, ewf)
+        if is_root:
+            be.set_fluxes(inj.pxx_flux, inj.pxz_flux, inj.energy_flux)
+        if multi:
+            if dev_t is not None:
+                if not is_root:   # per-species fills are baselines too
+                    for name in ("psd", "esc_psd_up", "esc_psd_down"):
+                        tview(dev_t[0], name).zero_()
+                if G_pool is not None:   # ions' donated energy, merged at the previous species end
+                    tview(dev_t[0], "energy_recv_pool").copy_(G_pool)
+            else:
+                f, i = be.read_tallies()
+                if not is_root:
+                    for name in ("psd", "esc_psd_up", "esc_psd_down"):
+                        L.view(f, name)[...] = 0.0
+                if G_pool is not None:
+                    L.view(f, "energy_recv_pool")[...] = G_pool
+                be.write_tallies(f, i)
+
+        n_total = inj.n_pts_use
+        # the shard: global index of local particle k = first + k * stride, or gidx[k] after a local split
+        first, stride, gidx = comm.rank, comm.world, None
+        n_local = (n_total - comm.rank + comm.world - 1) // comm.world if n_total > comm.rank else 0
+        if stride == 1:
+            be.init_pop(inj, 0, n_local, n_total)
+        else:
+            be.init_pop(inj, first, n_local, n_total, stride)
+        p_pcut_hi = inputs.pcut_hi(cfg.EN_PCUT_HI, sp.mass)
+        n_use_global = n_total
+        # One rank, no per-pcut hook: the whole pcut loop of the species is queued on the device at once -- n_saved, i_mult and
+        # the next population's size are decided there (mcs_run_pcuts_fused), one read-back per species instead of one per pcut.
+        fused = (fused_pcuts and not multi and hook is None and hasattr(be, "run_pcuts_fused") and n_pcuts >= 1
+                 and os.environ.get("MCS_FUSED_PCUTS", "1") != "0")
+        # Long histories told apart (long_draws > 0; MCS_LONG_DRAWS): the next population is ordered non-long before long, which lets a
+        # pcut's long histories finish beside the next pcut (mcs_run_pcuts_pipelined; one rank).  A backend without that entry point
+        # (the oracle) is told the order (set_long_draws) and runs the ordinary loop: same populations, same streams, same results.
+        if long_draws:
+            if multi:
+                raise ValueError("long_draws: the pipelined pcut loop and its population order are single-rank (one process per replica)")
+            if not hasattr(be, "run_pcuts_pipelined") and not hasattr(be, "set_long_draws"):
+                raise ValueError("long_draws: the backend can neither pipeline the pcuts nor order the population by history length")
+        pipelined = bool(long_draws) and hook is None and hasattr(be, "run_pcuts_pipelined") and n_pcuts >= 1 and not getattr(P, "state_fp32", 0)
+        if long_draws and not pipelined:
+            if not hasattr(be, "set_long_draws"):
+                raise ValueError("long_draws: this configuration runs the per-pcut loop, and the backend cannot order the population there")
+            be.set_long_draws(int(long_draws))
+        i_mult_prev = 0                 # (the rule of mcs_run_pcuts_pipelined for the per-pcut loop: see long_imult_max)
+        if pipelined:
+            fused = False
+            t0 = time.perf_counter()
+            targets = [cfg.N_PTS_PCUT if prob.pcuts[ip - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI for ip in range(1, n_pcuts + 1)]
+            n_use_a, n_saved_a, i_mult_a, ms_a, strag_a = be.run_pcuts_pipelined(1, n_pcuts, targets, int(long_draws), int(long_imult_max))
+            wall = (time.perf_counter() - t0) * 1e3
+            n_done = n_pcuts
+            for ip in range(1, n_pcuts + 1):
+                if int(n_saved_a[ip - 1]) == 0:
+                    n_done = ip
+                    break
+            for ip in range(1, n_done + 1):
+                nu, nsv, im = int(n_use_a[ip - 1]), int(n_saved_a[ip - 1]), int(i_mult_a[ip - 1])
+                out_stats.append(PcutStat(i_iter, i_ion, ip, nu, nsv, im if nsv > 0 else 0, nu, "-", float(ms_a[ip - 1]), wall / max(n_done, 1)))
+                if verbose and is_root:
+                    print(f"[iter {i_iter} ion {i_ion} pcut {ip:2d}] n_use={nu} n_saved={nsv} i_mult={im} kernel={ms_a[ip - 1]:.2f} ms "
+                          f"(pipelined: {int(strag_a[ip - 1][0])} long histories exported{', waited' if strag_a[ip - 1][1] else ''})", flush=True)
+        if fused:
+            t0 = time.perf_counter()
+            targets = [cfg.N_PTS_PCUT if prob.pcuts[ip - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI for ip in range(1, n_pcuts + 1)]
+            # (in chunks: a species that ends early -- the thermal electrons in their first pcut -- would otherwise pay ~35 us of
+            # empty launches for every remaining pcut; one read-back per chunk of 12 instead of one per pcut)
+            chunk = max(1, int(os.environ.get("MCS_FUSED_CHUNK", "12")))
+            n_use_a, n_saved_a, i_mult_a, ms_a = [], [], [], []
+            for c0 in range(1, n_pcuts + 1, chunk):
+                c1 = min(c0 + chunk - 1, n_pcuts)
+                a_, b_, c_, d_ = be.run_pcuts_fused(c0, c1, targets[c0 - 1:c1])
+                n_use_a.extend(a_); n_saved_a.extend(b_); i_mult_a.extend(c_); ms_a.extend(d_)
+                if min(b_) == 0:
+                    break
+            n_done = len(n_use_a)
+            wall = (time.perf_counter() - t0) * 1e3
+            for ip in range(1, n_done + 1):
+                nu, nsv, im = int(n_use_a[ip - 1]), int(n_saved_a[ip - 1]), int(i_mult_a[ip - 1])
+                last = nsv == 0 or ip == n_pcuts
+                out_stats.append(PcutStat(i_iter, i_ion, ip, nu, nsv, im if nsv > 0 else 0, nu, "-", float(ms_a[ip - 1]), wall / max(n_done, 1)))
+                if verbose and is_root:
+                    print(f"[iter {i_iter} ion {i_ion} pcut {ip:2d}] n_use={nu} n_saved={nsv} i_mult={im} kernel={ms_a[ip - 1]:.2f} ms (fused loop)", flush=True)
+                if last:
+                    out_empty.extend((i_iter, i_ion, jp, float(ms_a[jp - 1])) for jp in range(ip + 1, n_done + 1))
+                    break
+        for i_pcut in (() if (fused or pipelined) else range(1, n_pcuts + 1)):
+            t0 = time.perf_counter()
+            if hook is not None:
+                hook(i_iter, i_ion, i_pcut)
+            if long_draws and not pipelined:
+                be.set_long_draws(int(long_draws) if (i_pcut == 1 or long_imult_max <= 0 or i_mult_prev <= long_imult_max) else 0)
+            if gidx is not None:
+                n_saved_local = be.run_pcut_indexed(i_pcut, gidx)
+            else:
+                n_saved_local = be.run_pcut(i_pcut, first, stride)
+            gathered = comm.all_gather_ints([n_saved_local, n_local])
+            counts = [g[0] for g in gathered]
+            n_use_max = max(g[1] for g in gathered)
+            n_saved = sum(counts)
+            wall = (time.perf_counter() - t0) * 1e3
+            # pcut_finalize (src/cuts.jl:100-124)
+            i_mult = 0
+            if n_saved > 0:
+                n_target = cfg.N_PTS_PCUT if prob.pcuts[i_pcut - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI
+                i_mult = max(n_target // n_saved, 1)         # new_pcut, src/cuts.jl:42
+            i_mult_prev = i_mult
+            last = n_saved == 0 or i_pcut == n_pcuts
+            local_ok = not multi or (n_saved > gather_max and max(counts) * comm.world <= skew_max * n_saved)
+            st = PcutStat(i_iter, i_ion, i_pcut, n_use_global, n_saved, i_mult, n_use_max,
+                          "-" if last else ("local" if local_ok else "gather"), be.last_kernel_ms(), wall)
+            out_stats.append(st)
+            if verbose and is_root:
+                print(f"[iter {i_iter} ion {i_ion} pcut {i_pcut:2d}] n_use={n_use_global} (max local {n_use_max}) "
+                      f"n_saved={n_saved} i_mult={i_mult} split={st.split} kernel={be.last_kernel_ms():.2f} ms "
+                      f"wall={wall:.1f} ms", flush=True)
+            if n_saved == 0:
+                break
+            identity = multi and n_saved == n_use_global and i_mult == 1
+            n_prev_global = n_use_global                     # (every global index of the pcut just run is below this)
+            n_use_global = n_saved * i_mult
+            if identity:
+                # everybody was saved and nobody is replicated (the first pcuts of a species): the saved particles' positions
+                # in the global order ARE their indices, so every rank's children keep the global indices their parents had
+                # -- no index column to exchange, no particle to move; the shard description (first / stride / gidx) stands
+                be.new_pcut(1)
+                out_stats[-1].split = "identity"
+            elif not multi:
+                be.new_pcut(i_mult)                     # one process: the shard stays 0, 1, 2, ...
+                n_local = n_use_global
+            elif local_ok:
+                # every rank splits its own saved particles; the index column alone goes round
+                g_loc = be.saved_gidx()                                  # ascending, counts[rank] entries
+                cap = max(max(counts), 1)
+                # (padded with the largest integer: every row of the gathered table stays sorted; for each of my saved particles a
+                # searchsorted per peer row counts that rank's saved particles below it.  One row at a time, accumulated in place:
+                # the working set is O(n) -- round 3 searched all rows at once through an expanded [W, n] key matrix and an int64
+                # [W, n] result, 0.5 + 0.8 GB per rank and pcut at config[3]'s 1.25e7 particles per GPU)
+                # (the column travels as int32 while every index fits: half the bytes on the wire and in the search -- 4 B per saved
+                # particle per peer, 32 MB per rank and pcut at 10^6 particles per GPU on 8 GPUs)
+                idt = torch.int32 if n_prev_global < 2 ** 31 - 1 else torch.int64
+                g_key = g_loc.to(idt)
+                pad = torch.full((cap,), torch.iinfo(idt).max, dtype=idt, device=g_loc.device)
+                pad[:g_key.numel()] = g_key
+                g_all = comm.all_gather_rows(pad)                             # [W, cap]
+                pos = torch.zeros(g_key.numel(), dtype=torch.int64, device=g_loc.device)
+                for w in range(g_all.shape[0]):
+                    pos += torch.searchsorted(g_all[w], g_key)
+                gidx = (pos[:, None] * i_mult + torch.arange(i_mult, dtype=torch.int64, device=g_loc.device)[None, :]).reshape(-1).contiguous()
+                be.new_pcut(i_mult)
+                n_local = counts[comm.rank] * i_mult
+            else:
+                # all ranks see all parents (sorted by global index); rank r builds elements r, r+W, ... of the split
+                g, f64, meta = be.export_saved(max(max(counts), 1))
+                g = comm.all_gather_cols(g, counts)
+                f64 = comm.all_gather_cols(f64, counts)
+                meta = comm.all_gather_cols(meta, counts)
+                order = torch.argsort(g, stable=True)
+                f64 = f64.index_select(1, order).contiguous()
+                meta = meta.index_select(0, order).contiguous()
+                first, stride, gidx = comm.rank, comm.world, None
+                n_local = (n_use_global - comm.rank + comm.world - 1) // comm.world if n_use_global > comm.rank else 0
+                be.import_split(f64, meta, n_saved, i_mult, first, stride, n_local)
+
+    for be in secondaries:          # (a context reused from an earlier call must add nothing stale)
+        zero_running_sums(be)
     for i_iter in range(first_iter, first_iter + n_itrs):
         backend.begin_iteration(i_iter)
         if multi and not is_root:
@@ -219,176 +561,10 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                 f, i = backend.read_tallies()
                 f[:] = 0.0
                 backend.write_tallies(f, i)
-        for i_ion, sp in enumerate(cfg.species, start=1):
-            pmax_cutoff = inputs.get_pmax_cutoff(prob.Emax_keV, prob.Emax_per_aa_keV, prob.pmax, sp.aa)
-            inj = inputs.init_pop_host(prob, i_ion)
-            zz = abs(sp.zz) if cfg.abs_charge else sp.zz
-            ewf = 1.0 / cfg.species[-1].density if cfg.species[-1].density != 0 else float("inf")
-            backend.begin_species(i_iter, i_ion, sp.aa, zz, pmax_cutoff, sp.density, ewf)
-            if is_root:
-                backend.set_fluxes(inj.pxx_flux, inj.pxz_flux, inj.energy_flux)
-            if multi:
-                if dev_t is not None:
-                    if not is_root:   # per-species fills are baselines too
-                        for name in ("psd", "esc_psd_up", "esc_psd_down"):
-                            tview(dev_t[0], name).zero_()
-                    if G_pool is not None:   # ions' donated energy, merged at the previous species end
-                        tview(dev_t[0], "energy_recv_pool").copy_(G_pool)
-                else:
-                    f, i = backend.read_tallies()
-                    if not is_root:
-                        for name in ("psd", "esc_psd_up", "esc_psd_down"):
-                            L.view(f, name)[...] = 0.0
-                    if G_pool is not None:
-                        L.view(f, "energy_recv_pool")[...] = G_pool
-                    backend.write_tallies(f, i)
-
-            n_total = inj.n_pts_use
-            # the shard: global index of local particle k = first + k * stride, or gidx[k] after a local split
-            first, stride, gidx = comm.rank, comm.world, None
-            n_local = (n_total - comm.rank + comm.world - 1) // comm.world if n_total > comm.rank else 0
-            if stride == 1:
-                backend.init_pop(inj, 0, n_local, n_total)
-            else:
-                backend.init_pop(inj, first, n_local, n_total, stride)
-            p_pcut_hi = inputs.pcut_hi(cfg.EN_PCUT_HI, sp.mass)
-            n_use_global = n_total
-            # One rank, no per-pcut hook: the whole pcut loop of the species is queued on the device at once -- n_saved, i_mult and
-            # the next population's size are decided there (mcs_run_pcuts_fused), one read-back per species instead of one per pcut.
-            fused = (fused_pcuts and not multi and before_pcut is None and hasattr(backend, "run_pcuts_fused") and n_pcuts >= 1
-                     and os.environ.get("MCS_FUSED_PCUTS", "1") != "0")
-            # Long histories told apart (long_draws > 0; MCS_LONG_DRAWS): the next population is ordered non-long before long, which lets a
-            # pcut's long histories finish beside the next pcut (mcs_run_pcuts_pipelined; one rank).  A backend without that entry point
-            # (the oracle) is told the order (set_long_draws) and runs the ordinary loop: same populations, same streams, same results.
-            if long_draws:
-                if multi:
-                    raise ValueError("long_draws: the pipelined pcut loop and its population order are single-rank (one process per replica)")
-                if not hasattr(backend, "run_pcuts_pipelined") and not hasattr(backend, "set_long_draws"):
-                    raise ValueError("long_draws: the backend can neither pipeline the pcuts nor order the population by history length")
-            pipelined = bool(long_draws) and before_pcut is None and hasattr(backend, "run_pcuts_pipelined") and n_pcuts >= 1 and not getattr(P, "state_fp32", 0)
-            if long_draws and not pipelined:
-                if not hasattr(backend, "set_long_draws"):
-                    raise ValueError("long_draws: this configuration runs the per-pcut loop, and the backend cannot order the population there")
-                backend.set_long_draws(int(long_draws))
-            i_mult_prev = 0                 # (the rule of mcs_run_pcuts_pipelined for the per-pcut loop: see long_imult_max)
-            if pipelined:
-                fused = False
-                t0 = time.perf_counter()
-                targets = [cfg.N_PTS_PCUT if prob.pcuts[ip - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI for ip in range(1, n_pcuts + 1)]
-                n_use_a, n_saved_a, i_mult_a, ms_a, strag_a = backend.run_pcuts_pipelined(1, n_pcuts, targets, int(long_draws), int(long_imult_max))
-                wall = (time.perf_counter() - t0) * 1e3
-                n_done = n_pcuts
-                for ip in range(1, n_pcuts + 1):
-                    if int(n_saved_a[ip - 1]) == 0:
-                        n_done = ip
-                        break
-                for ip in range(1, n_done + 1):
-                    nu, nsv, im = int(n_use_a[ip - 1]), int(n_saved_a[ip - 1]), int(i_mult_a[ip - 1])
-                    stats.append(PcutStat(i_iter, i_ion, ip, nu, nsv, im if nsv > 0 else 0, nu, "-", float(ms_a[ip - 1]), wall / max(n_done, 1)))
-                    if verbose and is_root:
-                        print(f"[iter {i_iter} ion {i_ion} pcut {ip:2d}] n_use={nu} n_saved={nsv} i_mult={im} kernel={ms_a[ip - 1]:.2f} ms "
-                              f"(pipelined: {int(strag_a[ip - 1][0])} long histories exported{', waited' if strag_a[ip - 1][1] else ''})", flush=True)
-            if fused:
-                t0 = time.perf_counter()
-                targets = [cfg.N_PTS_PCUT if prob.pcuts[ip - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI for ip in range(1, n_pcuts + 1)]
-                # (in chunks: a species that ends early -- the thermal electrons in their first pcut -- would otherwise pay ~35 us of
-                # empty launches for every remaining pcut; one read-back per chunk of 12 instead of one per pcut)
-                chunk = max(1, int(os.environ.get("MCS_FUSED_CHUNK", "12")))
-                n_use_a, n_saved_a, i_mult_a, ms_a = [], [], [], []
-                for c0 in range(1, n_pcuts + 1, chunk):
-                    c1 = min(c0 + chunk - 1, n_pcuts)
-                    a_, b_, c_, d_ = backend.run_pcuts_fused(c0, c1, targets[c0 - 1:c1])
-                    n_use_a.extend(a_); n_saved_a.extend(b_); i_mult_a.extend(c_); ms_a.extend(d_)
-                    if min(b_) == 0:
-                        break
-                n_done = len(n_use_a)
-                wall = (time.perf_counter() - t0) * 1e3
-                for ip in range(1, n_done + 1):
-                    nu, nsv, im = int(n_use_a[ip - 1]), int(n_saved_a[ip - 1]), int(i_mult_a[ip - 1])
-                    last = nsv == 0 or ip == n_pcuts
-                    stats.append(PcutStat(i_iter, i_ion, ip, nu, nsv, im if nsv > 0 else 0, nu, "-", float(ms_a[ip - 1]), wall / max(n_done, 1)))
-                    if verbose and is_root:
-                        print(f"[iter {i_iter} ion {i_ion} pcut {ip:2d}] n_use={nu} n_saved={nsv} i_mult={im} kernel={ms_a[ip - 1]:.2f} ms (fused loop)", flush=True)
-                    if last:
-                        empty_launches.extend((i_iter, i_ion, jp, float(ms_a[jp - 1])) for jp in range(ip + 1, n_done + 1))
-                        break
-            for i_pcut in (() if (fused or pipelined) else range(1, n_pcuts + 1)):
-                t0 = time.perf_counter()
-                if before_pcut is not None:
-                    before_pcut(i_iter, i_ion, i_pcut)
-                if long_draws and not pipelined:
-                    backend.set_long_draws(int(long_draws) if (i_pcut == 1 or long_imult_max <= 0 or i_mult_prev <= long_imult_max) else 0)
-                if gidx is not None:
-                    n_saved_local = backend.run_pcut_indexed(i_pcut, gidx)
-                else:
-                    n_saved_local = backend.run_pcut(i_pcut, first, stride)
-                gathered = comm.all_gather_ints([n_saved_local, n_local])
-                counts = [g[0] for g in gathered]
-                n_use_max = max(g[1] for g in gathered)
-                n_saved = sum(counts)
-                wall = (time.perf_counter() - t0) * 1e3
-                # pcut_finalize (src/cuts.jl:100-124)
-                i_mult = 0
-                if n_saved > 0:
-                    n_target = cfg.N_PTS_PCUT if prob.pcuts[i_pcut - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI
-                    i_mult = max(n_target // n_saved, 1)         # new_pcut, src/cuts.jl:42
-                i_mult_prev = i_mult
-                last = n_saved == 0 or i_pcut == n_pcuts
-                local_ok = not multi or (n_saved > gather_max and max(counts) * comm.world <= skew_max * n_saved)
-                st = PcutStat(i_iter, i_ion, i_pcut, n_use_global, n_saved, i_mult, n_use_max,
-                              "-" if last else ("local" if local_ok else "gather"), backend.last_kernel_ms(), wall)
-                stats.append(st)
-                if verbose and is_root:
-                    print(f"[iter {i_iter} ion {i_ion} pcut {i_pcut:2d}] n_use={n_use_global} (max local {n_use_max}) "
-                          f"n_saved={n_saved} i_mult={i_mult} split={st.split} kernel={backend.last_kernel_ms():.2f} ms "
-                          f"wall={wall:.1f} ms", flush=True)
-                if n_saved == 0:
-                    break
-                identity = multi and n_saved == n_use_global and i_mult == 1
-                n_prev_global = n_use_global                     # (every global index of the pcut just run is below this)
-                n_use_global = n_saved * i_mult
-                if identity:
-                    # everybody was saved and nobody is replicated (the first pcuts of a species): the saved particles' positions
-                    # in the global order ARE their indices, so every rank's children keep the global indices their parents had
-                    # -- no index column to exchange, no particle to move; the shard description (first / stride / gidx) stands
-                    backend.new_pcut(1)
-                    stats[-1].split = "identity"
-                elif not multi:
-                    backend.new_pcut(i_mult)                     # one process: the shard stays 0, 1, 2, ...
-                    n_local = n_use_global
-                elif local_ok:
-                    # every rank splits its own saved particles; the index column alone goes round
-                    g_loc = backend.saved_gidx()                                  # ascending, counts[rank] entries
-                    cap = max(max(counts), 1)
-                    # (padded with the largest integer: every row of the gathered table stays sorted; for each of my saved particles a
-                    # searchsorted per peer row counts that rank's saved particles below it.  One row at a time, accumulated in place:
-                    # the working set is O(n) -- round 3 searched all rows at once through an expanded [W, n] key matrix and an int64
-                    # [W, n] result, 0.5 + 0.8 GB per rank and pcut at config[3]'s 1.25e7 particles per GPU)
-                    # (the column travels as int32 while every index fits: half the bytes on the wire and in the search -- 4 B per saved
-                    # particle per peer, 32 MB per rank and pcut at 10^6 particles per GPU on 8 GPUs)
-                    idt = torch.int32 if n_prev_global < 2 ** 31 - 1 else torch.int64
-                    g_key = g_loc.to(idt)
-                    pad = torch.full((cap,), torch.iinfo(idt).max, dtype=idt, device=g_loc.device)
-                    pad[:g_key.numel()] = g_key
-                    g_all = comm.all_gather_rows(pad)                             # [W, cap]
-                    pos = torch.zeros(g_key.numel(), dtype=torch.int64, device=g_loc.device)
-                    for w in range(g_all.shape[0]):
-                        pos += torch.searchsorted(g_all[w], g_key)
-                    gidx = (pos[:, None] * i_mult + torch.arange(i_mult, dtype=torch.int64, device=g_loc.device)[None, :]).reshape(-1).contiguous()
-                    backend.new_pcut(i_mult)
-                    n_local = counts[comm.rank] * i_mult
-                else:
-                    # all ranks see all parents (sorted by global index); rank r builds elements r, r+W, ... of the split
-                    g, f64, meta = backend.export_saved(max(max(counts), 1))
-                    g = comm.all_gather_cols(g, counts)
-                    f64 = comm.all_gather_cols(f64, counts)
-                    meta = comm.all_gather_cols(meta, counts)
-                    order = torch.argsort(g, stable=True)
-                    f64 = f64.index_select(1, order).contiguous()
-                    meta = meta.index_select(0, order).contiguous()
-                    first, stride, gidx = comm.rank, comm.world, None
-                    n_local = (n_use_global - comm.rank + comm.world - 1) // comm.world if n_use_global > comm.rank else 0
-                    backend.import_split(f64, meta, n_saved, i_mult, first, stride, n_local)
+        if secondaries:
+            concurrent_species(i_iter)
+        for i_ion, sp in (() if secondaries else enumerate(cfg.species, start=1)):
+            species_transport(backend, i_iter, i_ion, before_pcut, stats, empty_launches)
 
             # species end: merge the partial tallies of all ranks (C1)
             if multi and dev_t is not None:
@@ -456,8 +632,9 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                 changed = True
             if changed:
                 itf.populate_eps_target(prob)        # src/main_loops.jl:76-81, top of the next iteration
-                backend.set_grid(prob)
-                backend.set_cuts(prob)
+                for be in [backend] + secondaries:
+                    be.set_grid(prob)
+                    be.set_cuts(prob)
         if tcut_print and P.do_tcuts:
             # (after iter_finalize, as at src/main_loops.jl:363-389; G_f is the merged buffer of the last species, which holds the
             # coupled arrays of every species -- they are per-ion slices of one array).  The rewrite is applied to a COPY of the
@@ -477,7 +654,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     from .capi import IC
     return RunResult(G_f, G_i, per_species, stats,
                      int(G_i[ng + IC["STEPS_HELIX"]]), int(G_i[ng + IC["STEPS_RETRO"]]), iter_finals,
-                     it_state if finalize else None, local_steps, empty_launches)
+                     it_state if finalize else None, local_steps, empty_launches, species_spans)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over

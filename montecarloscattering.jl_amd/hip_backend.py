@@ -303,6 +303,18 @@ class HipBackend:
         assert a.size == int(np.prod(self.layout.shapes[name]))
         self._chk(self.lib.mcs_write_tallies_part(self.h, int(self.layout.offsets[name]), a.size, _dp(a)))
 
+    def accumulate_tallies_from(self, other: "HipBackend"):
+        """mcs_accumulate_tallies(self, other): other's running sums added into this context's and cleared in other; the
+        per-species sections of both stay (include/mcs.h).  Queued on the two streams, no host synchronisation."""
+        self._chk(self.lib.mcs_accumulate_tallies(self.h, other.h))
+
+    def k1_blocks_per_cu(self) -> int:
+        """Workgroups of the current species' transport kernel a CU holds under an explicit launch geometry (mcs_k1_blocks_per_cu)."""
+        n = int(self.lib.mcs_k1_blocks_per_cu(self.h))
+        if n <= 0:
+            raise RuntimeError("libmcs_hip: " + self.lib.mcs_last_error().decode())
+        return n
+
     # -- consumers of the tallies (K4)
     def dndp_cr(self, tabs):
         """get_dNdp_cr + CR normalisation on the resident psd -> ([3][n_grid][nmom+2], diag[2])."""
