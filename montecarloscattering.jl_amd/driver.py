@@ -30,16 +30,19 @@ fluxes) live on rank 0 only so that the sum over ranks is the single-GPU result.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import os
 import threading
 import time
+import types
+from concurrent.futures import FIRST_COMPLETED, ThreadPoolExecutor, wait
 from typing import Callable, List, Optional
 
 import numpy as np
 
-from . import inputs
-from .capi import RUNNING_F64, running_i64
+from . import consumers, inputs, iter_finalize as itf
+from .capi import IC, RUNNING_F64, running_i64
 from .inputs import Problem
 
 
@@ -157,6 +160,412 @@ def _launch_share(be, n_flight: int) -> int:
     return max(be.num_cus() * be.k1_blocks_per_cu() // n_flight, 1)
 
 
+# Optional backend methods and their fallbacks (capability is duck-typed on the instance and looked up at call time: tests wrap
+# backends in proxies, tools patch methods).
+def _read_light(be):
+    """(f64, i64) without the three big histograms where the backend can leave them on the device; the whole buffers otherwise."""
+    return be.read_tallies_light() if hasattr(be, "read_tallies_light") else be.read_tallies()
+
+
+def _read_counters(be):
+    """The int64 tallies alone."""
+    return be.read_counters() if hasattr(be, "read_counters") else be.read_tallies()[1]
+
+
+def _steps(i64, n_grid: int):
+    """(helix, retro) step counters of an int64 tally buffer, host array or device tensor: never reset, a context's running totals."""
+    return int(i64[n_grid + IC["STEPS_HELIX"]]), int(i64[n_grid + IC["STEPS_RETRO"]])
+
+
+def _zero_running_sums(L, be):
+    f, i = _read_light(be)
+    if any(np.any(L.view(f, name)) for name in RUNNING_F64) or np.any(i[running_i64(L)]):
+        f, i = be.read_tallies()
+        for name in RUNNING_F64:
+            L.view(f, name)[...] = 0.0
+        i[running_i64(L)] = 0
+        be.write_tallies(f, i)
+
+
+class _ChipShare:
+    """Launches of several contexts that share the chip (run_overlapped's iterations, run's side-by-side species): how many
+    are in flight, and the launch geometry of each while it is not alone."""
+
+    def __init__(self):
+        self.n, self.lock = 0, threading.Lock()
+
+    def enter(self):
+        with self.lock:
+            self.n += 1
+
+    @contextlib.contextmanager
+    def geometry(self, be, share: Callable, active=True):
+        """For a context that has entered: yields its before_pcut hook, which gives every launch share(number in flight)
+        workgroups (0: the automatic geometry); leaves on exit.  Not active, or no set_launch: the hook does nothing."""
+        geo = active and hasattr(be, "set_launch")
+
+        def hook(*_):
+            # decided before EVERY launch: one left alone on the chip (the last iteration of an odd count, a species whose
+            # neighbour has ended) gets the automatic full-chip geometry back
+            if geo:
+                blocks = int(share(self.n))
+                be.set_launch(blocks, 256 if blocks else 0)
+        try:
+            yield hook
+        finally:
+            with self.lock:
+                self.n -= 1
+            if geo:
+                be.set_launch(0, 0)          # back to the automatic geometry, also when the body raised
+
+
+def _pcut_target(rs, i_pcut, p_pcut_hi):
+    return rs.prob.cfg.N_PTS_PCUT if rs.prob.pcuts[i_pcut - 1] < p_pcut_hi else rs.prob.cfg.N_PTS_PCUT_HI
+
+
+def _device_pcut_rows(rs, i_iter, i_ion, counts, wall, note, out_stats, out_empty=None):
+    """PcutStat rows and verbose lines (ended by note(ip)) of a pcut loop decided on the device, from its (n_use, n_saved, i_mult, kernel_ms)
+    per launch.  The rows end with the pcut that saved nobody; out_empty takes the launches after it (None: they are not recorded)."""
+    n_use_a, n_saved_a, i_mult_a, ms_a = counts
+    n_rows = next((ip for ip in range(1, len(n_saved_a) + 1) if int(n_saved_a[ip - 1]) == 0), len(n_saved_a))
+    n_timed = n_rows if out_empty is None else len(n_saved_a)
+    for ip in range(1, n_rows + 1):
+        nu, nsv, im = int(n_use_a[ip - 1]), int(n_saved_a[ip - 1]), int(i_mult_a[ip - 1])
+        out_stats.append(PcutStat(i_iter, i_ion, ip, nu, nsv, im if nsv > 0 else 0, nu, "-", float(ms_a[ip - 1]), wall / max(n_timed, 1)))
+        if rs.verbose and rs.is_root:
+            print(f"[iter {i_iter} ion {i_ion} pcut {ip:2d}] n_use={nu} n_saved={nsv} i_mult={im} kernel={ms_a[ip - 1]:.2f} ms {note(ip)}", flush=True)
+    if out_empty is not None:
+        out_empty.extend((i_iter, i_ion, jp, float(ms_a[jp - 1])) for jp in range(n_rows + 1, len(n_saved_a) + 1))
+
+
+def _pcuts_pipelined(rs, be, i_iter, i_ion, targets, out_stats):
+    """The species' pcuts in one backend call (mcs_run_pcuts_pipelined)."""
+    t0 = time.perf_counter()
+    *counts, strag_a = be.run_pcuts_pipelined(1, rs.n_pcuts, targets, int(rs.long_draws), int(rs.long_imult_max))
+    wall = (time.perf_counter() - t0) * 1e3
+    _device_pcut_rows(rs, i_iter, i_ion, counts, wall, lambda ip: f"(pipelined: {int(strag_a[ip - 1][0])} long histories exported"
+                      f"{', waited' if strag_a[ip - 1][1] else ''})", out_stats)
+
+
+def _pcuts_fused(rs, be, i_iter, i_ion, targets, out_stats, out_empty):
+    """The species' pcuts in one backend call per chunk (mcs_run_pcuts_fused)."""
+    t0 = time.perf_counter()
+    # (in chunks: a species that ends early -- the thermal electrons in their first pcut -- would otherwise pay ~35 us of
+    # empty launches for every remaining pcut; one read-back per chunk of 12 instead of one per pcut)
+    chunk = max(1, int(os.environ.get("MCS_FUSED_CHUNK", "12")))
+    counts = ([], [], [], [])
+    for c0 in range(1, rs.n_pcuts + 1, chunk):
+        c1 = min(c0 + chunk - 1, rs.n_pcuts)
+        got = be.run_pcuts_fused(c0, c1, targets[c0 - 1:c1])
+        for all_, new in zip(counts, got):
+            all_.extend(new)
+        if min(got[1]) == 0:
+            break
+    wall = (time.perf_counter() - t0) * 1e3
+    _device_pcut_rows(rs, i_iter, i_ion, counts, wall, lambda ip: "(fused loop)", out_stats, out_empty)
+
+
+def _next_population(rs, be, row, counts, n_prev_global, local_ok, shard):
+    """new_pcut (src/cuts.jl:34-98) after a pcut that saved row.n_saved particles in all, counts[r] of them on rank r: the next
+    population in one of the four ways of the module docstring -> its shard (first, stride, gidx, n_local)."""
+    import torch
+    comm, i_mult = rs.comm, row.i_mult
+    first, stride, gidx, n_local = shard
+    n_use_global = row.n_saved * i_mult
+    if rs.multi and row.n_saved == n_prev_global and i_mult == 1:
+        # everybody was saved and nobody is replicated (the first pcuts of a species): the saved particles' positions
+        # in the global order ARE their indices, so every rank's children keep the global indices their parents had
+        # -- no index column to exchange, no particle to move; the shard description (first / stride / gidx) stands
+        be.new_pcut(1)
+        row.split = "identity"
+    elif not rs.multi:
+        be.new_pcut(i_mult)                     # one process: the shard stays 0, 1, 2, ...
+        n_local = n_use_global
+    elif local_ok:
+        # every rank splits its own saved particles; the index column alone goes round
+        g_loc = be.saved_gidx()                                  # ascending, counts[rank] entries
+        cap = max(max(counts), 1)
+        # (padded with the largest integer: every row of the gathered table stays sorted; for each of my saved particles a
+        # searchsorted per peer row counts that rank's saved particles below it.  One row at a time, accumulated in place:
+        # the working set is O(n) -- round 3 searched all rows at once through an expanded [W, n] key matrix and an int64
+        # [W, n] result, 0.5 + 0.8 GB per rank and pcut at config[3]'s 1.25e7 particles per GPU)
+        # (the column travels as int32 while every index fits: half the bytes on the wire and in the search -- 4 B per saved
+        # particle per peer, 32 MB per rank and pcut at 10^6 particles per GPU on 8 GPUs)
+        idt = torch.int32 if n_prev_global < 2 ** 31 - 1 else torch.int64
+        g_key = g_loc.to(idt)
+        pad = torch.full((cap,), torch.iinfo(idt).max, dtype=idt, device=g_loc.device)
+        pad[:g_key.numel()] = g_key
+        g_all = comm.all_gather_rows(pad)                             # [W, cap]
+        pos = torch.zeros(g_key.numel(), dtype=torch.int64, device=g_loc.device)
+        for w in range(g_all.shape[0]):
+            pos += torch.searchsorted(g_all[w], g_key)
+        gidx = (pos[:, None] * i_mult + torch.arange(i_mult, dtype=torch.int64, device=g_loc.device)[None, :]).reshape(-1).contiguous()
+        be.new_pcut(i_mult)
+        n_local = counts[comm.rank] * i_mult
+    else:
+        # all ranks see all parents (sorted by global index); rank r builds elements r, r+W, ... of the split
+        g, f64, meta = be.export_saved(max(max(counts), 1))
+        g = comm.all_gather_cols(g, counts)
+        f64 = comm.all_gather_cols(f64, counts)
+        meta = comm.all_gather_cols(meta, counts)
+        order = torch.argsort(g, stable=True)
+        f64 = f64.index_select(1, order).contiguous()
+        meta = meta.index_select(0, order).contiguous()
+        first, stride, gidx = comm.rank, comm.world, None
+        n_local = (n_use_global - comm.rank + comm.world - 1) // comm.world if n_use_global > comm.rank else 0
+        be.import_split(f64, meta, row.n_saved, i_mult, first, stride, n_local)
+    return first, stride, gidx, n_local
+
+
+def _pcuts_one_by_one(rs, be, i_iter, i_ion, hook, p_pcut_hi, n_use_global, shard, out_stats):
+    """One backend call and one small collective per pcut; the host decides i_mult and builds the next population."""
+    comm, long_draws = rs.comm, rs.long_draws
+    i_mult_prev = 0                 # (the rule of mcs_run_pcuts_pipelined for the per-pcut loop: see long_imult_max)
+    for i_pcut in range(1, rs.n_pcuts + 1):
+        t0 = time.perf_counter()
+        first, stride, gidx, n_local = shard
+        if hook is not None:
+            hook(i_iter, i_ion, i_pcut)
+        if long_draws:
+            be.set_long_draws(int(long_draws) if (i_pcut == 1 or rs.long_imult_max <= 0 or i_mult_prev <= rs.long_imult_max) else 0)
+        n_saved_local = be.run_pcut_indexed(i_pcut, gidx) if gidx is not None else be.run_pcut(i_pcut, first, stride)
+        gathered = comm.all_gather_ints([n_saved_local, n_local])
+        counts = [g[0] for g in gathered]
+        n_use_max = max(g[1] for g in gathered)
+        n_saved = sum(counts)
+        wall = (time.perf_counter() - t0) * 1e3
+        # pcut_finalize (src/cuts.jl:100-124)
+        i_mult = max(_pcut_target(rs, i_pcut, p_pcut_hi) // n_saved, 1) if n_saved > 0 else 0         # new_pcut, src/cuts.jl:42
+        i_mult_prev = i_mult
+        last = n_saved == 0 or i_pcut == rs.n_pcuts
+        local_ok = not rs.multi or (n_saved > rs.gather_max and max(counts) * comm.world <= rs.skew_max * n_saved)
+        row = PcutStat(i_iter, i_ion, i_pcut, n_use_global, n_saved, i_mult, n_use_max,
+                       "-" if last else ("local" if local_ok else "gather"), be.last_kernel_ms(), wall)
+        out_stats.append(row)
+        if rs.verbose and rs.is_root:
+            print(f"[iter {i_iter} ion {i_ion} pcut {i_pcut:2d}] n_use={n_use_global} (max local {n_use_max}) "
+                  f"n_saved={n_saved} i_mult={i_mult} split={row.split} kernel={be.last_kernel_ms():.2f} ms "
+                  f"wall={wall:.1f} ms", flush=True)
+        if n_saved == 0:
+            break
+        # (every global index of the pcut just run is below n_use_global)
+        shard = _next_population(rs, be, row, counts, n_use_global, local_ok, shard)
+        n_use_global = n_saved * i_mult
+
+
+def _species_transport(rs, be, i_iter, i_ion, hook, out_stats, out_empty):
+    """begin_species .. the last pcut of species i_ion on context `be`; its pcuts go to out_stats / out_empty.  hook: the
+    before_pcut of this species (None: the fused loop where it applies)."""
+    prob, comm, L, cfg = rs.prob, rs.comm, rs.L, rs.prob.cfg
+    sp = cfg.species[i_ion - 1]
+    pmax_cutoff = inputs.get_pmax_cutoff(prob.Emax_keV, prob.Emax_per_aa_keV, prob.pmax, sp.aa)
+    inj = inputs.init_pop_host(prob, i_ion)
+    zz = abs(sp.zz) if cfg.abs_charge else sp.zz
+    ewf = 1.0 / cfg.species[-1].density if cfg.species[-1].density != 0 else float("inf")
+    be.begin_species(i_iter, i_ion, sp.aa, zz, pmax_cutoff, sp.density, ewf)
+    if rs.is_root:
+        be.set_fluxes(inj.pxx_flux, inj.pxz_flux, inj.energy_flux)
+    if rs.multi:
+        # (on the bound device tensors in place, otherwise on the host's copy of the buffers)
+        f, i = (rs.dev_t[0], None) if rs.dev_t is not None else be.read_tallies()
+        if not rs.is_root:   # per-species fills are baselines too
+            for name in ("psd", "esc_psd_up", "esc_psd_down"):
+                L.view(f, name)[...] = 0.0
+        if rs.G_pool is not None:   # ions' donated energy, merged at the previous species end
+            L.view(f, "energy_recv_pool")[...] = rs.G_pool
+        if rs.dev_t is None:
+            be.write_tallies(f, i)
+
+    n_total = inj.n_pts_use
+    # the shard: global index of local particle k = first + k * stride, or gidx[k] after a local split
+    first, stride = comm.rank, comm.world
+    n_local = (n_total - comm.rank + comm.world - 1) // comm.world if n_total > comm.rank else 0
+    if stride == 1:
+        be.init_pop(inj, 0, n_local, n_total)
+    else:
+        be.init_pop(inj, first, n_local, n_total, stride)
+    p_pcut_hi = inputs.pcut_hi(cfg.EN_PCUT_HI, sp.mass)
+    # One rank, no per-pcut hook: the whole pcut loop of the species is queued on the device at once -- n_saved, i_mult and
+    # the next population's size are decided there (mcs_run_pcuts_fused), one read-back per species instead of one per pcut.
+    fused = (rs.fused_pcuts and not rs.multi and hook is None and hasattr(be, "run_pcuts_fused") and rs.n_pcuts >= 1
+             and os.environ.get("MCS_FUSED_PCUTS", "1") != "0")
+    # Long histories told apart (long_draws > 0; MCS_LONG_DRAWS): the next population is ordered non-long before long, which lets a
+    # pcut's long histories finish beside the next pcut (mcs_run_pcuts_pipelined; one rank).  A backend without that entry point
+    # (the oracle) is told the order (set_long_draws) and runs the ordinary loop: same populations, same streams, same results.
+    pipelined = False
+    if rs.long_draws:
+        if rs.multi:
+            raise ValueError("long_draws: the pipelined pcut loop and its population order are single-rank (one process per replica)")
+        if not hasattr(be, "run_pcuts_pipelined") and not hasattr(be, "set_long_draws"):
+            raise ValueError("long_draws: the backend can neither pipeline the pcuts nor order the population by history length")
+        pipelined = hook is None and hasattr(be, "run_pcuts_pipelined") and rs.n_pcuts >= 1 and not getattr(prob.params, "state_fp32", 0)
+        if not pipelined:
+            if not hasattr(be, "set_long_draws"):
+                raise ValueError("long_draws: this configuration runs the per-pcut loop, and the backend cannot order the population there")
+            be.set_long_draws(int(rs.long_draws))
+    targets = [_pcut_target(rs, ip, p_pcut_hi) for ip in range(1, rs.n_pcuts + 1)]
+    if pipelined:
+        _pcuts_pipelined(rs, be, i_iter, i_ion, targets, out_stats)
+    elif fused:
+        _pcuts_fused(rs, be, i_iter, i_ion, targets, out_stats, out_empty)
+    else:
+        _pcuts_one_by_one(rs, be, i_iter, i_ion, hook, p_pcut_hi, n_total, (first, stride, None, n_local), out_stats)
+
+
+def _merge_ranks_device(rs, light):
+    """Species end over the ranks, in place on the bound tally tensors (RCCL, no host round trip) -> (G_f, G_i, this rank's own step total)."""
+    L, comm = rs.L, rs.comm
+    rs.backend.sync()          # the bound tensors are complete after mcs_sync (it folds the tally replicas in)
+    tf, ti = rs.dev_t
+    local = sum(_steps(ti, L.n_grid))
+    if not rs.is_root:   # every rank carried a full copy of the received-energy pool
+        L.view(tf, "energy_recv_pool").zero_()
+    comm.all_reduce_sum_(tf); comm.all_reduce_sum_(ti)
+    rs.G_pool = L.view(tf, "energy_transfer_pool").clone()
+    if light:
+        o_small = L.offsets["esc_psd_up"]
+        G_f = np.zeros(L.total)
+        G_f[o_small:] = tf[o_small:].cpu().numpy()
+        G_i = ti.cpu().numpy()
+    else:
+        G_f, G_i = tf.cpu().numpy(), ti.cpu().numpy()
+    if not rs.is_root:
+        tf.zero_(); ti.zero_()
+    return G_f, G_i, local
+
+
+def _merge_ranks_host(rs):
+    """The same steps through read_tallies / write_tallies (CPU test backends)."""
+    import torch
+    L, comm, backend = rs.L, rs.comm, rs.backend
+    f, i = backend.read_tallies()
+    local = sum(_steps(i, L.n_grid))
+    if not rs.is_root:
+        L.view(f, "energy_recv_pool")[...] = 0.0
+    tf, ti = torch.from_numpy(f), torch.from_numpy(i)
+    comm.all_reduce_sum_(tf); comm.all_reduce_sum_(ti)
+    G_f, G_i = f.copy(), i.copy()
+    rs.G_pool = L.view(G_f, "energy_transfer_pool").copy()
+    if rs.is_root:
+        backend.write_tallies(G_f, G_i)
+    else:
+        backend.write_tallies(np.zeros_like(G_f), np.zeros_like(G_i))
+    return G_f, G_i, local
+
+
+def _species_end(rs, k, i_iter, i_ion, before_hook=None):
+    """Species i_ion has ended on context k (k > 0: a secondary, already merged into the primary): the tallies of all ranks merged (C1)
+    and handed to the host -- rs.G_f / rs.G_i, per_species, local_steps, on_species_end.  before_hook: called once the context is read."""
+    L, be = rs.L, rs.ctxs[k]
+    last_read = rs.final_full_read and i_iter == rs.last_iter and i_ion == len(rs.prob.cfg.species)
+    light = rs.species_tallies == "light" and not last_read
+    if rs.multi:
+        G_f, G_i, local = _merge_ranks_device(rs, light) if rs.dev_t is not None else _merge_ranks_host(rs)
+        seen = sum(_steps(G_i, L.n_grid)) if rs.is_root else 0     # rank 0 carries the merged totals on
+    else:
+        G_f, G_i = _read_light(be) if light else be.read_tallies()
+        if k > 0:
+            # species k's own per-species sections (the secondary's) with the running sums of species 1..k (the primary's)
+            pf, pi = _read_light(rs.backend)
+            for name in RUNNING_F64:
+                L.view(G_f, name)[...] = L.view(pf, name)
+            G_i[running_i64(L)] = pi[running_i64(L)]
+        local = seen = sum(_steps(G_i, L.n_grid))
+    rs.local_steps.append((i_iter, i_ion, local - rs.steps_seen))
+    rs.steps_seen = seen
+    rs.G_f, rs.G_i = G_f, G_i
+    rs.per_species.append((i_iter, i_ion, G_f, G_i))      # fresh host arrays: no copy needed
+    if before_hook is not None:
+        before_hook()
+    if rs.on_species_end is not None:
+        rs.on_species_end(i_iter, i_ion, G_f, G_i)
+
+
+class _SpeciesScheduler:
+    """Which species of an iteration runs on which context, and when (run's species_backends): species 1, every receiver and the last
+    species on the primary, each after every earlier species has been merged; any other on a secondary as soon as one is free."""
+
+    def __init__(self, rs, pool, i_iter):
+        cfg = rs.prob.cfg
+        self.rs, self.pool, self.i_iter, self.n_sp = rs, pool, i_iter, len(cfg.species)
+        etf = rs.prob.params.energy_transfer_frac > 0
+        self.on_primary = {k: k == 1 or k == self.n_sp or (etf and cfg.species[k - 1].aa < 1) for k in range(1, self.n_sp + 1)}
+        self.free = list(range(1, len(rs.ctxs)))      # idle secondaries (context indices)
+        self.started = {}                             # i_ion -> (context index, future)
+        self.flight = _ChipShare()                    # species in flight on the chip (their launches share it)
+        self.next_merge = 1                           # every species before this one is merged into the primary
+        self.start_ready(True)
+
+    def _job(self, k, i_ion, overlapped):
+        be = self.rs.ctxs[k]
+        out_stats, out_empty = [], []
+        t0 = time.perf_counter()
+        with self.flight.geometry(be, lambda n: _launch_share(be, n), overlapped) as geometry:
+            _species_transport(self.rs, be, self.i_iter, i_ion, geometry if overlapped else None, out_stats, out_empty)
+            t1 = time.perf_counter()
+        return out_stats, out_empty, t0, t1
+
+    def start_ready(self, primary_too):
+        started, on_primary = self.started, self.on_primary
+        for i_ion in range(1, self.n_sp + 1):
+            if i_ion in started:
+                continue
+            if on_primary[i_ion]:
+                if not (primary_too and i_ion == self.next_merge):
+                    continue
+                k = 0
+            elif self.free:
+                k = self.free.pop(0)
+            else:
+                continue
+            # the primary's species overlap whatever species of a secondary has not ended yet (or is still to start); one that
+            # starts alone keeps the fused loop
+            overlapped = k > 0 or any(not on_primary[j] and not (j in started and started[j][1].done()) for j in range(1, self.n_sp + 1))
+            self.flight.enter()
+            started[i_ion] = (k, self.pool.submit(self._job, k, i_ion, overlapped))
+
+    def result(self, i_ion):
+        """Waits for species i_ion -> (context index, stats, empty launches, t_start, t_end); re-raises what it or, meanwhile, another raised."""
+        k, fu = self.started[i_ion]
+        while not fu.done():
+            wait([f for _, f in self.started.values() if not f.done()], return_when=FIRST_COMPLETED)
+            for j in sorted(self.started):         # a species that raised: no more merges; the pool's exit waits for the others
+                if self.started[j][1].done() and self.started[j][1].exception() is not None:
+                    raise self.started[j][1].exception()
+        return (k,) + fu.result()
+
+    def merged(self, k):
+        """Species next_merge is merged and its context read: a freed secondary takes its next species (the primary waits for the hook)."""
+        if k > 0:
+            self.free = sorted(self.free + [k])
+        self.next_merge += 1
+        self.start_ready(False)
+
+
+def _iteration_species(rs, i_iter, before_pcut):
+    """The species of iteration i_iter in order: its transport (here, or with secondaries on the pool's threads as the
+    scheduler places it), its merge into the primary if it ran on a secondary, its species end."""
+    n_sp = len(rs.prob.cfg.species)
+    if len(rs.ctxs) == 1:
+        for i_ion in range(1, n_sp + 1):
+            _species_transport(rs, rs.backend, i_iter, i_ion, before_pcut, rs.stats, rs.empty_launches)
+            _species_end(rs, 0, i_iter, i_ion)
+        return
+    with ThreadPoolExecutor(max_workers=len(rs.ctxs)) as pool:   # (leaving the block waits for every thread, also on an exception)
+        sched = _SpeciesScheduler(rs, pool, i_iter)
+        for i_ion in range(1, n_sp + 1):
+            k, out_stats, out_empty, t0, t1 = sched.result(i_ion)
+            if k > 0 and hasattr(rs.backend, "accumulate_tallies_from") and type(rs.ctxs[k]) is type(rs.backend):
+                rs.backend.accumulate_tallies_from(rs.ctxs[k])      # its running sums added to the primary's and cleared
+            elif k > 0:
+                accumulate_tallies_host(rs.L, rs.backend, rs.ctxs[k])
+            rs.stats.extend(out_stats)
+            rs.empty_launches.extend(out_empty)
+            rs.species_spans.append((i_iter, i_ion, k, t0, t1))
+            _species_end(rs, k, i_iter, i_ion, lambda: sched.merged(k))
+            sched.start_ready(True)
+
+
 def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[int] = None,
         max_pcuts: Optional[int] = None, on_species_end: Optional[Callable] = None,
         verbose: bool = False, gather_max: int = 1 << 17, skew_max: float = 1.1,
@@ -206,42 +615,30 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     the one-context loop.  Single process without a communicator, no long_draws and no before_pcut.
     """
     import torch
-
     comm = comm or Comm(False)
-    cfg, P = prob.cfg, prob.params
+    cfg, P, L = prob.cfg, prob.params, backend.layout
     n_itrs = n_itrs if n_itrs is not None else cfg.num_iterations
-    n_pcuts = len(prob.pcuts) if max_pcuts is None else min(max_pcuts, len(prob.pcuts))
-    L = backend.layout
-    stats: List[PcutStat] = []
-    per_species = []
-    # rank > 0 keeps only its local partial sums: everything it contributes is a delta
-    is_root = comm.rank == 0
     multi = comm.enabled          # (a forced one-rank group runs the multi-rank path too: bench.py MCS_BENCH_FORCE_COMM)
     if long_draws is None:
         long_draws = int(os.environ.get("MCS_LONG_DRAWS", "0")) if not multi else 0
     if long_imult_max is None:
         long_imult_max = int(os.environ.get("MCS_LONG_IMULT_MAX", "8"))
-    G_f = G_i = None
-    # Live device tensors of the tallies (HIP backend with torch_tallies): the multi-GPU merge
-    # then runs in place on the device (RCCL all-reduce, no host round trip).  Otherwise
-    # (CPU test backends) the same steps go through read_tallies/write_tallies.
-    dev_t = backend.tally_tensors() if (multi and hasattr(backend, "tally_tensors")) else None
-    G_pool = None       # merged energy_transfer_pool of the previous species
-    local_steps = []    # (i_iter, i_ion, steps this rank's kernels made for that species)
-    from .capi import IC as _IC
-    i_h, i_r = P.n_grid + _IC["STEPS_HELIX"], P.n_grid + _IC["STEPS_RETRO"]
+    secondaries = list(species_backends or [])
+    # The state of the run, shared by the steps above.  dev_t: live device tensors of the tallies (HIP backend with torch_tallies):
+    # the multi-GPU merge then runs in place on the device; otherwise (CPU test backends) through read_tallies / write_tallies.
+    # G_f / G_i: the merged tallies of the latest species end; G_pool: its merged energy_transfer_pool (multi-rank).
+    # rank > 0 keeps only its local partial sums: everything it contributes is a delta.
+    rs = types.SimpleNamespace(
+        prob=prob, L=L, backend=backend, ctxs=[backend] + secondaries, comm=comm, is_root=comm.rank == 0, multi=multi,
+        dev_t=backend.tally_tensors() if (multi and hasattr(backend, "tally_tensors")) else None,
+        n_pcuts=len(prob.pcuts) if max_pcuts is None else min(max_pcuts, len(prob.pcuts)), last_iter=first_iter + n_itrs - 1,
+        verbose=verbose, gather_max=gather_max, skew_max=skew_max, fused_pcuts=fused_pcuts, long_draws=long_draws,
+        long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
+        G_f=None, G_i=None, G_pool=None, stats=[], per_species=[], local_steps=[], empty_launches=[], species_spans=[], iter_finals=[])
     # the step counters are never reset: this rank's running total.  A context that has run before (run() called again with
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
-    if dev_t is not None:
-        steps_seen = int(dev_t[1][i_h].item() + dev_t[1][i_r].item())
-    else:
-        # (the two counter words only: run_overlapped calls run() once per iteration)
-        _i0 = backend.read_counters() if hasattr(backend, "read_counters") else backend.read_tallies()[1]
-        steps_seen = int(_i0[i_h] + _i0[i_r])
-    iter_finals = []
-    empty_launches = []
-    species_spans = []
-    secondaries = list(species_backends or [])
+    # (the two counter words only: run_overlapped calls run() once per iteration)
+    rs.steps_seen = sum(_steps(rs.dev_t[1] if rs.dev_t is not None else _read_counters(backend), P.n_grid))
     if secondaries:
         if comm.enabled:
             raise ValueError("species_backends: one process without a communicator (the species' merges are not collectives)")
@@ -257,369 +654,32 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                 raise ValueError("species_backends: a secondary context's tally layout differs from the primary's")
             if getattr(be, "device", None) != getattr(backend, "device", None):
                 raise ValueError("species_backends: every context must be on the primary's device")
-    if smoothing is not None:
-        finalize = True
+    finalize = finalize or smoothing is not None
+    it_state = None
     if finalize:
-        from . import consumers, iter_finalize as itf
         sm = smoothing if smoothing is not None else itf.SmoothingConfig(smooth_shocks=False)
         it_state = iter_state if iter_state is not None else itf.IterState.create(prob, sm, P.n_itrs)
 
-    def tview(t, name):
-        o = L.offsets[name]
-        return t[o:o + int(np.prod(L.shapes[name]))]
-
-    def zero_running_sums(be):
-        f, i = be.read_tallies_light() if hasattr(be, "read_tallies_light") else be.read_tallies()
-        if any(np.any(L.view(f, name)) for name in RUNNING_F64) or np.any(i[running_i64(L)]):
-            f, i = be.read_tallies()
-            for name in RUNNING_F64:
-                L.view(f, name)[...] = 0.0
-            i[running_i64(L)] = 0
-            be.write_tallies(f, i)
-
-    def concurrent_species(i_iter):
-        """The species of iteration i_iter on the primary and the secondary contexts (run's species_backends)."""
-        nonlocal G_f, G_i, steps_seen
-        from concurrent.futures import ThreadPoolExecutor, wait, FIRST_COMPLETED
-        n_sp = len(cfg.species)
-        ctxs = [backend] + secondaries
-        etf = P.energy_transfer_frac > 0
-        on_primary = {k: k == 1 or k == n_sp or (etf and cfg.species[k - 1].aa < 1) for k in range(1, n_sp + 1)}
-        free = list(range(1, len(ctxs)))      # idle secondaries (context indices)
-        started = {}                          # i_ion -> (context index, future)
-        flight = {"n": 0}                     # species in flight on the chip (their launches share it)
-        lock = threading.Lock()
-        next_merge = 1                        # every species before this one is merged into the primary
-
-        def job(k, i_ion, overlapped):
-            be = ctxs[k]
-            out_stats, out_empty = [], []
-            geo = overlapped and hasattr(be, "set_launch")
-
-            def geometry(*_):
-                # decided before EVERY launch: a species left alone on the chip gets the automatic geometry back
-                if geo:
-                    blocks = _launch_share(be, flight["n"])
-                    be.set_launch(blocks, 256 if blocks else 0)
-            t0 = time.perf_counter()
-            try:
-                species_transport(be, i_iter, i_ion, geometry if overlapped else None, out_stats, out_empty)
-            finally:
-                t1 = time.perf_counter()
-                with lock:
-                    flight["n"] -= 1
-                if geo:
-                    be.set_launch(0, 0)          # back to the automatic geometry, also when the species raised
-            return out_stats, out_empty, t0, t1
-
-        def start_ready(primary_too):
-            for i_ion in range(1, n_sp + 1):
-                if i_ion in started:
-                    continue
-                if on_primary[i_ion]:
-                    if not (primary_too and i_ion == next_merge):
-                        continue
-                    k = 0
-                elif free:
-                    k = free.pop(0)
-                else:
-                    continue
-                # the primary's species overlap whatever species of a secondary has not ended yet (or is still to start); one that
-                # starts alone keeps the fused loop
-                overlapped = k > 0 or any(not on_primary[j] and not (j in started and started[j][1].done()) for j in range(1, n_sp + 1))
-                with lock:
-                    flight["n"] += 1
-                started[i_ion] = (k, pool.submit(job, k, i_ion, overlapped))
-
-        last_iter = first_iter + n_itrs - 1
-        with ThreadPoolExecutor(max_workers=len(ctxs)) as pool:   # (leaving the block waits for every thread, also on an exception)
-            start_ready(True)
-            while next_merge <= n_sp:
-                i_ion = next_merge
-                if i_ion in started and started[i_ion][1].done():
-                    k, fu = started[i_ion]
-                    out_stats, out_empty, t0, t1 = fu.result()            # (re-raises what the species raised)
-                    last_read = final_full_read and i_iter == last_iter and i_ion == n_sp
-                    be = ctxs[k]
-                    light = species_tallies == "light" and not last_read and hasattr(be, "read_tallies_light")
-                    if k > 0:
-                        if hasattr(backend, "accumulate_tallies_from") and type(be) is type(backend):
-                            backend.accumulate_tallies_from(be)
-                        else:
-                            accumulate_tallies_host(L, backend, be)
-                        # species k's own per-species sections (the secondary's) with the running sums of species 1..k (the primary's)
-                        f, i = be.read_tallies_light() if light else be.read_tallies()
-                        pf, pi = backend.read_tallies_light() if hasattr(backend, "read_tallies_light") else backend.read_tallies()
-                        for name in RUNNING_F64:
-                            L.view(f, name)[...] = L.view(pf, name)
-                        i[running_i64(L)] = pi[running_i64(L)]
-                        free.append(k)
-                        free.sort()
-                    else:
-                        f, i = backend.read_tallies_light() if light else backend.read_tallies()
-                    stats.extend(out_stats)
-                    empty_launches.extend(out_empty)
-                    species_spans.append((i_iter, i_ion, k, t0, t1))
-                    local_steps.append((i_iter, i_ion, int(i[i_h] + i[i_r]) - steps_seen))
-                    steps_seen = int(i[i_h] + i[i_r])
-                    G_f, G_i = f, i
-                    per_species.append((i_iter, i_ion, G_f, G_i))
-                    next_merge += 1
-                    start_ready(False)            # (a freed secondary takes its next species; the primary waits for the hook)
-                    if on_species_end is not None:
-                        on_species_end(i_iter, i_ion, G_f, G_i)
-                    start_ready(True)
-                    continue
-                running = [fu for _, fu in started.values() if not fu.done()]
-                wait(running, return_when=FIRST_COMPLETED)
-                for j in sorted(started):         # a species that raised: no more merges; the block's exit waits for the others
-                    if started[j][1].done() and started[j][1].exception() is not None:
-                        raise started[j][1].exception()
-
-    def species_transport(be, i_iter, i_ion, hook, out_stats, out_empty):
-        """begin_species .. the last pcut of species i_ion on context `be`; its pcuts go to out_stats / out_empty.  hook: the
-        before_pcut of this species (None: the fused loop where it applies)."""
-        sp = cfg.species[i_ion - 1]
-        pmax_cutoff = inputs.get_pmax_cutoff(prob.Emax_keV, prob.Emax_per_aa_keV, prob.pmax, sp.aa)
-        inj = inputs.init_pop_host(prob, i_ion)
-        zz = abs(sp.zz) if cfg.abs_charge else sp.zz
-        ewf = 1.0 / cfg.species[-1].density if cfg.species[-1].density != 0 else float("inf")
-        be.begin_species(i_iter, i_ion, sp.aa, zz, pmax_cutoff, sp.density, ewf)
-        if is_root:
-            be.set_fluxes(inj.pxx_flux, inj.pxz_flux, inj.energy_flux)
-        if multi:
-            if dev_t is not None:
-                if not is_root:   # per-species fills are baselines too
-                    for name in ("psd", "esc_psd_up", "esc_psd_down"):
-                        tview(dev_t[0], name).zero_()
-                if G_pool is not None:   # ions' donated energy, merged at the previous species end
-                    tview(dev_t[0], "energy_recv_pool").copy_(G_pool)
-            else:
-                f, i = be.read_tallies()
-                if not is_root:
-                    for name in ("psd", "esc_psd_up", "esc_psd_down"):
-                        L.view(f, name)[...] = 0.0
-                if G_pool is not None:
-                    L.view(f, "energy_recv_pool")[...] = G_pool
-                be.write_tallies(f, i)
-
-        n_total = inj.n_pts_use
-        # the shard: global index of local particle k = first + k * stride, or gidx[k] after a local split
-        first, stride, gidx = comm.rank, comm.world, None
-        n_local = (n_total - comm.rank + comm.world - 1) // comm.world if n_total > comm.rank else 0
-        if stride == 1:
-            be.init_pop(inj, 0, n_local, n_total)
-        else:
-            be.init_pop(inj, first, n_local, n_total, stride)
-        p_pcut_hi = inputs.pcut_hi(cfg.EN_PCUT_HI, sp.mass)
-        n_use_global = n_total
-        # One rank, no per-pcut hook: the whole pcut loop of the species is queued on the device at once -- n_saved, i_mult and
-        # the next population's size are decided there (mcs_run_pcuts_fused), one read-back per species instead of one per pcut.
-        fused = (fused_pcuts and not multi and hook is None and hasattr(be, "run_pcuts_fused") and n_pcuts >= 1
-                 and os.environ.get("MCS_FUSED_PCUTS", "1") != "0")
-        # Long histories told apart (long_draws > 0; MCS_LONG_DRAWS): the next population is ordered non-long before long, which lets a
-        # pcut's long histories finish beside the next pcut (mcs_run_pcuts_pipelined; one rank).  A backend without that entry point
-        # (the oracle) is told the order (set_long_draws) and runs the ordinary loop: same populations, same streams, same results.
-        if long_draws:
-            if multi:
-                raise ValueError("long_draws: the pipelined pcut loop and its population order are single-rank (one process per replica)")
-            if not hasattr(be, "run_pcuts_pipelined") and not hasattr(be, "set_long_draws"):
-                raise ValueError("long_draws: the backend can neither pipeline the pcuts nor order the population by history length")
-        pipelined = bool(long_draws) and hook is None and hasattr(be, "run_pcuts_pipelined") and n_pcuts >= 1 and not getattr(P, "state_fp32", 0)
-        if long_draws and not pipelined:
-            if not hasattr(be, "set_long_draws"):
-                raise ValueError("long_draws: this configuration runs the per-pcut loop, and the backend cannot order the population there")
-            be.set_long_draws(int(long_draws))
-        i_mult_prev = 0                 # (the rule of mcs_run_pcuts_pipelined for the per-pcut loop: see long_imult_max)
-        if pipelined:
-            fused = False
-            t0 = time.perf_counter()
-            targets = [cfg.N_PTS_PCUT if prob.pcuts[ip - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI for ip in range(1, n_pcuts + 1)]
-            n_use_a, n_saved_a, i_mult_a, ms_a, strag_a = be.run_pcuts_pipelined(1, n_pcuts, targets, int(long_draws), int(long_imult_max))
-            wall = (time.perf_counter() - t0) * 1e3
-            n_done = n_pcuts
-            for ip in range(1, n_pcuts + 1):
-                if int(n_saved_a[ip - 1]) == 0:
-                    n_done = ip
-                    break
-            for ip in range(1, n_done + 1):
-                nu, nsv, im = int(n_use_a[ip - 1]), int(n_saved_a[ip - 1]), int(i_mult_a[ip - 1])
-                out_stats.append(PcutStat(i_iter, i_ion, ip, nu, nsv, im if nsv > 0 else 0, nu, "-", float(ms_a[ip - 1]), wall / max(n_done, 1)))
-                if verbose and is_root:
-                    print(f"[iter {i_iter} ion {i_ion} pcut {ip:2d}] n_use={nu} n_saved={nsv} i_mult={im} kernel={ms_a[ip - 1]:.2f} ms "
-                          f"(pipelined: {int(strag_a[ip - 1][0])} long histories exported{', waited' if strag_a[ip - 1][1] else ''})", flush=True)
-        if fused:
-            t0 = time.perf_counter()
-            targets = [cfg.N_PTS_PCUT if prob.pcuts[ip - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI for ip in range(1, n_pcuts + 1)]
-            # (in chunks: a species that ends early -- the thermal electrons in their first pcut -- would otherwise pay ~35 us of
-            # empty launches for every remaining pcut; one read-back per chunk of 12 instead of one per pcut)
-            chunk = max(1, int(os.environ.get("MCS_FUSED_CHUNK", "12")))
-            n_use_a, n_saved_a, i_mult_a, ms_a = [], [], [], []
-            for c0 in range(1, n_pcuts + 1, chunk):
-                c1 = min(c0 + chunk - 1, n_pcuts)
-                a_, b_, c_, d_ = be.run_pcuts_fused(c0, c1, targets[c0 - 1:c1])
-                n_use_a.extend(a_); n_saved_a.extend(b_); i_mult_a.extend(c_); ms_a.extend(d_)
-                if min(b_) == 0:
-                    break
-            n_done = len(n_use_a)
-            wall = (time.perf_counter() - t0) * 1e3
-            for ip in range(1, n_done + 1):
-                nu, nsv, im = int(n_use_a[ip - 1]), int(n_saved_a[ip - 1]), int(i_mult_a[ip - 1])
-                last = nsv == 0 or ip == n_pcuts
-                out_stats.append(PcutStat(i_iter, i_ion, ip, nu, nsv, im if nsv > 0 else 0, nu, "-", float(ms_a[ip - 1]), wall / max(n_done, 1)))
-                if verbose and is_root:
-                    print(f"[iter {i_iter} ion {i_ion} pcut {ip:2d}] n_use={nu} n_saved={nsv} i_mult={im} kernel={ms_a[ip - 1]:.2f} ms (fused loop)", flush=True)
-                if last:
-                    out_empty.extend((i_iter, i_ion, jp, float(ms_a[jp - 1])) for jp in range(ip + 1, n_done + 1))
-                    break
-        for i_pcut in (() if (fused or pipelined) else range(1, n_pcuts + 1)):
-            t0 = time.perf_counter()
-            if hook is not None:
-                hook(i_iter, i_ion, i_pcut)
-            if long_draws and not pipelined:
-                be.set_long_draws(int(long_draws) if (i_pcut == 1 or long_imult_max <= 0 or i_mult_prev <= long_imult_max) else 0)
-            if gidx is not None:
-                n_saved_local = be.run_pcut_indexed(i_pcut, gidx)
-            else:
-                n_saved_local = be.run_pcut(i_pcut, first, stride)
-            gathered = comm.all_gather_ints([n_saved_local, n_local])
-            counts = [g[0] for g in gathered]
-            n_use_max = max(g[1] for g in gathered)
-            n_saved = sum(counts)
-            wall = (time.perf_counter() - t0) * 1e3
-            # pcut_finalize (src/cuts.jl:100-124)
-            i_mult = 0
-            if n_saved > 0:
-                n_target = cfg.N_PTS_PCUT if prob.pcuts[i_pcut - 1] < p_pcut_hi else cfg.N_PTS_PCUT_HI
-                i_mult = max(n_target // n_saved, 1)         # new_pcut, src/cuts.jl:42
-            i_mult_prev = i_mult
-            last = n_saved == 0 or i_pcut == n_pcuts
-            local_ok = not multi or (n_saved > gather_max and max(counts) * comm.world <= skew_max * n_saved)
-            st = PcutStat(i_iter, i_ion, i_pcut, n_use_global, n_saved, i_mult, n_use_max,
-                          "-" if last else ("local" if local_ok else "gather"), be.last_kernel_ms(), wall)
-            out_stats.append(st)
-            if verbose and is_root:
-                print(f"[iter {i_iter} ion {i_ion} pcut {i_pcut:2d}] n_use={n_use_global} (max local {n_use_max}) "
-                      f"n_saved={n_saved} i_mult={i_mult} split={st.split} kernel={be.last_kernel_ms():.2f} ms "
-                      f"wall={wall:.1f} ms", flush=True)
-            if n_saved == 0:
-                break
-            identity = multi and n_saved == n_use_global and i_mult == 1
-            n_prev_global = n_use_global                     # (every global index of the pcut just run is below this)
-            n_use_global = n_saved * i_mult
-            if identity:
-                # everybody was saved and nobody is replicated (the first pcuts of a species): the saved particles' positions
-                # in the global order ARE their indices, so every rank's children keep the global indices their parents had
-                # -- no index column to exchange, no particle to move; the shard description (first / stride / gidx) stands
-                be.new_pcut(1)
-                out_stats[-1].split = "identity"
-            elif not multi:
-                be.new_pcut(i_mult)                     # one process: the shard stays 0, 1, 2, ...
-                n_local = n_use_global
-            elif local_ok:
-                # every rank splits its own saved particles; the index column alone goes round
-                g_loc = be.saved_gidx()                                  # ascending, counts[rank] entries
-                cap = max(max(counts), 1)
-                # (padded with the largest integer: every row of the gathered table stays sorted; for each of my saved particles a
-                # searchsorted per peer row counts that rank's saved particles below it.  One row at a time, accumulated in place:
-                # the working set is O(n) -- round 3 searched all rows at once through an expanded [W, n] key matrix and an int64
-                # [W, n] result, 0.5 + 0.8 GB per rank and pcut at config[3]'s 1.25e7 particles per GPU)
-                # (the column travels as int32 while every index fits: half the bytes on the wire and in the search -- 4 B per saved
-                # particle per peer, 32 MB per rank and pcut at 10^6 particles per GPU on 8 GPUs)
-                idt = torch.int32 if n_prev_global < 2 ** 31 - 1 else torch.int64
-                g_key = g_loc.to(idt)
-                pad = torch.full((cap,), torch.iinfo(idt).max, dtype=idt, device=g_loc.device)
-                pad[:g_key.numel()] = g_key
-                g_all = comm.all_gather_rows(pad)                             # [W, cap]
-                pos = torch.zeros(g_key.numel(), dtype=torch.int64, device=g_loc.device)
-                for w in range(g_all.shape[0]):
-                    pos += torch.searchsorted(g_all[w], g_key)
-                gidx = (pos[:, None] * i_mult + torch.arange(i_mult, dtype=torch.int64, device=g_loc.device)[None, :]).reshape(-1).contiguous()
-                be.new_pcut(i_mult)
-                n_local = counts[comm.rank] * i_mult
-            else:
-                # all ranks see all parents (sorted by global index); rank r builds elements r, r+W, ... of the split
-                g, f64, meta = be.export_saved(max(max(counts), 1))
-                g = comm.all_gather_cols(g, counts)
-                f64 = comm.all_gather_cols(f64, counts)
-                meta = comm.all_gather_cols(meta, counts)
-                order = torch.argsort(g, stable=True)
-                f64 = f64.index_select(1, order).contiguous()
-                meta = meta.index_select(0, order).contiguous()
-                first, stride, gidx = comm.rank, comm.world, None
-                n_local = (n_use_global - comm.rank + comm.world - 1) // comm.world if n_use_global > comm.rank else 0
-                be.import_split(f64, meta, n_saved, i_mult, first, stride, n_local)
-
     for be in secondaries:          # (a context reused from an earlier call must add nothing stale)
-        zero_running_sums(be)
+        _zero_running_sums(L, be)
     for i_iter in range(first_iter, first_iter + n_itrs):
         backend.begin_iteration(i_iter)
-        if multi and not is_root:
-            if dev_t is not None:
-                dev_t[0].zero_()
+        if multi and not rs.is_root:
+            if rs.dev_t is not None:
+                rs.dev_t[0].zero_()
             else:
                 f, i = backend.read_tallies()
                 f[:] = 0.0
                 backend.write_tallies(f, i)
-        if secondaries:
-            concurrent_species(i_iter)
-        for i_ion, sp in (() if secondaries else enumerate(cfg.species, start=1)):
-            species_transport(backend, i_iter, i_ion, before_pcut, stats, empty_launches)
-
-            # species end: merge the partial tallies of all ranks (C1)
-            if multi and dev_t is not None:
-                backend.sync()          # the bound tensors are complete after mcs_sync (it folds the tally replicas in)
-                tf, ti = dev_t
-                local_steps.append((i_iter, i_ion, int(ti[i_h].item() + ti[i_r].item()) - steps_seen))
-                if not is_root:   # every rank carried a full copy of the received-energy pool
-                    tview(tf, "energy_recv_pool").zero_()
-                comm.all_reduce_sum_(tf)
-                comm.all_reduce_sum_(ti)
-                G_pool = tview(tf, "energy_transfer_pool").clone()
-                last_read = final_full_read and i_iter == first_iter + n_itrs - 1 and i_ion == len(cfg.species)
-                if species_tallies == "light" and not last_read:
-                    o_small = L.offsets["esc_psd_up"]
-                    G_f = np.zeros(L.total)
-                    G_f[o_small:] = tf[o_small:].cpu().numpy()
-                    G_i = ti.cpu().numpy()
-                else:
-                    G_f, G_i = tf.cpu().numpy(), ti.cpu().numpy()
-                steps_seen = int(G_i[i_h] + G_i[i_r]) if is_root else 0     # rank 0 carries the merged totals on
-                if not is_root:
-                    tf.zero_(); ti.zero_()
-            else:
-                last_read = final_full_read and i_iter == first_iter + n_itrs - 1 and i_ion == len(cfg.species)
-                light = species_tallies == "light" and not last_read and not multi and hasattr(backend, "read_tallies_light")
-                f, i = backend.read_tallies_light() if light else backend.read_tallies()
-                local_steps.append((i_iter, i_ion, int(i[i_h] + i[i_r]) - steps_seen))
-                steps_seen = int(i[i_h] + i[i_r])
-                if multi:
-                    if not is_root:
-                        L.view(f, "energy_recv_pool")[...] = 0.0
-                    tf, ti = torch.from_numpy(f), torch.from_numpy(i)
-                    comm.all_reduce_sum_(tf); comm.all_reduce_sum_(ti)
-                    G_f, G_i = f.copy(), i.copy()
-                    steps_seen = int(G_i[i_h] + G_i[i_r]) if is_root else 0
-                    G_pool = L.view(G_f, "energy_transfer_pool").copy()
-                    if is_root:
-                        backend.write_tallies(G_f, G_i)
-                    else:
-                        backend.write_tallies(np.zeros_like(G_f), np.zeros_like(G_i))
-                else:
-                    G_f, G_i = f, i
-            per_species.append((i_iter, i_ion, G_f, G_i))      # fresh host arrays: no copy needed
-            if on_species_end is not None:
-                on_species_end(i_iter, i_ion, G_f, G_i)
-
+        _iteration_species(rs, i_iter, before_pcut)
         if finalize:
             # ion_finalize of the last species (quirk Q2: only its fluxes and pressures reach iter_finalize) and
             # iter_finalize, on rank 0, whose device buffers hold the merged tallies
             changed = False
-            if is_root:
+            if rs.is_root:
                 ion_fin = consumers.ion_finalize(prob, backend, len(cfg.species))
-                fin = itf.iter_finalize(prob, it_state, sm, i_iter, G_f, L, ion_fin.P_psd_par, ion_fin.P_psd_perp,
-                                        ion_fin.energy_density_psd)
-                iter_finals.append((i_iter, fin, ion_fin))
+                fin = itf.iter_finalize(prob, it_state, sm, i_iter, rs.G_f, L, ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
+                rs.iter_finals.append((i_iter, fin, ion_fin))
                 changed = fin.profile_changed
             if multi and sm.smooth_shocks:
                 tabs = torch.from_numpy(np.stack([prob.ux, prob.gam_sf, prob.utot, prob.beta_ef, prob.gam_ef, prob.btot]))
@@ -632,7 +692,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                 changed = True
             if changed:
                 itf.populate_eps_target(prob)        # src/main_loops.jl:76-81, top of the next iteration
-                for be in [backend] + secondaries:
+                for be in rs.ctxs:
                     be.set_grid(prob)
                     be.set_cuts(prob)
         if tcut_print and P.do_tcuts:
@@ -640,21 +700,17 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             # coupled arrays of every species -- they are per-ion slices of one array).  The rewrite is applied to a COPY of the
             # buffer -- the entries already handed out in per_species / on_species_end stay the raw sums -- and on every rank, so
             # that all ranks return the same RunResult; only the root writes the device buffer.
-            from . import iter_finalize as _itf
-            G_f = G_f.copy()
-            wc, sc = L.view(G_f, "weight_coupled"), L.view(G_f, "spectra_coupled")
-            _itf.tcut_print(wc, sc, len(prob.tcuts), P.num_psd_mom_bins)
-            if is_root:
+            rs.G_f = rs.G_f.copy()
+            wc, sc = L.view(rs.G_f, "weight_coupled"), L.view(rs.G_f, "spectra_coupled")
+            itf.tcut_print(wc, sc, len(prob.tcuts), P.num_psd_mom_bins)
+            if rs.is_root:
                 backend.write_tally("weight_coupled", wc)
                 backend.write_tally("spectra_coupled", sc)
         if on_iteration_end is not None:
             on_iteration_end(i_iter)
 
-    ng = P.n_grid
-    from .capi import IC
-    return RunResult(G_f, G_i, per_species, stats,
-                     int(G_i[ng + IC["STEPS_HELIX"]]), int(G_i[ng + IC["STEPS_RETRO"]]), iter_finals,
-                     it_state if finalize else None, local_steps, empty_launches, species_spans)
+    return RunResult(rs.G_f, rs.G_i, rs.per_species, rs.stats, *_steps(rs.G_i, P.n_grid), rs.iter_finals, it_state,
+                     rs.local_steps, rs.empty_launches, rs.species_spans)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over
@@ -680,64 +736,40 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     lone-wave rate -- measured 254 ms per iteration against 275 with full-chip launches, which let the other launch in only
     as whole workgroups retire (tools/gpu_concurrent.py).
     Single process only (no communicator): collectives issued from two threads would need an order."""
-    import threading
-    from concurrent.futures import ThreadPoolExecutor
-    from . import consumers, iter_finalize as itf
     cfg, P = prob.cfg, prob.params
     n_itrs = n_itrs if n_itrs is not None else cfg.num_iterations
-    K = len(backends)
+    K, L = len(backends), backends[0].layout
     assert K >= 1
-    L = backends[0].layout
     sm = itf.SmoothingConfig(smooth_shocks=False)
     st = itf.IterState.create(prob, sm, P.n_itrs)
     locks = [threading.Lock() for _ in backends]
     if blocks_per_launch is None and K > 1 and hasattr(backends[0], "num_cus"):
         blocks_per_launch = max(2 * backends[0].num_cus() // K, 1)
-
-    state = {"busy": 0}
-    state_lock = threading.Lock()
+    busy = _ChipShare()                       # iterations in flight
 
     def one(i_iter):
         k = (i_iter - first_iter) % K
         with locks[k]:                       # a context carries one iteration at a time
             be = backends[k]
-            with state_lock:
-                state["busy"] += 1
-            geo = blocks_per_launch and K > 1 and hasattr(be, "set_launch")
-
-            def geometry(*_):
-                # decided before EVERY launch: an iteration that is alone on the chip (the last one of an odd count, once its
-                # neighbour has finished) gets the automatic full-chip geometry back
-                if geo:
-                    alone = state["busy"] <= 1
-                    be.set_launch(0 if alone else int(blocks_per_launch), 0 if alone else 256)
-            try:
+            busy.enter()
+            with busy.geometry(be, lambda n: blocks_per_launch if n > 1 else 0, bool(blocks_per_launch) and K > 1) as geometry:
                 # (long_draws=0: the pcuts are not pipelined here -- the other iterations' launches are what fills this one's tails, and
                 # the per-pcut hook needs the per-pcut loop; MCS_LONG_DRAWS does not reach this call)
                 res = run(prob, be, None, n_itrs=1, max_pcuts=max_pcuts, first_iter=i_iter, species_tallies="light", final_full_read=False,
                           before_pcut=geometry, long_draws=0)
                 ion_fin = consumers.ion_finalize(prob, be, len(cfg.species))     # K4, before the context is reused
-            finally:
-                with state_lock:
-                    state["busy"] -= 1
-                if geo:
-                    be.set_launch(0, 0)      # back to the automatic geometry, also when the iteration raised
         return k, res, ion_fin
 
     stats, per_species, iter_finals, local_steps = [], [], [], []
     last = {}                                 # context -> its latest result (running totals of the never-reset tallies)
-    from .capi import IC
     ng = P.n_grid
-    total = []                                # the step counters are running totals of a context: where each one starts
-    for be in backends:
-        i0 = be.read_counters() if hasattr(be, "read_counters") else be.read_tallies()[1]
-        total.append(int(i0[ng + IC["STEPS_HELIX"]] + i0[ng + IC["STEPS_RETRO"]]))
+    # the step counters are running totals of a context: where each one starts
+    total = [sum(_steps(_read_counters(be), ng)) for be in backends]
     with ThreadPoolExecutor(max_workers=K) as pool:
         futs = [pool.submit(one, i) for i in range(first_iter, first_iter + n_itrs)]
         for i_iter, fu in zip(range(first_iter, first_iter + n_itrs), futs):      # consumed in iteration order
             k, res, ion_fin = fu.result()
-            fin = itf.iter_finalize(prob, st, sm, i_iter, res.tallies_f64, L, ion_fin.P_psd_par, ion_fin.P_psd_perp,
-                                    ion_fin.energy_density_psd)
+            fin = itf.iter_finalize(prob, st, sm, i_iter, res.tallies_f64, L, ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
             local_steps.append((i_iter, len(cfg.species), res.steps_helix + res.steps_retro - total[k]))
             total[k] = res.steps_helix + res.steps_retro
             last[k] = res
@@ -750,10 +782,8 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     for k in last:
         if k == k_last:
             continue
-        fk, ik = (backends[k].read_tallies_light() if hasattr(backends[k], "read_tallies_light") else backends[k].read_tallies())
+        fk, ik = _read_light(backends[k])
         for name in ACCUMULATED_OVER_ITERATIONS:
             L.view(f, name)[...] += L.view(fk, name)
         i64[ng:] += ik[ng:]                   # the event counters are running totals too (num_crossings is per species)
-    return RunResult(f, i64, per_species, stats, int(i64[ng + IC["STEPS_HELIX"]]), int(i64[ng + IC["STEPS_RETRO"]]),
-                     iter_finals, st, local_steps)
-
+    return RunResult(f, i64, per_species, stats, *_steps(i64, ng), iter_finals, st, local_steps)
