@@ -1,11 +1,15 @@
 // mcs_api.hip -- the C ABI of include/mcs.h over the gfx950 kernels.
 //
 // A context owns: device mirrors of the grid/cut tables, the resident particle
-// population (two SoA buffers: current and saved) and, unless the caller binds its
-// own (mcs_bind_tallies), the flat fp64/int64 tally buffers.  All work is queued
-// on ONE HIP stream; mcs_run_pcut is synchronous only for the 8-byte n_saved.
-// There is no CPU code path in this library.
+// population (three rotating SoA buffers: current, saved and the target of the next
+// split; a second saved set for the pipelined loop) and, unless the caller binds its
+// own (mcs_bind_tallies), the flat fp64/int64 tally buffers.  Every block of memory,
+// stream and event is a member of an owning type of mcs_hip_owned.h: deleting the
+// context releases them, a failed allocation leaves its owner empty.  All work is
+// queued on ONE HIP stream (the pipelined loop adds a side stream); mcs_run_pcut is
+// synchronous only for the 8-byte n_saved.  There is no CPU code path in this library.
 #include "mcs_device.h"
+#include "mcs_hip_owned.h"
 #include "../../include/mcs_ic.h"
 
 #include <cmath>
@@ -15,6 +19,10 @@
 #include <string>
 #include <vector>
 #include <chrono>
+#include <climits>
+#include <cstdarg>
+#include <memory>
+#include <utility>
 
 extern "C" {
 int mcs_transport_max_entries(void);
@@ -73,28 +81,48 @@ int fail(const std::string& msg) { g_err = msg; return 1; }
     if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));    \
   } while (0)
 
-struct PopBuf {
+std::string format(const char* f, ...) {
+  char b[320];
+  va_list ap; va_start(ap, f); std::vsnprintf(b, sizeof b, f, ap); va_end(ap);
+  return b;
+}
+// reserve() of a DevBuf, PinnedBuf or PopBuf as a step of an ABI call
+template <class B> int reserve(B& b, long long n) {
+  const hipError_t e = b.reserve(n);
+  return e == hipSuccess ? 0 : fail(std::string(B::alloc_name()) + ": " + hipGetErrorString(e));
+}
+
+// the eight fp64 fields of a particle, in the order of PopBuf::f
+constexpr double* DevPop::*kPopF64[8] = {&DevPop::weight, &DevPop::ptot_pf, &DevPop::pb_pf, &DevPop::x_PT_cm,
+                                         &DevPop::xn_per, &DevPop::prp_x_cm, &DevPop::acctime_sec, &DevPop::phi_rad};
+constexpr double* mcs_soa::*kSoaF64[8] = {&mcs_soa::weight, &mcs_soa::ptot_pf, &mcs_soa::pb_pf, &mcs_soa::x_PT_cm,
+                                          &mcs_soa::xn_per, &mcs_soa::prp_x_cm, &mcs_soa::acctime_sec, &mcs_soa::phi_rad};
+// what the kernels take: the arrays of b, from particle `first` on
+DevPop pop_view(const PopBuf& b, long long first = 0) {
   DevPop d{};
-  long long cap = 0;
-};
+  for (int i = 0; i < 8; ++i) d.*kPopF64[i] = b.f[i] + first;
+  d.meta = b.meta + first;
+  return d;
+}
 }  // namespace
 
 struct mcs_ctx {
   mcs_params P;
   mcs_layout L;
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  Stream own_stream;           // (first member: destroyed after everything that was used on it)
+  hipStream_t stream = nullptr;     // own_stream, or the caller's
   // tables
-  double* d_tab = nullptr;     // 8 tables x (n_grid+2)
-  double* d_cuts = nullptr;    // pcuts | tcuts | x_spec | inj_fracs | eps_target
+  DevBuf<double> d_tab;        // 8 tables x (n_grid+2)
+  DevBuf<double> d_cuts;       // pcuts | tcuts | x_spec | inj_fracs | eps_target
   DevTables tb{};
   std::vector<double> h_inj_fracs, h_pcuts, h_ux;
   // tallies
-  double* d_T = nullptr; unsigned long long* d_I = nullptr; bool own_T = false, own_I = false;
+  DevBuf<double> own_T; DevBuf<unsigned long long> own_I;
+  double* d_T = nullptr; unsigned long long* d_I = nullptr;      // own_T / own_I, or the caller's (mcs_bind_tallies)
   // population
   PopBuf cur, sav, spare;      // spare: target of the next split (buffers rotate, no per-pcut allocation)
-  uint8_t* d_lsave = nullptr; long long lsave_cap = 0;
+  DevBuf<uint8_t> d_lsave;
   long long n = 0;             // current population size
   long long n_saved_last = 0;
   long long n_run_last = 0;    // population size of the last mcs_run_pcut (the saved arrays and src[] refer to it)
@@ -106,7 +134,7 @@ struct mcs_ctx {
   // exports its live particles and ends; the host relaunches them, spread over the chip's waves, until none is left
   int tail_budget = 0;         // trips; 0 = one launch per pcut, run to the end
   int tail_rounds_last = 0;    // launches the last mcs_run_pcut* took
-  double* d_strag[2] = {nullptr, nullptr}; long long strag_cap = 0;
+  DevBuf<double> d_strag[2]; long long strag_cap = 0;
   bool f32_exact = false;      // MCS_F32_EXACT=1: the plain loop with the exact fp32 primitives (include/mcs_math_f32.h): the kernel the CPU restatement
                                // oracle/mcs_oracle_f32.inc reproduces bit for bit (tests)
   bool f32_loop = false;       // MCS_F32_LOOP=1: the fp32-state variant as a plain per-lane loop (the reference semantics of that variant; tests)
@@ -115,22 +143,22 @@ struct mcs_ctx {
   int refill_min = 12;         // MCS_REFILL_MIN=<n> (environment) overrides: A/B measurements
   int defer_k = 8;             // MCS_DEFER_K=<n> (environment) overrides: A/B measurements, 1 = no deferral
   // finals
-  int32_t *f_reason = nullptr, *f_helix = nullptr, *f_retro = nullptr; double *f_ptot = nullptr, *f_x = nullptr;
+  DevBuf<int32_t> f_reason, f_helix, f_retro; DevBuf<double> f_ptot, f_x;
   long long f_cap = 0;
   // scan scratch
-  unsigned int* d_bcounts = nullptr; unsigned long long* d_boffs = nullptr; long long* d_src = nullptr; long long scan_cap = 0;
-  double* d_tally_rep = nullptr;               // replicas of the histograms at the head of the tally buffer (KArgs::tally_rep)
+  DevBuf<unsigned int> d_bcounts; DevBuf<unsigned long long> d_boffs; DevBuf<long long> d_src; long long scan_cap = 0;
+  DevBuf<double> d_tally_rep;                  // replicas of the histograms at the head of the tally buffer (KArgs::tally_rep)
   long long rep_n = 0;                         // doubles per replica (0: no replicas)
   bool rep_dirty = false;                    // a launch may have added to the replicas since the last fold
   bool tally_replicas = true;                  // MCS_TALLY_REPLICAS_OFF=1: tally straight into T
   bool park = true;                           // MCS_PARK=0: lanes that need the full Code Blocks run them at once (A/B measurements)
-  unsigned long long* d_counters = nullptr;   // [0] work counter, [1] n_saved, [2] scan total
+  DevBuf<unsigned long long> d_counters;      // [0] work counter, [1] n_saved, [2] scan total
   // staging for init_pop
-  double* d_stage = nullptr; long long stage_cap = 0;
+  DevBuf<double> d_stage;
   // launch constants: host copy in PINNED memory (the upload is then a true async copy: no staging through the runtime's
   // bounce buffer, ~10 us per pcut) and device copy; read-back words of a pcut, pinned for the same reason
-  KArgs* h_args_pin = nullptr; KArgs* d_args = nullptr;
-  unsigned long long* h_back = nullptr;       // [0..1] n_saved | count of l_save flags, [2] exported particles of a sliced run
+  PinnedBuf<KArgs> h_args_pin; DevBuf<KArgs> d_args;
+  PinnedBuf<unsigned long long> h_back;       // [0..1] n_saved | count of l_save flags, [2] exported particles of a sliced run
   // species
   int i_iter = 1, i_ion = 1;
   double aa = 1, zzq = MCS_QCGS, m = MCS_MP, mc = MCS_MP * MCS_C, pmax_cutoff = 0, density = 1, ewf = 1;
@@ -140,20 +168,20 @@ struct mcs_ctx {
   int kernel_last = -1;        // mcs_last_kernel
   // fused species loop (mcs_run_pcuts_fused): launch constants of every pcut (pinned + device), the per-pcut words decided on the
   // device, one event pair per pcut
-  KArgs* h_fargs = nullptr; KArgs* d_fargs = nullptr; PcutDev* d_pd = nullptr; PcutDev* h_pd = nullptr; int fused_cap = 0;
-  std::vector<hipEvent_t> f_ev;
+  PinnedBuf<KArgs> h_fargs; DevBuf<KArgs> d_fargs; DevBuf<PcutDev> d_pd; PinnedBuf<PcutDev> h_pd; int fused_cap = 0;
+  std::vector<Event> f_ev;
   // pipelined pcut loop (mcs_run_pcuts_pipelined): the side stream on which a pcut's long histories finish while the next pcut runs,
   // the second set of saved arrays / status bytes (pcut p's are still written while pcut p + 1 runs), the late group's scan scratch,
   // per-launch counters (device, and pinned for the one read-back per pcut), three launch-constant slots, the late group's sizes
-  hipStream_t pp_s2 = nullptr; hipEvent_t pp_reset = nullptr;
+  Stream pp_s2; Event pp_reset;
   // ... and, when the runtime grants them, two streams with complementary CU masks: the side stream's waves then have their SIMDs to
   // themselves (beside a wave of the main launch on the same SIMD a long history advances at half the speed -- the kernel is issue-bound
   // -- and the side chain, not the main launch, ends the pcut); a pcut with side work runs its main launch on the masked main stream
-  hipStream_t pp_s1m = nullptr, pp_s2m = nullptr; int pp_side_cus = 12;      // MCS_PIPE_SIDE_CUS=<n> (0: no masks)
-  PopBuf pp_sav2; uint8_t* pp_lsave2 = nullptr; long long pp_cap = 0;
-  unsigned int* pp_bcounts = nullptr; unsigned long long* pp_boffs = nullptr; long long* pp_src = nullptr;
-  unsigned long long* pp_dpc = nullptr; unsigned long long* pp_hpc = nullptr;
-  KArgs* pp_hargs = nullptr; KArgs* pp_dargs = nullptr; PcutDev* pp_dpdl = nullptr; PcutDev* pp_hpdl = nullptr;
+  Stream pp_s1m, pp_s2m; bool pp_masks_tried = false; int pp_side_cus = 12;      // MCS_PIPE_SIDE_CUS=<n> (0: no masks)
+  PopBuf pp_sav2; DevBuf<uint8_t> pp_lsave2; long long pp_cap = 0;
+  DevBuf<unsigned int> pp_bcounts; DevBuf<unsigned long long> pp_boffs; DevBuf<long long> pp_src;
+  DevBuf<unsigned long long> pp_dpc; PinnedBuf<unsigned long long> pp_hpc;
+  PinnedBuf<KArgs> pp_hargs; DevBuf<KArgs> pp_dargs; DevBuf<PcutDev> pp_dpdl; PinnedBuf<PcutDev> pp_hpdl;
   int pp_waits_last = 0;       // pcuts of the last pipelined run whose i_mult had to wait for the long histories
   bool force_general = false;  // MCS_FORCE_GENERAL=1: always the general kernel (tests compare the two)
   int k1_ws = 2;               // the wave-specialised kernels (mcs_transport_ws.inc), where they apply: MCS_K1_WS=1 always, =0 never, default (2)
@@ -161,85 +189,53 @@ struct mcs_ctx {
                                // faster at 1e7 and 7 % slower at 2e6, where its missing tail consolidation shows (profiles/r04_ws_kernel_ab.txt)
   long long ws_auto_min = 6000000;   // MCS_WS_AUTO_MIN=<n>
   // consumers (K4): table staging, outputs, thermo scratch slab
-  double* d_ctab = nullptr; double* d_cout = nullptr; double* d_cscratch = nullptr; unsigned long long* d_cdiag = nullptr;
-  double* d_c2d = nullptr; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
+  DevBuf<double> d_ctab, d_cout, d_cscratch; DevBuf<unsigned long long> d_cdiag;
+  DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
   // launch
   int blocks = 0, threads = 256;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t acc_ev = nullptr;  // mcs_accumulate_tallies: orders the two contexts' streams (no timing; ev0 / ev1 time K1)
+  Event ev0, ev1;
+  Event acc_ev;                 // mcs_accumulate_tallies: orders the two contexts' streams (no timing; ev0 / ev1 time K1)
   double last_ms = 0.0;
   int n_cu = 256;
 };
 
 namespace {
 
-int pop_alloc(mcs_ctx* c, PopBuf& b, long long cap) {
-  if (cap <= b.cap) return 0;
-  double** f[8] = {&b.d.weight, &b.d.ptot_pf, &b.d.pb_pf, &b.d.x_PT_cm, &b.d.xn_per, &b.d.prp_x_cm, &b.d.acctime_sec, &b.d.phi_rad};
-  for (auto pp : f) { if (*pp) HIPCHK(hipFree(*pp)); *pp = nullptr; HIPCHK(hipMalloc((void**)pp, (size_t)cap * sizeof(double))); }
-  if (b.d.meta) HIPCHK(hipFree(b.d.meta));
-  HIPCHK(hipMalloc((void**)&b.d.meta, (size_t)cap * sizeof(uint32_t)));
-  b.cap = cap;
-  return 0;
-}
-void pop_free(PopBuf& b) {
-  double* f[8] = {b.d.weight, b.d.ptot_pf, b.d.pb_pf, b.d.x_PT_cm, b.d.xn_per, b.d.prp_x_cm, b.d.acctime_sec, b.d.phi_rad};
-  for (auto p : f) if (p) (void)hipFree(p);
-  if (b.d.meta) (void)hipFree(b.d.meta);
-  b = PopBuf{};
-}
-
 int ensure_capacity(mcs_ctx* c, long long n) {
   // both buffers and every per-particle side array hold at least n entries
-  if (n > c->cur.cap || n > c->sav.cap) {
-    long long cap = n + n / 8 + 1024;
+  if (n > c->cur.cap() || n > c->sav.cap()) {
+    const long long cap = grow_cap(n);
     // growing must preserve the current population
-    if (c->n > 0 && c->cur.cap < cap) {
+    if (c->n > 0 && c->cur.cap() < cap) {
       PopBuf nb;
-      if (pop_alloc(c, nb, cap)) return 1;
-      double* src[8] = {c->cur.d.weight, c->cur.d.ptot_pf, c->cur.d.pb_pf, c->cur.d.x_PT_cm, c->cur.d.xn_per, c->cur.d.prp_x_cm, c->cur.d.acctime_sec, c->cur.d.phi_rad};
-      double* dst[8] = {nb.d.weight, nb.d.ptot_pf, nb.d.pb_pf, nb.d.x_PT_cm, nb.d.xn_per, nb.d.prp_x_cm, nb.d.acctime_sec, nb.d.phi_rad};
-      for (int i = 0; i < 8; ++i) HIPCHK(hipMemcpyAsync(dst[i], src[i], (size_t)c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(nb.d.meta, c->cur.d.meta, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+      if (reserve(nb, cap)) return 1;
+      for (int i = 0; i < 8; ++i) HIPCHK(hipMemcpyAsync(nb.f[i], c->cur.f[i], (size_t)c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(nb.meta, c->cur.meta, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
-      pop_free(c->cur);
-      c->cur = nb;
-    } else if (pop_alloc(c, c->cur, cap)) return 1;
-    if (pop_alloc(c, c->sav, cap)) return 1;
+      c->cur = std::move(nb);
+    } else if (reserve(c->cur, cap)) return 1;
+    if (reserve(c->sav, cap)) return 1;
   }
-  if (n > c->lsave_cap) {
-    long long cap = n + n / 8 + 1024;
-    if (c->d_lsave) HIPCHK(hipFree(c->d_lsave));
-    HIPCHK(hipMalloc((void**)&c->d_lsave, (size_t)cap));
-    c->lsave_cap = cap;
-  }
+  if (n > c->d_lsave.cap() && reserve(c->d_lsave, grow_cap(n))) return 1;
   if (c->debug_finals && n > c->f_cap) {
-    long long cap = n + n / 8 + 1024;
-    if (c->f_reason) { (void)hipFree(c->f_reason); (void)hipFree(c->f_helix); (void)hipFree(c->f_retro); (void)hipFree(c->f_ptot); (void)hipFree(c->f_x); }
-    HIPCHK(hipMalloc((void**)&c->f_reason, (size_t)cap * 4)); HIPCHK(hipMalloc((void**)&c->f_helix, (size_t)cap * 4));
-    HIPCHK(hipMalloc((void**)&c->f_retro, (size_t)cap * 4)); HIPCHK(hipMalloc((void**)&c->f_ptot, (size_t)cap * 8));
-    HIPCHK(hipMalloc((void**)&c->f_x, (size_t)cap * 8));
+    const long long cap = grow_cap(n);
+    c->f_cap = 0;
+    reset_all(c->f_reason, c->f_helix, c->f_retro, c->f_ptot, c->f_x);
+    if (reserve(c->f_reason, cap) || reserve(c->f_helix, cap) || reserve(c->f_retro, cap) || reserve(c->f_ptot, cap) || reserve(c->f_x, cap)) return 1;
     c->f_cap = cap;
   }
   if (n > c->scan_cap) {
-    long long cap = n + n / 8 + 1024;
-    long long nb = (cap + 1023) / 1024;
-    if (c->d_bcounts) { (void)hipFree(c->d_bcounts); (void)hipFree(c->d_boffs); (void)hipFree(c->d_src); }
-    HIPCHK(hipMalloc((void**)&c->d_bcounts, (size_t)nb * sizeof(unsigned int)));
-    HIPCHK(hipMalloc((void**)&c->d_boffs, (size_t)nb * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc((void**)&c->d_src, (size_t)cap * sizeof(long long)));
+    const long long cap = grow_cap(n);
+    const long long nb = (cap + 1023) / 1024;
+    c->scan_cap = 0;
+    reset_all(c->d_bcounts, c->d_boffs, c->d_src);
+    if (reserve(c->d_bcounts, nb) || reserve(c->d_boffs, nb) || reserve(c->d_src, cap)) return 1;
     c->scan_cap = cap;
   }
   return 0;
 }
 
-int ensure_stage(mcs_ctx* c, long long n_doubles) {
-  if (n_doubles <= c->stage_cap) return 0;
-  if (c->d_stage) HIPCHK(hipFree(c->d_stage));
-  HIPCHK(hipMalloc((void**)&c->d_stage, (size_t)n_doubles * sizeof(double)));
-  c->stage_cap = n_doubles;
-  return 0;
-}
+int ensure_stage(mcs_ctx* c, long long n_doubles) { return reserve(c->d_stage, n_doubles); }
 
 int fill(mcs_ctx* c, long long off, long long n, double v) {
   HIPCHK(mcs_launch_fill(c->d_T + off, n, v, c->stream));
@@ -247,22 +243,18 @@ int fill(mcs_ctx* c, long long off, long long n, double v) {
 }
 
 // host <-> packed device SoA
-int upload_soa(mcs_ctx* c, PopBuf& b, long long n, const mcs_soa* h) {
-  const double* src[8] = {h->weight, h->ptot_pf, h->pb_pf, h->x_PT_cm, h->xn_per, h->prp_x_cm, h->acctime_sec, h->phi_rad};
-  double* dst[8] = {b.d.weight, b.d.ptot_pf, b.d.pb_pf, b.d.x_PT_cm, b.d.xn_per, b.d.prp_x_cm, b.d.acctime_sec, b.d.phi_rad};
-  for (int i = 0; i < 8; ++i) HIPCHK(hipMemcpyAsync(dst[i], src[i], (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+int upload_soa(mcs_ctx* c, const PopBuf& b, long long n, const mcs_soa* h) {
+  for (int i = 0; i < 8; ++i) HIPCHK(hipMemcpyAsync(b.f[i], h->*kSoaF64[i], (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   std::vector<uint32_t> meta((size_t)n);
   for (long long k = 0; k < n; ++k) meta[k] = mcs_pack_meta((int)h->grid[k], (int)h->tcut[k], h->downstream[k] != 0, h->inj[k] != 0);
-  HIPCHK(hipMemcpyAsync(b.d.meta, meta.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(b.meta, meta.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 int download_soa(mcs_ctx* c, const PopBuf& b, long long n, mcs_soa* h) {
-  double* dst[8] = {h->weight, h->ptot_pf, h->pb_pf, h->x_PT_cm, h->xn_per, h->prp_x_cm, h->acctime_sec, h->phi_rad};
-  const double* src[8] = {b.d.weight, b.d.ptot_pf, b.d.pb_pf, b.d.x_PT_cm, b.d.xn_per, b.d.prp_x_cm, b.d.acctime_sec, b.d.phi_rad};
-  for (int i = 0; i < 8; ++i) HIPCHK(hipMemcpyAsync(dst[i], src[i], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  for (int i = 0; i < 8; ++i) HIPCHK(hipMemcpyAsync(h->*kSoaF64[i], b.f[i], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   std::vector<uint32_t> meta((size_t)n);
-  HIPCHK(hipMemcpyAsync(meta.data(), b.d.meta, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(meta.data(), b.meta, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (long long k = 0; k < n; ++k) {
     const uint32_t mm = meta[k];
@@ -301,64 +293,50 @@ int mcs_create(const mcs_params* p, int device, void* stream, mcs_ctx** out) {
   if (ndev <= 0) return fail("mcs_create: no HIP device visible; the transport path has no CPU fallback");
   if (device < 0 || device >= ndev) return fail("mcs_create: device ordinal out of range");
   HIPCHK(hipSetDevice(device));
-  mcs_ctx* c = new mcs_ctx();
-  // from here on a failing HIP call must not leak the context and what it has allocated so far
-#define CRCHK(expr)                                                                          \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      const std::string m_ = std::string(#expr) + ": " + hipGetErrorString(e_);              \
-      (void)mcs_destroy(c);                                                                  \
-      return fail(m_);                                                                       \
-    }                                                                                        \
-  } while (0)
-  { const char* e = std::getenv("MCS_FORCE_GENERAL"); c->force_general = e && e[0] == '1'; }
-  { const char* e = std::getenv("MCS_TAIL_MERGE"); c->tail_merge = !(e && e[0] == '0'); }
-  { const char* e = std::getenv("MCS_K1_WS"); c->k1_ws = !e ? 2 : (e[0] == '1' ? 1 : (e[0] == '0' ? 0 : 2)); }
-  { const char* e = std::getenv("MCS_WS_AUTO_MIN"); if (e && std::atoll(e) >= 0) c->ws_auto_min = std::atoll(e); }
-  { const char* e = std::getenv("MCS_PARK"); c->park = !(e && e[0] == '0'); }
-  { const char* e = std::getenv("MCS_TAIL_RING"); c->tail_ring = !(e && e[0] == '0'); }
-  { const char* e = std::getenv("MCS_TAIL_LOOP"); if (e && std::atoi(e) >= 0 && std::atoi(e) <= 32) c->tail_loop = std::atoi(e); }
-  { const char* e = std::getenv("MCS_F32_LOOP"); c->f32_loop = e && e[0] == '1'; }
-  { const char* e = std::getenv("MCS_F32_EXACT"); c->f32_exact = e && e[0] == '1'; }
-  { const char* e = std::getenv("MCS_TAIL_BUDGET"); if (e && std::atoi(e) >= 0) c->tail_budget = std::atoi(e); }
-  { const char* e = std::getenv("MCS_PIPE_SIDE_CUS"); if (e && std::atoi(e) >= 0 && std::atoi(e) <= 128) c->pp_side_cus = std::atoi(e); }
-  { const char* e = std::getenv("MCS_REFILL_MIN"); if (e && std::atoi(e) >= 1 && std::atoi(e) <= 48) c->refill_min = std::atoi(e); }
-  { const char* e = std::getenv("MCS_DEFER_K"); if (e && std::atoi(e) >= 1 && std::atoi(e) <= 40) c->defer_k = std::atoi(e); }
+  std::unique_ptr<mcs_ctx> c(new mcs_ctx());      // (a failing call below must not leak the context and what it has allocated so far)
+  c->force_general = env_on("MCS_FORCE_GENERAL");
+  c->tail_merge = env_not_off("MCS_TAIL_MERGE");
+  c->k1_ws = env_tristate("MCS_K1_WS");
+  c->ws_auto_min = env_int("MCS_WS_AUTO_MIN", 0, LLONG_MAX, c->ws_auto_min);
+  c->park = env_not_off("MCS_PARK");
+  c->tail_ring = env_not_off("MCS_TAIL_RING");
+  c->tail_loop = (int)env_int("MCS_TAIL_LOOP", 0, 32, c->tail_loop);
+  c->f32_loop = env_on("MCS_F32_LOOP");
+  c->f32_exact = env_on("MCS_F32_EXACT");
+  c->tail_budget = (int)env_int("MCS_TAIL_BUDGET", 0, INT_MAX, c->tail_budget);
+  c->pp_side_cus = (int)env_int("MCS_PIPE_SIDE_CUS", 0, 128, c->pp_side_cus);
+  c->refill_min = (int)env_int("MCS_REFILL_MIN", 1, 48, c->refill_min);
+  c->defer_k = (int)env_int("MCS_DEFER_K", 1, 40, c->defer_k);
+  c->tally_replicas = !env_on("MCS_TALLY_REPLICAS_OFF");
   c->P = *p;
   mcs_tally_layout(p, &c->L);
   c->device = device;
-  if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
-  else { CRCHK(hipStreamCreate(&c->stream)); c->own_stream = true; }
+  if (stream) c->stream = (hipStream_t)stream;
+  else { HIPCHK(c->own_stream.create()); c->stream = c->own_stream; }
   hipDeviceProp_t prop;
-  CRCHK(hipGetDeviceProperties(&prop, device));
+  HIPCHK(hipGetDeviceProperties(&prop, device));
   c->n_cu = prop.multiProcessorCount;
   const int ne = p->n_grid + 2;
-  CRCHK(hipMalloc((void**)&c->d_tab, (size_t)8 * ne * sizeof(double)));
-  CRCHK(hipMalloc((void**)&c->d_counters, 8 * sizeof(unsigned long long)));
-  CRCHK(hipMalloc((void**)&c->d_args, sizeof(KArgs)));
-  CRCHK(hipHostMalloc((void**)&c->h_args_pin, sizeof(KArgs)));
-  CRCHK(hipHostMalloc((void**)&c->h_back, 4 * sizeof(unsigned long long)));
-  { const char* e = std::getenv("MCS_TALLY_REPLICAS_OFF"); c->tally_replicas = !(e && e[0] == '1'); }
+  if (reserve(c->d_tab, (long long)8 * ne) || reserve(c->d_counters, 8) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1) ||
+      reserve(c->h_back, 4))
+    return 1;
   if (c->tally_replicas) {
     c->rep_n = c->L.total;     // the whole tally buffer: the three big histograms are 99 % of it
     const size_t nrep = (size_t)MCS_TALLY_REPLICAS * (size_t)c->rep_n;
-    CRCHK(hipMalloc((void**)&c->d_tally_rep, nrep * sizeof(double)));
-    CRCHK(hipMemsetAsync(c->d_tally_rep, 0, nrep * sizeof(double), c->stream));
+    if (reserve(c->d_tally_rep, (long long)nrep)) return 1;
+    HIPCHK(hipMemsetAsync(c->d_tally_rep, 0, nrep * sizeof(double), c->stream));
   }
-  CRCHK(hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), c->stream));
-  c->own_T = c->own_I = true;      // (before the allocations: mcs_destroy on a failure below frees whichever exists)
-  CRCHK(hipMalloc((void**)&c->d_T, (size_t)c->L.total * sizeof(double)));
-  CRCHK(hipMalloc((void**)&c->d_I, (size_t)mcs_i64_total(p) * sizeof(unsigned long long)));
-  CRCHK(hipMemsetAsync(c->d_T, 0, (size_t)c->L.total * sizeof(double), c->stream));
-  CRCHK(hipMemsetAsync(c->d_I, 0, (size_t)mcs_i64_total(p) * sizeof(unsigned long long), c->stream));
-  CRCHK(hipEventCreate(&c->ev0));
-  CRCHK(hipEventCreate(&c->ev1));
-  CRCHK(hipEventCreateWithFlags(&c->acc_ev, hipEventDisableTiming));
+  HIPCHK(hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), c->stream));
+  if (reserve(c->own_T, c->L.total) || reserve(c->own_I, mcs_i64_total(p))) return 1;
+  c->d_T = c->own_T; c->d_I = c->own_I;
+  HIPCHK(hipMemsetAsync(c->d_T, 0, (size_t)c->L.total * sizeof(double), c->stream));
+  HIPCHK(hipMemsetAsync(c->d_I, 0, (size_t)mcs_i64_total(p) * sizeof(unsigned long long), c->stream));
+  HIPCHK(c->ev0.create());
+  HIPCHK(c->ev1.create());
+  HIPCHK(c->acc_ev.create_untimed());
 
-  CRCHK(hipStreamSynchronize(c->stream));
-#undef CRCHK
-  *out = c;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *out = c.release();
   return 0;
 }
 
@@ -366,33 +344,6 @@ int mcs_destroy(mcs_ctx* c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  pop_free(c->cur); pop_free(c->sav); pop_free(c->spare);
-  void* ptrs[] = {c->d_tab, c->d_cuts, c->d_lsave, c->f_reason, c->f_helix, c->f_retro, c->f_ptot, c->f_x,
-                  c->d_bcounts, c->d_boffs, c->d_src, c->d_counters, c->d_stage, c->d_args, c->d_tally_rep,
-                  c->d_ctab, c->d_cout, c->d_cscratch, c->d_cdiag, c->d_strag[0], c->d_strag[1], c->d_c2d};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (c->own_T && c->d_T) (void)hipFree(c->d_T);
-  if (c->own_I && c->d_I) (void)hipFree(c->d_I);
-  if (c->h_args_pin) (void)hipHostFree(c->h_args_pin);
-  if (c->h_back) (void)hipHostFree(c->h_back);
-  if (c->h_fargs) (void)hipHostFree(c->h_fargs);
-  if (c->h_pd) (void)hipHostFree(c->h_pd);
-  if (c->d_fargs) (void)hipFree(c->d_fargs);
-  if (c->d_pd) (void)hipFree(c->d_pd);
-  pop_free(c->pp_sav2);
-  { void* pq[] = {c->pp_lsave2, c->pp_bcounts, c->pp_boffs, c->pp_src, c->pp_dpc, c->pp_dargs, c->pp_dpdl}; for (void* q : pq) if (q) (void)hipFree(q); }
-  if (c->pp_hpc) (void)hipHostFree(c->pp_hpc);
-  if (c->pp_hargs) (void)hipHostFree(c->pp_hargs);
-  if (c->pp_hpdl) (void)hipHostFree(c->pp_hpdl);
-  if (c->pp_reset) (void)hipEventDestroy(c->pp_reset);
-  if (c->pp_s2) (void)hipStreamDestroy(c->pp_s2);
-  if (c->pp_s1m) (void)hipStreamDestroy(c->pp_s1m);
-  if (c->pp_s2m) (void)hipStreamDestroy(c->pp_s2m);
-  for (auto e : c->f_ev) (void)hipEventDestroy(e);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->acc_ev) (void)hipEventDestroy(c->acc_ev);
-  if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return 0;
 }
@@ -410,13 +361,13 @@ int mcs_bind_tallies(mcs_ctx* c, double* dev_f64, int64_t n_f64, int64_t* dev_i6
   HIPCHK(hipStreamSynchronize(c->stream));
   if (dev_f64) {
     if (n_f64 < c->L.total) return fail("mcs_bind_tallies: f64 buffer smaller than layout.total");
-    if (c->own_T && c->d_T) (void)hipFree(c->d_T);
-    c->d_T = dev_f64; c->own_T = false;
+    c->own_T.reset();
+    c->d_T = dev_f64;
   }
   if (dev_i64) {
     if (n_i64 < mcs_i64_total(&c->P)) return fail("mcs_bind_tallies: i64 buffer too small");
-    if (c->own_I && c->d_I) (void)hipFree(c->d_I);
-    c->d_I = (unsigned long long*)dev_i64; c->own_I = false;
+    c->own_I.reset();
+    c->d_I = (unsigned long long*)dev_i64;
   }
   return 0;
 }
@@ -475,8 +426,9 @@ int mcs_set_cuts(mcs_ctx* c, int n_pcuts, const double* pcuts, int n_tcuts, cons
   h.insert(h.end(), x_spec, x_spec + n_xspec);
   h.insert(h.end(), inj_fracs, inj_fracs + ni);
   h.insert(h.end(), eps_target, eps_target + ng);
-  if (c->d_cuts) HIPCHK(hipFree(c->d_cuts));
-  HIPCHK(hipMalloc((void**)&c->d_cuts, h.size() * sizeof(double)));
+  c->have_cuts = false;      // (the table pointers of c->tb lead into the block that is replaced)
+  c->d_cuts.reset();
+  if (reserve(c->d_cuts, (long long)h.size())) return 1;
   HIPCHK(hipMemcpyAsync(c->d_cuts, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   double* q = c->d_cuts;
@@ -570,8 +522,7 @@ int mcs_saved_download(mcs_ctx* c, int64_t n, mcs_soa* host, uint8_t* l_save) {
   if (host) {       // the *_saved arrays of the reference hold zeros where nothing was saved (main_loops.jl:184-197)
     for (int64_t k = 0; k < n; ++k) {
       if (l_save[k]) continue;
-      host->weight[k] = 0; host->ptot_pf[k] = 0; host->pb_pf[k] = 0; host->x_PT_cm[k] = 0; host->xn_per[k] = 0;
-      host->prp_x_cm[k] = 0; host->acctime_sec[k] = 0; host->phi_rad[k] = 0;
+      for (auto f : kSoaF64) (host->*f)[k] = 0;
       host->grid[k] = 0; host->tcut[k] = 0; host->downstream[k] = 0; host->inj[k] = 0;
     }
   }
@@ -595,7 +546,7 @@ int mcs_init_pop(mcs_ctx* c, int64_t n, int64_t j_offset, int64_t n_total, const
     HIPCHK(hipMemcpyAsync(c->d_stage, ptot_pf_in, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_stage + n, weight_in, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned long long key = (unsigned long long)((long long)(c->i_iter - 1) * c->P.n_ions + (c->i_ion - 1));
-    HIPCHK(mcs_launch_init_pop(c->cur.d, c->d_stage, c->d_stage + n, n, j_offset, 1, n_total, key, c->m, c->h_ux[i_grid_start],
+    HIPCHK(mcs_launch_init_pop(pop_view(c->cur), c->d_stage, c->d_stage + n, n, j_offset, 1, n_total, key, c->m, c->h_ux[i_grid_start],
                                x_start_cm, i_grid_start, relativistic, fast_push, c->P.xn_per_fine, c->P.x_grid_stop, 0, nullptr, nullptr, nullptr,
                                c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -638,7 +589,7 @@ int mcs_init_pop_binned_strided(mcs_ctx* c, int64_t n, int64_t j_offset, int64_t
     std::memcpy(h.data() + 2 * n_bins, bin_start, sizeof(int64_t) * (n_bins + 1));
     HIPCHK(hipMemcpyAsync(c->d_stage, h.data(), nd * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned long long key = (unsigned long long)((long long)(c->i_iter - 1) * c->P.n_ions + (c->i_ion - 1));
-    HIPCHK(mcs_launch_init_pop(c->cur.d, nullptr, nullptr, n, j_offset, j_stride, n_total, key, c->m, c->h_ux[i_grid_start], x_start_cm,
+    HIPCHK(mcs_launch_init_pop(pop_view(c->cur), nullptr, nullptr, n, j_offset, j_stride, n_total, key, c->m, c->h_ux[i_grid_start], x_start_cm,
                                i_grid_start, relativistic, fast_push, c->P.xn_per_fine, c->P.x_grid_stop, n_bins, c->d_stage,
                                c->d_stage + n_bins, (const long long*)(c->d_stage + 2 * n_bins), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));     // h goes out of scope
@@ -691,10 +642,11 @@ int mcs_run_pcut_indexed(mcs_ctx* c, int i_pcut, const int64_t* dev_gidx, int64_
 // 78 KB of LDS each --, 1 for the wave-specialised ones, 3 for the fp32-state kernels -- the organised one: 168 VGPRs, 51 KB).
 // n: the population that decides the wave-specialised form (MCS_K1_WS, MCS_WS_AUTO_MIN).  sliced: a launch that suspends and resumes
 // particles -- the tail slicing of mcs_run_pcut* (mcs_set_tail_slicing) runs the general kernel's sliced form for every species, the
-// pipelined loop (which refuses tail slicing) the sliced form of the species' own kernel.
+// pipelined loop (which refuses tail slicing) the sliced form of the species' own kernel.  explicit_geometry: the launch has the
+// geometry of mcs_set_launch (never the wave-specialised form).
 struct K1Plan { int kernel, threads, per_cu; };
 static bool is_ws(int kernel) { return kernel == K1_WS || kernel == K1_WS_ETF; }
-static K1Plan k1_plan(const mcs_ctx* c, long long n, bool sliced) {
+static K1Plan k1_plan(const mcs_ctx* c, long long n, bool sliced, bool explicit_geometry) {
   const mcs_params& P = c->P;
   // the specialised kernel for the common configuration (see transport_body<PLAIN> in mcs_transport.hip)
   const bool plain_but_etf = !c->force_general && c->all_parallel && !P.dont_scatter && !P.use_custom_epsB && !P.dont_DSA &&
@@ -707,7 +659,7 @@ static K1Plan k1_plan(const mcs_ctx* c, long long n, bool sliced) {
   if (sliced && c->tail_budget > 0) return {K1_SLICED, 256, 2};
   if (sliced) return {plain ? K1_PLAIN_SLICED : (lossy ? K1_LOSSY_SLICED : (plain_etf ? K1_PLAIN_ETF_SLICED : K1_SLICED)), 256, 2};
   // the wave-specialised form of PLAIN / PLAIN_ETF (mcs_transport_ws.inc), not with an explicit launch geometry
-  if ((plain || plain_etf) && c->blocks <= 0 && (c->k1_ws == 1 || (c->k1_ws == 2 && n >= c->ws_auto_min)))
+  if ((plain || plain_etf) && !explicit_geometry && (c->k1_ws == 1 || (c->k1_ws == 2 && n >= c->ws_auto_min)))
     return {plain ? K1_WS : K1_WS_ETF, mcs_transport_ws_threads(), 1};
   return {plain ? K1_PLAIN : (lossy ? K1_LOSSY : (plain_etf ? K1_PLAIN_ETF : K1_GENERAL)), 256, 2};
 }
@@ -716,11 +668,7 @@ static K1Plan k1_plan(const mcs_ctx* c, long long n, bool sliced) {
 // the wave-specialised form).  0, with a message, before mcs_set_cuts.
 int mcs_k1_blocks_per_cu(mcs_ctx* c) {
   if (!c || !c->have_cuts) { (void)fail("mcs_k1_blocks_per_cu: cuts not set"); return 0; }
-  const int blocks = c->blocks;
-  c->blocks = 1;
-  const int per_cu = k1_plan(c, c->n, false).per_cu;
-  c->blocks = blocks;
-  return per_cu;
+  return k1_plan(c, c->n, false, true).per_cu;
 }
 
 // persistent lanes: fill the chip (`full` workgroups), never launch more lanes than particles, at least one workgroup
@@ -759,8 +707,8 @@ static int ensure_strag(mcs_ctx* c, long long need_cap) {
   if (need_cap <= c->strag_cap) return 0;
   HIPCHK(hipStreamSynchronize(c->stream));
   c->strag_cap = 0;
-  for (double*& p : c->d_strag) { if (p) (void)hipFree(p); p = nullptr; }
-  for (double*& p : c->d_strag) HIPCHK(hipMalloc((void**)&p, (size_t)need_cap * MCS_STRAG_WORDS * sizeof(double)));
+  reset_all(c->d_strag[0], c->d_strag[1]);
+  if (reserve(c->d_strag[0], need_cap * MCS_STRAG_WORDS) || reserve(c->d_strag[1], need_cap * MCS_STRAG_WORDS)) return 1;
   c->strag_cap = need_cap;
   return 0;
 }
@@ -768,7 +716,7 @@ static int ensure_strag(mcs_ctx* c, long long need_cap) {
 // the launch constants of one pcut that do not depend on the kernel chosen (shared by mcs_run_pcut* and mcs_run_pcuts_fused)
 static void fill_kargs(mcs_ctx* c, KArgs& a, int i_pcut, long long n, long long i_prt_offset, long long i_prt_stride, const long long* dev_gidx, int budget) {
   std::memset(&a, 0, sizeof(a));
-  a.P = c->P; a.L = c->L; a.tb = c->tb; a.in = c->cur.d; a.sv = c->sav.d; a.l_save = c->d_lsave;
+  a.P = c->P; a.L = c->L; a.tb = c->tb; a.in = pop_view(c->cur); a.sv = pop_view(c->sav); a.l_save = c->d_lsave;
   a.T = c->d_T; a.I = c->d_I;
   a.aa = c->aa; a.zzq = c->zzq; a.m = c->m; a.mc = c->mc; a.pmax_cutoff = c->pmax_cutoff; a.density = c->density; a.ewf = c->ewf;
   a.inj_frac = c->h_inj_fracs[c->i_ion - 1];
@@ -817,7 +765,7 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
   KArgs& a = *c->h_args_pin;     // (every launch below is followed by a stream synchronisation before this is written again)
   fill_kargs(c, a, i_pcut, n, i_prt_offset, i_prt_stride, (const long long*)dev_gidx, budget);
 
-  const K1Plan k1 = k1_plan(c, n, budget > 0);
+  const K1Plan k1 = k1_plan(c, n, budget > 0, c->blocks > 0);
   const bool ws = is_ws(k1.kernel);
   // the geometry of mcs_set_launch, else the persistent grid (mcs_set_launch's block size sizes the grid of the fp32-state kernels
   // too, which always run k1.threads)
@@ -863,9 +811,7 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
   HIPCHK(hipStreamSynchronize(c->stream));
   const unsigned long long ns[2] = {c->h_back[0], c->h_back[1]};
   if (ws && c->h_back[2] != 0) {
-    static char msg[160];
-    std::snprintf(msg, sizeof msg, "mcs_run_pcut: a bounded wait of the wave-specialised kernel ran out (the launch is incomplete; code 0x%llx)", (unsigned long long)c->h_back[2]);
-    return fail(msg);
+    return fail(format("mcs_run_pcut: a bounded wait of the wave-specialised kernel ran out (the launch is incomplete; code 0x%llx)", (unsigned long long)c->h_back[2]));
   }
   if (budget == 0) {
     float ms = 0.f;
@@ -900,31 +846,26 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   for (int k = 0; k < npc; ++k) { if (n_target[k] < 1) return fail("mcs_run_pcuts_fused: n_target < 1"); if (n_target[k] > cap_n) cap_n = n_target[k]; }
   // every population of the species fits: n_new = n_saved * (n_target / n_saved) <= max(n_target, n_saved)
   if (ensure_capacity(c, cap_n)) return 1;
-  if (pop_alloc(c, c->spare, cap_n + cap_n / 8 + 1024)) return 1;
-  if (c->sav.cap < cap_n && pop_alloc(c, c->sav, cap_n + cap_n / 8 + 1024)) return 1;
+  if (reserve(c->spare, grow_cap(cap_n))) return 1;
+  if (c->sav.cap() < cap_n && reserve(c->sav, grow_cap(cap_n))) return 1;
   if (npc > c->fused_cap) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->h_fargs) (void)hipHostFree(c->h_fargs);
-    if (c->h_pd) (void)hipHostFree(c->h_pd);
-    if (c->d_fargs) (void)hipFree(c->d_fargs);
-    if (c->d_pd) (void)hipFree(c->d_pd);
-    HIPCHK(hipHostMalloc((void**)&c->h_fargs, sizeof(KArgs) * (size_t)npc));
-    HIPCHK(hipHostMalloc((void**)&c->h_pd, sizeof(PcutDev) * (size_t)(npc + 1)));
-    HIPCHK(hipMalloc((void**)&c->d_fargs, sizeof(KArgs) * (size_t)npc));
-    HIPCHK(hipMalloc((void**)&c->d_pd, sizeof(PcutDev) * (size_t)(npc + 1)));
-    while ((int)c->f_ev.size() < 2 * npc) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); c->f_ev.push_back(e); }
+    c->fused_cap = 0;
+    reset_all(c->h_fargs, c->h_pd, c->d_fargs, c->d_pd);
+    if (reserve(c->h_fargs, npc) || reserve(c->h_pd, npc + 1) || reserve(c->d_fargs, npc) || reserve(c->d_pd, npc + 1)) return 1;
+    while ((int)c->f_ev.size() < 2 * npc) { Event e; HIPCHK(e.create()); c->f_ev.push_back(std::move(e)); }
     c->fused_cap = npc;
   }
-  // launch constants of every pcut: the buffers rotate (cur -> saved -> spare -> cur) independently of the sizes
-  PopBuf cur = c->cur, spare = c->spare;
+  // launch constants of every pcut: the buffers rotate (cur -> saved -> spare -> cur) independently of the sizes: pcut k reads
+  // pop[k & 1] and its split writes the other one; c->cur and c->spare themselves are swapped once the species is through
+  const DevPop pop[2] = {pop_view(c->cur), pop_view(c->spare)}, sav = pop_view(c->sav);
   for (int k = 0; k < npc; ++k) {
     KArgs& a = c->h_fargs[k];
     fill_kargs(c, a, i_pcut_first + k, 0, 0, 1, nullptr, 0);
-    a.in = cur.d; a.sv = c->sav.d;
+    a.in = pop[k & 1]; a.sv = sav;
     a.n_dev = &c->d_pd[k].n_use;
-    PopBuf t = cur; cur = spare; spare = t;
   }
-  const K1Plan k1 = k1_plan(c, cap_n, false);
+  const K1Plan k1 = k1_plan(c, cap_n, false, false);
   const int blocks = persistent_grid(cap_n, k1.threads, (long long)c->n_cu * k1.per_cu);
   std::memset(c->h_pd, 0, sizeof(PcutDev) * (size_t)(npc + 1));
   c->h_pd[0].n_use = c->n;
@@ -932,15 +873,13 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   HIPCHK(hipMemcpyAsync(c->d_pd, c->h_pd, sizeof(PcutDev) * (size_t)(npc + 1), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), c->stream));
   const int split_blocks = (int)std::min<long long>((cap_n + 255) / 256, (long long)c->n_cu * 16);
-  cur = c->cur; spare = c->spare;
   for (int k = 0; k < npc; ++k) {
     HIPCHK(hipMemsetAsync(c->d_lsave, 0, (size_t)cap_n, c->stream));
     HIPCHK(hipEventRecord(c->f_ev[2 * k], c->stream));
     HIPCHK(mcs_launch_transport(c->d_fargs + k, k1.kernel, blocks, k1.threads, c->stream));
     HIPCHK(hipEventRecord(c->f_ev[2 * k + 1], c->stream));
     HIPCHK(mcs_launch_finalize_split_dev(c->d_lsave, cap_n, c->d_bcounts, c->d_boffs, c->d_counters + 2, c->d_src, c->d_pd + k, c->d_pd + k + 1,
-                                         c->d_counters, (long long)n_target[k], c->d_counters + 4, c->sav.d, spare.d, split_blocks, c->stream));
-    PopBuf t = cur; cur = spare; spare = t;
+                                         c->d_counters, (long long)n_target[k], c->d_counters + 4, sav, pop[(k + 1) & 1], split_blocks, c->stream));
   }
   c->rep_dirty = true;
   HIPCHK(hipMemcpyAsync(c->h_pd, c->d_pd, sizeof(PcutDev) * (size_t)(npc + 1), hipMemcpyDeviceToHost, c->stream));
@@ -956,8 +895,11 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
     if (kernel_ms_out) kernel_ms_out[k] = ms;
     ms_sum += ms;
   }
-  c->cur = cur; c->spare = spare;
-  c->n = c->h_pd[npc].n_use;
+  // what the mcs_run_pcut / mcs_new_pcut sequence leaves: it ends with the first pcut that saved nobody, whose population stays as it
+  // ran (the pcuts after it ran empty and wrote nothing); if every pcut saved somebody, the children of the last split
+  int n_split = 0; while (n_split < npc && c->h_pd[n_split].n_saved > 0) ++n_split;
+  if (n_split & 1) std::swap(c->cur, c->spare);
+  c->n = c->h_pd[n_split].n_use;
   c->n_run_last = -1; c->n_saved_last = 0;
   c->last_ms = ms_sum; c->tail_rounds_last = npc;
   c->kernel_last = k1.kernel;
@@ -966,7 +908,7 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
 
 // What the pcut loop of mcs_run_pcuts_pipelined leaves to its caller, which drains the streams and commits the buffers on every exit.
 struct PipeRun {
-  PopBuf cur, nxt;             // the population of the current pcut and the target of its split: c->cur / c->spare, rotated
+  PopBuf *cur, *nxt;           // the population of the current pcut and the target of its split: c->cur / c->spare, rotated
   hipStream_t s1, s2;          // the main stream of the CURRENT pcut (c->stream, or the masked one when the pcut has side work); the side stream
   bool masked;                 // s1 and s2 have complementary CU masks (MCS_PIPE_SIDE_CUS)
   int n_done;                  // pcuts whose population size is in n_use_out
@@ -1002,48 +944,44 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
   const int npc = i_pcut_last - i_pcut_first + 1;
   long long cap_n = c->n;
   for (int k = 0; k < npc; ++k) { if (n_target[k] < 1) return fail("mcs_run_pcuts_pipelined: n_target < 1"); if (n_target[k] > cap_n) cap_n = n_target[k]; }
-  const long long cap = cap_n + cap_n / 8 + 1024;
+  const long long cap = grow_cap(cap_n);
   if (ensure_capacity(c, cap_n)) return 1;
-  if (pop_alloc(c, c->spare, cap)) return 1;
-  if (pop_alloc(c, c->pp_sav2, cap)) return 1;
+  if (reserve(c->spare, cap)) return 1;
+  if (reserve(c->pp_sav2, cap)) return 1;
   if (c->pp_cap < cap) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    { void* pq[] = {c->pp_lsave2, c->pp_bcounts, c->pp_boffs, c->pp_src}; for (void* q : pq) if (q) (void)hipFree(q); }
+    c->pp_cap = 0;
+    reset_all(c->pp_lsave2, c->pp_bcounts, c->pp_boffs, c->pp_src);
     const long long nb = (cap + 1023) / 1024;
-    HIPCHK(hipMalloc((void**)&c->pp_lsave2, (size_t)cap));
-    HIPCHK(hipMalloc((void**)&c->pp_bcounts, (size_t)nb * sizeof(unsigned int)));
-    HIPCHK(hipMalloc((void**)&c->pp_boffs, (size_t)nb * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc((void**)&c->pp_src, (size_t)cap * sizeof(long long)));
+    if (reserve(c->pp_lsave2, cap) || reserve(c->pp_bcounts, nb) || reserve(c->pp_boffs, nb) || reserve(c->pp_src, cap)) return 1;
     c->pp_cap = cap;
   }
-  if (!c->pp_s2) {
-    HIPCHK(hipStreamCreateWithFlags(&c->pp_s2, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->pp_reset, hipEventDisableTiming));
-    HIPCHK(hipMalloc((void**)&c->pp_dpc, 16 * sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc((void**)&c->pp_hpc, 16 * sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc((void**)&c->pp_hargs, 3 * sizeof(KArgs)));
-    HIPCHK(hipMalloc((void**)&c->pp_dargs, 3 * sizeof(KArgs)));
-    HIPCHK(hipMalloc((void**)&c->pp_dpdl, 2 * sizeof(PcutDev)));
-    HIPCHK(hipHostMalloc((void**)&c->pp_hpdl, 2 * sizeof(PcutDev)));
+  // what the first call creates (each guarded by itself: a call that failed half-way is made up for by the next one)
+  if (!c->pp_s2) HIPCHK(c->pp_s2.create_non_blocking());
+  if (!c->pp_reset) HIPCHK(c->pp_reset.create_untimed());
+  if (reserve(c->pp_dpc, 16) || reserve(c->pp_hpc, 16) || reserve(c->pp_hargs, 3) || reserve(c->pp_dargs, 3) || reserve(c->pp_dpdl, 2) ||
+      reserve(c->pp_hpdl, 2))
+    return 1;
+  if (!c->pp_masks_tried) {
+    c->pp_masks_tried = true;
     if (c->pp_side_cus > 0 && c->pp_side_cus < c->n_cu) {
       const int words = (c->n_cu + 31) / 32;
       std::vector<uint32_t> m_side((size_t)words, 0u), m_main((size_t)words, 0u);
       for (int i = 0; i < c->n_cu; ++i) (i < c->pp_side_cus ? m_side : m_main)[(size_t)(i >> 5)] |= 1u << (i & 31);
-      if (hipExtStreamCreateWithCUMask(&c->pp_s1m, (uint32_t)words, m_main.data()) != hipSuccess ||
-          hipExtStreamCreateWithCUMask(&c->pp_s2m, (uint32_t)words, m_side.data()) != hipSuccess) {
+      if (c->pp_s1m.create_cu_masked((uint32_t)words, m_main.data()) != hipSuccess ||
+          c->pp_s2m.create_cu_masked((uint32_t)words, m_side.data()) != hipSuccess) {
         (void)hipGetLastError();
-        if (c->pp_s1m) { (void)hipStreamDestroy(c->pp_s1m); c->pp_s1m = nullptr; }
-        if (c->pp_s2m) { (void)hipStreamDestroy(c->pp_s2m); c->pp_s2m = nullptr; }
+        reset_all(c->pp_s1m, c->pp_s2m);
       }
     }
   }
   // the sliced form of the species' kernel (PLAIN, LOSSY, PLAIN_ETF, general); a wave exports at most its 64 lanes, once: room for the
   // main and the late launch of one pcut
-  const K1Plan k1 = k1_plan(c, 0, true);
+  const K1Plan k1 = k1_plan(c, 0, true, false);
   if (ensure_strag(c, 2 * (long long)c->n_cu * k1.per_cu * k1.threads)) return 1;
   HIPCHK(hipStreamSynchronize(c->stream));
   const bool masked = c->pp_s1m && c->pp_s2m;
-  PipeRun r{c->cur, c->spare, c->stream, masked ? c->pp_s2m : c->pp_s2, masked, 0, 0.0};
+  PipeRun r{&c->cur, &c->spare, c->stream, masked ? c->pp_s2m : c->pp_s2, masked, 0, 0.0};
   int rc = pipelined_pcuts(c, r, k1, i_pcut_first, npc, cap_n, n_target, long_draws, long_imult_max, n_use_out, n_saved_out, i_mult_out,
                            kernel_ms_out, strag_out);
   // every exit of the loop, a failed one too: no stream may still write the population, the saved arrays or the tallies
@@ -1051,7 +989,7 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
     const hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess && rc == 0) rc = fail(std::string("mcs_run_pcuts_pipelined: hipStreamSynchronize: ") + hipGetErrorString(e));
   }
-  c->cur = r.cur; c->spare = r.nxt;
+  if (r.cur != &c->cur) std::swap(c->cur, c->spare);
   // (after a failure the population is half-written: it is not run or split again before the next mcs_init_pop* / mcs_pop_upload)
   c->n = rc ? 0 : (r.n_done > 0 ? n_use_out[r.n_done - 1] : c->n);
   c->n_run_last = -1; c->n_saved_last = 0;
@@ -1074,9 +1012,9 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
   const int side_max = 64;     // workgroups (of 2 per CU) the main launch leaves free for the side stream at most
   const int threads = k1.threads;
   const long long full = (long long)c->n_cu * k1.per_cu;
-  PopBuf& cur = r.cur;
-  PopBuf& nxt = r.nxt;
-  PopBuf savb[2] = {c->sav, c->pp_sav2};
+  PopBuf*& cur = r.cur;
+  PopBuf*& nxt = r.nxt;
+  const DevPop savb[2] = {pop_view(c->sav), pop_view(c->pp_sav2)};
   uint8_t* lsv[2] = {c->d_lsave, c->pp_lsave2};
   long long nA = c->n, nL = 0;
   // long histories are told apart in pcut k only when the pcut before it split by at most long_imult_max (<= 0: always): where few
@@ -1096,7 +1034,7 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
   auto launch_resume = [&](int i_pcut, int q, long long n_pop, long long n_x, hipStream_t st, bool alone) -> int {
     KArgs& a = c->pp_hargs[1];
     fill_kargs(c, a, i_pcut, n_pop, 0, 1, nullptr, 0);
-    a.in = cur.d; a.sv = savb[q].d; a.l_save = lsv[q];
+    a.in = pop_view(*cur); a.sv = savb[q]; a.l_save = lsv[q];
     a.work_counter = pc + 5; a.n_saved = pc + 6; a.strag_count = pc + 3 + (q ^ 1); a.strag_out = c->d_strag[q ^ 1];
     a.strag_in = c->d_strag[q]; a.n_resume = n_x; a.fresh_lo = n_pop; a.long_draws = (unsigned int)Bk; a.budget_trips = 0;
     // few particles per wave (sparse_claim), on at most one wave per SIMD of the chip (alone on the chip -- the pcut waits for them --
@@ -1115,7 +1053,7 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     if (nA > 0) {
       KArgs& a = c->pp_hargs[0];
       fill_kargs(c, a, i_pcut, nA, 0, 1, nullptr, Bk > 0 ? 1 : 0);
-      a.in = cur.d; a.sv = savb[q].d; a.l_save = lsv[q];
+      a.in = pop_view(*cur); a.sv = savb[q]; a.l_save = lsv[q];
       a.work_counter = pc; a.n_saved = pc + 1; a.strag_count = pc + 3 + q; a.strag_out = c->d_strag[q];
       a.long_draws = (unsigned int)Bk;
       HIPCHK(hipMemcpyAsync(c->pp_dargs, &a, sizeof(KArgs), hipMemcpyHostToDevice, s1));
@@ -1152,10 +1090,8 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
       nL = c->pp_hpdl[q].n_new;
       n_saved_out[k - 1] = n1_prev + n5_prev;
       if (sofar_prev + (long long)h[6] != n_saved_out[k - 1]) {
-        static char msg[256];
-        std::snprintf(msg, sizeof msg, "mcs_run_pcuts_pipelined: pcut %d: the kernels' n_saved counters (%lld + %llu resumed) and the count of status bytes (%lld + %lld long) differ",
-                      i_pcut - 1, sofar_prev, (unsigned long long)h[6], n1_prev, n5_prev);
-        return fail(msg);
+        return fail(format("mcs_run_pcuts_pipelined: pcut %d: the kernels' n_saved counters (%lld + %llu resumed) and the count of status bytes (%lld + %lld long) differ",
+                           i_pcut - 1, sofar_prev, (unsigned long long)h[6], n1_prev, n5_prev));
       }
     }
     side_pending = false;
@@ -1166,10 +1102,8 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     if (strag_out) strag_out[2 * k] = n_T;
     if (n_T > c->strag_cap) return fail("mcs_run_pcuts_pipelined: export buffer overrun");
     if (sofar < n1) {
-      static char msg[256];
-      std::snprintf(msg, sizeof msg, "mcs_run_pcuts_pipelined: pcut %d: the kernels' n_saved counters (%llu main + %llu late) are below the count of status bytes (%lld)",
-                    i_pcut, (unsigned long long)h[1], (unsigned long long)h[8], n1);
-      return fail(msg);
+      return fail(format("mcs_run_pcuts_pipelined: pcut %d: the kernels' n_saved counters (%llu main + %llu late) are below the count of status bytes (%lld)",
+                         i_pcut, (unsigned long long)h[1], (unsigned long long)h[8], n1));
     }
     const long long target = (long long)n_target[k];
     const bool last = k == npc - 1;
@@ -1221,20 +1155,17 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     HIPCHK(hipMemsetAsync(pc + 7, 0, 3 * sizeof(unsigned long long), s1));
     if (nA_next + nL_max > 0) HIPCHK(hipMemsetAsync(lsv[q ^ 1], 0, (size_t)(nA_next + nL_max), s1));
     HIPCHK(hipEventRecord(c->pp_reset, s1));
-    HIPCHK(mcs_launch_split(savb[q].d, nxt.d, c->d_src, nA_next, i_mult, s1));
+    HIPCHK(mcs_launch_split(savb[q], pop_view(*nxt), c->d_src, nA_next, i_mult, s1));
     n1_prev = n1; sofar_prev = sofar;
     if (n5_max > 0) {
       HIPCHK(hipStreamWaitEvent(s2, c->pp_reset, 0));
-      DevPop out = nxt.d;
-      out.weight += nA_next; out.ptot_pf += nA_next; out.pb_pf += nA_next; out.x_PT_cm += nA_next; out.xn_per += nA_next;
-      out.prp_x_cm += nA_next; out.acctime_sec += nA_next; out.phi_rad += nA_next; out.meta += nA_next;
       const int split_blocks = (int)std::min<long long>((nL_max + 255) / 256, (long long)c->n_cu * 4);
-      HIPCHK(mcs_launch_late_split(lsv[q], nA + nL, c->pp_bcounts, c->pp_boffs, pc + 9, c->pp_src, c->pp_dpdl + (q ^ 1), i_mult, nA_next, savb[q].d,
-                                   out, split_blocks < 1 ? 1 : split_blocks, s2));
+      HIPCHK(mcs_launch_late_split(lsv[q], nA + nL, c->pp_bcounts, c->pp_boffs, pc + 9, c->pp_src, c->pp_dpdl + (q ^ 1), i_mult, nA_next, savb[q],
+                                   pop_view(*nxt, nA_next), split_blocks < 1 ? 1 : split_blocks, s2));
       // the late launch of the next pcut: particles nA_next .. of its population, their number read on the device
       KArgs& a = c->pp_hargs[2];
       fill_kargs(c, a, i_pcut + 1, nA_next, 0, 1, nullptr, B_next > 0 ? 1 : 0);
-      a.in = nxt.d; a.sv = savb[q ^ 1].d; a.l_save = lsv[q ^ 1];
+      a.in = pop_view(*nxt); a.sv = savb[q ^ 1]; a.l_save = lsv[q ^ 1];
       a.n_dev = &c->pp_dpdl[q ^ 1].n_use; a.fresh_lo = nA_next;
       a.work_counter = pc + 7; a.n_saved = pc + 8; a.strag_count = pc + 3 + (q ^ 1); a.strag_out = c->d_strag[q ^ 1];
       a.long_draws = (unsigned int)B_next;
@@ -1251,7 +1182,7 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     }
     nA = nA_next;
     Bk = B_next;
-    PopBuf t = cur; cur = nxt; nxt = t;
+    std::swap(cur, nxt);
   }
   return 0;
 }
@@ -1264,9 +1195,9 @@ int mcs_new_pcut(mcs_ctx* c, int64_t i_mult, int64_t* n_new_out) {
   const long long n_new = n_saved * i_mult;
   // the split (src[] was computed behind the transport kernel) writes into the spare buffer, then the buffers
   // rotate; nothing is read back: the new size is known on the host
-  if (pop_alloc(c, c->spare, n_new + n_new / 8 + 1024)) return 1;
-  HIPCHK(mcs_launch_split(c->sav.d, c->spare.d, c->d_src, n_new, i_mult, c->stream));
-  PopBuf t = c->cur; c->cur = c->spare; c->spare = t;
+  if (reserve(c->spare, grow_cap(n_new))) return 1;
+  HIPCHK(mcs_launch_split(pop_view(c->sav), pop_view(c->spare), c->d_src, n_new, i_mult, c->stream));
+  std::swap(c->cur, c->spare);
   c->n = n_new; c->n_run_last = -1;
   if (ensure_capacity(c, n_new)) return 1;
   if (n_new_out) *n_new_out = n_new;
@@ -1278,7 +1209,7 @@ int mcs_saved_export(mcs_ctx* c, int64_t cap, int64_t* dev_gidx, double* dev_f64
   if (c->n != c->n_run_last) return fail("mcs_saved_export: no mcs_run_pcut since the population changed");
   if (cap < c->n_saved_last) return fail("mcs_saved_export: cap < n_saved");
   if (c->n_saved_last > 0 && (!dev_gidx || !dev_f64 || !dev_meta)) return fail("mcs_saved_export: null buffer");
-  HIPCHK(mcs_launch_saved_export(c->sav.d, c->d_src, c->n_saved_last, cap, c->idx_first, c->idx_stride, c->idx_gidx,
+  HIPCHK(mcs_launch_saved_export(pop_view(c->sav), c->d_src, c->n_saved_last, cap, c->idx_first, c->idx_stride, c->idx_gidx,
                                  (long long*)dev_gidx, dev_f64, dev_meta, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));      // the caller's library (RCCL on another stream) may read the buffers now
   return 0;
@@ -1289,7 +1220,7 @@ int mcs_saved_gidx(mcs_ctx* c, int64_t cap, int64_t* dev_gidx) {
   if (c->n != c->n_run_last) return fail("mcs_saved_gidx: no mcs_run_pcut since the population changed");
   if (cap < c->n_saved_last) return fail("mcs_saved_gidx: cap < n_saved");
   if (c->n_saved_last > 0 && !dev_gidx) return fail("mcs_saved_gidx: null buffer");
-  HIPCHK(mcs_launch_saved_export(c->sav.d, c->d_src, c->n_saved_last, cap, c->idx_first, c->idx_stride, c->idx_gidx,
+  HIPCHK(mcs_launch_saved_export(pop_view(c->sav), c->d_src, c->n_saved_last, cap, c->idx_first, c->idx_stride, c->idx_gidx,
                                  (long long*)dev_gidx, nullptr, nullptr, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -1303,10 +1234,10 @@ int mcs_split_import(mcs_ctx* c, int64_t n_parents, int64_t cap, const double* d
   if (n_local > 0 && (first + (n_local - 1) * stride) / i_mult >= n_parents)
     return fail("mcs_split_import: the local slice reaches past n_parents * i_mult");
   if (n_local > 0 && (!dev_f64 || !dev_meta)) return fail("mcs_split_import: null buffer");
-  if (pop_alloc(c, c->spare, n_local + n_local / 8 + 1024)) return 1;
-  HIPCHK(mcs_launch_split_import(c->spare.d, dev_f64, dev_meta, cap, i_mult, first, stride, n_local, c->stream));
+  if (reserve(c->spare, grow_cap(n_local))) return 1;
+  HIPCHK(mcs_launch_split_import(pop_view(c->spare), dev_f64, dev_meta, cap, i_mult, first, stride, n_local, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));      // the caller may free or reuse its buffers
-  PopBuf t = c->cur; c->cur = c->spare; c->spare = t;
+  std::swap(c->cur, c->spare);
   c->n = n_local; c->n_run_last = -1;
   if (ensure_capacity(c, n_local)) return 1;
   return 0;
@@ -1408,10 +1339,7 @@ static int consumers_ready(mcs_ctx* c, const mcs_consumer_in* in, const char* wh
   if (!c->have_grid) return fail(std::string(who) + ": grid not set");
   if (c->P.num_psd_mom_bins + 2 > 208 || c->P.num_psd_tht_bins + 2 > 208) return fail(std::string(who) + ": too many PSD bins");
   const int NM = c->P.num_psd_mom_bins + 2, NT = c->P.num_psd_tht_bins + 2, ng = c->P.n_grid;
-  if (!c->d_ctab) HIPCHK(hipMalloc((void**)&c->d_ctab, sizeof(double) * (size_t)(3 * NM + 2 * NT + 4 * ng)));
-  if (!c->d_cout) HIPCHK(hipMalloc((void**)&c->d_cout, sizeof(double) * (size_t)(3 * ng * NM + 3 * ng)));
-  if (!c->d_cdiag) HIPCHK(hipMalloc((void**)&c->d_cdiag, sizeof(unsigned long long) * 2));
-  return 0;
+  return reserve(c->d_ctab, 3 * NM + 2 * NT + 4 * ng) || reserve(c->d_cout, 3 * ng * NM + 3 * ng) || reserve(c->d_cdiag, 2);
 }
 
 int mcs_dndp_cr(mcs_ctx* c, const mcs_consumer_in* in, double* dNdp, int64_t* diag) {
@@ -1444,7 +1372,7 @@ int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, doubl
   if (!in->cos_center || !in->pt_center || !in->zone_pop || !in->density_loc || !in->cold_pressure || !P_par || !P_perp || !energy_density)
     return fail("mcs_thermo_calcs: null table");
   const int NM = c->P.num_psd_mom_bins + 2, NT = c->P.num_psd_tht_bins + 2, ng = c->P.n_grid;
-  if (!c->d_cscratch) HIPCHK(hipMalloc((void**)&c->d_cscratch, sizeof(double) * (size_t)NM * NT * ng));
+  if (reserve(c->d_cscratch, (long long)NM * NT * ng)) return 1;
   std::vector<double> h((size_t)(NT + NM + 3 * ng), 0.0);
   memcpy(h.data(), in->cos_center, sizeof(double) * (NT - 1));
   memcpy(h.data() + NT, in->pt_center, sizeof(double) * (NM - 1));
@@ -1522,8 +1450,7 @@ int mcs_dndp_2d(mcs_ctx* c, const mcs_consumer_in* in, double gam_x, double beta
   if (!(gam_x >= 1) || !(beta_x >= 0 && beta_x < 1)) return fail("mcs_dndp_2d: bad frame");
   const int NM = c->P.num_psd_mom_bins + 2, NT = c->P.num_psd_tht_bins + 2, ng = c->P.n_grid;
   const size_t slab = (size_t)NM * NT * ng;
-  if (!c->d_cscratch) HIPCHK(hipMalloc((void**)&c->d_cscratch, sizeof(double) * slab));
-  if (!c->d_c2d) HIPCHK(hipMalloc((void**)&c->d_c2d, sizeof(double) * slab));
+  if (reserve(c->d_cscratch, (long long)slab) || reserve(c->d_c2d, (long long)slab)) return 1;
   std::vector<double> h((size_t)(2 * NM + NT + ng), 0.0);
   memcpy(h.data(), in->mom_edge_cgs, sizeof(double) * NM);
   memcpy(h.data() + NM, in->cos_center, sizeof(double) * (NT - 1));

@@ -1341,3 +1341,47 @@ def test_fused_pcut_loop_equals_per_pcut_calls(case):
     assert np.array_equal(ra.tallies_i64, rb.tallies_i64)
     assert_tallies_close(L, ra.tallies_f64, rb.tallies_f64, TALLY_RTOL)
     assert all(s.kernel_ms > 0 for s in ra.stats)
+
+
+_OUTGROW_REF = {}
+
+
+def _outgrow_problem():
+    return mcs.inputs.build_problem(mcs.inputs.Config(N_PTS_INJ=256, N_PTS_PCUT=4096, N_PTS_PCUT_HI=8192))
+
+
+def _outgrow_reference(**kw):
+    """the oracle's run of _outgrow_problem, once per population order (long_draws)"""
+    key = tuple(sorted(kw.items()))
+    if key not in _OUTGROW_REF:
+        prob = _outgrow_problem()
+        ob = oracle_backend(prob, nthreads=16)
+        r = mcs.driver.run(prob, ob, None, n_itrs=1, **kw)
+        _OUTGROW_REF[key] = (r, ob.get_population())
+        ob.destroy()
+    return _OUTGROW_REF[key]
+
+
+@pytest.mark.parametrize("loop", ["per_pcut", "fused", "pipelined"])
+def test_population_outgrows_its_buffers(loop):
+    """The stock input's shape: fewer particles are injected than the pcuts aim for (256, then 4096, then 8192), so the population
+    outgrows the buffers it was injected into (at most 256 + 256 / 8 + 1024 = 1312 entries) while it is alive: the current buffer is
+    reallocated around the live population, the spare and saved buffers (and the pipelined loop's second saved set) grow between
+    pcuts.  Every other test injects as many particles as its pcuts aim for.  Each of the three pcut loops against the oracle: the same
+    population size, saved count and i_mult in every pcut, the same integer tallies, binned tallies up to add order, and the final
+    population bit for bit."""
+    order = dict(long_draws=400, long_imult_max=0) if loop == "pipelined" else {}
+    ro, po = _outgrow_reference(**order)
+    prob = _outgrow_problem()
+    hb = hip_backend(prob)
+    rg = mcs.driver.run(prob, hb, None, n_itrs=1, fused_pcuts=(loop != "per_pcut"), **order)
+    pg, L = hb.get_population(), hb.layout
+    hb.destroy()
+    rows_o = [(s.i_pcut, s.n_pts_use, s.n_saved, s.i_mult) for s in ro.stats]
+    rows_g = [(s.i_pcut, s.n_pts_use, s.n_saved, s.i_mult) for s in rg.stats]
+    print(loop, rows_g)
+    assert max(n for _, n, _, _ in rows_g) > 256 + 256 // 8 + 1024           # (the buffers of the injected population were outgrown)
+    assert rows_g == rows_o
+    assert np.array_equal(rg.tallies_i64, ro.tallies_i64)
+    assert_tallies_close(L, rg.tallies_f64, ro.tallies_f64, TALLY_RTOL)
+    assert_pop_equal(pg, po, loop)
