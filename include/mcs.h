@@ -185,6 +185,71 @@ static inline void mcs_tally_layout(const mcs_params* p, mcs_layout* L) {
   L->total = o;
 }
 
+/* ---- run options of a context ------------------------------------------------
+ * Every switch of the transport path is an option of the context, with a key of this enum.  A new context takes the built-in
+ * default of each, then -- unless it was created with use_env = 0 -- what the option's environment variable says, then what the
+ * caller's list says (mcs_create_with_options).  The variables are read once, at creation; they are the DEFAULT of a context that
+ * was not told otherwise (a host that must not depend on its shell passes use_env = 0).  mcs_get_option reads an option back,
+ * mcs_set_option changes it where "when" allows, mcs_option_describe hands out this table (csrc/mcs_options.h holds it).
+ *
+ * key                      variable                  default    range        when  applies   meaning
+ * MCS_OPT_FORCE_GENERAL    MCS_FORCE_GENERAL [on]    0          0..1         L     any       1: always the general transport kernel
+ *                                                                                            (mcs_last_kernel 0), never a specialisation
+ * MCS_OPT_K1_WS            MCS_K1_WS [tri]           2          0..2         L     any       the wave-specialised kernels (mcs_last_kernel
+ *                                                                                            7 / 8) where they apply: 0 never, 1 always,
+ *                                                                                            2 for populations of >= WS_AUTO_MIN particles
+ * MCS_OPT_WS_AUTO_MIN      MCS_WS_AUTO_MIN [int]     6000000    0..INT64_MAX L     any       that population size
+ * MCS_OPT_TAIL_MERGE       MCS_TAIL_MERGE [not off]  1          0..1         L     any       0: sparse waves are not consolidated
+ * MCS_OPT_PARK             MCS_PARK [not off]        1          0..1         L     any       0: lanes that need the rare code run it at
+ *                                                                                            once instead of waiting for company
+ * MCS_OPT_TAIL_RING        MCS_TAIL_RING [not off]   1          0..1         L     any       0: no precomputed scatter draws in the tail
+ *                                                                                            (and no tail loop)
+ * MCS_OPT_TAIL_LOOP        MCS_TAIL_LOOP [int]       12         0..32        L     any       live lanes at or below which an exhausted
+ *                                                                                            wave runs the tight tail loop (0: never)
+ * MCS_OPT_REFILL_MIN       MCS_REFILL_MIN [int]      12         1..48        L     any       idle lanes at which a wave claims new work
+ * MCS_OPT_DEFER_K          MCS_DEFER_K [int]         8          1..40        L     any       lanes a wave collects before it runs their
+ *                                                                                            rare code (1: no deferral); a launch uses
+ *                                                                                            min(DEFER_K, 64 - REFILL_MIN)
+ * MCS_OPT_TAIL_BUDGET      MCS_TAIL_BUDGET [int]     0          0..2^24      L     fp64 > 0  the sliced tail of mcs_set_tail_slicing
+ *                                                                                            (trips; 0 = one launch per pcut)
+ * MCS_OPT_PIPE_SIDE_CUS    MCS_PIPE_SIDE_CUS [int]   12         0..128       P     any       compute units the side stream of
+ *                                                                                            mcs_run_pcuts_pipelined has to itself (0: no
+ *                                                                                            CU masks)
+ * MCS_OPT_TALLY_REPLICAS   MCS_TALLY_REPLICAS_OFF    1          0..1         C     any       0: tally straight into the tally buffer, no
+ *                          [on, inverted]                                                    private copies (they cost device memory: 16
+ *                                                                                            times the tally buffer)
+ * MCS_OPT_F32_LOOP         MCS_F32_LOOP [on]         0          0..1         L     fp32      1: the fp32-state kernel as a plain per-lane
+ *                                                                                            loop (mcs_last_kernel 4)
+ * MCS_OPT_F32_EXACT        MCS_F32_EXACT [on]        0          0..1         L     fp32      1: that loop with the exact fp32 primitives
+ *                                                                                            (mcs_last_kernel 9; wins over F32_LOOP)
+ *
+ * How a variable is read: [on] 1 iff its first character is '1'; [not off] 0 iff its first character is '0'; [tri] '1' -> 1,
+ * '0' -> 0, anything else -> 2; [int] the number, if it lies inside the range.  An unset variable, or an [int] outside the range,
+ * leaves the built-in default, silently.  (MCS_TAIL_BUDGET once took numbers up to INT_MAX; it now has the range of the option.)
+ * A variable is not asked whether it applies: MCS_F32_EXACT=1 is carried by a fp64 context without effect, as it always was.
+ * when: L -- between launches: a change holds for the launches queued by calls made after it; P -- until the context's first
+ * mcs_run_pcuts_pipelined (the masked streams are made once); C -- at creation only (it decides an allocation).
+ * applies: fp32 -- the key is refused for a context with fp64 particle state (mcs_params.state_fp32 = 0); fp64 > 0 -- a value
+ * above 0 is refused for a context with fp32 particle state.
+ * Not options, because no property of a context: MCS_PIPE_DEBUG (a trace on stderr) and MCS_HIP_LIB (the file the Python package
+ * loads).  The Python driver's own four (MCS_FUSED_PCUTS, MCS_FUSED_CHUNK, MCS_LONG_DRAWS, MCS_LONG_IMULT_MAX) are the defaults of
+ * arguments of driver.run. */
+enum mcs_option {
+  MCS_OPT_FORCE_GENERAL = 0, MCS_OPT_K1_WS, MCS_OPT_WS_AUTO_MIN, MCS_OPT_TAIL_MERGE, MCS_OPT_PARK, MCS_OPT_TAIL_RING,
+  MCS_OPT_TAIL_LOOP, MCS_OPT_REFILL_MIN, MCS_OPT_DEFER_K, MCS_OPT_TAIL_BUDGET, MCS_OPT_PIPE_SIDE_CUS, MCS_OPT_TALLY_REPLICAS,
+  MCS_OPT_F32_LOOP, MCS_OPT_F32_EXACT,
+  MCS_OPT_COUNT
+};
+enum mcs_option_when { MCS_WHEN_BETWEEN_LAUNCHES = 0, MCS_WHEN_BEFORE_PIPELINED_RUN = 1, MCS_WHEN_CREATION = 2 };
+enum mcs_option_applies { MCS_APPLIES_ANY = 0, MCS_APPLIES_FP64_IF_POSITIVE = 1, MCS_APPLIES_FP32 = 2 };
+/* One row of the table; name and env point to static strings of the library. */
+typedef struct mcs_option_desc {
+  int32_t key, when, applies, reserved;
+  int64_t min, max, dflt;
+  const char* name;   /* lower case, the key without MCS_OPT_: "defer_k" */
+  const char* env;    /* the variable that seeds the default */
+} mcs_option_desc;
+
 typedef struct mcs_ctx mcs_ctx;
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -194,6 +259,22 @@ int         mcs_get_layout(const mcs_params* p, mcs_layout* out);
 const char* mcs_last_error(void);
 /* device: HIP device ordinal; stream: hipStream_t (NULL = default stream). */
 int mcs_create(const mcs_params* p, int device, void* stream, mcs_ctx** out);
+/* The same with run options (enum mcs_option): n_options pairs keys[i], values[i]; use_env = 0: no environment variable is read.
+ * Initial values: built-in default < environment (use_env != 0) < the list, in its order.  A pair the table does not allow --
+ * unknown key, value outside the range, a fp32 key for a fp64 context, MCS_OPT_TAIL_BUDGET > 0 for a fp32 one -- fails the call
+ * with a message that names the option and its range, BEFORE the device is touched (the same on a machine without a GPU).
+ * mcs_create(p, device, stream, out) is mcs_create_with_options(p, device, stream, NULL, NULL, 0, 1, out). */
+int mcs_create_with_options(const mcs_params* p, int device, void* stream, const int32_t* keys, const int64_t* values, int n_options,
+                            int use_env, mcs_ctx** out);
+/* Rows of the option table, and the row of one key (0 .. count - 1).  They need no context and no GPU. */
+int mcs_option_count(void);
+int mcs_option_describe(int key, mcs_option_desc* out);
+/* Change an option of a context for the launches queued by later calls; no synchronisation.  Refused, with a message and nothing
+ * changed: what mcs_create_with_options refuses, a creation-only key, MCS_OPT_PIPE_SIDE_CUS after the first pipelined run, a null
+ * context. */
+int mcs_set_option(mcs_ctx* ctx, int key, int64_t value);
+/* The value the next launch will use.  A null context or a null value pointer is an error. */
+int mcs_get_option(mcs_ctx* ctx, int key, int64_t* value);
 int mcs_destroy(mcs_ctx* ctx);
 int mcs_sync(mcs_ctx* ctx);
 
@@ -412,9 +493,10 @@ int mcs_set_launch(mcs_ctx* ctx, int blocks, int threads);
  * mcs_last_launches: launches the last mcs_run_pcut* took.
  * mcs_last_kernel: which transport kernel they ran -- 0 the general kernel, 1 its specialisation for the common configuration,
  * 2 the one for electrons with radiative losses, 3 the fp32-state kernel, 4 its plain-loop form, 5 its specialisation for
- * electrons with radiative losses, 6 the common configuration with ion -> electron energy transfer on.  * 7 / 8: the wave-specialised kernel for the common configuration / the same with energy transfer (MCS_K1_WS=1), 9: the fp32-state
- * plain loop with the exact primitives (MCS_F32_EXACT=1), 10: the general kernel's form for sliced launches, 11 / 12 / 13: the sliced forms
- * of 1 / 2 / 6 (what mcs_run_pcuts_pipelined launches). */
+ * electrons with radiative losses, 6 the common configuration with ion -> electron energy transfer on.  * 7 / 8: the wave-specialised kernel for the common configuration / the same with energy transfer (MCS_OPT_K1_WS), 9: the fp32-state
+ * plain loop with the exact primitives (MCS_OPT_F32_EXACT), 10: the general kernel's form for sliced launches, 11 / 12 / 13: the sliced forms
+ * of 1 / 2 / 6 (what mcs_run_pcuts_pipelined launches).
+ * mcs_set_tail_slicing(ctx, b) is mcs_set_option(ctx, MCS_OPT_TAIL_BUDGET, b) with messages of its own. */
 int mcs_set_tail_slicing(mcs_ctx* ctx, int budget_trips);
 /* A species' pcuts first .. last queued back to back: transport, pcut_finalize and new_pcut (src/cuts.jl:34-124) of every pcut with
  * nothing read back in between -- n_saved, i_mult = max(n_target / n_saved, 1) (src/cuts.jl:42) and the size of the next population

@@ -69,6 +69,19 @@ class McsConsumerIn(ct.Structure):
     ]
 
 
+class McsOptionDesc(ct.Structure):
+    """`mcs_option_desc`: one row of the library's option table (include/mcs.h, enum mcs_option)."""
+    _fields_ = [
+        ("key", ct.c_int32), ("when", ct.c_int32), ("applies", ct.c_int32), ("reserved", ct.c_int32),
+        ("min", ct.c_int64), ("max", ct.c_int64), ("dflt", ct.c_int64),
+        ("name", ct.c_char_p), ("env", ct.c_char_p),
+    ]
+
+
+# enum mcs_option_when / mcs_option_applies
+OPTION_WHEN = ("between launches", "before the first pipelined run", "creation only")
+OPTION_APPLIES = ("any", "fp64 state when > 0", "fp32 state")
+
 F64_FIELDS = ("weight", "ptot_pf", "pb_pf", "x_PT_cm", "xn_per", "prp_x_cm", "acctime_sec", "phi_rad")
 I64_FIELDS = ("grid", "tcut")
 U8_FIELDS = ("downstream", "inj")
@@ -268,13 +281,42 @@ def load_library() -> ct.CDLL:
         "mcs_photon_pion": (i32, [vp, c_double_p, c_double_p, dbl, dbl, c_double_p, dbl, i32, i32, dbl, dbl, c_double_p, c_double_p]),
         "mcs_accumulate_tallies": (i32, [vp, vp]),
         "mcs_k1_blocks_per_cu": (i32, [vp]),
+        "mcs_option_count": (i32, []),
+        "mcs_option_describe": (i32, [i32, ct.POINTER(McsOptionDesc)]),
+        "mcs_create_with_options": (i32, [ct.POINTER(McsParams), i32, vp, c_int32_p, c_int64_p, i32, i32, ct.POINTER(vp)]),
+        "mcs_set_option": (i32, [vp, i32, i64]),
+        "mcs_get_option": (i32, [vp, i32, c_int64_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args
     _LIB = lib
+    _OPTIONS.clear()
+    for key in range(lib.mcs_option_count()):
+        d = McsOptionDesc()
+        if lib.mcs_option_describe(key, ct.byref(d)) != 0:
+            raise RuntimeError("libmcs_hip: " + lib.mcs_last_error().decode())
+        _OPTIONS[d.name.decode()] = dict(key=int(d.key), name=d.name.decode(), env=d.env.decode(), min=int(d.min), max=int(d.max),
+                                         default=int(d.dflt), when=OPTION_WHEN[d.when], applies=OPTION_APPLIES[d.applies])
     return lib
+
+
+_OPTIONS: Dict[str, dict] = {}
+
+
+def option_table() -> Dict[str, dict]:
+    """The run options of a context, name -> {key, name, env, min, max, default, when, applies}: what the loaded library says
+    about itself (mcs_option_describe), read when it is loaded.  include/mcs.h documents every key."""
+    load_library()
+    return {name: dict(d) for name, d in _OPTIONS.items()}
+
+
+def option_key(name: str) -> int:
+    load_library()
+    if name not in _OPTIONS:
+        raise KeyError(f"unknown option {name!r}; the library has: {', '.join(_OPTIONS)}")
+    return _OPTIONS[name]["key"]
 
 
 EXPORTED_SYMBOLS = [
@@ -288,4 +330,5 @@ EXPORTED_SYMBOLS = [
     "mcs_set_tail_slicing", "mcs_last_launches", "mcs_last_kernel", "mcs_write_tallies_part", "mcs_photon_synch",
     "mcs_dndp_2d", "mcs_photon_ic", "mcs_run_pcuts_fused", "mcs_photon_pion", "mcs_run_pcuts_pipelined",
     "mcs_accumulate_tallies", "mcs_k1_blocks_per_cu",
+    "mcs_option_count", "mcs_option_describe", "mcs_create_with_options", "mcs_set_option", "mcs_get_option",
 ]

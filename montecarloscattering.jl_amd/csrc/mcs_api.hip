@@ -132,16 +132,21 @@ struct mcs_ctx {
   int retro_cap = MCS_RETRO_CAP;
   // sliced tail (mcs_set_tail_slicing; KArgs "sliced launches"): after the queue is exhausted a wave makes tail_budget more trips,
   // exports its live particles and ends; the host relaunches them, spread over the chip's waves, until none is left
-  int tail_budget = 0;         // trips; 0 = one launch per pcut, run to the end
+  // (the budget, in trips, is MCS_OPT_TAIL_BUDGET; 0 = one launch per pcut, run to the end)
   int tail_rounds_last = 0;    // launches the last mcs_run_pcut* took
   DevBuf<double> d_strag[2]; long long strag_cap = 0;
-  bool f32_exact = false;      // MCS_F32_EXACT=1: the plain loop with the exact fp32 primitives (include/mcs_math_f32.h): the kernel the CPU restatement
-                               // oracle/mcs_oracle_f32.inc reproduces bit for bit (tests)
-  bool f32_loop = false;       // MCS_F32_LOOP=1: the fp32-state variant as a plain per-lane loop (the reference semantics of that variant; tests)
-  bool tail_ring = true;       // MCS_TAIL_RING=0: no precomputed scatter draws in the tail (A/B measurements)
-  int tail_loop = 12;          // MCS_TAIL_LOOP=<n>: live lanes at or below which an exhausted wave runs the tight tail loop (0 = off; needs the tail ring)
-  int refill_min = 12;         // MCS_REFILL_MIN=<n> (environment) overrides: A/B measurements
-  int defer_k = 8;             // MCS_DEFER_K=<n> (environment) overrides: A/B measurements, 1 = no deferral
+  // The run options (enum mcs_option of include/mcs.h, one value per key; the table of mcs_options.h says what each allows): set at
+  // creation from the built-in defaults, the environment and the caller's list, changed by mcs_set_option, read where a launch is
+  // planned.  Notes on some of them:
+  //   F32_EXACT  the plain loop with the exact fp32 primitives (include/mcs_math_f32.h): the kernel the CPU restatement
+  //              oracle/mcs_oracle_f32.inc reproduces bit for bit (tests)
+  //   F32_LOOP   the fp32-state variant as a plain per-lane loop (the reference semantics of that variant; tests)
+  //   K1_WS      the wave-specialised kernels (mcs_transport_ws.inc), where they apply: 1 always, 0 never, 2 (default) for populations of
+  //              at least WS_AUTO_MIN particles -- measured level with transport_body at 4e6 particles, 3.8 % faster at 1e7 and 7 % slower
+  //              at 2e6, where its missing tail consolidation shows (profiles/r04_ws_kernel_ab.txt)
+  //   TAIL_RING, TAIL_LOOP, REFILL_MIN, DEFER_K, PARK, TAIL_MERGE   A/B measurements of the tail's parts
+  int64_t opt[MCS_OPT_COUNT] = {};
+  long long o(int key) const { return opt[key]; }
   // finals
   DevBuf<int32_t> f_reason, f_helix, f_retro; DevBuf<double> f_ptot, f_x;
   long long f_cap = 0;
@@ -150,8 +155,6 @@ struct mcs_ctx {
   DevBuf<double> d_tally_rep;                  // replicas of the histograms at the head of the tally buffer (KArgs::tally_rep)
   long long rep_n = 0;                         // doubles per replica (0: no replicas)
   bool rep_dirty = false;                    // a launch may have added to the replicas since the last fold
-  bool tally_replicas = true;                  // MCS_TALLY_REPLICAS_OFF=1: tally straight into T
-  bool park = true;                           // MCS_PARK=0: lanes that need the full Code Blocks run them at once (A/B measurements)
   DevBuf<unsigned long long> d_counters;      // [0] work counter, [1] n_saved, [2] scan total
   // staging for init_pop
   DevBuf<double> d_stage;
@@ -164,7 +167,6 @@ struct mcs_ctx {
   double aa = 1, zzq = MCS_QCGS, m = MCS_MP, mc = MCS_MP * MCS_C, pmax_cutoff = 0, density = 1, ewf = 1;
   bool have_grid = false, have_cuts = false;
   bool all_parallel = false;   // theta == 0 in every zone (mcs_set_grid)
-  bool tail_merge = true;      // MCS_TAIL_MERGE=0: no consolidation of sparse waves (A/B measurements)
   int kernel_last = -1;        // mcs_last_kernel
   // fused species loop (mcs_run_pcuts_fused): launch constants of every pcut (pinned + device), the per-pcut words decided on the
   // device, one event pair per pcut
@@ -177,17 +179,12 @@ struct mcs_ctx {
   // ... and, when the runtime grants them, two streams with complementary CU masks: the side stream's waves then have their SIMDs to
   // themselves (beside a wave of the main launch on the same SIMD a long history advances at half the speed -- the kernel is issue-bound
   // -- and the side chain, not the main launch, ends the pcut); a pcut with side work runs its main launch on the masked main stream
-  Stream pp_s1m, pp_s2m; bool pp_masks_tried = false; int pp_side_cus = 12;      // MCS_PIPE_SIDE_CUS=<n> (0: no masks)
+  Stream pp_s1m, pp_s2m; bool pp_masks_tried = false;      // (MCS_OPT_PIPE_SIDE_CUS of the chip's CUs for the side stream; 0: no masks)
   PopBuf pp_sav2; DevBuf<uint8_t> pp_lsave2; long long pp_cap = 0;
   DevBuf<unsigned int> pp_bcounts; DevBuf<unsigned long long> pp_boffs; DevBuf<long long> pp_src;
   DevBuf<unsigned long long> pp_dpc; PinnedBuf<unsigned long long> pp_hpc;
   PinnedBuf<KArgs> pp_hargs; DevBuf<KArgs> pp_dargs; DevBuf<PcutDev> pp_dpdl; PinnedBuf<PcutDev> pp_hpdl;
   int pp_waits_last = 0;       // pcuts of the last pipelined run whose i_mult had to wait for the long histories
-  bool force_general = false;  // MCS_FORCE_GENERAL=1: always the general kernel (tests compare the two)
-  int k1_ws = 2;               // the wave-specialised kernels (mcs_transport_ws.inc), where they apply: MCS_K1_WS=1 always, =0 never, default (2)
-                               // for populations of at least ws_auto_min particles -- measured level with transport_body at 4e6 particles, 3.8 %
-                               // faster at 1e7 and 7 % slower at 2e6, where its missing tail consolidation shows (profiles/r04_ws_kernel_ab.txt)
-  long long ws_auto_min = 6000000;   // MCS_WS_AUTO_MIN=<n>
   // consumers (K4): table staging, outputs, thermo scratch slab
   DevBuf<double> d_ctab, d_cout, d_cscratch; DevBuf<unsigned long long> d_cdiag;
   DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
@@ -282,32 +279,38 @@ const char* mcs_last_error(void) { return g_err.c_str(); }
 int mcs_get_layout(const mcs_params* p, mcs_layout* out) { mcs_tally_layout(p, out); return 0; }
 
 int mcs_create(const mcs_params* p, int device, void* stream, mcs_ctx** out) {
+  return mcs_create_with_options(p, device, stream, nullptr, nullptr, 0, 1, out);
+}
+
+int mcs_option_count(void) { return MCS_OPT_COUNT; }
+int mcs_option_describe(int key, mcs_option_desc* out) {
+  if (!out) return fail("mcs_option_describe: null argument");
+  const McsOptionRow* r = mcs_option_row(key);
+  if (!r) return fail(format("mcs_option_describe: unknown option key %d (the keys are 0..%d, enum mcs_option)", key, MCS_OPT_COUNT - 1));
+  *out = mcs_option_desc{r->key, r->when, r->applies, 0, r->min, r->max, r->dflt, r->name, r->env};
+  return 0;
+}
+
+int mcs_create_with_options(const mcs_params* p, int device, void* stream, const int32_t* keys, const int64_t* values, int n_options,
+                            int use_env, mcs_ctx** out) {
   if (!p || !out) return fail("mcs_create: null argument");
   if (p->abi_version != MCS_ABI_VERSION) return fail("mcs_create: abi_version mismatch");
   if (p->use_custom_frg) return fail("Use of custom f(r_g) not yet supported. Add functionality or use standard. (src/scattering.jl:52-53)");
   if (!p->do_retro) return fail("Code not set up for analytical PRP calculations. (src/prob_return.jl:134)");
   if (p->num_psd_mom_bins + 1 > MCS_PSD_MAX || p->num_psd_tht_bins + 1 > MCS_PSD_MAX) return fail("mcs_create: psd bins exceed psd_max (src/parameters.jl:18)");
   if (p->n_grid < 1 || p->n_grid + 2 > mcs_transport_max_entries()) return fail("mcs_create: n_grid + 2 exceeds the LDS table size (208 entries; psd_max = 200 in src/parameters.jl:18)");
+  // the options, before the device is touched: a bad list fails the same way without a GPU
+  int64_t opt[MCS_OPT_COUNT];
+  std::string why;
+  if (mcs_options_resolve(keys, values, n_options, use_env != 0, p->state_fp32, opt, &why) != MCS_OPTION_OK)
+    return fail("mcs_create_with_options: " + why);
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (ndev <= 0) return fail("mcs_create: no HIP device visible; the transport path has no CPU fallback");
   if (device < 0 || device >= ndev) return fail("mcs_create: device ordinal out of range");
   HIPCHK(hipSetDevice(device));
   std::unique_ptr<mcs_ctx> c(new mcs_ctx());      // (a failing call below must not leak the context and what it has allocated so far)
-  c->force_general = env_on("MCS_FORCE_GENERAL");
-  c->tail_merge = env_not_off("MCS_TAIL_MERGE");
-  c->k1_ws = env_tristate("MCS_K1_WS");
-  c->ws_auto_min = env_int("MCS_WS_AUTO_MIN", 0, LLONG_MAX, c->ws_auto_min);
-  c->park = env_not_off("MCS_PARK");
-  c->tail_ring = env_not_off("MCS_TAIL_RING");
-  c->tail_loop = (int)env_int("MCS_TAIL_LOOP", 0, 32, c->tail_loop);
-  c->f32_loop = env_on("MCS_F32_LOOP");
-  c->f32_exact = env_on("MCS_F32_EXACT");
-  c->tail_budget = (int)env_int("MCS_TAIL_BUDGET", 0, INT_MAX, c->tail_budget);
-  c->pp_side_cus = (int)env_int("MCS_PIPE_SIDE_CUS", 0, 128, c->pp_side_cus);
-  c->refill_min = (int)env_int("MCS_REFILL_MIN", 1, 48, c->refill_min);
-  c->defer_k = (int)env_int("MCS_DEFER_K", 1, 40, c->defer_k);
-  c->tally_replicas = !env_on("MCS_TALLY_REPLICAS_OFF");
+  std::memcpy(c->opt, opt, sizeof opt);
   c->P = *p;
   mcs_tally_layout(p, &c->L);
   c->device = device;
@@ -320,7 +323,7 @@ int mcs_create(const mcs_params* p, int device, void* stream, mcs_ctx** out) {
   if (reserve(c->d_tab, (long long)8 * ne) || reserve(c->d_counters, 8) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1) ||
       reserve(c->h_back, 4))
     return 1;
-  if (c->tally_replicas) {
+  if (c->o(MCS_OPT_TALLY_REPLICAS)) {
     c->rep_n = c->L.total;     // the whole tally buffer: the three big histograms are 99 % of it
     const size_t nrep = (size_t)MCS_TALLY_REPLICAS * (size_t)c->rep_n;
     if (reserve(c->d_tally_rep, (long long)nrep)) return 1;
@@ -607,10 +610,28 @@ int mcs_set_launch(mcs_ctx* c, int blocks, int threads) {
 }
 
 int mcs_set_debug_finals(mcs_ctx* c, int on) { c->debug_finals = on != 0; return 0; }
+// Host words only: the launches that are queued have their constants already, the next ones read these.
+int mcs_set_option(mcs_ctx* c, int key, int64_t value) {
+  if (!c) return fail("mcs_set_option: null context");
+  std::string why;
+  if (mcs_option_check_set(key, value, c->P.state_fp32, c->pp_masks_tried, &why) != MCS_OPTION_OK) return fail("mcs_set_option: " + why);
+  c->opt[key] = value;
+  return 0;
+}
+int mcs_get_option(mcs_ctx* c, int key, int64_t* value) {
+  if (!c || !value) return fail("mcs_get_option: null argument");
+  if (!mcs_option_row(key)) return fail(format("mcs_get_option: unknown option key %d (the keys are 0..%d, enum mcs_option)", key, MCS_OPT_COUNT - 1));
+  *value = c->opt[key];
+  return 0;
+}
 int mcs_set_tail_slicing(mcs_ctx* c, int budget_trips) {
-  if (budget_trips < 0 || budget_trips > (1 << 24)) return fail("mcs_set_tail_slicing: budget out of range");
-  if (budget_trips > 0 && c->P.state_fp32) return fail("mcs_set_tail_slicing: the fp32-state kernels are not sliced (fp64 contexts only)");
-  c->tail_budget = budget_trips;
+  if (!c) return fail("mcs_set_tail_slicing: null context");
+  switch (mcs_option_check_set(MCS_OPT_TAIL_BUDGET, budget_trips, c->P.state_fp32, c->pp_masks_tried, nullptr)) {
+    case MCS_OPTION_OK: break;
+    case MCS_OPTION_APPLIES: return fail("mcs_set_tail_slicing: the fp32-state kernels are not sliced (fp64 contexts only)");
+    default: return fail("mcs_set_tail_slicing: budget out of range");
+  }
+  c->opt[MCS_OPT_TAIL_BUDGET] = budget_trips;
   return 0;
 }
 int mcs_last_launches(mcs_ctx* c) { return c->tail_rounds_last; }
@@ -640,7 +661,7 @@ int mcs_run_pcut_indexed(mcs_ctx* c, int i_pcut, const int64_t* dev_gidx, int64_
 
 // The K1 kernel the context's current species runs, its block size and the workgroups of it a CU holds (2 for the fp64 kernels --
 // 78 KB of LDS each --, 1 for the wave-specialised ones, 3 for the fp32-state kernels -- the organised one: 168 VGPRs, 51 KB).
-// n: the population that decides the wave-specialised form (MCS_K1_WS, MCS_WS_AUTO_MIN).  sliced: a launch that suspends and resumes
+// n: the population that decides the wave-specialised form (MCS_OPT_K1_WS, MCS_OPT_WS_AUTO_MIN).  sliced: a launch that suspends and resumes
 // particles -- the tail slicing of mcs_run_pcut* (mcs_set_tail_slicing) runs the general kernel's sliced form for every species, the
 // pipelined loop (which refuses tail slicing) the sliced form of the species' own kernel.  explicit_geometry: the launch has the
 // geometry of mcs_set_launch (never the wave-specialised form).
@@ -649,17 +670,17 @@ static bool is_ws(int kernel) { return kernel == K1_WS || kernel == K1_WS_ETF; }
 static K1Plan k1_plan(const mcs_ctx* c, long long n, bool sliced, bool explicit_geometry) {
   const mcs_params& P = c->P;
   // the specialised kernel for the common configuration (see transport_body<PLAIN> in mcs_transport.hip)
-  const bool plain_but_etf = !c->force_general && c->all_parallel && !P.dont_scatter && !P.use_custom_epsB && !P.dont_DSA &&
+  const bool plain_but_etf = !c->o(MCS_OPT_FORCE_GENERAL) && c->all_parallel && !P.dont_scatter && !P.use_custom_epsB && !P.dont_DSA &&
                              !(P.feb_downstream > 0) && c->aa >= 1 && c->tb.n_xspec == 0 && !(c->h_inj_fracs[c->i_ion - 1] < 1);
   const bool plain = plain_but_etf && !(P.energy_transfer_frac > 0);
   const bool plain_etf = plain_but_etf && !plain;      // the ions of a run with energy transfer: PLAIN with that one flag at run time
   // the specialised kernel for electrons with radiative losses (transport_body<false, LOSSY>): the loss in line in the common pass
-  const bool lossy = !c->force_general && P.do_rad_losses && c->aa < 1 && !P.use_custom_epsB && !P.dont_scatter;
-  if (P.state_fp32) return {c->f32_exact ? K1_F32_LOOP_EXACT : (c->f32_loop ? K1_F32_LOOP : (lossy ? K1_F32_LOSSY : K1_F32)), 256, 3};
-  if (sliced && c->tail_budget > 0) return {K1_SLICED, 256, 2};
+  const bool lossy = !c->o(MCS_OPT_FORCE_GENERAL) && P.do_rad_losses && c->aa < 1 && !P.use_custom_epsB && !P.dont_scatter;
+  if (P.state_fp32) return {c->o(MCS_OPT_F32_EXACT) ? K1_F32_LOOP_EXACT : (c->o(MCS_OPT_F32_LOOP) ? K1_F32_LOOP : (lossy ? K1_F32_LOSSY : K1_F32)), 256, 3};
+  if (sliced && c->o(MCS_OPT_TAIL_BUDGET) > 0) return {K1_SLICED, 256, 2};
   if (sliced) return {plain ? K1_PLAIN_SLICED : (lossy ? K1_LOSSY_SLICED : (plain_etf ? K1_PLAIN_ETF_SLICED : K1_SLICED)), 256, 2};
   // the wave-specialised form of PLAIN / PLAIN_ETF (mcs_transport_ws.inc), not with an explicit launch geometry
-  if ((plain || plain_etf) && !explicit_geometry && (c->k1_ws == 1 || (c->k1_ws == 2 && n >= c->ws_auto_min)))
+  if ((plain || plain_etf) && !explicit_geometry && (c->o(MCS_OPT_K1_WS) == 1 || (c->o(MCS_OPT_K1_WS) == 2 && n >= c->o(MCS_OPT_WS_AUTO_MIN))))
     return {plain ? K1_WS : K1_WS_ETF, mcs_transport_ws_threads(), 1};
   return {plain ? K1_PLAIN : (lossy ? K1_LOSSY : (plain_etf ? K1_PLAIN_ETF : K1_GENERAL)), 256, 2};
 }
@@ -683,9 +704,9 @@ static void set_claim(const mcs_ctx* c, KArgs& a, int claim_max) {
   a.claim_max = claim_max;
   // a wave whose live lanes all wait for company (fewer than defer_k of them) must be able to refill: with
   // defer_k + refill_min <= 64 either defer_k lanes are live or refill_min are idle (see the deferral in transport_body)
-  a.defer_k = dense ? std::min(c->defer_k, 64 - c->refill_min) : 1;
-  a.wait_full = dense && c->park;
-  a.tail_merge = dense && c->tail_merge;
+  a.defer_k = dense ? (int)std::min(c->o(MCS_OPT_DEFER_K), 64 - c->o(MCS_OPT_REFILL_MIN)) : 1;
+  a.wait_full = dense && c->o(MCS_OPT_PARK);
+  a.tail_merge = dense && c->o(MCS_OPT_TAIL_MERGE);
 }
 
 // A launch of n_x resumed particles spread over `waves` waves: a pass costs a wave the same with 1 live lane as with 64, but the rare
@@ -725,10 +746,10 @@ static void fill_kargs(mcs_ctx* c, KArgs& a, int i_pcut, long long n, long long 
   a.i_iter = c->i_iter; a.i_ion = c->i_ion; a.i_pcut = i_pcut;
   a.n = n; a.i_prt_offset = i_prt_offset; a.i_prt_stride = i_prt_stride; a.gidx = dev_gidx;
   a.retro_cap = c->retro_cap;
-  a.refill_min = c->refill_min;
+  a.refill_min = (int)c->o(MCS_OPT_REFILL_MIN);
   set_claim(c, a, 64);
-  a.tail_ring = c->tail_ring ? 1 : 0;
-  a.tail_loop = c->tail_ring ? c->tail_loop : 0;
+  a.tail_ring = c->o(MCS_OPT_TAIL_RING) ? 1 : 0;
+  a.tail_loop = c->o(MCS_OPT_TAIL_RING) ? (int)c->o(MCS_OPT_TAIL_LOOP) : 0;
   // iseed_mod - i_prt, src/particle_loop.jl:35-40
   a.seed_base = (unsigned long long)((long long)(c->i_iter - 1) * c->P.n_pts_max * c->tb.n_pcuts * c->P.n_ions +
                                      (long long)(c->i_ion - 1) * c->P.n_pts_max * c->tb.n_pcuts +
@@ -754,7 +775,7 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
   // particles in the host copy it hands out (nine fills per pcut less in the timed path).
   if (n > 0) HIPCHK(hipMemsetAsync(c->d_lsave, 0, (size_t)n, c->stream));
   HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
-  const int budget = (c->P.state_fp32 || n == 0) ? 0 : c->tail_budget;      // (the fp32 study kernel is not sliced)
+  const int budget = (c->P.state_fp32 || n == 0) ? 0 : (int)c->o(MCS_OPT_TAIL_BUDGET);      // (the fp32 study kernel is not sliced)
   if (budget > 0) {
     // one entry per lane a launch can hold: 2 workgroups of 256 threads per CU, or the geometry of mcs_set_launch if that is larger
     long long need_cap = (long long)2 * c->n_cu * 256;
@@ -840,7 +861,7 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   if (!c->have_grid || !c->have_cuts) return fail("mcs_run_pcuts_fused: grid/cuts not set");
   if (i_pcut_first < 1 || i_pcut_last > c->tb.n_pcuts || i_pcut_last < i_pcut_first) return fail("mcs_run_pcuts_fused: pcut range");
   if (!n_target || !n_use_out || !n_saved_out || !i_mult_out) return fail("mcs_run_pcuts_fused: null argument");
-  if (c->tail_budget > 0 || c->blocks > 0) return fail("mcs_run_pcuts_fused: not with sliced launches or an explicit launch geometry");
+  if (c->o(MCS_OPT_TAIL_BUDGET) > 0 || c->blocks > 0) return fail("mcs_run_pcuts_fused: not with sliced launches or an explicit launch geometry");
   const int npc = i_pcut_last - i_pcut_first + 1;
   long long cap_n = c->n;
   for (int k = 0; k < npc; ++k) { if (n_target[k] < 1) return fail("mcs_run_pcuts_fused: n_target < 1"); if (n_target[k] > cap_n) cap_n = n_target[k]; }
@@ -939,7 +960,7 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
   if (i_pcut_first < 1 || i_pcut_last > c->tb.n_pcuts || i_pcut_last < i_pcut_first) return fail("mcs_run_pcuts_pipelined: pcut range");
   if (!n_target || !n_use_out || !n_saved_out || !i_mult_out) return fail("mcs_run_pcuts_pipelined: null argument");
   if (c->P.state_fp32) return fail("mcs_run_pcuts_pipelined: not for the fp32-state variant");
-  if (c->tail_budget > 0 || c->blocks > 0) return fail("mcs_run_pcuts_pipelined: not with sliced launches or an explicit launch geometry");
+  if (c->o(MCS_OPT_TAIL_BUDGET) > 0 || c->blocks > 0) return fail("mcs_run_pcuts_pipelined: not with sliced launches or an explicit launch geometry");
   if (long_draws < 64 || long_draws > 2000000000LL) return fail("mcs_run_pcuts_pipelined: long_draws out of range (64 .. 2e9)");
   const int npc = i_pcut_last - i_pcut_first + 1;
   long long cap_n = c->n;
@@ -964,10 +985,10 @@ int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const
     return 1;
   if (!c->pp_masks_tried) {
     c->pp_masks_tried = true;
-    if (c->pp_side_cus > 0 && c->pp_side_cus < c->n_cu) {
+    if ((int)c->o(MCS_OPT_PIPE_SIDE_CUS) > 0 && (int)c->o(MCS_OPT_PIPE_SIDE_CUS) < c->n_cu) {
       const int words = (c->n_cu + 31) / 32;
       std::vector<uint32_t> m_side((size_t)words, 0u), m_main((size_t)words, 0u);
-      for (int i = 0; i < c->n_cu; ++i) (i < c->pp_side_cus ? m_side : m_main)[(size_t)(i >> 5)] |= 1u << (i & 31);
+      for (int i = 0; i < c->n_cu; ++i) (i < (int)c->o(MCS_OPT_PIPE_SIDE_CUS) ? m_side : m_main)[(size_t)(i >> 5)] |= 1u << (i & 31);
       if (c->pp_s1m.create_cu_masked((uint32_t)words, m_main.data()) != hipSuccess ||
           c->pp_s2m.create_cu_masked((uint32_t)words, m_side.data()) != hipSuccess) {
         (void)hipGetLastError();
@@ -1061,7 +1082,7 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
       // (the main launch is persistent and fills every slot of the chip: it leaves room for the side stream's workgroups, which would
       // otherwise wait for its workgroups to leave -- and run after it instead of beside it)
       int blocks_a = persistent_grid(nA, threads, full);
-      if (masked) { if (s1 == c->pp_s1m && blocks_a > 2 * (c->n_cu - c->pp_side_cus)) blocks_a = 2 * (c->n_cu - c->pp_side_cus); }
+      if (masked) { if (s1 == c->pp_s1m && blocks_a > 2 * (c->n_cu - (int)c->o(MCS_OPT_PIPE_SIDE_CUS))) blocks_a = 2 * (c->n_cu - (int)c->o(MCS_OPT_PIPE_SIDE_CUS)); }
       else if (side_blocks > 0 && blocks_a > full - side_blocks) blocks_a = (int)(full - side_blocks);
       HIPCHK(mcs_launch_transport(c->pp_dargs, k1.kernel, blocks_a, threads, s1));
       HIPCHK(hipEventRecord(c->ev1, s1));
@@ -1112,7 +1133,7 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     const long long im_hi = target / (sofar + n_T) > 1 ? target / (sofar + n_T) : 1;
     const long long im_lo = sofar > 0 ? (target / sofar > 1 ? target / sofar : 1) : -1;
     // (more long histories than the side stream's CUs hold at 16 per wave, twice over: beside the main launch they would outlast it)
-    const long long side_cap = masked ? (long long)c->pp_side_cus * 8 * 16 * 2 : (long long)side_max * 4 * 16 * 2;
+    const long long side_cap = masked ? (long long)(int)c->o(MCS_OPT_PIPE_SIDE_CUS) * 8 * 16 * 2 : (long long)side_max * 4 * 16 * 2;
     if ((last || im_lo != im_hi || n_T > side_cap) && n_T > 0) {
       // i_mult depends on how many of the long histories end saved (or this is the last pcut, or they are too many): they finish first
       HIPCHK(hipMemsetAsync(pc + 5, 0, 2 * sizeof(unsigned long long), s_alone));

@@ -1,8 +1,11 @@
 // mcs_hip_owned.h -- what the context of mcs_api.hip owns, each in a type that cannot be left half-valid: device and pinned
-// buffers, the particle population's nine arrays, streams, events; and the three rules by which the library reads its environment.
+// buffers, the particle population's nine arrays, streams, events.  (The rules by which the library reads its environment, once
+// declared here, live with the option table in mcs_options.h, which this header includes.)
 // Host code only (the runtime API, no kernels): a plain C++ compiler builds it, tests/host/hip_owned_main.cpp does.
 #pragma once
 #include <hip/hip_runtime_api.h>
+
+#include "mcs_options.h"
 
 #include <cstdint>
 #include <cstdlib>
@@ -88,18 +91,3 @@ struct Event : HipHandle<hipEvent_t, hipEventDestroy> {
   hipError_t create() { return created(hipEventCreate(fresh())); }
   hipError_t create_untimed() { return created(hipEventCreateWithFlags(fresh(), hipEventDisableTiming)); }
 };
-
-// ---- the environment: switches for tests and A/B measurements, read once per context
-// on iff the first character is '1'
-inline bool env_on(const char* name) { const char* e = std::getenv(name); return e && e[0] == '1'; }
-// off iff the first character is '0'
-inline bool env_not_off(const char* name) { const char* e = std::getenv(name); return !(e && e[0] == '0'); }
-// an integer inside lo..hi, else (unset, outside, not a number that lies inside) the default stays
-inline long long env_int(const char* name, long long lo, long long hi, long long dflt) {
-  const char* e = std::getenv(name);
-  if (!e) return dflt;
-  const long long v = std::atoll(e);
-  return v >= lo && v <= hi ? v : dflt;
-}
-// '1' -> 1, '0' -> 0, anything else or unset -> 2
-inline int env_tristate(const char* name) { const char* e = std::getenv(name); return !e ? 2 : (e[0] == '1' ? 1 : (e[0] == '0' ? 0 : 2)); }

@@ -75,6 +75,9 @@ class RunResult:
                                                                   # loop on an EMPTY population (the pcuts after the one that saved nobody)
     species_spans: list = dataclasses.field(default_factory=list)    # [(i_iter, i_ion, context index, t_start, t_end)]: host times
                                                                   # (time.perf_counter) around each species' transport, run(species_backends=...)
+    options: dict = dataclasses.field(default_factory=dict)          # what the run ran with: the primary backend's options() (a backend that
+                                                                  # has them: the run options of the HIP context, by name) and the driver's own
+                                                                  # fused_pcuts, fused_chunk, long_draws, long_imult_max as actually used
 
 
 class Comm:
@@ -252,7 +255,7 @@ def _pcuts_fused(rs, be, i_iter, i_ion, targets, out_stats, out_empty):
     t0 = time.perf_counter()
     # (in chunks: a species that ends early -- the thermal electrons in their first pcut -- would otherwise pay ~35 us of
     # empty launches for every remaining pcut; one read-back per chunk of 12 instead of one per pcut)
-    chunk = max(1, int(os.environ.get("MCS_FUSED_CHUNK", "12")))
+    chunk = rs.fused_chunk
     counts = ([], [], [], [])
     for c0 in range(1, rs.n_pcuts + 1, chunk):
         c1 = min(c0 + chunk - 1, rs.n_pcuts)
@@ -387,9 +390,8 @@ def _species_transport(rs, be, i_iter, i_ion, hook, out_stats, out_empty):
     p_pcut_hi = inputs.pcut_hi(cfg.EN_PCUT_HI, sp.mass)
     # One rank, no per-pcut hook: the whole pcut loop of the species is queued on the device at once -- n_saved, i_mult and
     # the next population's size are decided there (mcs_run_pcuts_fused), one read-back per species instead of one per pcut.
-    fused = (rs.fused_pcuts and not rs.multi and hook is None and hasattr(be, "run_pcuts_fused") and rs.n_pcuts >= 1
-             and os.environ.get("MCS_FUSED_PCUTS", "1") != "0")
-    # Long histories told apart (long_draws > 0; MCS_LONG_DRAWS): the next population is ordered non-long before long, which lets a
+    fused = rs.fused_pcuts and not rs.multi and hook is None and hasattr(be, "run_pcuts_fused") and rs.n_pcuts >= 1
+    # Long histories told apart (long_draws > 0): the next population is ordered non-long before long, which lets a
     # pcut's long histories finish beside the next pcut (mcs_run_pcuts_pipelined; one rank).  A backend without that entry point
     # (the oracle) is told the order (set_long_draws) and runs the ordinary loop: same populations, same streams, same results.
     pipelined = False
@@ -571,8 +573,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         verbose: bool = False, gather_max: int = 1 << 17, skew_max: float = 1.1,
         finalize: bool = False, smoothing=None, on_iteration_end: Optional[Callable] = None,
         first_iter: int = 1, iter_state=None, species_tallies: str = "full", final_full_read: bool = True,
-        before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: bool = True, long_draws: Optional[int] = None,
-        long_imult_max: Optional[int] = None, species_backends: Optional[list] = None) -> RunResult:
+        before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
+        long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -613,6 +615,13 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     species 1..k and species k's own per-species sections) are in species order, and what the hook writes back through
     `backend.write_tallies` is what the later species start from.  RunResult.species_spans says what overlapped.  None or []:
     the one-context loop.  Single process without a communicator, no long_draws and no before_pcut.
+    fused_pcuts, fused_chunk, long_draws, long_imult_max: how the driver walks a species' pcuts; these arguments are the supported way
+    to set them.  fused_pcuts: one rank without a per-pcut hook queues the pcuts on the device in calls of fused_chunk pcuts
+    (mcs_run_pcuts_fused), False: one mcs_run_pcut + mcs_new_pcut per pcut.  long_draws > 0: histories of at least that many random
+    draws finish beside the next pcut (mcs_run_pcuts_pipelined), in pcuts whose predecessor split by at most long_imult_max (<= 0: in
+    every pcut).  An argument left out (None) takes the default an environment variable gives, else the built-in one: MCS_FUSED_PCUTS
+    (off iff "0"; True), MCS_FUSED_CHUNK (12), MCS_LONG_DRAWS (0; not read by a multi-rank run), MCS_LONG_IMULT_MAX (8).  The values used
+    are in RunResult.options, beside the run options of the backend's context (HipBackend.options()).
     """
     import torch
     comm = comm or Comm(False)
@@ -623,6 +632,13 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         long_draws = int(os.environ.get("MCS_LONG_DRAWS", "0")) if not multi else 0
     if long_imult_max is None:
         long_imult_max = int(os.environ.get("MCS_LONG_IMULT_MAX", "8"))
+    if fused_pcuts is None:
+        fused_pcuts = os.environ.get("MCS_FUSED_PCUTS", "1") != "0"
+    if fused_chunk is None:
+        fused_chunk = int(os.environ.get("MCS_FUSED_CHUNK", "12"))
+    fused_chunk = max(1, int(fused_chunk))
+    options = dict(backend.options()) if hasattr(backend, "options") else {}
+    options.update(fused_pcuts=bool(fused_pcuts), fused_chunk=fused_chunk, long_draws=int(long_draws), long_imult_max=int(long_imult_max))
     secondaries = list(species_backends or [])
     # The state of the run, shared by the steps above.  dev_t: live device tensors of the tallies (HIP backend with torch_tallies):
     # the multi-GPU merge then runs in place on the device; otherwise (CPU test backends) through read_tallies / write_tallies.
@@ -632,8 +648,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         prob=prob, L=L, backend=backend, ctxs=[backend] + secondaries, comm=comm, is_root=comm.rank == 0, multi=multi,
         dev_t=backend.tally_tensors() if (multi and hasattr(backend, "tally_tensors")) else None,
         n_pcuts=len(prob.pcuts) if max_pcuts is None else min(max_pcuts, len(prob.pcuts)), last_iter=first_iter + n_itrs - 1,
-        verbose=verbose, gather_max=gather_max, skew_max=skew_max, fused_pcuts=fused_pcuts, long_draws=long_draws,
-        long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
+        verbose=verbose, gather_max=gather_max, skew_max=skew_max, fused_pcuts=fused_pcuts, fused_chunk=fused_chunk,
+        long_draws=long_draws, long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
         G_f=None, G_i=None, G_pool=None, stats=[], per_species=[], local_steps=[], empty_launches=[], species_spans=[], iter_finals=[])
     # the step counters are never reset: this rank's running total.  A context that has run before (run() called again with
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
@@ -710,7 +726,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             on_iteration_end(i_iter)
 
     return RunResult(rs.G_f, rs.G_i, rs.per_species, rs.stats, *_steps(rs.G_i, P.n_grid), rs.iter_finals, it_state,
-                     rs.local_steps, rs.empty_launches, rs.species_spans)
+                     rs.local_steps, rs.empty_launches, rs.species_spans, options)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over

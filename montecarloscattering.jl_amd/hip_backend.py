@@ -24,12 +24,15 @@ def _dp(a: np.ndarray):
 class HipBackend:
     name = "hip"
 
-    def __init__(self, device: int = 0, stream: int = 0, torch_tallies: bool = False, debug_finals: bool = False):
+    def __init__(self, device: int = 0, stream: int = 0, torch_tallies: bool = False, debug_finals: bool = False,
+                 options: dict | None = None, use_env: bool = True):
         """torch_tallies: keep the flat tally buffers in torch CUDA tensors, so that torch.distributed can
         all-reduce them in place (multi-GPU driver).  The context then works on torch's CURRENT stream
         (passed to mcs_create), so torch ops and library kernels are ordered by that stream; with
         stream=0 and torch_tallies=False the context creates its own blocking stream.
-        debug_finals: record per-particle end states for finals() (tests; 24 B of stores per particle)."""
+        debug_finals: record per-particle end states for finals() (tests; 24 B of stores per particle).
+        options: run options of the context by name, e.g. {"k1_ws": 1} (capi.option_table() lists them, include/mcs.h documents
+        them); use_env=False: the MCS_* environment variables, otherwise the default of every option not given, are not read."""
         self.lib = capi.load_library()          # raises MissingNativeLibrary
         if self.lib.mcs_abi_version() != capi.MCS_ABI_VERSION:
             raise RuntimeError("libmcs_hip.so ABI version mismatch")
@@ -37,6 +40,8 @@ class HipBackend:
         self.stream = int(stream)
         self.torch_tallies = torch_tallies
         self.debug_finals = debug_finals
+        self._options = {capi.option_key(name): int(v) for name, v in (options or {}).items()}     # KeyError: no such option
+        self.use_env = bool(use_env)
         self.h = ct.c_void_p(None)
         self._bound = None
 
@@ -53,7 +58,10 @@ class HipBackend:
             import torch
             torch.cuda.set_device(self.device)
             self.stream = int(torch.cuda.current_stream(self.device).cuda_stream)
-        self._chk(self.lib.mcs_create(ct.byref(self.P), self.device, ct.c_void_p(self.stream or None), ct.byref(self.h)))
+        keys = (ct.c_int32 * len(self._options))(*self._options.keys())
+        values = (ct.c_int64 * len(self._options))(*self._options.values())
+        self._chk(self.lib.mcs_create_with_options(ct.byref(self.P), self.device, ct.c_void_p(self.stream or None), keys, values,
+                                                   len(self._options), int(self.use_env), ct.byref(self.h)))
         if self.debug_finals:
             self._chk(self.lib.mcs_set_debug_finals(self.h, 1))
         if self.torch_tallies:
@@ -99,6 +107,21 @@ class HipBackend:
     def set_tail_slicing(self, budget_trips: int):
         """Sliced tail of run_pcut* (mcs_set_tail_slicing): 0 = one launch per pcut."""
         self._chk(self.lib.mcs_set_tail_slicing(self.h, int(budget_trips)))
+
+    def set_option(self, name: str, value: int):
+        """Change a run option for the launches queued from now on (mcs_set_option); RuntimeError with the library's message where
+        the option, the value or the moment is not allowed -- the context is then unchanged."""
+        self._chk(self.lib.mcs_set_option(self.h, capi.option_key(name), int(value)))
+
+    def get_option(self, name: str) -> int:
+        """The value the next launch will use (mcs_get_option)."""
+        v = ct.c_int64(0)
+        self._chk(self.lib.mcs_get_option(self.h, capi.option_key(name), ct.byref(v)))
+        return int(v.value)
+
+    def options(self) -> dict:
+        """Every run option's effective value, by name."""
+        return {name: self.get_option(name) for name in capi.option_table()}
 
     def last_launches(self) -> int:
         return int(self.lib.mcs_last_launches(self.h))
@@ -260,7 +283,7 @@ class HipBackend:
 
     def run_pcuts_fused(self, i_pcut_first: int, i_pcut_last: int, n_target):
         """mcs_run_pcuts_fused: the pcuts first .. last of the current species queued back to back, n_saved / i_mult / the next
-        population's size decided on the device -> (n_use, n_saved, i_mult, kernel_ms) per pcut.  MCS_FUSED_PCUTS=0: not offered."""
+        population's size decided on the device -> (n_use, n_saved, i_mult, kernel_ms) per pcut.  driver.run(fused_pcuts=False): not used."""
         npc = i_pcut_last - i_pcut_first + 1
         tg = np.ascontiguousarray(n_target, dtype=np.int64)
         assert tg.shape == (npc,)
