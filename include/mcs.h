@@ -468,8 +468,26 @@ int mcs_photon_ic(mcs_ctx* ctx, const double* mom_edge_cgs, double mc_e, int j_m
 /* ---- test / measurement hooks ------------------------------------------- */
 /* evaluate device math/RNG primitives (bit-parity tests): fn ids in mcs_fn */
 enum mcs_fn { MCS_FN_SIN = 0, MCS_FN_COS, MCS_FN_ASIN, MCS_FN_ACOS, MCS_FN_ATAN2, MCS_FN_LOG10,
-              MCS_FN_MOD2PI, MCS_FN_SQRT, MCS_FN_DIV, MCS_FN_HYPOT1, MCS_FN_UNIFORM };
+              MCS_FN_MOD2PI, MCS_FN_SQRT, MCS_FN_DIV, MCS_FN_HYPOT1, MCS_FN_UNIFORM,
+              /* The forms the transport kernel itself runs, evaluated by a kernel inside ITS translation unit (mcs_k_eval_hot in
+               * csrc/mcs_transport.hip: MCS_DEVICE_FAST_SQRT, the kernel's own division helpers and coefficient tables); the codes
+               * above are evaluated in csrc/mcs_population.hip, the build of K3.  SQRT_FAST / SQRT_NN: mcsm::sqrt_ / sqrt_nn_;
+               * SQRT_NN_K, ASIN_TK, MOD2PI_K: the tail loop's spellings; HYPOT1_HOT: mcsm::hypot1; FDIV: fdiv(a, b);
+               * DIV_R / DIV_R2: div_r(a, b, r) and div_r(2 a, b, r) with ONE r = rcp_refined(b) per lane (DIV_R2 must be exactly
+               * twice DIV_R); SIN_T / COS_T: the two outputs of mcsm::sincos_t; ASIN_T: mcsm::asin_t. */
+              MCS_FN_SQRT_FAST, MCS_FN_SQRT_NN, MCS_FN_SQRT_NN_K, MCS_FN_HYPOT1_HOT, MCS_FN_FDIV, MCS_FN_DIV_R, MCS_FN_DIV_R2,
+              MCS_FN_SIN_T, MCS_FN_COS_T, MCS_FN_ASIN_T, MCS_FN_ASIN_TK, MCS_FN_MOD2PI_K,
+              MCS_FN_COUNT };
+/* an fn outside the enum is an error (with a message), not a result */
 int mcs_eval_fn(mcs_ctx* ctx, int fn, int64_t n, const double* a, const double* b, double* out);
+/* One scatter (src/scattering.jl:29-101) of n particle states, in the spelling `form` of the transport kernel:
+ *   0  refresh_scatter + scattering(): the common pass of every K1 kernel;
+ *   1  refresh_scatter_k, scatter_draws, scatter_cone, scattering_rest: the in-line loss of the lossy kernel and the tail ring;
+ *   2  the same with scattering_rest_k and the TailK constants: the tail loop.
+ * in [n][10]: key (the 64 bits of the slot are the particle's RNG key, not a number), draw index (even, < 2^32), aa, gyro_denom,
+ * ptot_pf, gam_pf, xn_per, pb_pf, p_perp, phi.  out [n][5]: pb_pf, p_perp, phi, gyro_period, cos_max.  pe_crit, game_crit and eta_mfp
+ * are those of the context's mcs_params.  All three forms must equal the oracle bit for bit (tests/test_gpu_math_forms.py). */
+int mcs_eval_scatter(mcs_ctx* ctx, int form, int64_t n, const double* in, double* out);
 /* per-particle end state of the last mcs_run_pcut (bit-parity tests): i_reason
  * (0 = saved), helix_count, retro step count, final ptot_pf and x. Any pointer may be NULL.
  * The kernel records them only after mcs_set_debug_finals(ctx, 1) (24 B of stores per particle

@@ -53,7 +53,16 @@ MCS_HD double fma_(double a, double b, double c) { return __builtin_fma(a, b, c)
  * v_rsq_f64 + two Goldschmidt/Newton steps wrapped in an exponent rescale (for arguments
  * below 2^-767) and a class test: 17 instructions.  With MCS_DEVICE_FAST_SQRT the same
  * iteration is used WITHOUT the rescale (the path never takes roots of subnormal-range
- * numbers): 10 instructions, identical bits for every normal argument and for +0. */
+ * numbers): 10 instructions, identical bits for +0, +inf and every argument from 2^-968 up --
+ * down to there every intermediate is the rescaled sequence's times an exact power of two; the
+ * smallest of them, the remainder d = x - g*g, is a multiple of ulp(g)^2 >= 2^-1074 and so still
+ * exact.  Below 2^-968 d is rounded to the subnormal grid and the last bit of the root may differ
+ * (measured on an MI355X, 2000 draws per binade: one-ulp differences in the binades 2^-1022 ..
+ * 2^-1011, none found from 2^-1010 up).  tests/test_gpu_math_forms.py holds the
+ * claim on the device, in the transport kernel's own translation unit, bit for bit against the
+ * correctly rounded root: test_sqrt_fast_is_correctly_rounded on 0, +inf and [2^-767, 2^1023],
+ * test_sqrt_nn_is_correctly_rounded for sqrt_nn_ on +-0 and [2^-767, 4] -- what the path
+ * passes --, test_sqrt_fast_below_the_rescale_threshold on [2^-968, 2^-767). */
 #if defined(__HIP_DEVICE_COMPILE__) && defined(MCS_DEVICE_FAST_SQRT)
 MCS_HD double sqrt_(double x) {
   const double y = __builtin_amdgcn_rsq(x);
@@ -258,7 +267,10 @@ MCS_HD double atan2(double y, double x) {
     r = bh + (p + bl);
     if (ay > ax) r = MCS_SC(MCS_PIO2_DD_0) - (r - MCS_PIO2_DD_1);
   }
-  if (x < 0.0 || (x == 0.0 && (bits_(x) >> 63))) r = MCS_SC(MCS_PI_DD_0) - (r - MCS_PI_DD_1);
+  /* the reflection about pi/2 for x < 0, and for x = -0 only where it decides the result: atan(+-0, -0) = +-pi.  With
+   * y != 0 and x = -0 the angle is pi/2 already, and reflecting it (pi - pi/2 in double-double) came out one ulp above
+   * pi/2 where IEEE 754 and Base.atan give pi/2 itself (tests/test_math.py::test_atan2_signed_zeros). */
+  if (x < 0.0 || (mx == 0.0 && (bits_(x) >> 63))) r = MCS_SC(MCS_PI_DD_0) - (r - MCS_PI_DD_1);
   return copysign_(r, y);
 }
 

@@ -55,6 +55,8 @@ hipError_t mcs_launch_accumulate_tallies(double* dT, double* sT, unsigned long l
                                          long long a_n, long long b_lo, long long b_n, long long i_lo, long long i_n, hipStream_t st);
 hipError_t mcs_launch_copy(double* dst, const double* src, long long n, hipStream_t st);
 hipError_t mcs_launch_eval(int fn, long long n, const double* a, const double* b, double* out, hipStream_t st);
+hipError_t mcs_launch_eval_hot(int fn, long long n, const double* a, const double* b, double* out, hipStream_t st);
+hipError_t mcs_launch_eval_scatter(const KArgs* a_dev, int form, long long n, const double* in, double* out, hipStream_t st);
 hipError_t mcs_launch_dndp_cr(const mcs_params* P, const double* psd, const double* gam_sf, const double* ux, const double* tabs,
                               double rest_energy, double n0, double gam0, double* out_dndp, unsigned long long* diag, hipStream_t st);
 hipError_t mcs_launch_dndp_2d(const mcs_params* P, const double* psd, const double* therm_sf, const unsigned long long* num_crossings, const double* tabs,
@@ -1326,14 +1328,38 @@ int mcs_accumulate_tallies(mcs_ctx* dst, mcs_ctx* src) {
   return 0;
 }
 
+// fn < MCS_FN_SQRT_FAST: mcs_k_eval_fn in mcs_population.hip (the build of K3); from there on: mcs_k_eval_hot in mcs_transport.hip,
+// the transport kernel's own forms in its own translation unit
 int mcs_eval_fn(mcs_ctx* c, int fn, int64_t n, const double* a, const double* b, double* out) {
+  if (!c || n < 0 || (n > 0 && (!a || !out))) return fail("mcs_eval_fn: null argument or negative n");
+  if (fn < 0 || fn >= MCS_FN_COUNT) return fail("mcs_eval_fn: unknown fn " + std::to_string(fn) + " (enum mcs_fn, include/mcs.h)");
   HIPCHK(hipSetDevice(c->device));
   if (ensure_stage(c, 3 * n + 3)) return 1;
   double *da = c->d_stage, *db = c->d_stage + n, *dout = c->d_stage + 2 * n;
   HIPCHK(hipMemcpyAsync(da, a, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(db, b ? b : a, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(mcs_launch_eval(fn, n, da, db, dout, c->stream));
+  HIPCHK(fn < MCS_FN_SQRT_FAST ? mcs_launch_eval(fn, n, da, db, dout, c->stream) : mcs_launch_eval_hot(fn, n, da, db, dout, c->stream));
   HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// One scatter per state in the transport kernel's three spellings (include/mcs.h).  The kernel reads pe_crit, game_crit and eta_mfp
+// where K1 reads them: from a KArgs in the constant address space -- the context's own, with nothing but the parameters filled in.
+int mcs_eval_scatter(mcs_ctx* c, int form, int64_t n, const double* in, double* out) {
+  if (!c || n < 0 || (n > 0 && (!in || !out))) return fail("mcs_eval_scatter: null argument or negative n");
+  if (form < 0 || form > 2) return fail("mcs_eval_scatter: unknown form " + std::to_string(form) + " (0, 1 or 2: include/mcs.h)");
+  HIPCHK(hipSetDevice(c->device));
+  if (ensure_stage(c, 15 * n + 2) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1)) return 1;
+  HIPCHK(hipStreamSynchronize(c->stream));         // (nothing queued may still read the launch constants)
+  KArgs& a = *c->h_args_pin;
+  a = KArgs{};
+  a.P = c->P;
+  double *din = c->d_stage, *dout = c->d_stage + 10 * n;
+  HIPCHK(hipMemcpyAsync(c->d_args, c->h_args_pin, sizeof(KArgs), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(din, in, (size_t)n * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(mcs_launch_eval_scatter(c->d_args, form, n, din, dout, c->stream));
+  HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }

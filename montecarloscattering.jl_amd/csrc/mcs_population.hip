@@ -323,7 +323,7 @@ extern "C" __global__ void mcs_k_copy_f64(double* dst, const double* src, long l
 extern "C" __global__ void mcs_k_eval_fn(int fn, long long n, const double* a, const double* b, double* out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  double r = 0.0;
+  double r = __builtin_nan("");      // an fn this kernel does not know (mcs_launch_eval refuses it) is no zero
   switch (fn) {
     case MCS_FN_SIN: r = mcsm::sin(a[i]); break;
     case MCS_FN_COS: r = mcsm::cos(a[i]); break;
@@ -431,6 +431,7 @@ hipError_t mcs_launch_copy(double* dst, const double* src, long long n, hipStrea
   return hipGetLastError();
 }
 hipError_t mcs_launch_eval(int fn, long long n, const double* a, const double* b, double* out, hipStream_t st) {
+  if (fn < 0 || fn > MCS_FN_UNIFORM) return hipErrorInvalidValue;
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(mcs_k_eval_fn, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fn, n, a, b, out);
   return hipGetLastError();

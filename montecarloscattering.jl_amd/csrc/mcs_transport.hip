@@ -93,6 +93,9 @@ namespace {
 // very sequence, div_r(a,b,r) its quotient step: bit-identical quotients in 8 instructions,
 // and the reciprocal can be shared by divisions with the same denominator (pb/ptot and
 // p_perp/ptot, scattering.jl:65-66) or cached while the denominator is unchanged.
+// What holds the claim: tests/test_gpu_math_forms.py (test_fdiv_is_correctly_rounded, test_div_r_with_a_shared_reciprocal) compares
+// fdiv and div_r, as compiled HERE, with IEEE division bit for bit for |a|, |b|, |a / b| in [1e-100, 1e100] and 0 / b -- quotients
+// right beside a rounding tie among them; every division of the path lies tens of decades inside (the list is in that test).
 __device__ __forceinline__ double rcp_refined(double b) {
   double r = __builtin_amdgcn_rcp(b);
   double e = __builtin_fma(-b, r, 1.0);
@@ -763,6 +766,26 @@ struct Hot {
 };
 __device__ __forceinline__ double sconst(double x) { asm volatile("" : "+s"(x)); return x; }
 __device__ __forceinline__ int sconsti(int x) { asm volatile("" : "+s"(x)); return x; }
+
+// The two constant tables of the hot forms, filled in ONE place each: transport_body (every K1 kernel), the tail loop and the
+// test kernel mcs_k_eval_hot take them from here, so a test of the forms runs on the very values the particle loop holds.
+// The 29 constants of the per-step sincos + asin, resident in VGPRs:
+__device__ __forceinline__ void hot_coef_init(mcsm::HotCoef& kc) {
+  kc.S0 = vconst(MCS_SIN_0); kc.S1 = vconst(MCS_SIN_1); kc.S2 = vconst(MCS_SIN_2); kc.S3 = vconst(MCS_SIN_3);
+  kc.S4 = vconst(MCS_SIN_4); kc.S5 = vconst(MCS_SIN_5);
+  kc.C0 = vconst(MCS_COS_0); kc.C1 = vconst(MCS_COS_1); kc.C2 = vconst(MCS_COS_2); kc.C3 = vconst(MCS_COS_3);
+  kc.C4 = vconst(MCS_COS_4); kc.C5 = vconst(MCS_COS_5);
+  kc.A0 = vconst(MCS_ASIN_0); kc.A1 = vconst(MCS_ASIN_1); kc.A2 = vconst(MCS_ASIN_2); kc.A3 = vconst(MCS_ASIN_3);
+  kc.A4 = vconst(MCS_ASIN_4); kc.A5 = vconst(MCS_ASIN_5); kc.A6 = vconst(MCS_ASIN_6); kc.A7 = vconst(MCS_ASIN_7);
+  kc.A8 = vconst(MCS_ASIN_8); kc.A9 = vconst(MCS_ASIN_9); kc.A10 = vconst(MCS_ASIN_10); kc.A11 = vconst(MCS_ASIN_11);
+  kc.A12 = vconst(MCS_ASIN_12);
+  kc.R0 = vconst(MCS_TWO_OVER_PI); kc.R1 = vconst(MCS_PIO2_0); kc.R2 = vconst(MCS_PIO2_1); kc.R3 = vconst(MCS_PIO2_2);
+}
+// ... and the seven 64-bit literals of the tail loop's forms (TailK), pinned in scalar registers:
+__device__ __forceinline__ void tail_k_init(TailK& K) {
+  K.halfpi = sconst(MCS_PIO2_DD_0); K.pio2_lo = sconst(MCS_PIO2_DD_1); K.twopi = sconst(MCS_TWOPI_DD_0); K.twopi_lo = sconst(MCS_TWOPI_DD_1);
+  K.inv_twopi = sconst(MCS_INV_TWOPI); K.sin_ul = sconst(0x1.fffffffffffffp-1); K.dmin = sconst(2.2250738585072014e-308);
+}
 
 
 // src/particle_loop.jl:652-723
@@ -1724,15 +1747,7 @@ __device__ __forceinline__ void transport_body(const KArgs* __restrict__ ka) {
 
   // the 29 constants of the per-step sincos + asin, resident in VGPRs
   mcsm::HotCoef kc;
-  kc.S0 = vconst(MCS_SIN_0); kc.S1 = vconst(MCS_SIN_1); kc.S2 = vconst(MCS_SIN_2); kc.S3 = vconst(MCS_SIN_3);
-  kc.S4 = vconst(MCS_SIN_4); kc.S5 = vconst(MCS_SIN_5);
-  kc.C0 = vconst(MCS_COS_0); kc.C1 = vconst(MCS_COS_1); kc.C2 = vconst(MCS_COS_2); kc.C3 = vconst(MCS_COS_3);
-  kc.C4 = vconst(MCS_COS_4); kc.C5 = vconst(MCS_COS_5);
-  kc.A0 = vconst(MCS_ASIN_0); kc.A1 = vconst(MCS_ASIN_1); kc.A2 = vconst(MCS_ASIN_2); kc.A3 = vconst(MCS_ASIN_3);
-  kc.A4 = vconst(MCS_ASIN_4); kc.A5 = vconst(MCS_ASIN_5); kc.A6 = vconst(MCS_ASIN_6); kc.A7 = vconst(MCS_ASIN_7);
-  kc.A8 = vconst(MCS_ASIN_8); kc.A9 = vconst(MCS_ASIN_9); kc.A10 = vconst(MCS_ASIN_10); kc.A11 = vconst(MCS_ASIN_11);
-  kc.A12 = vconst(MCS_ASIN_12);
-  kc.R0 = vconst(MCS_TWO_OVER_PI); kc.R1 = vconst(MCS_PIO2_0); kc.R2 = vconst(MCS_PIO2_1); kc.R3 = vconst(MCS_PIO2_2);
+  hot_coef_init(kc);
 
   Pt p;
   Rng rng;
@@ -2265,8 +2280,7 @@ __device__ __forceinline__ void transport_body(const KArgs* __restrict__ ka) {
       unsigned e = (rrow + jj) & 63u;
       const unsigned long long m_halt = __builtin_amdgcn_ballot_w64(!may_go_on);      // (flags do not change in a pass)
       TailK K;
-      K.halfpi = sconst(MCS_PIO2_DD_0); K.pio2_lo = sconst(MCS_PIO2_DD_1); K.twopi = sconst(MCS_TWOPI_DD_0); K.twopi_lo = sconst(MCS_TWOPI_DD_1);
-      K.inv_twopi = sconst(MCS_INV_TWOPI); K.sin_ul = sconst(0x1.fffffffffffffp-1); K.dmin = sconst(2.2250738585072014e-308);
+      tail_k_init(K);
 #pragma nounroll
       for (;;) {
         PROF_LANES(9, active); PROF_ADD(7, 1);
@@ -2466,6 +2480,102 @@ extern "C" int mcs_prof_read(unsigned long long* out, int reset) {
 #endif
 #include "mcs_transport_ws.inc"
 #include "mcs_transport_f32.inc"
+
+// ---- the hot forms one at a time (mcs_eval_fn codes MCS_FN_SQRT_FAST .. MCS_FN_MOD2PI_K; tests/test_gpu_math_forms.py).
+// In THIS translation unit on purpose: the square roots are the MCS_DEVICE_FAST_SQRT ones, the helpers the anonymous-namespace
+// functions the particle loop calls, the two tables come from hot_coef_init / tail_k_init, the flags are K1's.  (The codes below
+// MCS_FN_SQRT_FAST stay in mcs_population.hip, the build K3 uses.)  No zero for an unknown code: the host refuses it, and a
+// kernel that got one all the same answers NaN.
+extern "C" __global__ void __launch_bounds__(256) mcs_k_eval_hot(int fn, long long n, const double* __restrict__ a,
+                                                                 const double* __restrict__ b, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  mcsm::HotCoef kc;
+  hot_coef_init(kc);
+  TailK K;
+  tail_k_init(K);
+  const double x = a[i], y = b[i];
+  double r = __builtin_nan("");
+  switch (fn) {
+    case MCS_FN_SQRT_FAST: r = mcsm::sqrt_(x); break;
+    case MCS_FN_SQRT_NN: r = mcsm::sqrt_nn_(x); break;
+    case MCS_FN_SQRT_NN_K: r = sqrt_nn_k(x, K); break;
+    case MCS_FN_HYPOT1_HOT: r = mcsm::hypot1(x); break;
+    case MCS_FN_FDIV: r = fdiv(x, y); break;
+    case MCS_FN_DIV_R:
+    case MCS_FN_DIV_R2: {
+      // one refined reciprocal, two quotients (as pb / ptot and p_perp / ptot, or dphi and t_step of one xn_per)
+      const double rb = rcp_refined(y);
+      const double q1 = div_r(x, y, rb), q2 = div_r(2 * x, y, rb);
+      r = fn == MCS_FN_DIV_R ? q1 : q2;
+      break;
+    }
+    case MCS_FN_SIN_T:
+    case MCS_FN_COS_T: {
+      double s, c;
+      mcsm::sincos_t(x, &s, &c, kc);
+      r = fn == MCS_FN_SIN_T ? s : c;
+      break;
+    }
+    case MCS_FN_ASIN_T: r = mcsm::asin_t(x, kc); break;
+    case MCS_FN_ASIN_TK: r = asin_tk(x, kc, K); break;
+    case MCS_FN_MOD2PI_K: r = mod2pi_k(x, K); break;
+    default: break;
+  }
+  out[i] = r;
+}
+
+// One scatter of one particle state per lane, in the three spellings the kernels above run (mcs_eval_scatter, include/mcs.h).
+// in [n][10]: key (the 64 bits of the slot), draw index (even, < 2^32), aa, gyro_denom, ptot_pf, gam_pf, xn_per, pb_pf, p_perp, phi;
+// out [n][5]: pb_pf, p_perp, phi, gyro_period, cos_max.  pe_crit, game_crit and eta_mfp are the context's (ka->P).
+extern "C" __global__ void __launch_bounds__(256) mcs_k_eval_scatter(const KArgs* __restrict__ ka, int form, long long n,
+                                                                     const double* __restrict__ in, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  CK* a = (CK*)ka;
+  mcsm::HotCoef kc;
+  hot_coef_init(kc);
+  const double* s = in + 10 * i;
+  Pt p{};
+  Rng rng;
+  rng.init((unsigned long long)__double_as_longlong(s[0]));
+  rng.n = (uint32_t)s[1];
+  const double aa = s[2];
+  p.gyro_denom = s[3]; p.ptot_pf = s[4]; p.gam_pf = s[5]; p.xn_per = s[6]; p.pb_pf = s[7]; p.p_perp = s[8]; p.phi = s[9];
+  if (form == 0) {
+    // the common pass: refresh_scatter (rare code) + scattering()
+    refresh_scatter(a, p, aa, aa * MP_ * CC_, a->P.eta_mfp);
+    scattering(rng, p, kc);
+  } else {
+    // the lossy kernel's refresh and the pieces of a pass as the loop and the tail ring run them; form 2: the tail loop's _k forms
+    refresh_scatter_k(p, kc, aa, aa * MP_ * CC_, a->P.eta_mfp, a->P.pe_crit, a->P.game_crit);
+    double U1, s_ps, c_ps, cos_d, sin_d, ssd;
+    scatter_draws(rng.k0, rng.k1, rng.n >> 1, kc, U1, s_ps, c_ps);
+    scatter_cone(U1, s_ps, 1 - p.cm_val, cos_d, sin_d, ssd);
+    if (form == 1) {
+      scattering_rest(p, kc, cos_d, sin_d, c_ps, ssd);
+    } else {
+      TailK K;
+      tail_k_init(K);
+      scattering_rest_k(p, kc, K, cos_d, sin_d, c_ps, ssd);
+    }
+  }
+  double* o = out + 5 * i;
+  o[0] = p.pb_pf; o[1] = p.p_perp; o[2] = p.phi; o[3] = p.gyro_period; o[4] = p.cm_val;
+}
+
+extern "C" hipError_t mcs_launch_eval_hot(int fn, long long n, const double* a, const double* b, double* out, hipStream_t st) {
+  if (fn < MCS_FN_SQRT_FAST || fn >= MCS_FN_COUNT) return hipErrorInvalidValue;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcs_k_eval_hot, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fn, n, a, b, out);
+  return hipGetLastError();
+}
+extern "C" hipError_t mcs_launch_eval_scatter(const KArgs* a_dev, int form, long long n, const double* in, double* out, hipStream_t st) {
+  if (form < 0 || form > 2) return hipErrorInvalidValue;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcs_k_eval_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a_dev, form, n, in, out);
+  return hipGetLastError();
+}
 
 extern "C" int mcs_transport_max_entries(void) { return MCS_MAXNE; }
 

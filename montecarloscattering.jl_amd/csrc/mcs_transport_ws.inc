@@ -221,15 +221,7 @@ __device__ __forceinline__ void transport_ws(const KArgs* __restrict__ ka) {
   (void)ne;
 
   mcsm::HotCoef kc;
-  kc.S0 = vconst(MCS_SIN_0); kc.S1 = vconst(MCS_SIN_1); kc.S2 = vconst(MCS_SIN_2); kc.S3 = vconst(MCS_SIN_3);
-  kc.S4 = vconst(MCS_SIN_4); kc.S5 = vconst(MCS_SIN_5);
-  kc.C0 = vconst(MCS_COS_0); kc.C1 = vconst(MCS_COS_1); kc.C2 = vconst(MCS_COS_2); kc.C3 = vconst(MCS_COS_3);
-  kc.C4 = vconst(MCS_COS_4); kc.C5 = vconst(MCS_COS_5);
-  kc.A0 = vconst(MCS_ASIN_0); kc.A1 = vconst(MCS_ASIN_1); kc.A2 = vconst(MCS_ASIN_2); kc.A3 = vconst(MCS_ASIN_3);
-  kc.A4 = vconst(MCS_ASIN_4); kc.A5 = vconst(MCS_ASIN_5); kc.A6 = vconst(MCS_ASIN_6); kc.A7 = vconst(MCS_ASIN_7);
-  kc.A8 = vconst(MCS_ASIN_8); kc.A9 = vconst(MCS_ASIN_9); kc.A10 = vconst(MCS_ASIN_10); kc.A11 = vconst(MCS_ASIN_11);
-  kc.A12 = vconst(MCS_ASIN_12);
-  kc.R0 = vconst(MCS_TWO_OVER_PI); kc.R1 = vconst(MCS_PIO2_0); kc.R2 = vconst(MCS_PIO2_1); kc.R3 = vconst(MCS_PIO2_2);
+  hot_coef_init(kc);
 
   Pt p;
   Rng rng;

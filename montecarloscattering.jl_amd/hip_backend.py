@@ -404,3 +404,14 @@ class HipBackend:
         out = np.zeros_like(a)
         self._chk(self.lib.mcs_eval_fn(self.h, capi.FN[name], len(a), _dp(a), _dp(b), _dp(out)))
         return out
+
+    def eval_scatter(self, form: int, states):
+        """One scatter per state in the transport kernel's spelling `form` (0 common pass, 1 lossy kernel / tail ring, 2 tail
+        loop: mcs_eval_scatter in include/mcs.h).  states [n][10]: key (as the BITS of the float64 slot: np.uint64 viewed as
+        float64), draw index, aa, gyro_denom, ptot_pf, gam_pf, xn_per, pb_pf, p_perp, phi -> [n][5]: pb_pf, p_perp, phi,
+        gyro_period, cos_max."""
+        s = np.ascontiguousarray(states, dtype=np.float64)
+        assert s.ndim == 2 and s.shape[1] == 10
+        out = np.zeros((len(s), 5))
+        self._chk(self.lib.mcs_eval_scatter(self.h, int(form), len(s), _dp(s), _dp(out)))
+        return out

@@ -58,6 +58,7 @@ def load(math: str = "det", capi=None):
         "orc_uniform": (dbl, [ct.c_uint64, ct.c_uint32, ct.c_uint64]),
         "orc_eval_fn": (i32, [i32, i64, dp, dp, dp]),
         "orc_scattering": (None, [vp, ct.c_uint64, dbl, dbl, dbl, dbl, dbl, dp, dp, dp, dp]),
+        "orc_eval_scatter": (i32, [vp, i64, dp, dp]),
         "orc_transform_p_PS": (None, [dbl] * 11 + [dp]),
         "orc_transform_p_PSP": (None, [vp] + [dbl] * 5 + [dp, dp, dp]),
         "orc_set_long_draws": (i32, [vp, i64]),
@@ -350,3 +351,12 @@ class OracleBackend:
 
     def last_kernel_ms(self):
         return float("nan")
+
+    def eval_scatter(self, states):
+        """One scatter per state, from its own draw index on, with the cone's cos_max: the reference of HipBackend.eval_scatter
+        (same [n][10] in, [n][5] out; the oracle has one spelling, so no `form`)."""
+        s = np.ascontiguousarray(states, dtype=np.float64)
+        assert s.ndim == 2 and s.shape[1] == 10
+        out = np.zeros((len(s), 5))
+        self._chk(self.lib.orc_eval_scatter(self.h, len(s), _dp(s), _dp(out)))
+        return out
