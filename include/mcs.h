@@ -465,6 +465,73 @@ int mcs_dndp_2d(mcs_ctx* ctx, const mcs_consumer_in* in, double gam_x, double be
 int mcs_photon_ic(mcs_ctx* ctx, const double* mom_edge_cgs, double mc_e, int j_max, int n_nu, const double* alpha_in, const double* n_in, int n_photon,
                   double emin_mev, double bins_per_dec, double beam_area, double* energy_erg, double* emis);
 
+/* ---- ensemble statistics (K8): per-word mean and standard error over the iterations of a fixed-profile run --------------------
+ * With a fixed shock profile the iterations of a run are independent realisations.  An accumulator keeps, on the device, a running
+ * mean and a sum of squared deviations M2 of every word of a SAMPLE vector, per slot; a slot takes species samples or iteration
+ * samples, never both.  Create gives n_species_slots species slots (0 .. n_species_slots - 1; a driver uses slot i_ion - 1) and one
+ * iteration slot (index n_species_slots).
+ *
+ * Species sample, taken at the end of a species, tally replicas folded in:
+ *   1  words [psd, esc_flux) of the fp64 buffer: psd, therm_sf, therm_pf, esc_psd_up, esc_psd_down and the three flux vectors
+ *   2  energy_recv_pool [n_grid]
+ *   3  num_crossings [n_grid], converted to double (exact below 2^53)
+ *   4  the marginals of psd, therm_sf, therm_pf, in that order, for each the momentum marginal [n_grid][nmom+2] (summed over the
+ *      angle index) and then the angle marginal [n_grid][ntht+2] (summed over the momentum index); every word is the serial sum of
+ *      its terms in ascending index order, starting from the first term.  (The variance of a marginal cannot be had from the
+ *      per-cell variances, so the marginal itself is sampled.)
+ * Iteration sample, taken at the end of an iteration: words [esc_flux, energy_recv_pool) and then [scalars, total).  The sections
+ * the transport never resets -- esc_flux, esc_energy_eff, esc_num_eff, spectra_coupled, spectra_sf, spectra_pf -- enter as their
+ * growth since the snapshot of the begin-iteration call below; weight_coupled, energy_transfer_pool, scalars and the two arrays
+ * indexed by iteration (px_esc_feb, energy_esc_feb, whose statistics mean nothing) enter as they stand.
+ *
+ * Update of a slot by a sample x, per word, no fused operation:   n += 1; d = x - mean; mean = mean + d / n; M2 = M2 + d * (x - mean)
+ * Merge of slot b into slot a (Chan), per word:                   n = na + nb; d = mb - ma; mean = ma + d * (nb / n);
+ *                                                                 M2 = (qa + qb) + (d * d) * (na * nb / n)
+ * (all of n, na, nb as doubles); an empty b changes nothing, an empty a takes b as it is.
+ * Device memory: two vectors of the sample length per slot -- for a species slot about twice the tally buffer -- plus one marginal
+ * vector and one snapshot of [esc_flux, energy_recv_pool).
+ *
+ * The contexts handed to these calls may be any context on the accumulator's device with the accumulator's tally layout (species
+ * that ran on a secondary context are sampled there).  Work is queued on that context's stream, after what the accumulator's
+ * previous operation queued (an event orders them, as in the accumulate-tallies call); merge, read and load-mean of a source
+ * accumulator are ordered the same way.  Only count and read synchronise with the host.  The `home` context of create gives the
+ * device, the layout and the stream that merge and read use; it must outlive the accumulator.  The caller serialises the calls on
+ * one accumulator, and each with the calls on the context it names.
+ * Refused, with a message and nothing changed: a null argument, a slot out of range, a species sample for the iteration slot or
+ * the reverse, a context on another device or with another layout, a merge of an accumulator into itself or of accumulators with
+ * different slots, an iteration sample without a snapshot of that context taken since the last one, a standard error with n < 2. */
+typedef struct mcs_ens mcs_ens;
+/* Offsets and lengths, in doubles, of the parts of the two sample vectors, and where the parts lie in the fp64 tally buffer. */
+typedef struct mcs_ens_layout {
+  int64_t sp_tallies, sp_tallies_n;               /* part 1: sample word sp_tallies + w is buffer word tally_sp_first + w */
+  int64_t sp_recv_pool, sp_recv_pool_n;           /* part 2 */
+  int64_t sp_num_crossings, sp_num_crossings_n;   /* part 3 */
+  int64_t sp_psd_mom, sp_psd_tht, sp_therm_sf_mom, sp_therm_sf_tht, sp_therm_pf_mom, sp_therm_pf_tht;   /* part 4 */
+  int64_t sp_marg_mom_n, sp_marg_tht_n;           /* n_grid * (nmom+2), n_grid * (ntht+2) */
+  int64_t sp_total;
+  int64_t it_sums, it_sums_n;                     /* sample word it_sums + w is buffer word tally_it_first + w */
+  int64_t it_scalars, it_scalars_n;
+  int64_t it_total;
+  int64_t tally_sp_first, tally_it_first, tally_recv_pool, tally_scalars;   /* psd, esc_flux, energy_recv_pool, scalars of mcs_layout */
+} mcs_ens_layout;
+int mcs_ens_get_layout(const mcs_params* p, mcs_ens_layout* out);      /* needs no GPU */
+int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out);
+int mcs_ens_destroy(mcs_ens* ens);
+/* snapshot of src's [esc_flux, energy_recv_pool), the base of the next iteration sample from src */
+int mcs_ens_begin_iteration(mcs_ens* ens, mcs_ctx* src);
+int mcs_ens_add_species(mcs_ens* ens, mcs_ctx* src, int slot);
+int mcs_ens_add_iteration(mcs_ens* ens, mcs_ctx* src);
+/* every slot of src merged into the same slot of dst; src is left as it is */
+int mcs_ens_merge(mcs_ens* dst, mcs_ens* src);
+int mcs_ens_count(mcs_ens* ens, int slot, int64_t* n);
+/* words [first, first + count) of a slot's sample vector into host[0 .. count): what = 0 the mean, 1 M2, 2 the standard error of
+ * the mean, sqrt(M2 / (n (n - 1))) */
+int mcs_ens_read(mcs_ens* ens, int slot, int what, int64_t first, int64_t count, double* host);
+/* The mean of a species slot written into dst's per-species sections: parts 1 and 2 into the fp64 buffer, part 3, rounded to
+ * nearest, into num_crossings.  The consumers above then run unchanged on the ensemble-mean histograms (what a two-dimensional
+ * consumer call left on the device is dropped). */
+int mcs_ens_load_mean(mcs_ens* ens, int slot, mcs_ctx* dst);
+
 /* ---- test / measurement hooks ------------------------------------------- */
 /* evaluate device math/RNG primitives (bit-parity tests): fn ids in mcs_fn */
 enum mcs_fn { MCS_FN_SIN = 0, MCS_FN_COS, MCS_FN_ASIN, MCS_FN_ACOS, MCS_FN_ATAN2, MCS_FN_LOG10,

@@ -78,6 +78,16 @@ class McsOptionDesc(ct.Structure):
     ]
 
 
+class McsEnsLayout(ct.Structure):
+    """`mcs_ens_layout`: offsets and lengths of the parts of the two sample vectors of the ensemble statistics (include/mcs.h)."""
+    _fields_ = [(name, ct.c_int64) for name in (
+        "sp_tallies", "sp_tallies_n", "sp_recv_pool", "sp_recv_pool_n", "sp_num_crossings", "sp_num_crossings_n",
+        "sp_psd_mom", "sp_psd_tht", "sp_therm_sf_mom", "sp_therm_sf_tht", "sp_therm_pf_mom", "sp_therm_pf_tht",
+        "sp_marg_mom_n", "sp_marg_tht_n", "sp_total",
+        "it_sums", "it_sums_n", "it_scalars", "it_scalars_n", "it_total",
+        "tally_sp_first", "tally_it_first", "tally_recv_pool", "tally_scalars")]
+
+
 # enum mcs_option_when / mcs_option_applies
 OPTION_WHEN = ("between launches", "before the first pipelined run", "creation only")
 OPTION_APPLIES = ("any", "fp64 state when > 0", "fp32 state")
@@ -290,6 +300,16 @@ def load_library() -> ct.CDLL:
         "mcs_create_with_options": (i32, [ct.POINTER(McsParams), i32, vp, c_int32_p, c_int64_p, i32, i32, ct.POINTER(vp)]),
         "mcs_set_option": (i32, [vp, i32, i64]),
         "mcs_get_option": (i32, [vp, i32, c_int64_p]),
+        "mcs_ens_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsEnsLayout)]),
+        "mcs_ens_create": (i32, [vp, i32, ct.POINTER(vp)]),
+        "mcs_ens_destroy": (i32, [vp]),
+        "mcs_ens_begin_iteration": (i32, [vp, vp]),
+        "mcs_ens_add_species": (i32, [vp, vp, i32]),
+        "mcs_ens_add_iteration": (i32, [vp, vp]),
+        "mcs_ens_merge": (i32, [vp, vp]),
+        "mcs_ens_count": (i32, [vp, i32, c_int64_p]),
+        "mcs_ens_read": (i32, [vp, i32, i32, i64, i64, c_double_p]),
+        "mcs_ens_load_mean": (i32, [vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -335,4 +355,9 @@ EXPORTED_SYMBOLS = [
     "mcs_dndp_2d", "mcs_photon_ic", "mcs_run_pcuts_fused", "mcs_photon_pion", "mcs_run_pcuts_pipelined",
     "mcs_accumulate_tallies", "mcs_k1_blocks_per_cu",
     "mcs_option_count", "mcs_option_describe", "mcs_create_with_options", "mcs_set_option", "mcs_get_option",
+]
+# the ensemble statistics (K8)
+EXPORTED_SYMBOLS += [
+    "mcs_ens_get_layout", "mcs_ens_create", "mcs_ens_destroy", "mcs_ens_begin_iteration", "mcs_ens_add_species",
+    "mcs_ens_add_iteration", "mcs_ens_merge", "mcs_ens_count", "mcs_ens_read", "mcs_ens_load_mean",
 ]

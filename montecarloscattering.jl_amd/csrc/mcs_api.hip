@@ -10,6 +10,7 @@
 // synchronous only for the 8-byte n_saved.  There is no CPU code path in this library.
 #include "mcs_device.h"
 #include "mcs_hip_owned.h"
+#include "mcs_ctx_view.h"
 #include "../../include/mcs_ic.h"
 
 #include <cmath>
@@ -1536,5 +1537,15 @@ int mcs_photon_ic(mcs_ctx* c, const double* mom_edge_cgs, double mc_e, int j_max
   if (energy_erg) for (int k = 0; k < n_photon; ++k) energy_erg[k] = mcs_ic_alpha_out(log_min_rm, bins_per_dec, k) * (MCS_ME * MCS_C * MCS_C);
   return 0;
 }
+
+// ---- the view of a context that mcs_ensemble.hip (K8) works through (mcs_ctx_view.h) ----
+int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
+  HIPCHK(hipSetDevice(c->device));
+  if (fold_replicas(c)) return 1;
+  *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L};
+  return 0;
+}
+void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; }
+int mcs_ctx_view_fail(const char* msg) { return fail(msg); }
 
 }  // extern "C"

@@ -1,0 +1,27 @@
+// mcs_ctx_view.h -- what a translation unit beside mcs_api.hip may see of a context (struct mcs_ctx is private to that file):
+// its device, stream, tally buffers, parameters and layout.  mcs_ensemble.hip (K8) works through this view.
+// Not part of the C ABI of include/mcs.h.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include "../../include/mcs.h"
+
+struct McsCtxView {
+  int device;
+  hipStream_t stream;
+  double* T;                  // flat fp64 tallies (layout L)
+  unsigned long long* I;      // int64 tallies
+  mcs_params P;
+  mcs_layout L;
+};
+
+extern "C" {
+// The view of ctx, with its device made current and its tally replicas folded into T (queued on its stream), as every reader of
+// the tally buffer does.  Non-zero, with the message set: the fold could not be queued.
+int mcs_ctx_view_get(mcs_ctx* ctx, McsCtxView* out);
+// The tally buffer of ctx has been rewritten: what was derived from the old contents (the d2N/dp dcos array of the last
+// two-dimensional consumer call) is no longer valid.
+void mcs_ctx_view_tallies_written(mcs_ctx* ctx);
+// Sets the message of the calling thread's last error (what the ABI's error call returns); returns 1.
+int mcs_ctx_view_fail(const char* msg);
+}

@@ -42,6 +42,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from . import consumers, inputs, iter_finalize as itf
+from . import ensemble as ens
 from .capi import IC, RUNNING_F64, running_i64
 from .inputs import Problem
 
@@ -78,6 +79,7 @@ class RunResult:
     options: dict = dataclasses.field(default_factory=dict)          # what the run ran with: the primary backend's options() (a backend that
                                                                   # has them: the run options of the HIP context, by name) and the driver's own
                                                                   # fused_pcuts, fused_chunk, long_draws, long_imult_max as actually used
+    ensemble: object = None       # the ensemble statistics the run fed (run(ensemble=...), run_overlapped(ensemble=True)); ensemble.py
 
 
 class Comm:
@@ -477,6 +479,9 @@ def _species_end(rs, k, i_iter, i_ion, before_hook=None):
     rs.steps_seen = seen
     rs.G_f, rs.G_i = G_f, G_i
     rs.per_species.append((i_iter, i_ion, G_f, G_i))      # fresh host arrays: no copy needed
+    if rs.ensemble is not None:
+        # from the context that holds this species' per-species sections, before it is freed for its next species
+        rs.ensemble.add_species(be, i_ion - 1)
     if before_hook is not None:
         before_hook()
     if rs.on_species_end is not None:
@@ -574,7 +579,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         finalize: bool = False, smoothing=None, on_iteration_end: Optional[Callable] = None,
         first_iter: int = 1, iter_state=None, species_tallies: str = "full", final_full_read: bool = True,
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
-        long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None) -> RunResult:
+        long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None,
+        ensemble=None) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -622,6 +628,12 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     every pcut).  An argument left out (None) takes the default an environment variable gives, else the built-in one: MCS_FUSED_PCUTS
     (off iff "0"; True), MCS_FUSED_CHUNK (12), MCS_LONG_DRAWS (0; not read by a multi-rank run), MCS_LONG_IMULT_MAX (8).  The values used
     are in RunResult.options, beside the run options of the backend's context (HipBackend.options()).
+    ensemble: an ensemble.Ensemble (Ensemble.for_backend(backend, number of species)) that takes one sample per species end -- slot
+    i_ion - 1, from the context that holds the species' per-species sections, after a secondary context's merge -- and one per
+    iteration end (the growth of the never-reset tallies since begin_iteration, the rest as it stands): per-cell mean and standard
+    error over the iterations, which are independent realisations while the profile is fixed (ensemble.py; on a HIP backend the
+    histograms stay on the device).  Not with tcut_print (the in-place rewrite makes the coupled spectra no longer sums), not with
+    smooth_shocks (the iterations then depend on each other), not with an enabled communicator: the multi-rank case is left out.
     """
     import torch
     comm = comm or Comm(False)
@@ -655,6 +667,16 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
     # (the two counter words only: run_overlapped calls run() once per iteration)
     rs.steps_seen = sum(_steps(rs.dev_t[1] if rs.dev_t is not None else _read_counters(backend), P.n_grid))
+    rs.ensemble = ensemble
+    if ensemble is not None:
+        if tcut_print:
+            raise ValueError("ensemble: not with tcut_print (its in-place rewrite makes the coupled spectra no longer sums over the iterations)")
+        if smoothing is not None and smoothing.smooth_shocks:
+            raise ValueError("ensemble: not with smooth_shocks (the iterations of a run with a changing profile are not independent)")
+        if comm.enabled:
+            raise ValueError("ensemble: one process without a communicator (the multi-rank case is left out)")
+        if ensemble.n_species < len(cfg.species):
+            raise ValueError(f"ensemble: {ensemble.n_species} species slots for {len(cfg.species)} species")
     if secondaries:
         if comm.enabled:
             raise ValueError("species_backends: one process without a communicator (the species' merges are not collectives)")
@@ -680,6 +702,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         _zero_running_sums(L, be)
     for i_iter in range(first_iter, first_iter + n_itrs):
         backend.begin_iteration(i_iter)
+        if ensemble is not None:
+            ensemble.begin_iteration(backend)
         if multi and not rs.is_root:
             if rs.dev_t is not None:
                 rs.dev_t[0].zero_()
@@ -722,11 +746,13 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             if rs.is_root:
                 backend.write_tally("weight_coupled", wc)
                 backend.write_tally("spectra_coupled", sc)
+        if ensemble is not None:
+            ensemble.add_iteration(backend)
         if on_iteration_end is not None:
             on_iteration_end(i_iter)
 
     return RunResult(rs.G_f, rs.G_i, rs.per_species, rs.stats, *_steps(rs.G_i, P.n_grid), rs.iter_finals, it_state,
-                     rs.local_steps, rs.empty_launches, rs.species_spans, options)
+                     rs.local_steps, rs.empty_launches, rs.species_spans, options, ensemble)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over
@@ -737,7 +763,7 @@ ACCUMULATED_OVER_ITERATIONS = ("esc_flux", "px_esc_feb", "energy_esc_feb", "esc_
 
 def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pcuts: Optional[int] = None,
                    on_iteration_end: Optional[Callable] = None, first_iter: int = 1,
-                   blocks_per_launch: Optional[int] = None) -> RunResult:
+                   blocks_per_launch: Optional[int] = None, ensemble: bool = False) -> RunResult:
     """The iterations of a run with a FIXED shock profile (smooth-shocks = false -- the stock mc_in.toml, BASELINE
     config[1]) are independent Monte-Carlo realisations: nothing an iteration computes enters the next one's transport
     (src/main_loops.jl:52-121: every tally the transport reads is reset at the top; the RNG keys carry i_iter).  Their
@@ -751,7 +777,11 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     workgroups), each SIMD carries one wave of either, and a wave whose neighbour is in its launch's tail issues at the
     lone-wave rate -- measured 254 ms per iteration against 275 with full-chip launches, which let the other launch in only
     as whole workgroups retire (tools/gpu_concurrent.py).
-    Single process only (no communicator): collectives issued from two threads would need an order."""
+    Single process only (no communicator): collectives issued from two threads would need an order.
+    ensemble: True -- every context feeds an ensemble of its own (ensemble.Ensemble.for_backend; run(ensemble=...)); at the end they
+    are merged in context order into the first context's, which RunResult.ensemble hands back: per-cell mean and standard error of
+    the tallies over the iterations.  Its finalize_mean / finalize_stderr / finalize_count are the same statistics, on the host, of
+    the per-iteration ion_finalize of the last species (ensemble.FINALIZE_NAMES), in iteration order."""
     cfg, P = prob.cfg, prob.params
     n_itrs = n_itrs if n_itrs is not None else cfg.num_iterations
     K, L = len(backends), backends[0].layout
@@ -762,6 +792,7 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     if blocks_per_launch is None and K > 1 and hasattr(backends[0], "num_cus"):
         blocks_per_launch = max(2 * backends[0].num_cus() // K, 1)
     busy = _ChipShare()                       # iterations in flight
+    enss = [ens.Ensemble.for_backend(be, len(cfg.species)) for be in backends] if ensemble else [None] * K
 
     def one(i_iter):
         k = (i_iter - first_iter) % K
@@ -772,7 +803,7 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
                 # (long_draws=0: the pcuts are not pipelined here -- the other iterations' launches are what fills this one's tails, and
                 # the per-pcut hook needs the per-pcut loop; MCS_LONG_DRAWS does not reach this call)
                 res = run(prob, be, None, n_itrs=1, max_pcuts=max_pcuts, first_iter=i_iter, species_tallies="light", final_full_read=False,
-                          before_pcut=geometry, long_draws=0)
+                          before_pcut=geometry, long_draws=0, ensemble=enss[k])
                 ion_fin = consumers.ion_finalize(prob, be, len(cfg.species))     # K4, before the context is reused
         return k, res, ion_fin
 
@@ -802,4 +833,11 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
         for name in ACCUMULATED_OVER_ITERATIONS:
             L.view(f, name)[...] += L.view(fk, name)
         i64[ng:] += ik[ng:]                   # the event counters are running totals too (num_crossings is per species)
-    return RunResult(f, i64, per_species, stats, *_steps(i64, ng), iter_finals, st, local_steps)
+    if ensemble:
+        for other in enss[1:]:
+            enss[0].merge(other)
+            other.destroy()
+        for name in ens.FINALIZE_NAMES:
+            enss[0].finalize_mean[name], enss[0].finalize_stderr[name], enss[0].finalize_count = ens.stats_over(
+                [getattr(ion_fin, name) for _, _, ion_fin in iter_finals])
+    return RunResult(f, i64, per_species, stats, *_steps(i64, ng), iter_finals, st, local_steps, ensemble=enss[0])
