@@ -8,7 +8,7 @@
 // context releases them, a failed allocation leaves its owner empty.  All work is
 // queued on ONE HIP stream (the pipelined loop adds a side stream); mcs_run_pcut is
 // synchronous only for the 8-byte n_saved.  There is no CPU code path in this library.
-#include "mcs_device.h"
+#include "mcs_launch.h"      // (and mcs_device.h)
 #include "mcs_hip_owned.h"
 #include "mcs_ctx_view.h"
 #include "../../include/mcs_ic.h"
@@ -20,58 +20,9 @@
 #include <string>
 #include <vector>
 #include <chrono>
-#include <climits>
 #include <cstdarg>
 #include <memory>
 #include <utility>
-
-extern "C" {
-int mcs_transport_max_entries(void);
-hipError_t mcs_launch_transport(const KArgs* a_dev, int kernel, int blocks, int threads, hipStream_t st);
-int mcs_transport_ws_threads(void);
-hipError_t mcs_launch_finalize_split_dev(const uint8_t* l_save, long long cap_n, unsigned int* block_counts, unsigned long long* block_offsets,
-                                         unsigned long long* scan_total, long long* src, PcutDev* pd, PcutDev* pd_next, unsigned long long* counters,
-                                         long long n_target, unsigned long long* err, DevPop sv, DevPop out, int split_blocks, hipStream_t st);
-hipError_t mcs_launch_compact(const uint8_t* l_save, long long n, unsigned int* block_counts, unsigned long long* block_offsets,
-                              unsigned long long* total_dev, long long* src, hipStream_t st);
-hipError_t mcs_launch_split(DevPop sv, DevPop out, const long long* src, long long n_new, long long i_mult, hipStream_t st);
-hipError_t mcs_launch_compact_match(const uint8_t* l_save, long long n, unsigned int* block_counts, unsigned long long* block_offsets,
-                                    unsigned long long* total_dev, long long* src, unsigned int match, hipStream_t st);
-hipError_t mcs_launch_late_split(const uint8_t* l_save, long long n, unsigned int* block_counts, unsigned long long* block_offsets,
-                                 unsigned long long* total_dev, long long* src, PcutDev* pd, long long i_mult, long long n_main_next, DevPop sv,
-                                 DevPop out_at_main_end, int split_blocks, hipStream_t st);
-hipError_t mcs_launch_saved_export(DevPop sv, const long long* src, long long n_saved, long long cap, long long first,
-                                   long long stride, const long long* gin, long long* gidx, double* f64, uint32_t* meta,
-                                   hipStream_t st);
-hipError_t mcs_launch_split_import(DevPop out, const double* f64, const uint32_t* meta, long long cap, long long i_mult,
-                                   long long first, long long stride, long long n_local, hipStream_t st);
-hipError_t mcs_launch_init_pop(DevPop out, const double* ptot_in, const double* weight_in, long long n, long long j_offset,
-                               long long j_stride, long long n_total, unsigned long long key, double m, double u, double x_start,
-                               int i_grid_start, int relativistic, int fast_push, double xn_per_fine, double x_grid_stop,
-                               int n_bins, const double* bin_ptot, const double* bin_weight, const long long* bin_start,
-                               hipStream_t st);
-hipError_t mcs_launch_fill(double* p, long long n, double v, hipStream_t st);
-hipError_t mcs_launch_fold_replicas(double* dst, double* rep, long long n, int n_rep, hipStream_t st);
-hipError_t mcs_launch_accumulate_tallies(double* dT, double* sT, unsigned long long* dI, unsigned long long* sI, long long a_lo,
-                                         long long a_n, long long b_lo, long long b_n, long long i_lo, long long i_n, hipStream_t st);
-hipError_t mcs_launch_copy(double* dst, const double* src, long long n, hipStream_t st);
-hipError_t mcs_launch_eval(int fn, long long n, const double* a, const double* b, double* out, hipStream_t st);
-hipError_t mcs_launch_eval_hot(int fn, long long n, const double* a, const double* b, double* out, hipStream_t st);
-hipError_t mcs_launch_eval_scatter(const KArgs* a_dev, int form, long long n, const double* in, double* out, hipStream_t st);
-hipError_t mcs_launch_dndp_cr(const mcs_params* P, const double* psd, const double* gam_sf, const double* ux, const double* tabs,
-                              double rest_energy, double n0, double gam0, double* out_dndp, unsigned long long* diag, hipStream_t st);
-hipError_t mcs_launch_dndp_2d(const mcs_params* P, const double* psd, const double* therm_sf, const unsigned long long* num_crossings, const double* tabs,
-                              double rest_energy, double n0, int therm_from_hist, double gam_x, double beta_x, double* scratch, double* ef, hipStream_t st);
-hipError_t mcs_launch_photon_ic(const double* ef, const double* p_edge, const double* field, int n_grid, int NM, int NT, int j_max, int n_nu, int n_photon,
-                                double log_min_rm, double bins_per_dec, double mc_e, double beam_area, double* out, hipStream_t st);
-hipError_t mcs_launch_photon_pion(const double* dndp_pf, const double* p_edge, const double* target, int n_grid, int NM, int n_photon,
-                                  double log_emin_erg, double bins_per_dec, double mc, double aa, double scaling, int i_data, double* out, hipStream_t st);
-hipError_t mcs_launch_photon_synch(const double* dndp_pf, const double* p_edge, const double* btot, int n_grid, int NM, int n_photon,
-                                   double log_emin_erg, double bins_per_dec, double mc, double* out, hipStream_t st);
-hipError_t mcs_launch_thermo(const mcs_params* P, const double* psd, const double* therm_pf, const unsigned long long* num_crossings,
-                             const double* gam_sf, const double* ux, const double* tabs, double rest_energy, double mc, double n0,
-                             int therm_from_hist, double* scratch, double* out3, hipStream_t st);
-}
 
 #define MCS_MEV_ERG_ 1.602176634e-6
 namespace {
@@ -83,6 +34,9 @@ int fail(const std::string& msg) { g_err = msg; return 1; }
     hipError_t e_ = (expr);                                                                  \
     if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));    \
   } while (0)
+// The top of every ABI call that takes a context and returns a status: a null context is an error, else its device is made current.
+#define MCS_ENTER_AS(c, who) do { if (!(c)) return fail(std::string(who) + ": null context"); HIPCHK(hipSetDevice((c)->device)); } while (0)
+#define MCS_ENTER(c) MCS_ENTER_AS(c, __func__)
 
 std::string format(const char* f, ...) {
   char b[320];
@@ -106,6 +60,33 @@ DevPop pop_view(const PopBuf& b, long long first = 0) {
   for (int i = 0; i < 8; ++i) d.*kPopF64[i] = b.f[i] + first;
   d.meta = b.meta + first;
   return d;
+}
+
+// two export buffers of cap() lane states each (sliced launches): a launch resumes from one and exports into the other
+struct StragBuf : BufGroup<StragBuf> {
+  DevBuf<double> d[2];
+  long long cap() const { return d[1].cap() / MCS_STRAG_WORDS; }
+  hipError_t grow(long long n) { return reserve_all({n * MCS_STRAG_WORDS, n * MCS_STRAG_WORDS}, d[0], d[1]); }
+};
+// the fused species loop's launch constants and device-decided words for cap() pcuts (one PcutDev more: the population after the last)
+struct FusedBuf : BufGroup<FusedBuf> {
+  PinnedBuf<KArgs> h_args; PinnedBuf<PcutDev> h_pd; DevBuf<KArgs> d_args; DevBuf<PcutDev> d_pd;
+  long long cap() const { return d_args.cap(); }
+  hipError_t grow(long long n) { return reserve_all({n, n + 1, n, n + 1}, h_args, h_pd, d_args, d_pd); }
+};
+
+// The words of mcs_ctx::d_counters (h_back holds the host's copy of a word at the same index): the next unclaimed particle of a launch |
+// the kernel's own count of saved particles | the compaction's count of l_save flags | EXPORT has TWO meanings: the particles a sliced
+// launch exported, and the panic code of a wave-specialised launch (which is never sliced) | fused loop: set on the device when SAVED and
+// SCAN of some pcut differed.
+enum Ctr { CTR_WORK, CTR_SAVED, CTR_SCAN, CTR_EXPORT, CTR_MISMATCH, CTR_COUNT = 8 };
+// The pipelined loop's own words (pp_dpc; pp_hpc is the host's copy), a work / saved pair for every launch that can be in flight at once:
+// the main launch's pair | count of the main group's saved particles that are not long | EXPORT + q: particles exported by the launches of
+// pcut parity q (two words) | the pair of the resumed long histories | the late launch's pair | count of the saved long particles.
+enum PipeCtr { PC_WORK, PC_SAVED, PC_SCAN, PC_EXPORT, PC_RES_WORK = PC_EXPORT + 2, PC_RES_SAVED, PC_LATE_WORK, PC_LATE_SAVED, PC_LATE_SCAN, PC_COUNT = 16 };
+// points a launch at its own words of `ctr`
+void set_counters(KArgs& a, unsigned long long* ctr, int work, int saved, int exported) {
+  a.work_counter = ctr + work; a.n_saved = ctr + saved; a.strag_count = ctr + exported;
 }
 }  // namespace
 
@@ -137,7 +118,7 @@ struct mcs_ctx {
   // exports its live particles and ends; the host relaunches them, spread over the chip's waves, until none is left
   // (the budget, in trips, is MCS_OPT_TAIL_BUDGET; 0 = one launch per pcut, run to the end)
   int tail_rounds_last = 0;    // launches the last mcs_run_pcut* took
-  DevBuf<double> d_strag[2]; long long strag_cap = 0;
+  StragBuf strag;
   // The run options (enum mcs_option of include/mcs.h, one value per key; the table of mcs_options.h says what each allows): set at
   // creation from the built-in defaults, the environment and the caller's list, changed by mcs_set_option, read where a launch is
   // planned.  Notes on some of them:
@@ -150,21 +131,17 @@ struct mcs_ctx {
   //   TAIL_RING, TAIL_LOOP, REFILL_MIN, DEFER_K, PARK, TAIL_MERGE   A/B measurements of the tail's parts
   int64_t opt[MCS_OPT_COUNT] = {};
   long long o(int key) const { return opt[key]; }
-  // finals
-  DevBuf<int32_t> f_reason, f_helix, f_retro; DevBuf<double> f_ptot, f_x;
-  long long f_cap = 0;
-  // scan scratch
-  DevBuf<unsigned int> d_bcounts; DevBuf<unsigned long long> d_boffs; DevBuf<long long> d_src; long long scan_cap = 0;
+  FinalsBuf fin; ScanScratch scan;      // the end states of a debug run; the compaction's scratch (src[]: the saved particles' indices)
   DevBuf<double> d_tally_rep;                  // replicas of the histograms at the head of the tally buffer (KArgs::tally_rep)
   long long rep_n = 0;                         // doubles per replica (0: no replicas)
   bool rep_dirty = false;                    // a launch may have added to the replicas since the last fold
-  DevBuf<unsigned long long> d_counters;      // [0] work counter, [1] n_saved, [2] scan total
+  DevBuf<unsigned long long> d_counters;      // CTR_COUNT words, named by enum Ctr above
   // staging for init_pop
   DevBuf<double> d_stage;
   // launch constants: host copy in PINNED memory (the upload is then a true async copy: no staging through the runtime's
   // bounce buffer, ~10 us per pcut) and device copy; read-back words of a pcut, pinned for the same reason
   PinnedBuf<KArgs> h_args_pin; DevBuf<KArgs> d_args;
-  PinnedBuf<unsigned long long> h_back;       // [0..1] n_saved | count of l_save flags, [2] exported particles of a sliced run
+  PinnedBuf<unsigned long long> h_back;       // the words of d_counters a call reads back, each at its own index
   // species
   int i_iter = 1, i_ion = 1;
   double aa = 1, zzq = MCS_QCGS, m = MCS_MP, mc = MCS_MP * MCS_C, pmax_cutoff = 0, density = 1, ewf = 1;
@@ -173,7 +150,7 @@ struct mcs_ctx {
   int kernel_last = -1;        // mcs_last_kernel
   // fused species loop (mcs_run_pcuts_fused): launch constants of every pcut (pinned + device), the per-pcut words decided on the
   // device, one event pair per pcut
-  PinnedBuf<KArgs> h_fargs; DevBuf<KArgs> d_fargs; DevBuf<PcutDev> d_pd; PinnedBuf<PcutDev> h_pd; int fused_cap = 0;
+  FusedBuf fused;
   std::vector<Event> f_ev;
   // pipelined pcut loop (mcs_run_pcuts_pipelined): the side stream on which a pcut's long histories finish while the next pcut runs,
   // the second set of saved arrays / status bytes (pcut p's are still written while pcut p + 1 runs), the late group's scan scratch,
@@ -183,9 +160,8 @@ struct mcs_ctx {
   // themselves (beside a wave of the main launch on the same SIMD a long history advances at half the speed -- the kernel is issue-bound
   // -- and the side chain, not the main launch, ends the pcut); a pcut with side work runs its main launch on the masked main stream
   Stream pp_s1m, pp_s2m; bool pp_masks_tried = false;      // (MCS_OPT_PIPE_SIDE_CUS of the chip's CUs for the side stream; 0: no masks)
-  PopBuf pp_sav2; DevBuf<uint8_t> pp_lsave2; long long pp_cap = 0;
-  DevBuf<unsigned int> pp_bcounts; DevBuf<unsigned long long> pp_boffs; DevBuf<long long> pp_src;
-  DevBuf<unsigned long long> pp_dpc; PinnedBuf<unsigned long long> pp_hpc;
+  PopBuf pp_sav2; DevBuf<uint8_t> pp_lsave2; ScanScratch pp_scan;
+  DevBuf<unsigned long long> pp_dpc; PinnedBuf<unsigned long long> pp_hpc;      // PC_COUNT words, named by enum PipeCtr above
   PinnedBuf<KArgs> pp_hargs; DevBuf<KArgs> pp_dargs; DevBuf<PcutDev> pp_dpdl; PinnedBuf<PcutDev> pp_hpdl;
   int pp_waits_last = 0;       // pcuts of the last pipelined run whose i_mult had to wait for the long histories
   // consumers (K4): table staging, outputs, thermo scratch slab
@@ -217,25 +193,10 @@ int ensure_capacity(mcs_ctx* c, long long n) {
     if (reserve(c->sav, cap)) return 1;
   }
   if (n > c->d_lsave.cap() && reserve(c->d_lsave, grow_cap(n))) return 1;
-  if (c->debug_finals && n > c->f_cap) {
-    const long long cap = grow_cap(n);
-    c->f_cap = 0;
-    reset_all(c->f_reason, c->f_helix, c->f_retro, c->f_ptot, c->f_x);
-    if (reserve(c->f_reason, cap) || reserve(c->f_helix, cap) || reserve(c->f_retro, cap) || reserve(c->f_ptot, cap) || reserve(c->f_x, cap)) return 1;
-    c->f_cap = cap;
-  }
-  if (n > c->scan_cap) {
-    const long long cap = grow_cap(n);
-    const long long nb = (cap + 1023) / 1024;
-    c->scan_cap = 0;
-    reset_all(c->d_bcounts, c->d_boffs, c->d_src);
-    if (reserve(c->d_bcounts, nb) || reserve(c->d_boffs, nb) || reserve(c->d_src, cap)) return 1;
-    c->scan_cap = cap;
-  }
+  if (c->debug_finals && n > c->fin.cap() && reserve(c->fin, grow_cap(n))) return 1;
+  if (n > c->scan.cap() && reserve(c->scan, grow_cap(n))) return 1;
   return 0;
 }
-
-int ensure_stage(mcs_ctx* c, long long n_doubles) { return reserve(c->d_stage, n_doubles); }
 
 int fill(mcs_ctx* c, long long off, long long n, double v) {
   HIPCHK(mcs_launch_fill(c->d_T + off, n, v, c->stream));
@@ -323,8 +284,8 @@ int mcs_create_with_options(const mcs_params* p, int device, void* stream, const
   HIPCHK(hipGetDeviceProperties(&prop, device));
   c->n_cu = prop.multiProcessorCount;
   const int ne = p->n_grid + 2;
-  if (reserve(c->d_tab, (long long)8 * ne) || reserve(c->d_counters, 8) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1) ||
-      reserve(c->h_back, 4))
+  if (reserve(c->d_tab, (long long)8 * ne) || reserve(c->d_counters, CTR_COUNT) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1) ||
+      reserve(c->h_back, CTR_COUNT))
     return 1;
   if (c->o(MCS_OPT_TALLY_REPLICAS)) {
     c->rep_n = c->L.total;     // the whole tally buffer: the three big histograms are 99 % of it
@@ -332,7 +293,7 @@ int mcs_create_with_options(const mcs_params* p, int device, void* stream, const
     if (reserve(c->d_tally_rep, (long long)nrep)) return 1;
     HIPCHK(hipMemsetAsync(c->d_tally_rep, 0, nrep * sizeof(double), c->stream));
   }
-  HIPCHK(hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), c->stream));
+  HIPCHK(hipMemsetAsync(c->d_counters, 0, CTR_COUNT * sizeof(unsigned long long), c->stream));
   if (reserve(c->own_T, c->L.total) || reserve(c->own_I, mcs_i64_total(p))) return 1;
   c->d_T = c->own_T; c->d_I = c->own_I;
   HIPCHK(hipMemsetAsync(c->d_T, 0, (size_t)c->L.total * sizeof(double), c->stream));
@@ -355,14 +316,14 @@ int mcs_destroy(mcs_ctx* c) {
 }
 
 int mcs_sync(mcs_ctx* c) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 
 int mcs_bind_tallies(mcs_ctx* c, double* dev_f64, int64_t n_f64, int64_t* dev_i64, int64_t n_i64) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
   HIPCHK(hipStreamSynchronize(c->stream));
   if (dev_f64) {
@@ -382,7 +343,7 @@ int64_t* mcs_tallies_i64_devptr(mcs_ctx* c) { return (int64_t*)c->d_I; }
 
 int mcs_set_grid(mcs_ctx* c, int n_entries, const double* x_grid_cm, const double* ux, const double* uz, const double* utot,
                  const double* gam_sf, const double* gam_ef, const double* beta_ef, const double* btot, const double* theta) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   const int ne = c->P.n_grid + 2;
   if (n_entries != ne) return fail("mcs_set_grid: n_entries != n_grid+2");
   for (int i = 0; i < ne; ++i) {
@@ -420,7 +381,7 @@ int mcs_set_grid(mcs_ctx* c, int n_entries, const double* x_grid_cm, const doubl
 
 int mcs_set_cuts(mcs_ctx* c, int n_pcuts, const double* pcuts, int n_tcuts, const double* tcuts, int n_xspec,
                  const double* x_spec, const double* inj_fracs, const double* eps_target) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (n_pcuts < 1 || n_pcuts > MCS_NA_C) return fail("momentum-cutoffs: parameter na_c smaller than desired number of pcuts.");
   if (n_tcuts + 1 > MCS_NA_C) return fail("TCUTS: parameter na_c smaller than desired number of tcuts.");
   if (n_tcuts > 255) return fail("mcs_set_cuts: n_tcuts > 255");
@@ -448,7 +409,7 @@ int mcs_set_cuts(mcs_ctx* c, int n_pcuts, const double* pcuts, int n_tcuts, cons
 }
 
 int mcs_begin_iteration(mcs_ctx* c, int i_iter) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (i_iter < 1 || i_iter > c->P.n_itrs) return fail("mcs_begin_iteration: i_iter out of 1..n_itrs");
   const mcs_params& P = c->P;
   c->i_iter = i_iter;
@@ -461,7 +422,7 @@ int mcs_begin_iteration(mcs_ctx* c, int i_iter) {
 }
 
 int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, double pmax_cutoff, double density, double ewf) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   const mcs_params& P = c->P;
   if (i_ion < 1 || i_ion > P.n_ions) return fail("mcs_begin_species: i_ion out of 1..n_ions");
   if (i_iter < 1 || i_iter > P.n_itrs) return fail("mcs_begin_species: i_iter out of 1..n_itrs");
@@ -480,7 +441,7 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
 }
 
 int mcs_set_fluxes(mcs_ctx* c, const double* pxx, const double* pxz, const double* en) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   const int ng = c->P.n_grid;
   HIPCHK(hipMemcpyAsync(c->d_T + c->L.pxx_flux, pxx, ng * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->d_T + c->L.pxz_flux, pxz, ng * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -490,7 +451,7 @@ int mcs_set_fluxes(mcs_ctx* c, const double* pxx, const double* pxz, const doubl
 }
 
 int mcs_pop_upload(mcs_ctx* c, int64_t n, const mcs_soa* host) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (n < 0) return fail("mcs_pop_upload: n < 0");
   for (int64_t k = 0; k < n; ++k) {
     if (!(host->ptot_pf[k] > 0)) return fail("mcs_pop_upload: ptot_pf must be > 0 (zero-momentum particle: reference quirk G6)");
@@ -511,12 +472,12 @@ int mcs_pop_upload(mcs_ctx* c, int64_t n, const mcs_soa* host) {
   return 0;
 }
 int mcs_pop_download(mcs_ctx* c, int64_t n, mcs_soa* host) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (n > c->n) return fail("mcs_pop_download: n exceeds the population size");
   return download_soa(c, c->cur, n, host);
 }
 int mcs_saved_download(mcs_ctx* c, int64_t n, mcs_soa* host, uint8_t* l_save) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (n > c->n) return fail("mcs_saved_download: n exceeds the population size");
   if (host && download_soa(c, c->sav, n, host)) return 1;
   std::vector<uint8_t> own;
@@ -538,7 +499,7 @@ int64_t mcs_pop_size(mcs_ctx* c) { return c->n; }
 
 int mcs_init_pop(mcs_ctx* c, int64_t n, int64_t j_offset, int64_t n_total, const double* ptot_pf_in, const double* weight_in,
                  double x_start_cm, int i_grid_start, int relativistic, int fast_push) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (!c->have_grid) return fail("mcs_init_pop: call mcs_set_grid first");
   if (n < 0 || i_grid_start < 0 || i_grid_start > c->P.n_grid) return fail("mcs_init_pop: bad arguments");
   if (!std::isfinite(x_start_cm)) return fail("mcs_init_pop: x_start_cm must be finite");
@@ -547,7 +508,7 @@ int mcs_init_pop(mcs_ctx* c, int64_t n, int64_t j_offset, int64_t n_total, const
       return fail("mcs_init_pop: ptot_pf must be finite and > 0 (reference quirk G6), weight finite");
   c->n = 0; c->n_run_last = -1; c->n_saved_last = 0; c->idx_gidx = nullptr;   // the saved arrays / src[] of the last run no longer describe this population
   if (ensure_capacity(c, n)) return 1;
-  if (ensure_stage(c, 2 * n + 2)) return 1;
+  if (reserve(c->d_stage, 2 * n + 2)) return 1;
   if (n > 0) {
     HIPCHK(hipMemcpyAsync(c->d_stage, ptot_pf_in, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_stage + n, weight_in, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -571,7 +532,7 @@ int mcs_init_pop_binned(mcs_ctx* c, int64_t n, int64_t j_offset, int64_t n_total
 int mcs_init_pop_binned_strided(mcs_ctx* c, int64_t n, int64_t j_offset, int64_t j_stride, int64_t n_total, int n_bins,
                                 const double* bin_ptot_pf, const double* bin_weight, const int64_t* bin_start, double x_start_cm,
                                 int i_grid_start, int relativistic, int fast_push) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (!c->have_grid) return fail("mcs_init_pop_binned: call mcs_set_grid first");
   if (n < 0 || n_bins < 1 || n_bins > 4096 || i_grid_start < 0 || i_grid_start > c->P.n_grid || !bin_ptot_pf || !bin_weight || !bin_start)
     return fail("mcs_init_pop_binned: bad arguments");
@@ -587,7 +548,7 @@ int mcs_init_pop_binned_strided(mcs_ctx* c, int64_t n, int64_t j_offset, int64_t
   c->n = 0; c->n_run_last = -1; c->n_saved_last = 0; c->idx_gidx = nullptr;   // the saved arrays / src[] of the last run no longer describe this population
   if (ensure_capacity(c, n)) return 1;
   const size_t nd = (size_t)3 * n_bins + 1;      // ptot | weight | start (int64 in a double slot)
-  if (ensure_stage(c, (long long)nd + 2)) return 1;
+  if (reserve(c->d_stage, (long long)nd + 2)) return 1;
   if (n > 0) {
     std::vector<double> h(nd);
     std::memcpy(h.data(), bin_ptot_pf, sizeof(double) * n_bins);
@@ -607,28 +568,30 @@ int mcs_init_pop_binned_strided(mcs_ctx* c, int64_t n, int64_t j_offset, int64_t
 int mcs_num_cus(mcs_ctx* c) { return c->n_cu; }
 
 int mcs_set_launch(mcs_ctx* c, int blocks, int threads) {
+  MCS_ENTER(c);
   if (threads != 0 && (threads % 64 != 0 || threads > 256)) return fail("mcs_set_launch: threads must be a multiple of 64, <= 256");
   c->blocks = blocks; c->threads = threads ? threads : 256;
   return 0;
 }
 
-int mcs_set_debug_finals(mcs_ctx* c, int on) { c->debug_finals = on != 0; return 0; }
+int mcs_set_debug_finals(mcs_ctx* c, int on) { MCS_ENTER(c); c->debug_finals = on != 0; return 0; }
 // Host words only: the launches that are queued have their constants already, the next ones read these.
 int mcs_set_option(mcs_ctx* c, int key, int64_t value) {
-  if (!c) return fail("mcs_set_option: null context");
+  MCS_ENTER(c);
   std::string why;
   if (mcs_option_check_set(key, value, c->P.state_fp32, c->pp_masks_tried, &why) != MCS_OPTION_OK) return fail("mcs_set_option: " + why);
   c->opt[key] = value;
   return 0;
 }
 int mcs_get_option(mcs_ctx* c, int key, int64_t* value) {
-  if (!c || !value) return fail("mcs_get_option: null argument");
+  MCS_ENTER(c);
+  if (!value) return fail("mcs_get_option: null argument");
   if (!mcs_option_row(key)) return fail(format("mcs_get_option: unknown option key %d (the keys are 0..%d, enum mcs_option)", key, MCS_OPT_COUNT - 1));
   *value = c->opt[key];
   return 0;
 }
 int mcs_set_tail_slicing(mcs_ctx* c, int budget_trips) {
-  if (!c) return fail("mcs_set_tail_slicing: null context");
+  MCS_ENTER(c);
   switch (mcs_option_check_set(MCS_OPT_TAIL_BUDGET, budget_trips, c->P.state_fp32, c->pp_masks_tried, nullptr)) {
     case MCS_OPTION_OK: break;
     case MCS_OPTION_APPLIES: return fail("mcs_set_tail_slicing: the fp32-state kernels are not sliced (fp64 contexts only)");
@@ -640,24 +603,10 @@ int mcs_set_tail_slicing(mcs_ctx* c, int budget_trips) {
 int mcs_last_launches(mcs_ctx* c) { return c->tail_rounds_last; }
 int mcs_last_kernel(mcs_ctx* c) { return c->kernel_last; }
 int mcs_set_retro_cap(mcs_ctx* c, int64_t cap) {
+  MCS_ENTER(c);
   if (cap < 0 || cap > 2000000000LL) return fail("mcs_set_retro_cap: cap out of range");
   c->retro_cap = cap > 0 ? (int)cap : MCS_RETRO_CAP;
   return 0;
-}
-
-int mcs_run_pcut(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t* n_saved) {
-  return mcs_run_pcut_strided(c, i_pcut, i_prt_offset, 1, n_saved);
-}
-
-static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i_prt_stride, const int64_t* dev_gidx, int64_t* n_saved);
-
-int mcs_run_pcut_strided(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i_prt_stride, int64_t* n_saved) {
-  return run_pcut_impl(c, i_pcut, i_prt_offset, i_prt_stride, nullptr, n_saved);
-}
-
-int mcs_run_pcut_indexed(mcs_ctx* c, int i_pcut, const int64_t* dev_gidx, int64_t* n_saved) {
-  if (!dev_gidx && c->n > 0) return fail("mcs_run_pcut_indexed: null index list");
-  return run_pcut_impl(c, i_pcut, 0, 1, dev_gidx, n_saved);
 }
 
 // ---- K1 launches: which kernel, its geometry, the launch constants
@@ -728,13 +677,9 @@ static int sparse_claim(const mcs_ctx* c, KArgs& a, long long n_x, long long wav
 
 // two export buffers of need_cap lane states each (sliced launches)
 static int ensure_strag(mcs_ctx* c, long long need_cap) {
-  if (need_cap <= c->strag_cap) return 0;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  c->strag_cap = 0;
-  reset_all(c->d_strag[0], c->d_strag[1]);
-  if (reserve(c->d_strag[0], need_cap * MCS_STRAG_WORDS) || reserve(c->d_strag[1], need_cap * MCS_STRAG_WORDS)) return 1;
-  c->strag_cap = need_cap;
-  return 0;
+  if (need_cap <= c->strag.cap()) return 0;
+  HIPCHK(hipStreamSynchronize(c->stream));      // (queued launches may still export into the blocks that are freed)
+  return reserve(c->strag, need_cap);
 }
 
 // the launch constants of one pcut that do not depend on the kernel chosen (shared by mcs_run_pcut* and mcs_run_pcuts_fused)
@@ -757,17 +702,17 @@ static void fill_kargs(mcs_ctx* c, KArgs& a, int i_pcut, long long n, long long 
   a.seed_base = (unsigned long long)((long long)(c->i_iter - 1) * c->P.n_pts_max * c->tb.n_pcuts * c->P.n_ions +
                                      (long long)(c->i_ion - 1) * c->P.n_pts_max * c->tb.n_pcuts +
                                      (long long)(i_pcut - 1) * c->P.n_pts_max);
-  a.work_counter = c->d_counters; a.n_saved = c->d_counters + 1;
+  set_counters(a, c->d_counters, CTR_WORK, CTR_SAVED, CTR_EXPORT);
   a.tally_rep = c->d_tally_rep; a.rep_n = c->d_tally_rep ? c->rep_n : 0;
-  if (c->debug_finals) { a.f_reason = c->f_reason; a.f_helix = c->f_helix; a.f_retro = c->f_retro; a.f_ptot = c->f_ptot; a.f_x = c->f_x; }
-  a.budget_trips = budget; a.strag_count = c->d_counters + 3;
-  a.strag_out = c->d_strag[0];
+  if (c->debug_finals) { a.f_reason = c->fin.reason; a.f_helix = c->fin.helix; a.f_retro = c->fin.retro; a.f_ptot = c->fin.ptot; a.f_x = c->fin.x; }
+  a.budget_trips = budget;
+  a.strag_out = c->strag.d[0];
   a.ws_pop_max = mcs_transport_ws_threads() + 160;      // (read by the wave-specialised kernels only)
   a.ws_serve_min = 64;
 }
 
 static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i_prt_stride, const int64_t* dev_gidx, int64_t* n_saved) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER_AS(c, "mcs_run_pcut");
   if (i_prt_offset < 0 || i_prt_stride < 1) return fail("mcs_run_pcut: i_prt_first must be >= 0 and i_prt_stride >= 1");
   if (!c->have_grid || !c->have_cuts) return fail("mcs_run_pcut: grid/cuts not set");
   if (i_pcut < 1 || i_pcut > c->tb.n_pcuts) return fail("mcs_run_pcut: i_pcut out of range");
@@ -777,7 +722,7 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
   // exports read saved entries through the compacted index list, and mcs_saved_download zeroes the entries of unsaved
   // particles in the host copy it hands out (nine fills per pcut less in the timed path).
   if (n > 0) HIPCHK(hipMemsetAsync(c->d_lsave, 0, (size_t)n, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_counters, 0, 4 * sizeof(unsigned long long), c->stream));
+  HIPCHK(hipMemsetAsync(c->d_counters, 0, (CTR_EXPORT + 1) * sizeof(unsigned long long), c->stream));
   const int budget = (c->P.state_fp32 || n == 0) ? 0 : (int)c->o(MCS_OPT_TAIL_BUDGET);      // (the fp32 study kernel is not sliced)
   if (budget > 0) {
     // one entry per lane a launch can hold: 2 workgroups of 256 threads per CU, or the geometry of mcs_set_launch if that is larger
@@ -797,7 +742,7 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
   const int launch_threads = c->P.state_fp32 ? k1.threads : threads;
   const long long full = (long long)c->n_cu * k1.per_cu;
   int blocks = c->blocks > 0 ? c->blocks : persistent_grid(n, threads, full);
-  if (budget > 0 && (long long)blocks * threads > c->strag_cap) return fail("mcs_run_pcut: launch geometry exceeds the export buffer of a sliced run");
+  if (budget > 0 && (long long)blocks * threads > c->strag.cap()) return fail("mcs_run_pcut: launch geometry exceeds the export buffer of a sliced run");
   double ms_total = 0.0;
   c->tail_rounds_last = 0;
   c->kernel_last = k1.kernel;
@@ -812,17 +757,17 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
     ++c->tail_rounds_last;
     if (budget == 0) break;
     // sliced run: how many particles did the launch export?  They are the next launch's queue, spread over the chip's waves
-    HIPCHK(hipMemcpyAsync(c->h_back + 2, c->d_counters + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_back + CTR_EXPORT, c->d_counters + CTR_EXPORT, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    const unsigned long long n_x = c->h_back[2];
+    const unsigned long long n_x = c->h_back[CTR_EXPORT];
     float ms_r = 0.f;
     HIPCHK(hipEventElapsedTime(&ms_r, c->ev0, c->ev1));
     ms_total += ms_r;
     if (n_x == 0) break;
-    if ((long long)n_x > c->strag_cap) return fail("mcs_run_pcut: export buffer overrun");
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, sizeof(unsigned long long), c->stream));        // work counter
-    HIPCHK(hipMemsetAsync(c->d_counters + 3, 0, sizeof(unsigned long long), c->stream));    // export counter
-    a.strag_in = c->d_strag[round & 1]; a.strag_out = c->d_strag[(round + 1) & 1];
+    if ((long long)n_x > c->strag.cap()) return fail("mcs_run_pcut: export buffer overrun");
+    HIPCHK(hipMemsetAsync(c->d_counters + CTR_WORK, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_counters + CTR_EXPORT, 0, sizeof(unsigned long long), c->stream));
+    a.strag_in = c->strag.d[round & 1]; a.strag_out = c->strag.d[(round + 1) & 1];
     a.n_resume = (long long)n_x; a.fresh_lo = n;
     blocks = sparse_claim(c, a, (long long)n_x, (long long)c->n_cu * (threads / 64), threads, full);     // one wave per SIMD
     // few particles per wave already: nothing left to gain from another slice
@@ -830,12 +775,12 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
   }
   // the compaction half of new_pcut, queued behind the kernel: src[] for mcs_new_pcut / mcs_saved_export and an
   // independent count of the l_save flags next to the kernel's own n_saved counter, read back together
-  HIPCHK(mcs_launch_compact(c->d_lsave, n, c->d_bcounts, c->d_boffs, c->d_counters + 2, c->d_src, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_back, c->d_counters + 1, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(mcs_launch_compact(c->d_lsave, n, c->scan.bcounts, c->scan.boffs, c->d_counters + CTR_SCAN, c->scan.src, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_back + CTR_SAVED, c->d_counters + CTR_SAVED, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));      // SAVED, SCAN, EXPORT
   HIPCHK(hipStreamSynchronize(c->stream));
-  const unsigned long long ns[2] = {c->h_back[0], c->h_back[1]};
-  if (ws && c->h_back[2] != 0) {
-    return fail(format("mcs_run_pcut: a bounded wait of the wave-specialised kernel ran out (the launch is incomplete; code 0x%llx)", (unsigned long long)c->h_back[2]));
+  const unsigned long long ns[2] = {c->h_back[CTR_SAVED], c->h_back[CTR_SCAN]};
+  if (ws && c->h_back[CTR_EXPORT] != 0) {
+    return fail(format("mcs_run_pcut: a bounded wait of the wave-specialised kernel ran out (the launch is incomplete; code 0x%llx)", (unsigned long long)c->h_back[CTR_EXPORT]));
   }
   if (budget == 0) {
     float ms = 0.f;
@@ -851,6 +796,32 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
   if (n_saved) *n_saved = (int64_t)ns[0];
   return 0;
 }
+int mcs_run_pcut_strided(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i_prt_stride, int64_t* n_saved) {
+  return run_pcut_impl(c, i_pcut, i_prt_offset, i_prt_stride, nullptr, n_saved);
+}
+int mcs_run_pcut(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t* n_saved) { return run_pcut_impl(c, i_pcut, i_prt_offset, 1, nullptr, n_saved); }
+int mcs_run_pcut_indexed(mcs_ctx* c, int i_pcut, const int64_t* dev_gidx, int64_t* n_saved) {
+  MCS_ENTER(c);
+  if (!dev_gidx && c->n > 0) return fail("mcs_run_pcut_indexed: null index list");
+  return run_pcut_impl(c, i_pcut, 0, 1, dev_gidx, n_saved);
+}
+
+// the per-pcut outputs of a species loop: host arrays with one entry per pcut (strag: two); kernel_ms and strag may be null
+struct PcutOut { int64_t *n_use, *n_saved, *i_mult; double* kernel_ms; int64_t* strag; };
+
+// What mcs_run_pcuts_fused and mcs_run_pcuts_pipelined (`who`) do before they diverge: the arguments they share are checked, and the
+// population, saved and spare buffers hold *cap_n particles -- every population of the species fits:
+// n_new = n_saved * (n_target / n_saved) <= max(n_target, n_saved)
+static int species_loop_open(mcs_ctx* c, const char* who, int i_pcut_first, int i_pcut_last, const int64_t* n_target, const PcutOut& o, long long* cap_n) {
+  const std::string w = std::string(who) + ": ";
+  if (!c->have_grid || !c->have_cuts) return fail(w + "grid/cuts not set");
+  if (i_pcut_first < 1 || i_pcut_last > c->tb.n_pcuts || i_pcut_last < i_pcut_first) return fail(w + "pcut range");
+  if (!n_target || !o.n_use || !o.n_saved || !o.i_mult) return fail(w + "null argument");
+  if (c->o(MCS_OPT_TAIL_BUDGET) > 0 || c->blocks > 0) return fail(w + "not with sliced launches or an explicit launch geometry");
+  *cap_n = c->n;
+  for (int k = 0; k <= i_pcut_last - i_pcut_first; ++k) { if (n_target[k] < 1) return fail(w + "n_target < 1"); if (n_target[k] > *cap_n) *cap_n = n_target[k]; }
+  return ensure_capacity(c, *cap_n) || reserve(c->spare, grow_cap(*cap_n));
+}
 
 // ---- A species' pcuts queued back to back (the device side of it): transport, pcut_finalize and new_pcut of every
 // pcut first .. last with NOTHING read back in between -- n_saved, i_mult = max(n_target / n_saved, 1) (src/cuts.jl:42) and the
@@ -860,184 +831,79 @@ static int run_pcut_impl(mcs_ctx* c, int i_pcut, int64_t i_prt_offset, int64_t i
 // would have returned per pcut, and each transport launch's kernel time.  Pcuts after the one that saved nobody run empty.
 int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int64_t* n_target, int64_t* n_use_out, int64_t* n_saved_out,
                         int64_t* i_mult_out, double* kernel_ms_out) {
-  HIPCHK(hipSetDevice(c->device));
-  if (!c->have_grid || !c->have_cuts) return fail("mcs_run_pcuts_fused: grid/cuts not set");
-  if (i_pcut_first < 1 || i_pcut_last > c->tb.n_pcuts || i_pcut_last < i_pcut_first) return fail("mcs_run_pcuts_fused: pcut range");
-  if (!n_target || !n_use_out || !n_saved_out || !i_mult_out) return fail("mcs_run_pcuts_fused: null argument");
-  if (c->o(MCS_OPT_TAIL_BUDGET) > 0 || c->blocks > 0) return fail("mcs_run_pcuts_fused: not with sliced launches or an explicit launch geometry");
+  MCS_ENTER(c);
+  const PcutOut o{n_use_out, n_saved_out, i_mult_out, kernel_ms_out, nullptr};
   const int npc = i_pcut_last - i_pcut_first + 1;
-  long long cap_n = c->n;
-  for (int k = 0; k < npc; ++k) { if (n_target[k] < 1) return fail("mcs_run_pcuts_fused: n_target < 1"); if (n_target[k] > cap_n) cap_n = n_target[k]; }
-  // every population of the species fits: n_new = n_saved * (n_target / n_saved) <= max(n_target, n_saved)
-  if (ensure_capacity(c, cap_n)) return 1;
-  if (reserve(c->spare, grow_cap(cap_n))) return 1;
-  if (c->sav.cap() < cap_n && reserve(c->sav, grow_cap(cap_n))) return 1;
-  if (npc > c->fused_cap) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->fused_cap = 0;
-    reset_all(c->h_fargs, c->h_pd, c->d_fargs, c->d_pd);
-    if (reserve(c->h_fargs, npc) || reserve(c->h_pd, npc + 1) || reserve(c->d_fargs, npc) || reserve(c->d_pd, npc + 1)) return 1;
-    while ((int)c->f_ev.size() < 2 * npc) { Event e; HIPCHK(e.create()); c->f_ev.push_back(std::move(e)); }
-    c->fused_cap = npc;
+  long long cap_n = 0;
+  if (species_loop_open(c, "mcs_run_pcuts_fused", i_pcut_first, i_pcut_last, n_target, o, &cap_n)) return 1;
+  if (npc > c->fused.cap()) {
+    HIPCHK(hipStreamSynchronize(c->stream));      // (queued launches may still read the constants that are freed)
+    if (reserve(c->fused, npc)) return 1;
   }
+  while ((int)c->f_ev.size() < 2 * npc) { Event e; HIPCHK(e.create()); c->f_ev.push_back(std::move(e)); }
   // launch constants of every pcut: the buffers rotate (cur -> saved -> spare -> cur) independently of the sizes: pcut k reads
   // pop[k & 1] and its split writes the other one; c->cur and c->spare themselves are swapped once the species is through
   const DevPop pop[2] = {pop_view(c->cur), pop_view(c->spare)}, sav = pop_view(c->sav);
   for (int k = 0; k < npc; ++k) {
-    KArgs& a = c->h_fargs[k];
+    KArgs& a = c->fused.h_args[k];
     fill_kargs(c, a, i_pcut_first + k, 0, 0, 1, nullptr, 0);
     a.in = pop[k & 1]; a.sv = sav;
-    a.n_dev = &c->d_pd[k].n_use;
+    a.n_dev = &c->fused.d_pd[k].n_use;
   }
   const K1Plan k1 = k1_plan(c, cap_n, false, false);
   const int blocks = persistent_grid(cap_n, k1.threads, (long long)c->n_cu * k1.per_cu);
-  std::memset(c->h_pd, 0, sizeof(PcutDev) * (size_t)(npc + 1));
-  c->h_pd[0].n_use = c->n;
-  HIPCHK(hipMemcpyAsync(c->d_fargs, c->h_fargs, sizeof(KArgs) * (size_t)npc, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_pd, c->h_pd, sizeof(PcutDev) * (size_t)(npc + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), c->stream));
+  std::memset(c->fused.h_pd, 0, sizeof(PcutDev) * (size_t)(npc + 1));
+  c->fused.h_pd[0].n_use = c->n;
+  HIPCHK(hipMemcpyAsync(c->fused.d_args, c->fused.h_args, sizeof(KArgs) * (size_t)npc, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->fused.d_pd, c->fused.h_pd, sizeof(PcutDev) * (size_t)(npc + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_counters, 0, CTR_COUNT * sizeof(unsigned long long), c->stream));
   const int split_blocks = (int)std::min<long long>((cap_n + 255) / 256, (long long)c->n_cu * 16);
   for (int k = 0; k < npc; ++k) {
     HIPCHK(hipMemsetAsync(c->d_lsave, 0, (size_t)cap_n, c->stream));
     HIPCHK(hipEventRecord(c->f_ev[2 * k], c->stream));
-    HIPCHK(mcs_launch_transport(c->d_fargs + k, k1.kernel, blocks, k1.threads, c->stream));
+    HIPCHK(mcs_launch_transport(c->fused.d_args + k, k1.kernel, blocks, k1.threads, c->stream));
     HIPCHK(hipEventRecord(c->f_ev[2 * k + 1], c->stream));
-    HIPCHK(mcs_launch_finalize_split_dev(c->d_lsave, cap_n, c->d_bcounts, c->d_boffs, c->d_counters + 2, c->d_src, c->d_pd + k, c->d_pd + k + 1,
-                                         c->d_counters, (long long)n_target[k], c->d_counters + 4, sav, pop[(k + 1) & 1], split_blocks, c->stream));
+    HIPCHK(mcs_launch_finalize_split_dev(c->d_lsave, cap_n, c->scan.bcounts, c->scan.boffs, c->d_counters + CTR_SCAN, c->scan.src, c->fused.d_pd + k, c->fused.d_pd + k + 1,
+                                         c->d_counters, (long long)n_target[k], c->d_counters + CTR_MISMATCH, sav, pop[(k + 1) & 1], split_blocks, c->stream));
   }
   c->rep_dirty = true;
-  HIPCHK(hipMemcpyAsync(c->h_pd, c->d_pd, sizeof(PcutDev) * (size_t)(npc + 1), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_back, c->d_counters + 3, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->fused.h_pd, c->fused.d_pd, sizeof(PcutDev) * (size_t)(npc + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->h_back + CTR_EXPORT, c->d_counters + CTR_EXPORT, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));      // EXPORT, MISMATCH
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->h_back[1] != 0) return fail("mcs_run_pcuts_fused: the kernel's n_saved counter and the count of l_save flags differ");
-  if (is_ws(k1.kernel) && c->h_back[0] != 0) return fail("mcs_run_pcuts_fused: a bounded wait of the wave-specialised kernel ran out (a launch is incomplete)");
+  if (c->h_back[CTR_MISMATCH] != 0) return fail("mcs_run_pcuts_fused: the kernel's n_saved counter and the count of l_save flags differ");
+  if (is_ws(k1.kernel) && c->h_back[CTR_EXPORT] != 0) return fail("mcs_run_pcuts_fused: a bounded wait of the wave-specialised kernel ran out (a launch is incomplete)");
   double ms_sum = 0.0;
   for (int k = 0; k < npc; ++k) {
-    n_use_out[k] = c->h_pd[k].n_use; n_saved_out[k] = c->h_pd[k].n_saved; i_mult_out[k] = c->h_pd[k].i_mult;
+    o.n_use[k] = c->fused.h_pd[k].n_use; o.n_saved[k] = c->fused.h_pd[k].n_saved; o.i_mult[k] = c->fused.h_pd[k].i_mult;
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, c->f_ev[2 * k], c->f_ev[2 * k + 1]));
-    if (kernel_ms_out) kernel_ms_out[k] = ms;
+    if (o.kernel_ms) o.kernel_ms[k] = ms;
     ms_sum += ms;
   }
   // what the mcs_run_pcut / mcs_new_pcut sequence leaves: it ends with the first pcut that saved nobody, whose population stays as it
   // ran (the pcuts after it ran empty and wrote nothing); if every pcut saved somebody, the children of the last split
-  int n_split = 0; while (n_split < npc && c->h_pd[n_split].n_saved > 0) ++n_split;
+  int n_split = 0; while (n_split < npc && c->fused.h_pd[n_split].n_saved > 0) ++n_split;
   if (n_split & 1) std::swap(c->cur, c->spare);
-  c->n = c->h_pd[n_split].n_use;
+  c->n = c->fused.h_pd[n_split].n_use;
   c->n_run_last = -1; c->n_saved_last = 0;
   c->last_ms = ms_sum; c->tail_rounds_last = npc;
   c->kernel_last = k1.kernel;
   return 0;
 }
 
-// What the pcut loop of mcs_run_pcuts_pipelined leaves to its caller, which drains the streams and commits the buffers on every exit.
-struct PipeRun {
-  PopBuf *cur, *nxt;           // the population of the current pcut and the target of its split: c->cur / c->spare, rotated
-  hipStream_t s1, s2;          // the main stream of the CURRENT pcut (c->stream, or the masked one when the pcut has side work); the side stream
-  bool masked;                 // s1 and s2 have complementary CU masks (MCS_PIPE_SIDE_CUS)
-  int n_done;                  // pcuts whose population size is in n_use_out
-  double ms_sum;               // kernel time of the main launches
-};
-static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_first, int npc, long long cap_n, const int64_t* n_target,
-                           int64_t long_draws, int64_t long_imult_max, int64_t* n_use_out, int64_t* n_saved_out, int64_t* i_mult_out,
-                           double* kernel_ms_out, int64_t* strag_out);
-
-// ---- A species' pcuts with the long histories of pcut p finishing BESIDE pcut p + 1 (DESIGN.md "Pipelined pcuts").
-// A launch waits for its longest histories -- 10^4 passes of single particles while the chip idles (40 % of an iteration at 10^6
-// particles).  What stands in the way of starting the next pcut is the ORDER of its population: child o of the split is a copy of
-// saved particle o / i_mult in index order (src/cuts.jl:66-92), and the index keys the child's random stream -- one unresolved
-// particle leaves every index behind it open.  Here the order is made independent of the schedule: a particle is LONG in a pcut when its
-// history there took at least `long_draws` random draws (a property of its stream alone), and the next population is the children of
-// the saved particles that are not long, in index order, followed by the children of the saved long ones, in index order.  The oracle
-// orders the same way (orc_set_long_draws), so parity stays bit for bit; long_draws is a parameter of the algorithm like the seeds.
-// Per pcut: the main launch (stream) and the late launch (side stream: the children of the previous pcut's saved long particles)
-// export the particles that are still running once they are long and end; both join; the main group is split and the next main
-// launch starts, while on the side stream the exported particles run to their end, the late group is split and the next late launch
-// runs.  i_mult = max(n_target / n_saved, 1) needs the number of long particles that will be saved: it is taken as soon as both
-// bounds give the same quotient, else the pcut waits for them (counted in strag_out).  One rank, global indices 0, 1, 2, ...; fp64 state.
-// Outputs as mcs_run_pcuts_fused; strag_out (or NULL): [2k] particles pcut k exported, [2k + 1] 1 if its i_mult had to wait.
-int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int64_t* n_target, int64_t long_draws, int64_t long_imult_max,
-                            int64_t* n_use_out, int64_t* n_saved_out, int64_t* i_mult_out, double* kernel_ms_out, int64_t* strag_out) {
-  HIPCHK(hipSetDevice(c->device));
-  if (!c->have_grid || !c->have_cuts) return fail("mcs_run_pcuts_pipelined: grid/cuts not set");
-  if (i_pcut_first < 1 || i_pcut_last > c->tb.n_pcuts || i_pcut_last < i_pcut_first) return fail("mcs_run_pcuts_pipelined: pcut range");
-  if (!n_target || !n_use_out || !n_saved_out || !i_mult_out) return fail("mcs_run_pcuts_pipelined: null argument");
-  if (c->P.state_fp32) return fail("mcs_run_pcuts_pipelined: not for the fp32-state variant");
-  if (c->o(MCS_OPT_TAIL_BUDGET) > 0 || c->blocks > 0) return fail("mcs_run_pcuts_pipelined: not with sliced launches or an explicit launch geometry");
-  if (long_draws < 64 || long_draws > 2000000000LL) return fail("mcs_run_pcuts_pipelined: long_draws out of range (64 .. 2e9)");
-  const int npc = i_pcut_last - i_pcut_first + 1;
-  long long cap_n = c->n;
-  for (int k = 0; k < npc; ++k) { if (n_target[k] < 1) return fail("mcs_run_pcuts_pipelined: n_target < 1"); if (n_target[k] > cap_n) cap_n = n_target[k]; }
-  const long long cap = grow_cap(cap_n);
-  if (ensure_capacity(c, cap_n)) return 1;
-  if (reserve(c->spare, cap)) return 1;
-  if (reserve(c->pp_sav2, cap)) return 1;
-  if (c->pp_cap < cap) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->pp_cap = 0;
-    reset_all(c->pp_lsave2, c->pp_bcounts, c->pp_boffs, c->pp_src);
-    const long long nb = (cap + 1023) / 1024;
-    if (reserve(c->pp_lsave2, cap) || reserve(c->pp_bcounts, nb) || reserve(c->pp_boffs, nb) || reserve(c->pp_src, cap)) return 1;
-    c->pp_cap = cap;
-  }
-  // what the first call creates (each guarded by itself: a call that failed half-way is made up for by the next one)
-  if (!c->pp_s2) HIPCHK(c->pp_s2.create_non_blocking());
-  if (!c->pp_reset) HIPCHK(c->pp_reset.create_untimed());
-  if (reserve(c->pp_dpc, 16) || reserve(c->pp_hpc, 16) || reserve(c->pp_hargs, 3) || reserve(c->pp_dargs, 3) || reserve(c->pp_dpdl, 2) ||
-      reserve(c->pp_hpdl, 2))
-    return 1;
-  if (!c->pp_masks_tried) {
-    c->pp_masks_tried = true;
-    if ((int)c->o(MCS_OPT_PIPE_SIDE_CUS) > 0 && (int)c->o(MCS_OPT_PIPE_SIDE_CUS) < c->n_cu) {
-      const int words = (c->n_cu + 31) / 32;
-      std::vector<uint32_t> m_side((size_t)words, 0u), m_main((size_t)words, 0u);
-      for (int i = 0; i < c->n_cu; ++i) (i < (int)c->o(MCS_OPT_PIPE_SIDE_CUS) ? m_side : m_main)[(size_t)(i >> 5)] |= 1u << (i & 31);
-      if (c->pp_s1m.create_cu_masked((uint32_t)words, m_main.data()) != hipSuccess ||
-          c->pp_s2m.create_cu_masked((uint32_t)words, m_side.data()) != hipSuccess) {
-        (void)hipGetLastError();
-        reset_all(c->pp_s1m, c->pp_s2m);
-      }
-    }
-  }
-  // the sliced form of the species' kernel (PLAIN, LOSSY, PLAIN_ETF, general); a wave exports at most its 64 lanes, once: room for the
-  // main and the late launch of one pcut
-  const K1Plan k1 = k1_plan(c, 0, true, false);
-  if (ensure_strag(c, 2 * (long long)c->n_cu * k1.per_cu * k1.threads)) return 1;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const bool masked = c->pp_s1m && c->pp_s2m;
-  PipeRun r{&c->cur, &c->spare, c->stream, masked ? c->pp_s2m : c->pp_s2, masked, 0, 0.0};
-  int rc = pipelined_pcuts(c, r, k1, i_pcut_first, npc, cap_n, n_target, long_draws, long_imult_max, n_use_out, n_saved_out, i_mult_out,
-                           kernel_ms_out, strag_out);
-  // every exit of the loop, a failed one too: no stream may still write the population, the saved arrays or the tallies
-  for (hipStream_t st : {r.s2, r.s1, c->stream}) {
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess && rc == 0) rc = fail(std::string("mcs_run_pcuts_pipelined: hipStreamSynchronize: ") + hipGetErrorString(e));
-  }
-  if (r.cur != &c->cur) std::swap(c->cur, c->spare);
-  // (after a failure the population is half-written: it is not run or split again before the next mcs_init_pop* / mcs_pop_upload)
-  c->n = rc ? 0 : (r.n_done > 0 ? n_use_out[r.n_done - 1] : c->n);
-  c->n_run_last = -1; c->n_saved_last = 0;
-  c->last_ms = r.ms_sum;
-  c->kernel_last = k1.kernel;
-  return rc;
-}
-
-// the pcut loop of mcs_run_pcuts_pipelined: on failure it returns at once, its caller drains and commits
-static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_first, int npc, long long cap_n, const int64_t* n_target,
-                           int64_t long_draws, int64_t long_imult_max, int64_t* n_use_out, int64_t* n_saved_out, int64_t* i_mult_out,
-                           double* kernel_ms_out, int64_t* strag_out) {
-  // counters: [0] work, [1] n_saved of the main launch | [2] main scan total | [3 + q] particles exported by pcut parity q |
-  // [5] work, [6] n_saved of the resumed long histories | [7] work, [8] n_saved of the late launch | [9] late scan total
-  unsigned long long* const pc = c->pp_dpc;
-  const bool masked = r.masked;
-  hipStream_t& s1 = r.s1;
-  hipStream_t const s2 = r.s2;
+// The pcut loop of mcs_run_pcuts_pipelined: on failure it returns at once, its caller drains the streams.  It keeps the context's own
+// words as it goes: c->cur / c->spare are the population of the current pcut and the target of its split (swapped per pcut), c->n the
+// size of the last population it has put into the outputs, c->last_ms the kernel time of the main launches.
+static int pipelined_pcuts(mcs_ctx* c, const K1Plan& k1, int i_pcut_first, int npc, long long cap_n, const int64_t* n_target,
+                           int64_t long_draws, int64_t long_imult_max, const PcutOut& o) {
+  unsigned long long* const pc = c->pp_dpc;      // (the words of enum PipeCtr)
+  const bool masked = c->pp_s1m && c->pp_s2m;      // the two streams with complementary CU masks exist (MCS_PIPE_SIDE_CUS)
+  hipStream_t s1 = c->stream;                      // the main stream of the CURRENT pcut: the masked one when the pcut has side work
+  hipStream_t const s2 = masked ? c->pp_s2m : c->pp_s2;
   hipStream_t const s_alone = masked ? c->stream : c->pp_s2;   // long histories the pcut waits for: the whole chip
   const int side_max = 64;     // workgroups (of 2 per CU) the main launch leaves free for the side stream at most
   const int threads = k1.threads;
   const long long full = (long long)c->n_cu * k1.per_cu;
-  PopBuf*& cur = r.cur;
-  PopBuf*& nxt = r.nxt;
   const DevPop savb[2] = {pop_view(c->sav), pop_view(c->pp_sav2)};
   uint8_t* lsv[2] = {c->d_lsave, c->pp_lsave2};
   long long nA = c->n, nL = 0;
@@ -1050,17 +916,18 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
   long long n1_prev = 0, sofar_prev = 0;
   c->pp_waits_last = 0;
   c->tail_rounds_last = 0;
+  c->last_ms = 0.0;
   const bool dbg_pipe = std::getenv("MCS_PIPE_DEBUG") != nullptr;
-  for (int k = 0; k < npc; ++k) { n_use_out[k] = 0; n_saved_out[k] = 0; i_mult_out[k] = 1; if (kernel_ms_out) kernel_ms_out[k] = 0.0; if (strag_out) { strag_out[2 * k] = 0; strag_out[2 * k + 1] = 0; } }
-  HIPCHK(hipMemsetAsync(pc, 0, 16 * sizeof(unsigned long long), s1));
+  for (int k = 0; k < npc; ++k) { o.n_use[k] = 0; o.n_saved[k] = 0; o.i_mult[k] = 1; if (o.kernel_ms) o.kernel_ms[k] = 0.0; if (o.strag) { o.strag[2 * k] = 0; o.strag[2 * k + 1] = 0; } }
+  HIPCHK(hipMemsetAsync(pc, 0, PC_COUNT * sizeof(unsigned long long), s1));
   if (nA > 0) HIPCHK(hipMemsetAsync(lsv[0], 0, (size_t)nA, s1));
   // the launch of the exported particles of pcut `i_pcut` (parity q), to their end, on `st`
   auto launch_resume = [&](int i_pcut, int q, long long n_pop, long long n_x, hipStream_t st, bool alone) -> int {
     KArgs& a = c->pp_hargs[1];
     fill_kargs(c, a, i_pcut, n_pop, 0, 1, nullptr, 0);
-    a.in = pop_view(*cur); a.sv = savb[q]; a.l_save = lsv[q];
-    a.work_counter = pc + 5; a.n_saved = pc + 6; a.strag_count = pc + 3 + (q ^ 1); a.strag_out = c->d_strag[q ^ 1];
-    a.strag_in = c->d_strag[q]; a.n_resume = n_x; a.fresh_lo = n_pop; a.long_draws = (unsigned int)Bk; a.budget_trips = 0;
+    a.in = pop_view(c->cur); a.sv = savb[q]; a.l_save = lsv[q];
+    set_counters(a, pc, PC_RES_WORK, PC_RES_SAVED, PC_EXPORT + (q ^ 1)); a.strag_out = c->strag.d[q ^ 1];
+    a.strag_in = c->strag.d[q]; a.n_resume = n_x; a.fresh_lo = n_pop; a.long_draws = (unsigned int)Bk; a.budget_trips = 0;
     // few particles per wave (sparse_claim), on at most one wave per SIMD of the chip (alone on the chip -- the pcut waits for them --
     // one wave per SIMD; beside a main launch every wave they hold is taken from it: 16 particles per wave cost 12 % on the longest
     // history and 1 / 16 of the slots)
@@ -1077,8 +944,8 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     if (nA > 0) {
       KArgs& a = c->pp_hargs[0];
       fill_kargs(c, a, i_pcut, nA, 0, 1, nullptr, Bk > 0 ? 1 : 0);
-      a.in = pop_view(*cur); a.sv = savb[q]; a.l_save = lsv[q];
-      a.work_counter = pc; a.n_saved = pc + 1; a.strag_count = pc + 3 + q; a.strag_out = c->d_strag[q];
+      a.in = pop_view(c->cur); a.sv = savb[q]; a.l_save = lsv[q];
+      set_counters(a, pc, PC_WORK, PC_SAVED, PC_EXPORT + q); a.strag_out = c->strag.d[q];
       a.long_draws = (unsigned int)Bk;
       HIPCHK(hipMemcpyAsync(c->pp_dargs, &a, sizeof(KArgs), hipMemcpyHostToDevice, s1));
       HIPCHK(hipEventRecord(c->ev0, s1));
@@ -1100,64 +967,63 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     if (side_pending) HIPCHK(hipMemcpyAsync(c->pp_hpdl + q, c->pp_dpdl + q, sizeof(PcutDev), hipMemcpyDeviceToHost, s1));
     // (the late group's size is on the device until here: the compaction below covers every index it can have)
     const long long n_hi = nA + nL;       // nL: the host's upper bound while side_pending
-    HIPCHK(mcs_launch_compact_match(lsv[q], n_hi, c->d_bcounts, c->d_boffs, pc + 2, c->d_src, 1u, s1));
-    HIPCHK(hipMemcpyAsync(c->pp_hpc, pc, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s1));
+    HIPCHK(mcs_launch_compact_match(lsv[q], n_hi, c->scan.bcounts, c->scan.boffs, pc + PC_SCAN, c->scan.src, 1u, s1));
+    HIPCHK(hipMemcpyAsync(c->pp_hpc, pc, PC_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, s1));
     HIPCHK(hipStreamSynchronize(s1));
     const auto tj2 = std::chrono::steady_clock::now();
     float ms_main = 0.f;
-    if (nA > 0) { HIPCHK(hipEventElapsedTime(&ms_main, c->ev0, c->ev1)); if (kernel_ms_out) kernel_ms_out[k] = ms_main; r.ms_sum += ms_main; }
+    if (nA > 0) { HIPCHK(hipEventElapsedTime(&ms_main, c->ev0, c->ev1)); if (o.kernel_ms) o.kernel_ms[k] = ms_main; c->last_ms += ms_main; }
     const unsigned long long* h = c->pp_hpc;
     double dbg_wait_ms = 0.0;
     if (side_pending) {
       // the previous pcut is complete now: its saved long particles, the size of this pcut's late group
       const long long n5_prev = c->pp_hpdl[q].n_saved;
       nL = c->pp_hpdl[q].n_new;
-      n_saved_out[k - 1] = n1_prev + n5_prev;
-      if (sofar_prev + (long long)h[6] != n_saved_out[k - 1]) {
+      o.n_saved[k - 1] = n1_prev + n5_prev;
+      if (sofar_prev + (long long)h[PC_RES_SAVED] != o.n_saved[k - 1]) {
         return fail(format("mcs_run_pcuts_pipelined: pcut %d: the kernels' n_saved counters (%lld + %llu resumed) and the count of status bytes (%lld + %lld long) differ",
-                           i_pcut - 1, sofar_prev, (unsigned long long)h[6], n1_prev, n5_prev));
+                           i_pcut - 1, sofar_prev, (unsigned long long)h[PC_RES_SAVED], n1_prev, n5_prev));
       }
     }
     side_pending = false;
-    n_use_out[k] = nA + nL;
-    r.n_done = k + 1;
-    const long long n1 = (long long)h[2], n_T = (long long)h[3 + q];
-    long long sofar = (long long)h[1] + (long long)h[8];        // saved by the main and the late launch: not long, or long and already ended
-    if (strag_out) strag_out[2 * k] = n_T;
-    if (n_T > c->strag_cap) return fail("mcs_run_pcuts_pipelined: export buffer overrun");
+    c->n = o.n_use[k] = nA + nL;
+    const long long n1 = (long long)h[PC_SCAN], n_T = (long long)h[PC_EXPORT + q];
+    long long sofar = (long long)h[PC_SAVED] + (long long)h[PC_LATE_SAVED];        // saved by the main and the late launch: not long, or long and already ended
+    if (o.strag) o.strag[2 * k] = n_T;
+    if (n_T > c->strag.cap()) return fail("mcs_run_pcuts_pipelined: export buffer overrun");
     if (sofar < n1) {
       return fail(format("mcs_run_pcuts_pipelined: pcut %d: the kernels' n_saved counters (%llu main + %llu late) are below the count of status bytes (%lld)",
-                         i_pcut, (unsigned long long)h[1], (unsigned long long)h[8], n1));
+                         i_pcut, (unsigned long long)h[PC_SAVED], (unsigned long long)h[PC_LATE_SAVED], n1));
     }
     const long long target = (long long)n_target[k];
     const bool last = k == npc - 1;
     long long n_open = n_T;                 // exported particles that have not been resumed yet
-    if (sofar + n_T == 0) { n_saved_out[k] = 0; break; }                       // nobody left: the species ends here
+    if (sofar + n_T == 0) { o.n_saved[k] = 0; break; }                       // nobody left: the species ends here
     const long long im_hi = target / (sofar + n_T) > 1 ? target / (sofar + n_T) : 1;
     const long long im_lo = sofar > 0 ? (target / sofar > 1 ? target / sofar : 1) : -1;
     // (more long histories than the side stream's CUs hold at 16 per wave, twice over: beside the main launch they would outlast it)
     const long long side_cap = masked ? (long long)(int)c->o(MCS_OPT_PIPE_SIDE_CUS) * 8 * 16 * 2 : (long long)side_max * 4 * 16 * 2;
     if ((last || im_lo != im_hi || n_T > side_cap) && n_T > 0) {
       // i_mult depends on how many of the long histories end saved (or this is the last pcut, or they are too many): they finish first
-      HIPCHK(hipMemsetAsync(pc + 5, 0, 2 * sizeof(unsigned long long), s_alone));
+      HIPCHK(hipMemsetAsync(pc + PC_RES_WORK, 0, 2 * sizeof(unsigned long long), s_alone));      // RES_WORK, RES_SAVED
       if (launch_resume(i_pcut, q, nA + nL, n_T, s_alone, true)) return 1;
-      HIPCHK(hipMemcpyAsync(c->pp_hpc + 6, pc + 6, sizeof(unsigned long long), hipMemcpyDeviceToHost, s_alone));
+      HIPCHK(hipMemcpyAsync(c->pp_hpc + PC_RES_SAVED, pc + PC_RES_SAVED, sizeof(unsigned long long), hipMemcpyDeviceToHost, s_alone));
       const auto tw0 = std::chrono::steady_clock::now();
       HIPCHK(hipStreamSynchronize(s_alone));
       dbg_wait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-      sofar += (long long)c->pp_hpc[6];
+      sofar += (long long)c->pp_hpc[PC_RES_SAVED];
       n_open = 0;
-      if (strag_out) strag_out[2 * k + 1] = 1;
+      if (o.strag) o.strag[2 * k + 1] = 1;
       ++c->pp_waits_last;
     }
     if (dbg_pipe)
       std::fprintf(stderr, "[pipe] pcut %2d n_use %8lld (late %7lld) main %6.2f ms | side-sync %6.2f ms main-sync %6.2f ms | saved so far %8lld exported %6lld %s %6.2f ms\n",
                    i_pcut, nA + nL, nL, ms_main, std::chrono::duration<double, std::milli>(tj1 - tj0).count(),
                    std::chrono::duration<double, std::milli>(tj2 - tj1).count(), sofar, n_T, n_open == 0 && n_T > 0 ? "WAITED" : "      ", dbg_wait_ms);
-    if (sofar + n_open == 0) { n_saved_out[k] = 0; break; }                  // (the long histories all ended: the species ends here)
+    if (sofar + n_open == 0) { o.n_saved[k] = 0; break; }                  // (the long histories all ended: the species ends here)
     const long long i_mult = target / (sofar + n_open) > 1 ? target / (sofar + n_open) : 1;     // (== for both bounds when n_open > 0)
-    i_mult_out[k] = i_mult;
-    n_saved_out[k] = sofar;                 // (complete unless long histories are still open: then the next join adds those that end saved)
+    o.i_mult[k] = i_mult;
+    o.n_saved[k] = sofar;                 // (complete unless long histories are still open: then the next join adds those that end saved)
     if (last || sofar + n_open == 0) break;
     const long long B_next = (long_imult_max <= 0 || i_mult <= long_imult_max) ? long_draws : 0;
     // ---- the next pcut: main group = children of the saved particles that are not long; late group = children of the saved long ones
@@ -1172,26 +1038,26 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     side_blocks = 0;
     s1 = (masked && n5_max > 0) ? c->pp_s1m : c->stream;      // (both are idle: the join synchronised the host with every stream)
     if (n5_max > 0) {
-      HIPCHK(hipMemsetAsync(pc + 5, 0, 2 * sizeof(unsigned long long), s2));
+      HIPCHK(hipMemsetAsync(pc + PC_RES_WORK, 0, 2 * sizeof(unsigned long long), s2));
       if (n_open > 0 && launch_resume(i_pcut, q, nA + nL, n_open, s2, false)) return 1;
     }
-    HIPCHK(hipMemsetAsync(pc, 0, 5 * sizeof(unsigned long long), s1));
-    HIPCHK(hipMemsetAsync(pc + 7, 0, 3 * sizeof(unsigned long long), s1));
+    HIPCHK(hipMemsetAsync(pc, 0, PC_RES_WORK * sizeof(unsigned long long), s1));                 // the main launch's words, both export counts
+    HIPCHK(hipMemsetAsync(pc + PC_LATE_WORK, 0, 3 * sizeof(unsigned long long), s1));            // LATE_WORK, LATE_SAVED, LATE_SCAN
     if (nA_next + nL_max > 0) HIPCHK(hipMemsetAsync(lsv[q ^ 1], 0, (size_t)(nA_next + nL_max), s1));
     HIPCHK(hipEventRecord(c->pp_reset, s1));
-    HIPCHK(mcs_launch_split(savb[q], pop_view(*nxt), c->d_src, nA_next, i_mult, s1));
+    HIPCHK(mcs_launch_split(savb[q], pop_view(c->spare), c->scan.src, nA_next, i_mult, s1));
     n1_prev = n1; sofar_prev = sofar;
     if (n5_max > 0) {
       HIPCHK(hipStreamWaitEvent(s2, c->pp_reset, 0));
       const int split_blocks = (int)std::min<long long>((nL_max + 255) / 256, (long long)c->n_cu * 4);
-      HIPCHK(mcs_launch_late_split(lsv[q], nA + nL, c->pp_bcounts, c->pp_boffs, pc + 9, c->pp_src, c->pp_dpdl + (q ^ 1), i_mult, nA_next, savb[q],
-                                   pop_view(*nxt, nA_next), split_blocks < 1 ? 1 : split_blocks, s2));
+      HIPCHK(mcs_launch_late_split(lsv[q], nA + nL, c->pp_scan.bcounts, c->pp_scan.boffs, pc + PC_LATE_SCAN, c->pp_scan.src, c->pp_dpdl + (q ^ 1), i_mult, nA_next, savb[q],
+                                   pop_view(c->spare, nA_next), split_blocks < 1 ? 1 : split_blocks, s2));
       // the late launch of the next pcut: particles nA_next .. of its population, their number read on the device
       KArgs& a = c->pp_hargs[2];
       fill_kargs(c, a, i_pcut + 1, nA_next, 0, 1, nullptr, B_next > 0 ? 1 : 0);
-      a.in = pop_view(*nxt); a.sv = savb[q ^ 1]; a.l_save = lsv[q ^ 1];
+      a.in = pop_view(c->spare); a.sv = savb[q ^ 1]; a.l_save = lsv[q ^ 1];
       a.n_dev = &c->pp_dpdl[q ^ 1].n_use; a.fresh_lo = nA_next;
-      a.work_counter = pc + 7; a.n_saved = pc + 8; a.strag_count = pc + 3 + (q ^ 1); a.strag_out = c->d_strag[q ^ 1];
+      set_counters(a, pc, PC_LATE_WORK, PC_LATE_SAVED, PC_EXPORT + (q ^ 1)); a.strag_out = c->strag.d[q ^ 1];
       a.long_draws = (unsigned int)B_next;
       HIPCHK(hipMemcpyAsync(c->pp_dargs + 2, &a, sizeof(KArgs), hipMemcpyHostToDevice, s2));
       const int blocks_l = persistent_grid(nL_max, threads, full);
@@ -1206,13 +1072,79 @@ static int pipelined_pcuts(mcs_ctx* c, PipeRun& r, const K1Plan& k1, int i_pcut_
     }
     nA = nA_next;
     Bk = B_next;
-    std::swap(cur, nxt);
+    std::swap(c->cur, c->spare);
   }
   return 0;
 }
 
+// ---- A species' pcuts with the long histories of pcut p finishing BESIDE pcut p + 1 (DESIGN.md "Pipelined pcuts").
+// A launch waits for its longest histories -- 10^4 passes of single particles while the chip idles (40 % of an iteration at 10^6
+// particles).  What stands in the way of starting the next pcut is the ORDER of its population: child o of the split is a copy of
+// saved particle o / i_mult in index order (src/cuts.jl:66-92), and the index keys the child's random stream -- one unresolved
+// particle leaves every index behind it open.  Here the order is made independent of the schedule: a particle is LONG in a pcut when its
+// history there took at least `long_draws` random draws (a property of its stream alone), and the next population is the children of
+// the saved particles that are not long, in index order, followed by the children of the saved long ones, in index order.  The oracle
+// orders the same way (orc_set_long_draws), so parity stays bit for bit; long_draws is a parameter of the algorithm like the seeds.
+// Per pcut: the main launch (stream) and the late launch (side stream: the children of the previous pcut's saved long particles)
+// export the particles that are still running once they are long and end; both join; the main group is split and the next main
+// launch starts, while on the side stream the exported particles run to their end, the late group is split and the next late launch
+// runs.  i_mult = max(n_target / n_saved, 1) needs the number of long particles that will be saved: it is taken as soon as both
+// bounds give the same quotient, else the pcut waits for them (counted in strag_out).  One rank, global indices 0, 1, 2, ...; fp64 state.
+// Outputs as mcs_run_pcuts_fused; strag_out (or NULL): [2k] particles pcut k exported, [2k + 1] 1 if its i_mult had to wait.
+int mcs_run_pcuts_pipelined(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int64_t* n_target, int64_t long_draws, int64_t long_imult_max,
+                            int64_t* n_use_out, int64_t* n_saved_out, int64_t* i_mult_out, double* kernel_ms_out, int64_t* strag_out) {
+  MCS_ENTER(c);
+  if (c->P.state_fp32) return fail("mcs_run_pcuts_pipelined: not for the fp32-state variant");
+  if (long_draws < 64 || long_draws > 2000000000LL) return fail("mcs_run_pcuts_pipelined: long_draws out of range (64 .. 2e9)");
+  const PcutOut o{n_use_out, n_saved_out, i_mult_out, kernel_ms_out, strag_out};
+  const int npc = i_pcut_last - i_pcut_first + 1;
+  long long cap_n = 0;
+  if (species_loop_open(c, "mcs_run_pcuts_pipelined", i_pcut_first, i_pcut_last, n_target, o, &cap_n)) return 1;
+  const long long cap = grow_cap(cap_n);
+  if (reserve(c->pp_sav2, cap)) return 1;
+  if (c->pp_lsave2.cap() < cap || c->pp_scan.cap() < cap) {
+    HIPCHK(hipStreamSynchronize(c->stream));      // (queued work may still use the blocks that are freed)
+    if (reserve(c->pp_lsave2, cap) || reserve(c->pp_scan, cap)) return 1;
+  }
+  // what the first call creates (each guarded by itself: a call that failed half-way is made up for by the next one)
+  if (!c->pp_s2) HIPCHK(c->pp_s2.create_non_blocking());
+  if (!c->pp_reset) HIPCHK(c->pp_reset.create_untimed());
+  if (reserve(c->pp_dpc, PC_COUNT) || reserve(c->pp_hpc, PC_COUNT) || reserve(c->pp_hargs, 3) || reserve(c->pp_dargs, 3) || reserve(c->pp_dpdl, 2) ||
+      reserve(c->pp_hpdl, 2))
+    return 1;
+  if (!c->pp_masks_tried) {
+    c->pp_masks_tried = true;
+    if ((int)c->o(MCS_OPT_PIPE_SIDE_CUS) > 0 && (int)c->o(MCS_OPT_PIPE_SIDE_CUS) < c->n_cu) {
+      const int words = (c->n_cu + 31) / 32;
+      std::vector<uint32_t> m_side((size_t)words, 0u), m_main((size_t)words, 0u);
+      for (int i = 0; i < c->n_cu; ++i) (i < (int)c->o(MCS_OPT_PIPE_SIDE_CUS) ? m_side : m_main)[(size_t)(i >> 5)] |= 1u << (i & 31);
+      if (c->pp_s1m.create_cu_masked((uint32_t)words, m_main.data()) != hipSuccess ||
+          c->pp_s2m.create_cu_masked((uint32_t)words, m_side.data()) != hipSuccess) {
+        (void)hipGetLastError();
+        reset_all(c->pp_s1m, c->pp_s2m);
+      }
+    }
+  }
+  // the sliced form of the species' kernel (PLAIN, LOSSY, PLAIN_ETF, general); a wave exports at most its 64 lanes, once: room for the
+  // main and the late launch of one pcut
+  const K1Plan k1 = k1_plan(c, 0, true, false);
+  if (ensure_strag(c, 2 * (long long)c->n_cu * k1.per_cu * k1.threads)) return 1;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  int rc = pipelined_pcuts(c, k1, i_pcut_first, npc, cap_n, n_target, long_draws, long_imult_max, o);
+  // every exit of the loop, a failed one too: no stream may still write the population, the saved arrays or the tallies
+  for (hipStream_t st : {(hipStream_t)c->pp_s2, (hipStream_t)c->pp_s2m, (hipStream_t)c->pp_s1m, c->stream}) {
+    if (!st) continue;
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess && rc == 0) rc = fail(std::string("mcs_run_pcuts_pipelined: hipStreamSynchronize: ") + hipGetErrorString(e));
+  }
+  if (rc) c->n = 0;      // (the population is half-written: it is not run or split again before the next mcs_init_pop* / mcs_pop_upload)
+  c->n_run_last = -1; c->n_saved_last = 0;
+  c->kernel_last = k1.kernel;
+  return rc;
+}
+
 int mcs_new_pcut(mcs_ctx* c, int64_t i_mult, int64_t* n_new_out) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (i_mult < 1) return fail("mcs_new_pcut: i_mult < 1");
   if (c->n != c->n_run_last) return fail("mcs_new_pcut: no mcs_run_pcut since the population changed");
   const long long n_saved = c->n_saved_last;
@@ -1220,7 +1152,7 @@ int mcs_new_pcut(mcs_ctx* c, int64_t i_mult, int64_t* n_new_out) {
   // the split (src[] was computed behind the transport kernel) writes into the spare buffer, then the buffers
   // rotate; nothing is read back: the new size is known on the host
   if (reserve(c->spare, grow_cap(n_new))) return 1;
-  HIPCHK(mcs_launch_split(pop_view(c->sav), pop_view(c->spare), c->d_src, n_new, i_mult, c->stream));
+  HIPCHK(mcs_launch_split(pop_view(c->sav), pop_view(c->spare), c->scan.src, n_new, i_mult, c->stream));
   std::swap(c->cur, c->spare);
   c->n = n_new; c->n_run_last = -1;
   if (ensure_capacity(c, n_new)) return 1;
@@ -1228,31 +1160,26 @@ int mcs_new_pcut(mcs_ctx* c, int64_t i_mult, int64_t* n_new_out) {
   return 0;
 }
 
-int mcs_saved_export(mcs_ctx* c, int64_t cap, int64_t* dev_gidx, double* dev_f64, uint32_t* dev_meta) {
-  HIPCHK(hipSetDevice(c->device));
-  if (c->n != c->n_run_last) return fail("mcs_saved_export: no mcs_run_pcut since the population changed");
-  if (cap < c->n_saved_last) return fail("mcs_saved_export: cap < n_saved");
-  if (c->n_saved_last > 0 && (!dev_gidx || !dev_f64 || !dev_meta)) return fail("mcs_saved_export: null buffer");
-  HIPCHK(mcs_launch_saved_export(pop_view(c->sav), c->d_src, c->n_saved_last, cap, c->idx_first, c->idx_stride, c->idx_gidx,
+// mcs_saved_export, and mcs_saved_gidx (`state` false: the global indices alone)
+static int saved_export(mcs_ctx* c, const char* who, bool state, int64_t cap, int64_t* dev_gidx, double* dev_f64, uint32_t* dev_meta) {
+  MCS_ENTER_AS(c, who);
+  const std::string w = std::string(who) + ": ";
+  if (c->n != c->n_run_last) return fail(w + "no mcs_run_pcut since the population changed");
+  if (cap < c->n_saved_last) return fail(w + "cap < n_saved");
+  if (c->n_saved_last > 0 && (!dev_gidx || (state && (!dev_f64 || !dev_meta)))) return fail(w + "null buffer");
+  HIPCHK(mcs_launch_saved_export(pop_view(c->sav), c->scan.src, c->n_saved_last, cap, c->idx_first, c->idx_stride, c->idx_gidx,
                                  (long long*)dev_gidx, dev_f64, dev_meta, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));      // the caller's library (RCCL on another stream) may read the buffers now
   return 0;
 }
-
-int mcs_saved_gidx(mcs_ctx* c, int64_t cap, int64_t* dev_gidx) {
-  HIPCHK(hipSetDevice(c->device));
-  if (c->n != c->n_run_last) return fail("mcs_saved_gidx: no mcs_run_pcut since the population changed");
-  if (cap < c->n_saved_last) return fail("mcs_saved_gidx: cap < n_saved");
-  if (c->n_saved_last > 0 && !dev_gidx) return fail("mcs_saved_gidx: null buffer");
-  HIPCHK(mcs_launch_saved_export(pop_view(c->sav), c->d_src, c->n_saved_last, cap, c->idx_first, c->idx_stride, c->idx_gidx,
-                                 (long long*)dev_gidx, nullptr, nullptr, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+int mcs_saved_export(mcs_ctx* c, int64_t cap, int64_t* dev_gidx, double* dev_f64, uint32_t* dev_meta) {
+  return saved_export(c, "mcs_saved_export", true, cap, dev_gidx, dev_f64, dev_meta);
 }
+int mcs_saved_gidx(mcs_ctx* c, int64_t cap, int64_t* dev_gidx) { return saved_export(c, "mcs_saved_gidx", false, cap, dev_gidx, nullptr, nullptr); }
 
 int mcs_split_import(mcs_ctx* c, int64_t n_parents, int64_t cap, const double* dev_f64, const uint32_t* dev_meta, int64_t i_mult,
                      int64_t first, int64_t stride, int64_t n_local) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (i_mult < 1 || stride < 1 || first < 0 || n_local < 0 || n_parents < 0 || cap < n_parents)
     return fail("mcs_split_import: bad arguments");
   if (n_local > 0 && (first + (n_local - 1) * stride) / i_mult >= n_parents)
@@ -1275,15 +1202,11 @@ int mcs_run_pcut_host(mcs_ctx* c, int i_pcut, int64_t n_pts_use, int64_t i_prt_o
 }
 
 int mcs_read_tallies(mcs_ctx* c, double* host_f64, int64_t* host_i64) {
-  HIPCHK(hipSetDevice(c->device));
-  if (fold_replicas(c)) return 1;
-  if (host_f64) HIPCHK(hipMemcpyAsync(host_f64, c->d_T, (size_t)c->L.total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (host_i64) HIPCHK(hipMemcpyAsync(host_i64, c->d_I, (size_t)mcs_i64_total(&c->P) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  MCS_ENTER(c);
+  return mcs_read_tallies_part(c, 0, host_f64 ? c->L.total : 0, host_f64, host_i64);
 }
 int mcs_read_tallies_part(mcs_ctx* c, int64_t first, int64_t count, double* host_f64, int64_t* host_i64) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (first < 0 || count < 0 || first + count > c->L.total || (count > 0 && !host_f64)) return fail("mcs_read_tallies_part: range outside the tally buffer");
   if (fold_replicas(c)) return 1;
   if (count > 0) HIPCHK(hipMemcpyAsync(host_f64, c->d_T + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1292,7 +1215,7 @@ int mcs_read_tallies_part(mcs_ctx* c, int64_t first, int64_t count, double* host
   return 0;
 }
 int mcs_write_tallies_part(mcs_ctx* c, int64_t first, int64_t count, const double* host_f64) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (first < 0 || count < 0 || first + count > c->L.total || (count > 0 && !host_f64)) return fail("mcs_write_tallies_part: range outside the tally buffer");
   if (fold_replicas(c)) return 1;
   if (count > 0) HIPCHK(hipMemcpyAsync(c->d_T + first, host_f64, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1300,7 +1223,7 @@ int mcs_write_tallies_part(mcs_ctx* c, int64_t first, int64_t count, const doubl
   return 0;
 }
 int mcs_write_tallies(mcs_ctx* c, const double* host_f64, const int64_t* host_i64) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
   if (host_f64) HIPCHK(hipMemcpyAsync(c->d_T, host_f64, (size_t)c->L.total * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (host_i64) HIPCHK(hipMemcpyAsync(c->d_I, host_i64, (size_t)mcs_i64_total(&c->P) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
@@ -1317,7 +1240,7 @@ int mcs_accumulate_tallies(mcs_ctx* dst, mcs_ctx* src) {
   if (dst->device != src->device) return fail("mcs_accumulate_tallies: the contexts are on different devices");
   if (dst->L.total != src->L.total || dst->P.n_grid != src->P.n_grid || dst->P.n_ions != src->P.n_ions || dst->P.n_itrs != src->P.n_itrs)
     return fail("mcs_accumulate_tallies: the contexts' tally layouts differ (total, n_grid, n_ions or n_itrs)");
-  HIPCHK(hipSetDevice(dst->device));
+  MCS_ENTER(dst);
   if (fold_replicas(src) || fold_replicas(dst)) return 1;
   const mcs_layout& L = dst->L;
   HIPCHK(hipEventRecord(src->acc_ev, src->stream));
@@ -1332,10 +1255,10 @@ int mcs_accumulate_tallies(mcs_ctx* dst, mcs_ctx* src) {
 // fn < MCS_FN_SQRT_FAST: mcs_k_eval_fn in mcs_population.hip (the build of K3); from there on: mcs_k_eval_hot in mcs_transport.hip,
 // the transport kernel's own forms in its own translation unit
 int mcs_eval_fn(mcs_ctx* c, int fn, int64_t n, const double* a, const double* b, double* out) {
-  if (!c || n < 0 || (n > 0 && (!a || !out))) return fail("mcs_eval_fn: null argument or negative n");
+  MCS_ENTER(c);
+  if (n < 0 || (n > 0 && (!a || !out))) return fail("mcs_eval_fn: null argument or negative n");
   if (fn < 0 || fn >= MCS_FN_COUNT) return fail("mcs_eval_fn: unknown fn " + std::to_string(fn) + " (enum mcs_fn, include/mcs.h)");
-  HIPCHK(hipSetDevice(c->device));
-  if (ensure_stage(c, 3 * n + 3)) return 1;
+  if (reserve(c->d_stage, 3 * n + 3)) return 1;
   double *da = c->d_stage, *db = c->d_stage + n, *dout = c->d_stage + 2 * n;
   HIPCHK(hipMemcpyAsync(da, a, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(db, b ? b : a, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1348,10 +1271,10 @@ int mcs_eval_fn(mcs_ctx* c, int fn, int64_t n, const double* a, const double* b,
 // One scatter per state in the transport kernel's three spellings (include/mcs.h).  The kernel reads pe_crit, game_crit and eta_mfp
 // where K1 reads them: from a KArgs in the constant address space -- the context's own, with nothing but the parameters filled in.
 int mcs_eval_scatter(mcs_ctx* c, int form, int64_t n, const double* in, double* out) {
-  if (!c || n < 0 || (n > 0 && (!in || !out))) return fail("mcs_eval_scatter: null argument or negative n");
+  MCS_ENTER(c);
+  if (n < 0 || (n > 0 && (!in || !out))) return fail("mcs_eval_scatter: null argument or negative n");
   if (form < 0 || form > 2) return fail("mcs_eval_scatter: unknown form " + std::to_string(form) + " (0, 1 or 2: include/mcs.h)");
-  HIPCHK(hipSetDevice(c->device));
-  if (ensure_stage(c, 15 * n + 2) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1)) return 1;
+  if (reserve(c->d_stage, 15 * n + 2) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1)) return 1;
   HIPCHK(hipStreamSynchronize(c->stream));         // (nothing queued may still read the launch constants)
   KArgs& a = *c->h_args_pin;
   a = KArgs{};
@@ -1367,14 +1290,14 @@ int mcs_eval_scatter(mcs_ctx* c, int form, int64_t n, const double* in, double* 
 
 int mcs_final_download(mcs_ctx* c, int64_t n, int32_t* reason, int32_t* helix_count, int32_t* retro_count, double* ptot_pf,
                        double* x_PT_cm) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (!c->debug_finals) return fail("mcs_final_download: end states are recorded only after mcs_set_debug_finals(ctx, 1)");
-  if (n > c->f_cap) return fail("mcs_final_download: n too large");
-  if (reason) HIPCHK(hipMemcpyAsync(reason, c->f_reason, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (helix_count) HIPCHK(hipMemcpyAsync(helix_count, c->f_helix, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (retro_count) HIPCHK(hipMemcpyAsync(retro_count, c->f_retro, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (ptot_pf) HIPCHK(hipMemcpyAsync(ptot_pf, c->f_ptot, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (x_PT_cm) HIPCHK(hipMemcpyAsync(x_PT_cm, c->f_x, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (n > c->fin.cap()) return fail("mcs_final_download: n too large");
+  if (reason) HIPCHK(hipMemcpyAsync(reason, c->fin.reason, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (helix_count) HIPCHK(hipMemcpyAsync(helix_count, c->fin.helix, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (retro_count) HIPCHK(hipMemcpyAsync(retro_count, c->fin.retro, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (ptot_pf) HIPCHK(hipMemcpyAsync(ptot_pf, c->fin.ptot, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (x_PT_cm) HIPCHK(hipMemcpyAsync(x_PT_cm, c->fin.x, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1383,7 +1306,7 @@ double mcs_last_kernel_ms(mcs_ctx* c) { return c->last_ms; }
 
 // ---- consumers of the tallies (K4) ------------------------------------------------------
 static int consumers_ready(mcs_ctx* c, const mcs_consumer_in* in, const char* who) {
-  if (!c || !in) return fail(std::string(who) + ": null argument");
+  if (!in) return fail(std::string(who) + ": null argument");
   if (!c->have_grid) return fail(std::string(who) + ": grid not set");
   if (c->P.num_psd_mom_bins + 2 > 208 || c->P.num_psd_tht_bins + 2 > 208) return fail(std::string(who) + ": too many PSD bins");
   const int NM = c->P.num_psd_mom_bins + 2, NT = c->P.num_psd_tht_bins + 2, ng = c->P.n_grid;
@@ -1391,7 +1314,7 @@ static int consumers_ready(mcs_ctx* c, const mcs_consumer_in* in, const char* wh
 }
 
 int mcs_dndp_cr(mcs_ctx* c, const mcs_consumer_in* in, double* dNdp, int64_t* diag) {
-  HIPCHK(hipSetDevice(c ? c->device : 0));
+  MCS_ENTER(c);
   if (consumers_ready(c, in, "mcs_dndp_cr")) return 1;
   if (fold_replicas(c)) return 1;
   if (!in->mom_log_cgs || !in->mom_edge_cgs || !in->cos_edge || !in->zone_pop || !dNdp) return fail("mcs_dndp_cr: null table");
@@ -1414,7 +1337,7 @@ int mcs_dndp_cr(mcs_ctx* c, const mcs_consumer_in* in, double* dNdp, int64_t* di
 }
 
 int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, double* P_perp, double* energy_density) {
-  HIPCHK(hipSetDevice(c ? c->device : 0));
+  MCS_ENTER(c);
   if (consumers_ready(c, in, "mcs_thermo_calcs")) return 1;
   if (fold_replicas(c)) return 1;
   if (!in->cos_center || !in->pt_center || !in->zone_pop || !in->density_loc || !in->cold_pressure || !P_par || !P_perp || !energy_density)
@@ -1442,14 +1365,14 @@ int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, doubl
 
 int mcs_photon_synch(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_cgs, double mc, int n_photon, double emin_mev,
                      double bins_per_dec, double* energy_erg, double* emis) {
-  HIPCHK(hipSetDevice(c ? c->device : 0));
-  if (!c || !dNdp_pf || !mom_edge_cgs || !emis) return fail("mcs_photon_synch: null argument");
+  MCS_ENTER(c);
+  if (!dNdp_pf || !mom_edge_cgs || !emis) return fail("mcs_photon_synch: null argument");
   if (!c->have_grid) return fail("mcs_photon_synch: grid not set");
   if (n_photon < 1 || n_photon > 4096 || !(emin_mev > 0) || !(bins_per_dec > 0) || !(mc > 0)) return fail("mcs_photon_synch: bad arguments");
   const int NM = c->P.num_psd_mom_bins + 2, ng = c->P.n_grid;
   if (NM > 208) return fail("mcs_photon_synch: too many momentum bins");
   const size_t n_in = (size_t)ng * NM + NM, n_out = (size_t)ng * n_photon;
-  if (ensure_stage(c, (long long)(n_in + n_out) + 4)) return 1;
+  if (reserve(c->d_stage, (long long)(n_in + n_out) + 4)) return 1;
   double* d_in = c->d_stage; double* d_out = c->d_stage + n_in;
   HIPCHK(hipMemcpyAsync(d_in, dNdp_pf, sizeof(double) * (size_t)ng * NM, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_in + (size_t)ng * NM, mom_edge_cgs, sizeof(double) * NM, hipMemcpyHostToDevice, c->stream));
@@ -1464,8 +1387,8 @@ int mcs_photon_synch(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_c
 // The pion-decay fold (include/mcs_pion.h) over the plasma-frame dN/dp of a nucleus species.
 int mcs_photon_pion(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_cgs, double mc, double aa, const double* target_density, double scaling,
                     int i_data, int n_photon, double emin_mev, double bins_per_dec, double* energy_erg, double* emis) {
-  HIPCHK(hipSetDevice(c ? c->device : 0));
-  if (!c || !dNdp_pf || !mom_edge_cgs || !target_density || !emis) return fail("mcs_photon_pion: null argument");
+  MCS_ENTER(c);
+  if (!dNdp_pf || !mom_edge_cgs || !target_density || !emis) return fail("mcs_photon_pion: null argument");
   if (!c->have_grid) return fail("mcs_photon_pion: grid not set");
   if (n_photon < 1 || n_photon > 4096 || !(emin_mev > 0) || !(bins_per_dec > 0) || !(mc > 0) || !(aa >= 1) || !(scaling >= 0))
     return fail("mcs_photon_pion: bad arguments");
@@ -1473,7 +1396,7 @@ int mcs_photon_pion(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_cg
   const int NM = c->P.num_psd_mom_bins + 2, ng = c->P.n_grid;
   if (NM > 208) return fail("mcs_photon_pion: too many momentum bins");
   const size_t n_in = (size_t)ng * NM + NM + ng, n_out = (size_t)ng * n_photon;
-  if (ensure_stage(c, (long long)(n_in + n_out) + 4)) return 1;
+  if (reserve(c->d_stage, (long long)(n_in + n_out) + 4)) return 1;
   double* d_in = c->d_stage; double* d_out = c->d_stage + n_in;
   HIPCHK(hipMemcpyAsync(d_in, dNdp_pf, sizeof(double) * (size_t)ng * NM, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_in + (size_t)ng * NM, mom_edge_cgs, sizeof(double) * NM, hipMemcpyHostToDevice, c->stream));
@@ -1491,7 +1414,7 @@ int mcs_photon_pion(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_cg
 // the frame that moves with (gam_x, beta_x) against the shock frame (the ISM frame: gam0, beta0).  The result stays on the device
 // for mcs_photon_ic; d2N (host, [n_grid][ntht+2][nmom+2], momentum fastest) may be null.
 int mcs_dndp_2d(mcs_ctx* c, const mcs_consumer_in* in, double gam_x, double beta_x, double* d2N) {
-  HIPCHK(hipSetDevice(c ? c->device : 0));
+  MCS_ENTER(c);
   if (consumers_ready(c, in, "mcs_dndp_2d")) return 1;
   if (fold_replicas(c)) return 1;
   if (!in->mom_edge_cgs || !in->cos_center || !in->pt_center || !in->zone_pop) return fail("mcs_dndp_2d: null table");
@@ -1516,8 +1439,8 @@ int mcs_dndp_2d(mcs_ctx* c, const mcs_consumer_in* in, double gam_x, double beta
 // The inverse-Compton fold (include/mcs_ic.h) over the d2N/dp dcos the last mcs_dndp_2d left on the device.
 int mcs_photon_ic(mcs_ctx* c, const double* mom_edge_cgs, double mc_e, int j_max, int n_nu, const double* alpha_in, const double* n_in, int n_photon,
                   double emin_mev, double bins_per_dec, double beam_area, double* energy_erg, double* emis) {
-  HIPCHK(hipSetDevice(c ? c->device : 0));
-  if (!c || !mom_edge_cgs || !alpha_in || !n_in || !emis) return fail("mcs_photon_ic: null argument");
+  MCS_ENTER(c);
+  if (!mom_edge_cgs || !alpha_in || !n_in || !emis) return fail("mcs_photon_ic: null argument");
   if (!c->have_c2d) return fail("mcs_photon_ic: no mcs_dndp_2d result on the device");
   const int NM = c->P.num_psd_mom_bins + 2, NT = c->P.num_psd_tht_bins + 2, ng = c->P.n_grid;
   if (NM > 208) return fail("mcs_photon_ic: too many momentum bins");
@@ -1525,7 +1448,7 @@ int mcs_photon_ic(mcs_ctx* c, const double* mom_edge_cgs, double mc_e, int j_max
       !(mc_e > 0) || !(beam_area > 0))
     return fail("mcs_photon_ic: bad arguments");
   const size_t n_in_w = (size_t)NM + 2 * (size_t)n_nu, n_out = (size_t)ng * n_photon;
-  if (ensure_stage(c, (long long)(n_in_w + n_out) + 4)) return 1;
+  if (reserve(c->d_stage, (long long)(n_in_w + n_out) + 4)) return 1;
   double* d_in = c->d_stage; double* d_out = c->d_stage + n_in_w;
   HIPCHK(hipMemcpyAsync(d_in, mom_edge_cgs, sizeof(double) * NM, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_in + NM, alpha_in, sizeof(double) * n_nu, hipMemcpyHostToDevice, c->stream));
@@ -1540,7 +1463,7 @@ int mcs_photon_ic(mcs_ctx* c, const double* mom_edge_cgs, double mc_e, int j_max
 
 // ---- the view of a context that mcs_ensemble.hip (K8) works through (mcs_ctx_view.h) ----
 int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
-  HIPCHK(hipSetDevice(c->device));
+  MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
   *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L};
   return 0;

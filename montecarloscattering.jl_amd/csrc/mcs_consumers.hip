@@ -13,6 +13,7 @@
 // written once.  HBM-bound: 8 B per PSD cell per kernel (+ 16 B per cell for the thermo scratch).
 // The reference's consumer quirks C1-C6 are handled as DESIGN.md section 3b says.
 #include "mcs_device.h"
+#include "mcs_launch.h"
 #include "../../include/mcs_math.h"
 #include "../../include/mcs_synch.h"
 #include "../../include/mcs_ic.h"

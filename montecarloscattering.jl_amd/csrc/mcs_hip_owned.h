@@ -48,22 +48,42 @@ template <class T> using PinnedBuf = HipBuf<T, true>;
 
 template <class... B> void reset_all(B&... b) { (b.reset(), ...); }
 
+// SEVERAL buffers that exist together or not at all.  A group derives from BufGroup, names its members, reads cap() from one of them
+// and says in grow(n) what each holds for n entries (a failed grow leaves every member empty); reserve(n) is a no-op while n fit.
+template <class G> struct BufGroup {
+  static const char* alloc_name() { return "hipMalloc"; }
+  hipError_t reserve(long long n) { G& g = static_cast<G&>(*this); return n <= g.cap() ? hipSuccess : g.grow(n); }
+};
+// what grow() is made of: b[i] gets n[i] elements.  The blocks they hold are freed first: old and new never lie side by side.
+template <class... B> hipError_t reserve_all(const long long (&n)[sizeof...(B)], B&... b) {
+  reset_all(b...);
+  hipError_t e = hipSuccess;
+  int i = 0;
+  ((e = e == hipSuccess ? b.reserve(n[i++]) : e), ...);
+  if (e != hipSuccess) reset_all(b...);
+  return e;
+}
+
 // The resident population's arrays: the eight fp64 fields in the order of DevPop / mcs_soa, and the packed meta word.
-// All nine hold cap() entries, or none exists.
-struct PopBuf {
+struct PopBuf : BufGroup<PopBuf> {
   DevBuf<double> f[8];
   DevBuf<uint32_t> meta;
-  static const char* alloc_name() { return "hipMalloc"; }
   long long cap() const { return meta.cap(); }      // (meta is allocated last)
-  void reset() { for (auto& b : f) b.reset(); meta.reset(); }
-  hipError_t reserve(long long n) {
-    if (n <= cap()) return hipSuccess;
-    hipError_t e = hipSuccess;
-    for (auto& b : f) if (e == hipSuccess) e = b.reserve(n);
-    if (e == hipSuccess) e = meta.reserve(n);
-    if (e != hipSuccess) reset();
-    return e;
-  }
+  hipError_t grow(long long n) { return reserve_all({n, n, n, n, n, n, n, n, n}, f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], meta); }
+};
+// The per-particle end states a debug run records (mcs_set_debug_finals).
+struct FinalsBuf : BufGroup<FinalsBuf> {
+  DevBuf<int32_t> reason, helix, retro; DevBuf<double> ptot, x;
+  long long cap() const { return x.cap(); }
+  hipError_t grow(long long n) { return reserve_all({n, n, n, n, n}, reason, helix, retro, ptot, x); }
+};
+// The compaction's scratch for cap() status bytes: the count and the offset of every block of them, the index list src[].
+struct ScanScratch : BufGroup<ScanScratch> {
+  static constexpr long long kBlock = 1024;      // entries per block of the compaction kernels (mcs_k_count_saved & co., mcs_population.hip)
+  static long long blocks(long long n) { return (n + kBlock - 1) / kBlock; }
+  DevBuf<unsigned int> bcounts; DevBuf<unsigned long long> boffs; DevBuf<long long> src;
+  long long cap() const { return src.cap(); }
+  hipError_t grow(long long n) { return reserve_all({blocks(n), blocks(n), n}, bcounts, boffs, src); }
 };
 
 // A stream or an event the context created (null: none).

@@ -9,6 +9,7 @@
 // K3 replaces the fast-push branch of init_pop (src/initializers.jl:1078-1131) and
 // assign_particle_properties_to_population! (src/ion_init.jl:29-53).
 #include "mcs_device.h"
+#include "mcs_launch.h"
 #include "../../include/mcs_math.h"
 
 #pragma clang fp contract(off)

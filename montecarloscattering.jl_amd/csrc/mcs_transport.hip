@@ -37,6 +37,7 @@
 // Values that are pure functions of unchanged inputs (per-zone sin/cos/1/(qB),
 // cos_max of the scattering cone) are cached, which does not change a bit.
 #include "mcs_device.h"
+#include "mcs_launch.h"
 #define MCS_DEVICE_FAST_SQRT 1
 #include "../../include/mcs_math.h"
 #include "../../include/mcs_math_f32.h"

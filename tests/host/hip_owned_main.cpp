@@ -129,7 +129,7 @@ static void test_popbuf() {
         CHECK(e1 == hipSuccess && pop_holds(b, 100) && g_live == 9);
         Calls c0 = calls();
         CHECK(b.reserve(100) == hipSuccess && b.reserve(7) == hipSuccess && no_calls_since(c0) && pop_holds(b, 100));
-        // the grow fails at field k - 9: the fields before it hold 300 entries by then, those after it still 100
+        // the grow fails at field k - 9: the fields before it hold 300 entries by then, those after it nothing (a group frees first)
         CHECK(b.reserve(300) == hipErrorOutOfMemory && pop_empty(b) && g_live == 0);
       }
       fail_allocation(-1);
@@ -150,6 +150,77 @@ static void test_popbuf() {
     CHECK(n.reserve(20) == hipSuccess);
     a = std::move(n);                    // the preserving grow: the old nine blocks are freed, the new ones move in
     CHECK(g_frees == c0.frees + 9 && pop_holds(a, 20) && pop_empty(n));
+  }
+  CHECK(g_live == 0);
+}
+
+// Groups of buffers (BufGroup + reserve_all): state(g, n) says that every member of g holds what n entries take -- n == 0: nothing,
+// and no block -- and that the capacity read from the members is n.
+static bool fin_state(const FinalsBuf& b, long long n) {
+  const long long caps[5] = {b.reason.cap(), b.helix.cap(), b.retro.cap(), b.ptot.cap(), b.x.cap()};
+  const void* const ps[5] = {b.reason.get(), b.helix.get(), b.retro.get(), b.ptot.get(), b.x.get()};
+  for (int i = 0; i < 5; ++i) if (caps[i] != n || (ps[i] != nullptr) != (n > 0)) return false;
+  return b.cap() == n;
+}
+static bool scan_state(const ScanScratch& b, long long n) {
+  const long long nb = ScanScratch::blocks(n);
+  if (b.bcounts.cap() != nb || b.boffs.cap() != nb || b.src.cap() != n || b.cap() != n) return false;
+  return (b.bcounts.get() != nullptr) == (n > 0) && (b.boffs.get() != nullptr) == (n > 0) && (b.src.get() != nullptr) == (n > 0);
+}
+template <class G, class State> static void test_group(long members, State state) {
+  {
+    G g;
+    CHECK(state(g, 0));
+    Calls c0 = calls();
+    CHECK(g.reserve(0) == hipSuccess && no_calls_since(c0) && state(g, 0));
+    // a first reserve: one allocation per member
+    CHECK(g.reserve(100) == hipSuccess && state(g, 100) && g_allocs == c0.allocs + members && g_frees == c0.frees && g_live == members);
+    // no-op reserve
+    Calls c1 = calls();
+    CHECK(g.reserve(100) == hipSuccess && g.reserve(7) == hipSuccess && g.reserve(0) == hipSuccess && no_calls_since(c1) && state(g, 100));
+    // a grow: every member is freed and allocated again, with its own exact size
+    CHECK(g.reserve(2000) == hipSuccess && state(g, 2000) && g_allocs == c1.allocs + members && g_frees == c1.frees + members && g_live == members);
+  }
+  CHECK(g_live == 0);
+  // reserve(100), reserve(2000) makes 2 * members allocations: whichever fails, every member is empty afterwards, the capacity is 0 and
+  // nothing of the group is left allocated; a later reserve succeeds
+  for (long k = 0; k < 2 * members; ++k) {
+    {
+      PopBuf other;                      // (somebody else's blocks stay)
+      CHECK(other.reserve(3) == hipSuccess);
+      const long live0 = g_live;
+      G g;
+      fail_allocation(k);
+      const hipError_t e1 = g.reserve(100);
+      if (k < members) {
+        CHECK(e1 == hipErrorOutOfMemory && state(g, 0) && g.cap() == 0 && g_live == live0);
+      } else {
+        CHECK(e1 == hipSuccess && state(g, 100) && g_live == live0 + members);
+        CHECK(g.reserve(2000) == hipErrorOutOfMemory && state(g, 0) && g.cap() == 0 && g_live == live0);
+      }
+      fail_allocation(-1);
+      CHECK(g.reserve(2000) == hipSuccess && state(g, 2000) && g_live == live0 + members);
+    }
+    CHECK(g_live == 0);
+  }
+}
+static void test_groups() {
+  test_group<FinalsBuf>(5, fin_state);
+  test_group<ScanScratch>(3, scan_state);
+  // the scan scratch has one count and one offset per 1024 status bytes, the block of the compaction kernels
+  CHECK(ScanScratch::blocks(0) == 0 && ScanScratch::blocks(1) == 1 && ScanScratch::blocks(1024) == 1 && ScanScratch::blocks(1025) == 2);
+  for (long long n : {1LL, 1024LL, 1025LL}) {
+    ScanScratch s;
+    CHECK(s.reserve(n) == hipSuccess && scan_state(s, n) && s.bcounts.cap() == (n + 1023) / 1024);
+    s.src.get()[n - 1] = 0; s.bcounts.get()[s.bcounts.cap() - 1] = 0u; s.boffs.get()[s.boffs.cap() - 1] = 0ull;      // (ASan: there is room)
+  }
+  {
+    FinalsBuf a, b;
+    CHECK(a.reserve(5) == hipSuccess && b.reserve(9) == hipSuccess);
+    a.x.get()[4] = 1.0; a.reason.get()[4] = 1;
+    Calls c0 = calls();
+    a = std::move(b);                    // (a's five blocks are freed, b's move in)
+    CHECK(g_frees == c0.frees + 5 && g_allocs == c0.allocs && fin_state(a, 9) && fin_state(b, 0));
   }
   CHECK(g_live == 0);
 }
@@ -217,6 +288,7 @@ int main() {
   test_buffer<DevBuf<double>, double>();
   test_buffer<PinnedBuf<uint32_t>, uint32_t>();
   test_popbuf();
+  test_groups();
   test_handles();
   test_env();
   CHECK(g_live == 0 && g_handles == 0 && g_allocs == g_frees);

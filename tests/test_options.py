@@ -141,6 +141,38 @@ def test_null_arguments():
     assert lib.mcs_set_tail_slicing(None, 1) != 0 and "null" in _err(lib)
 
 
+def _status_entry_points_taking_a_context():
+    """The entry points of capi.py's signature table that return a status and take the context first.  Not among them: the getters,
+    whose int is a value; mcs_destroy, for which no context is nothing to destroy (0, like free(NULL)); the mcs_ens_* calls other
+    than mcs_ens_create, whose first argument is the ensemble."""
+    lib = mcs.capi.load_library()
+    values = {"mcs_num_cus", "mcs_last_launches", "mcs_last_kernel", "mcs_k1_blocks_per_cu"}
+    names = []
+    for name in mcs.capi.EXPORTED_SYMBOLS:
+        fn = getattr(lib, name)
+        if fn.restype is not ct.c_int or not fn.argtypes or fn.argtypes[0] is not ct.c_void_p:
+            continue
+        if name in values or name == "mcs_destroy" or (name.startswith("mcs_ens_") and name != "mcs_ens_create"):
+            continue
+        names.append(name)
+    return names
+
+
+@pytest.mark.parametrize("name", _status_entry_points_taking_a_context())
+def test_null_context_is_an_error_not_a_crash(name):
+    lib = mcs.capi.load_library()
+    fn = getattr(lib, name)
+    assert lib.mcs_option_describe(-1, ct.byref(mcs.capi.McsOptionDesc())) != 0 and "null" not in _err(lib)      # (a stale message)
+    assert fn(None, *[t() for t in fn.argtypes[1:]]) != 0, name
+    assert "null" in _err(lib), (name, _err(lib))
+
+
+def test_every_status_entry_point_is_covered():
+    names = _status_entry_points_taking_a_context()
+    assert len(names) >= 40 and {"mcs_sync", "mcs_run_pcut", "mcs_run_pcuts_fused", "mcs_run_pcuts_pipelined", "mcs_photon_ic",
+                                 "mcs_set_launch", "mcs_accumulate_tallies"} <= set(names)
+
+
 def test_hip_backend_refuses_unknown_option_names():
     from mcs_amd import hip_backend as hb
     with pytest.raises(KeyError, match="no_such_option"):
