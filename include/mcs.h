@@ -531,6 +531,32 @@ int mcs_ens_read(mcs_ens* ens, int slot, int what, int64_t first, int64_t count,
  * nearest, into num_crossings.  The consumers above then run unchanged on the ensemble-mean histograms (what a two-dimensional
  * consumer call left on the device is dropped). */
 int mcs_ens_load_mean(mcs_ens* ens, int slot, mcs_ctx* dst);
+/* A summary of word ranges of a slot, reduced on the device: what a stop rule ("tally trigger") needs of the error bars without
+ * reading the vectors.  For one range [first, first + count) of a slot with n >= 2 samples, every operation a separate rounding:
+ *   finite word    mean[w] and M2[w] are both finite; n_nonfinite counts the others, which take part in nothing else
+ *   amax           the maximum of |mean[w]| over the finite words; 0 for an empty range
+ *   selected word  a finite word with |mean[w]| > 0 and |mean[w]| >= floor_frac * amax; n_selected counts them
+ *   per selected word   se = sqrt(M2[w] / (n (n - 1))), the denominator (double)n * (double)(n - 1) as in the read call;
+ *                       rel = se / |mean[w]|         (sqrt and / correctly rounded)
+ *   max_rel        the maximum of rel (0 when nothing is selected); argmax: the lowest w - first that attains it, -1 when
+ *                  nothing is selected
+ *   n_over         the selected words with rel > tol
+ *   sum_se, sum_abs_mean, sum_rel2   the sums over the selected words of se, |mean| and rel * rel
+ * One call serves all its ranges (at most 256; they may overlap and start at any word) and waits for the device once; it is
+ * ordered like the read call: on the home context's stream, after what the accumulator queued last.  Two sweeps over a range --
+ * the means for amax, then means and M2 -- each thread over its words in ascending order, the threads of a block joined by
+ * shuffles and LDS, one partial per block in a scratch buffer of the accumulator (allocated at the first call, sized by the
+ * largest), the partials of a range joined in index order: no atomics, and the same state gives the same bits in every field.
+ * The three sums are sums of non-negative terms in an order the call fixes: within n_selected * 2^-53 relative of the exact sum.
+ * (A word with a finite mean and a non-finite M2 that carries a range's largest |mean| is seen only by the second sweep; the
+ * call then repeats that sweep with the amax of the finite words and waits a second time.)
+ * n_ranges = 0 does nothing and returns 0.  Refused, with a message, nothing changed and nothing queued: a null argument, a slot
+ * out of range, a slot with n < 2, n_ranges outside 0..256, a range outside the slot's vector or with a negative count,
+ * floor_frac not in [0, 1] (NaN included), tol negative or NaN. */
+typedef struct mcs_ens_range   { int64_t first, count; double floor_frac, tol; } mcs_ens_range;
+typedef struct mcs_ens_summary { double amax, max_rel, sum_se, sum_abs_mean, sum_rel2;
+                                 int64_t n_selected, n_over, n_nonfinite, argmax; } mcs_ens_summary;
+int mcs_ens_summarize(mcs_ens* ens, int slot, int n_ranges, const mcs_ens_range* ranges, mcs_ens_summary* out);
 
 /* ---- test / measurement hooks ------------------------------------------- */
 /* evaluate device math/RNG primitives (bit-parity tests): fn ids in mcs_fn */

@@ -88,6 +88,17 @@ class McsEnsLayout(ct.Structure):
         "tally_sp_first", "tally_it_first", "tally_recv_pool", "tally_scalars")]
 
 
+class McsEnsRange(ct.Structure):
+    """`mcs_ens_range`: a word range of a slot's sample vector, with the floor and the tolerance of its summary (include/mcs.h)."""
+    _fields_ = [("first", ct.c_int64), ("count", ct.c_int64), ("floor_frac", ct.c_double), ("tol", ct.c_double)]
+
+
+class McsEnsSummary(ct.Structure):
+    """`mcs_ens_summary`: what `mcs_ens_summarize` says about one range (include/mcs.h)."""
+    _fields_ = [(name, ct.c_double) for name in ("amax", "max_rel", "sum_se", "sum_abs_mean", "sum_rel2")] + \
+               [(name, ct.c_int64) for name in ("n_selected", "n_over", "n_nonfinite", "argmax")]
+
+
 # enum mcs_option_when / mcs_option_applies
 OPTION_WHEN = ("between launches", "before the first pipelined run", "creation only")
 OPTION_APPLIES = ("any", "fp64 state when > 0", "fp32 state")
@@ -310,6 +321,7 @@ def load_library() -> ct.CDLL:
         "mcs_ens_count": (i32, [vp, i32, c_int64_p]),
         "mcs_ens_read": (i32, [vp, i32, i32, i64, i64, c_double_p]),
         "mcs_ens_load_mean": (i32, [vp, i32, vp]),
+        "mcs_ens_summarize": (i32, [vp, i32, i32, ct.POINTER(McsEnsRange), ct.POINTER(McsEnsSummary)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -359,5 +371,5 @@ EXPORTED_SYMBOLS = [
 # the ensemble statistics (K8)
 EXPORTED_SYMBOLS += [
     "mcs_ens_get_layout", "mcs_ens_create", "mcs_ens_destroy", "mcs_ens_begin_iteration", "mcs_ens_add_species",
-    "mcs_ens_add_iteration", "mcs_ens_merge", "mcs_ens_count", "mcs_ens_read", "mcs_ens_load_mean",
+    "mcs_ens_add_iteration", "mcs_ens_merge", "mcs_ens_count", "mcs_ens_read", "mcs_ens_load_mean", "mcs_ens_summarize",
 ]

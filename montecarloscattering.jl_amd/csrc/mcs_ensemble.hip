@@ -7,13 +7,19 @@
 //   momentum marginal  thread (z, i) walks the angle index; neighbouring threads read neighbouring words of every row
 //   angle marginal     one block per (histogram, zone): tiles of MARG_COLS momentum columns of all rows go through LDS (read along
 //                      the momentum index), thread j then adds its row's columns of the tile in ascending order
+// The summary of word ranges (mcs_ens_summarize) is the one reduction to a handful of numbers: two sweeps over every range -- the
+// largest |mean|, then the relative errors of the words that pass the floor it sets -- each thread over its words in ascending
+// order, then per wave by shuffles, per block through LDS, one partial per block into a scratch buffer of the accumulator, and a
+// last kernel that folds a range's partials in index order.  No atomics: the same state gives the same bits.
 // A context is seen through mcs_ctx_view.h; its stream carries the work, an event of the accumulator orders successive operations
 // that were queued on different streams.
 #include <hip/hip_runtime.h>
 
 #include "mcs_ctx_view.h"
 #include "mcs_hip_owned.h"
+#include "../../include/mcs_math.h"
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <memory>
@@ -132,6 +138,184 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_load_mean(const double*
   }
 }
 
+// ---- the summary of word ranges --------------------------------------------------------------------------------------------
+constexpr int SUM_MAX_RANGES = 256;
+constexpr int SUM_CHUNK = 4096;            // words of a range per block (16 per thread) before a range gets ...
+constexpr int SUM_MAX_BLOCKS = 2048;       // ... this many blocks, which then stride on: 8 per CU
+constexpr int SUM_WAVES = ENS_THREADS / 64;
+
+struct SumRange { long long first, count; double floor_frac, tol; };
+// block b of the launch works on range r, off[r] <= b < off[r + 1], as its block b - off[r] (a range of no words has no block)
+struct SumParams { SumRange r[SUM_MAX_RANGES]; int off[SUM_MAX_RANGES + 1]; int n_ranges; };
+// What a thread, a wave, a block, a range has seen.  amax: over the finite words; amax_used: the one the selection was made with;
+// arg: LLONG_MAX while nothing is selected (max_rel is then -1: every relative error beats it).
+struct SumRec { double amax, amax_used, max_rel, sum_se, sum_abs, sum_rel2; long long n_sel, n_over, n_nonf, arg; };
+
+__device__ inline SumRec rec_empty(double amax_used) { return SumRec{0.0, amax_used, -1.0, 0.0, 0.0, 0.0, 0, 0, 0, LLONG_MAX}; }
+
+__device__ inline bool finite_(double x) {
+  return (__double_as_longlong(x) & 0x7ff0000000000000LL) != 0x7ff0000000000000LL;
+}
+
+// b joins a; a holds the words (or partials) before b's: the sums add in that order, equal relative errors keep the lower word
+__device__ inline void rec_join(SumRec& a, const SumRec& b) {
+  a.amax = b.amax > a.amax ? b.amax : a.amax;
+  if (b.max_rel > a.max_rel || (b.max_rel == a.max_rel && b.arg < a.arg)) { a.max_rel = b.max_rel; a.arg = b.arg; }
+  a.sum_se = a.sum_se + b.sum_se;
+  a.sum_abs = a.sum_abs + b.sum_abs;
+  a.sum_rel2 = a.sum_rel2 + b.sum_rel2;
+  a.n_sel += b.n_sel; a.n_over += b.n_over; a.n_nonf += b.n_nonf;
+}
+
+__device__ inline SumRec rec_shfl_down(const SumRec& v, int d) {
+  SumRec o;
+  o.amax = __shfl_down(v.amax, d, 64); o.amax_used = v.amax_used; o.max_rel = __shfl_down(v.max_rel, d, 64);
+  o.sum_se = __shfl_down(v.sum_se, d, 64); o.sum_abs = __shfl_down(v.sum_abs, d, 64); o.sum_rel2 = __shfl_down(v.sum_rel2, d, 64);
+  o.n_sel = __shfl_down(v.n_sel, d, 64); o.n_over = __shfl_down(v.n_over, d, 64); o.n_nonf = __shfl_down(v.n_nonf, d, 64);
+  o.arg = __shfl_down(v.arg, d, 64);
+  return o;
+}
+
+// the block's threads' records joined in a fixed order -> thread 0's v (a binary tree over the lanes of a wave, then the waves
+// in order); tmp: SUM_WAVES records of LDS
+__device__ inline void rec_block_join(SumRec& v, SumRec* tmp) {
+  const int lane = threadIdx.x & 63;
+  for (int d = 1; d < 64; d <<= 1) {
+    const SumRec o = rec_shfl_down(v, d);
+    if ((lane & (2 * d - 1)) == 0) rec_join(v, o);      // (lane + d holds the lanes lane + d .. lane + 2 d - 1)
+  }
+  if (lane == 0) tmp[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int k = 1; k < SUM_WAVES; ++k) rec_join(v, tmp[k]);
+}
+
+__device__ inline double block_max(double v, double* tmp) {      // -> every thread
+  for (int d = 32; d > 0; d >>= 1) { const double o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
+  if ((threadIdx.x & 63) == 0) tmp[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double m = tmp[0];
+  for (int k = 1; k < SUM_WAVES; ++k) m = tmp[k] > m ? tmp[k] : m;
+  __syncthreads();
+  return m;
+}
+
+__device__ inline int range_of_block(const SumParams* __restrict__ P, int b) {
+  int lo = 0, hi = P->n_ranges;                     // off[lo] <= b < off[hi]
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (P->off[mid] <= b) lo = mid; else hi = mid; }
+  return lo;
+}
+
+// A block's words of the range [first, first + count): the whole 16-byte pairs inside it, pair j for the block's thread
+// j mod (blocks * ENS_THREADS), four loads in flight per thread; the odd word at either end goes to thread 0 of the range's
+// first block.  f1(word index - first, mean) / f2(.., mean, M2) see a thread's words in ascending order.
+struct SumSpan { long long first, count, pair0, n_pairs, j0, stride; bool ends; };
+__device__ inline SumSpan span_of(const SumRange& R, int blk, int n_blk) {
+  SumSpan s;
+  s.first = R.first; s.count = R.count;
+  const long long a0 = (R.first + 1) & ~1LL, a1 = (R.first + R.count) & ~1LL;
+  s.pair0 = a0 >> 1; s.n_pairs = a1 > a0 ? (a1 - a0) >> 1 : 0;
+  s.j0 = (long long)blk * ENS_THREADS + threadIdx.x; s.stride = (long long)n_blk * ENS_THREADS;
+  s.ends = blk == 0 && threadIdx.x == 0;
+  return s;
+}
+
+// sweep 1: the largest |mean| over the words whose mean is finite, per block
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_amax(const double* __restrict__ mean, const SumParams* __restrict__ P,
+                                                                  double* __restrict__ pmax) {
+  __shared__ double tmp[SUM_WAVES];
+  const int r = range_of_block(P, blockIdx.x), o0 = P->off[r];
+  const SumSpan s = span_of(P->r[r], blockIdx.x - o0, P->off[r + 1] - o0);
+  const double2* __restrict__ m2v = reinterpret_cast<const double2*>(mean) + s.pair0;
+  double a = 0.0;
+  auto see = [&](double m) { const double x = fabs(m); if (finite_(m) && x > a) a = x; };
+  if (s.ends && (s.first & 1)) see(mean[s.first]);
+  long long j = s.j0;
+  for (; j + 3 * s.stride < s.n_pairs; j += 4 * s.stride) {
+    const double2 p0 = m2v[j], p1 = m2v[j + s.stride], p2 = m2v[j + 2 * s.stride], p3 = m2v[j + 3 * s.stride];
+    see(p0.x); see(p0.y); see(p1.x); see(p1.y); see(p2.x); see(p2.y); see(p3.x); see(p3.y);
+  }
+  for (; j < s.n_pairs; j += s.stride) { const double2 p = m2v[j]; see(p.x); see(p.y); }
+  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(mean[s.first + s.count - 1]);
+  a = block_max(a, tmp);
+  if (threadIdx.x == 0) pmax[blockIdx.x] = a;
+}
+
+// sweep 2: with amax_used = the largest of the range's pmax, the record of the block's words
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_stats(const double* __restrict__ mean, const double* __restrict__ m2,
+                                                                   const SumParams* __restrict__ P, const double* __restrict__ pmax,
+                                                                   SumRec* __restrict__ part, double denom) {
+  __shared__ double tmp[SUM_WAVES];
+  __shared__ SumRec rtmp[SUM_WAVES];
+  const int r = range_of_block(P, blockIdx.x), o0 = P->off[r], n_blk = P->off[r + 1] - o0;
+  const SumRange R = P->r[r];
+  const SumSpan s = span_of(R, blockIdx.x - o0, n_blk);
+  double a = 0.0;
+  for (int k = threadIdx.x; k < n_blk; k += ENS_THREADS) { const double x = pmax[o0 + k]; a = x > a ? x : a; }
+  const double amax_used = block_max(a, tmp);
+  const double floor_abs = R.floor_frac * amax_used, tol = R.tol;
+  SumRec v = rec_empty(amax_used);
+  auto see = [&](long long idx, double m, double q) {
+    if (!finite_(m) || !finite_(q)) { v.n_nonf += 1; return; }
+    const double x = fabs(m);
+    v.amax = x > v.amax ? x : v.amax;
+    if (x > 0.0 && x >= floor_abs) {
+      const double se = mcsm::sqrt_(q / denom);
+      const double rel = se / x;
+      v.n_sel += 1;
+      if (rel > tol) v.n_over += 1;
+      v.sum_se = v.sum_se + se;
+      v.sum_abs = v.sum_abs + x;
+      v.sum_rel2 = v.sum_rel2 + rel * rel;
+      if (rel > v.max_rel || (rel == v.max_rel && idx < v.arg)) { v.max_rel = rel; v.arg = idx; }
+    }
+  };
+  const double2* __restrict__ mv = reinterpret_cast<const double2*>(mean) + s.pair0;
+  const double2* __restrict__ qv = reinterpret_cast<const double2*>(m2) + s.pair0;
+  const long long i0 = 2 * s.pair0 - s.first;        // word index - first of pair 0's first word
+  if (s.ends && (s.first & 1)) see(0, mean[s.first], m2[s.first]);
+  long long j = s.j0;
+  for (; j + 3 * s.stride < s.n_pairs; j += 4 * s.stride) {
+    const long long j1 = j + s.stride, j2 = j + 2 * s.stride, j3 = j + 3 * s.stride;
+    const double2 a0 = mv[j], a1 = mv[j1], a2 = mv[j2], a3 = mv[j3];
+    const double2 b0 = qv[j], b1 = qv[j1], b2 = qv[j2], b3 = qv[j3];
+    see(i0 + 2 * j, a0.x, b0.x); see(i0 + 2 * j + 1, a0.y, b0.y);
+    see(i0 + 2 * j1, a1.x, b1.x); see(i0 + 2 * j1 + 1, a1.y, b1.y);
+    see(i0 + 2 * j2, a2.x, b2.x); see(i0 + 2 * j2 + 1, a2.y, b2.y);
+    see(i0 + 2 * j3, a3.x, b3.x); see(i0 + 2 * j3 + 1, a3.y, b3.y);
+  }
+  for (; j < s.n_pairs; j += s.stride) {
+    const double2 a0 = mv[j], b0 = qv[j];
+    see(i0 + 2 * j, a0.x, b0.x); see(i0 + 2 * j + 1, a0.y, b0.y);
+  }
+  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) {
+    const long long w = s.first + s.count - 1;
+    see(s.count - 1, mean[w], m2[w]);
+  }
+  rec_block_join(v, rtmp);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+
+// one block per range: its partials joined in index order (thread t: t, t + ENS_THREADS, ..; then the block's tree).  The
+// range's pmax become amax of the finite words: a second sweep 2, needed when that is not what the first one used, finds it there.
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_final(const SumParams* __restrict__ P, const SumRec* __restrict__ part,
+                                                                   double* __restrict__ pmax, SumRec* __restrict__ out) {
+  __shared__ SumRec rtmp[SUM_WAVES];
+  __shared__ double amax;
+  const int r = blockIdx.x, o0 = P->off[r], o1 = P->off[r + 1];
+  SumRec v = rec_empty(0.0);
+  for (int k = o0 + threadIdx.x; k < o1; k += ENS_THREADS) rec_join(v, part[k]);
+  rec_block_join(v, rtmp);
+  if (threadIdx.x == 0) {
+    v.amax_used = o1 > o0 ? part[o0].amax_used : 0.0;
+    if (v.arg == LLONG_MAX) { v.arg = -1; v.max_rel = v.n_sel > 0 ? __builtin_nan("") : 0.0; }
+    out[r] = v;
+    amax = v.amax;
+  }
+  __syncthreads();
+  for (int k = o0 + threadIdx.x; k < o1; k += ENS_THREADS) pmax[k] = amax;
+}
+
 int fail(const std::string& msg) { return mcs_ctx_view_fail(msg.c_str()); }
 #define ENSCHK(expr)                                                                          \
   do {                                                                                        \
@@ -178,6 +362,11 @@ struct mcs_ens {
   mcs_ctx* snap_of = nullptr;                 // (null: no snapshot since the last iteration sample)
   Event ev;                                   // recorded after every operation on the stream that carried it
   bool ev_set = false;
+  // mcs_ens_summarize, allocated at its first call: the ranges of a call and its results (pinned, and on the device), and one
+  // pmax / one record per block of the largest call so far
+  PinnedBuf<SumParams> sum_par_h; DevBuf<SumParams> sum_par;
+  PinnedBuf<SumRec> sum_out_h;    DevBuf<SumRec> sum_out;
+  DevBuf<double> sum_pmax;        DevBuf<SumRec> sum_part;
   long long len(int slot) const { return slot == n_slots - 1 ? E.it_total : E.sp_total; }
 };
 
@@ -355,6 +544,76 @@ int mcs_ens_read(mcs_ens* e, int slot, int what, int64_t first, int64_t count, d
   if (what == 2) {
     const double denom = (double)n * (double)(n - 1);
     for (int64_t k = 0; k < count; ++k) host[k] = std::sqrt(host[k] / denom);
+  }
+  return 0;
+}
+
+int mcs_ens_summarize(mcs_ens* e, int slot, int n_ranges, const mcs_ens_range* ranges, mcs_ens_summary* out) {
+  if (!e) return fail("mcs_ens_summarize: null argument");
+  if (slot < 0 || slot >= e->n_slots) return fail("mcs_ens_summarize: slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail("mcs_ens_summarize: n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
+  if (n_ranges == 0) return 0;
+  if (!ranges || !out) return fail("mcs_ens_summarize: null argument");
+  const long long n = e->n[(size_t)slot], len = e->len(slot);
+  if (n < 2) return fail("mcs_ens_summarize: the standard error needs at least two samples; the slot has " + std::to_string(n));
+  long long n_blocks = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    const mcs_ens_range& R = ranges[r];
+    const std::string who = "mcs_ens_summarize: range " + std::to_string(r);
+    if (R.first < 0 || R.count < 0 || R.first > len || R.count > len - R.first) return fail(who + " lies outside the slot's sample vector");
+    if (!(R.floor_frac >= 0.0 && R.floor_frac <= 1.0)) return fail(who + ": floor_frac outside [0, 1]");
+    if (!(R.tol >= 0.0)) return fail(who + ": tol is negative or not a number");
+    const long long b = (R.count + SUM_CHUNK - 1) / SUM_CHUNK;
+    n_blocks += b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b;
+  }
+  McsCtxView v;
+  if (mcs_ctx_view_get(e->home, &v)) return 1;
+  hipError_t a = e->sum_par_h.reserve(1);
+  if (a == hipSuccess) a = e->sum_par.reserve(1);
+  if (a == hipSuccess) a = e->sum_out_h.reserve(SUM_MAX_RANGES);
+  if (a == hipSuccess) a = e->sum_out.reserve(SUM_MAX_RANGES);
+  if (a == hipSuccess) a = e->sum_pmax.reserve(n_blocks);
+  if (a == hipSuccess) a = e->sum_part.reserve(n_blocks);
+  if (a != hipSuccess) return fail(std::string("mcs_ens_summarize: scratch allocation: ") + hipGetErrorString(a));
+  // (every earlier call has waited for its copies: the pinned blocks are free)
+  SumParams* P = e->sum_par_h.get();
+  P->n_ranges = n_ranges;
+  P->off[0] = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    P->r[r] = SumRange{ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].tol};
+    const long long b = (ranges[r].count + SUM_CHUNK - 1) / SUM_CHUNK;
+    P->off[r + 1] = P->off[r] + (int)(b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b);
+  }
+  if (enter(e, v.stream)) return 1;
+  const double* mean = e->mean[(size_t)slot].get();
+  const double* m2 = e->m2[(size_t)slot].get();
+  const double denom = (double)n * (double)(n - 1);
+  ENSCHK(hipMemcpyAsync(e->sum_par.get(), P, sizeof(SumParams), hipMemcpyHostToDevice, v.stream));
+  if (n_blocks > 0) {
+    hipLaunchKernelGGL(mcs_k_ens_sum_amax, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, mean, e->sum_par.get(), e->sum_pmax.get());
+    ENSCHK(hipGetLastError());
+  }
+  // One pass gives the answer unless a word with a finite mean and a non-finite M2 carried the largest |mean| of a range: sweep 1
+  // reads the means alone, sweep 2 sees it.  The second pass then selects with the amax of the finite words (and waits once more).
+  const SumRec* got = e->sum_out_h.get();
+  for (int pass = 0; pass < 2; ++pass) {
+    if (n_blocks > 0) {
+      hipLaunchKernelGGL(mcs_k_ens_sum_stats, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, mean, m2, e->sum_par.get(), e->sum_pmax.get(),
+                         e->sum_part.get(), denom);
+      ENSCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mcs_k_ens_sum_final, dim3((unsigned)n_ranges), dim3(ENS_THREADS), 0, v.stream, e->sum_par.get(), e->sum_part.get(),
+                       e->sum_pmax.get(), e->sum_out.get());
+    ENSCHK(hipGetLastError());
+    ENSCHK(hipMemcpyAsync(e->sum_out_h.get(), e->sum_out.get(), (size_t)n_ranges * sizeof(SumRec), hipMemcpyDeviceToHost, v.stream));
+    ENSCHK(hipStreamSynchronize(v.stream));
+    bool again = false;
+    for (int r = 0; r < n_ranges; ++r) again = again || got[r].amax != got[r].amax_used;
+    if (!again) break;
+  }
+  for (int r = 0; r < n_ranges; ++r) {
+    const SumRec& g = got[r];
+    out[r] = mcs_ens_summary{g.amax, g.max_rel, g.sum_se, g.sum_abs, g.sum_rel2, g.n_sel, g.n_over, g.n_nonf, g.arg};
   }
   return 0;
 }

@@ -80,6 +80,23 @@ class RunResult:
                                                                   # has them: the run options of the HIP context, by name) and the driver's own
                                                                   # fused_pcuts, fused_chunk, long_draws, long_imult_max as actually used
     ensemble: object = None       # the ensemble statistics the run fed (run(ensemble=...), run_overlapped(ensemble=True)); ensemble.py
+    convergence: object = None    # a Convergence: what run(triggers=...) checked and where it stopped; None without triggers
+
+
+@dataclasses.dataclass
+class TriggerCheck:
+    trigger: object               # the ensemble.Trigger
+    summary: object               # the ensemble.Summary of its range; None while its slot has fewer than two samples
+    value: float                  # the trigger's statistic (nan where it has none)
+    met: bool
+    predicted_samples: Optional[int]      # ensemble.Trigger.predicted_samples
+
+
+@dataclasses.dataclass
+class Convergence:
+    checks: list                  # [(i_iter, [TriggerCheck, in the order of run's triggers])], one per iteration end that was checked
+    stopped_at: int               # the last iteration the run did
+    satisfied: bool               # every trigger was met at the last check (False: the run did all its n_itrs)
 
 
 class Comm:
@@ -549,6 +566,19 @@ class _SpeciesScheduler:
         self.start_ready(False)
 
 
+def _check_triggers(ensemble, triggers):
+    """One summary per slot that has triggers -> [TriggerCheck] in the order of `triggers`."""
+    rows = [None] * len(triggers)
+    for slot in sorted({t.slot for t in triggers}):
+        mine = [k for k, t in enumerate(triggers) if t.slot == slot]
+        # (a slot that has not had two samples yet meets nothing)
+        got = ensemble.summarize(slot, [triggers[k].request for k in mine]) if ensemble.count(slot) >= 2 else [None] * len(mine)
+        for k, s in zip(mine, got):
+            t = triggers[k]
+            rows[k] = TriggerCheck(t, s, float("nan"), False, None) if s is None else TriggerCheck(t, s, t.value(s), t.met(s), t.predicted_samples(s))
+    return rows
+
+
 def _iteration_species(rs, i_iter, before_pcut):
     """The species of iteration i_iter in order: its transport (here, or with secondaries on the pool's threads as the
     scheduler places it), its merge into the primary if it ran on a secondary, its species end."""
@@ -580,7 +610,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         first_iter: int = 1, iter_state=None, species_tallies: str = "full", final_full_read: bool = True,
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
         long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None,
-        ensemble=None) -> RunResult:
+        ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -634,6 +664,17 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     error over the iterations, which are independent realisations while the profile is fixed (ensemble.py; on a HIP backend the
     histograms stay on the device).  Not with tcut_print (the in-place rewrite makes the coupled spectra no longer sums), not with
     smooth_shocks (the iterations then depend on each other), not with an enabled communicator: the multi-rank case is left out.
+    triggers: a list of ensemble.Trigger on parts of `ensemble`'s slots: the run ends once their error bars are small enough.  After
+    the ensemble has taken the iteration sample of iteration i, when done = i - first_iter + 1 >= min_iterations and done -
+    min_iterations is a multiple of check_every, every slot that has triggers is summarised once (Ensemble.summarize: on a HIP backend
+    one reduction on the device, a few hundred bytes to the host) and the loop ends when every trigger is met.  n_itrs stays the cap
+    (the per-iteration tallies px_esc_feb / energy_esc_feb are sized by the problem's).  A run that stops after iteration k has done
+    exactly what the same call with n_itrs = k - first_iter + 1 does: same tallies, same per_species, same ensemble (with
+    species_tallies = "light" the buffers of the last species end are fetched whole once the run has stopped, as they are at the last
+    species end of a run that knew its length; on_species_end has seen that species end without the histograms).
+    RunResult.convergence holds the checks, stopped_at and satisfied; predicted_samples in a check is a report, nothing acts on it.
+    Refused: triggers without ensemble, min_iterations < 2 (no error bar below two samples), check_every < 1, a trigger whose slot or
+    part the ensemble does not have.  None or []: no check, RunResult.convergence is None.
     """
     import torch
     comm = comm or Comm(False)
@@ -677,6 +718,17 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             raise ValueError("ensemble: one process without a communicator (the multi-rank case is left out)")
         if ensemble.n_species < len(cfg.species):
             raise ValueError(f"ensemble: {ensemble.n_species} species slots for {len(cfg.species)} species")
+    triggers = list(triggers or [])
+    if triggers:
+        if ensemble is None:
+            raise ValueError("triggers: they read the error bars of an ensemble; pass ensemble=")
+        if min_iterations < 2:
+            raise ValueError(f"triggers: min_iterations {min_iterations} < 2 (there is no standard error below two samples)")
+        if check_every < 1:
+            raise ValueError(f"triggers: check_every {check_every} < 1")
+        for t in triggers:
+            ensemble.check_trigger(t)
+    checks, stopped_at, satisfied = [], first_iter + n_itrs - 1, False
     if secondaries:
         if comm.enabled:
             raise ValueError("species_backends: one process without a communicator (the species' merges are not collectives)")
@@ -748,11 +800,24 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                 backend.write_tally("spectra_coupled", sc)
         if ensemble is not None:
             ensemble.add_iteration(backend)
+        done = i_iter - first_iter + 1
+        if triggers and done >= min_iterations and (done - min_iterations) % check_every == 0:
+            rows = _check_triggers(ensemble, triggers)
+            checks.append((i_iter, rows))
+            satisfied = all(row.met for row in rows)
         if on_iteration_end is not None:
             on_iteration_end(i_iter)
+        if satisfied:
+            stopped_at = i_iter
+            break
 
+    if satisfied and stopped_at < rs.last_iter and species_tallies == "light" and final_full_read:
+        # the last species end did not know it was the last: its whole buffers now, as a run of this length hands them back
+        rs.G_f, rs.G_i = backend.read_tallies()
+        rs.per_species[-1] = rs.per_species[-1][:2] + (rs.G_f, rs.G_i)
     return RunResult(rs.G_f, rs.G_i, rs.per_species, rs.stats, *_steps(rs.G_i, P.n_grid), rs.iter_finals, it_state,
-                     rs.local_steps, rs.empty_launches, rs.species_spans, options, ensemble)
+                     rs.local_steps, rs.empty_launches, rs.species_spans, options, ensemble,
+                     Convergence(checks, stopped_at, satisfied) if triggers else None)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over
@@ -778,6 +843,8 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     lone-wave rate -- measured 254 ms per iteration against 275 with full-chip launches, which let the other launch in only
     as whole workgroups retire (tools/gpu_concurrent.py).
     Single process only (no communicator): collectives issued from two threads would need an order.
+    No stop rule here (run(triggers=...)): the contexts run their iterations free of one another, so "stop once converged" needs rounds
+    of iterations and a scratch accumulator merged over the contexts at the end of each; that is left for later.
     ensemble: True -- every context feeds an ensemble of its own (ensemble.Ensemble.for_backend; run(ensemble=...)); at the end they
     are merged in context order into the first context's, which RunResult.ensemble hands back: per-cell mean and standard error of
     the tallies over the iterations.  Its finalize_mean / finalize_stderr / finalize_count are the same statistics, on the host, of

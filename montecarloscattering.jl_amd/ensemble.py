@@ -16,6 +16,16 @@ deviations M2 of every word of a SAMPLE vector, per slot (include/mcs.h, "ensemb
   merge    n = na + nb; d = mb - ma; mean = ma + d * (nb / n); M2 = (qa + qb) + (d * d) * (na * nb / n)        (Chan)
   stderr   sqrt(M2 / (n (n - 1)))
 
+Running until the error bars are small enough (`Ensemble.summarize`, `Trigger`; driver.run(triggers=...)): a summary reduces a part
+of a slot -- or a contiguous slice of its zones -- to a handful of numbers, mcs_ens_summary of include/mcs.h, where the definition is:
+
+  finite word    mean and M2 both finite; n_nonfinite counts the others, which take part in nothing else
+  amax           max |mean| over the finite words (0 for an empty range)
+  selected word  finite, |mean| > 0 and |mean| >= floor_frac * amax
+  per selected word   se = sqrt(M2 / (n (n - 1))), rel = se / |mean|
+  max_rel, argmax (the lowest word of the range that attains it; -1: nothing selected), n_over (rel > tol),
+  sum_se, sum_abs_mean, sum_rel2 (of rel * rel)
+
 `HipEnsemble` keeps the vectors on the device and updates them with the kernels of csrc/mcs_ensemble.hip: the 22 MB histograms
 never cross to the host (it costs device memory: two vectors of the sample length per slot, about twice the tally buffer per
 species slot).  `HostEnsemble` does the same arithmetic in numpy, in the same order, on read_tallies() buffers: it lets the driver
@@ -24,7 +34,9 @@ path run with the CPU test backends (driver.accumulate_tallies_host is the prece
 from __future__ import annotations
 
 import ctypes as ct
-from typing import Dict, Tuple
+import dataclasses
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -40,6 +52,11 @@ ITERATION_INCREMENTS = ("esc_flux", "esc_energy_eff", "esc_num_eff", "spectra_co
 ITERATION_AS_IS = ("weight_coupled", "energy_transfer_pool", "scalars")
 # (px_esc_feb and energy_esc_feb are indexed by iteration: they are part of the sample vector, their statistics mean nothing)
 ITERATION_NAMES = ITERATION_INCREMENTS + ITERATION_AS_IS
+# the parts whose first axis is the zone index: a zone slice of one is a contiguous word range
+ZONE_PARTS = HISTOGRAMS + ("pxx_flux", "pxz_flux", "energy_flux", "energy_recv_pool", "num_crossings") + MARGINALS + (
+    "spectra_sf", "spectra_pf", "energy_transfer_pool")
+STATISTICS = ("max", "rms", "weighted", "fraction_over")
+MAX_RANGES = 256          # of one mcs_ens_summarize call
 # what run_overlapped(ensemble=True) adds from the per-iteration ion_finalize of the last species
 FINALIZE_NAMES = ("dNdp_cr", "P_psd_par", "P_psd_perp", "energy_density_psd")
 
@@ -129,6 +146,119 @@ def stats_over(samples):
     return mean, err, n
 
 
+def _check_part(name: str, zones):
+    """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis."""
+    if name not in SPECIES_NAMES + ITERATION_NAMES:
+        raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}")
+    if zones is not None:
+        if name not in ZONE_PARTS:
+            raise ValueError(f"ensemble: {name!r} has no zone axis; a zone slice fits: {', '.join(ZONE_PARTS)}")
+        if len(zones) != 2 or int(zones[0]) != zones[0] or int(zones[1]) != zones[1]:
+            raise ValueError(f"ensemble: a zone slice is a pair (z_lo, z_hi) of integers, not {zones!r}")
+
+
+@dataclasses.dataclass(frozen=True)
+class Request:
+    """One range of a summary: a named part of a slot, or its zones [z_lo, z_hi) where the part's first axis is the zone index."""
+    name: str
+    zones: Optional[Tuple[int, int]] = None
+    floor_frac: float = 1e-3
+    tol: float = 0.0
+
+    def __post_init__(self):
+        _check_part(self.name, self.zones)
+        if not 0.0 <= self.floor_frac <= 1.0:
+            raise ValueError(f"ensemble: floor_frac {self.floor_frac!r} outside [0, 1]")
+        if not self.tol >= 0.0:
+            raise ValueError(f"ensemble: tol {self.tol!r} is negative or not a number")
+
+
+@dataclasses.dataclass(frozen=True)
+class Summary:
+    """mcs_ens_summary of one range, and the sample count n of its slot."""
+    amax: float
+    max_rel: float
+    sum_se: float
+    sum_abs_mean: float
+    sum_rel2: float
+    n_selected: int
+    n_over: int
+    n_nonfinite: int
+    argmax: int
+    n: int
+
+
+def summary_of(mean: np.ndarray, m2: np.ndarray, n: int, floor_frac: float, tol: float) -> Summary:
+    """The definition of the module docstring on the host, for the words of one range; the three sums correctly rounded."""
+    mean, m2 = np.asarray(mean, dtype=np.float64).ravel(), np.asarray(m2, dtype=np.float64).ravel()
+    finite = np.isfinite(mean) & np.isfinite(m2)
+    a = np.abs(mean)
+    amax = float(a[finite].max()) if finite.any() else 0.0
+    where = np.flatnonzero(finite & (a > 0.0) & (a >= floor_frac * amax))
+    n_nonfinite = int(mean.size - np.count_nonzero(finite))
+    if where.size == 0:
+        return Summary(amax, 0.0, 0.0, 0.0, 0.0, 0, 0, n_nonfinite, -1, int(n))
+    se = np.sqrt(m2[where] / (float(n) * float(n - 1)))
+    rel = se / a[where]
+    k = int(np.argmax(rel))            # (the first of equal maxima)
+    return Summary(amax, float(rel[k]), math.fsum(se), math.fsum(a[where]), math.fsum(rel * rel), int(where.size),
+                   int(np.count_nonzero(rel > tol)), n_nonfinite, int(where[k]), int(n))
+
+
+class Trigger:
+    """A stop rule on the error bars of one part of a slot (driver.run(triggers=...)): met when its value is <= threshold.
+      "max"            max_rel: the largest relative standard error of a selected word
+      "rms"            sqrt(sum_rel2 / n_selected)
+      "weighted"       sum_se / sum_abs_mean
+      "fraction_over"  n_over / n_selected: the share of the selected words whose relative error exceeds tol
+    Selected: the words of at least floor_frac times the part's largest |mean| (module docstring).  zones = (z_lo, z_hi): those zones
+    of a part whose first axis is the zone index.  Never met while the slot has fewer than two samples, nothing is selected or a
+    word of the range is not finite.  predicted_samples: for the three error statistics, the count at which the value would reach the
+    threshold if it goes on falling as 1 / sqrt(n): ceil(n (value / threshold)^2); a report, nothing acts on it.
+    Refused here: an unknown statistic, threshold <= 0, "fraction_over" without tol, a negative slot, a name no slot has, a zone
+    slice on a part without a zone axis.  Whether `slot` is a species slot or the iteration slot only an ensemble knows:
+    Ensemble.check_trigger, which driver.run calls before the first iteration, refuses a name the slot does not have."""
+
+    def __init__(self, slot: int, name: str, statistic: str, threshold: float, zones=None, floor_frac: float = 1e-3, tol: Optional[float] = None):
+        if statistic not in STATISTICS:
+            raise ValueError(f"trigger: unknown statistic {statistic!r}; there are: {', '.join(STATISTICS)}")
+        if not threshold > 0:
+            raise ValueError(f"trigger: threshold {threshold!r} must be positive")
+        if statistic == "fraction_over" and tol is None:
+            raise ValueError("trigger: 'fraction_over' needs tol, the relative error a word may have")
+        if int(slot) != slot or slot < 0:
+            raise ValueError(f"trigger: slot {slot!r} is no slot")
+        self.request = Request(name, None if zones is None else (int(zones[0]), int(zones[1])), float(floor_frac), 0.0 if tol is None else float(tol))
+        self.slot, self.name, self.statistic, self.threshold = int(slot), name, statistic, float(threshold)
+        self.zones, self.floor_frac, self.tol = self.request.zones, self.request.floor_frac, tol
+
+    def __repr__(self):
+        return (f"Trigger(slot={self.slot}, name={self.name!r}, statistic={self.statistic!r}, threshold={self.threshold!r}, zones={self.zones!r}, "
+                f"floor_frac={self.floor_frac!r}, tol={self.tol!r})")
+
+    def value(self, s: Summary) -> float:
+        """The statistic of a summary; nan where it has none (fewer than two samples, nothing selected)."""
+        if s.n < 2 or s.n_selected == 0:
+            return float("nan")
+        if self.statistic == "max":
+            return s.max_rel
+        if self.statistic == "rms":
+            return math.sqrt(s.sum_rel2 / s.n_selected)
+        if self.statistic == "weighted":
+            return s.sum_se / s.sum_abs_mean
+        return s.n_over / s.n_selected
+
+    def met(self, s: Summary) -> bool:
+        return s.n >= 2 and s.n_selected > 0 and s.n_nonfinite == 0 and self.value(s) <= self.threshold
+
+    def predicted_samples(self, s: Summary) -> Optional[int]:
+        """None for "fraction_over" (no 1 / sqrt(n) law) and where there is no finite value."""
+        v = self.value(s)
+        if self.statistic == "fraction_over" or not math.isfinite(v):
+            return None
+        return int(math.ceil(s.n * (v / self.threshold) ** 2))
+
+
 class Ensemble:
     """What both kinds have in common: the slots, the named views of a slot's vectors."""
 
@@ -178,6 +308,36 @@ class Ensemble:
     def stderr(self, slot: int, name: str) -> np.ndarray:
         """The standard error of the mean, sqrt(M2 / (n (n - 1))); refused below two samples."""
         return self._named(slot, 2, name)
+
+    def word_range(self, slot: int, name: str, zones=None) -> Tuple[int, int]:
+        """(first, count) of a part of the slot's sample vector, or of its zones [z_lo, z_hi)."""
+        off, shape = self._where(slot, name)
+        _check_part(name, zones)
+        n = int(np.prod(shape))
+        if zones is None:
+            return off, n
+        z_lo, z_hi = int(zones[0]), int(zones[1])
+        if not 0 <= z_lo <= z_hi <= shape[0]:
+            raise ValueError(f"ensemble: zones ({z_lo}, {z_hi}) outside 0..{shape[0]} of {name!r}")
+        per = n // shape[0]
+        return off + z_lo * per, (z_hi - z_lo) * per
+
+    def summarize(self, slot: int, requests: Sequence[Request]) -> List[Summary]:
+        """One Summary per request (at most MAX_RANGES; they may overlap), in one pass over the slot: on the device one
+        mcs_ens_summarize call and one wait.  Refused below two samples."""
+        requests = list(requests)
+        self._check_slot(slot)
+        if len(requests) > MAX_RANGES:
+            raise ValueError(f"ensemble: {len(requests)} requests in one summary; at most {MAX_RANGES}")
+        ranges = [self.word_range(slot, q.name, q.zones) + (float(q.floor_frac), float(q.tol)) for q in requests]
+        n = self.count(slot)
+        if n < 2:
+            raise ValueError(f"ensemble: a summary needs at least two samples; slot {slot} has {n}")
+        return self._summarize(slot, n, ranges) if ranges else []
+
+    def check_trigger(self, trigger: Trigger):
+        """Refuses a trigger whose slot this ensemble does not have, or whose part (or zone slice) that slot does not have."""
+        self.word_range(trigger.slot, trigger.name, trigger.zones)
 
     def destroy(self):
         pass
@@ -245,6 +405,10 @@ class HostEnsemble(Ensemble):
             return np.sqrt(self._m2[slot][first:first + count] / (float(n) * float(n - 1)))
         return (self._mean if what == 0 else self._m2)[slot][first:first + count].copy()
 
+    def _summarize(self, slot, n, ranges):
+        mean, m2 = self._mean[slot], self._m2[slot]
+        return [summary_of(mean[first:first + count], m2[first:first + count], n, floor_frac, tol) for first, count, floor_frac, tol in ranges]
+
     def load_mean(self, slot: int, backend):
         """The mean of a species slot written into the backend's per-species sections (num_crossings rounded to nearest)."""
         self._check_slot(slot)
@@ -303,6 +467,13 @@ class HipEnsemble(Ensemble):
         out = np.zeros(count)
         self._chk(self.lib.mcs_ens_read(self.h, int(slot), int(what), int(first), int(count), out.ctypes.data_as(capi.c_double_p)))
         return out
+
+    def _summarize(self, slot, n, ranges):
+        rs = (capi.McsEnsRange * len(ranges))(*[capi.McsEnsRange(*r) for r in ranges])
+        out = (capi.McsEnsSummary * len(ranges))()
+        self._chk(self.lib.mcs_ens_summarize(self.h, int(slot), len(ranges), rs, out))
+        return [Summary(o.amax, o.max_rel, o.sum_se, o.sum_abs_mean, o.sum_rel2, int(o.n_selected), int(o.n_over), int(o.n_nonfinite),
+                        int(o.argmax), n) for o in out]
 
     def load_mean(self, slot: int, backend: HipBackend):
         self._chk(self.lib.mcs_ens_load_mean(self.h, int(slot), backend.h))
