@@ -557,6 +557,32 @@ typedef struct mcs_ens_range   { int64_t first, count; double floor_frac, tol; }
 typedef struct mcs_ens_summary { double amax, max_rel, sum_se, sum_abs_mean, sum_rel2;
                                  int64_t n_selected, n_over, n_nonfinite, argmax; } mcs_ens_summary;
 int mcs_ens_summarize(mcs_ens* ens, int slot, int n_ranges, const mcs_ens_range* ranges, mcs_ens_summary* out);
+/* The same summary of the MERGE of several accumulators, without forming it: what a stop rule needs when every context of an
+ * overlapped run owns an accumulator (a scratch accumulator to merge them into would cost two more vectors per slot, and every
+ * check would rewrite it whole).  For every word w of the slot the merged pair (mean, M2) is the left fold of the merge formula
+ * above over the accumulators of the list that have samples in this slot, in list order, every operation a separate rounding:
+ *   the first non-empty accumulator gives (m, q, na); each further non-empty accumulator b merges in with
+ *   n = na + nb; d = mb - m; m = m + d * f_mean; q = (q + qb) + (d * d) * f_m2; na = n,
+ *   f_mean = (double)nb / n and f_m2 = (double)na * (double)nb / n computed on the host exactly as the merge call does;
+ *   an empty accumulator is skipped (an empty b changes nothing, an empty a takes b).
+ * The total count n = sum of the n_k is returned in *n_total; the denominator is (double)n * (double)(n - 1).  On these merged
+ * words the summary is word for word that of mcs_ens_summarize: a word is finite or not by its MERGED mean and M2 (a word finite in
+ * every accumulator whose merge is not -- d * d overflows -- is counted in n_nonfinite), and the repeated second sweep applies
+ * when a finite merged mean with a non-finite merged M2 carried a range's amax.  Each word's fold is made in registers; no
+ * accumulator is changed and nothing but the block partials is written.  Which words a thread sees, in which order, and how
+ * threads, waves, blocks and partials are joined depends on the ranges alone, so every field, the three sums included, has the
+ * bits that merging the same accumulators in the same order into an empty accumulator with mcs_ens_merge and calling
+ * mcs_ens_summarize on it gives; with n_ens = 1 the result is that of mcs_ens_summarize.
+ * Work is queued on the stream of ens[0]'s home context, after what every accumulator of the list queued last; the call waits for
+ * the device before it returns.  Scratch (parameters, partials, pinned results) is ens[0]'s, shared with mcs_ens_summarize.
+ * n_ranges = 0 returns 0 and still writes *n_total.  The count is checked before that, here and not in mcs_ens_summarize: a total
+ * below 2 is refused even with n_ranges = 0, where mcs_ens_summarize returns 0; the two calls agree from two samples on.  Refused, with a message, nothing changed and nothing queued: a null argument
+ * or null entry, n_ens outside 1..MCS_ENS_MAX_MERGED, the same accumulator twice, accumulators on different devices or with
+ * different slots or layouts (the conditions of mcs_ens_merge), a slot out of range, a total count below 2, and every condition on
+ * the ranges that mcs_ens_summarize refuses. */
+#define MCS_ENS_MAX_MERGED 8
+int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ranges, const mcs_ens_range* ranges,
+                             mcs_ens_summary* out, int64_t* n_total);
 
 /* ---- test / measurement hooks ------------------------------------------- */
 /* evaluate device math/RNG primitives (bit-parity tests): fn ids in mcs_fn */

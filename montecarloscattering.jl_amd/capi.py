@@ -322,6 +322,7 @@ def load_library() -> ct.CDLL:
         "mcs_ens_read": (i32, [vp, i32, i32, i64, i64, c_double_p]),
         "mcs_ens_load_mean": (i32, [vp, i32, vp]),
         "mcs_ens_summarize": (i32, [vp, i32, i32, ct.POINTER(McsEnsRange), ct.POINTER(McsEnsSummary)]),
+        "mcs_ens_summarize_merged": (i32, [i32, ct.POINTER(vp), i32, i32, ct.POINTER(McsEnsRange), ct.POINTER(McsEnsSummary), c_int64_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -372,4 +373,5 @@ EXPORTED_SYMBOLS = [
 EXPORTED_SYMBOLS += [
     "mcs_ens_get_layout", "mcs_ens_create", "mcs_ens_destroy", "mcs_ens_begin_iteration", "mcs_ens_add_species",
     "mcs_ens_add_iteration", "mcs_ens_merge", "mcs_ens_count", "mcs_ens_read", "mcs_ens_load_mean", "mcs_ens_summarize",
+    "mcs_ens_summarize_merged",
 ]

@@ -207,8 +207,8 @@ __device__ inline int range_of_block(const SumParams* __restrict__ P, int b) {
 }
 
 // A block's words of the range [first, first + count): the whole 16-byte pairs inside it, pair j for the block's thread
-// j mod (blocks * ENS_THREADS), four loads in flight per thread; the odd word at either end goes to thread 0 of the range's
-// first block.  f1(word index - first, mean) / f2(.., mean, M2) see a thread's words in ascending order.
+// j mod (blocks * ENS_THREADS); the odd word at either end goes to thread 0 of the range's first block.  A thread sees its words
+// in ascending order.
 struct SumSpan { long long first, count, pair0, n_pairs, j0, stride; bool ends; };
 __device__ inline SumSpan span_of(const SumRange& R, int blk, int n_blk) {
   SumSpan s;
@@ -220,36 +220,107 @@ __device__ inline SumSpan span_of(const SumRange& R, int blk, int n_blk) {
   return s;
 }
 
+// Where the sweeps take a word's (mean, M2) from.  A source says how many pairs a thread loads before it looks at them (LOADS);
+// which words a thread sees, and in which order, is span_of's business alone, the same for every source.
+//   SrcOne         the two vectors of one accumulator
+//   SrcMerged<N>   the Chan merge of N >= 2 accumulators, folded per word in registers in list order with the factors of every
+//                  step (f_mean[k] = nb / n, f_m2[k] = na * nb / n, host doubles as in mcs_k_ens_merge); nothing is written back
+struct SrcOne {
+  static constexpr int LOADS = 4;
+  const double* mean; const double* m2;
+  __device__ double mean_at(long long w) const { return mean[w]; }
+  __device__ double2 mean_pair(long long p) const { return reinterpret_cast<const double2*>(mean)[p]; }
+  __device__ void at(long long w, double& m, double& q) const { m = mean[w]; q = m2[w]; }
+  __device__ void pair(long long p, double2& m, double2& q) const {
+    m = reinterpret_cast<const double2*>(mean)[p]; q = reinterpret_cast<const double2*>(m2)[p];
+  }
+};
+
+template <int N>
+struct SrcMerged {
+  // One pair in flight per thread and sweep whatever N is: a pair already costs 2 N loads of 16 bytes, and the registers that
+  // LOADS > 1 would take grow with N.  For N = 2 that is half the bytes SrcOne keeps in flight; no other value has been measured.
+  static constexpr int LOADS = 1;
+  const double* mean[N]; const double* m2[N];
+  double f_mean[N], f_m2[N];               // [0] unused: accumulator 0 is the fold's start
+  // Step k of the fold: accumulator k's word (x, y) joins (m, q).  The one place where the formula stands: both sweeps, pairs and
+  // single words, go through it, so a word's merged mean has the same bits wherever it is computed (a caller that wants the mean
+  // only passes a q it throws away).
+  __device__ void step(double& m, double& q, double x, double y, int k) const {
+    const double d = x - m;
+    m = m + d * f_mean[k];
+    q = (q + y) + (d * d) * f_m2[k];
+  }
+  __device__ double mean_at(long long w) const {
+    double x[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = mean[k][w];
+    double m = x[0], q = 0.0;
+#pragma unroll
+    for (int k = 1; k < N; ++k) step(m, q, x[k], 0.0, k);
+    return m;
+  }
+  __device__ double2 mean_pair(long long p) const {
+    double2 x[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = reinterpret_cast<const double2*>(mean[k])[p];
+    double2 m = x[0], q = {0.0, 0.0};
+#pragma unroll
+    for (int k = 1; k < N; ++k) { step(m.x, q.x, x[k].x, 0.0, k); step(m.y, q.y, x[k].y, 0.0, k); }
+    return m;
+  }
+  __device__ void at(long long w, double& m, double& q) const {
+    double x[N], y[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) { x[k] = mean[k][w]; y[k] = m2[k][w]; }
+    m = x[0]; q = y[0];
+#pragma unroll
+    for (int k = 1; k < N; ++k) step(m, q, x[k], y[k], k);
+  }
+  __device__ void pair(long long p, double2& m, double2& q) const {
+    double2 x[N], y[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) { x[k] = reinterpret_cast<const double2*>(mean[k])[p]; y[k] = reinterpret_cast<const double2*>(m2[k])[p]; }
+    m = x[0]; q = y[0];
+#pragma unroll
+    for (int k = 1; k < N; ++k) { step(m.x, q.x, x[k].x, y[k].x, k); step(m.y, q.y, x[k].y, y[k].y, k); }
+  }
+};
+
 // sweep 1: the largest |mean| over the words whose mean is finite, per block
-__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_amax(const double* __restrict__ mean, const SumParams* __restrict__ P,
-                                                                  double* __restrict__ pmax) {
+template <class Src>
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_amax(const Src src, const SumParams* __restrict__ P, double* __restrict__ pmax) {
   __shared__ double tmp[SUM_WAVES];
   const int r = range_of_block(P, blockIdx.x), o0 = P->off[r];
   const SumSpan s = span_of(P->r[r], blockIdx.x - o0, P->off[r + 1] - o0);
-  const double2* __restrict__ m2v = reinterpret_cast<const double2*>(mean) + s.pair0;
+  constexpr int U = Src::LOADS;
   double a = 0.0;
   auto see = [&](double m) { const double x = fabs(m); if (finite_(m) && x > a) a = x; };
-  if (s.ends && (s.first & 1)) see(mean[s.first]);
+  if (s.ends && (s.first & 1)) see(src.mean_at(s.first));
   long long j = s.j0;
-  for (; j + 3 * s.stride < s.n_pairs; j += 4 * s.stride) {
-    const double2 p0 = m2v[j], p1 = m2v[j + s.stride], p2 = m2v[j + 2 * s.stride], p3 = m2v[j + 3 * s.stride];
-    see(p0.x); see(p0.y); see(p1.x); see(p1.y); see(p2.x); see(p2.y); see(p3.x); see(p3.y);
+  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
+    double2 p[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) p[u] = src.mean_pair(s.pair0 + j + u * s.stride);
+#pragma unroll
+    for (int u = 0; u < U; ++u) { see(p[u].x); see(p[u].y); }
   }
-  for (; j < s.n_pairs; j += s.stride) { const double2 p = m2v[j]; see(p.x); see(p.y); }
-  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(mean[s.first + s.count - 1]);
+  for (; j < s.n_pairs; j += s.stride) { const double2 p = src.mean_pair(s.pair0 + j); see(p.x); see(p.y); }
+  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(src.mean_at(s.first + s.count - 1));
   a = block_max(a, tmp);
   if (threadIdx.x == 0) pmax[blockIdx.x] = a;
 }
 
 // sweep 2: with amax_used = the largest of the range's pmax, the record of the block's words
-__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_stats(const double* __restrict__ mean, const double* __restrict__ m2,
-                                                                   const SumParams* __restrict__ P, const double* __restrict__ pmax,
+template <class Src>
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_stats(const Src src, const SumParams* __restrict__ P, const double* __restrict__ pmax,
                                                                    SumRec* __restrict__ part, double denom) {
   __shared__ double tmp[SUM_WAVES];
   __shared__ SumRec rtmp[SUM_WAVES];
   const int r = range_of_block(P, blockIdx.x), o0 = P->off[r], n_blk = P->off[r + 1] - o0;
   const SumRange R = P->r[r];
   const SumSpan s = span_of(R, blockIdx.x - o0, n_blk);
+  constexpr int U = Src::LOADS;
   double a = 0.0;
   for (int k = threadIdx.x; k < n_blk; k += ENS_THREADS) { const double x = pmax[o0 + k]; a = x > a ? x : a; }
   const double amax_used = block_max(a, tmp);
@@ -270,27 +341,28 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_stats(const double*
       if (rel > v.max_rel || (rel == v.max_rel && idx < v.arg)) { v.max_rel = rel; v.arg = idx; }
     }
   };
-  const double2* __restrict__ mv = reinterpret_cast<const double2*>(mean) + s.pair0;
-  const double2* __restrict__ qv = reinterpret_cast<const double2*>(m2) + s.pair0;
   const long long i0 = 2 * s.pair0 - s.first;        // word index - first of pair 0's first word
-  if (s.ends && (s.first & 1)) see(0, mean[s.first], m2[s.first]);
+  if (s.ends && (s.first & 1)) { double m, q; src.at(s.first, m, q); see(0, m, q); }
   long long j = s.j0;
-  for (; j + 3 * s.stride < s.n_pairs; j += 4 * s.stride) {
-    const long long j1 = j + s.stride, j2 = j + 2 * s.stride, j3 = j + 3 * s.stride;
-    const double2 a0 = mv[j], a1 = mv[j1], a2 = mv[j2], a3 = mv[j3];
-    const double2 b0 = qv[j], b1 = qv[j1], b2 = qv[j2], b3 = qv[j3];
-    see(i0 + 2 * j, a0.x, b0.x); see(i0 + 2 * j + 1, a0.y, b0.y);
-    see(i0 + 2 * j1, a1.x, b1.x); see(i0 + 2 * j1 + 1, a1.y, b1.y);
-    see(i0 + 2 * j2, a2.x, b2.x); see(i0 + 2 * j2 + 1, a2.y, b2.y);
-    see(i0 + 2 * j3, a3.x, b3.x); see(i0 + 2 * j3 + 1, a3.y, b3.y);
+  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
+    double2 m[U], q[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) src.pair(s.pair0 + j + u * s.stride, m[u], q[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long ju = j + u * s.stride;
+      see(i0 + 2 * ju, m[u].x, q[u].x); see(i0 + 2 * ju + 1, m[u].y, q[u].y);
+    }
   }
   for (; j < s.n_pairs; j += s.stride) {
-    const double2 a0 = mv[j], b0 = qv[j];
-    see(i0 + 2 * j, a0.x, b0.x); see(i0 + 2 * j + 1, a0.y, b0.y);
+    double2 m, q;
+    src.pair(s.pair0 + j, m, q);
+    see(i0 + 2 * j, m.x, q.x); see(i0 + 2 * j + 1, m.y, q.y);
   }
   if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) {
-    const long long w = s.first + s.count - 1;
-    see(s.count - 1, mean[w], m2[w]);
+    double m, q;
+    src.at(s.first + s.count - 1, m, q);
+    see(s.count - 1, m, q);
   }
   rec_block_join(v, rtmp);
   if (threadIdx.x == 0) part[blockIdx.x] = v;
@@ -392,6 +464,85 @@ int enter(mcs_ens* e, hipStream_t st) {
 int leave(mcs_ens* e, hipStream_t st) {
   ENSCHK(hipEventRecord(e->ev, st));
   e->ev_set = true;
+  return 0;
+}
+
+// the ranges of a summary call against a vector of len words -> the blocks they take
+int check_ranges(const std::string& who, long long len, int n_ranges, const mcs_ens_range* ranges, long long* n_blocks) {
+  *n_blocks = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    const mcs_ens_range& R = ranges[r];
+    const std::string which = who + ": range " + std::to_string(r);
+    if (R.first < 0 || R.count < 0 || R.first > len || R.count > len - R.first) return fail(which + " lies outside the slot's sample vector");
+    if (!(R.floor_frac >= 0.0 && R.floor_frac <= 1.0)) return fail(which + ": floor_frac outside [0, 1]");
+    if (!(R.tol >= 0.0)) return fail(which + ": tol is negative or not a number");
+    const long long b = (R.count + SUM_CHUNK - 1) / SUM_CHUNK;
+    *n_blocks += b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b;
+  }
+  return 0;
+}
+
+template <int N>
+SrcMerged<N> merged_src(const double* const* mean, const double* const* m2, const double* f_mean, const double* f_m2) {
+  SrcMerged<N> s;
+  for (int k = 0; k < N; ++k) { s.mean[k] = mean[k]; s.m2[k] = m2[k]; s.f_mean[k] = f_mean[k]; s.f_m2[k] = f_m2[k]; }
+  return s;
+}
+
+// The checked ranges summarised from the word source src with the count n: on the stream of list[0]'s home context, after what
+// every accumulator of the list queued last, with list[0]'s scratch; waits for the device.
+template <class Src>
+int sum_run(const std::string& who, mcs_ens* const* list, int n_list, const Src& src, long long n, int n_ranges, const mcs_ens_range* ranges,
+            long long n_blocks, mcs_ens_summary* out) {
+  mcs_ens* e = list[0];
+  McsCtxView v;
+  if (mcs_ctx_view_get(e->home, &v)) return 1;
+  hipError_t a = e->sum_par_h.reserve(1);
+  if (a == hipSuccess) a = e->sum_par.reserve(1);
+  if (a == hipSuccess) a = e->sum_out_h.reserve(SUM_MAX_RANGES);
+  if (a == hipSuccess) a = e->sum_out.reserve(SUM_MAX_RANGES);
+  if (a == hipSuccess) a = e->sum_pmax.reserve(n_blocks);
+  if (a == hipSuccess) a = e->sum_part.reserve(n_blocks);
+  if (a != hipSuccess) return fail(who + ": scratch allocation: " + hipGetErrorString(a));
+  // (every earlier call has waited for its copies: the pinned blocks are free)
+  SumParams* P = e->sum_par_h.get();
+  P->n_ranges = n_ranges;
+  P->off[0] = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    P->r[r] = SumRange{ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].tol};
+    const long long b = (ranges[r].count + SUM_CHUNK - 1) / SUM_CHUNK;
+    P->off[r + 1] = P->off[r] + (int)(b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b);
+  }
+  for (int k = 0; k < n_list; ++k)
+    if (enter(list[k], v.stream)) return 1;
+  const double denom = (double)n * (double)(n - 1);
+  ENSCHK(hipMemcpyAsync(e->sum_par.get(), P, sizeof(SumParams), hipMemcpyHostToDevice, v.stream));
+  if (n_blocks > 0) {
+    hipLaunchKernelGGL(mcs_k_ens_sum_amax<Src>, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, src, e->sum_par.get(), e->sum_pmax.get());
+    ENSCHK(hipGetLastError());
+  }
+  // One pass gives the answer unless a word with a finite mean and a non-finite M2 carried the largest |mean| of a range: sweep 1
+  // reads the means alone, sweep 2 sees it.  The second pass then selects with the amax of the finite words (and waits once more).
+  const SumRec* got = e->sum_out_h.get();
+  for (int pass = 0; pass < 2; ++pass) {
+    if (n_blocks > 0) {
+      hipLaunchKernelGGL(mcs_k_ens_sum_stats<Src>, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, src, e->sum_par.get(), e->sum_pmax.get(),
+                         e->sum_part.get(), denom);
+      ENSCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mcs_k_ens_sum_final, dim3((unsigned)n_ranges), dim3(ENS_THREADS), 0, v.stream, e->sum_par.get(), e->sum_part.get(),
+                       e->sum_pmax.get(), e->sum_out.get());
+    ENSCHK(hipGetLastError());
+    ENSCHK(hipMemcpyAsync(e->sum_out_h.get(), e->sum_out.get(), (size_t)n_ranges * sizeof(SumRec), hipMemcpyDeviceToHost, v.stream));
+    ENSCHK(hipStreamSynchronize(v.stream));
+    bool again = false;
+    for (int r = 0; r < n_ranges; ++r) again = again || got[r].amax != got[r].amax_used;
+    if (!again) break;
+  }
+  for (int r = 0; r < n_ranges; ++r) {
+    const SumRec& g = got[r];
+    out[r] = mcs_ens_summary{g.amax, g.max_rel, g.sum_se, g.sum_abs, g.sum_rel2, g.n_sel, g.n_over, g.n_nonf, g.arg};
+  }
   return 0;
 }
 
@@ -549,73 +700,72 @@ int mcs_ens_read(mcs_ens* e, int slot, int what, int64_t first, int64_t count, d
 }
 
 int mcs_ens_summarize(mcs_ens* e, int slot, int n_ranges, const mcs_ens_range* ranges, mcs_ens_summary* out) {
-  if (!e) return fail("mcs_ens_summarize: null argument");
-  if (slot < 0 || slot >= e->n_slots) return fail("mcs_ens_summarize: slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
-  if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail("mcs_ens_summarize: n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
+  const std::string who = "mcs_ens_summarize";
+  if (!e) return fail(who + ": null argument");
+  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges == 0) return 0;
-  if (!ranges || !out) return fail("mcs_ens_summarize: null argument");
-  const long long n = e->n[(size_t)slot], len = e->len(slot);
-  if (n < 2) return fail("mcs_ens_summarize: the standard error needs at least two samples; the slot has " + std::to_string(n));
+  if (!ranges || !out) return fail(who + ": null argument");
+  const long long n = e->n[(size_t)slot];
+  if (n < 2) return fail(who + ": the standard error needs at least two samples; the slot has " + std::to_string(n));
   long long n_blocks = 0;
-  for (int r = 0; r < n_ranges; ++r) {
-    const mcs_ens_range& R = ranges[r];
-    const std::string who = "mcs_ens_summarize: range " + std::to_string(r);
-    if (R.first < 0 || R.count < 0 || R.first > len || R.count > len - R.first) return fail(who + " lies outside the slot's sample vector");
-    if (!(R.floor_frac >= 0.0 && R.floor_frac <= 1.0)) return fail(who + ": floor_frac outside [0, 1]");
-    if (!(R.tol >= 0.0)) return fail(who + ": tol is negative or not a number");
-    const long long b = (R.count + SUM_CHUNK - 1) / SUM_CHUNK;
-    n_blocks += b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b;
+  if (check_ranges(who, e->len(slot), n_ranges, ranges, &n_blocks)) return 1;
+  mcs_ens* list[1] = {e};
+  return sum_run(who, list, 1, SrcOne{e->mean[(size_t)slot].get(), e->m2[(size_t)slot].get()}, n, n_ranges, ranges, n_blocks, out);
+}
+
+int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ranges, const mcs_ens_range* ranges, mcs_ens_summary* out,
+                             int64_t* n_total) {
+  const std::string who = "mcs_ens_summarize_merged";
+  if (!ens || !n_total) return fail(who + ": null argument");
+  if (n_ens < 1 || n_ens > MCS_ENS_MAX_MERGED) return fail(who + ": n_ens outside 1.." + std::to_string(MCS_ENS_MAX_MERGED));
+  for (int k = 0; k < n_ens; ++k) {
+    if (!ens[k]) return fail(who + ": null argument (accumulator " + std::to_string(k) + " of the list)");
+    for (int j = 0; j < k; ++j)
+      if (ens[j] == ens[k]) return fail(who + ": accumulators " + std::to_string(j) + " and " + std::to_string(k) + " of the list are the same one");
   }
-  McsCtxView v;
-  if (mcs_ctx_view_get(e->home, &v)) return 1;
-  hipError_t a = e->sum_par_h.reserve(1);
-  if (a == hipSuccess) a = e->sum_par.reserve(1);
-  if (a == hipSuccess) a = e->sum_out_h.reserve(SUM_MAX_RANGES);
-  if (a == hipSuccess) a = e->sum_out.reserve(SUM_MAX_RANGES);
-  if (a == hipSuccess) a = e->sum_pmax.reserve(n_blocks);
-  if (a == hipSuccess) a = e->sum_part.reserve(n_blocks);
-  if (a != hipSuccess) return fail(std::string("mcs_ens_summarize: scratch allocation: ") + hipGetErrorString(a));
-  // (every earlier call has waited for its copies: the pinned blocks are free)
-  SumParams* P = e->sum_par_h.get();
-  P->n_ranges = n_ranges;
-  P->off[0] = 0;
-  for (int r = 0; r < n_ranges; ++r) {
-    P->r[r] = SumRange{ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].tol};
-    const long long b = (ranges[r].count + SUM_CHUNK - 1) / SUM_CHUNK;
-    P->off[r + 1] = P->off[r] + (int)(b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b);
+  const mcs_ens* a = ens[0];
+  for (int k = 1; k < n_ens; ++k) {
+    const mcs_ens* b = ens[k];
+    if (a->device != b->device) return fail(who + ": the accumulators are on different devices");
+    if (a->n_slots != b->n_slots || a->E.sp_total != b->E.sp_total || a->E.it_total != b->E.it_total || a->L.total != b->L.total ||
+        a->P.n_grid != b->P.n_grid || a->P.n_ions != b->P.n_ions || a->P.n_itrs != b->P.n_itrs)
+      return fail(who + ": the accumulators' slots or layouts differ");
   }
-  if (enter(e, v.stream)) return 1;
-  const double* mean = e->mean[(size_t)slot].get();
-  const double* m2 = e->m2[(size_t)slot].get();
-  const double denom = (double)n * (double)(n - 1);
-  ENSCHK(hipMemcpyAsync(e->sum_par.get(), P, sizeof(SumParams), hipMemcpyHostToDevice, v.stream));
-  if (n_blocks > 0) {
-    hipLaunchKernelGGL(mcs_k_ens_sum_amax, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, mean, e->sum_par.get(), e->sum_pmax.get());
-    ENSCHK(hipGetLastError());
+  if (slot < 0 || slot >= a->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(a->n_slots - 1));
+  if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
+  if (n_ranges > 0 && (!ranges || !out)) return fail(who + ": null argument");
+  // the accumulators that have samples in this slot, in list order, and the factors of every step of the fold (as mcs_ens_merge)
+  mcs_ens* list[MCS_ENS_MAX_MERGED];
+  const double *mean[MCS_ENS_MAX_MERGED], *m2[MCS_ENS_MAX_MERGED];
+  double f_mean[MCS_ENS_MAX_MERGED], f_m2[MCS_ENS_MAX_MERGED];
+  long long n = 0;
+  int m = 0;
+  for (int k = 0; k < n_ens; ++k) {
+    list[k] = ens[k];
+    const long long nb = ens[k]->n[(size_t)slot];
+    if (nb == 0) continue;
+    const double nn = (double)(n + nb);
+    f_mean[m] = m ? (double)nb / nn : 0.0;
+    f_m2[m] = m ? (double)n * (double)nb / nn : 0.0;
+    mean[m] = ens[k]->mean[(size_t)slot].get(); m2[m] = ens[k]->m2[(size_t)slot].get();
+    n += nb; ++m;
   }
-  // One pass gives the answer unless a word with a finite mean and a non-finite M2 carried the largest |mean| of a range: sweep 1
-  // reads the means alone, sweep 2 sees it.  The second pass then selects with the amax of the finite words (and waits once more).
-  const SumRec* got = e->sum_out_h.get();
-  for (int pass = 0; pass < 2; ++pass) {
-    if (n_blocks > 0) {
-      hipLaunchKernelGGL(mcs_k_ens_sum_stats, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, mean, m2, e->sum_par.get(), e->sum_pmax.get(),
-                         e->sum_part.get(), denom);
-      ENSCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(mcs_k_ens_sum_final, dim3((unsigned)n_ranges), dim3(ENS_THREADS), 0, v.stream, e->sum_par.get(), e->sum_part.get(),
-                       e->sum_pmax.get(), e->sum_out.get());
-    ENSCHK(hipGetLastError());
-    ENSCHK(hipMemcpyAsync(e->sum_out_h.get(), e->sum_out.get(), (size_t)n_ranges * sizeof(SumRec), hipMemcpyDeviceToHost, v.stream));
-    ENSCHK(hipStreamSynchronize(v.stream));
-    bool again = false;
-    for (int r = 0; r < n_ranges; ++r) again = again || got[r].amax != got[r].amax_used;
-    if (!again) break;
+  if (n < 2) return fail(who + ": the standard error needs at least two samples; the slot has " + std::to_string(n) + " over the list");
+  long long n_blocks = 0;
+  if (check_ranges(who, a->len(slot), n_ranges, ranges, &n_blocks)) return 1;
+  *n_total = n;
+  if (n_ranges == 0) return 0;
+  switch (m) {
+    case 1: return sum_run(who, list, n_ens, SrcOne{mean[0], m2[0]}, n, n_ranges, ranges, n_blocks, out);
+    case 2: return sum_run(who, list, n_ens, merged_src<2>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
+    case 3: return sum_run(who, list, n_ens, merged_src<3>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
+    case 4: return sum_run(who, list, n_ens, merged_src<4>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
+    case 5: return sum_run(who, list, n_ens, merged_src<5>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
+    case 6: return sum_run(who, list, n_ens, merged_src<6>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
+    case 7: return sum_run(who, list, n_ens, merged_src<7>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
+    default: return sum_run(who, list, n_ens, merged_src<8>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
   }
-  for (int r = 0; r < n_ranges; ++r) {
-    const SumRec& g = got[r];
-    out[r] = mcs_ens_summary{g.amax, g.max_rel, g.sum_se, g.sum_abs, g.sum_rel2, g.n_sel, g.n_over, g.n_nonf, g.arg};
-  }
-  return 0;
 }
 
 int mcs_ens_load_mean(mcs_ens* e, int slot, mcs_ctx* dst) {

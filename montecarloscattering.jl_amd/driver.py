@@ -80,7 +80,7 @@ class RunResult:
                                                                   # has them: the run options of the HIP context, by name) and the driver's own
                                                                   # fused_pcuts, fused_chunk, long_draws, long_imult_max as actually used
     ensemble: object = None       # the ensemble statistics the run fed (run(ensemble=...), run_overlapped(ensemble=True)); ensemble.py
-    convergence: object = None    # a Convergence: what run(triggers=...) checked and where it stopped; None without triggers
+    convergence: object = None    # a Convergence: what run / run_overlapped(triggers=...) checked and where it stopped; None without triggers
 
 
 @dataclasses.dataclass
@@ -95,6 +95,7 @@ class TriggerCheck:
 @dataclasses.dataclass
 class Convergence:
     checks: list                  # [(i_iter, [TriggerCheck, in the order of run's triggers])], one per iteration end that was checked
+                                  # (run_overlapped: per round end that was checked, i_iter the round's last iteration)
     stopped_at: int               # the last iteration the run did
     satisfied: bool               # every trigger was met at the last check (False: the run did all its n_itrs)
 
@@ -566,13 +567,29 @@ class _SpeciesScheduler:
         self.start_ready(False)
 
 
-def _check_triggers(ensemble, triggers):
-    """One summary per slot that has triggers -> [TriggerCheck] in the order of `triggers`."""
+def _check_trigger_args(have_ensemble, pass_what, min_iterations, check_every):
+    """What run and run_overlapped refuse of a stop rule's arguments before anything runs (the triggers themselves: Ensemble.check_trigger)."""
+    if not have_ensemble:
+        raise ValueError(f"triggers: they read the error bars of an ensemble; pass {pass_what}")
+    if min_iterations < 2:
+        raise ValueError(f"triggers: min_iterations {min_iterations} < 2 (there is no standard error below two samples)")
+    if check_every < 1:
+        raise ValueError(f"triggers: check_every {check_every} < 1")
+
+
+def _check_triggers(ensemble, triggers, others=()):
+    """One summary per slot that has triggers -> [TriggerCheck] in the order of `triggers`.  others: further ensembles, of the other
+    contexts of an overlapped run; the summary is then that of `ensemble` merged with them in that order (Ensemble.summarize_merged)."""
     rows = [None] * len(triggers)
+    others = list(others)
     for slot in sorted({t.slot for t in triggers}):
         mine = [k for k, t in enumerate(triggers) if t.slot == slot]
+        reqs = [triggers[k].request for k in mine]
         # (a slot that has not had two samples yet meets nothing)
-        got = ensemble.summarize(slot, [triggers[k].request for k in mine]) if ensemble.count(slot) >= 2 else [None] * len(mine)
+        if sum(e.count(slot) for e in [ensemble] + others) < 2:
+            got = [None] * len(mine)
+        else:
+            got = ensemble.summarize_merged(others, slot, reqs) if others else ensemble.summarize(slot, reqs)
         for k, s in zip(mine, got):
             t = triggers[k]
             rows[k] = TriggerCheck(t, s, float("nan"), False, None) if s is None else TriggerCheck(t, s, t.value(s), t.met(s), t.predicted_samples(s))
@@ -720,12 +737,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             raise ValueError(f"ensemble: {ensemble.n_species} species slots for {len(cfg.species)} species")
     triggers = list(triggers or [])
     if triggers:
-        if ensemble is None:
-            raise ValueError("triggers: they read the error bars of an ensemble; pass ensemble=")
-        if min_iterations < 2:
-            raise ValueError(f"triggers: min_iterations {min_iterations} < 2 (there is no standard error below two samples)")
-        if check_every < 1:
-            raise ValueError(f"triggers: check_every {check_every} < 1")
+        _check_trigger_args(ensemble is not None, "ensemble=", min_iterations, check_every)
         for t in triggers:
             ensemble.check_trigger(t)
     checks, stopped_at, satisfied = [], first_iter + n_itrs - 1, False
@@ -828,7 +840,8 @@ ACCUMULATED_OVER_ITERATIONS = ("esc_flux", "px_esc_feb", "energy_esc_feb", "esc_
 
 def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pcuts: Optional[int] = None,
                    on_iteration_end: Optional[Callable] = None, first_iter: int = 1,
-                   blocks_per_launch: Optional[int] = None, ensemble: bool = False) -> RunResult:
+                   blocks_per_launch: Optional[int] = None, ensemble: bool = False, triggers: Optional[list] = None,
+                   min_iterations: int = 2, check_every: int = 1) -> RunResult:
     """The iterations of a run with a FIXED shock profile (smooth-shocks = false -- the stock mc_in.toml, BASELINE
     config[1]) are independent Monte-Carlo realisations: nothing an iteration computes enters the next one's transport
     (src/main_loops.jl:52-121: every tally the transport reads is reset at the top; the RNG keys carry i_iter).  Their
@@ -843,23 +856,61 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     lone-wave rate -- measured 254 ms per iteration against 275 with full-chip launches, which let the other launch in only
     as whole workgroups retire (tools/gpu_concurrent.py).
     Single process only (no communicator): collectives issued from two threads would need an order.
-    No stop rule here (run(triggers=...)): the contexts run their iterations free of one another, so "stop once converged" needs rounds
-    of iterations and a scratch accumulator merged over the contexts at the end of each; that is left for later.
+    triggers: a list of ensemble.Trigger, the stop rule of run(triggers=...) for this path; needs ensemble=True.  Without triggers every
+    iteration is submitted up front and the contexts run free of one another.  With triggers the run proceeds in ROUNDS of
+    K = len(backends) iterations (the last one shorter when n_itrs, which stays the cap, is no multiple of K): iteration
+    first_iter + r K + k runs on context k as always, and a round's iterations are all consumed, in iteration order, before the next
+    round is submitted.  At the end of a round with `done` iterations finished a check is due at the first round end with
+    done >= min_iterations and then at every round end with done - (done at the last check) >= check_every; with K = 1 that is run's
+    schedule.  A check makes one Ensemble.summarize_merged per slot that has triggers over the contexts' ensembles in context order:
+    the summary of their merge, reduced on the device straight from the K accumulators, none of which is changed (there is no
+    scratch accumulator to merge into).  When every trigger is met no further round starts, and the run ends as a run of that length:
+    the never-reset tallies summed over the contexts, the ensembles merged in context order into the first, the finalize statistics
+    over the iterations that ran.  A run that stops after k iterations hands back what run_overlapped(n_itrs=k, ensemble=True) on
+    fresh contexts hands back.  RunResult.convergence holds the checks (keyed by the round's last iteration), stopped_at (the last
+    iteration done) and satisfied.  A round ends at a barrier: its last launches overlap with nothing, which costs a part of what
+    overlapping gains -- measured at 10^6 protons with three contexts and one check per round: 237.6 ms per iteration against 236.8
+    free-running (profiles/overlapped_stop.txt; small because a fixed profile's iterations take the same time, so that free-running
+    contexts stay nearly in step anyway; iterations of unequal length would lose more).  Opt-in.  If anything raises after the
+    ensembles were created -- a refused trigger, an iteration, on_iteration_end, a check -- they are destroyed before it propagates.  Refused: triggers without ensemble=True,
+    min_iterations < 2, check_every < 1, a trigger whose slot or part the ensembles do not have -- before any iteration runs.
     ensemble: True -- every context feeds an ensemble of its own (ensemble.Ensemble.for_backend; run(ensemble=...)); at the end they
     are merged in context order into the first context's, which RunResult.ensemble hands back: per-cell mean and standard error of
     the tallies over the iterations.  Its finalize_mean / finalize_stderr / finalize_count are the same statistics, on the host, of
     the per-iteration ion_finalize of the last species (ensemble.FINALIZE_NAMES), in iteration order."""
     cfg, P = prob.cfg, prob.params
     n_itrs = n_itrs if n_itrs is not None else cfg.num_iterations
-    K, L = len(backends), backends[0].layout
+    K = len(backends)
     assert K >= 1
+    if blocks_per_launch is None and K > 1 and hasattr(backends[0], "num_cus"):
+        blocks_per_launch = max(2 * backends[0].num_cus() // K, 1)
+    triggers = list(triggers or [])
+    if triggers:
+        _check_trigger_args(bool(ensemble), "ensemble=True", min_iterations, check_every)
+    enss = [ens.Ensemble.for_backend(be, len(cfg.species)) for be in backends] if ensemble else [None] * K
+    try:
+        for t in triggers:
+            enss[0].check_trigger(t)
+        return _overlapped_rounds(prob, backends, enss, n_itrs, max_pcuts, on_iteration_end, first_iter, blocks_per_launch, triggers,
+                                  min_iterations, check_every)
+    except BaseException:       # (a refused trigger, or whatever an iteration, a hook or a check raised: the run's accumulators go with it)
+        for e in enss:
+            if e is not None:
+                e.destroy()
+        raise
+
+
+def _overlapped_rounds(prob, backends, enss, n_itrs, max_pcuts, on_iteration_end, first_iter, blocks_per_launch, triggers, min_iterations,
+                       check_every) -> RunResult:
+    """run_overlapped once its arguments have passed: the rounds, the checks and the end of the run.  enss: one ensemble per context,
+    or None each."""
+    cfg, P = prob.cfg, prob.params
+    K, L = len(backends), backends[0].layout
+    ensemble = enss[0] is not None
     sm = itf.SmoothingConfig(smooth_shocks=False)
     st = itf.IterState.create(prob, sm, P.n_itrs)
     locks = [threading.Lock() for _ in backends]
-    if blocks_per_launch is None and K > 1 and hasattr(backends[0], "num_cus"):
-        blocks_per_launch = max(2 * backends[0].num_cus() // K, 1)
     busy = _ChipShare()                       # iterations in flight
-    enss = [ens.Ensemble.for_backend(be, len(cfg.species)) for be in backends] if ensemble else [None] * K
 
     def one(i_iter):
         k = (i_iter - first_iter) % K
@@ -879,19 +930,33 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     ng = P.n_grid
     # the step counters are running totals of a context: where each one starts
     total = [sum(_steps(_read_counters(be), ng)) for be in backends]
+    its = list(range(first_iter, first_iter + n_itrs))
+    # without triggers one "round" of everything; with them rounds of K, each consumed whole before the next is submitted
+    rounds = [its[r:r + K] for r in range(0, n_itrs, K)] if triggers else [its]
+    checks, satisfied, done, done_at_check = [], False, 0, None
     with ThreadPoolExecutor(max_workers=K) as pool:
-        futs = [pool.submit(one, i) for i in range(first_iter, first_iter + n_itrs)]
-        for i_iter, fu in zip(range(first_iter, first_iter + n_itrs), futs):      # consumed in iteration order
-            k, res, ion_fin = fu.result()
-            fin = itf.iter_finalize(prob, st, sm, i_iter, res.tallies_f64, L, ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
-            local_steps.append((i_iter, len(cfg.species), res.steps_helix + res.steps_retro - total[k]))
-            total[k] = res.steps_helix + res.steps_retro
-            last[k] = res
-            stats.extend(res.stats); per_species.extend(res.per_species); iter_finals.append((i_iter, fin, ion_fin))
-            if on_iteration_end is not None:
-                on_iteration_end(i_iter)
+        for rnd in rounds:
+            futs = [pool.submit(one, i) for i in rnd]
+            for i_iter, fu in zip(rnd, futs):      # consumed in iteration order
+                k, res, ion_fin = fu.result()
+                fin = itf.iter_finalize(prob, st, sm, i_iter, res.tallies_f64, L, ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
+                local_steps.append((i_iter, len(cfg.species), res.steps_helix + res.steps_retro - total[k]))
+                total[k] = res.steps_helix + res.steps_retro
+                last[k] = res
+                stats.extend(res.stats); per_species.extend(res.per_species); iter_finals.append((i_iter, fin, ion_fin))
+                if on_iteration_end is not None:
+                    on_iteration_end(i_iter)
+            done += len(rnd)
+            if triggers and (done >= min_iterations if done_at_check is None else done - done_at_check >= check_every):
+                rows = _check_triggers(enss[0], triggers, enss[1:])
+                checks.append((rnd[-1], rows))
+                done_at_check = done
+                satisfied = all(row.met for row in rows)
+                if satisfied:
+                    break
+    n_done = done
     # the state after the last iteration: its context's buffer, with the never-reset tallies summed over the contexts
-    k_last = (n_itrs - 1) % K
+    k_last = (n_done - 1) % K
     f, i64 = backends[k_last].read_tallies()              # the only time the three histograms cross to the host
     for k in last:
         if k == k_last:
@@ -907,4 +972,5 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
         for name in ens.FINALIZE_NAMES:
             enss[0].finalize_mean[name], enss[0].finalize_stderr[name], enss[0].finalize_count = ens.stats_over(
                 [getattr(ion_fin, name) for _, _, ion_fin in iter_finals])
-    return RunResult(f, i64, per_species, stats, *_steps(i64, ng), iter_finals, st, local_steps, ensemble=enss[0])
+    return RunResult(f, i64, per_species, stats, *_steps(i64, ng), iter_finals, st, local_steps, ensemble=enss[0],
+                     convergence=Convergence(checks, first_iter + n_done - 1, satisfied) if triggers else None)

@@ -26,6 +26,11 @@ of a slot -- or a contiguous slice of its zones -- to a handful of numbers, mcs_
   max_rel, argmax (the lowest word of the range that attains it; -1: nothing selected), n_over (rel > tol),
   sum_se, sum_abs_mean, sum_rel2 (of rel * rel)
 
+An overlapped run (driver.run_overlapped) keeps one accumulator per context.  `Ensemble.summarize_merged` gives the summary of their
+merge without forming it: per word the left fold of the merge above over the accumulators that have samples, in list order, then
+the definition above on the merged words with the total count (mcs_ens_summarize_merged of include/mcs.h; on the device each word's
+fold is made in registers, no accumulator is changed, no scratch accumulator exists).
+
 `HipEnsemble` keeps the vectors on the device and updates them with the kernels of csrc/mcs_ensemble.hip: the 22 MB histograms
 never cross to the host (it costs device memory: two vectors of the sample length per slot, about twice the tally buffer per
 species slot).  `HostEnsemble` does the same arithmetic in numpy, in the same order, on read_tallies() buffers: it lets the driver
@@ -57,6 +62,7 @@ ZONE_PARTS = HISTOGRAMS + ("pxx_flux", "pxz_flux", "energy_flux", "energy_recv_p
     "spectra_sf", "spectra_pf", "energy_transfer_pool")
 STATISTICS = ("max", "rms", "weighted", "fraction_over")
 MAX_RANGES = 256          # of one mcs_ens_summarize call
+MAX_MERGED = 8            # accumulators of one mcs_ens_summarize_merged call (MCS_ENS_MAX_MERGED)
 # what run_overlapped(ensemble=True) adds from the per-iteration ion_finalize of the last species
 FINALIZE_NAMES = ("dNdp_cr", "P_psd_par", "P_psd_perp", "energy_density_psd")
 
@@ -335,6 +341,33 @@ class Ensemble:
             raise ValueError(f"ensemble: a summary needs at least two samples; slot {slot} has {n}")
         return self._summarize(slot, n, ranges) if ranges else []
 
+    def summarize_merged(self, others: Sequence["Ensemble"], slot: int, requests: Sequence[Request]) -> List[Summary]:
+        """`summarize` of this ensemble merged with `others` in that order (at most MAX_MERGED in all, of this kind, slots and
+        layout, each once), none of them changed: Summary.n is the total count, which must be at least two.  On the device one
+        mcs_ens_summarize_merged call and one wait; bit for bit what merging them in that order into an empty ensemble and
+        summarising it gives.  summarize_merged([], ...) is summarize(...)."""
+        others, requests = list(others), list(requests)
+        if not others:
+            return self.summarize(slot, requests)
+        self._check_slot(slot)
+        self._check_merged(others)
+        if len(requests) > MAX_RANGES:
+            raise ValueError(f"ensemble: {len(requests)} requests in one summary; at most {MAX_RANGES}")
+        ranges = [self.word_range(slot, q.name, q.zones) + (float(q.floor_frac), float(q.tol)) for q in requests]
+        n = self.count(slot) + sum(o.count(slot) for o in others)
+        if n < 2:
+            raise ValueError(f"ensemble: a summary needs at least two samples; slot {slot} has {n} over the {1 + len(others)} ensembles")
+        return self._summarize_merged(others, slot, n, ranges) if ranges else []
+
+    def _check_merged(self, others):
+        if 1 + len(others) > MAX_MERGED:
+            raise ValueError(f"ensemble: a merged summary of {1 + len(others)} ensembles; at most {MAX_MERGED}")
+        if len({id(e) for e in [self] + others}) != 1 + len(others):
+            raise ValueError("ensemble: a merged summary takes every ensemble once")
+        for o in others:
+            if type(o) is not type(self) or o.n_species != self.n_species or o.layout.fields != self.layout.fields:
+                raise ValueError("ensemble: a merged summary needs ensembles of the same kind, slots and layout")
+
     def check_trigger(self, trigger: Trigger):
         """Refuses a trigger whose slot this ensemble does not have, or whose part (or zone slice) that slot does not have."""
         self.word_range(trigger.slot, trigger.name, trigger.zones)
@@ -409,6 +442,27 @@ class HostEnsemble(Ensemble):
         mean, m2 = self._mean[slot], self._m2[slot]
         return [summary_of(mean[first:first + count], m2[first:first + count], n, floor_frac, tol) for first, count, floor_frac, tol in ranges]
 
+    def _summarize_merged(self, others, slot, n, ranges):
+        out = []
+        for first, count, floor_frac, tol in ranges:
+            m, q, na = None, None, 0
+            for e in [self] + others:
+                nb = e._n[slot]
+                if nb == 0:
+                    continue
+                mb, qb = e._mean[slot][first:first + count], e._m2[slot][first:first + count]
+                if na == 0:
+                    m, q = mb, qb
+                else:
+                    nn = float(na + nb)
+                    with np.errstate(over="ignore", invalid="ignore"):      # (a merge that is not finite is counted, not an error)
+                        d = mb - m
+                        m = m + d * (float(nb) / nn)
+                        q = (q + qb) + (d * d) * (float(na) * float(nb) / nn)
+                na += nb
+            out.append(summary_of(m, q, n, floor_frac, tol))
+        return out
+
     def load_mean(self, slot: int, backend):
         """The mean of a species slot written into the backend's per-species sections (num_crossings rounded to nearest)."""
         self._check_slot(slot)
@@ -474,6 +528,22 @@ class HipEnsemble(Ensemble):
         self._chk(self.lib.mcs_ens_summarize(self.h, int(slot), len(ranges), rs, out))
         return [Summary(o.amax, o.max_rel, o.sum_se, o.sum_abs_mean, o.sum_rel2, int(o.n_selected), int(o.n_over), int(o.n_nonfinite),
                         int(o.argmax), n) for o in out]
+
+    def _check_merged(self, others):
+        # (the library refuses a duplicate, another device, other slots or layouts)
+        if 1 + len(others) > MAX_MERGED:
+            raise ValueError(f"ensemble: a merged summary of {1 + len(others)} ensembles; at most {MAX_MERGED}")
+        if not all(isinstance(o, HipEnsemble) for o in others):
+            raise ValueError("ensemble: a merged summary needs ensembles of the same kind, slots and layout")
+
+    def _summarize_merged(self, others, slot, n, ranges):
+        hs = (ct.c_void_p * (1 + len(others)))(*[e.h.value for e in [self] + others])
+        rs = (capi.McsEnsRange * len(ranges))(*[capi.McsEnsRange(*r) for r in ranges])
+        out = (capi.McsEnsSummary * len(ranges))()
+        total = ct.c_int64(0)
+        self._chk(self.lib.mcs_ens_summarize_merged(len(hs), hs, int(slot), len(ranges), rs, out, ct.byref(total)))
+        return [Summary(o.amax, o.max_rel, o.sum_se, o.sum_abs_mean, o.sum_rel2, int(o.n_selected), int(o.n_over), int(o.n_nonfinite),
+                        int(o.argmax), int(total.value)) for o in out]
 
     def load_mean(self, slot: int, backend: HipBackend):
         self._chk(self.lib.mcs_ens_load_mean(self.h, int(slot), backend.h))
