@@ -584,6 +584,49 @@ int mcs_ens_summarize(mcs_ens* ens, int slot, int n_ranges, const mcs_ens_range*
 int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ranges, const mcs_ens_range* ranges,
                              mcs_ens_summary* out, int64_t* n_total);
 
+/* ---- products sample: error bars of what a run publishes -- dN/dp in the three frames, the pressures and the energy density of
+ * ion_finalize, the spectral slope.  They are non-linear in the tallies (a normalisation, a rebinning between frames, a fit), so
+ * their error bars cannot be had from the per-cell ones: they are sampled once per iteration.
+ * Every species slot s has a companion PRODUCTS slot, MCS_ENS_PRODUCTS(s) in the count, read, summarize and summarize-merged
+ * calls.  Its two vectors are allocated at its first sample: an accumulator that never takes one costs no more memory and behaves
+ * as before.  The sample holds 3 n_grid NM + 6 n_grid doubles (NM = nmom + 2), mcs_ens_products_layout:
+ *   dNdp_sf, dNdp_pf, dNdp_isf                     [n_grid][NM] each: frames 0, 1, 2 of the last mcs_dndp_cr on the context, as that
+ *                                                  call left them on the device
+ *   P_psd_par, P_psd_perp, energy_density_psd      [n_grid] each: the last mcs_thermo_calcs on the context
+ *   slope_sf, slope_pf, slope_isf                  [n_grid] each: per zone the least-squares slope of log10 dN/dp against
+ *                                                  log10 p over the slope window
+ * Slope of frame m in zone z, over the window bins l_lo <= l < l_hi with x_l = x_log[l]: bin l is VALID if
+ * d = dNdp[m][z][l] > 1.0e-99 (the consumers' floor marks an empty bin); y_l = log10(d), the deterministic log10 of
+ * include/mcs_math.h.  With the k valid bins in ascending l, every operation a separate rounding, serial sums that start from 0:
+ *   xbar = (sum x_l) / k;  ybar = (sum y_l) / k;  Sxx = sum (x_l - xbar)(x_l - xbar);  Sxy = sum (x_l - xbar)(y_l - ybar);
+ *   slope = Sxy / Sxx
+ * k < 3 gives a quiet NaN.  The word's mean then stays non-finite: a summary counts it in n_nonfinite, and a stop rule over it is
+ * never met -- a slope trigger belongs on zones that the accelerated population reaches.  It is the slope of dN/dp, about -2.2
+ * behind a strong shock, not the index of f(p).
+ * mcs_ens_set_slope_window: x_log is a host array [nmom+1], log10 of each momentum bin's centre, copied to the device; the window
+ * needs 0 <= l_lo, l_hi <= nmom + 1, l_hi - l_lo >= 3 and finite x_log.  It may be called again until the first products sample of
+ * any slot and is refused afterwards, so that the samples of a slot stay comparable; the call waits for its copy.
+ * mcs_ens_add_products: one sample from what mcs_dndp_cr AND mcs_thermo_calcs left on src.  Refused unless both have run on src
+ * since its last mcs_begin_species and since the last products sample taken from it (no other call writes the buffer they leave
+ * their results in), without a slope window, and for what mcs_ens_add_species refuses.  Queued on src's stream behind the
+ * accumulator's event, no host synchronisation.
+ * mcs_ens_merge merges the products slots that src has, allocating in dst where needed; a dst without a window takes src's.  A
+ * merge, or a merged summary of a products slot, of accumulators that both have a window is refused when the windows differ in a
+ * bound or in the bits of any x_log word.  A products slot that was never sampled has count 0, and its reads are refused.
+ * mcs_ens_load_mean takes species slots only. */
+#define MCS_ENS_PRODUCTS(s) ((s) | (1 << 30))
+typedef struct mcs_ens_products_layout {
+  int64_t dNdp_sf, dNdp_pf, dNdp_isf;                       /* offsets, in doubles */
+  int64_t dNdp_n;                                           /* n_grid * (nmom+2): the length of each of the three */
+  int64_t P_psd_par, P_psd_perp, energy_density_psd;
+  int64_t slope_sf, slope_pf, slope_isf;
+  int64_t zone_n;                                           /* n_grid: the length of each of the six */
+  int64_t total;
+} mcs_ens_products_layout;
+int mcs_ens_products_get_layout(const mcs_params* p, mcs_ens_products_layout* out);      /* needs no GPU */
+int mcs_ens_set_slope_window(mcs_ens* ens, int l_lo, int l_hi, const double* x_log);
+int mcs_ens_add_products(mcs_ens* ens, mcs_ctx* src, int species_slot);
+
 /* ---- test / measurement hooks ------------------------------------------- */
 /* evaluate device math/RNG primitives (bit-parity tests): fn ids in mcs_fn */
 enum mcs_fn { MCS_FN_SIN = 0, MCS_FN_COS, MCS_FN_ASIN, MCS_FN_ACOS, MCS_FN_ATAN2, MCS_FN_LOG10,

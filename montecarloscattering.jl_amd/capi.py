@@ -88,6 +88,16 @@ class McsEnsLayout(ct.Structure):
         "tally_sp_first", "tally_it_first", "tally_recv_pool", "tally_scalars")]
 
 
+class McsEnsProductsLayout(ct.Structure):
+    """`mcs_ens_products_layout`: offsets and lengths of the nine parts of a products sample (include/mcs.h, "products sample")."""
+    _fields_ = [(name, ct.c_int64) for name in (
+        "dNdp_sf", "dNdp_pf", "dNdp_isf", "dNdp_n", "P_psd_par", "P_psd_perp", "energy_density_psd",
+        "slope_sf", "slope_pf", "slope_isf", "zone_n", "total")]
+
+
+ENS_PRODUCTS_BIT = 1 << 30      # MCS_ENS_PRODUCTS(s) = s | ENS_PRODUCTS_BIT
+
+
 class McsEnsRange(ct.Structure):
     """`mcs_ens_range`: a word range of a slot's sample vector, with the floor and the tolerance of its summary (include/mcs.h)."""
     _fields_ = [("first", ct.c_int64), ("count", ct.c_int64), ("floor_frac", ct.c_double), ("tol", ct.c_double)]
@@ -323,6 +333,9 @@ def load_library() -> ct.CDLL:
         "mcs_ens_load_mean": (i32, [vp, i32, vp]),
         "mcs_ens_summarize": (i32, [vp, i32, i32, ct.POINTER(McsEnsRange), ct.POINTER(McsEnsSummary)]),
         "mcs_ens_summarize_merged": (i32, [i32, ct.POINTER(vp), i32, i32, ct.POINTER(McsEnsRange), ct.POINTER(McsEnsSummary), c_int64_p]),
+        "mcs_ens_products_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsEnsProductsLayout)]),
+        "mcs_ens_set_slope_window": (i32, [vp, i32, i32, c_double_p]),
+        "mcs_ens_add_products": (i32, [vp, vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -373,5 +386,5 @@ EXPORTED_SYMBOLS = [
 EXPORTED_SYMBOLS += [
     "mcs_ens_get_layout", "mcs_ens_create", "mcs_ens_destroy", "mcs_ens_begin_iteration", "mcs_ens_add_species",
     "mcs_ens_add_iteration", "mcs_ens_merge", "mcs_ens_count", "mcs_ens_read", "mcs_ens_load_mean", "mcs_ens_summarize",
-    "mcs_ens_summarize_merged",
+    "mcs_ens_summarize_merged", "mcs_ens_products_get_layout", "mcs_ens_set_slope_window", "mcs_ens_add_products",
 ]

@@ -166,6 +166,10 @@ struct mcs_ctx {
   int pp_waits_last = 0;       // pcuts of the last pipelined run whose i_mult had to wait for the long histories
   // consumers (K4): table staging, outputs, thermo scratch slab
   DevBuf<double> d_ctab, d_cout, d_cscratch; DevBuf<unsigned long long> d_cdiag;
+  // d_cout holds the result of a whole mcs_dndp_cr / mcs_thermo_calcs: each consumer sets its own flag, mcs_begin_species and a
+  // products sample of the ensemble statistics (mcs_ens_add_products) clear both.  No other call writes d_cout: mcs_dndp_2d writes
+  // d_cscratch and d_c2d (consumers_ready only sizes d_cout, whose size never changes), the photon folds work in d_stage.
+  bool have_cout_dndp = false, have_cout_thermo = false;
   DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
   // launch
   int blocks = 0, threads = 256;
@@ -429,6 +433,7 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
   if (!(aa > 0) || zz == 0) return fail("mcs_begin_species: aa must be > 0 and zz != 0");
   c->i_iter = i_iter; c->i_ion = i_ion; c->aa = aa; c->zzq = zz * MCS_QCGS; c->m = aa * MCS_MP; c->mc = c->m * MCS_C;
   c->pmax_cutoff = pmax_cutoff; c->density = density; c->ewf = ewf;
+  c->have_cout_dndp = c->have_cout_thermo = false;
   if (fold_replicas(c)) return 1;      // (the previous species' replicas, before its histograms are cleared)
   const long long npsd = c->L.psd_stride_zone * P.n_grid;
   const long long pm = MCS_PSD_MAX + 1;
@@ -1318,6 +1323,7 @@ int mcs_dndp_cr(mcs_ctx* c, const mcs_consumer_in* in, double* dNdp, int64_t* di
   if (consumers_ready(c, in, "mcs_dndp_cr")) return 1;
   if (fold_replicas(c)) return 1;
   if (!in->mom_log_cgs || !in->mom_edge_cgs || !in->cos_edge || !in->zone_pop || !dNdp) return fail("mcs_dndp_cr: null table");
+  c->have_cout_dndp = false;
   const int NM = c->P.num_psd_mom_bins + 2, NT = c->P.num_psd_tht_bins + 2, ng = c->P.n_grid;
   std::vector<double> h((size_t)(2 * NM + NT + ng));
   memcpy(h.data(), in->mom_log_cgs, sizeof(double) * NM);
@@ -1333,6 +1339,7 @@ int mcs_dndp_cr(mcs_ctx* c, const mcs_consumer_in* in, double* dNdp, int64_t* di
   HIPCHK(hipMemcpyAsync(hd, c->d_cdiag, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (diag) { diag[0] = (int64_t)hd[0]; diag[1] = (int64_t)hd[1]; }
+  c->have_cout_dndp = true;
   return 0;
 }
 
@@ -1342,6 +1349,7 @@ int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, doubl
   if (fold_replicas(c)) return 1;
   if (!in->cos_center || !in->pt_center || !in->zone_pop || !in->density_loc || !in->cold_pressure || !P_par || !P_perp || !energy_density)
     return fail("mcs_thermo_calcs: null table");
+  c->have_cout_thermo = false;
   const int NM = c->P.num_psd_mom_bins + 2, NT = c->P.num_psd_tht_bins + 2, ng = c->P.n_grid;
   if (reserve(c->d_cscratch, (long long)NM * NT * ng)) return 1;
   std::vector<double> h((size_t)(NT + NM + 3 * ng), 0.0);
@@ -1360,6 +1368,7 @@ int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, doubl
   memcpy(P_par, o.data(), sizeof(double) * ng);
   memcpy(P_perp, o.data() + ng, sizeof(double) * ng);
   memcpy(energy_density, o.data() + 2 * ng, sizeof(double) * ng);
+  c->have_cout_thermo = true;
   return 0;
 }
 
@@ -1465,10 +1474,11 @@ int mcs_photon_ic(mcs_ctx* c, const double* mom_edge_cgs, double mc_e, int j_max
 int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
   MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
-  *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L};
+  *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo};
   return 0;
 }
 void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; }
+void mcs_ctx_view_products_taken(mcs_ctx* c) { c->have_cout_dndp = c->have_cout_thermo = false; }
 int mcs_ctx_view_fail(const char* msg) { return fail(msg); }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // mcs_ctx_view.h -- what a translation unit beside mcs_api.hip may see of a context (struct mcs_ctx is private to that file):
-// its device, stream, tally buffers, parameters and layout.  mcs_ensemble.hip (K8) works through this view.
+// its device, stream, tally buffers, parameters, layout and consumer output buffer.  mcs_ensemble.hip (K8) works through this view.
 // Not part of the C ABI of include/mcs.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -13,6 +13,10 @@ struct McsCtxView {
   unsigned long long* I;      // int64 tallies
   mcs_params P;
   mcs_layout L;
+  // the consumer output buffer, [3][n_grid][nmom+2] of mcs_dndp_cr then 3 x [n_grid] of mcs_thermo_calcs (null before the first
+  // consumer call), and whether each has left a whole result there since the last mcs_begin_species / products sample
+  const double* cout;
+  bool have_dndp_cr, have_thermo;
 };
 
 extern "C" {
@@ -22,6 +26,9 @@ int mcs_ctx_view_get(mcs_ctx* ctx, McsCtxView* out);
 // The tally buffer of ctx has been rewritten: what was derived from the old contents (the d2N/dp dcos array of the last
 // two-dimensional consumer call) is no longer valid.
 void mcs_ctx_view_tallies_written(mcs_ctx* ctx);
+// A products sample of the ensemble statistics has been queued from ctx's consumer output buffer: both consumers have to run again
+// before the next one.
+void mcs_ctx_view_products_taken(mcs_ctx* ctx);
 // Sets the message of the calling thread's last error (what the ABI's error call returns); returns 1.
 int mcs_ctx_view_fail(const char* msg);
 }

@@ -22,6 +22,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -115,6 +116,45 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_add_iteration(double* _
     }
     welford(mean, m2, w, x, n);
   }
+}
+
+// The slope of log10 dN/dp against x_log over the window's valid bins (include/mcs.h, "products sample"): one thread per
+// (frame, zone) row of dndp [3 * ng][nm], its sums serial in ascending bin order.  A row is read three times (count and sums, then
+// the squares about the means); log10 gives the same bits each time.  3 * ng rows of at most nm - 1 bins: a few hundred threads, each
+// on a row of its own -- too little work to be worth a wave per row and the fixed-order join that would need.
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_slope(const double* __restrict__ dndp, const double* __restrict__ x_log,
+                                                               double* __restrict__ slope, long long rows, int nm, int l_lo, int l_hi) {
+  for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long long)gridDim.x * blockDim.x) {
+    const double* row = dndp + r * nm;
+    int k = 0;
+    double sx = 0.0, sy = 0.0;
+    for (int l = l_lo; l < l_hi; ++l) {
+      const double d = row[l];
+      if (d > 1.0e-99) { sx = sx + x_log[l]; sy = sy + mcsm::log10(d); ++k; }
+    }
+    double out = __builtin_nan("");
+    if (k >= 3) {
+      const double xbar = sx / (double)k, ybar = sy / (double)k;
+      double sxx = 0.0, sxy = 0.0;
+      for (int l = l_lo; l < l_hi; ++l) {
+        const double d = row[l];
+        if (d > 1.0e-99) {
+          const double dx = x_log[l] - xbar;
+          sxx = sxx + dx * dx;
+          sxy = sxy + dx * (mcsm::log10(d) - ybar);
+        }
+      }
+      out = sxy / sxx;
+    }
+    slope[r] = out;
+  }
+}
+
+// cout: the context's consumer output buffer, n_cout = 3 ng nm + 3 ng words; the last 3 ng words of the sample are the slopes
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_add_products(double* __restrict__ mean, double* __restrict__ m2, const double* __restrict__ cout,
+                                                                      const double* __restrict__ slope, long long n_cout, long long total, double n) {
+  for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long long)gridDim.x * blockDim.x)
+    welford(mean, m2, w, w < n_cout ? cout[w] : slope[w - n_cout], n);
 }
 
 // Chan: f_mean = nb / n, f_m2 = na * nb / n (host doubles)
@@ -417,6 +457,24 @@ void ens_layout(const mcs_params* p, mcs_ens_layout* E) {
   E->tally_sp_first = L.psd; E->tally_it_first = L.esc_flux; E->tally_recv_pool = L.energy_recv_pool; E->tally_scalars = L.scalars;
 }
 
+void products_layout(const mcs_params* p, mcs_ens_products_layout* PL) {
+  const int64_t ng = p->n_grid, nm = p->num_psd_mom_bins + 2;
+  PL->dNdp_n = ng * nm; PL->zone_n = ng;
+  PL->dNdp_sf = 0; PL->dNdp_pf = ng * nm; PL->dNdp_isf = 2 * ng * nm;
+  int64_t o = 3 * ng * nm;
+  PL->P_psd_par = o;          o += ng;
+  PL->P_psd_perp = o;         o += ng;
+  PL->energy_density_psd = o; o += ng;
+  PL->slope_sf = o;           o += ng;
+  PL->slope_pf = o;           o += ng;
+  PL->slope_isf = o;          o += ng;
+  PL->total = o;
+}
+
+constexpr int PRODUCTS_BIT = 1 << 30;      // MCS_ENS_PRODUCTS
+// (a negative slot has every high bit set: it is no products slot, and is refused as it always was)
+bool is_products(int slot) { return slot >= 0 && (slot & PRODUCTS_BIT) != 0; }
+
 }  // namespace
 
 struct mcs_ens {
@@ -439,7 +497,16 @@ struct mcs_ens {
   PinnedBuf<SumParams> sum_par_h; DevBuf<SumParams> sum_par;
   PinnedBuf<SumRec> sum_out_h;    DevBuf<SumRec> sum_out;
   DevBuf<double> sum_pmax;        DevBuf<SumRec> sum_part;
-  long long len(int slot) const { return slot == n_slots - 1 ? E.it_total : E.sp_total; }
+  // the products slots, one beside every species slot (include/mcs.h, "products sample"): vectors allocated at the first sample
+  mcs_ens_products_layout PL;
+  std::vector<long long> pn;
+  std::vector<DevBuf<double>> pmean, pm2;     // per species slot: PL.total doubles each, or nothing
+  int win_lo = 0, win_hi = 0;                 // the slope window; none while x_log_h is empty
+  std::vector<double> x_log_h;                // [nmom+1]
+  DevBuf<double> x_log, slope;                // its device copy; the slopes of the sample being added [3][n_grid]
+  bool products_sampled = false;              // some products slot has taken a sample (or a merge): the window is fixed
+  long long len(int slot) const { return is_products(slot) ? PL.total : slot == n_slots - 1 ? E.it_total : E.sp_total; }
+  bool has_window() const { return !x_log_h.empty(); }
 };
 
 namespace {
@@ -464,6 +531,42 @@ int enter(mcs_ens* e, hipStream_t st) {
 int leave(mcs_ens* e, hipStream_t st) {
   ENSCHK(hipEventRecord(e->ev, st));
   e->ev_set = true;
+  return 0;
+}
+
+// What a count, read or summary call works on: a species slot, the iteration slot, or the products slot of a species slot.
+// mean / m2 are null for a products slot that was never sampled (n is then 0).
+struct SlotRef { long long n; double* mean; double* m2; };
+int slot_ref(const mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
+  if (is_products(slot)) {
+    const int s = slot ^ PRODUCTS_BIT;
+    if (s >= e->n_slots - 1)
+      return fail(who + ": products slot of slot " + std::to_string(s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
+    *out = SlotRef{e->pn[(size_t)s], e->pmean[(size_t)s].get(), e->pm2[(size_t)s].get()};
+    return 0;
+  }
+  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  *out = SlotRef{e->n[(size_t)slot], e->mean[(size_t)slot].get(), e->m2[(size_t)slot].get()};
+  return 0;
+}
+
+// both have a slope window, and the two differ in a bound or in the bits of an x_log word
+bool windows_differ(const mcs_ens* a, const mcs_ens* b) {
+  if (!a->has_window() || !b->has_window()) return false;
+  return a->win_lo != b->win_lo || a->win_hi != b->win_hi || a->x_log_h.size() != b->x_log_h.size() ||
+         memcmp(a->x_log_h.data(), b->x_log_h.data(), a->x_log_h.size() * sizeof(double)) != 0;
+}
+
+// room for the two vectors of species slot s's products slot, zeroed on st when they are new
+int products_reserve(mcs_ens* e, const std::string& who, int s, hipStream_t st) {
+  DevBuf<double>& m = e->pmean[(size_t)s];
+  DevBuf<double>& q = e->pm2[(size_t)s];
+  if (m.get() && q.get()) return 0;
+  hipError_t a = m.reserve(e->PL.total);
+  if (a == hipSuccess) a = q.reserve(e->PL.total);
+  if (a != hipSuccess) { m.reset(); q.reset(); return fail(who + ": hipMalloc: " + hipGetErrorString(a)); }
+  ENSCHK(hipMemsetAsync(m.get(), 0, (size_t)e->PL.total * sizeof(double), st));
+  ENSCHK(hipMemsetAsync(q.get(), 0, (size_t)e->PL.total * sizeof(double), st));
   return 0;
 }
 
@@ -556,6 +659,12 @@ int mcs_ens_get_layout(const mcs_params* p, mcs_ens_layout* out) {
   return 0;
 }
 
+int mcs_ens_products_get_layout(const mcs_params* p, mcs_ens_products_layout* out) {
+  if (!p || !out) return fail("mcs_ens_products_get_layout: null argument");
+  products_layout(p, out);
+  return 0;
+}
+
 int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   if (!home || !out) return fail("mcs_ens_create: null argument");
   if (n_species_slots < 0 || n_species_slots > 4096) return fail("mcs_ens_create: n_species_slots outside 0..4096");
@@ -565,6 +674,9 @@ int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   std::unique_ptr<mcs_ens> e(new mcs_ens());
   e->device = v.device; e->home = home; e->P = v.P; e->L = v.L;
   ens_layout(&v.P, &e->E);
+  products_layout(&v.P, &e->PL);
+  e->pn.assign((size_t)n_species_slots, 0);
+  e->pmean.resize((size_t)n_species_slots); e->pm2.resize((size_t)n_species_slots);
   const mcs_layout& L = v.L;
   e->inc = IncRanges{{L.esc_flux, L.esc_energy_eff, L.spectra_coupled}, {L.px_esc_feb, L.weight_coupled, L.energy_transfer_pool}};
   e->n_slots = n_species_slots + 1;
@@ -644,6 +756,56 @@ int mcs_ens_add_iteration(mcs_ens* e, mcs_ctx* src) {
   return leave(e, v.stream);
 }
 
+int mcs_ens_set_slope_window(mcs_ens* e, int l_lo, int l_hi, const double* x_log) {
+  const std::string who = "mcs_ens_set_slope_window";
+  if (!e || !x_log) return fail(who + ": null argument");
+  if (e->products_sampled) return fail(who + ": a products slot has taken a sample; the window stays as it is");
+  const int nx = e->P.num_psd_mom_bins + 1;
+  if (l_lo < 0 || l_hi > nx || l_hi - l_lo < 3)
+    return fail(who + ": window [" + std::to_string(l_lo) + ", " + std::to_string(l_hi) + ") needs 0 <= l_lo, l_hi <= " + std::to_string(nx) +
+                " and at least three bins");
+  for (int l = 0; l < nx; ++l)
+    if (!std::isfinite(x_log[l])) return fail(who + ": x_log[" + std::to_string(l) + "] is not finite");
+  McsCtxView v;
+  if (mcs_ctx_view_get(e->home, &v)) return 1;
+  hipError_t a = e->x_log.reserve(nx);
+  if (a == hipSuccess) a = e->slope.reserve(3LL * e->P.n_grid);
+  if (a != hipSuccess) return fail(who + ": hipMalloc: " + hipGetErrorString(a));
+  if (enter(e, v.stream)) return 1;
+  ENSCHK(hipMemcpyAsync(e->x_log.get(), x_log, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, v.stream));
+  ENSCHK(hipStreamSynchronize(v.stream));      // (the caller's array is free again)
+  e->x_log_h.assign(x_log, x_log + nx);
+  e->win_lo = l_lo; e->win_hi = l_hi;
+  return leave(e, v.stream);
+}
+
+int mcs_ens_add_products(mcs_ens* e, mcs_ctx* src, int slot) {
+  const std::string who = "mcs_ens_add_products";
+  if (!e || !src) return fail(who + ": null argument");
+  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  if (slot == e->n_slots - 1) return fail(who + ": slot " + std::to_string(slot) + " is the iteration slot; only a species slot has a products slot");
+  if (!e->has_window()) return fail(who + ": no slope window (mcs_ens_set_slope_window)");
+  McsCtxView v;
+  if (view_of(e, src, who.c_str(), &v)) return 1;
+  if (!v.have_dndp_cr || !v.have_thermo || !v.cout)
+    return fail(who + ": the context needs an mcs_dndp_cr and an mcs_thermo_calcs since its last mcs_begin_species and its last products sample");
+  if (enter(e, v.stream)) return 1;
+  if (products_reserve(e, who, slot, v.stream)) return 1;
+  const long long ng = e->P.n_grid, n_cout = e->PL.slope_sf;
+  const int nm = e->P.num_psd_mom_bins + 2;
+  hipLaunchKernelGGL(mcs_k_ens_slope, dim3(grid_for(3 * ng)), dim3(ENS_THREADS), 0, v.stream, v.cout, e->x_log.get(), e->slope.get(), 3 * ng, nm,
+                     e->win_lo, e->win_hi);
+  ENSCHK(hipGetLastError());
+  const long long n = e->pn[(size_t)slot] + 1;
+  hipLaunchKernelGGL(mcs_k_ens_add_products, dim3(grid_for(e->PL.total)), dim3(ENS_THREADS), 0, v.stream, e->pmean[(size_t)slot].get(),
+                     e->pm2[(size_t)slot].get(), v.cout, e->slope.get(), n_cout, (long long)e->PL.total, (double)n);
+  ENSCHK(hipGetLastError());
+  e->pn[(size_t)slot] = n;
+  e->products_sampled = true;
+  mcs_ctx_view_products_taken(src);
+  return leave(e, v.stream);
+}
+
 int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (!dst || !src) return fail("mcs_ens_merge: null argument");
   if (dst == src) return fail("mcs_ens_merge: dst and src are the same accumulator");
@@ -651,9 +813,37 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (dst->n_slots != src->n_slots || dst->E.sp_total != src->E.sp_total || dst->E.it_total != src->E.it_total || dst->L.total != src->L.total ||
       dst->P.n_grid != src->P.n_grid || dst->P.n_ions != src->P.n_ions || dst->P.n_itrs != src->P.n_itrs)
     return fail("mcs_ens_merge: the accumulators' slots or layouts differ");
+  if (windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' slope windows differ");
   McsCtxView v;
   if (mcs_ctx_view_get(dst->home, &v)) return 1;
+  bool any_products = false;
+  for (int s = 0; s < src->n_slots - 1; ++s) any_products = any_products || src->pn[(size_t)s] > 0;
+  if (any_products && !dst->has_window()) {
+    hipError_t a = dst->x_log.reserve((long long)src->x_log_h.size());
+    if (a == hipSuccess) a = dst->slope.reserve(3LL * dst->P.n_grid);
+    if (a != hipSuccess) return fail(std::string("mcs_ens_merge: hipMalloc: ") + hipGetErrorString(a));
+  }
   if (enter(dst, v.stream) || enter(src, v.stream)) return 1;
+  if (any_products && !dst->has_window()) {      // an accumulator without a window takes the one its samples were made with
+    ENSCHK(hipMemcpyAsync(dst->x_log.get(), src->x_log.get(), src->x_log_h.size() * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
+    dst->x_log_h = src->x_log_h; dst->win_lo = src->win_lo; dst->win_hi = src->win_hi;
+  }
+  for (int s = 0; s < src->n_slots - 1; ++s) {
+    const long long na = dst->pn[(size_t)s], nb = src->pn[(size_t)s], len = dst->PL.total;
+    if (nb == 0) continue;
+    if (products_reserve(dst, "mcs_ens_merge", s, v.stream)) return 1;
+    if (na == 0) {
+      ENSCHK(hipMemcpyAsync(dst->pmean[(size_t)s], src->pmean[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
+      ENSCHK(hipMemcpyAsync(dst->pm2[(size_t)s], src->pm2[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
+    } else {
+      const double n = (double)(na + nb);
+      hipLaunchKernelGGL(mcs_k_ens_merge, dim3(grid_for(len)), dim3(ENS_THREADS), 0, v.stream, dst->pmean[(size_t)s].get(), dst->pm2[(size_t)s].get(),
+                         src->pmean[(size_t)s].get(), src->pm2[(size_t)s].get(), len, (double)nb / n, (double)na * (double)nb / n);
+      ENSCHK(hipGetLastError());
+    }
+    dst->pn[(size_t)s] = na + nb;
+    dst->products_sampled = true;
+  }
   for (int s = 0; s < dst->n_slots; ++s) {
     const long long na = dst->n[(size_t)s], nb = src->n[(size_t)s], len = dst->len(s);
     if (nb == 0) continue;
@@ -674,22 +864,25 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
 
 int mcs_ens_count(mcs_ens* e, int slot, int64_t* n) {
   if (!e || !n) return fail("mcs_ens_count: null argument");
-  if (slot < 0 || slot >= e->n_slots) return fail("mcs_ens_count: slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
-  *n = e->n[(size_t)slot];
+  SlotRef r;
+  if (slot_ref(e, "mcs_ens_count", slot, &r)) return 1;
+  *n = r.n;
   return 0;
 }
 
 int mcs_ens_read(mcs_ens* e, int slot, int what, int64_t first, int64_t count, double* host) {
   if (!e || (count > 0 && !host)) return fail("mcs_ens_read: null argument");
-  if (slot < 0 || slot >= e->n_slots) return fail("mcs_ens_read: slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  SlotRef r;
+  if (slot_ref(e, "mcs_ens_read", slot, &r)) return 1;
   if (what < 0 || what > 2) return fail("mcs_ens_read: what must be 0 (mean), 1 (M2) or 2 (standard error)");
   if (first < 0 || count < 0 || first + count > e->len(slot)) return fail("mcs_ens_read: range outside the slot's sample vector");
-  const long long n = e->n[(size_t)slot];
+  const long long n = r.n;
+  if (is_products(slot) && n == 0) return fail("mcs_ens_read: the products slot has never taken a sample");
   if (what == 2 && n < 2) return fail("mcs_ens_read: the standard error needs at least two samples; the slot has " + std::to_string(n));
   McsCtxView v;
   if (mcs_ctx_view_get(e->home, &v)) return 1;
   if (enter(e, v.stream)) return 1;
-  const double* from = what == 0 ? e->mean[(size_t)slot].get() : e->m2[(size_t)slot].get();
+  const double* from = what == 0 ? r.mean : r.m2;
   if (count > 0) ENSCHK(hipMemcpyAsync(host, from + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, v.stream));
   ENSCHK(hipStreamSynchronize(v.stream));
   if (what == 2) {
@@ -702,16 +895,17 @@ int mcs_ens_read(mcs_ens* e, int slot, int what, int64_t first, int64_t count, d
 int mcs_ens_summarize(mcs_ens* e, int slot, int n_ranges, const mcs_ens_range* ranges, mcs_ens_summary* out) {
   const std::string who = "mcs_ens_summarize";
   if (!e) return fail(who + ": null argument");
-  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  SlotRef sr;
+  if (slot_ref(e, who, slot, &sr)) return 1;
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges == 0) return 0;
   if (!ranges || !out) return fail(who + ": null argument");
-  const long long n = e->n[(size_t)slot];
+  const long long n = sr.n;
   if (n < 2) return fail(who + ": the standard error needs at least two samples; the slot has " + std::to_string(n));
   long long n_blocks = 0;
   if (check_ranges(who, e->len(slot), n_ranges, ranges, &n_blocks)) return 1;
   mcs_ens* list[1] = {e};
-  return sum_run(who, list, 1, SrcOne{e->mean[(size_t)slot].get(), e->m2[(size_t)slot].get()}, n, n_ranges, ranges, n_blocks, out);
+  return sum_run(who, list, 1, SrcOne{sr.mean, sr.m2}, n, n_ranges, ranges, n_blocks, out);
 }
 
 int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ranges, const mcs_ens_range* ranges, mcs_ens_summary* out,
@@ -732,7 +926,12 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
         a->P.n_grid != b->P.n_grid || a->P.n_ions != b->P.n_ions || a->P.n_itrs != b->P.n_itrs)
       return fail(who + ": the accumulators' slots or layouts differ");
   }
-  if (slot < 0 || slot >= a->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(a->n_slots - 1));
+  SlotRef sr;
+  if (slot_ref(a, who, slot, &sr)) return 1;
+  if (is_products(slot))
+    for (int k = 1; k < n_ens; ++k)
+      for (int j = 0; j < k; ++j)
+        if (windows_differ(ens[j], ens[k])) return fail(who + ": the accumulators' slope windows differ");
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges > 0 && (!ranges || !out)) return fail(who + ": null argument");
   // the accumulators that have samples in this slot, in list order, and the factors of every step of the fold (as mcs_ens_merge)
@@ -743,12 +942,13 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
   int m = 0;
   for (int k = 0; k < n_ens; ++k) {
     list[k] = ens[k];
-    const long long nb = ens[k]->n[(size_t)slot];
+    (void)slot_ref(ens[k], who, slot, &sr);      // (the slot exists in every accumulator: their slots are the same)
+    const long long nb = sr.n;
     if (nb == 0) continue;
     const double nn = (double)(n + nb);
     f_mean[m] = m ? (double)nb / nn : 0.0;
     f_m2[m] = m ? (double)n * (double)nb / nn : 0.0;
-    mean[m] = ens[k]->mean[(size_t)slot].get(); m2[m] = ens[k]->m2[(size_t)slot].get();
+    mean[m] = sr.mean; m2[m] = sr.m2;
     n += nb; ++m;
   }
   if (n < 2) return fail(who + ": the standard error needs at least two samples; the slot has " + std::to_string(n) + " over the list");

@@ -577,6 +577,15 @@ def _check_trigger_args(have_ensemble, pass_what, min_iterations, check_every):
         raise ValueError(f"triggers: check_every {check_every} < 1")
 
 
+def _add_products(ensemble, prob, backend, ion_fin):
+    """The products sample of the iteration whose last species' ion_finalize has just run on `backend` (ensemble.py, "Products"):
+    slot n_species - 1, from what the consumers left on the device (a HIP backend) or from ion_fin (the numpy ensemble).  An ensemble
+    without a slope window first gets one over all bins."""
+    if not ensemble.has_slope_window():
+        ensemble.set_slope_window(0, prob.params.num_psd_mom_bins + 1, ens.bin_centres_log10(prob))
+    ensemble.add_products(backend, len(prob.cfg.species) - 1, ion_fin)
+
+
 def _check_triggers(ensemble, triggers, others=()):
     """One summary per slot that has triggers -> [TriggerCheck] in the order of `triggers`.  others: further ensembles, of the other
     contexts of an overlapped run; the summary is then that of `ensemble` merged with them in that order (Ensemble.summarize_merged)."""
@@ -691,7 +700,12 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     species end of a run that knew its length; on_species_end has seen that species end without the histograms).
     RunResult.convergence holds the checks, stopped_at and satisfied; predicted_samples in a check is a report, nothing acts on it.
     Refused: triggers without ensemble, min_iterations < 2 (no error bar below two samples), check_every < 1, a trigger whose slot or
-    part the ensemble does not have.  None or []: no check, RunResult.convergence is None.
+    part the ensemble does not have, a trigger on a products slot without finalize.  None or []: no check, RunResult.convergence is None.
+    With finalize and ensemble, the ensemble also takes one PRODUCTS sample per iteration, right after the last species' ion_finalize,
+    into the products slot of species slot n_species - 1 (ensemble.py, "Products": dN/dp in the three frames, pressures, energy
+    density, spectral slope; Ensemble.products_slot).  An ensemble without a slope window first gets one over all bins; set a
+    narrower one before the run (Ensemble.set_slope_window, ensemble.slope_window).  Triggers may name its parts, with
+    bins=(l_lo, l_hi) for a momentum window of one zone.
     """
     import torch
     comm = comm or Comm(False)
@@ -757,6 +771,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             if getattr(be, "device", None) != getattr(backend, "device", None):
                 raise ValueError("species_backends: every context must be on the primary's device")
     finalize = finalize or smoothing is not None
+    if not finalize and any(ens.Ensemble.is_products(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on a products slot needs finalize=True (ion_finalize makes the products; no sample would ever arrive)")
     it_state = None
     if finalize:
         sm = smoothing if smoothing is not None else itf.SmoothingConfig(smooth_shocks=False)
@@ -782,6 +798,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             changed = False
             if rs.is_root:
                 ion_fin = consumers.ion_finalize(prob, backend, len(cfg.species))
+                if ensemble is not None:
+                    _add_products(ensemble, prob, backend, ion_fin)
                 fin = itf.iter_finalize(prob, it_state, sm, i_iter, rs.G_f, L, ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
                 rs.iter_finals.append((i_iter, fin, ion_fin))
                 changed = fin.profile_changed
@@ -877,7 +895,9 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     ensemble: True -- every context feeds an ensemble of its own (ensemble.Ensemble.for_backend; run(ensemble=...)); at the end they
     are merged in context order into the first context's, which RunResult.ensemble hands back: per-cell mean and standard error of
     the tallies over the iterations.  Its finalize_mean / finalize_stderr / finalize_count are the same statistics, on the host, of
-    the per-iteration ion_finalize of the last species (ensemble.FINALIZE_NAMES), in iteration order."""
+    the per-iteration ion_finalize of the last species (ensemble.FINALIZE_NAMES), in iteration order.  Every context's ensemble also
+    takes the products sample of run(finalize=True, ensemble=...) right after that ion_finalize, inside the iteration's job, so that
+    triggers on a products slot work through the rounds and the merged summary like any other."""
     cfg, P = prob.cfg, prob.params
     n_itrs = n_itrs if n_itrs is not None else cfg.num_iterations
     K = len(backends)
@@ -923,6 +943,8 @@ def _overlapped_rounds(prob, backends, enss, n_itrs, max_pcuts, on_iteration_end
                 res = run(prob, be, None, n_itrs=1, max_pcuts=max_pcuts, first_iter=i_iter, species_tallies="light", final_full_read=False,
                           before_pcut=geometry, long_draws=0, ensemble=enss[k])
                 ion_fin = consumers.ion_finalize(prob, be, len(cfg.species))     # K4, before the context is reused
+                if enss[k] is not None:
+                    _add_products(enss[k], prob, be, ion_fin)
         return k, res, ion_fin
 
     stats, per_species, iter_finals, local_steps = [], [], [], []

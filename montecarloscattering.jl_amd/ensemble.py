@@ -31,6 +31,26 @@ merge without forming it: per word the left fold of the merge above over the acc
 the definition above on the merged words with the total count (mcs_ens_summarize_merged of include/mcs.h; on the device each word's
 fold is made in registers, no accumulator is changed, no scratch accumulator exists).
 
+Products (include/mcs.h, "products sample"): what a run publishes -- the normalised dN/dp in the three frames, the pressures and the
+energy density of ion_finalize, the spectral slope -- is non-linear in the tallies, so its error bars cannot be had from the per-cell
+ones; it is sampled once per iteration.  Every species slot s has a companion products slot, `Ensemble.products_slot(s)`, whose two
+vectors exist from its first sample on:
+
+  dNdp_sf, dNdp_pf, dNdp_isf                  [n_grid][nmom+2]: frames 0, 1, 2 of ion_finalize's dNdp_cr
+  P_psd_par, P_psd_perp, energy_density_psd   [n_grid]
+  slope_sf, slope_pf, slope_isf               [n_grid]: the least-squares slope of log10 dN/dp against log10 p (cgs) over the bins
+      l_lo <= l < l_hi of the slope window (`set_slope_window`, `slope_window`).  A bin is valid if dN/dp > 1e-99, the consumers'
+      floor of an empty bin; with the k valid bins in ascending order, every operation a separate rounding, serial sums:
+      xbar = (sum x) / k, ybar = (sum y) / k, Sxx = sum (x - xbar)^2, Sxy = sum (x - xbar)(y - ybar), slope = Sxy / Sxx, where
+      y = log10(dN/dp) by the deterministic log10 of include/mcs_math.h.  k < 3 gives NaN: the word stays non-finite, a summary
+      counts it in n_nonfinite and a trigger over it is never met -- a slope trigger belongs on zones that the accelerated
+      population reaches.  It is the slope of dN/dp, about -2.2 behind a strong shock, not the index of f(p).
+
+A summary range can be restricted in momentum: `Request` / `Trigger(bins=(l_lo, l_hi))` together with a single zone, zones=(z, z+1),
+on a part of shape [zone][bins] (the three dNdp_* and the six marginals) is the word range off + z * per + l_lo of l_hi - l_lo
+words.  dN/dp spans a dozen decades: without it the floor_frac selection keeps the thermal peak and drops the tail.  Several zones
+are several requests (MAX_RANGES in one summary).
+
 `HipEnsemble` keeps the vectors on the device and updates them with the kernels of csrc/mcs_ensemble.hip: the 22 MB histograms
 never cross to the host (it costs device memory: two vectors of the sample length per slot, about twice the tally buffer per
 species slot).  `HostEnsemble` does the same arithmetic in numpy, in the same order, on read_tallies() buffers: it lets the driver
@@ -65,6 +85,15 @@ MAX_RANGES = 256          # of one mcs_ens_summarize call
 MAX_MERGED = 8            # accumulators of one mcs_ens_summarize_merged call (MCS_ENS_MAX_MERGED)
 # what run_overlapped(ensemble=True) adds from the per-iteration ion_finalize of the last species
 FINALIZE_NAMES = ("dNdp_cr", "P_psd_par", "P_psd_perp", "energy_density_psd")
+# the parts of a products slot, in the order of mcs_ens_products_layout; all have the zone as first axis
+PRODUCT_DNDP = ("dNdp_sf", "dNdp_pf", "dNdp_isf")
+PRODUCT_SLOPES = ("slope_sf", "slope_pf", "slope_isf")
+PRODUCT_NAMES = PRODUCT_DNDP + ("P_psd_par", "P_psd_perp", "energy_density_psd") + PRODUCT_SLOPES
+ZONE_PARTS = ZONE_PARTS + PRODUCT_NAMES
+# the parts of shape [zone][bins]: a bins=(l_lo, l_hi) window of one zone of them is a contiguous word range
+BIN_PARTS = PRODUCT_DNDP + MARGINALS
+PRODUCTS_BIT = capi.ENS_PRODUCTS_BIT      # products slot of species slot s: s | PRODUCTS_BIT (MCS_ENS_PRODUCTS)
+DNDP_FLOOR = 1.0e-99                      # the consumers' floor: a bin at or below it is empty
 
 
 class EnsLayout:
@@ -97,6 +126,16 @@ class EnsLayout:
         self.fields.update(sp_total=w, it_sums=0, it_sums_n=n_sums, it_scalars=n_sums, it_scalars_n=L.total - o["scalars"],
                            it_total=self.iteration_total, tally_sp_first=o["psd"], tally_it_first=o["esc_flux"],
                            tally_recv_pool=o["energy_recv_pool"], tally_scalars=o["scalars"])
+        # the products sample: mirror of `mcs_ens_products_get_layout`
+        self.products: Dict[str, Tuple[int, tuple]] = {}
+        w = 0
+        for name in PRODUCT_NAMES:
+            shape = (ng, nm) if name in PRODUCT_DNDP else (ng,)
+            self.products[name] = (w, shape)
+            w += int(np.prod(shape))
+        self.products_total = w
+        self.products_fields = {name: off for name, (off, _) in self.products.items()}
+        self.products_fields.update(dNdp_n=ng * nm, zone_n=ng, total=w)
 
     def species_sample(self, f: np.ndarray, i: np.ndarray) -> np.ndarray:
         """The species sample of the tally buffers (f, i).  The marginals are serial sums in ascending index order, one index
@@ -152,10 +191,19 @@ def stats_over(samples):
     return mean, err, n
 
 
-def _check_part(name: str, zones):
-    """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis."""
-    if name not in SPECIES_NAMES + ITERATION_NAMES:
-        raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}")
+def _check_part(name: str, zones, bins=None):
+    """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis, a bins
+    window is a pair, comes with a single zone and the part has a bins axis."""
+    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES:
+        raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}; "
+                         f"a products slot: {', '.join(PRODUCT_NAMES)}")
+    if bins is not None:
+        if name not in BIN_PARTS:
+            raise ValueError(f"ensemble: {name!r} has no [zone][bins] shape; a bins window fits: {', '.join(BIN_PARTS)}")
+        if len(bins) != 2 or int(bins[0]) != bins[0] or int(bins[1]) != bins[1]:
+            raise ValueError(f"ensemble: a bins window is a pair (l_lo, l_hi) of integers, not {bins!r}")
+        if zones is None or len(zones) != 2 or zones[1] != zones[0] + 1:
+            raise ValueError(f"ensemble: a bins window needs a single zone, zones=(z, z + 1), not zones={zones!r}; several zones are several requests")
     if zones is not None:
         if name not in ZONE_PARTS:
             raise ValueError(f"ensemble: {name!r} has no zone axis; a zone slice fits: {', '.join(ZONE_PARTS)}")
@@ -165,14 +213,16 @@ def _check_part(name: str, zones):
 
 @dataclasses.dataclass(frozen=True)
 class Request:
-    """One range of a summary: a named part of a slot, or its zones [z_lo, z_hi) where the part's first axis is the zone index."""
+    """One range of a summary: a named part of a slot, or its zones [z_lo, z_hi) where the part's first axis is the zone index, or
+    the bins [l_lo, l_hi) of one zone (zones=(z, z + 1)) of a part of shape [zone][bins]."""
     name: str
     zones: Optional[Tuple[int, int]] = None
     floor_frac: float = 1e-3
     tol: float = 0.0
+    bins: Optional[Tuple[int, int]] = None
 
     def __post_init__(self):
-        _check_part(self.name, self.zones)
+        _check_part(self.name, self.zones, self.bins)
         if not 0.0 <= self.floor_frac <= 1.0:
             raise ValueError(f"ensemble: floor_frac {self.floor_frac!r} outside [0, 1]")
         if not self.tol >= 0.0:
@@ -218,14 +268,16 @@ class Trigger:
       "weighted"       sum_se / sum_abs_mean
       "fraction_over"  n_over / n_selected: the share of the selected words whose relative error exceeds tol
     Selected: the words of at least floor_frac times the part's largest |mean| (module docstring).  zones = (z_lo, z_hi): those zones
-    of a part whose first axis is the zone index.  Never met while the slot has fewer than two samples, nothing is selected or a
+    of a part whose first axis is the zone index; bins = (l_lo, l_hi): those bins of the single zone zones = (z, z + 1) of a part of
+    shape [zone][bins] (the dNdp_* parts of a products slot, the marginals).  Never met while the slot has fewer than two samples, nothing is selected or a
     word of the range is not finite.  predicted_samples: for the three error statistics, the count at which the value would reach the
     threshold if it goes on falling as 1 / sqrt(n): ceil(n (value / threshold)^2); a report, nothing acts on it.
     Refused here: an unknown statistic, threshold <= 0, "fraction_over" without tol, a negative slot, a name no slot has, a zone
-    slice on a part without a zone axis.  Whether `slot` is a species slot or the iteration slot only an ensemble knows:
+    slice on a part without a zone axis, bins without a single zone or on a part without a bins axis.  Whether `slot` is a species slot or the iteration slot only an ensemble knows:
     Ensemble.check_trigger, which driver.run calls before the first iteration, refuses a name the slot does not have."""
 
-    def __init__(self, slot: int, name: str, statistic: str, threshold: float, zones=None, floor_frac: float = 1e-3, tol: Optional[float] = None):
+    def __init__(self, slot: int, name: str, statistic: str, threshold: float, zones=None, floor_frac: float = 1e-3, tol: Optional[float] = None,
+                 bins=None):
         if statistic not in STATISTICS:
             raise ValueError(f"trigger: unknown statistic {statistic!r}; there are: {', '.join(STATISTICS)}")
         if not threshold > 0:
@@ -234,13 +286,14 @@ class Trigger:
             raise ValueError("trigger: 'fraction_over' needs tol, the relative error a word may have")
         if int(slot) != slot or slot < 0:
             raise ValueError(f"trigger: slot {slot!r} is no slot")
-        self.request = Request(name, None if zones is None else (int(zones[0]), int(zones[1])), float(floor_frac), 0.0 if tol is None else float(tol))
+        self.request = Request(name, None if zones is None else (int(zones[0]), int(zones[1])), float(floor_frac), 0.0 if tol is None else float(tol),
+                               None if bins is None else (int(bins[0]), int(bins[1])))
         self.slot, self.name, self.statistic, self.threshold = int(slot), name, statistic, float(threshold)
-        self.zones, self.floor_frac, self.tol = self.request.zones, self.request.floor_frac, tol
+        self.zones, self.floor_frac, self.tol, self.bins = self.request.zones, self.request.floor_frac, tol, self.request.bins
 
     def __repr__(self):
         return (f"Trigger(slot={self.slot}, name={self.name!r}, statistic={self.statistic!r}, threshold={self.threshold!r}, zones={self.zones!r}, "
-                f"floor_frac={self.floor_frac!r}, tol={self.tol!r})")
+                f"floor_frac={self.floor_frac!r}, tol={self.tol!r}, bins={self.bins!r})")
 
     def value(self, s: Summary) -> float:
         """The statistic of a summary; nan where it has none (fewer than two samples, nothing selected)."""
@@ -265,6 +318,69 @@ class Trigger:
         return int(math.ceil(s.n * (v / self.threshold) ** 2))
 
 
+def bin_centres_log10(prob) -> np.ndarray:
+    """x_log [nmom+1] of `Ensemble.set_slope_window`: log10 of every momentum bin's centre in cgs, the centre 0.5 (b[l] + b[l + 1])
+    of prob.psd_mom_bounds (log10 of p / m_p c) brought to cgs as consumers.consumer_tables does (pt_center)."""
+    from .constants import C, MP
+    mb = np.asarray(prob.psd_mom_bounds, dtype=np.float64)
+    return np.ascontiguousarray(np.log10(10.0 ** (0.5 * (mb[:-1] + mb[1:])) * (MP * C)))
+
+
+def slope_window(prob, p_lo: float, p_hi: float):
+    """(l_lo, l_hi, x_log), the arguments of `Ensemble.set_slope_window`, from the problem's momentum bins and two momenta in cgs:
+    x_log[l] = log10 of the centre of bin l in cgs, the centre 0.5 (b[l] + b[l + 1]) of prob.psd_mom_bounds brought to cgs as
+    consumers.consumer_tables does (pt_center), and the window the bins whose centre lies in [p_lo, p_hi]."""
+    x_log = bin_centres_log10(prob)
+    if not 0 < p_lo < p_hi:
+        raise ValueError(f"ensemble: slope window needs momenta 0 < p_lo < p_hi, not {p_lo!r}, {p_hi!r}")
+    inside = np.flatnonzero((x_log >= math.log10(p_lo)) & (x_log <= math.log10(p_hi)))
+    if inside.size < 3:
+        raise ValueError(f"ensemble: fewer than three momentum bins have their centre in [{p_lo!r}, {p_hi!r}]")
+    return int(inside[0]), int(inside[-1]) + 1, x_log
+
+
+def _det_log10(backend):
+    """The deterministic log10 of include/mcs_math.h as the backend evaluates it: a -> log10(a), elementwise."""
+    if hasattr(backend, "eval_fn"):
+        return lambda a: backend.eval_fn("log10", a)
+    lib = getattr(backend, "lib", None)
+    if lib is not None and hasattr(lib, "orc_eval_fn"):
+        def log10(a):
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            out = np.zeros_like(a)
+            if lib.orc_eval_fn(capi.FN["log10"], a.size, a.ctypes.data_as(capi.c_double_p), a.ctypes.data_as(capi.c_double_p),
+                               out.ctypes.data_as(capi.c_double_p)) != 0:
+                raise RuntimeError("ensemble: the backend's log10 failed")
+            return out
+        return log10
+    raise ValueError("ensemble: the backend evaluates no deterministic log10 (eval_fn); a products sample needs it for the slopes")
+
+
+def slopes_of(dndp: np.ndarray, l_lo: int, l_hi: int, x_log: np.ndarray, log10) -> np.ndarray:
+    """The slope definition of the module docstring for every row of dndp [...][nmom+2] -> [...]: the rows side by side in numpy,
+    the bins of a row one after the other, so that every sum is the serial one."""
+    d = np.asarray(dndp, dtype=np.float64)
+    rows = d.reshape(-1, d.shape[-1])[:, l_lo:l_hi]
+    valid = rows > DNDP_FLOOR
+    y = np.zeros_like(rows)
+    y[valid] = log10(np.ascontiguousarray(rows[valid]))
+    x = np.asarray(x_log, dtype=np.float64)[l_lo:l_hi]
+    k = valid.sum(axis=1).astype(np.float64)
+    sx, sy = np.zeros(len(rows)), np.zeros(len(rows))
+    for l in range(rows.shape[1]):
+        sx = np.where(valid[:, l], sx + x[l], sx)
+        sy = np.where(valid[:, l], sy + y[:, l], sy)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        xbar, ybar = sx / k, sy / k
+        sxx, sxy = np.zeros(len(rows)), np.zeros(len(rows))
+        for l in range(rows.shape[1]):
+            dx = x[l] - xbar
+            sxx = np.where(valid[:, l], sxx + dx * dx, sxx)
+            sxy = np.where(valid[:, l], sxy + dx * (y[:, l] - ybar), sxy)
+        slope = np.where(k >= 3, sxy / sxx, np.nan)
+    return slope.reshape(d.shape[:-1])
+
+
 class Ensemble:
     """What both kinds have in common: the slots, the named views of a slot's vectors."""
 
@@ -276,6 +392,7 @@ class Ensemble:
         self.finalize_mean: Dict[str, np.ndarray] = {}
         self.finalize_stderr: Dict[str, np.ndarray] = {}
         self.finalize_count = 0
+        self.window = None             # (l_lo, l_hi, x_log) of set_slope_window
 
     @staticmethod
     def for_backend(backend, n_species: int) -> "Ensemble":
@@ -284,19 +401,43 @@ class Ensemble:
             return HipEnsemble(backend, n_species)
         return HostEnsemble(backend.P, n_species)
 
+    def products_slot(self, s: int) -> int:
+        """The slot number of the products of species slot s (MCS_ENS_PRODUCTS)."""
+        if not 0 <= s < self.n_species:
+            raise ValueError(f"ensemble: slot {s} is no species slot (0..{self.n_species - 1}); only a species slot has a products slot")
+        return int(s) | PRODUCTS_BIT
+
+    @staticmethod
+    def is_products(slot: int) -> bool:
+        return slot >= 0 and bool(slot & PRODUCTS_BIT)
+
     def names(self, slot: int):
         self._check_slot(slot)
+        if self.is_products(slot):
+            return PRODUCT_NAMES
         return ITERATION_NAMES if slot == self.iteration_slot else SPECIES_NAMES
 
     def _check_slot(self, slot: int):
-        if not 0 <= slot <= self.n_species:
+        if self.is_products(slot):
+            if not 0 <= slot ^ PRODUCTS_BIT < self.n_species:
+                raise ValueError(f"ensemble: products slot of slot {slot ^ PRODUCTS_BIT}, which is no species slot (0..{self.n_species - 1})")
+        elif not 0 <= slot <= self.n_species:
             raise ValueError(f"ensemble: slot {slot} outside 0..{self.n_species}")
+
+    def _len(self, slot: int) -> int:
+        if self.is_products(slot):
+            return self.layout.products_total
+        return self.layout.iteration_total if slot == self.iteration_slot else self.layout.species_total
 
     def _where(self, slot: int, name: str):
         self._check_slot(slot)
-        table = self.layout.iteration if slot == self.iteration_slot else self.layout.species
+        if self.is_products(slot):
+            table, kind = self.layout.products, f"the products slot of species slot {slot ^ PRODUCTS_BIT}"
+        elif slot == self.iteration_slot:
+            table, kind = self.layout.iteration, "the iteration slot"
+        else:
+            table, kind = self.layout.species, f"species slot {slot}"
         if name not in self.names(slot):
-            kind = "the iteration slot" if slot == self.iteration_slot else f"species slot {slot}"
             raise KeyError(f"ensemble: {kind} has no {name!r}; it has: {', '.join(self.names(slot))}")
         return table[name]
 
@@ -315,10 +456,11 @@ class Ensemble:
         """The standard error of the mean, sqrt(M2 / (n (n - 1))); refused below two samples."""
         return self._named(slot, 2, name)
 
-    def word_range(self, slot: int, name: str, zones=None) -> Tuple[int, int]:
-        """(first, count) of a part of the slot's sample vector, or of its zones [z_lo, z_hi)."""
+    def word_range(self, slot: int, name: str, zones=None, bins=None) -> Tuple[int, int]:
+        """(first, count) of a part of the slot's sample vector, of its zones [z_lo, z_hi), or of the bins [l_lo, l_hi) of its one
+        zone zones = (z, z + 1)."""
         off, shape = self._where(slot, name)
-        _check_part(name, zones)
+        _check_part(name, zones, bins)
         n = int(np.prod(shape))
         if zones is None:
             return off, n
@@ -326,7 +468,12 @@ class Ensemble:
         if not 0 <= z_lo <= z_hi <= shape[0]:
             raise ValueError(f"ensemble: zones ({z_lo}, {z_hi}) outside 0..{shape[0]} of {name!r}")
         per = n // shape[0]
-        return off + z_lo * per, (z_hi - z_lo) * per
+        if bins is None:
+            return off + z_lo * per, (z_hi - z_lo) * per
+        l_lo, l_hi = int(bins[0]), int(bins[1])
+        if not 0 <= l_lo <= l_hi <= per:
+            raise ValueError(f"ensemble: bins ({l_lo}, {l_hi}) outside 0..{per} of {name!r}")
+        return off + z_lo * per + l_lo, l_hi - l_lo
 
     def summarize(self, slot: int, requests: Sequence[Request]) -> List[Summary]:
         """One Summary per request (at most MAX_RANGES; they may overlap), in one pass over the slot: on the device one
@@ -335,7 +482,7 @@ class Ensemble:
         self._check_slot(slot)
         if len(requests) > MAX_RANGES:
             raise ValueError(f"ensemble: {len(requests)} requests in one summary; at most {MAX_RANGES}")
-        ranges = [self.word_range(slot, q.name, q.zones) + (float(q.floor_frac), float(q.tol)) for q in requests]
+        ranges = [self.word_range(slot, q.name, q.zones, q.bins) + (float(q.floor_frac), float(q.tol)) for q in requests]
         n = self.count(slot)
         if n < 2:
             raise ValueError(f"ensemble: a summary needs at least two samples; slot {slot} has {n}")
@@ -353,7 +500,7 @@ class Ensemble:
         self._check_merged(others)
         if len(requests) > MAX_RANGES:
             raise ValueError(f"ensemble: {len(requests)} requests in one summary; at most {MAX_RANGES}")
-        ranges = [self.word_range(slot, q.name, q.zones) + (float(q.floor_frac), float(q.tol)) for q in requests]
+        ranges = [self.word_range(slot, q.name, q.zones, q.bins) + (float(q.floor_frac), float(q.tol)) for q in requests]
         n = self.count(slot) + sum(o.count(slot) for o in others)
         if n < 2:
             raise ValueError(f"ensemble: a summary needs at least two samples; slot {slot} has {n} over the {1 + len(others)} ensembles")
@@ -369,8 +516,26 @@ class Ensemble:
                 raise ValueError("ensemble: a merged summary needs ensembles of the same kind, slots and layout")
 
     def check_trigger(self, trigger: Trigger):
-        """Refuses a trigger whose slot this ensemble does not have, or whose part (or zone slice) that slot does not have."""
-        self.word_range(trigger.slot, trigger.name, trigger.zones)
+        """Refuses a trigger whose slot this ensemble does not have, or whose part (or zone slice, or bins window) that slot does
+        not have."""
+        self.word_range(trigger.slot, trigger.name, trigger.zones, trigger.bins)
+
+    def set_slope_window(self, l_lo: int, l_hi: int, x_log):
+        """The bins l_lo <= l < l_hi over which the slopes of a products sample are fitted, and x_log [nmom+1], the log10 of every
+        momentum bin's centre (`slope_window` builds both).  Before the first products sample; refused afterwards."""
+        nx = self.layout.tally.shapes["psd"][2] - 1
+        x_log = np.ascontiguousarray(x_log, dtype=np.float64)
+        if x_log.shape != (nx,):
+            raise ValueError(f"ensemble: x_log has shape {x_log.shape}; it holds the {nx} bin centres")
+        if int(l_lo) != l_lo or int(l_hi) != l_hi or not (0 <= l_lo and l_hi <= nx and l_hi - l_lo >= 3):
+            raise ValueError(f"ensemble: slope window ({l_lo}, {l_hi}) needs 0 <= l_lo, l_hi <= {nx} and at least three bins")
+        if not np.all(np.isfinite(x_log)):
+            raise ValueError("ensemble: x_log is not finite")
+        self._set_slope_window(int(l_lo), int(l_hi), x_log)
+        self.window = (int(l_lo), int(l_hi), x_log.copy())
+
+    def has_slope_window(self) -> bool:
+        return self.window is not None
 
     def destroy(self):
         pass
@@ -386,6 +551,46 @@ class HostEnsemble(Ensemble):
         self._m2 = [np.zeros(n) for n in lens]
         self._n = [0] * len(lens)
         self._snapshot = None          # (backend, words [esc_flux, energy_recv_pool))
+        # the products slots: species slot -> vector, from the first sample on
+        self._pmean: Dict[int, np.ndarray] = {}
+        self._pm2: Dict[int, np.ndarray] = {}
+        self._pn = [0] * self.n_species
+
+    def _vectors(self, slot: int):
+        """(mean, M2, n) of a slot; (None, None, 0) for a products slot that was never sampled."""
+        if self.is_products(slot):
+            s = slot ^ PRODUCTS_BIT
+            return self._pmean.get(s), self._pm2.get(s), self._pn[s]
+        return self._mean[slot], self._m2[slot], self._n[slot]
+
+    def _set_slope_window(self, l_lo, l_hi, x_log):
+        if any(self._pn):
+            raise ValueError("ensemble: a products slot has taken a sample; the slope window stays as it is")
+
+    def add_products(self, backend, slot: int, ion_final):
+        """One products sample of species slot `slot` from an `IonFinal` (consumers.ion_finalize on `backend`), the slopes by the
+        backend's deterministic log10."""
+        self._check_slot(slot)
+        if self.is_products(slot) or slot == self.iteration_slot:
+            raise ValueError(f"ensemble: slot {slot} is no species slot; only a species slot has a products slot")
+        if self.window is None:
+            raise ValueError("ensemble: no slope window (set_slope_window)")
+        l_lo, l_hi, x_log = self.window
+        dndp = np.asarray(ion_final.dNdp_cr, dtype=np.float64)
+        x = np.concatenate([dndp.ravel(), np.asarray(ion_final.P_psd_par, dtype=np.float64), np.asarray(ion_final.P_psd_perp, dtype=np.float64),
+                            np.asarray(ion_final.energy_density_psd, dtype=np.float64), slopes_of(dndp, l_lo, l_hi, x_log, _det_log10(backend)).ravel()])
+        if x.size != self.layout.products_total:
+            raise ValueError(f"ensemble: the IonFinal holds {x.size} words; a products sample has {self.layout.products_total}")
+        if slot not in self._pmean:
+            self._pmean[slot], self._pm2[slot] = np.zeros(x.size), np.zeros(x.size)
+        with np.errstate(invalid="ignore"):          # (a NaN slope stays NaN)
+            self._pn[slot] = welford_update(self._pmean[slot], self._pm2[slot], self._pn[slot], x)
+
+    @staticmethod
+    def _windows_differ(a, b) -> bool:
+        if a.window is None or b.window is None:
+            return False
+        return a.window[:2] != b.window[:2] or not np.array_equal(a.window[2].view(np.uint64), b.window[2].view(np.uint64))
 
     def begin_iteration(self, backend):
         o = self.layout.tally.offsets
@@ -412,6 +617,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: merge of an ensemble into itself")
         if not isinstance(other, HostEnsemble) or other.n_species != self.n_species or other.layout.fields != self.layout.fields:
             raise ValueError("ensemble: merge needs an ensemble of the same kind, slots and layout")
+        if self._windows_differ(self, other):
+            raise ValueError("ensemble: merge of ensembles whose slope windows differ")
         for s in range(self.n_species + 1):
             na, nb = self._n[s], other._n[s]
             if nb == 0:
@@ -425,32 +632,53 @@ class HostEnsemble(Ensemble):
                 self._mean[s][...] = self._mean[s] + d * (float(nb) / n)
                 self._m2[s][...] = (self._m2[s] + other._m2[s]) + (d * d) * (float(na) * float(nb) / n)
             self._n[s] = na + nb
+        if any(other._pn) and self.window is None:      # an ensemble without a window takes the one its samples were made with
+            self.window = other.window
+        for s in range(self.n_species):
+            na, nb = self._pn[s], other._pn[s]
+            if nb == 0:
+                continue
+            if na == 0:
+                self._pmean[s], self._pm2[s] = other._pmean[s].copy(), other._pm2[s].copy()
+            else:
+                n = float(na + nb)
+                with np.errstate(invalid="ignore"):
+                    d = other._pmean[s] - self._pmean[s]
+                    self._pmean[s] = self._pmean[s] + d * (float(nb) / n)
+                    self._pm2[s] = (self._pm2[s] + other._pm2[s]) + (d * d) * (float(na) * float(nb) / n)
+            self._pn[s] = na + nb
 
     def count(self, slot: int) -> int:
         self._check_slot(slot)
-        return self._n[slot]
+        return self._vectors(slot)[2]
 
     def _read(self, slot, what, first, count):
+        mean, m2, n = self._vectors(slot)
+        if mean is None:
+            raise ValueError(f"ensemble: the products slot of species slot {slot ^ PRODUCTS_BIT} has never taken a sample")
         if what == 2:
-            n = self._n[slot]
             if n < 2:
                 raise ValueError(f"ensemble: the standard error needs at least two samples; slot {slot} has {n}")
-            return np.sqrt(self._m2[slot][first:first + count] / (float(n) * float(n - 1)))
-        return (self._mean if what == 0 else self._m2)[slot][first:first + count].copy()
+            with np.errstate(invalid="ignore"):
+                return np.sqrt(m2[first:first + count] / (float(n) * float(n - 1)))
+        return (mean if what == 0 else m2)[first:first + count].copy()
 
     def _summarize(self, slot, n, ranges):
-        mean, m2 = self._mean[slot], self._m2[slot]
+        mean, m2, _ = self._vectors(slot)
         return [summary_of(mean[first:first + count], m2[first:first + count], n, floor_frac, tol) for first, count, floor_frac, tol in ranges]
 
     def _summarize_merged(self, others, slot, n, ranges):
         out = []
+        es = [self] + others
+        if self.is_products(slot) and any(self._windows_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
+            raise ValueError("ensemble: a merged summary of ensembles whose slope windows differ")
         for first, count, floor_frac, tol in ranges:
             m, q, na = None, None, 0
             for e in [self] + others:
-                nb = e._n[slot]
+                mean_e, m2_e, nb = e._vectors(slot)
                 if nb == 0:
                     continue
-                mb, qb = e._mean[slot][first:first + count], e._m2[slot][first:first + count]
+                mb, qb = mean_e[first:first + count], m2_e[first:first + count]
                 if na == 0:
                     m, q = mb, qb
                 else:
@@ -507,10 +735,20 @@ class HipEnsemble(Ensemble):
     def add_iteration(self, backend: HipBackend):
         self._chk(self.lib.mcs_ens_add_iteration(self.h, backend.h))
 
+    def _set_slope_window(self, l_lo, l_hi, x_log):
+        self._chk(self.lib.mcs_ens_set_slope_window(self.h, l_lo, l_hi, x_log.ctypes.data_as(capi.c_double_p)))
+
+    def add_products(self, backend: HipBackend, slot: int, ion_final=None):
+        """One products sample of species slot `slot` from what mcs_dndp_cr and mcs_thermo_calcs (consumers.ion_finalize) left on
+        the backend's device (mcs_ens_add_products); nothing crosses to the host, ion_final is not read."""
+        self._chk(self.lib.mcs_ens_add_products(self.h, backend.h, int(slot)))
+
     def merge(self, other: "HipEnsemble"):
         if not isinstance(other, HipEnsemble):
             raise ValueError("ensemble: merge needs an ensemble of the same kind, slots and layout")
         self._chk(self.lib.mcs_ens_merge(self.h, other.h))
+        if self.window is None and other.window is not None and any(other.count(other.products_slot(s)) for s in range(other.n_species)):
+            self.window = other.window      # (as the library does: an accumulator without a window takes the one its samples were made with)
 
     def count(self, slot: int) -> int:
         n = ct.c_int64(0)
