@@ -101,6 +101,18 @@ def dndp_2d_numpy(prob, t, T, I, L, gam_x, beta_x):
     return out, weights
 
 
+def own_size_excess_2d(P, tallies_f64, got, want):
+    """The per-cell criterion beside the max-normalised one: largest |got - want| / bound over the lit cells, each cell against its
+    OWN value.  A cell of get_dNdp_2D's array is a sum of positive addends, n_c <= N_z of them (N_z: the zone's lit psd and therm_sf
+    cells), each normalised by a density that is a sum of N_z cells: either side is within (n_c + N_z + 10) 2^-53 of the exact value
+    (consumers_common.dndp_2d_reference), the two within 2 (2 N_z + 10) 2^-53 of each other."""
+    import consumers_common as cc
+    n_z = cc.lit_cells_per_zone(mcs.capi.Layout(P), tallies_f64, ("psd", "therm_sf"))
+    r = cc.own_size_excess(got, want, (2 * n_z + 10)[:, None, None])
+    print("dndp_2d per cell: worst |a - b| / bound =", r)
+    return r
+
+
 @pytest.mark.parametrize("which", ["protons", "electrons"])
 def test_dndp_2d_matches_independent_numpy(prun, erun, which):
     prob, be, res = prun if which == "protons" else erun
@@ -116,6 +128,7 @@ def test_dndp_2d_matches_independent_numpy(prun, erun, which):
     assert got.shape == want.shape and want.max() > 1e-60
     assert relerr(got, want) < 1e-12
     assert np.array_equal(got > 1e-90, want > 1e-90)
+    assert own_size_excess_2d(P, T, got, want) <= 1.0
     # the rebin conserves the cell weights: sum of ef * dp over a zone == sum of the normalised shock-frame cells * dp
     dp = np.diff(t.mom_edge_cgs)
     back = ((got[:, :, :P.num_psd_mom_bins + 1] - 1e-99) * dp[None, None, :]).sum(axis=(1, 2))
@@ -269,6 +282,7 @@ def test_gpu_ic_matches_cpu_twin():
             assert d_o.max() > 1e-60
             assert relerr(d_g, d_o) < 1e-11
             assert np.array_equal(d_g > 1e-90, d_o > 1e-90)
+            assert own_size_excess_2d(P, res.tallies_f64, d_g, d_o) <= 1.0
     be.destroy(); hb.destroy()
     # electrons (the species the reference calls it for), and the fold over the result
     prob, be, res = electron_run(1500)
@@ -285,6 +299,7 @@ def test_gpu_ic_matches_cpu_twin():
             assert d_o.max() > 1e-60 or not hist
             assert relerr(d_g, d_o) < 1e-11
             assert np.array_equal(d_g > 1e-90, d_o > 1e-90)
+            assert own_size_excess_2d(P, res.tallies_f64, d_g, d_o) <= 1.0
         area = 4 * math.pi * (3.0e24) ** 2 * 0.03
         for j_max, n_photon, emin, bpd in ((P.num_psd_tht_bins, 140, 1e-2, 10), (P.num_psd_tht_bins // 2, 40, 1e-6, 4)):
             Eo, o = be.photon_ic(t.mom_edge_cgs, t.mc, j_max, alpha_in, n_in, n_photon, emin, bpd, area)
@@ -307,6 +322,7 @@ def test_gpu_ic_matches_cpu_twin():
     t = mcs.consumers.consumer_tables(prob, 2)
     d_o, d_g = be.dndp_2d(t, P.gam0, P.beta0), hb.dndp_2d(t, P.gam0, P.beta0)
     assert relerr(d_g, d_o) < 1e-11
+    assert np.array_equal(d_g > 1e-90, d_o > 1e-90) and own_size_excess_2d(P, Tf, d_g, d_o) <= 1.0
     lit = 0
     for j_max, n_photon, emin, bpd in ((P.num_psd_tht_bins, 140, 1e-2, 10), (40, 60, 1e-8, 5)):
         Eo, o = be.photon_ic(t.mom_edge_cgs, t.mc, j_max, alpha_in, n_in, n_photon, emin, bpd, area)
