@@ -627,6 +627,48 @@ int mcs_ens_products_get_layout(const mcs_params* p, mcs_ens_products_layout* ou
 int mcs_ens_set_slope_window(mcs_ens* ens, int l_lo, int l_hi, const double* x_log);
 int mcs_ens_add_products(mcs_ens* ens, mcs_ctx* src, int species_slot);
 
+/* ---- comparison of two slots: does run B agree with run A within their error bars?  Per-word z-scores and their chi-square,
+ * reduced on the device.  Slot slot_a of accumulator a (A, n_a >= 2 samples) against slot slot_b of b (B, n_b >= 2): two slots of
+ * the same kind and length -- both species slots, both iteration slots or both products slots -- of accumulators on one device
+ * with one tally layout.  For every word w of a range [first, first + count), every operation a separate rounding, sqrt and /
+ * correctly rounded as in mcs_ens_summarize (ma, qa: mean and M2 of A; mb, qb: of B):
+ *   va = qa[w] / ((double)n_a * (double)(n_a - 1))      vb likewise      (the variance of each mean)
+ *   s2 = va + vb            d = ma[w] - mb[w]           scale = max(|ma[w]|, |mb[w]|)
+ *   finite word      ma, qa, mb, qb, d and s2 are all finite; n_nonfinite counts the others, which take part in nothing else
+ *   amax             the maximum of scale over the finite words; 0 for an empty range
+ *   selected word    a finite word with scale > 0 and scale >= floor_frac * amax; n_selected counts them
+ *   degenerate word  a selected word with s2 == 0 and d != 0: counted in n_degenerate, in sum_abs_diff and sum_scale, nothing else
+ *   z                0 for a selected word with s2 == 0 and d == 0; d / sqrt(s2) for every other selected word
+ * Over the selected words that are not degenerate:
+ *   max_abs_z        the maximum of |z| (0 when there is none); argmax: the lowest w - first that attains it, -1 when there is none
+ *   n_over           the words with |z| > zcut
+ *   sum_z, sum_abs_z, sum_z2     the sums of z, |z| and z * z; sum_z2 is the chi-square
+ * Over all selected words:
+ *   sum_abs_diff, sum_scale      the sums of |d| and scale
+ * With few samples z follows Welch's t and not a normal law: under the null E[z^2] = nu / (nu - 2) with nu between
+ * min(n_a, n_b) - 1 and n_a + n_b - 2, so a threshold is best calibrated on a null pair (two runs of one configuration over
+ * different iteration numbers).
+ * One call serves all its ranges (at most 256; they may overlap and start at any word) and waits for the device once.  a == b is
+ * allowed when the slots differ (protons against He).  Work is queued on the stream of a's home context, after what both
+ * accumulators queued last; neither accumulator is changed; scratch is a's, shared with the summaries.
+ * Two sweeps over a range, both of whole (mean, M2) pairs of A and B: whether a word is finite depends on all four of its words,
+ * so the first sweep takes amax over exactly the words the second calls finite, and no sweep is ever repeated.  Which words a
+ * thread sees and in which order, and how threads, waves, blocks and partials join, is the summary's walk and depends on the
+ * ranges alone: no atomics, the same state gives the same bits in every field, equal |z| keep the lower word at every join.
+ * Swapping A and B leaves the bits of every field as they are, except that sum_z changes its sign bit (unless it is zero).
+ * sum_abs_z, sum_z2, sum_abs_diff and sum_scale are sums of non-negative terms: within n_selected * 2^-53 relative of the exact
+ * sum; sum_z within n_selected * 2^-53 * sum_abs_z of it.
+ * n_ranges = 0 does nothing and returns 0.  Refused, with a message, nothing changed and nothing queued: a null argument, a slot
+ * out of range, the same slot of the same accumulator, accumulators on different devices or with different layouts, slots of
+ * different kind or length, n_ranges outside 0..256, a products slot that never took a sample, products slots of accumulators
+ * whose slope windows differ in a bound or in the bits of any x_log word (the condition of mcs_ens_merge), either count below 2,
+ * a range outside the slot's vector or with a negative count, floor_frac not in [0, 1] (NaN included), zcut negative or NaN. */
+typedef struct mcs_ens_cmp_range  { int64_t first, count; double floor_frac, zcut; } mcs_ens_cmp_range;
+typedef struct mcs_ens_difference { double amax, max_abs_z, sum_z, sum_abs_z, sum_z2, sum_abs_diff, sum_scale;
+                                    int64_t n_selected, n_over, n_nonfinite, n_degenerate, argmax; } mcs_ens_difference;
+int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges, const mcs_ens_cmp_range* ranges,
+                    mcs_ens_difference* out);
+
 /* ---- test / measurement hooks ------------------------------------------- */
 /* evaluate device math/RNG primitives (bit-parity tests): fn ids in mcs_fn */
 enum mcs_fn { MCS_FN_SIN = 0, MCS_FN_COS, MCS_FN_ASIN, MCS_FN_ACOS, MCS_FN_ATAN2, MCS_FN_LOG10,

@@ -109,6 +109,17 @@ class McsEnsSummary(ct.Structure):
                [(name, ct.c_int64) for name in ("n_selected", "n_over", "n_nonfinite", "argmax")]
 
 
+class McsEnsCmpRange(ct.Structure):
+    """`mcs_ens_cmp_range`: a word range of the two slots of a comparison, with its floor and its |z| cut (include/mcs.h)."""
+    _fields_ = [("first", ct.c_int64), ("count", ct.c_int64), ("floor_frac", ct.c_double), ("zcut", ct.c_double)]
+
+
+class McsEnsDifference(ct.Structure):
+    """`mcs_ens_difference`: what `mcs_ens_compare` says about one range (include/mcs.h)."""
+    _fields_ = [(name, ct.c_double) for name in ("amax", "max_abs_z", "sum_z", "sum_abs_z", "sum_z2", "sum_abs_diff", "sum_scale")] + \
+               [(name, ct.c_int64) for name in ("n_selected", "n_over", "n_nonfinite", "n_degenerate", "argmax")]
+
+
 # enum mcs_option_when / mcs_option_applies
 OPTION_WHEN = ("between launches", "before the first pipelined run", "creation only")
 OPTION_APPLIES = ("any", "fp64 state when > 0", "fp32 state")
@@ -336,6 +347,7 @@ def load_library() -> ct.CDLL:
         "mcs_ens_products_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsEnsProductsLayout)]),
         "mcs_ens_set_slope_window": (i32, [vp, i32, i32, c_double_p]),
         "mcs_ens_add_products": (i32, [vp, vp, i32]),
+        "mcs_ens_compare": (i32, [vp, i32, vp, i32, i32, ct.POINTER(McsEnsCmpRange), ct.POINTER(McsEnsDifference)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -387,4 +399,5 @@ EXPORTED_SYMBOLS += [
     "mcs_ens_get_layout", "mcs_ens_create", "mcs_ens_destroy", "mcs_ens_begin_iteration", "mcs_ens_add_species",
     "mcs_ens_add_iteration", "mcs_ens_merge", "mcs_ens_count", "mcs_ens_read", "mcs_ens_load_mean", "mcs_ens_summarize",
     "mcs_ens_summarize_merged", "mcs_ens_products_get_layout", "mcs_ens_set_slope_window", "mcs_ens_add_products",
+    "mcs_ens_compare",
 ]

@@ -11,6 +11,7 @@
 // largest |mean|, then the relative errors of the words that pass the floor it sets -- each thread over its words in ascending
 // order, then per wave by shuffles, per block through LDS, one partial per block into a scratch buffer of the accumulator, and a
 // last kernel that folds a range's partials in index order.  No atomics: the same state gives the same bits.
+// The comparison of two slots (mcs_ens_compare) is the same walk over the (mean, M2) pairs of both with a record of its own.
 // A context is seen through mcs_ctx_view.h; its stream carries the work, an event of the accumulator orders successive operations
 // that were queued on different streams.
 #include <hip/hip_runtime.h>
@@ -217,11 +218,12 @@ __device__ inline SumRec rec_shfl_down(const SumRec& v, int d) {
 }
 
 // the block's threads' records joined in a fixed order -> thread 0's v (a binary tree over the lanes of a wave, then the waves
-// in order); tmp: SUM_WAVES records of LDS
-__device__ inline void rec_block_join(SumRec& v, SumRec* tmp) {
+// in order); tmp: SUM_WAVES records of LDS.  Rec: SumRec, or the CmpRec of the comparison below, with its rec_join / rec_shfl_down
+template <class Rec>
+__device__ inline void rec_block_join(Rec& v, Rec* tmp) {
   const int lane = threadIdx.x & 63;
   for (int d = 1; d < 64; d <<= 1) {
-    const SumRec o = rec_shfl_down(v, d);
+    const Rec o = rec_shfl_down(v, d);
     if ((lane & (2 * d - 1)) == 0) rec_join(v, o);      // (lane + d holds the lanes lane + d .. lane + 2 d - 1)
   }
   if (lane == 0) tmp[threadIdx.x >> 6] = v;
@@ -428,6 +430,157 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_final(const SumPara
   for (int k = o0 + threadIdx.x; k < o1; k += ENS_THREADS) pmax[k] = amax;
 }
 
+// ---- the comparison of two slots (mcs_ens_compare) -------------------------------------------------------------------------
+// The walk of the summary -- span_of, range_of_block, SumParams (a range's tol holds its zcut), pmax, the joins -- over the words of
+// TWO (mean, M2) pairs with another record.  Both sweeps read all four words of a word: whether it is finite depends on all of
+// them, so sweep 1 takes amax over exactly the words that sweep 2 calls finite and no sweep is ever repeated.
+// arg: LLONG_MAX while no z has been seen (max_z is then -1: every |z| beats it).  amax: the one the selection was made with.
+struct CmpRec { double amax, max_z, sum_z, sum_abs_z, sum_z2, sum_diff, sum_scale; long long n_sel, n_over, n_nonf, n_degen, arg; };
+
+__device__ inline CmpRec cmp_empty(double amax) { return CmpRec{amax, -1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, LLONG_MAX}; }
+
+// b joins a; a holds the words (or partials) before b's: the sums add in that order, equal |z| keep the lower word
+__device__ inline void rec_join(CmpRec& a, const CmpRec& b) {
+  if (b.max_z > a.max_z || (b.max_z == a.max_z && b.arg < a.arg)) { a.max_z = b.max_z; a.arg = b.arg; }
+  a.sum_z = a.sum_z + b.sum_z;
+  a.sum_abs_z = a.sum_abs_z + b.sum_abs_z;
+  a.sum_z2 = a.sum_z2 + b.sum_z2;
+  a.sum_diff = a.sum_diff + b.sum_diff;
+  a.sum_scale = a.sum_scale + b.sum_scale;
+  a.n_sel += b.n_sel; a.n_over += b.n_over; a.n_nonf += b.n_nonf; a.n_degen += b.n_degen;
+}
+
+__device__ inline CmpRec rec_shfl_down(const CmpRec& v, int d) {
+  CmpRec o;
+  o.amax = v.amax; o.max_z = __shfl_down(v.max_z, d, 64); o.sum_z = __shfl_down(v.sum_z, d, 64);
+  o.sum_abs_z = __shfl_down(v.sum_abs_z, d, 64); o.sum_z2 = __shfl_down(v.sum_z2, d, 64);
+  o.sum_diff = __shfl_down(v.sum_diff, d, 64); o.sum_scale = __shfl_down(v.sum_scale, d, 64);
+  o.n_sel = __shfl_down(v.n_sel, d, 64); o.n_over = __shfl_down(v.n_over, d, 64); o.n_nonf = __shfl_down(v.n_nonf, d, 64);
+  o.n_degen = __shfl_down(v.n_degen, d, 64); o.arg = __shfl_down(v.arg, d, 64);
+  return o;
+}
+
+// What the definition makes of one word of A and B (include/mcs.h): every operation a separate rounding.
+struct CmpWord { double d, s2, scale; bool finite; };
+// The two slots.  den_a = (double)n_a * (double)(n_a - 1), den_b likewise.
+struct SrcCmp {
+  // Pairs a thread loads before it looks at them: a pair is four loads of 16 bytes, so 2 keep in flight the 128 bytes per thread that
+  // SrcOne's sweep 2 keeps with its 4.  Not measured against other values.
+  static constexpr int LOADS = 2;
+  const double* ma; const double* qa; const double* mb; const double* qb;
+  double den_a, den_b;
+  __device__ CmpWord word(double xa, double ya, double xb, double yb) const {
+    CmpWord w;
+    const double va = ya / den_a, vb = yb / den_b;
+    w.s2 = va + vb;
+    w.d = xa - xb;
+    const double fa = fabs(xa), fb = fabs(xb);
+    w.scale = fa > fb ? fa : fb;
+    w.finite = finite_(xa) && finite_(ya) && finite_(xb) && finite_(yb) && finite_(w.d) && finite_(w.s2);
+    return w;
+  }
+  __device__ CmpWord at(long long i) const { return word(ma[i], qa[i], mb[i], qb[i]); }
+  __device__ void pair(long long p, double2& xa, double2& ya, double2& xb, double2& yb) const {
+    xa = reinterpret_cast<const double2*>(ma)[p]; ya = reinterpret_cast<const double2*>(qa)[p];
+    xb = reinterpret_cast<const double2*>(mb)[p]; yb = reinterpret_cast<const double2*>(qb)[p];
+  }
+};
+
+// sweep 1: the largest scale = max(|ma|, |mb|) over the finite words, per block
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_cmp_amax(const SrcCmp src, const SumParams* __restrict__ P, double* __restrict__ pmax) {
+  __shared__ double tmp[SUM_WAVES];
+  const int r = range_of_block(P, blockIdx.x), o0 = P->off[r];
+  const SumSpan s = span_of(P->r[r], blockIdx.x - o0, P->off[r + 1] - o0);
+  constexpr int U = SrcCmp::LOADS;
+  double a = 0.0;
+  auto see = [&](const CmpWord& w) { if (w.finite && w.scale > a) a = w.scale; };
+  if (s.ends && (s.first & 1)) see(src.at(s.first));
+  long long j = s.j0;
+  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
+    double2 xa[U], ya[U], xb[U], yb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) src.pair(s.pair0 + j + u * s.stride, xa[u], ya[u], xb[u], yb[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) { see(src.word(xa[u].x, ya[u].x, xb[u].x, yb[u].x)); see(src.word(xa[u].y, ya[u].y, xb[u].y, yb[u].y)); }
+  }
+  for (; j < s.n_pairs; j += s.stride) {
+    double2 xa, ya, xb, yb;
+    src.pair(s.pair0 + j, xa, ya, xb, yb);
+    see(src.word(xa.x, ya.x, xb.x, yb.x)); see(src.word(xa.y, ya.y, xb.y, yb.y));
+  }
+  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(src.at(s.first + s.count - 1));
+  a = block_max(a, tmp);
+  if (threadIdx.x == 0) pmax[blockIdx.x] = a;
+}
+
+// sweep 2: with amax = the largest of the range's pmax, the record of the block's words
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_cmp_stats(const SrcCmp src, const SumParams* __restrict__ P, const double* __restrict__ pmax,
+                                                                   CmpRec* __restrict__ part) {
+  __shared__ double tmp[SUM_WAVES];
+  __shared__ CmpRec rtmp[SUM_WAVES];
+  const int r = range_of_block(P, blockIdx.x), o0 = P->off[r], n_blk = P->off[r + 1] - o0;
+  const SumRange R = P->r[r];
+  const SumSpan s = span_of(R, blockIdx.x - o0, n_blk);
+  constexpr int U = SrcCmp::LOADS;
+  double a = 0.0;
+  for (int k = threadIdx.x; k < n_blk; k += ENS_THREADS) { const double x = pmax[o0 + k]; a = x > a ? x : a; }
+  const double amax = block_max(a, tmp);
+  const double floor_abs = R.floor_frac * amax, zcut = R.tol;
+  CmpRec v = cmp_empty(amax);
+  auto see = [&](long long idx, const CmpWord& w) {
+    if (!w.finite) { v.n_nonf += 1; return; }
+    if (w.scale > 0.0 && w.scale >= floor_abs) {
+      v.n_sel += 1;
+      v.sum_diff = v.sum_diff + fabs(w.d);
+      v.sum_scale = v.sum_scale + w.scale;
+      if (w.s2 == 0.0 && w.d != 0.0) { v.n_degen += 1; return; }
+      const double z = w.s2 == 0.0 ? 0.0 : w.d / mcsm::sqrt_(w.s2);
+      const double az = fabs(z);
+      if (az > zcut) v.n_over += 1;
+      v.sum_z = v.sum_z + z;
+      v.sum_abs_z = v.sum_abs_z + az;
+      v.sum_z2 = v.sum_z2 + z * z;
+      if (az > v.max_z || (az == v.max_z && idx < v.arg)) { v.max_z = az; v.arg = idx; }
+    }
+  };
+  const long long i0 = 2 * s.pair0 - s.first;        // word index - first of pair 0's first word
+  if (s.ends && (s.first & 1)) see(0, src.at(s.first));
+  long long j = s.j0;
+  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
+    double2 xa[U], ya[U], xb[U], yb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) src.pair(s.pair0 + j + u * s.stride, xa[u], ya[u], xb[u], yb[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long ju = j + u * s.stride;
+      see(i0 + 2 * ju, src.word(xa[u].x, ya[u].x, xb[u].x, yb[u].x)); see(i0 + 2 * ju + 1, src.word(xa[u].y, ya[u].y, xb[u].y, yb[u].y));
+    }
+  }
+  for (; j < s.n_pairs; j += s.stride) {
+    double2 xa, ya, xb, yb;
+    src.pair(s.pair0 + j, xa, ya, xb, yb);
+    see(i0 + 2 * j, src.word(xa.x, ya.x, xb.x, yb.x)); see(i0 + 2 * j + 1, src.word(xa.y, ya.y, xb.y, yb.y));
+  }
+  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(s.count - 1, src.at(s.first + s.count - 1));
+  rec_block_join(v, rtmp);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+
+// one block per range: its partials joined in index order, as mcs_k_ens_sum_final joins a summary's
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_cmp_final(const SumParams* __restrict__ P, const CmpRec* __restrict__ part,
+                                                                   CmpRec* __restrict__ out) {
+  __shared__ CmpRec rtmp[SUM_WAVES];
+  const int r = blockIdx.x, o0 = P->off[r], o1 = P->off[r + 1];
+  CmpRec v = cmp_empty(0.0);
+  for (int k = o0 + threadIdx.x; k < o1; k += ENS_THREADS) rec_join(v, part[k]);
+  rec_block_join(v, rtmp);
+  if (threadIdx.x == 0) {
+    v.amax = o1 > o0 ? part[o0].amax : 0.0;
+    if (v.arg == LLONG_MAX) { v.arg = -1; v.max_z = v.n_sel > v.n_degen ? __builtin_nan("") : 0.0; }
+    out[r] = v;
+  }
+}
+
 int fail(const std::string& msg) { return mcs_ctx_view_fail(msg.c_str()); }
 #define ENSCHK(expr)                                                                          \
   do {                                                                                        \
@@ -497,6 +650,8 @@ struct mcs_ens {
   PinnedBuf<SumParams> sum_par_h; DevBuf<SumParams> sum_par;
   PinnedBuf<SumRec> sum_out_h;    DevBuf<SumRec> sum_out;
   DevBuf<double> sum_pmax;        DevBuf<SumRec> sum_part;
+  // mcs_ens_compare with this accumulator as A shares sum_par and sum_pmax with it; its records are another type
+  PinnedBuf<CmpRec> cmp_out_h;    DevBuf<CmpRec> cmp_out, cmp_part;
   // the products slots, one beside every species slot (include/mcs.h, "products sample"): vectors allocated at the first sample
   mcs_ens_products_layout PL;
   std::vector<long long> pn;
@@ -570,18 +725,23 @@ int products_reserve(mcs_ens* e, const std::string& who, int s, hipStream_t st) 
   return 0;
 }
 
+// one range of a summary or a comparison against a vector of len words; cut: its tol or zcut, by that name -> its blocks added
+int check_range(const std::string& which, long long len, long long first, long long count, double floor_frac, double cut, const char* cut_name,
+                long long* n_blocks) {
+  if (first < 0 || count < 0 || first > len || count > len - first) return fail(which + " lies outside the slot's sample vector");
+  if (!(floor_frac >= 0.0 && floor_frac <= 1.0)) return fail(which + ": floor_frac outside [0, 1]");
+  if (!(cut >= 0.0)) return fail(which + ": " + cut_name + " is negative or not a number");
+  const long long b = (count + SUM_CHUNK - 1) / SUM_CHUNK;
+  *n_blocks += b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b;
+  return 0;
+}
+
 // the ranges of a summary call against a vector of len words -> the blocks they take
 int check_ranges(const std::string& who, long long len, int n_ranges, const mcs_ens_range* ranges, long long* n_blocks) {
   *n_blocks = 0;
-  for (int r = 0; r < n_ranges; ++r) {
-    const mcs_ens_range& R = ranges[r];
-    const std::string which = who + ": range " + std::to_string(r);
-    if (R.first < 0 || R.count < 0 || R.first > len || R.count > len - R.first) return fail(which + " lies outside the slot's sample vector");
-    if (!(R.floor_frac >= 0.0 && R.floor_frac <= 1.0)) return fail(which + ": floor_frac outside [0, 1]");
-    if (!(R.tol >= 0.0)) return fail(which + ": tol is negative or not a number");
-    const long long b = (R.count + SUM_CHUNK - 1) / SUM_CHUNK;
-    *n_blocks += b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b;
-  }
+  for (int r = 0; r < n_ranges; ++r)
+    if (check_range(who + ": range " + std::to_string(r), len, ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].tol, "tol", n_blocks))
+      return 1;
   return 0;
 }
 
@@ -966,6 +1126,74 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
     case 7: return sum_run(who, list, n_ens, merged_src<7>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
     default: return sum_run(who, list, n_ens, merged_src<8>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
   }
+}
+
+int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges, const mcs_ens_cmp_range* ranges, mcs_ens_difference* out) {
+  const std::string who = "mcs_ens_compare";
+  if (!a || !b) return fail(who + ": null argument");
+  SlotRef ra, rb;
+  if (slot_ref(a, who + " (A)", slot_a, &ra) || slot_ref(b, who + " (B)", slot_b, &rb)) return 1;
+  if (a == b && slot_a == slot_b) return fail(who + ": A and B are the same slot of the same accumulator");
+  if (a->device != b->device) return fail(who + ": the accumulators are on different devices");
+  if (a->E.sp_total != b->E.sp_total || a->E.it_total != b->E.it_total || a->L.total != b->L.total || a->P.n_grid != b->P.n_grid ||
+      a->P.n_ions != b->P.n_ions || a->P.n_itrs != b->P.n_itrs || a->P.num_psd_mom_bins != b->P.num_psd_mom_bins ||
+      a->P.num_psd_tht_bins != b->P.num_psd_tht_bins)
+    return fail(who + ": the accumulators' layouts differ");
+  // species slot, iteration slot or products slot
+  const auto kind = [](const mcs_ens* e, int slot) { return is_products(slot) ? 2 : slot == e->n_slots - 1 ? 1 : 0; };
+  const long long len = a->len(slot_a);
+  if (kind(a, slot_a) != kind(b, slot_b) || len != b->len(slot_b)) return fail(who + ": the two slots differ in kind or length");
+  if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
+  if (n_ranges == 0) return 0;
+  if (!ranges || !out) return fail(who + ": null argument");
+  if (is_products(slot_a)) {
+    if (ra.n == 0 || rb.n == 0) return fail(who + ": a products slot has never taken a sample");
+    if (windows_differ(a, b)) return fail(who + ": the accumulators' slope windows differ");
+  }
+  if (ra.n < 2 || rb.n < 2)
+    return fail(who + ": a standard error needs at least two samples; A has " + std::to_string(ra.n) + ", B has " + std::to_string(rb.n));
+  long long n_blocks = 0;
+  for (int r = 0; r < n_ranges; ++r)
+    if (check_range(who + ": range " + std::to_string(r), len, ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].zcut, "zcut", &n_blocks))
+      return 1;
+  McsCtxView v;
+  if (mcs_ctx_view_get(a->home, &v)) return 1;
+  hipError_t h = a->sum_par_h.reserve(1);
+  if (h == hipSuccess) h = a->sum_par.reserve(1);
+  if (h == hipSuccess) h = a->cmp_out_h.reserve(SUM_MAX_RANGES);
+  if (h == hipSuccess) h = a->cmp_out.reserve(SUM_MAX_RANGES);
+  if (h == hipSuccess) h = a->sum_pmax.reserve(n_blocks);
+  if (h == hipSuccess) h = a->cmp_part.reserve(n_blocks);
+  if (h != hipSuccess) return fail(who + ": scratch allocation: " + hipGetErrorString(h));
+  // (every earlier call has waited for its copies: the pinned blocks are free)
+  SumParams* P = a->sum_par_h.get();
+  P->n_ranges = n_ranges;
+  P->off[0] = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    P->r[r] = SumRange{ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].zcut};
+    const long long nb = (ranges[r].count + SUM_CHUNK - 1) / SUM_CHUNK;
+    P->off[r + 1] = P->off[r] + (int)(nb > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : nb);
+  }
+  if (enter(a, v.stream) || (b != a && enter(b, v.stream))) return 1;
+  const SrcCmp src{ra.mean, ra.m2, rb.mean, rb.m2, (double)ra.n * (double)(ra.n - 1), (double)rb.n * (double)(rb.n - 1)};
+  ENSCHK(hipMemcpyAsync(a->sum_par.get(), P, sizeof(SumParams), hipMemcpyHostToDevice, v.stream));
+  if (n_blocks > 0) {
+    hipLaunchKernelGGL(mcs_k_ens_cmp_amax, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, src, a->sum_par.get(), a->sum_pmax.get());
+    ENSCHK(hipGetLastError());
+    hipLaunchKernelGGL(mcs_k_ens_cmp_stats, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, src, a->sum_par.get(), a->sum_pmax.get(),
+                       a->cmp_part.get());
+    ENSCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(mcs_k_ens_cmp_final, dim3((unsigned)n_ranges), dim3(ENS_THREADS), 0, v.stream, a->sum_par.get(), a->cmp_part.get(), a->cmp_out.get());
+  ENSCHK(hipGetLastError());
+  ENSCHK(hipMemcpyAsync(a->cmp_out_h.get(), a->cmp_out.get(), (size_t)n_ranges * sizeof(CmpRec), hipMemcpyDeviceToHost, v.stream));
+  ENSCHK(hipStreamSynchronize(v.stream));
+  const CmpRec* got = a->cmp_out_h.get();
+  for (int r = 0; r < n_ranges; ++r) {
+    const CmpRec& g = got[r];
+    out[r] = mcs_ens_difference{g.amax, g.max_z, g.sum_z, g.sum_abs_z, g.sum_z2, g.sum_diff, g.sum_scale, g.n_sel, g.n_over, g.n_nonf, g.n_degen, g.arg};
+  }
+  return 0;
 }
 
 int mcs_ens_load_mean(mcs_ens* e, int slot, mcs_ctx* dst) {

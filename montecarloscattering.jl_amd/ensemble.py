@@ -51,6 +51,20 @@ on a part of shape [zone][bins] (the three dNdp_* and the six marginals) is the 
 words.  dN/dp spans a dozen decades: without it the floor_frac selection keeps the thermal peak and drops the tail.  Several zones
 are several requests (MAX_RANGES in one summary).
 
+Does run B agree with run A within their error bars?  `Ensemble.compare` (`CompareRequest`, `Difference`, `Agreement`,
+`check_agreements`) holds a slot of one ensemble against a slot of the same kind of another -- or of the same one: protons against
+He -- word by word, mcs_ens_compare of include/mcs.h, where the definition is:
+
+  per word       va = M2_a / (n_a (n_a - 1)), vb likewise; s2 = va + vb; d = mean_a - mean_b; scale = max(|mean_a|, |mean_b|)
+  finite word    both means, both M2, d and s2 are finite; n_nonfinite counts the others, which take part in nothing else
+  amax           max scale over the finite words; selected word: finite, scale > 0 and scale >= floor_frac * amax
+  degenerate     a selected word with s2 == 0 and d != 0 (n_degenerate; it has no z)
+  z              0 where s2 == 0 and d == 0, else d / sqrt(s2)
+  max_abs_z, argmax, n_over (|z| > zcut), sum_z, sum_abs_z, sum_z2 (the chi-square) over the selected words that have a z;
+  sum_abs_diff, sum_scale over all selected words
+
+`Agreement` says what the numbers mean with few samples.
+
 `HipEnsemble` keeps the vectors on the device and updates them with the kernels of csrc/mcs_ensemble.hip: the 22 MB histograms
 never cross to the host (it costs device memory: two vectors of the sample length per slot, about twice the tally buffer per
 species slot).  `HostEnsemble` does the same arithmetic in numpy, in the same order, on read_tallies() buffers: it lets the driver
@@ -318,6 +332,151 @@ class Trigger:
         return int(math.ceil(s.n * (v / self.threshold) ** 2))
 
 
+AGREEMENT_STATISTICS = ("max_z", "chi2_per_word", "fraction_over", "mean_z", "weighted_diff")
+
+
+@dataclasses.dataclass(frozen=True)
+class CompareRequest:
+    """One range of a comparison (`Ensemble.compare`): a named part, a zone slice or a bins window of it as in `Request`, the
+    floor of the selection and the |z| above which a word counts in n_over."""
+    name: str
+    zones: Optional[Tuple[int, int]] = None
+    floor_frac: float = 1e-3
+    zcut: float = 3.0
+    bins: Optional[Tuple[int, int]] = None
+
+    def __post_init__(self):
+        _check_part(self.name, self.zones, self.bins)
+        if not 0.0 <= self.floor_frac <= 1.0:
+            raise ValueError(f"ensemble: floor_frac {self.floor_frac!r} outside [0, 1]")
+        if not self.zcut >= 0.0:
+            raise ValueError(f"ensemble: zcut {self.zcut!r} is negative or not a number")
+
+
+@dataclasses.dataclass(frozen=True)
+class Difference:
+    """mcs_ens_difference of one range, and the sample counts n_a, n_b of the two slots."""
+    amax: float
+    max_abs_z: float
+    sum_z: float
+    sum_abs_z: float
+    sum_z2: float
+    sum_abs_diff: float
+    sum_scale: float
+    n_selected: int
+    n_over: int
+    n_nonfinite: int
+    n_degenerate: int
+    argmax: int
+    n_a: int
+    n_b: int
+
+
+def difference_of(ma, qa, n_a: int, mb, qb, n_b: int, floor_frac: float, zcut: float) -> Difference:
+    """The definition of mcs_ens_compare (include/mcs.h) on the host, for the words of one range of A (mean ma, M2 qa, n_a samples)
+    and B: the per-word quantities elementwise, the five sums correctly rounded."""
+    ma, qa, mb, qb = (np.asarray(x, dtype=np.float64).ravel() for x in (ma, qa, mb, qb))
+    with np.errstate(all="ignore"):
+        s2 = qa / (float(n_a) * float(n_a - 1)) + qb / (float(n_b) * float(n_b - 1))
+        d = ma - mb
+        scale = np.maximum(np.abs(ma), np.abs(mb))
+        finite = np.isfinite(ma) & np.isfinite(qa) & np.isfinite(mb) & np.isfinite(qb) & np.isfinite(d) & np.isfinite(s2)
+    n_nonfinite = int(ma.size - np.count_nonzero(finite))
+    amax = float(scale[finite].max()) if finite.any() else 0.0
+    where = np.flatnonzero(finite & (scale > 0.0) & (scale >= floor_frac * amax))
+    if where.size == 0:
+        return Difference(amax, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, n_nonfinite, 0, -1, int(n_a), int(n_b))
+    d, s2, scale = d[where], s2[where], scale[where]
+    keep = ~((s2 == 0.0) & (d != 0.0))                # (the others are degenerate)
+    some = s2[keep] != 0.0
+    z = np.zeros(int(np.count_nonzero(keep)))         # (s2 == 0 and d == 0: z = 0)
+    with np.errstate(all="ignore"):
+        z[some] = d[keep][some] / np.sqrt(s2[keep][some])
+    az = np.abs(z)
+    k = int(np.argmax(az)) if az.size else -1         # (the first of equal maxima)
+    return Difference(amax, float(az[k]) if az.size else 0.0, math.fsum(z), math.fsum(az), math.fsum(z * z), math.fsum(np.abs(d)),
+                      math.fsum(scale), int(where.size), int(np.count_nonzero(az > zcut)), n_nonfinite,
+                      int(where.size - np.count_nonzero(keep)), int(where[keep][k]) if az.size else -1, int(n_a), int(n_b))
+
+
+class Agreement:
+    """A rule on the difference of one part of two slots (`check_agreements`): met when its value is <= threshold.
+      "max_z"          max_abs_z: the largest |z| of a selected word
+      "chi2_per_word"  sum_z2 / (n_selected - n_degenerate)
+      "fraction_over"  n_over / (n_selected - n_degenerate): the share of the words with |z| > zcut
+      "mean_z"         sum_z / (n_selected - n_degenerate); met when its absolute value is <= threshold (a bias has a sign)
+      "weighted_diff"  sum_abs_diff / sum_scale
+    z = (mean_a - mean_b) / sqrt(se_a^2 + se_b^2) per word, over the selected words: those whose larger |mean| is at least floor_frac
+    times the part's largest (mcs_ens_compare of include/mcs.h has the definition).  A degenerate word has no z: both error bars are
+    zero and the means differ.  Never met with nothing selected, with a word of the range that is not finite, or with a degenerate
+    word -- except "weighted_diff", which counts degenerate words like any other.
+
+    What the numbers mean: with few samples z follows Welch's t and not a normal law.  Under the null hypothesis
+    E[z^2] = nu / (nu - 2) with nu between min(n_a, n_b) - 1 and n_a + n_b - 2: with three samples a side, chi2_per_word of a
+    perfectly good pair lies near 2 and not near 1, and |z| > 3 is nothing rare.  A threshold is therefore best calibrated on a null
+    pair: two runs of the same configuration over different iteration numbers (driver.run(first_iter=...))."""
+
+    def __init__(self, slot: int, name: str, statistic: str, threshold: float, zones=None, bins=None, floor_frac: float = 1e-3, zcut: float = 3.0,
+                 other_slot: Optional[int] = None):
+        if statistic not in AGREEMENT_STATISTICS:
+            raise ValueError(f"agreement: unknown statistic {statistic!r}; there are: {', '.join(AGREEMENT_STATISTICS)}")
+        if not threshold > 0:
+            raise ValueError(f"agreement: threshold {threshold!r} must be positive")
+        for s in (slot,) if other_slot is None else (slot, other_slot):
+            if int(s) != s or s < 0:
+                raise ValueError(f"agreement: slot {s!r} is no slot")
+        self.request = CompareRequest(name, None if zones is None else (int(zones[0]), int(zones[1])), float(floor_frac), float(zcut),
+                                      None if bins is None else (int(bins[0]), int(bins[1])))
+        self.slot, self.other_slot = int(slot), int(slot if other_slot is None else other_slot)
+        self.name, self.statistic, self.threshold = name, statistic, float(threshold)
+        self.zones, self.bins, self.floor_frac, self.zcut = self.request.zones, self.request.bins, self.request.floor_frac, self.request.zcut
+
+    def __repr__(self):
+        return (f"Agreement(slot={self.slot}, name={self.name!r}, statistic={self.statistic!r}, threshold={self.threshold!r}, zones={self.zones!r}, "
+                f"bins={self.bins!r}, floor_frac={self.floor_frac!r}, zcut={self.zcut!r}, other_slot={self.other_slot})")
+
+    def value(self, d: Difference) -> float:
+        """The statistic of a difference; nan where it has none (no selected word, or none that is not degenerate)."""
+        if self.statistic == "weighted_diff":
+            return d.sum_abs_diff / d.sum_scale if d.n_selected > 0 else float("nan")
+        n = d.n_selected - d.n_degenerate
+        if n <= 0:
+            return float("nan")
+        if self.statistic == "max_z":
+            return d.max_abs_z
+        if self.statistic == "chi2_per_word":
+            return d.sum_z2 / n
+        if self.statistic == "fraction_over":
+            return d.n_over / n
+        return d.sum_z / n
+
+    def met(self, d: Difference) -> bool:
+        if d.n_selected == 0 or d.n_nonfinite > 0 or (d.n_degenerate > 0 and self.statistic != "weighted_diff"):
+            return False
+        return abs(self.value(d)) <= self.threshold
+
+
+@dataclasses.dataclass
+class AgreementCheck:
+    """One row of `check_agreements`, the counterpart of driver.TriggerCheck."""
+    agreement: Agreement
+    difference: Difference
+    value: float
+    met: bool
+
+
+def check_agreements(a: "Ensemble", b: "Ensemble", agreements: Sequence[Agreement]) -> List[AgreementCheck]:
+    """One `a.compare(b, ...)` per (slot, other_slot) pair that has agreements -> a row per agreement, in their order."""
+    agreements = list(agreements)
+    rows: List[Optional[AgreementCheck]] = [None] * len(agreements)
+    for slot, other_slot in sorted({(t.slot, t.other_slot) for t in agreements}):
+        mine = [k for k, t in enumerate(agreements) if (t.slot, t.other_slot) == (slot, other_slot)]
+        got = a.compare(b, slot, [agreements[k].request for k in mine], other_slot)
+        for k, d in zip(mine, got):
+            rows[k] = AgreementCheck(agreements[k], d, agreements[k].value(d), agreements[k].met(d))
+    return rows
+
+
 def bin_centres_log10(prob) -> np.ndarray:
     """x_log [nmom+1] of `Ensemble.set_slope_window`: log10 of every momentum bin's centre in cgs, the centre 0.5 (b[l] + b[l + 1])
     of prob.psd_mom_bounds (log10 of p / m_p c) brought to cgs as consumers.consumer_tables does (pt_center)."""
@@ -515,6 +674,32 @@ class Ensemble:
             if type(o) is not type(self) or o.n_species != self.n_species or o.layout.fields != self.layout.fields:
                 raise ValueError("ensemble: a merged summary needs ensembles of the same kind, slots and layout")
 
+    def _kind(self, slot: int) -> str:
+        return "products" if self.is_products(slot) else "iteration" if slot == self.iteration_slot else "species"
+
+    def compare(self, other: "Ensemble", slot: int, requests: Sequence[CompareRequest], other_slot: Optional[int] = None) -> List[Difference]:
+        """One Difference per request (at most MAX_RANGES; they may overlap): slot `slot` of this ensemble, A, against slot
+        `other_slot` (default: the same number) of `other`, B -- two slots of one kind of ensembles of one kind and layout, each with
+        at least two samples; `other` may be this ensemble when the slots differ.  Neither is changed.  On the device one
+        mcs_ens_compare call and one wait (include/mcs.h has the definition; `Agreement` says what the numbers mean)."""
+        requests = list(requests)
+        other_slot = slot if other_slot is None else other_slot
+        if type(other) is not type(self) or other.layout.fields != self.layout.fields:
+            raise ValueError("ensemble: a comparison needs ensembles of the same kind and layout")
+        self._check_slot(slot)
+        other._check_slot(other_slot)
+        if other is self and slot == other_slot:
+            raise ValueError(f"ensemble: a comparison of slot {slot} with itself")
+        if self._kind(slot) != other._kind(other_slot):
+            raise ValueError(f"ensemble: a comparison of a {self._kind(slot)} slot with a {other._kind(other_slot)} slot")
+        if len(requests) > MAX_RANGES:
+            raise ValueError(f"ensemble: {len(requests)} requests in one comparison; at most {MAX_RANGES}")
+        ranges = [self.word_range(slot, q.name, q.zones, q.bins) + (float(q.floor_frac), float(q.zcut)) for q in requests]
+        n_a, n_b = self.count(slot), other.count(other_slot)
+        if n_a < 2 or n_b < 2:
+            raise ValueError(f"ensemble: a comparison needs at least two samples on either side; slot {slot} has {n_a}, the other's slot {other_slot} has {n_b}")
+        return self._compare(other, slot, other_slot, n_a, n_b, ranges) if ranges else []
+
     def check_trigger(self, trigger: Trigger):
         """Refuses a trigger whose slot this ensemble does not have, or whose part (or zone slice, or bins window) that slot does
         not have."""
@@ -691,6 +876,13 @@ class HostEnsemble(Ensemble):
             out.append(summary_of(m, q, n, floor_frac, tol))
         return out
 
+    def _compare(self, other, slot, other_slot, n_a, n_b, ranges):
+        if self.is_products(slot) and self._windows_differ(self, other):
+            raise ValueError("ensemble: a comparison of ensembles whose slope windows differ")
+        (ma, qa, _), (mb, qb, _) = self._vectors(slot), other._vectors(other_slot)
+        return [difference_of(ma[first:first + count], qa[first:first + count], n_a, mb[first:first + count], qb[first:first + count], n_b,
+                              floor_frac, zcut) for first, count, floor_frac, zcut in ranges]
+
     def load_mean(self, slot: int, backend):
         """The mean of a species slot written into the backend's per-species sections (num_crossings rounded to nearest)."""
         self._check_slot(slot)
@@ -782,6 +974,13 @@ class HipEnsemble(Ensemble):
         self._chk(self.lib.mcs_ens_summarize_merged(len(hs), hs, int(slot), len(ranges), rs, out, ct.byref(total)))
         return [Summary(o.amax, o.max_rel, o.sum_se, o.sum_abs_mean, o.sum_rel2, int(o.n_selected), int(o.n_over), int(o.n_nonfinite),
                         int(o.argmax), int(total.value)) for o in out]
+
+    def _compare(self, other, slot, other_slot, n_a, n_b, ranges):
+        rs = (capi.McsEnsCmpRange * len(ranges))(*[capi.McsEnsCmpRange(*r) for r in ranges])
+        out = (capi.McsEnsDifference * len(ranges))()
+        self._chk(self.lib.mcs_ens_compare(self.h, int(slot), other.h, int(other_slot), len(ranges), rs, out))
+        return [Difference(o.amax, o.max_abs_z, o.sum_z, o.sum_abs_z, o.sum_z2, o.sum_abs_diff, o.sum_scale, int(o.n_selected), int(o.n_over),
+                           int(o.n_nonfinite), int(o.n_degenerate), int(o.argmax), n_a, n_b) for o in out]
 
     def load_mean(self, slot: int, backend: HipBackend):
         self._chk(self.lib.mcs_ens_load_mean(self.h, int(slot), backend.h))
