@@ -692,6 +692,35 @@ int mcs_eval_fn(mcs_ctx* ctx, int fn, int64_t n, const double* a, const double* 
  * ptot_pf, gam_pf, xn_per, pb_pf, p_perp, phi.  out [n][5]: pb_pf, p_perp, phi, gyro_period, cos_max.  pe_crit, game_crit and eta_mfp
  * are those of the context's mcs_params.  All three forms must equal the oracle bit for bit (tests/test_gpu_math_forms.py). */
 int mcs_eval_scatter(mcs_ctx* ctx, int form, int64_t n, const double* in, double* out);
+/* The pcut bookkeeping (K2: compaction of the status bytes, pcut_finalize, new_pcut; src/cuts.jl:34-124) on the CALLER's status bytes
+ * and saved states, through the launchers and the launch geometry of mcs_run_pcut*, in one of three forms:
+ *   0  host-sized (mcs_run_pcut + mcs_new_pcut [+ mcs_saved_export / mcs_saved_gidx]): bytes equal to `match` count as saved, i_mult given;
+ *   1  device-sized (one pcut of mcs_run_pcuts_fused): n is read on the device, the grids are sized for cap_n, i_mult from n_target;
+ *      ctr_work / ctr_saved are the launch's two counter words before the call (ctr_saved: the transport kernel's own count);
+ *   2  late (the late group of mcs_run_pcuts_pipelined; fp64 state only): status 5 counts, the children go behind n_main_next others.
+ * In: l_save[cap_n] and saved[cap_n] (cap_n >= n; what lies beyond n is stale and must be ignored), src_fill in [0, cap_n): every
+ * word of src[] before the call.  The target holds guard + out_cap + guard particles, every byte 0xA5 before the split; the
+ * children are written from particle `guard` on (form 2: guard + n_main_next).  A call whose children would not fit is refused.
+ * export_mode (form 0): 0 none, 1 the global indices only, 2 indices and states, into buffers of exp_cap (>= n_saved) entries whose
+ * bytes are 0xA5 before the call (mode 1 returns exp_f64 / exp_meta, where given, as they were filled); the global index of local particle j is exp_gin[j], or exp_first + j * exp_stride when exp_gin is NULL.
+ * Out (host arrays of the caller): src[cap_n]; out_f64[8][guard + out_cap + guard] in the field order of mcs_soa and out_meta of the
+ * same length (the packed word: grid | tcut << 16 | downstream << 24 | inj << 25); exp_gidx[exp_cap], exp_f64[8][exp_cap],
+ * exp_meta[exp_cap]; scan_total; pd / pd_next: n_use, n_saved, i_mult, n_new as the device holds them after the call, every word
+ * -7 before it but pd.n_use = n in form 1; the two counter words and the mismatch word (0 before the call) after it.
+ * Refused with a message, the context unchanged: a null argument, a form outside 0..2, cap_n < n, n < 0, i_mult < 1, n_target < 1,
+ * n_main_next < 0, match other than 1 or 5, src_fill outside [0, cap_n), a saved state whose grid (0..65535) or tcut (0..255) does not fit the packed word, children that
+ * do not fit out_cap, exp_cap < n_saved, form 2 with fp32 state, export_mode outside 0..2 or set in forms 1 and 2.  The population
+ * of the context is not touched; the saved arrays of the last mcs_run_pcut are replaced. */
+typedef struct mcs_pcut_eval {
+  int32_t form, match, export_mode, reserved;
+  int64_t n, cap_n, src_fill, i_mult, n_target, n_main_next, guard, out_cap, exp_cap, exp_first, exp_stride;
+  uint64_t ctr_work, ctr_saved;
+  const uint8_t* l_save; const mcs_soa* saved; const int64_t* exp_gin;
+  int64_t* src; double* out_f64; uint32_t* out_meta; int64_t* exp_gidx; double* exp_f64; uint32_t* exp_meta;
+  uint64_t scan_total, ctr_work_after, ctr_saved_after, mismatch;
+  int64_t pd[4], pd_next[4];
+} mcs_pcut_eval;
+int mcs_eval_pcut_split(mcs_ctx* ctx, mcs_pcut_eval* io);
 /* per-particle end state of the last mcs_run_pcut (bit-parity tests): i_reason
  * (0 = saved), helix_count, retro step count, final ptot_pf and x. Any pointer may be NULL.
  * The kernel records them only after mcs_set_debug_finals(ctx, 1) (24 B of stores per particle

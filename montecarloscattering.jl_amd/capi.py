@@ -120,6 +120,19 @@ class McsEnsDifference(ct.Structure):
                [(name, ct.c_int64) for name in ("n_selected", "n_over", "n_nonfinite", "n_degenerate", "argmax")]
 
 
+class McsPcutEval(ct.Structure):
+    """`mcs_pcut_eval`: the inputs and outputs of `mcs_eval_pcut_split` (include/mcs.h, test hooks)."""
+    _fields_ = [(name, ct.c_int32) for name in ("form", "match", "export_mode", "reserved")] + \
+               [(name, ct.c_int64) for name in ("n", "cap_n", "src_fill", "i_mult", "n_target", "n_main_next", "guard", "out_cap",
+                                                "exp_cap", "exp_first", "exp_stride")] + \
+               [("ctr_work", ct.c_uint64), ("ctr_saved", ct.c_uint64),
+                ("l_save", c_uint8_p), ("saved", ct.POINTER(McsSoa)), ("exp_gin", c_int64_p),
+                ("src", c_int64_p), ("out_f64", c_double_p), ("out_meta", ct.POINTER(ct.c_uint32)),
+                ("exp_gidx", c_int64_p), ("exp_f64", c_double_p), ("exp_meta", ct.POINTER(ct.c_uint32))] + \
+               [(name, ct.c_uint64) for name in ("scan_total", "ctr_work_after", "ctr_saved_after", "mismatch")] + \
+               [("pd", ct.c_int64 * 4), ("pd_next", ct.c_int64 * 4)]
+
+
 # enum mcs_option_when / mcs_option_applies
 OPTION_WHEN = ("between launches", "before the first pipelined run", "creation only")
 OPTION_APPLIES = ("any", "fp64 state when > 0", "fp32 state")
@@ -310,6 +323,7 @@ def load_library() -> ct.CDLL:
         "mcs_write_tallies": (i32, [vp, c_double_p, c_int64_p]),
         "mcs_eval_fn": (i32, [vp, i32, i64, c_double_p, c_double_p, c_double_p]),
         "mcs_eval_scatter": (i32, [vp, i32, i64, c_double_p, c_double_p]),
+        "mcs_eval_pcut_split": (i32, [vp, ct.POINTER(McsPcutEval)]),
         "mcs_final_download": (i32, [vp, i64, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p]),
         "mcs_last_kernel_ms": (dbl, [vp]),
         "mcs_set_launch": (i32, [vp, i32, i32]),
@@ -386,7 +400,7 @@ EXPORTED_SYMBOLS = [
     "mcs_tallies_f64_devptr", "mcs_tallies_i64_devptr", "mcs_set_grid", "mcs_set_cuts", "mcs_begin_iteration",
     "mcs_begin_species", "mcs_set_fluxes", "mcs_pop_upload", "mcs_pop_download", "mcs_saved_download",
     "mcs_pop_size", "mcs_init_pop", "mcs_init_pop_binned", "mcs_run_pcut", "mcs_new_pcut", "mcs_run_pcut_host", "mcs_read_tallies", "mcs_read_tallies_part", "mcs_num_cus",
-    "mcs_write_tallies", "mcs_eval_fn", "mcs_eval_scatter", "mcs_final_download", "mcs_last_kernel_ms", "mcs_set_launch",
+    "mcs_write_tallies", "mcs_eval_fn", "mcs_eval_scatter", "mcs_eval_pcut_split", "mcs_final_download", "mcs_last_kernel_ms", "mcs_set_launch",
     "mcs_get_layout", "mcs_dndp_cr", "mcs_thermo_calcs",
     "mcs_run_pcut_strided", "mcs_run_pcut_indexed", "mcs_saved_gidx", "mcs_init_pop_binned_strided", "mcs_saved_export", "mcs_split_import", "mcs_set_debug_finals", "mcs_set_retro_cap",
     "mcs_set_tail_slicing", "mcs_last_launches", "mcs_last_kernel", "mcs_write_tallies_part", "mcs_photon_synch",

@@ -202,6 +202,13 @@ int ensure_capacity(mcs_ctx* c, long long n) {
   return 0;
 }
 
+// the grid of mcs_k_split_dev (grid-stride, 256 threads a block) for at most n_max children: per_cu blocks per CU at the most --
+// 16 behind a fused pcut, 4 for a late group, which shares the chip with the next pcut's main launch --, one at the least
+int split_blocks(const mcs_ctx* c, long long n_max, int per_cu) {
+  const long long b = std::min<long long>((n_max + 255) / 256, (long long)c->n_cu * per_cu);
+  return b < 1 ? 1 : (int)b;
+}
+
 int fill(mcs_ctx* c, long long off, long long n, double v) {
   HIPCHK(mcs_launch_fill(c->d_T + off, n, v, c->stream));
   return 0;
@@ -862,14 +869,14 @@ int mcs_run_pcuts_fused(mcs_ctx* c, int i_pcut_first, int i_pcut_last, const int
   HIPCHK(hipMemcpyAsync(c->fused.d_args, c->fused.h_args, sizeof(KArgs) * (size_t)npc, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->fused.d_pd, c->fused.h_pd, sizeof(PcutDev) * (size_t)(npc + 1), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(c->d_counters, 0, CTR_COUNT * sizeof(unsigned long long), c->stream));
-  const int split_blocks = (int)std::min<long long>((cap_n + 255) / 256, (long long)c->n_cu * 16);
+  const int n_split_blocks = split_blocks(c, cap_n, 16);      // (cap_n >= 1)
   for (int k = 0; k < npc; ++k) {
     HIPCHK(hipMemsetAsync(c->d_lsave, 0, (size_t)cap_n, c->stream));
     HIPCHK(hipEventRecord(c->f_ev[2 * k], c->stream));
     HIPCHK(mcs_launch_transport(c->fused.d_args + k, k1.kernel, blocks, k1.threads, c->stream));
     HIPCHK(hipEventRecord(c->f_ev[2 * k + 1], c->stream));
     HIPCHK(mcs_launch_finalize_split_dev(c->d_lsave, cap_n, c->scan.bcounts, c->scan.boffs, c->d_counters + CTR_SCAN, c->scan.src, c->fused.d_pd + k, c->fused.d_pd + k + 1,
-                                         c->d_counters, (long long)n_target[k], c->d_counters + CTR_MISMATCH, sav, pop[(k + 1) & 1], split_blocks, c->stream));
+                                         c->d_counters, (long long)n_target[k], c->d_counters + CTR_MISMATCH, sav, pop[(k + 1) & 1], n_split_blocks, c->stream));
   }
   c->rep_dirty = true;
   HIPCHK(hipMemcpyAsync(c->fused.h_pd, c->fused.d_pd, sizeof(PcutDev) * (size_t)(npc + 1), hipMemcpyDeviceToHost, c->stream));
@@ -1054,9 +1061,8 @@ static int pipelined_pcuts(mcs_ctx* c, const K1Plan& k1, int i_pcut_first, int n
     n1_prev = n1; sofar_prev = sofar;
     if (n5_max > 0) {
       HIPCHK(hipStreamWaitEvent(s2, c->pp_reset, 0));
-      const int split_blocks = (int)std::min<long long>((nL_max + 255) / 256, (long long)c->n_cu * 4);
       HIPCHK(mcs_launch_late_split(lsv[q], nA + nL, c->pp_scan.bcounts, c->pp_scan.boffs, pc + PC_LATE_SCAN, c->pp_scan.src, c->pp_dpdl + (q ^ 1), i_mult, nA_next, savb[q],
-                                   pop_view(c->spare, nA_next), split_blocks < 1 ? 1 : split_blocks, s2));
+                                   pop_view(c->spare, nA_next), split_blocks(c, nL_max, 4), s2));
       // the late launch of the next pcut: particles nA_next .. of its population, their number read on the device
       KArgs& a = c->pp_hargs[2];
       fill_kargs(c, a, i_pcut + 1, nA_next, 0, 1, nullptr, B_next > 0 ? 1 : 0);
@@ -1290,6 +1296,120 @@ int mcs_eval_scatter(mcs_ctx* c, int form, int64_t n, const double* in, double* 
   HIPCHK(mcs_launch_eval_scatter(c->d_args, form, n, din, dout, c->stream));
   HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// K2 on the caller's status bytes and saved states (include/mcs.h): the launchers mcs_run_pcut / mcs_new_pcut / mcs_saved_export (form 0),
+// mcs_run_pcuts_fused (form 1) and pipelined_pcuts (form 2) call, with their grids, on the context's own saved arrays, status bytes,
+// scan scratch and counter words; the target is the spare buffer between two guards.  Everything is checked before anything is
+// changed; the number of children is known on the host (a count of the caller's bytes), so a target that is too small is refused.
+int mcs_eval_pcut_split(mcs_ctx* c, mcs_pcut_eval* io) {
+  MCS_ENTER(c);
+  const std::string w = "mcs_eval_pcut_split: ";
+  if (!io) return fail(w + "null argument");
+  const long long n = io->n, cap_n = io->cap_n, guard = io->guard, out_cap = io->out_cap, exp_cap = io->exp_cap;
+  const int form = io->form;
+  if (form < 0 || form > 2) return fail(w + "unknown form " + std::to_string(form) + " (0, 1 or 2: include/mcs.h)");
+  if (n < 0 || cap_n < n) return fail(w + "n < 0 or n > cap_n");
+  if (guard < 0 || out_cap < 0 || guard > (1LL << 40) || out_cap > (1LL << 40)) return fail(w + "guard or out_cap out of range");
+  const long long total = 2 * guard + out_cap;
+  if (cap_n > 0) {
+    if (!io->l_save || !io->saved || !io->src) return fail(w + "null buffer");
+    for (auto f : kSoaF64) if (!(io->saved->*f)) return fail(w + "null buffer");
+    if (!io->saved->grid || !io->saved->tcut || !io->saved->downstream || !io->saved->inj) return fail(w + "null buffer");
+    if (io->src_fill < 0 || io->src_fill >= cap_n) return fail(w + "src_fill outside [0, cap_n)");
+  }
+  if (total > 0 && (!io->out_f64 || !io->out_meta)) return fail(w + "null buffer");
+  if (form != 0 && io->export_mode != 0) return fail(w + "export_mode only with form 0");
+  if (form == 0 && io->match != 1 && io->match != 5) return fail(w + "match must be 1 or 5");
+  if (form == 0 && (io->export_mode < 0 || io->export_mode > 2)) return fail(w + "unknown export_mode");
+  if (form != 1 && io->i_mult < 1) return fail(w + "i_mult < 1");
+  if (form == 1 && (io->n_target < 1 || cap_n < 1)) return fail(w + "n_target < 1 or cap_n < 1");
+  if (form == 2 && c->P.state_fp32) return fail(w + "the late form is not for the fp32-state variant");
+  if (form == 2 && io->n_main_next < 0) return fail(w + "n_main_next < 0");
+  for (long long k = 0; k < cap_n; ++k)
+    if (io->saved->grid[k] < 0 || io->saved->grid[k] > 0xffff || io->saved->tcut[k] < 0 || io->saved->tcut[k] > 0xff)
+      return fail(w + "a saved state's grid or tcut does not fit the packed word");
+  const unsigned int match = form == 0 ? (unsigned int)io->match : form == 1 ? 1u : 5u;
+  long long ns = 0;
+  for (long long k = 0; k < n; ++k) ns += io->l_save[k] == match;
+  const long long im = form == 1 ? (ns > 0 && io->n_target / ns > 1 ? io->n_target / ns : 1) : (long long)io->i_mult;
+  const long long off = form == 2 ? (long long)io->n_main_next : 0;
+  if (off > out_cap || (ns > 0 && im > (out_cap - off) / ns)) return fail(w + "the children do not fit out_cap");
+  const bool exporting = form == 0 && io->export_mode != 0, states = io->export_mode == 2;
+  if (exporting) {
+    if (exp_cap < ns || exp_cap > (1LL << 40)) return fail(w + "exp_cap < n_saved");
+    if (exp_cap > 0 && (!io->exp_gidx || (states && (!io->exp_f64 || !io->exp_meta)))) return fail(w + "null buffer");
+  }
+  // ---- nothing was changed so far
+  hipStream_t st = c->stream;
+  HIPCHK(hipStreamSynchronize(st));      // (queued work may still use the blocks that are freed)
+  if (ensure_capacity(c, cap_n) || reserve(c->spare, total) || reserve(c->fused, 1)) return 1;
+  if (exporting && reserve(c->d_stage, n + 9 * exp_cap + exp_cap / 2 + 2)) return 1;
+  c->n_run_last = -1; c->n_saved_last = 0; c->idx_gidx = nullptr;      // the saved arrays / src[] no longer describe a run
+  if (cap_n > 0) {
+    HIPCHK(hipMemcpyAsync(c->d_lsave, io->l_save, (size_t)cap_n, hipMemcpyHostToDevice, st));
+    if (upload_soa(c, c->sav, cap_n, io->saved)) return 1;
+    const std::vector<long long> stale((size_t)cap_n, (long long)io->src_fill);
+    HIPCHK(hipMemcpyAsync(c->scan.src, stale.data(), (size_t)cap_n * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  if (total > 0) {
+    for (int i = 0; i < 8; ++i) HIPCHK(hipMemsetAsync(c->spare.f[i], 0xA5, (size_t)total * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(c->spare.meta, 0xA5, (size_t)total * sizeof(uint32_t), st));
+  }
+  PcutDev h_pd[2] = {{form == 1 ? n : -7, -7, -7, -7}, {-7, -7, -7, -7}};
+  unsigned long long h_ctr[CTR_COUNT] = {};
+  if (form == 1) { h_ctr[CTR_WORK] = io->ctr_work; h_ctr[CTR_SAVED] = io->ctr_saved; }
+  HIPCHK(hipMemcpyAsync(c->fused.d_pd, h_pd, sizeof h_pd, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->d_counters, h_ctr, sizeof h_ctr, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const DevPop sav = pop_view(c->sav);
+  unsigned long long* const scan_total = c->d_counters + CTR_SCAN;
+  if (form == 0) {
+    HIPCHK(mcs_launch_compact_match(c->d_lsave, n, c->scan.bcounts, c->scan.boffs, scan_total, c->scan.src, match, st));
+    HIPCHK(hipMemcpyAsync(c->h_back + CTR_SCAN, scan_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const long long n_saved = (long long)c->h_back[CTR_SCAN];
+    if (n_saved != ns) return fail(w + format("the compaction counted %lld saved particles, the host %lld: the split was not run", n_saved, ns));
+    HIPCHK(mcs_launch_split(sav, pop_view(c->spare, guard), c->scan.src, n_saved * im, im, st));
+    if (exporting) {
+      long long* d_gin = (long long*)c->d_stage.get();
+      long long* d_gidx = d_gin + n;
+      double* d_f64 = c->d_stage + n + exp_cap;
+      uint32_t* d_meta = (uint32_t*)(c->d_stage + n + 9 * exp_cap);
+      if (io->exp_gin && n > 0) HIPCHK(hipMemcpyAsync(d_gin, io->exp_gin, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemsetAsync(d_gidx, 0xA5, (size_t)(9 * exp_cap + exp_cap / 2 + 1) * sizeof(double), st));
+      HIPCHK(mcs_launch_saved_export(sav, c->scan.src, n_saved, exp_cap, io->exp_first, io->exp_stride, io->exp_gin ? d_gin : nullptr, d_gidx,
+                                     states ? d_f64 : nullptr, states ? d_meta : nullptr, st));
+      if (exp_cap > 0) {
+        HIPCHK(hipMemcpyAsync(io->exp_gidx, d_gidx, (size_t)exp_cap * sizeof(long long), hipMemcpyDeviceToHost, st));
+        // (indices only: the state buffers, where the caller wants them, must come back as they were filled)
+        if (io->exp_f64) HIPCHK(hipMemcpyAsync(io->exp_f64, d_f64, (size_t)(8 * exp_cap) * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (io->exp_meta) HIPCHK(hipMemcpyAsync(io->exp_meta, d_meta, (size_t)exp_cap * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      }
+    }
+  } else if (form == 1) {
+    HIPCHK(mcs_launch_finalize_split_dev(c->d_lsave, cap_n, c->scan.bcounts, c->scan.boffs, scan_total, c->scan.src, c->fused.d_pd, c->fused.d_pd + 1,
+                                         c->d_counters, (long long)io->n_target, c->d_counters + CTR_MISMATCH, sav, pop_view(c->spare, guard),
+                                         split_blocks(c, cap_n, 16), st));
+  } else {
+    HIPCHK(mcs_launch_late_split(c->d_lsave, n, c->scan.bcounts, c->scan.boffs, scan_total, c->scan.src, c->fused.d_pd, im, off, sav,
+                                 pop_view(c->spare, guard + off), split_blocks(c, ns * im, 4), st));
+  }
+  if (cap_n > 0) HIPCHK(hipMemcpyAsync(io->src, c->scan.src, (size_t)cap_n * sizeof(long long), hipMemcpyDeviceToHost, st));
+  for (int i = 0; i < 8 && total > 0; ++i)
+    HIPCHK(hipMemcpyAsync(io->out_f64 + (size_t)i * (size_t)total, c->spare.f[i], (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (total > 0) HIPCHK(hipMemcpyAsync(io->out_meta, c->spare.meta, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h_pd, c->fused.d_pd, sizeof h_pd, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h_ctr, c->d_counters, sizeof h_ctr, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemsetAsync(c->d_counters, 0, sizeof h_ctr, st));
+  HIPCHK(hipStreamSynchronize(st));
+  io->scan_total = h_ctr[CTR_SCAN]; io->ctr_work_after = h_ctr[CTR_WORK]; io->ctr_saved_after = h_ctr[CTR_SAVED]; io->mismatch = h_ctr[CTR_MISMATCH];
+  for (int k = 0; k < 2; ++k) {
+    int64_t* o = k ? io->pd_next : io->pd;
+    o[0] = h_pd[k].n_use; o[1] = h_pd[k].n_saved; o[2] = h_pd[k].i_mult; o[3] = h_pd[k].n_new;
+  }
   return 0;
 }
 

@@ -415,3 +415,38 @@ class HipBackend:
         out = np.zeros((len(s), 5))
         self._chk(self.lib.mcs_eval_scatter(self.h, int(form), len(s), _dp(s), _dp(out)))
         return out
+
+    def eval_pcut_split(self, form: int, l_save, saved: Population, n=None, *, match=1, i_mult=1, n_target=1, ctr_work=0, ctr_saved=0,
+                        n_main_next=0, src_fill=0, guard=64, out_cap=0, export_mode=0, exp_cap=0, exp_first=0, exp_stride=1, exp_gin=None):
+        """The pcut bookkeeping kernels on the caller's status bytes and saved states (mcs_eval_pcut_split in include/mcs.h: form 0
+        host-sized, 1 device-sized, 2 late).  len(l_save) = saved.n is cap_n; n (default: all of them) the population size the kernels
+        are told.  Returns a dict: src [cap_n], scan_total, pd / pd_next (n_use, n_saved, i_mult, n_new), ctr_work, ctr_saved and
+        mismatch after the call, out_f64 [8][guard + out_cap + guard] and out_meta (the whole target, guards included), and with
+        export_mode 1 / 2 exp_gidx [exp_cap] (2: exp_f64 [8][exp_cap], exp_meta [exp_cap])."""
+        ls = np.ascontiguousarray(l_save, dtype=np.uint8)
+        cap_n = len(ls)
+        assert saved.n == cap_n
+        io = capi.McsPcutEval()
+        io.form, io.match, io.export_mode = int(form), int(match), int(export_mode)
+        io.n, io.cap_n, io.src_fill = cap_n if n is None else int(n), cap_n, int(src_fill)
+        io.i_mult, io.n_target, io.n_main_next = int(i_mult), int(n_target), int(n_main_next)
+        io.guard, io.out_cap, io.exp_cap, io.exp_first, io.exp_stride = int(guard), int(out_cap), int(exp_cap), int(exp_first), int(exp_stride)
+        io.ctr_work, io.ctr_saved = int(ctr_work), int(ctr_saved)
+        total = max(2 * int(guard) + int(out_cap), 0)
+        s = saved.soa()
+        src = np.zeros(cap_n, dtype=np.int64)
+        out_f64, out_meta = np.zeros((8, total)), np.zeros(total, dtype=np.uint32)
+        ne = max(int(exp_cap), 0) if export_mode else 0
+        exp_gidx, exp_f64, exp_meta = np.zeros(ne, dtype=np.int64), np.zeros((8, ne)), np.zeros(ne, dtype=np.uint32)
+        u32p = ct.POINTER(ct.c_uint32)
+        io.l_save, io.saved, io.src = ls.ctypes.data_as(c_uint8_p), ct.pointer(s), src.ctypes.data_as(c_int64_p)
+        io.out_f64, io.out_meta = _dp(out_f64), out_meta.ctypes.data_as(u32p)
+        io.exp_gidx, io.exp_f64, io.exp_meta = exp_gidx.ctypes.data_as(c_int64_p), _dp(exp_f64), exp_meta.ctypes.data_as(u32p)
+        if exp_gin is not None:
+            gin = np.ascontiguousarray(exp_gin, dtype=np.int64)
+            assert len(gin) >= io.n
+            io.exp_gin = gin.ctypes.data_as(c_int64_p)
+        self._chk(self.lib.mcs_eval_pcut_split(self.h, ct.byref(io)))
+        return dict(src=src, scan_total=int(io.scan_total), pd=[int(v) for v in io.pd], pd_next=[int(v) for v in io.pd_next],
+                    ctr_work=int(io.ctr_work_after), ctr_saved=int(io.ctr_saved_after), mismatch=int(io.mismatch),
+                    out_f64=out_f64, out_meta=out_meta, exp_gidx=exp_gidx, exp_f64=exp_f64, exp_meta=exp_meta)
