@@ -465,6 +465,47 @@ int mcs_dndp_2d(mcs_ctx* ctx, const mcs_consumer_in* in, double gam_x, double be
 int mcs_photon_ic(mcs_ctx* ctx, const double* mom_edge_cgs, double mc_e, int j_max, int n_nu, const double* alpha_in, const double* n_in, int n_photon,
                   double emin_mev, double bins_per_dec, double beam_area, double* energy_erg, double* emis);
 
+/* ---- observed shell spectra (K9): what an observer at Earth sees of one emission process -- the per-zone emission of a fold above
+ * turned into a photon flux, shifted from the plasma frame of every zone into the ISM frame, summed over the zones of every photon
+ * shell (the arithmetic of src/get_summed_emission.jl:37-413 as consumers.py restates it: S1-S6 there), on the device.
+ * Each of the three folds above keeps its emis[n_grid][n_photon] in a buffer of the context that nothing else writes, one per
+ * process, with a flag that records n_photon; a begin-species call, a write of the tally buffer and a photons sample of the ensemble
+ * statistics clear the flags.
+ * process: MCS_PHOTON_SYNCH, MCS_PHOTON_IC or MCS_PHOTON_PION.  All arrays are host arrays; the call looks nothing up itself:
+ *   emis            [n_grid][n_photon], or NULL: what the last fold of that process left on the context (refused when its flag is
+ *                   clear or records another n_photon)
+ *   energy_div      [n_photon] the energies the energy flux is divided by (MeV for synchrotron and inverse Compton, erg for pion decay)
+ *   energy_grid     [n_photon] the MeV grid of the Doppler step
+ *   area            4 pi d_L^2 (synchrotron, pion decay; the inverse-Compton fold has its beam area inside already and ignores it)
+ *   dlog, last_mid_ratio      the logarithmic bin width and 10^dlog as the host computes it
+ *   cos_edge        [181] the boundaries of the 180 slices in cos(theta), -1 .. 1
+ *   gam_ef, beta_ef, gam3_ef  [n_grid] each, zones 1..n_grid: the flow's Lorentz factor and speed against the ISM, and the host's gam^3
+ *                   (a table on purpose: a power function and g*g*g differ in the last bit)
+ *   shell_ends      [n_shells + 1] 1-based zone numbers, 0 = no zone: shell s holds zones shell_ends[s] .. shell_ends[s+1] - 1
+ * out [n_shells + 1][n], n = n_photon - 1 (the last energy of a spectrum is dropped): photons per bin of every shell, then of all
+ * shells, floor 1e-99; to the host (may be NULL), and kept on the device per process with a flag of its own (cleared like the others).
+ * Definition, every operation a separate rounding, / and sqrt correctly rounded, E = energy_grid, z a zone, j an energy < n:
+ *   1  flux  x = emis[z][j];  synchrotron: e = x / area, e = e > 1e-99 ? e : 1e-99, e = e > 1e-99 ? e / MeV : 1e-99;
+ *            inverse Compton: e = x > 1e-99 ? x / MeV : 1e-99;  pion decay: e = x / area, e = e >= 1e-99 ? e : 1e-99   (MeV = 1.602176634e-6 erg)
+ *            f = e <= 1e-99 ? 1e-99 : e / energy_div[j];   g = f > 1e-90 ? f * dlog : f
+ *   2  frame inverse Compton: nb[z][j] = g.  Otherwise num_j = g / 180; mid_j = sqrt(E[j] E[j+1]) for j < n - 1, mid_(n-1) =
+ *            mid_(n-2) * last_mid_ratio; fac_l = gam sqrt((1 - beta c_l)(1 - beta c_(l+1))); the target of (l, j) is the first m >= 1
+ *            with E[m] >= mid_j * fac_l, and the pair counts if num_j > 1e-99 and m < n.  acc_b = the serial sum, starting from 1e-99,
+ *            of num_j over the pairs with m - 1 = b, in ascending l and within l ascending j;  nb[z][b] = acc_b > 1e-95 ? acc_b * gam3 : 1e-99
+ *   3  shell s with lo = shell_ends[s] >= 1 and hi = shell_ends[s+1] - 1 >= lo: a = the serial sum from 0 over z = lo .. hi of
+ *            (nb[z][j] > 1e-95 ? nb[z][j] : 0); out[s][j] = a > 1e-99 ? a : 1e-99.  Otherwise out[s][j] = 1e-99
+ *   4  out[n_shells][j]: the serial sum from 0 over s of (out[s][j] > 1e-99 ? out[s][j] : 0), then the same floor.
+ * Step 2 is a scatter as written; the device gathers in the same order (no atomics: the same input gives the same bits).
+ * The emission itself is not checked: a NaN is no flux (every comparison of step 1 is false for it), +infinity stays one.
+ * Refused, with a message and nothing changed: a null context or table, a process outside the three, n_photon outside 3..256 (a
+ * zone's tables live in LDS), n_shells outside 1..4096, a clear flag with emis = NULL, a non-finite or non-positive energy, area, dlog
+ * or gam, last_mid_ratio not finite or below 1, beta outside [0, 1), gam3 or a slice boundary not finite, a boundary outside [-1, 1],
+ * energies that decrease, a shell end outside 0 .. n_grid + 1. */
+enum { MCS_PHOTON_SYNCH = 0, MCS_PHOTON_IC = 1, MCS_PHOTON_PION = 2 };
+int mcs_photon_observe(mcs_ctx* ctx, int process, int n_photon, const double* emis, const double* energy_div, const double* energy_grid,
+                       double area, double dlog, double last_mid_ratio, const double* cos_edge, const double* gam_ef, const double* beta_ef,
+                       const double* gam3_ef, int n_shells, const int64_t* shell_ends, double* out);
+
 /* ---- ensemble statistics (K8): per-word mean and standard error over the iterations of a fixed-profile run --------------------
  * With a fixed shock profile the iterations of a run are independent realisations.  An accumulator keeps, on the device, a running
  * mean and a sum of squared deviations M2 of every word of a SAMPLE vector, per slot; a slot takes species samples or iteration
@@ -626,6 +667,40 @@ typedef struct mcs_ens_products_layout {
 int mcs_ens_products_get_layout(const mcs_params* p, mcs_ens_products_layout* out);      /* needs no GPU */
 int mcs_ens_set_slope_window(mcs_ens* ens, int l_lo, int l_hi, const double* x_log);
 int mcs_ens_add_products(mcs_ens* ens, mcs_ctx* src, int species_slot);
+
+/* ---- photons sample: error bars of the photon spectra at Earth.  A shell spectrum is a sum over zones, slices and processes: its
+ * variance does not follow from per-cell variances, so the spectrum itself is sampled once per iteration, from what
+ * mcs_photon_observe left on a context.
+ * Every species slot s has a second companion, the PHOTONS slot MCS_ENS_PHOTONS(s), in the count, read, summarize, summarize-merged
+ * and compare calls.  Like the products slot it is allocated at its first sample: an accumulator that never takes one costs no
+ * more memory and behaves as before.
+ * mcs_ens_set_photon_layout fixes the sample vector: n_shells shells (rows = n_shells + 1, the last row all shells), the energy words
+ * per process n_synch, n_ic, n_pion (the n = n_photon - 1 of mcs_photon_observe), their offsets start_* on the common energy grid
+ * and its length n_pts (the stock run: 179, 139, 119 at 0, 110, 130 of 250).  It needs 1 <= n_shells <= 4096, 1 <= n <= 255 and
+ * 0 <= start, start + n <= n_pts <= 65536; it may be called again until the first photons sample (or merge) of any slot and is
+ * refused afterwards.  The vector has four sections, mcs_ens_photons_layout:
+ *   synch, ic, pion   [rows][n] each: the last mcs_photon_observe of that process on the context; a process not observed there since
+ *                     the last begin-species call, tally write or photons sample enters as 1e-99 throughout
+ *   total             [rows][n_pts]: total[s][t], s < n_shells, starts at 1e-99 and adds (x > 1e-99 ? x : 0) of x = pion[s][t - start_pion],
+ *                     synch[s][t - start_synch], ic[s][t - start_ic], in that order, where t lies in the process' window; the last
+ *                     row is the serial sum from 0 over s, ascending, of total[s][t] as they stand, floors included
+ * mcs_ens_add_photons: one sample; the update is that of every slot.  Refused unless the context holds at least one observation,
+ * when an observation's shells or energy words differ from the layout, without a layout, and for what mcs_ens_add_products refuses.
+ * Queued on src's stream behind the accumulator's event, no host synchronisation; it clears the context's photon flags.
+ * mcs_ens_merge merges the photons slots that src has, allocating in dst where needed; a dst without a layout takes src's.  A merge,
+ * a comparison or a merged summary of a photons slot of accumulators that both have a layout is refused when the layouts differ.  A
+ * photons slot that was never sampled has count 0, and its reads are refused.  mcs_ens_load_mean takes species slots only. */
+#define MCS_ENS_PHOTONS(s) ((s) | (1 << 29))
+typedef struct mcs_ens_photons_layout {
+  int64_t synch, ic, pion, total_section;                   /* offsets, in doubles */
+  int64_t n_synch, n_ic, n_pion, n_pts;                     /* the row length of each section */
+  int64_t rows;                                             /* n_shells + 1 */
+  int64_t total;
+} mcs_ens_photons_layout;
+int mcs_ens_photons_get_layout(int n_shells, int n_synch, int n_ic, int n_pion, int n_pts, mcs_ens_photons_layout* out);      /* needs no GPU */
+int mcs_ens_set_photon_layout(mcs_ens* ens, int n_shells, int n_synch, int n_ic, int n_pion, int start_synch, int start_ic, int start_pion,
+                              int n_pts);
+int mcs_ens_add_photons(mcs_ens* ens, mcs_ctx* src, int species_slot);
 
 /* ---- comparison of two slots: does run B agree with run A within their error bars?  Per-word z-scores and their chi-square,
  * reduced on the device.  Slot slot_a of accumulator a (A, n_a >= 2 samples) against slot slot_b of b (B, n_b >= 2): two slots of

@@ -98,6 +98,14 @@ class McsEnsProductsLayout(ct.Structure):
 ENS_PRODUCTS_BIT = 1 << 30      # MCS_ENS_PRODUCTS(s) = s | ENS_PRODUCTS_BIT
 
 
+class McsEnsPhotonsLayout(ct.Structure):
+    """`mcs_ens_photons_layout`: offsets and row lengths of the four sections of a photons sample (include/mcs.h, "photons sample")."""
+    _fields_ = [(name, ct.c_int64) for name in ("synch", "ic", "pion", "total_section", "n_synch", "n_ic", "n_pion", "n_pts", "rows", "total")]
+
+
+ENS_PHOTONS_BIT = 1 << 29       # MCS_ENS_PHOTONS(s) = s | ENS_PHOTONS_BIT
+
+
 class McsEnsRange(ct.Structure):
     """`mcs_ens_range`: a word range of a slot's sample vector, with the floor and the tolerance of its summary (include/mcs.h)."""
     _fields_ = [("first", ct.c_int64), ("count", ct.c_int64), ("floor_frac", ct.c_double), ("tol", ct.c_double)]
@@ -339,6 +347,8 @@ def load_library() -> ct.CDLL:
         "mcs_dndp_2d": (i32, [vp, ct.POINTER(McsConsumerIn), dbl, dbl, c_double_p]),
         "mcs_photon_ic": (i32, [vp, c_double_p, dbl, i32, i32, c_double_p, c_double_p, i32, dbl, dbl, dbl, c_double_p, c_double_p]),
         "mcs_photon_pion": (i32, [vp, c_double_p, c_double_p, dbl, dbl, c_double_p, dbl, i32, i32, dbl, dbl, c_double_p, c_double_p]),
+        "mcs_photon_observe": (i32, [vp, i32, i32, c_double_p, c_double_p, c_double_p, dbl, dbl, dbl, c_double_p, c_double_p, c_double_p, c_double_p,
+                               i32, c_int64_p, c_double_p]),
         "mcs_accumulate_tallies": (i32, [vp, vp]),
         "mcs_k1_blocks_per_cu": (i32, [vp]),
         "mcs_option_count": (i32, []),
@@ -361,6 +371,9 @@ def load_library() -> ct.CDLL:
         "mcs_ens_products_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsEnsProductsLayout)]),
         "mcs_ens_set_slope_window": (i32, [vp, i32, i32, c_double_p]),
         "mcs_ens_add_products": (i32, [vp, vp, i32]),
+        "mcs_ens_photons_get_layout": (i32, [i32, i32, i32, i32, i32, ct.POINTER(McsEnsPhotonsLayout)]),
+        "mcs_ens_set_photon_layout": (i32, [vp] + [i32] * 8),
+        "mcs_ens_add_photons": (i32, [vp, vp, i32]),
         "mcs_ens_compare": (i32, [vp, i32, vp, i32, i32, ct.POINTER(McsEnsCmpRange), ct.POINTER(McsEnsDifference)]),
     }
     for name, (res, args) in sig.items():
@@ -415,3 +428,6 @@ EXPORTED_SYMBOLS += [
     "mcs_ens_summarize_merged", "mcs_ens_products_get_layout", "mcs_ens_set_slope_window", "mcs_ens_add_products",
     "mcs_ens_compare",
 ]
+# the observed shell spectra (K9)
+EXPORTED_SYMBOLS += ["mcs_photon_observe", "mcs_ens_photons_get_layout", "mcs_ens_set_photon_layout", "mcs_ens_add_photons"]
+PHOTON_PROCESS = {"synch": 0, "ic": 1, "pion": 2}      # MCS_PHOTON_SYNCH, _IC, _PION

@@ -297,6 +297,7 @@ class PhotonPion:
     photon_flux: np.ndarray        # [n_grid][n_photon]  energy_flux / E, floor 1e-99
     pion_photon_sum: np.ndarray    # [n_grid][n_photon]  this species' term of the array get_summed_emission reads (:118-125)
     n_pion_specs: int              # nuclei species of the run (:69)
+    energy_erg: object = None      # [n_photon]  the energies as the fold returned them (the photon flux is divided by these)
 
 
 def pion_scaling_factor(cfg, aa: float) -> float:
@@ -327,7 +328,7 @@ def photon_pion(prob, backend, ion_fin: IonFinal, i_ion: int, jet_dist_kpc: floa
     eflux = np.where(lit, eflux, 1.0e-99)
     psum = np.where(lit, eflux / E_erg[None, :], 0.0)
     pflux = np.where(eflux <= 1.0e-99, 1.0e-99, eflux / E_erg[None, :])
-    return PhotonPion(E_erg / MEV_ERG, emis, eflux, pflux, psum, sum(1 for s in cfg.species if s.aa >= 1))
+    return PhotonPion(E_erg / MEV_ERG, emis, eflux, pflux, psum, sum(1 for s in cfg.species if s.aa >= 1), E_erg)
 
 
 # ---- get_summed_emission (src/get_summed_emission.jl:37-413): the arithmetic of it ------------------------------------------------------
@@ -451,3 +452,217 @@ def summed_emission(prob, n_shell_endpoints, pion: PhotonPion = None, synch: Pho
 def _takes_download(backend) -> bool:
     import inspect
     return "download" in inspect.signature(backend.dndp_2d).parameters
+
+
+# ---- the observed shell spectra (K9; include/mcs.h "observed shell spectra"): what `summed_emission` computes, per process and as numbers
+# (not log10), from the emission a fold returns -- on the device where the backend has `photon_observe`, else by `shell_spectra_host`,
+# the numpy statement of the same definition.  Every word of the two is required to have the same bits (tests/test_gpu_photon_observed.py).
+PHOTON_PROCESSES = ("synch", "ic", "pion")           # the order of the sections of a photons sample (ensemble.py)
+
+
+def photon_flux_host(process: str, emis, energy_div, area):
+    """Step 1: the photon flux at Earth per d(log E), floor 1e-99, as `photon_synch` (:197-199), `photon_ic` (:281-282) and `photon_pion`
+    (:325-329) convert their emission."""
+    emis = np.asarray(emis, dtype=np.float64); E = np.asarray(energy_div, dtype=np.float64)
+    if process == "synch":
+        flux_erg = emis / area
+        flux_erg = np.where(flux_erg > 1.0e-99, flux_erg, 1.0e-99)          # (as the definition reads: a NaN becomes the floor)
+        eflux = np.where(flux_erg > 1.0e-99, flux_erg / MEV_ERG, 1.0e-99)
+    elif process == "ic":
+        eflux = np.where(emis > 1.0e-99, emis / MEV_ERG, 1.0e-99)
+    elif process == "pion":
+        eflux = emis / area
+        eflux = np.where(eflux >= 1.0e-99, eflux, 1.0e-99)
+    else:
+        raise ValueError(f"photon process {process!r}: one of {PHOTON_PROCESSES}")
+    return np.where(eflux <= 1.0e-99, 1.0e-99, eflux / E[None, :])
+
+
+def shell_spectra_host(process: str, emis, energy_div, energy_grid, area, dlog, last_mid_ratio, cos_edge, gam_ef, beta_ef, gam3_ef, shell_ends,
+                       flux=None):
+    """The definition of mcs_photon_observe in numpy: photons per bin [n_shells + 1][n_photon - 1] of every shell and, last row, of all
+    shells, floor 1e-99.  The arguments are those of HipBackend.photon_observe; flux (the [n_grid][n_photon] result of step 1) may be
+    given in place of emis.  The Doppler step is `doppler_to_ism` with the caller's tables; np.add.at adds in ascending slice and,
+    within a slice, ascending energy -- the order the device gathers in."""
+    if process not in PHOTON_PROCESSES:
+        raise ValueError(f"photon process {process!r}: one of {PHOTON_PROCESSES}")
+    if flux is None:
+        flux = photon_flux_host(process, emis, energy_div, area)
+    f = np.asarray(flux, dtype=np.float64)[:, :-1]               # the last energy of a spectrum is not written out (:431-432)
+    E = np.asarray(energy_grid, dtype=np.float64)[:-1]
+    nz, n = f.shape
+    ends = np.asarray(shell_ends, dtype=np.int64)
+    n_shells = len(ends) - 1
+    if process == "ic":
+        nb = np.where(f > 1.0e-90, f * dlog, f)                  # S5
+    else:
+        cos_e = np.asarray(cos_edge, dtype=np.float64)
+        n_cos = len(cos_e) - 1
+        mid = np.empty(n)
+        mid[:-1] = np.sqrt(E[:-1] * E[1:]); mid[-1] = mid[-2] * last_mid_ratio
+        nb = np.full((nz, n), 1.0e-99)
+        for i in range(nz):
+            num = np.where(f[i] > 1.0e-90, f[i] * dlog, f[i]) / n_cos
+            fac = gam_ef[i] * np.sqrt((1 - beta_ef[i] * cos_e[:-1]) * (1 - beta_ef[i] * cos_e[1:]))
+            Et = mid[None, :] * fac[:, None]
+            m = np.maximum(np.searchsorted(E, Et, side="left"), 1)
+            ok = (num[None, :] > 1.0e-99) & (m < n)
+            np.add.at(nb[i], (m - 1)[ok], np.broadcast_to(num[None, :], Et.shape)[ok])
+            nb[i] = np.where(nb[i] > 1.0e-95, nb[i] * gam3_ef[i], 1.0e-99)
+    out = np.full((n_shells + 1, n), 1.0e-99)
+    allsh = np.zeros(n)
+    for s in range(n_shells):
+        lo, hi = int(ends[s]), int(ends[s + 1]) - 1
+        if lo >= 1 and hi >= lo:
+            a = np.where(nb[lo - 1:hi] > 1.0e-95, nb[lo - 1:hi], 0.0).sum(axis=0)      # S6
+            out[s] = np.where(a > 1.0e-99, a, 1.0e-99)
+        allsh = allsh + np.where(out[s] > 1.0e-99, out[s], 0.0)
+    out[n_shells] = np.where(allsh > 1.0e-99, allsh, 1.0e-99)
+    return out
+
+
+@dataclasses.dataclass
+class PhotonSetup:
+    """What the observed spectra need beyond the run itself: the photon shells (`photon_shells`) and the source's distance."""
+    num_upstream_shells: int
+    num_downstream_shells: int
+    jet_dist_kpc: float = 1.0e6
+    redshift: float = 0.0
+    jet_sph_frac: object = None
+
+    @property
+    def n_shells(self) -> int:
+        return int(self.num_upstream_shells) + int(self.num_downstream_shells)
+
+
+@dataclasses.dataclass
+class PhotonLayout:
+    """The photons sample of the ensemble statistics (mcs_ens_set_photon_layout): energies per process and their offsets on the common
+    grid of `summed_emission` (:442)."""
+    n_shells: int
+    n: dict            # process -> energy words (n_photon - 1)
+    start: dict        # process -> offset on the common grid
+    n_pts: int
+
+    def args(self):
+        return (self.n_shells, *(int(self.n[p]) for p in PHOTON_PROCESSES), *(int(self.start[p]) for p in PHOTON_PROCESSES), self.n_pts)
+
+    @property
+    def rows(self) -> int:
+        return self.n_shells + 1
+
+    def offsets(self) -> dict:
+        """section -> (first word, row length) of the sample vector: synch, ic, pion, total; `total` the length of the vector."""
+        o, out = 0, {}
+        for name in PHOTON_PROCESSES + ("total",):
+            w = self.n_pts if name == "total" else int(self.n[name])
+            out[name] = (o, w)
+            o += self.rows * w
+        out["_total"] = o
+        return out
+
+
+def photon_e_min(process: str) -> float:
+    return {"synch": PHOTON_E_MIN_MEV, "ic": PHOTON_IC_E_MIN_MEV, "pion": PHOTON_PION_E_MIN_MEV}[process]
+
+
+def photon_n_photon(process: str) -> int:
+    e_max = PHOTON_SYNCH_E_MAX_MEV if process == "synch" else PHOTON_E_MAX_MEV
+    return int(math.log10(e_max / photon_e_min(process)) * PHOTON_BINS_PER_DEC)      # photon_calcs.jl:49-51
+
+
+def stock_photon_layout(n_shells: int) -> PhotonLayout:
+    """The layout of the stock energy grids: 179 / 139 / 119 words at offsets 0 / 110 / 130 of 250."""
+    n = {p: photon_n_photon(p) - 1 for p in PHOTON_PROCESSES}
+    start = {p: int(math.log10(photon_e_min(p) / PHOTON_E_MIN_MEV) * PHOTON_BINS_PER_DEC) for p in PHOTON_PROCESSES}
+    n_pts = int((math.log10(PHOTON_E_MAX_MEV) - math.log10(PHOTON_E_MIN_MEV)) * PHOTON_BINS_PER_DEC)
+    return PhotonLayout(int(n_shells), n, start, n_pts)
+
+
+def photon_total(per_process: dict, layout: PhotonLayout) -> np.ndarray:
+    """The total section of a photons sample, [n_shells + 1][n_pts]: per shell 1e-99 plus the lit words of pion decay, synchrotron and
+    inverse Compton, in that order, at their offsets (S4); the last row the serial sum of the shell rows as they stand, floors included
+    (`tot_sh.sum(axis=0)` of `summed_emission`)."""
+    ns = layout.n_shells
+    tot = np.full((ns + 1, layout.n_pts), 1.0e-99)
+    for name in ("pion", "synch", "ic"):
+        sh = per_process.get(name)
+        if sh is None:
+            continue
+        a = layout.start[name]
+        tot[:ns, a:a + sh.shape[1]] += np.where(sh[:ns] > 1.0e-99, sh[:ns], 0.0)
+    tot[ns] = tot[:ns].sum(axis=0)
+    return tot
+
+
+@dataclasses.dataclass
+class ObservedSpectra:
+    """The photon spectra at Earth of one species: photons / (cm^2 s) per BIN, linear, floor 1e-99."""
+    processes: tuple               # the processes that were observed, in the order of PHOTON_PROCESSES
+    per_process: dict              # name -> [n_shells + 1][n]; the last row is the sum over the shells
+    energy_MeV: dict               # name -> [n] the energies of its words
+    total: np.ndarray              # [n_shells + 1][n_pts] all processes on the common grid
+    log_energy_MeV: np.ndarray     # [n_pts] the common grid
+    layout: PhotonLayout
+    dlog: float
+
+    def per_dlog(self) -> "ObservedSpectra":
+        """The same per d(log10 E)."""
+        return dataclasses.replace(self, per_process={k: v / self.dlog for k, v in self.per_process.items()}, total=self.total / self.dlog)
+
+    def sample(self) -> np.ndarray:
+        """The sample vector of the ensemble statistics: synch | ic | pion | total, an absent process 1e-99 throughout."""
+        parts = []
+        for name in PHOTON_PROCESSES:
+            a = self.per_process.get(name)
+            parts.append((np.full((self.layout.rows, self.layout.n[name]), 1.0e-99) if a is None else a).ravel())
+        parts.append(self.total.ravel())
+        return np.concatenate(parts)
+
+
+def observe_tables(prob, setup: PhotonSetup, process: str, energy_MeV) -> dict:
+    """The host tables of one mcs_photon_observe call, as keyword arguments of HipBackend.photon_observe / shell_spectra_host."""
+    n = prob.params.n_grid
+    gam = np.ascontiguousarray(np.asarray(prob.gam_ef, dtype=np.float64)[1:n + 1])
+    beta = np.ascontiguousarray(np.asarray(prob.beta_ef, dtype=np.float64)[1:n + 1])
+    E_MeV = np.ascontiguousarray(energy_MeV, dtype=np.float64)
+    dist_lum = setup.jet_dist_kpc * (1 + setup.redshift) * KPC_CM
+    dlog = 1.0 / PHOTON_BINS_PER_DEC
+    _, zones = photon_shells(prob, setup.num_upstream_shells, setup.num_downstream_shells)
+    return dict(energy_div=E_MeV * MEV_ERG if process == "pion" else E_MeV, energy_grid=E_MeV, area=4 * math.pi * dist_lum ** 2, dlog=dlog,
+                last_mid_ratio=10.0 ** dlog, cos_edge=np.linspace(-1.0, 1.0, N_COS_BINS_DOPPLER + 1), gam_ef=gam, beta_ef=beta,
+                gam3_ef=gam ** 3, shell_ends=zones)
+
+
+def observed_spectra(prob, backend, i_ion: int, setup: PhotonSetup, ion_fin: IonFinal) -> ObservedSpectra:
+    """The photon spectra at Earth of species i_ion from the tallies on the backend: its folds (electrons: synchrotron, get_dNdp_2D and
+    inverse Compton; nuclei: pion decay), then frame, shells and common grid -- on the device where the backend has `photon_observe`
+    (K9 reads the emission where the fold left it; the shell spectra come back and also stay there for Ensemble.add_photons), else
+    through `shell_spectra_host`.  The folds themselves are the existing calls: they still hand their per-zone emission to the host."""
+    sp = prob.cfg.species[i_ion - 1]
+    kw = dict(jet_dist_kpc=setup.jet_dist_kpc, redshift=setup.redshift)
+    folds = {}
+    if sp.aa < 1:
+        folds["synch"] = photon_synch(prob, backend, ion_fin, i_ion, **kw)
+        folds["ic"] = photon_ic(prob, backend, i_ion, jet_sph_frac=setup.jet_sph_frac, **kw)
+    else:
+        folds["pion"] = photon_pion(prob, backend, ion_fin, i_ion, **kw)
+    on_device = hasattr(backend, "photon_observe")
+    per, energy = {}, {}
+    for name in PHOTON_PROCESSES:
+        if name not in folds:
+            continue
+        ph = folds[name]
+        tabs = observe_tables(prob, setup, name, ph.energy_MeV)
+        if name == "pion":       # (photon_pion keeps its energies in MeV; its flux is divided by the erg values the fold returned)
+            tabs["energy_div"] = np.ascontiguousarray(ph.energy_erg)
+        if on_device:
+            per[name] = backend.photon_observe(name, **tabs)
+        else:
+            emis = ph.emis_erg if name == "ic" else ph.emis_erg_s
+            per[name] = shell_spectra_host(name, emis, **tabs)
+        energy[name] = np.asarray(ph.energy_MeV)[:-1]
+    layout = stock_photon_layout(setup.n_shells)
+    dlog = 1.0 / PHOTON_BINS_PER_DEC
+    grid = math.log10(PHOTON_E_MIN_MEV) + dlog * np.arange(layout.n_pts)
+    return ObservedSpectra(tuple(per), per, energy, photon_total(per, layout), grid, layout, dlog)

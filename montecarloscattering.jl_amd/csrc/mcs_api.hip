@@ -168,9 +168,17 @@ struct mcs_ctx {
   DevBuf<double> d_ctab, d_cout, d_cscratch; DevBuf<unsigned long long> d_cdiag;
   // d_cout holds the result of a whole mcs_dndp_cr / mcs_thermo_calcs: each consumer sets its own flag, mcs_begin_species and a
   // products sample of the ensemble statistics (mcs_ens_add_products) clear both.  No other call writes d_cout: mcs_dndp_2d writes
-  // d_cscratch and d_c2d (consumers_ready only sizes d_cout, whose size never changes), the photon folds work in d_stage.
+  // d_cscratch and d_c2d (consumers_ready only sizes d_cout, whose size never changes), the photon folds stage their inputs in d_stage and
+  // write d_pemis (below).
   bool have_cout_dndp = false, have_cout_thermo = false;
   DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
+  // K9, per process (MCS_PHOTON_SYNCH / _IC / _PION): d_pemis the emis[n_grid][n_photon] its fold left (pemis_n: that n_photon, 0 =
+  // nothing), d_pobs the [n_shells+1][n] of the last mcs_photon_observe (pobs_n: its n, 0 = nothing; pobs_shells).  Only those calls
+  // write them; mcs_begin_species, the tally writes and a photons sample of the ensemble statistics clear the flags (photon_flags_clear).
+  // d_ptab / d_pnb: the tables and the per-zone spectra of one mcs_photon_observe.
+  DevBuf<double> d_pemis[3], d_pobs[3], d_ptab, d_pnb;
+  int pemis_n[3] = {0, 0, 0}, pobs_n[3] = {0, 0, 0}, pobs_shells[3] = {0, 0, 0};
+  void photon_flags_clear() { for (int p = 0; p < 3; ++p) pemis_n[p] = pobs_n[p] = pobs_shells[p] = 0; }
   // launch
   int blocks = 0, threads = 256;
   Event ev0, ev1;
@@ -441,6 +449,7 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
   c->i_iter = i_iter; c->i_ion = i_ion; c->aa = aa; c->zzq = zz * MCS_QCGS; c->m = aa * MCS_MP; c->mc = c->m * MCS_C;
   c->pmax_cutoff = pmax_cutoff; c->density = density; c->ewf = ewf;
   c->have_cout_dndp = c->have_cout_thermo = false;
+  c->photon_flags_clear();
   if (fold_replicas(c)) return 1;      // (the previous species' replicas, before its histograms are cleared)
   const long long npsd = c->L.psd_stride_zone * P.n_grid;
   const long long pm = MCS_PSD_MAX + 1;
@@ -1229,6 +1238,7 @@ int mcs_write_tallies_part(mcs_ctx* c, int64_t first, int64_t count, const doubl
   MCS_ENTER(c);
   if (first < 0 || count < 0 || first + count > c->L.total || (count > 0 && !host_f64)) return fail("mcs_write_tallies_part: range outside the tally buffer");
   if (fold_replicas(c)) return 1;
+  c->photon_flags_clear();
   if (count > 0) HIPCHK(hipMemcpyAsync(c->d_T + first, host_f64, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -1236,6 +1246,7 @@ int mcs_write_tallies_part(mcs_ctx* c, int64_t first, int64_t count, const doubl
 int mcs_write_tallies(mcs_ctx* c, const double* host_f64, const int64_t* host_i64) {
   MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
+  c->photon_flags_clear();
   if (host_f64) HIPCHK(hipMemcpyAsync(c->d_T, host_f64, (size_t)c->L.total * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (host_i64) HIPCHK(hipMemcpyAsync(c->d_I, host_i64, (size_t)mcs_i64_total(&c->P) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1501,8 +1512,9 @@ int mcs_photon_synch(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_c
   const int NM = c->P.num_psd_mom_bins + 2, ng = c->P.n_grid;
   if (NM > 208) return fail("mcs_photon_synch: too many momentum bins");
   const size_t n_in = (size_t)ng * NM + NM, n_out = (size_t)ng * n_photon;
-  if (reserve(c->d_stage, (long long)(n_in + n_out) + 4)) return 1;
-  double* d_in = c->d_stage; double* d_out = c->d_stage + n_in;
+  if (reserve(c->d_stage, (long long)n_in + 4) || reserve(c->d_pemis[MCS_PHOTON_SYNCH], (long long)n_out)) return 1;
+  c->pemis_n[MCS_PHOTON_SYNCH] = 0;
+  double* d_in = c->d_stage; double* d_out = c->d_pemis[MCS_PHOTON_SYNCH];      // (kept for mcs_photon_observe)
   HIPCHK(hipMemcpyAsync(d_in, dNdp_pf, sizeof(double) * (size_t)ng * NM, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_in + (size_t)ng * NM, mom_edge_cgs, sizeof(double) * NM, hipMemcpyHostToDevice, c->stream));
   const double log_emin = std::log10(emin_mev * MCS_MEV_ERG_);
@@ -1510,6 +1522,7 @@ int mcs_photon_synch(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_c
   HIPCHK(hipMemcpyAsync(emis, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (energy_erg) for (int j = 0; j < n_photon; ++j) energy_erg[j] = std::pow(10.0, log_emin + j * (1.0 / bins_per_dec));
+  c->pemis_n[MCS_PHOTON_SYNCH] = n_photon;
   return 0;
 }
 
@@ -1525,8 +1538,9 @@ int mcs_photon_pion(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_cg
   const int NM = c->P.num_psd_mom_bins + 2, ng = c->P.n_grid;
   if (NM > 208) return fail("mcs_photon_pion: too many momentum bins");
   const size_t n_in = (size_t)ng * NM + NM + ng, n_out = (size_t)ng * n_photon;
-  if (reserve(c->d_stage, (long long)(n_in + n_out) + 4)) return 1;
-  double* d_in = c->d_stage; double* d_out = c->d_stage + n_in;
+  if (reserve(c->d_stage, (long long)n_in + 4) || reserve(c->d_pemis[MCS_PHOTON_PION], (long long)n_out)) return 1;
+  c->pemis_n[MCS_PHOTON_PION] = 0;
+  double* d_in = c->d_stage; double* d_out = c->d_pemis[MCS_PHOTON_PION];       // (kept for mcs_photon_observe)
   HIPCHK(hipMemcpyAsync(d_in, dNdp_pf, sizeof(double) * (size_t)ng * NM, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_in + (size_t)ng * NM, mom_edge_cgs, sizeof(double) * NM, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_in + (size_t)ng * NM + NM, target_density, sizeof(double) * ng, hipMemcpyHostToDevice, c->stream));
@@ -1536,6 +1550,7 @@ int mcs_photon_pion(mcs_ctx* c, const double* dNdp_pf, const double* mom_edge_cg
   HIPCHK(hipMemcpyAsync(emis, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (energy_erg) for (int j = 0; j < n_photon; ++j) energy_erg[j] = std::pow(10.0, log_emin + j * (1.0 / bins_per_dec));
+  c->pemis_n[MCS_PHOTON_PION] = n_photon;
   return 0;
 }
 
@@ -1577,8 +1592,9 @@ int mcs_photon_ic(mcs_ctx* c, const double* mom_edge_cgs, double mc_e, int j_max
       !(mc_e > 0) || !(beam_area > 0))
     return fail("mcs_photon_ic: bad arguments");
   const size_t n_in_w = (size_t)NM + 2 * (size_t)n_nu, n_out = (size_t)ng * n_photon;
-  if (reserve(c->d_stage, (long long)(n_in_w + n_out) + 4)) return 1;
-  double* d_in = c->d_stage; double* d_out = c->d_stage + n_in_w;
+  if (reserve(c->d_stage, (long long)n_in_w + 4) || reserve(c->d_pemis[MCS_PHOTON_IC], (long long)n_out)) return 1;
+  c->pemis_n[MCS_PHOTON_IC] = 0;
+  double* d_in = c->d_stage; double* d_out = c->d_pemis[MCS_PHOTON_IC];         // (kept for mcs_photon_observe)
   HIPCHK(hipMemcpyAsync(d_in, mom_edge_cgs, sizeof(double) * NM, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_in + NM, alpha_in, sizeof(double) * n_nu, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_in + NM + n_nu, n_in, sizeof(double) * n_nu, hipMemcpyHostToDevice, c->stream));
@@ -1587,6 +1603,68 @@ int mcs_photon_ic(mcs_ctx* c, const double* mom_edge_cgs, double mc_e, int j_max
   HIPCHK(hipMemcpyAsync(emis, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (energy_erg) for (int k = 0; k < n_photon; ++k) energy_erg[k] = mcs_ic_alpha_out(log_min_rm, bins_per_dec, k) * (MCS_ME * MCS_C * MCS_C);
+  c->pemis_n[MCS_PHOTON_IC] = n_photon;
+  return 0;
+}
+
+// K9: the observed shell spectra of one emission process (include/mcs.h has the definition and the refusals).  Everything is checked
+// before anything is queued or changed.
+int mcs_photon_observe(mcs_ctx* c, int process, int n_photon, const double* emis, const double* energy_div, const double* energy_grid, double area,
+                       double dlog, double last_mid_ratio, const double* cos_edge, const double* gam_ef, const double* beta_ef, const double* gam3_ef,
+                       int n_shells, const int64_t* shell_ends, double* out) {
+  MCS_ENTER(c);
+  const std::string who = "mcs_photon_observe: ";
+  if (process != MCS_PHOTON_SYNCH && process != MCS_PHOTON_IC && process != MCS_PHOTON_PION) return fail(who + "process must be MCS_PHOTON_SYNCH, _IC or _PION");
+  if (!energy_div || !energy_grid || !cos_edge || !gam_ef || !beta_ef || !gam3_ef || !shell_ends) return fail(who + "null table");
+  if (n_photon < 3 || n_photon > 256) return fail(who + format("n_photon = %d; the kernel holds a zone's tables in LDS and takes 3..256 energies", n_photon));
+  if (n_shells < 1 || n_shells > 4096) return fail(who + "n_shells must be 1..4096");
+  if (!emis && c->pemis_n[process] == 0)
+    return fail(who + "no emission of this process on the context (its fold has not run since the last mcs_begin_species, tally write or photons sample)");
+  if (!emis && c->pemis_n[process] != n_photon)
+    return fail(who + format("the fold of this process left %d energies on the context, the call names %d", c->pemis_n[process], n_photon));
+  const int ng = c->P.n_grid, n = n_photon - 1;
+  const bool shifted = process != MCS_PHOTON_IC;
+  if (!(dlog > 0) || !std::isfinite(dlog)) return fail(who + "dlog must be positive and finite");
+  if (!(last_mid_ratio >= 1) || !std::isfinite(last_mid_ratio)) return fail(who + "last_mid_ratio must be finite and at least 1");
+  if (shifted && (!(area > 0) || !std::isfinite(area))) return fail(who + "area must be positive and finite");
+  for (int j = 0; j < n_photon; ++j) {
+    if (!(energy_div[j] > 0) || !std::isfinite(energy_div[j]) || !(energy_grid[j] > 0) || !std::isfinite(energy_grid[j]))
+      return fail(who + format("energy %d is not positive and finite", j));
+    if (j > 0 && energy_grid[j] < energy_grid[j - 1]) return fail(who + format("energy_grid decreases at entry %d", j));
+  }
+  for (int l = 0; l <= 180; ++l)
+    if (!std::isfinite(cos_edge[l]) || cos_edge[l] < -1 || cos_edge[l] > 1) return fail(who + format("cos_edge[%d] is not a cosine", l));
+  for (int z = 0; z < ng; ++z) {
+    if (!(gam_ef[z] > 0) || !std::isfinite(gam_ef[z]) || !std::isfinite(gam3_ef[z])) return fail(who + format("gam_ef / gam3_ef of zone %d is not positive and finite", z + 1));
+    if (!(beta_ef[z] >= 0 && beta_ef[z] < 1)) return fail(who + format("beta_ef of zone %d is outside [0, 1)", z + 1));
+  }
+  for (int s = 0; s <= n_shells; ++s)
+    if (shell_ends[s] < 0 || shell_ends[s] > (int64_t)ng + 1) return fail(who + format("shell_ends[%d] is outside 0 .. n_grid + 1", s));
+  const size_t n_tab = 2 * (size_t)n_photon + 181 + 3 * (size_t)ng + (size_t)n_shells + 1, n_out = ((size_t)n_shells + 1) * n;
+  if (reserve(c->d_ptab, (long long)n_tab) || reserve(c->d_pnb, (long long)ng * n) || (emis && reserve(c->d_stage, (long long)ng * n_photon))) return 1;
+  // (the kept result last: growing its buffer drops it, so its flag goes first; every other allocation has succeeded by now)
+  if (c->d_pobs[process].cap() < (long long)n_out) c->pobs_n[process] = 0;
+  if (reserve(c->d_pobs[process], (long long)n_out)) return 1;
+  std::vector<double> h(n_tab);
+  double* q = h.data();
+  memcpy(q, energy_div, sizeof(double) * n_photon); q += n_photon;
+  memcpy(q, energy_grid, sizeof(double) * n_photon); q += n_photon;
+  memcpy(q, cos_edge, sizeof(double) * 181); q += 181;
+  memcpy(q, gam_ef, sizeof(double) * ng); q += ng;
+  memcpy(q, beta_ef, sizeof(double) * ng); q += ng;
+  memcpy(q, gam3_ef, sizeof(double) * ng); q += ng;
+  for (int s = 0; s <= n_shells; ++s) q[s] = (double)shell_ends[s];
+  c->pobs_n[process] = 0;
+  HIPCHK(hipMemcpyAsync(c->d_ptab, h.data(), sizeof(double) * n_tab, hipMemcpyHostToDevice, c->stream));
+  const double* d_emis = c->d_pemis[process];
+  if (emis) {
+    HIPCHK(hipMemcpyAsync(c->d_stage, emis, sizeof(double) * (size_t)ng * n_photon, hipMemcpyHostToDevice, c->stream));
+    d_emis = c->d_stage;
+  }
+  HIPCHK(mcs_launch_photon_observe(d_emis, c->d_ptab, process, ng, n_photon, area, dlog, last_mid_ratio, n_shells, c->d_pnb, c->d_pobs[process], c->stream));
+  if (out) HIPCHK(hipMemcpyAsync(out, c->d_pobs[process], sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->pobs_n[process] = n; c->pobs_shells[process] = n_shells;
   return 0;
 }
 
@@ -1594,11 +1672,13 @@ int mcs_photon_ic(mcs_ctx* c, const double* mom_edge_cgs, double mc_e, int j_max
 int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
   MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
-  *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo};
+  *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo, {}, {}, {}};
+  for (int p = 0; p < 3; ++p) { out->pobs[p] = c->d_pobs[p]; out->pobs_n[p] = c->pobs_n[p]; out->pobs_shells[p] = c->pobs_shells[p]; }
   return 0;
 }
-void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; }
+void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; c->photon_flags_clear(); }
 void mcs_ctx_view_products_taken(mcs_ctx* c) { c->have_cout_dndp = c->have_cout_thermo = false; }
+void mcs_ctx_view_photons_taken(mcs_ctx* c) { c->photon_flags_clear(); }
 int mcs_ctx_view_fail(const char* msg) { return fail(msg); }
 
 }  // extern "C"

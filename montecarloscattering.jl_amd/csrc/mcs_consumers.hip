@@ -539,3 +539,99 @@ extern "C" hipError_t mcs_launch_photon_ic(const double* ef, const double* p_edg
                      mc_e, beam_area, out);
   return hipGetLastError();
 }
+
+// ---- K9: the photon spectra an observer sees (include/mcs.h, "observed shell spectra"; DESIGN.md "K9") ---------------------------------
+// mcs_k_photon_observe_zone: one workgroup per grid zone.  The zone's emission becomes a photon flux at Earth, one thread per energy
+// (the conversions of the three host routines, each operation a separate rounding); inverse Compton is done with that.  Synchrotron and
+// pion decay are re-binned by the Doppler-shifted energy of 180 slices in cos(theta): on the host a scatter (numpy's add.at, slices
+// ascending and within a slice energies ascending), here a GATHER in that order -- one thread per target bin b walks the slices l in
+// ascending order and adds, for each, the source bins j that land in b, ascending.  For a fixed slice the shifted energy
+// mid[j] * fac[l] does not decrease with j (the launcher's caller checks: energies sorted, last_mid_ratio >= 1, gam > 0, 0 <= beta < 1),
+// so those j are one contiguous range, found by two bisections over the products themselves: no table of targets, no atomics, and the
+// same input gives the same bits.  LDS: 3 x 256 + 180 doubles.
+#define KP_MAXN 256            // energies of a spectrum at the most (n_photon)
+#define KP_NCOS 180            // get_summed_emission.jl:117
+
+namespace {
+// first j in [0, n] with mid[j] * fac > x (n: none)
+__device__ __forceinline__ int p_first_above(const double* mid, int n, double fac, double x) {
+  int lo = 0, hi = n;
+  while (lo < hi) { const int m = (lo + hi) >> 1; if (mid[m] * fac > x) hi = m; else lo = m + 1; }
+  return lo;
+}
+}  // namespace
+
+__global__ void __launch_bounds__(256) mcs_k_photon_observe_zone(const double* __restrict__ emis /*[n_grid][n_photon]*/, const double* __restrict__ e_div,
+                                                                const double* __restrict__ e_grid, const double* __restrict__ cos_edge /*[181]*/,
+                                                                const double* __restrict__ gam, const double* __restrict__ beta,
+                                                                const double* __restrict__ gam3, int process, int n_photon, double area, double dlog,
+                                                                double last_mid_ratio, double* __restrict__ nb /*[n_grid][n_photon - 1]*/) {
+  __shared__ double s_E[KP_MAXN], s_mid[KP_MAXN], s_num[KP_MAXN], s_fac[KP_NCOS];
+  const int zone = blockIdx.x, n = n_photon - 1;                        // the last energy of a spectrum is not written out
+  for (int j = threadIdx.x; j < n; j += blockDim.x) {
+    const double em = emis[(long long)zone * n_photon + j];
+    double ef;                                                          // energy flux at Earth, floor 1e-99
+    if (process == MCS_PHOTON_IC) ef = em > 1.0e-99 ? em / MCS_MEV_ERG : 1.0e-99;
+    else if (process == MCS_PHOTON_SYNCH) { double fe = em / area; fe = fe > 1.0e-99 ? fe : 1.0e-99; ef = fe > 1.0e-99 ? fe / MCS_MEV_ERG : 1.0e-99; }
+    else { const double fe = em / area; ef = fe >= 1.0e-99 ? fe : 1.0e-99; }
+    const double f = ef <= 1.0e-99 ? 1.0e-99 : ef / e_div[j];            // photons per d(log E)
+    const double per_bin = f > 1.0e-90 ? f * dlog : f;
+    if (process == MCS_PHOTON_IC) nb[(long long)zone * n + j] = per_bin;  // (computed in the observer's frame)
+    else { s_num[j] = per_bin / KP_NCOS; s_E[j] = e_grid[j]; }
+  }
+  if (process == MCS_PHOTON_IC) return;
+  const double g = gam[zone], bt = beta[zone];
+  for (int l = threadIdx.x; l < KP_NCOS; l += blockDim.x) s_fac[l] = g * __builtin_sqrt((1 - bt * cos_edge[l]) * (1 - bt * cos_edge[l + 1]));
+  __syncthreads();
+  for (int j = threadIdx.x; j < n - 1; j += blockDim.x) s_mid[j] = __builtin_sqrt(s_E[j] * s_E[j + 1]);
+  __syncthreads();
+  if (threadIdx.x == 0) s_mid[n - 1] = s_mid[n - 2] * last_mid_ratio;
+  __syncthreads();
+  for (int b = threadIdx.x; b < n; b += blockDim.x) {
+    double acc = 1.0e-99;
+    if (b < n - 1) {                                                    // (a photon shifted to the last energy or beyond is dropped: S3)
+      const double e_lo = s_E[b], e_hi = s_E[b + 1];
+      for (int l = 0; l < KP_NCOS; ++l) {
+        const double fac = s_fac[l];
+        const int j0 = b == 0 ? 0 : p_first_above(s_mid, n, fac, e_lo);  // (the search for the target starts at the second energy)
+        const int j1 = p_first_above(s_mid, n, fac, e_hi);
+        for (int j = j0; j < j1; ++j) { const double v = s_num[j]; if (v > 1.0e-99) acc += v; }
+      }
+    }
+    nb[(long long)zone * n + b] = acc > 1.0e-95 ? acc * gam3[zone] : 1.0e-99;
+  }
+}
+
+// mcs_k_photon_observe_shells: one thread per energy; shells ascending, within a shell its zones ascending, then the row of all shells.
+__global__ void __launch_bounds__(256) mcs_k_photon_observe_shells(const double* __restrict__ nb /*[n_grid][n]*/, const double* __restrict__ ends /*[n_shells+1]*/,
+                                                                  int n, int n_shells, double* __restrict__ out /*[n_shells+1][n]*/) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  double all = 0.0;
+  for (int s = 0; s < n_shells; ++s) {
+    const int lo = (int)ends[s], hi = (int)ends[s + 1] - 1;
+    double sh = 1.0e-99;
+    if (lo >= 1 && hi >= lo) {
+      double a = 0.0;
+      for (int z = lo; z <= hi; ++z) { const double v = nb[(long long)(z - 1) * n + k]; a += v > 1.0e-95 ? v : 0.0; }      // S6
+      sh = a > 1.0e-99 ? a : 1.0e-99;
+    }
+    out[(long long)s * n + k] = sh;
+    all += sh > 1.0e-99 ? sh : 0.0;
+  }
+  out[(long long)n_shells * n + k] = all > 1.0e-99 ? all : 1.0e-99;
+}
+
+extern "C" hipError_t mcs_launch_photon_observe(const double* emis, const double* tabs /*e_div[np] | e_grid[np] | cos_edge[181] | gam | beta | gam3 [n_grid] | ends*/,
+                                                int process, int n_grid, int n_photon, double area, double dlog, double last_mid_ratio, int n_shells,
+                                                double* nb, double* out, hipStream_t st) {
+  const double *e_div = tabs, *e_grid = tabs + n_photon, *cos_edge = tabs + 2 * n_photon, *gam = cos_edge + KP_NCOS + 1;
+  const double *beta = gam + n_grid, *gam3 = beta + n_grid, *ends = gam3 + n_grid;
+  const int n = n_photon - 1;
+  hipLaunchKernelGGL(mcs_k_photon_observe_zone, dim3((unsigned)n_grid), dim3(256), 0, st, emis, e_div, e_grid, cos_edge, gam, beta, gam3, process, n_photon, area,
+                     dlog, last_mid_ratio, nb);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mcs_k_photon_observe_shells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, nb, ends, n, n_shells, out);
+  return hipGetLastError();
+}

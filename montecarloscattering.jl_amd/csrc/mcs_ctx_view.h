@@ -17,6 +17,10 @@ struct McsCtxView {
   // consumer call), and whether each has left a whole result there since the last mcs_begin_species / products sample
   const double* cout;
   bool have_dndp_cr, have_thermo;
+  // per photon process (MCS_PHOTON_SYNCH / _IC / _PION): what the last mcs_photon_observe of it left on the device, [shells + 1][n]
+  // (pobs_n: that n, 0 = nothing since the last mcs_begin_species, tally write or photons sample)
+  const double* pobs[3];
+  int pobs_n[3], pobs_shells[3];
 };
 
 extern "C" {
@@ -29,6 +33,8 @@ void mcs_ctx_view_tallies_written(mcs_ctx* ctx);
 // A products sample of the ensemble statistics has been queued from ctx's consumer output buffer: both consumers have to run again
 // before the next one.
 void mcs_ctx_view_products_taken(mcs_ctx* ctx);
+// A photons sample has been queued from ctx's observed spectra: the folds and mcs_photon_observe have to run again before the next.
+void mcs_ctx_view_photons_taken(mcs_ctx* ctx);
 // Sets the message of the calling thread's last error (what the ABI's error call returns); returns 1.
 int mcs_ctx_view_fail(const char* msg);
 }

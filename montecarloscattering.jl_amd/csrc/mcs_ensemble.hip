@@ -158,6 +158,37 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_add_products(double* __
     welford(mean, m2, w, w < n_cout ? cout[w] : slope[w - n_cout], n);
 }
 
+// The photons sample (include/mcs.h, "photons sample"): sections synch | ic | pion, each [rows][n_p] as mcs_photon_observe left it on
+// the context (a null pointer: the process was not observed, every word 1e-99), then total [rows][n_pts].  A word of the total is
+// recomputed from the three sections by the thread that owns it: a shell row adds, to 1e-99, the lit words of pion decay, synchrotron
+// and inverse Compton in that order; the last row is the serial sum of the shell rows as they stand.
+struct PhotonSrc { const double* obs[3]; long long off[4]; int n[3], start[3]; int n_shells, n_pts; long long total; };
+__device__ inline double photon_total_word(const PhotonSrc& S, int s, int t) {
+  double x = 1.0e-99;
+  const int order[3] = {MCS_PHOTON_PION, MCS_PHOTON_SYNCH, MCS_PHOTON_IC};
+  for (int q = 0; q < 3; ++q) {
+    const int p = order[q];
+    if (!S.obs[p] || t < S.start[p] || t >= S.start[p] + S.n[p]) continue;
+    const double sh = S.obs[p][(long long)s * S.n[p] + (t - S.start[p])];
+    x = x + (sh > 1.0e-99 ? sh : 0.0);
+  }
+  return x;
+}
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_add_photons(double* __restrict__ mean, double* __restrict__ m2, PhotonSrc S, double n) {
+  for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < S.total; w += (long long)gridDim.x * blockDim.x) {
+    double x;
+    if (w < S.off[3]) {
+      const int p = w < S.off[1] ? 0 : w < S.off[2] ? 1 : 2;
+      x = S.obs[p] ? S.obs[p][w - S.off[p]] : 1.0e-99;
+    } else {
+      const int s = (int)((w - S.off[3]) / S.n_pts), t = (int)((w - S.off[3]) % S.n_pts);
+      if (s < S.n_shells) x = photon_total_word(S, s, t);
+      else { x = 0.0; for (int r = 0; r < S.n_shells; ++r) x = x + photon_total_word(S, r, t); }
+    }
+    welford(mean, m2, w, x, n);
+  }
+}
+
 // Chan: f_mean = nb / n, f_m2 = na * nb / n (host doubles)
 __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_merge(double* __restrict__ ma, double* __restrict__ qa, const double* __restrict__ mb,
                                                                const double* __restrict__ qb, long long total, double f_mean, double f_m2) {
@@ -624,7 +655,23 @@ void products_layout(const mcs_params* p, mcs_ens_products_layout* PL) {
   PL->total = o;
 }
 
+void photons_layout(int n_shells, const int n[3], int n_pts, mcs_ens_photons_layout* HL) {
+  const int64_t rows = (int64_t)n_shells + 1;
+  HL->rows = rows; HL->n_synch = n[0]; HL->n_ic = n[1]; HL->n_pion = n[2]; HL->n_pts = n_pts;
+  HL->synch = 0; HL->ic = rows * n[0]; HL->pion = HL->ic + rows * n[1]; HL->total_section = HL->pion + rows * n[2];
+  HL->total = HL->total_section + rows * n_pts;
+}
+const char* photons_layout_error(int n_shells, const int n[3], const int start[3], int n_pts) {
+  if (n_shells < 1 || n_shells > 4096) return "n_shells outside 1..4096";
+  if (n_pts < 1 || n_pts > 65536) return "n_pts outside 1..65536";
+  for (int p = 0; p < 3; ++p)
+    if (n[p] < 1 || n[p] > 255 || start[p] < 0 || start[p] + n[p] > n_pts) return "a process needs 1..255 energy words that lie inside the common grid";
+  return nullptr;
+}
+
 constexpr int PRODUCTS_BIT = 1 << 30;      // MCS_ENS_PRODUCTS
+constexpr int PHOTONS_BIT = 1 << 29;       // MCS_ENS_PHOTONS
+bool is_photons(int slot) { return slot >= 0 && (slot & PRODUCTS_BIT) == 0 && (slot & PHOTONS_BIT) != 0; }
 // (a negative slot has every high bit set: it is no products slot, and is refused as it always was)
 bool is_products(int slot) { return slot >= 0 && (slot & PRODUCTS_BIT) != 0; }
 
@@ -660,7 +707,16 @@ struct mcs_ens {
   std::vector<double> x_log_h;                // [nmom+1]
   DevBuf<double> x_log, slope;                // its device copy; the slopes of the sample being added [3][n_grid]
   bool products_sampled = false;              // some products slot has taken a sample (or a merge): the window is fixed
-  long long len(int slot) const { return is_products(slot) ? PL.total : slot == n_slots - 1 ? E.it_total : E.sp_total; }
+  // the photons slots, likewise (include/mcs.h, "photons sample"); no layout while ph_shells is 0
+  mcs_ens_photons_layout HL{};
+  int ph_shells = 0, ph_n[3] = {0, 0, 0}, ph_start[3] = {0, 0, 0}, ph_npts = 0;
+  std::vector<long long> hn;
+  std::vector<DevBuf<double>> hmean, hm2;     // per species slot: HL.total doubles each, or nothing
+  bool photons_sampled = false;               // some photons slot has taken a sample (or a merge): the layout is fixed
+  bool has_photon_layout() const { return ph_shells > 0; }
+  long long len(int slot) const {
+    return is_photons(slot) ? (has_photon_layout() ? HL.total : 0) : is_products(slot) ? PL.total : slot == n_slots - 1 ? E.it_total : E.sp_total;
+  }
   bool has_window() const { return !x_log_h.empty(); }
 };
 
@@ -693,6 +749,13 @@ int leave(mcs_ens* e, hipStream_t st) {
 // mean / m2 are null for a products slot that was never sampled (n is then 0).
 struct SlotRef { long long n; double* mean; double* m2; };
 int slot_ref(const mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
+  if (is_photons(slot)) {
+    const int s = slot ^ PHOTONS_BIT;
+    if (s >= e->n_slots - 1)
+      return fail(who + ": photons slot of slot " + std::to_string(s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
+    *out = SlotRef{e->hn[(size_t)s], e->hmean[(size_t)s].get(), e->hm2[(size_t)s].get()};
+    return 0;
+  }
   if (is_products(slot)) {
     const int s = slot ^ PRODUCTS_BIT;
     if (s >= e->n_slots - 1)
@@ -722,6 +785,30 @@ int products_reserve(mcs_ens* e, const std::string& who, int s, hipStream_t st) 
   if (a != hipSuccess) { m.reset(); q.reset(); return fail(who + ": hipMalloc: " + hipGetErrorString(a)); }
   ENSCHK(hipMemsetAsync(m.get(), 0, (size_t)e->PL.total * sizeof(double), st));
   ENSCHK(hipMemsetAsync(q.get(), 0, (size_t)e->PL.total * sizeof(double), st));
+  return 0;
+}
+
+// both have a photon layout, and the two differ
+bool photon_layouts_differ(const mcs_ens* a, const mcs_ens* b) {
+  if (!a->has_photon_layout() || !b->has_photon_layout()) return false;
+  return a->ph_shells != b->ph_shells || a->ph_npts != b->ph_npts || memcmp(a->ph_n, b->ph_n, sizeof a->ph_n) != 0 ||
+         memcmp(a->ph_start, b->ph_start, sizeof a->ph_start) != 0;
+}
+void photon_layout_take(mcs_ens* e, int n_shells, const int n[3], const int start[3], int n_pts) {
+  e->ph_shells = n_shells; e->ph_npts = n_pts;
+  for (int p = 0; p < 3; ++p) { e->ph_n[p] = n[p]; e->ph_start[p] = start[p]; }
+  photons_layout(n_shells, n, n_pts, &e->HL);
+}
+// room for the two vectors of species slot s's photons slot, zeroed on st when they are new
+int photons_reserve(mcs_ens* e, const std::string& who, int s, hipStream_t st) {
+  DevBuf<double>& m = e->hmean[(size_t)s];
+  DevBuf<double>& q = e->hm2[(size_t)s];
+  if (m.get() && q.get()) return 0;
+  hipError_t a = m.reserve(e->HL.total);
+  if (a == hipSuccess) a = q.reserve(e->HL.total);
+  if (a != hipSuccess) { m.reset(); q.reset(); return fail(who + ": hipMalloc: " + hipGetErrorString(a)); }
+  ENSCHK(hipMemsetAsync(m.get(), 0, (size_t)e->HL.total * sizeof(double), st));
+  ENSCHK(hipMemsetAsync(q.get(), 0, (size_t)e->HL.total * sizeof(double), st));
   return 0;
 }
 
@@ -837,6 +924,8 @@ int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   products_layout(&v.P, &e->PL);
   e->pn.assign((size_t)n_species_slots, 0);
   e->pmean.resize((size_t)n_species_slots); e->pm2.resize((size_t)n_species_slots);
+  e->hn.assign((size_t)n_species_slots, 0);
+  e->hmean.resize((size_t)n_species_slots); e->hm2.resize((size_t)n_species_slots);
   const mcs_layout& L = v.L;
   e->inc = IncRanges{{L.esc_flux, L.esc_energy_eff, L.spectra_coupled}, {L.px_esc_feb, L.weight_coupled, L.energy_transfer_pool}};
   e->n_slots = n_species_slots + 1;
@@ -966,6 +1055,59 @@ int mcs_ens_add_products(mcs_ens* e, mcs_ctx* src, int slot) {
   return leave(e, v.stream);
 }
 
+int mcs_ens_photons_get_layout(int n_shells, int n_synch, int n_ic, int n_pion, int n_pts, mcs_ens_photons_layout* out) {
+  if (!out) return fail("mcs_ens_photons_get_layout: null argument");
+  const int n[3] = {n_synch, n_ic, n_pion}, start[3] = {0, 0, 0};
+  if (n_pts >= 1 && (n_synch > n_pts || n_ic > n_pts || n_pion > n_pts)) return fail("mcs_ens_photons_get_layout: a process has more energy words than the common grid");
+  if (const char* msg = photons_layout_error(n_shells, n, start, n_pts)) return fail(std::string("mcs_ens_photons_get_layout: ") + msg);
+  photons_layout(n_shells, n, n_pts, out);
+  return 0;
+}
+
+int mcs_ens_set_photon_layout(mcs_ens* e, int n_shells, int n_synch, int n_ic, int n_pion, int start_synch, int start_ic, int start_pion, int n_pts) {
+  const std::string who = "mcs_ens_set_photon_layout";
+  if (!e) return fail(who + ": null argument");
+  if (e->photons_sampled) return fail(who + ": a photons slot has taken a sample; the layout stays as it is");
+  const int n[3] = {n_synch, n_ic, n_pion}, start[3] = {start_synch, start_ic, start_pion};
+  if (const char* msg = photons_layout_error(n_shells, n, start, n_pts)) return fail(who + ": " + msg);
+  photon_layout_take(e, n_shells, n, start, n_pts);
+  return 0;
+}
+
+int mcs_ens_add_photons(mcs_ens* e, mcs_ctx* src, int slot) {
+  const std::string who = "mcs_ens_add_photons";
+  if (!e || !src) return fail(who + ": null argument");
+  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  if (slot == e->n_slots - 1) return fail(who + ": slot " + std::to_string(slot) + " is the iteration slot; only a species slot has a photons slot");
+  if (!e->has_photon_layout()) return fail(who + ": no photon layout (mcs_ens_set_photon_layout)");
+  McsCtxView v;
+  if (view_of(e, src, who.c_str(), &v)) return 1;
+  PhotonSrc S{};
+  bool any = false;
+  for (int p = 0; p < 3; ++p) {
+    S.n[p] = e->ph_n[p]; S.start[p] = e->ph_start[p];
+    if (v.pobs_n[p] == 0 || !v.pobs[p]) continue;
+    if (v.pobs_n[p] != e->ph_n[p] || v.pobs_shells[p] != e->ph_shells)
+      return fail(who + ": process " + std::to_string(p) + " was observed with " + std::to_string(v.pobs_shells[p]) + " shells of " + std::to_string(v.pobs_n[p]) +
+                  " energy words, the layout has " + std::to_string(e->ph_shells) + " of " + std::to_string(e->ph_n[p]));
+    S.obs[p] = v.pobs[p];
+    any = true;
+  }
+  if (!any) return fail(who + ": the context holds no mcs_photon_observe result since its last mcs_begin_species, tally write or photons sample");
+  S.off[0] = e->HL.synch; S.off[1] = e->HL.ic; S.off[2] = e->HL.pion; S.off[3] = e->HL.total_section;
+  S.n_shells = e->ph_shells; S.n_pts = e->ph_npts; S.total = e->HL.total;
+  if (enter(e, v.stream)) return 1;
+  if (photons_reserve(e, who, slot, v.stream)) return 1;
+  const long long n = e->hn[(size_t)slot] + 1;
+  hipLaunchKernelGGL(mcs_k_ens_add_photons, dim3(grid_for(S.total)), dim3(ENS_THREADS), 0, v.stream, e->hmean[(size_t)slot].get(), e->hm2[(size_t)slot].get(), S,
+                     (double)n);
+  ENSCHK(hipGetLastError());
+  e->hn[(size_t)slot] = n;
+  e->photons_sampled = true;
+  mcs_ctx_view_photons_taken(src);
+  return leave(e, v.stream);
+}
+
 int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (!dst || !src) return fail("mcs_ens_merge: null argument");
   if (dst == src) return fail("mcs_ens_merge: dst and src are the same accumulator");
@@ -974,6 +1116,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
       dst->P.n_grid != src->P.n_grid || dst->P.n_ions != src->P.n_ions || dst->P.n_itrs != src->P.n_itrs)
     return fail("mcs_ens_merge: the accumulators' slots or layouts differ");
   if (windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' slope windows differ");
+  if (photon_layouts_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' photon layouts differ");
   McsCtxView v;
   if (mcs_ctx_view_get(dst->home, &v)) return 1;
   bool any_products = false;
@@ -1003,6 +1146,24 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
     }
     dst->pn[(size_t)s] = na + nb;
     dst->products_sampled = true;
+  }
+  for (int s = 0; s < src->n_slots - 1; ++s) {
+    const long long na = dst->hn[(size_t)s], nb = src->hn[(size_t)s];
+    if (nb == 0) continue;
+    if (!dst->has_photon_layout()) photon_layout_take(dst, src->ph_shells, src->ph_n, src->ph_start, src->ph_npts);
+    const long long len = dst->HL.total;
+    if (photons_reserve(dst, "mcs_ens_merge", s, v.stream)) return 1;
+    if (na == 0) {
+      ENSCHK(hipMemcpyAsync(dst->hmean[(size_t)s], src->hmean[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
+      ENSCHK(hipMemcpyAsync(dst->hm2[(size_t)s], src->hm2[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
+    } else {
+      const double n = (double)(na + nb);
+      hipLaunchKernelGGL(mcs_k_ens_merge, dim3(grid_for(len)), dim3(ENS_THREADS), 0, v.stream, dst->hmean[(size_t)s].get(), dst->hm2[(size_t)s].get(),
+                         src->hmean[(size_t)s].get(), src->hm2[(size_t)s].get(), len, (double)nb / n, (double)na * (double)nb / n);
+      ENSCHK(hipGetLastError());
+    }
+    dst->hn[(size_t)s] = na + nb;
+    dst->photons_sampled = true;
   }
   for (int s = 0; s < dst->n_slots; ++s) {
     const long long na = dst->n[(size_t)s], nb = src->n[(size_t)s], len = dst->len(s);
@@ -1038,6 +1199,7 @@ int mcs_ens_read(mcs_ens* e, int slot, int what, int64_t first, int64_t count, d
   if (first < 0 || count < 0 || first + count > e->len(slot)) return fail("mcs_ens_read: range outside the slot's sample vector");
   const long long n = r.n;
   if (is_products(slot) && n == 0) return fail("mcs_ens_read: the products slot has never taken a sample");
+  if (is_photons(slot) && n == 0) return fail("mcs_ens_read: the photons slot has never taken a sample");
   if (what == 2 && n < 2) return fail("mcs_ens_read: the standard error needs at least two samples; the slot has " + std::to_string(n));
   McsCtxView v;
   if (mcs_ctx_view_get(e->home, &v)) return 1;
@@ -1092,6 +1254,13 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
     for (int k = 1; k < n_ens; ++k)
       for (int j = 0; j < k; ++j)
         if (windows_differ(ens[j], ens[k])) return fail(who + ": the accumulators' slope windows differ");
+  long long len = a->len(slot);
+  if (is_photons(slot))
+    for (int k = 1; k < n_ens; ++k) {
+      for (int j = 0; j < k; ++j)
+        if (photon_layouts_differ(ens[j], ens[k])) return fail(who + ": the accumulators' photon layouts differ");
+      if (ens[k]->len(slot) > len) len = ens[k]->len(slot);      // (an accumulator without a layout has no photons sample)
+    }
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges > 0 && (!ranges || !out)) return fail(who + ": null argument");
   // the accumulators that have samples in this slot, in list order, and the factors of every step of the fold (as mcs_ens_merge)
@@ -1113,7 +1282,7 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
   }
   if (n < 2) return fail(who + ": the standard error needs at least two samples; the slot has " + std::to_string(n) + " over the list");
   long long n_blocks = 0;
-  if (check_ranges(who, a->len(slot), n_ranges, ranges, &n_blocks)) return 1;
+  if (check_ranges(who, len, n_ranges, ranges, &n_blocks)) return 1;
   *n_total = n;
   if (n_ranges == 0) return 0;
   switch (m) {
@@ -1140,7 +1309,7 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
       a->P.num_psd_tht_bins != b->P.num_psd_tht_bins)
     return fail(who + ": the accumulators' layouts differ");
   // species slot, iteration slot or products slot
-  const auto kind = [](const mcs_ens* e, int slot) { return is_products(slot) ? 2 : slot == e->n_slots - 1 ? 1 : 0; };
+  const auto kind = [](const mcs_ens* e, int slot) { return is_photons(slot) ? 3 : is_products(slot) ? 2 : slot == e->n_slots - 1 ? 1 : 0; };
   const long long len = a->len(slot_a);
   if (kind(a, slot_a) != kind(b, slot_b) || len != b->len(slot_b)) return fail(who + ": the two slots differ in kind or length");
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
@@ -1149,6 +1318,10 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   if (is_products(slot_a)) {
     if (ra.n == 0 || rb.n == 0) return fail(who + ": a products slot has never taken a sample");
     if (windows_differ(a, b)) return fail(who + ": the accumulators' slope windows differ");
+  }
+  if (is_photons(slot_a)) {
+    if (ra.n == 0 || rb.n == 0) return fail(who + ": a photons slot has never taken a sample");
+    if (photon_layouts_differ(a, b)) return fail(who + ": the accumulators' photon layouts differ");
   }
   if (ra.n < 2 || rb.n < 2)
     return fail(who + ": a standard error needs at least two samples; A has " + std::to_string(ra.n) + ", B has " + std::to_string(rb.n));

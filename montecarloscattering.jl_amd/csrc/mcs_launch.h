@@ -43,6 +43,8 @@ hipError_t mcs_launch_dndp_2d(const mcs_params* P, const double* psd, const doub
                               double rest_energy, double n0, int therm_from_hist, double gam_x, double beta_x, double* scratch, double* ef, hipStream_t st);
 hipError_t mcs_launch_photon_ic(const double* ef, const double* p_edge, const double* field, int n_grid, int NM, int NT, int j_max, int n_nu, int n_photon,
                                 double log_min_rm, double bins_per_dec, double mc_e, double beam_area, double* out, hipStream_t st);
+hipError_t mcs_launch_photon_observe(const double* emis, const double* tabs, int process, int n_grid, int n_photon, double area, double dlog,
+                                     double last_mid_ratio, int n_shells, double* nb, double* out, hipStream_t st);
 hipError_t mcs_launch_photon_pion(const double* dndp_pf, const double* p_edge, const double* target, int n_grid, int NM, int n_photon,
                                   double log_emin_erg, double bins_per_dec, double mc, double aa, double scaling, int i_data, double* out, hipStream_t st);
 hipError_t mcs_launch_photon_synch(const double* dndp_pf, const double* p_edge, const double* btot, int n_grid, int NM, int n_photon,

@@ -81,6 +81,7 @@ class RunResult:
                                                                   # fused_pcuts, fused_chunk, long_draws, long_imult_max as actually used
     ensemble: object = None       # the ensemble statistics the run fed (run(ensemble=...), run_overlapped(ensemble=True)); ensemble.py
     convergence: object = None    # a Convergence: what run / run_overlapped(triggers=...) checked and where it stopped; None without triggers
+    photons: object = None        # [consumers.ObservedSpectra], one per species, of the last iteration (run(photons=...)); None without
 
 
 @dataclasses.dataclass
@@ -605,6 +606,20 @@ def _check_triggers(ensemble, triggers, others=()):
     return rows
 
 
+def _species_photons(rs, i_iter, i_ion):
+    """The photon spectra at Earth of the species that has just ended on the primary context (run(photons=...)): one ion_finalize of
+    ITS tallies (K4; the last species' is the one the iteration's finalize step needs, and is kept for it), its folds and the observed
+    shell spectra (consumers.observed_spectra: K5-K7 and K9 on a HIP backend), and one photons sample of the ensemble."""
+    prob, be = rs.prob, rs.backend
+    ion_fin = consumers.ion_finalize(prob, be, i_ion)
+    if i_ion == len(prob.cfg.species):
+        rs.last_ion_fin = ion_fin
+    obs = consumers.observed_spectra(prob, be, i_ion, rs.photons, ion_fin)
+    rs.photon_spectra[i_ion - 1] = obs
+    if rs.ensemble is not None:
+        rs.ensemble.add_photons(be, i_ion - 1, obs)
+
+
 def _iteration_species(rs, i_iter, before_pcut):
     """The species of iteration i_iter in order: its transport (here, or with secondaries on the pool's threads as the
     scheduler places it), its merge into the primary if it ran on a secondary, its species end."""
@@ -613,6 +628,8 @@ def _iteration_species(rs, i_iter, before_pcut):
         for i_ion in range(1, n_sp + 1):
             _species_transport(rs, rs.backend, i_iter, i_ion, before_pcut, rs.stats, rs.empty_launches)
             _species_end(rs, 0, i_iter, i_ion)
+            if rs.photons is not None:
+                _species_photons(rs, i_iter, i_ion)
         return
     with ThreadPoolExecutor(max_workers=len(rs.ctxs)) as pool:   # (leaving the block waits for every thread, also on an exception)
         sched = _SpeciesScheduler(rs, pool, i_iter)
@@ -636,7 +653,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         first_iter: int = 1, iter_state=None, species_tallies: str = "full", final_full_read: bool = True,
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
         long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None,
-        ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1) -> RunResult:
+        ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1, photons=None) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -706,6 +723,15 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     density, spectral slope; Ensemble.products_slot).  An ensemble without a slope window first gets one over all bins; set a
     narrower one before the run (Ensemble.set_slope_window, ensemble.slope_window).  Triggers may name its parts, with
     bins=(l_lo, l_hi) for a momentum window of one zone.
+    photons: a consumers.PhotonSetup (photon shells, distance, redshift): at every species end, on the context that ran it, one
+    ion_finalize of that species (the last species' is the one the finalize step uses: it is not run twice) and
+    consumers.observed_spectra -- the species' emission folds and the spectra an observer sees per photon shell, on the device with a
+    HIP backend (K9).  RunResult.photons holds the last iteration's ObservedSpectra, one per species.  With ensemble, one PHOTONS sample
+    per species and iteration goes into Ensemble.photons_slot(i_ion - 1) (ensemble.py, "Photons"); an ensemble without a photon layout
+    first gets consumers.stock_photon_layout(photons.n_shells); triggers may name its parts (zones= shell rows, bins= an energy window
+    of one row).  Refused: a trigger on a photons slot without photons=, photons with species_backends, with an enabled communicator,
+    or without finalize.  Error bars of sums across species are left out: means add on the host, variances do not without the
+    covariance.
     """
     import torch
     comm = comm or Comm(False)
@@ -734,6 +760,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         n_pcuts=len(prob.pcuts) if max_pcuts is None else min(max_pcuts, len(prob.pcuts)), last_iter=first_iter + n_itrs - 1,
         verbose=verbose, gather_max=gather_max, skew_max=skew_max, fused_pcuts=fused_pcuts, fused_chunk=fused_chunk,
         long_draws=long_draws, long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
+        photons=photons, photon_spectra=[None] * len(cfg.species), last_ion_fin=None,
         G_f=None, G_i=None, G_pool=None, stats=[], per_species=[], local_steps=[], empty_launches=[], species_spans=[], iter_finals=[])
     # the step counters are never reset: this rank's running total.  A context that has run before (run() called again with
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
@@ -750,6 +777,17 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         if ensemble.n_species < len(cfg.species):
             raise ValueError(f"ensemble: {ensemble.n_species} species slots for {len(cfg.species)} species")
     triggers = list(triggers or [])
+    if photons is None and any(ens.Ensemble.is_photons(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on a photons slot needs photons= (a consumers.PhotonSetup; no sample would ever arrive)")
+    if photons is not None:
+        if secondaries:
+            raise ValueError("photons: not with species_backends (the spectra are made on the context that ran the species, one at a time)")
+        if comm.enabled:
+            raise ValueError("photons: one process without a communicator (the multi-rank case is left out)")
+        if not (finalize or smoothing is not None):
+            raise ValueError("photons: needs finalize=True (the spectra are made from ion_finalize's dN/dp)")
+        if ensemble is not None and ensemble.photon_layout is None:
+            ensemble.set_photon_layout(consumers.stock_photon_layout(photons.n_shells))
     if triggers:
         _check_trigger_args(ensemble is not None, "ensemble=", min_iterations, check_every)
         for t in triggers:
@@ -797,7 +835,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             # iter_finalize, on rank 0, whose device buffers hold the merged tallies
             changed = False
             if rs.is_root:
-                ion_fin = consumers.ion_finalize(prob, backend, len(cfg.species))
+                # (with photons= the last species end has made it already)
+                ion_fin = rs.last_ion_fin if photons is not None else consumers.ion_finalize(prob, backend, len(cfg.species))
                 if ensemble is not None:
                     _add_products(ensemble, prob, backend, ion_fin)
                 fin = itf.iter_finalize(prob, it_state, sm, i_iter, rs.G_f, L, ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
@@ -847,7 +886,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         rs.per_species[-1] = rs.per_species[-1][:2] + (rs.G_f, rs.G_i)
     return RunResult(rs.G_f, rs.G_i, rs.per_species, rs.stats, *_steps(rs.G_i, P.n_grid), rs.iter_finals, it_state,
                      rs.local_steps, rs.empty_launches, rs.species_spans, options, ensemble,
-                     Convergence(checks, stopped_at, satisfied) if triggers else None)
+                     Convergence(checks, stopped_at, satisfied) if triggers else None,
+                     list(rs.photon_spectra) if photons is not None else None)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over
@@ -897,7 +937,8 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     the tallies over the iterations.  Its finalize_mean / finalize_stderr / finalize_count are the same statistics, on the host, of
     the per-iteration ion_finalize of the last species (ensemble.FINALIZE_NAMES), in iteration order.  Every context's ensemble also
     takes the products sample of run(finalize=True, ensemble=...) right after that ion_finalize, inside the iteration's job, so that
-    triggers on a products slot work through the rounds and the merged summary like any other."""
+    triggers on a products slot work through the rounds and the merged summary like any other.
+    The photon spectra of run(photons=...) are not made here: run_overlapped(photons=) is left out."""
     cfg, P = prob.cfg, prob.params
     n_itrs = n_itrs if n_itrs is not None else cfg.num_iterations
     K = len(backends)

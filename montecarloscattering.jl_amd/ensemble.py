@@ -46,6 +46,17 @@ vectors exist from its first sample on:
       counts it in n_nonfinite and a trigger over it is never met -- a slope trigger belongs on zones that the accelerated
       population reaches.  It is the slope of dN/dp, about -2.2 behind a strong shock, not the index of f(p).
 
+Photons (include/mcs.h, "photons sample"): the photon spectra at Earth per photon shell, consumers.observed_spectra.  A shell spectrum is
+a sum over zones, slices in cos(theta) and processes, so its variance does not follow from per-cell variances either: every species
+slot s has a second companion, `Ensemble.photons_slot(s)`, sampled once per iteration (`add_photons`) and allocated at its first
+sample.  `set_photon_layout` (a consumers.PhotonLayout) fixes the vector before that:
+
+  synch, ic, pion   [n_shells + 1][n]: photons per bin of every shell and, last row, of all shells; a process that was not observed
+                    enters as 1e-99 throughout
+  total             [n_shells + 1][n_pts]: the three on the common energy grid (consumers.photon_total)
+
+zones= of a `Request` or `Trigger` selects shell rows of one of these parts, bins= an energy window of one row.
+
 A summary range can be restricted in momentum: `Request` / `Trigger(bins=(l_lo, l_hi))` together with a single zone, zones=(z, z+1),
 on a part of shape [zone][bins] (the three dNdp_* and the six marginals) is the word range off + z * per + l_lo of l_hi - l_lo
 words.  dN/dp spans a dozen decades: without it the floor_frac selection keeps the thermal peak and drops the tail.  Several zones
@@ -108,6 +119,11 @@ ZONE_PARTS = ZONE_PARTS + PRODUCT_NAMES
 BIN_PARTS = PRODUCT_DNDP + MARGINALS
 PRODUCTS_BIT = capi.ENS_PRODUCTS_BIT      # products slot of species slot s: s | PRODUCTS_BIT (MCS_ENS_PRODUCTS)
 DNDP_FLOOR = 1.0e-99                      # the consumers' floor: a bin at or below it is empty
+# the parts of a photons slot, in the order of mcs_ens_photons_layout: first axis the shell row (zones=), second the energy (bins=)
+PHOTON_NAMES = ("synch", "ic", "pion", "total")
+ZONE_PARTS = ZONE_PARTS + PHOTON_NAMES
+BIN_PARTS = BIN_PARTS + PHOTON_NAMES
+PHOTONS_BIT = capi.ENS_PHOTONS_BIT        # photons slot of species slot s: s | PHOTONS_BIT (MCS_ENS_PHOTONS)
 
 
 class EnsLayout:
@@ -208,9 +224,9 @@ def stats_over(samples):
 def _check_part(name: str, zones, bins=None):
     """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis, a bins
     window is a pair, comes with a single zone and the part has a bins axis."""
-    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES:
+    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES:
         raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}; "
-                         f"a products slot: {', '.join(PRODUCT_NAMES)}")
+                         f"a products slot: {', '.join(PRODUCT_NAMES)}; a photons slot: {', '.join(PHOTON_NAMES)}")
     if bins is not None:
         if name not in BIN_PARTS:
             raise ValueError(f"ensemble: {name!r} has no [zone][bins] shape; a bins window fits: {', '.join(BIN_PARTS)}")
@@ -552,6 +568,7 @@ class Ensemble:
         self.finalize_stderr: Dict[str, np.ndarray] = {}
         self.finalize_count = 0
         self.window = None             # (l_lo, l_hi, x_log) of set_slope_window
+        self.photon_layout = None      # consumers.PhotonLayout of set_photon_layout
 
     @staticmethod
     def for_backend(backend, n_species: int) -> "Ensemble":
@@ -570,27 +587,65 @@ class Ensemble:
     def is_products(slot: int) -> bool:
         return slot >= 0 and bool(slot & PRODUCTS_BIT)
 
+    def photons_slot(self, s: int) -> int:
+        """The slot number of the photon spectra of species slot s (MCS_ENS_PHOTONS)."""
+        if not 0 <= s < self.n_species:
+            raise ValueError(f"ensemble: slot {s} is no species slot (0..{self.n_species - 1}); only a species slot has a photons slot")
+        return int(s) | PHOTONS_BIT
+
+    @staticmethod
+    def is_photons(slot: int) -> bool:
+        return slot >= 0 and not slot & PRODUCTS_BIT and bool(slot & PHOTONS_BIT)
+
+    def set_photon_layout(self, layout):
+        """The shells, the energy words of every process and their offsets on the common grid (a consumers.PhotonLayout;
+        consumers.stock_photon_layout(n_shells) is that of the stock energy grids).  Before the first photons sample; refused afterwards."""
+        from .consumers import PHOTON_PROCESSES
+        a = layout.args()
+        n_shells, n, start, n_pts = a[0], a[1:4], a[4:7], a[7]
+        if not 1 <= n_shells <= 4096 or not 1 <= n_pts <= 65536:
+            raise ValueError(f"ensemble: a photon layout needs 1..4096 shells and 1..65536 points on the common grid, not {n_shells} and {n_pts}")
+        for p, k, o in zip(PHOTON_PROCESSES, n, start):
+            if not (1 <= k <= 255 and 0 <= o and o + k <= n_pts):
+                raise ValueError(f"ensemble: {p!r} needs 1..255 energy words inside the common grid, not {k} at {o} of {n_pts}")
+        self._set_photon_layout(layout)
+        self.photon_layout = layout
+
     def names(self, slot: int):
         self._check_slot(slot)
+        if self.is_photons(slot):
+            return PHOTON_NAMES
         if self.is_products(slot):
             return PRODUCT_NAMES
         return ITERATION_NAMES if slot == self.iteration_slot else SPECIES_NAMES
 
     def _check_slot(self, slot: int):
-        if self.is_products(slot):
+        if self.is_photons(slot):
+            if not 0 <= slot ^ PHOTONS_BIT < self.n_species:
+                raise ValueError(f"ensemble: photons slot of slot {slot ^ PHOTONS_BIT}, which is no species slot (0..{self.n_species - 1})")
+        elif self.is_products(slot):
             if not 0 <= slot ^ PRODUCTS_BIT < self.n_species:
                 raise ValueError(f"ensemble: products slot of slot {slot ^ PRODUCTS_BIT}, which is no species slot (0..{self.n_species - 1})")
         elif not 0 <= slot <= self.n_species:
             raise ValueError(f"ensemble: slot {slot} outside 0..{self.n_species}")
 
     def _len(self, slot: int) -> int:
+        if self.is_photons(slot):
+            return 0 if self.photon_layout is None else self.photon_layout.offsets()["_total"]
         if self.is_products(slot):
             return self.layout.products_total
         return self.layout.iteration_total if slot == self.iteration_slot else self.layout.species_total
 
     def _where(self, slot: int, name: str):
         self._check_slot(slot)
-        if self.is_products(slot):
+        if self.is_photons(slot):
+            kind = f"the photons slot of species slot {slot ^ PHOTONS_BIT}"
+            if self.photon_layout is None:
+                raise ValueError(f"ensemble: {kind} has no layout yet (set_photon_layout)")
+            rows = self.photon_layout.rows
+            offs = self.photon_layout.offsets()
+            table = {part: (offs[part][0], (rows, offs[part][1])) for part in PHOTON_NAMES}
+        elif self.is_products(slot):
             table, kind = self.layout.products, f"the products slot of species slot {slot ^ PRODUCTS_BIT}"
         elif slot == self.iteration_slot:
             table, kind = self.layout.iteration, "the iteration slot"
@@ -675,7 +730,7 @@ class Ensemble:
                 raise ValueError("ensemble: a merged summary needs ensembles of the same kind, slots and layout")
 
     def _kind(self, slot: int) -> str:
-        return "products" if self.is_products(slot) else "iteration" if slot == self.iteration_slot else "species"
+        return "photons" if self.is_photons(slot) else "products" if self.is_products(slot) else "iteration" if slot == self.iteration_slot else "species"
 
     def compare(self, other: "Ensemble", slot: int, requests: Sequence[CompareRequest], other_slot: Optional[int] = None) -> List[Difference]:
         """One Difference per request (at most MAX_RANGES; they may overlap): slot `slot` of this ensemble, A, against slot
@@ -740,9 +795,46 @@ class HostEnsemble(Ensemble):
         self._pmean: Dict[int, np.ndarray] = {}
         self._pm2: Dict[int, np.ndarray] = {}
         self._pn = [0] * self.n_species
+        # the photons slots, likewise
+        self._hmean: Dict[int, np.ndarray] = {}
+        self._hm2: Dict[int, np.ndarray] = {}
+        self._hn = [0] * self.n_species
+
+    def _set_photon_layout(self, layout):
+        if any(self._hn):
+            raise ValueError("ensemble: a photons slot has taken a sample; the photon layout stays as it is")
+
+    def add_photons(self, backend, slot: int, observed):
+        """One photons sample of species slot `slot` from an `ObservedSpectra` (consumers.observed_spectra on `backend`): the observed
+        processes as they are, the others 1e-99, the total rebuilt on this ensemble's layout."""
+        from .consumers import PHOTON_PROCESSES, photon_total
+        self._check_slot(slot)
+        if self.is_photons(slot) or self.is_products(slot) or slot == self.iteration_slot:
+            raise ValueError(f"ensemble: slot {slot} is no species slot; only a species slot has a photons slot")
+        lay = self.photon_layout
+        if lay is None:
+            raise ValueError("ensemble: no photon layout (set_photon_layout)")
+        per = {p: np.asarray(a, dtype=np.float64) for p, a in observed.per_process.items()}
+        if not per:
+            raise ValueError("ensemble: the ObservedSpectra holds no process")
+        for p, a in per.items():
+            if a.shape != (lay.rows, lay.n[p]):
+                raise ValueError(f"ensemble: {p!r} was observed as {a.shape}; the layout has {(lay.rows, lay.n[p])}")
+        parts = [(per[p] if p in per else np.full((lay.rows, lay.n[p]), 1.0e-99)).ravel() for p in PHOTON_PROCESSES]
+        x = np.concatenate(parts + [photon_total(per, lay).ravel()])
+        if slot not in self._hmean:
+            self._hmean[slot], self._hm2[slot] = np.zeros(x.size), np.zeros(x.size)
+        self._hn[slot] = welford_update(self._hmean[slot], self._hm2[slot], self._hn[slot], x)
+
+    @staticmethod
+    def _photon_layouts_differ(a, b) -> bool:
+        return a.photon_layout is not None and b.photon_layout is not None and a.photon_layout.args() != b.photon_layout.args()
 
     def _vectors(self, slot: int):
         """(mean, M2, n) of a slot; (None, None, 0) for a products slot that was never sampled."""
+        if self.is_photons(slot):
+            s = slot ^ PHOTONS_BIT
+            return self._hmean.get(s), self._hm2.get(s), self._hn[s]
         if self.is_products(slot):
             s = slot ^ PRODUCTS_BIT
             return self._pmean.get(s), self._pm2.get(s), self._pn[s]
@@ -804,6 +896,22 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: merge needs an ensemble of the same kind, slots and layout")
         if self._windows_differ(self, other):
             raise ValueError("ensemble: merge of ensembles whose slope windows differ")
+        if self._photon_layouts_differ(self, other):
+            raise ValueError("ensemble: merge of ensembles whose photon layouts differ")
+        if any(other._hn) and self.photon_layout is None:
+            self.photon_layout = other.photon_layout
+        for s in range(self.n_species):
+            na, nb = self._hn[s], other._hn[s]
+            if nb == 0:
+                continue
+            if na == 0:
+                self._hmean[s], self._hm2[s] = other._hmean[s].copy(), other._hm2[s].copy()
+            else:
+                n = float(na + nb)
+                d = other._hmean[s] - self._hmean[s]
+                self._hmean[s] = self._hmean[s] + d * (float(nb) / n)
+                self._hm2[s] = (self._hm2[s] + other._hm2[s]) + (d * d) * (float(na) * float(nb) / n)
+            self._hn[s] = na + nb
         for s in range(self.n_species + 1):
             na, nb = self._n[s], other._n[s]
             if nb == 0:
@@ -839,6 +947,8 @@ class HostEnsemble(Ensemble):
 
     def _read(self, slot, what, first, count):
         mean, m2, n = self._vectors(slot)
+        if mean is None and self.is_photons(slot):
+            raise ValueError(f"ensemble: the photons slot of species slot {slot ^ PHOTONS_BIT} has never taken a sample")
         if mean is None:
             raise ValueError(f"ensemble: the products slot of species slot {slot ^ PRODUCTS_BIT} has never taken a sample")
         if what == 2:
@@ -857,6 +967,8 @@ class HostEnsemble(Ensemble):
         es = [self] + others
         if self.is_products(slot) and any(self._windows_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose slope windows differ")
+        if self.is_photons(slot) and any(self._photon_layouts_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
+            raise ValueError("ensemble: a merged summary of ensembles whose photon layouts differ")
         for first, count, floor_frac, tol in ranges:
             m, q, na = None, None, 0
             for e in [self] + others:
@@ -879,6 +991,8 @@ class HostEnsemble(Ensemble):
     def _compare(self, other, slot, other_slot, n_a, n_b, ranges):
         if self.is_products(slot) and self._windows_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose slope windows differ")
+        if self.is_photons(slot) and self._photon_layouts_differ(self, other):
+            raise ValueError("ensemble: a comparison of ensembles whose photon layouts differ")
         (ma, qa, _), (mb, qb, _) = self._vectors(slot), other._vectors(other_slot)
         return [difference_of(ma[first:first + count], qa[first:first + count], n_a, mb[first:first + count], qb[first:first + count], n_b,
                               floor_frac, zcut) for first, count, floor_frac, zcut in ranges]
@@ -935,10 +1049,20 @@ class HipEnsemble(Ensemble):
         the backend's device (mcs_ens_add_products); nothing crosses to the host, ion_final is not read."""
         self._chk(self.lib.mcs_ens_add_products(self.h, backend.h, int(slot)))
 
+    def _set_photon_layout(self, layout):
+        self._chk(self.lib.mcs_ens_set_photon_layout(self.h, *layout.args()))
+
+    def add_photons(self, backend: HipBackend, slot: int, observed=None):
+        """One photons sample of species slot `slot` from what mcs_photon_observe (consumers.observed_spectra) left on the backend's
+        device (mcs_ens_add_photons); nothing crosses to the host, `observed` is not read."""
+        self._chk(self.lib.mcs_ens_add_photons(self.h, backend.h, int(slot)))
+
     def merge(self, other: "HipEnsemble"):
         if not isinstance(other, HipEnsemble):
             raise ValueError("ensemble: merge needs an ensemble of the same kind, slots and layout")
         self._chk(self.lib.mcs_ens_merge(self.h, other.h))
+        if self.photon_layout is None and other.photon_layout is not None and any(other.count(other.photons_slot(s)) for s in range(other.n_species)):
+            self.photon_layout = other.photon_layout      # (as the library does)
         if self.window is None and other.window is not None and any(other.count(other.products_slot(s)) for s in range(other.n_species)):
             self.window = other.window      # (as the library does: an accumulator without a window takes the one its samples were made with)
 

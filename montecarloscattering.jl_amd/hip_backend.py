@@ -395,6 +395,26 @@ class HipBackend:
                                          float(bins_per_dec), float(beam_area), _dp(E), _dp(out)))
         return E, out
 
+    def photon_observe(self, process, energy_div, energy_grid, area, dlog, last_mid_ratio, cos_edge, gam_ef, beta_ef, gam3_ef, shell_ends,
+                       emis=None, download=True):
+        """K9: the observed shell spectra of one emission process ("synch", "ic" or "pion"; mcs_photon_observe in include/mcs.h) ->
+        photons per bin [n_shells + 1][n_photon - 1], the last row all shells.  emis=None: from what the last fold of that process left
+        on the context; else the caller's [n_grid][n_photon].  The result stays on the device for Ensemble.add_photons; download=False:
+        nothing comes back (None is returned)."""
+        ed, eg, ce, ga, be, g3 = (np.ascontiguousarray(a, dtype=np.float64) for a in (energy_div, energy_grid, cos_edge, gam_ef, beta_ef, gam3_ef))
+        ends = np.ascontiguousarray(shell_ends, dtype=np.int64)
+        n_photon, ng = len(ed), self.P.n_grid
+        assert eg.shape == (n_photon,) and ce.shape == (181,) and ga.shape == be.shape == g3.shape == (ng,) and ends.ndim == 1 and len(ends) >= 2
+        em = None
+        if emis is not None:
+            em = np.ascontiguousarray(emis, dtype=np.float64)
+            assert em.shape == (ng, n_photon)
+        out = np.zeros((len(ends), n_photon - 1)) if download else None
+        self._chk(self.lib.mcs_photon_observe(self.h, capi.PHOTON_PROCESS[process], n_photon, None if em is None else _dp(em), _dp(ed), _dp(eg),
+                                              float(area), float(dlog), float(last_mid_ratio), _dp(ce), _dp(ga), _dp(be), _dp(g3), len(ends) - 1,
+                                              ends.ctypes.data_as(c_int64_p), None if out is None else _dp(out)))
+        return out
+
     def last_kernel_ms(self) -> float:
         return float(self.lib.mcs_last_kernel_ms(self.h))
 
