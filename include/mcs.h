@@ -702,6 +702,38 @@ int mcs_ens_set_photon_layout(mcs_ens* ens, int n_shells, int n_synch, int n_ic,
                               int n_pts);
 int mcs_ens_add_photons(mcs_ens* ens, mcs_ctx* src, int species_slot);
 
+/* ---- source sample: error bars of the photon spectrum summed over species.  An observer sees one spectrum from the source; the
+ * species of one iteration share a shock profile and an energy-transfer pool and are correlated, so the variance of the sum is not
+ * the sum of the species' variances: the sum itself is sampled, once per iteration.
+ * The SOURCE slot MCS_ENS_PHOTONS_ALL, one per accumulator and no companion of a species slot, has exactly the photons layout above
+ * -- synch | ic | pion | total, the same offsets, the same mcs_ens_photons_layout -- in the count, read, summarize, summarize-merged,
+ * compare and merge calls.  The accumulator keeps a PENDING vector of layout.total doubles on the device, allocated at the first
+ * deposit, and on the host the species slots deposited since the last take, in call order; the two vectors of the source slot are
+ * allocated at its first sample or merge.  An accumulator that never deposits allocates nothing more and behaves as before.
+ * mcs_ens_add_photons_deposit: everything mcs_ens_add_photons does -- the species' photons slot ends with the same bits -- and, in
+ * the same kernel launch, the deposit of the sample into the pending vector.  A thread forms its word x[w] of the species' sample
+ * once, makes the update of the species' slot, and then, every operation a separate rounding (no fused multiply-add):
+ *   the first deposit since the last take    pending[w] = 1.0e-99 + (x[w] > 1.0e-99 ? x[w] : 0.0)       (pending[w] is not read)
+ *   a later one                              pending[w] = pending[w] + (x[w] > 1.0e-99 ? x[w] : 0.0)
+ * uniformly over the four sections, the all-shells rows included: the source's all-shells row is the sum over species of the
+ * species' all-shells rows (each the sum over its shells), not a sum over the source's shell rows.  The deposit order is the call
+ * order.  Queued on src's stream behind the accumulator's event, no host synchronisation; it clears the context's photon flags.
+ * Refused, with nothing changed (species slot, pending vector, flags, bookkeeping): everything mcs_ens_add_photons refuses, and a
+ * species slot already deposited since the last take.
+ * mcs_ens_add_photons_all: the take -- one sample x[w] = pending[w] into the source slot with the update of every slot, on the home
+ * context's stream behind the accumulator's event; the deposits are then forgotten.  Refused with no deposit pending.  It fixes the
+ * photon layout like a photons sample.
+ * mcs_ens_drop_pending_photons: forgets the deposits (host bookkeeping only: the next first deposit overwrites the vector); returns 0
+ * also when nothing is pending.  A run that raised in mid-iteration calls it so that the next iteration starts clean.
+ * mcs_ens_merge merges the source slot like a photons slot (allocating in dst; a dst without a layout takes src's); pending deposits
+ * are not merged and do not hinder a merge.  A source slot that was never sampled has count 0, and its reads are refused.  The
+ * refusals of differing layouts apply as to the photons slots.  mcs_ens_compare takes it against another source slot only: it is a
+ * kind of its own, and against a species' photons slot the slots "differ in kind".  mcs_ens_load_mean refuses it. */
+#define MCS_ENS_PHOTONS_ALL (1 << 28)
+int mcs_ens_add_photons_deposit(mcs_ens* ens, mcs_ctx* src, int species_slot);
+int mcs_ens_add_photons_all(mcs_ens* ens);
+int mcs_ens_drop_pending_photons(mcs_ens* ens);
+
 /* ---- comparison of two slots: does run B agree with run A within their error bars?  Per-word z-scores and their chi-square,
  * reduced on the device.  Slot slot_a of accumulator a (A, n_a >= 2 samples) against slot slot_b of b (B, n_b >= 2): two slots of
  * the same kind and length -- both species slots, both iteration slots or both products slots -- of accumulators on one device

@@ -104,6 +104,7 @@ class McsEnsPhotonsLayout(ct.Structure):
 
 
 ENS_PHOTONS_BIT = 1 << 29       # MCS_ENS_PHOTONS(s) = s | ENS_PHOTONS_BIT
+ENS_PHOTONS_ALL = 1 << 28       # MCS_ENS_PHOTONS_ALL: the source slot, one per accumulator
 
 
 class McsEnsRange(ct.Structure):
@@ -374,6 +375,9 @@ def load_library() -> ct.CDLL:
         "mcs_ens_photons_get_layout": (i32, [i32, i32, i32, i32, i32, ct.POINTER(McsEnsPhotonsLayout)]),
         "mcs_ens_set_photon_layout": (i32, [vp] + [i32] * 8),
         "mcs_ens_add_photons": (i32, [vp, vp, i32]),
+        "mcs_ens_add_photons_deposit": (i32, [vp, vp, i32]),
+        "mcs_ens_add_photons_all": (i32, [vp]),
+        "mcs_ens_drop_pending_photons": (i32, [vp]),
         "mcs_ens_compare": (i32, [vp, i32, vp, i32, i32, ct.POINTER(McsEnsCmpRange), ct.POINTER(McsEnsDifference)]),
     }
     for name, (res, args) in sig.items():
@@ -430,4 +434,6 @@ EXPORTED_SYMBOLS += [
 ]
 # the observed shell spectra (K9)
 EXPORTED_SYMBOLS += ["mcs_photon_observe", "mcs_ens_photons_get_layout", "mcs_ens_set_photon_layout", "mcs_ens_add_photons"]
+# the source sample: the photon spectrum summed over species
+EXPORTED_SYMBOLS += ["mcs_ens_add_photons_deposit", "mcs_ens_add_photons_all", "mcs_ens_drop_pending_photons"]
 PHOTON_PROCESS = {"synch": 0, "ic": 1, "pion": 2}      # MCS_PHOTON_SYNCH, _IC, _PION

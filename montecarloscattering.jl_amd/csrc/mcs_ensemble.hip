@@ -174,19 +174,41 @@ __device__ inline double photon_total_word(const PhotonSrc& S, int s, int t) {
   }
   return x;
 }
-__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_add_photons(double* __restrict__ mean, double* __restrict__ m2, PhotonSrc S, double n) {
-  for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < S.total; w += (long long)gridDim.x * blockDim.x) {
-    double x;
-    if (w < S.off[3]) {
-      const int p = w < S.off[1] ? 0 : w < S.off[2] ? 1 : 2;
-      x = S.obs[p] ? S.obs[p][w - S.off[p]] : 1.0e-99;
-    } else {
-      const int s = (int)((w - S.off[3]) / S.n_pts), t = (int)((w - S.off[3]) % S.n_pts);
-      if (s < S.n_shells) x = photon_total_word(S, s, t);
-      else { x = 0.0; for (int r = 0; r < S.n_shells; ++r) x = x + photon_total_word(S, r, t); }
-    }
-    welford(mean, m2, w, x, n);
+// word w of the sample: the one place where it is formed, for the plain sample and for the one that also deposits
+__device__ inline double photon_sample_word(const PhotonSrc& S, long long w) {
+  if (w < S.off[3]) {
+    const int p = w < S.off[1] ? 0 : w < S.off[2] ? 1 : 2;
+    return S.obs[p] ? S.obs[p][w - S.off[p]] : 1.0e-99;
   }
+  const int s = (int)((w - S.off[3]) / S.n_pts), t = (int)((w - S.off[3]) % S.n_pts);
+  if (s < S.n_shells) return photon_total_word(S, s, t);
+  double x = 0.0;
+  for (int r = 0; r < S.n_shells; ++r) x = x + photon_total_word(S, r, t);
+  return x;
+}
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_add_photons(double* __restrict__ mean, double* __restrict__ m2, PhotonSrc S, double n) {
+  for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < S.total; w += (long long)gridDim.x * blockDim.x)
+    welford(mean, m2, w, photon_sample_word(S, w), n);
+}
+
+// The same sample, and its deposit into the pending vector of the source slot (include/mcs.h, "source sample"): the word is formed
+// once, updates the species' photons slot, and its lit part joins pending[w] -- which the first deposit since the last take starts
+// at 1e-99 without reading it.  Uniform over the four sections, the all-shells rows included.
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_add_photons_deposit(double* __restrict__ mean, double* __restrict__ m2, PhotonSrc S, double n,
+                                                                             double* __restrict__ pending, int first) {
+  for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < S.total; w += (long long)gridDim.x * blockDim.x) {
+    const double x = photon_sample_word(S, w);
+    welford(mean, m2, w, x, n);
+    const double base = first ? 1.0e-99 : pending[w];
+    pending[w] = base + (x > 1.0e-99 ? x : 0.0);
+  }
+}
+
+// a sample that lies on the device as a vector (the source sample: the pending vector)
+__global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_add_vector(double* __restrict__ mean, double* __restrict__ m2, const double* __restrict__ x,
+                                                                    long long total, double n) {
+  for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long long)gridDim.x * blockDim.x)
+    welford(mean, m2, w, x[w], n);
 }
 
 // Chan: f_mean = nb / n, f_m2 = na * nb / n (host doubles)
@@ -671,7 +693,11 @@ const char* photons_layout_error(int n_shells, const int n[3], const int start[3
 
 constexpr int PRODUCTS_BIT = 1 << 30;      // MCS_ENS_PRODUCTS
 constexpr int PHOTONS_BIT = 1 << 29;       // MCS_ENS_PHOTONS
+constexpr int PHOTONS_ALL = 1 << 28;       // MCS_ENS_PHOTONS_ALL
 bool is_photons(int slot) { return slot >= 0 && (slot & PRODUCTS_BIT) == 0 && (slot & PHOTONS_BIT) != 0; }
+bool is_photons_all(int slot) { return slot == PHOTONS_ALL; }
+// (the source slot has the photons slots' vector and layout rules; it is a kind of its own in a comparison)
+bool has_photon_vector(int slot) { return is_photons(slot) || is_photons_all(slot); }
 // (a negative slot has every high bit set: it is no products slot, and is refused as it always was)
 bool is_products(int slot) { return slot >= 0 && (slot & PRODUCTS_BIT) != 0; }
 
@@ -713,9 +739,14 @@ struct mcs_ens {
   std::vector<long long> hn;
   std::vector<DevBuf<double>> hmean, hm2;     // per species slot: HL.total doubles each, or nothing
   bool photons_sampled = false;               // some photons slot has taken a sample (or a merge): the layout is fixed
+  // the source slot MCS_ENS_PHOTONS_ALL (include/mcs.h, "source sample"): its two vectors from its first sample or merge on; the
+  // pending vector from the first deposit on; the species slots deposited since the last take, in call order (host bookkeeping)
+  long long an = 0;
+  DevBuf<double> amean, am2, pending;
+  std::vector<int> deposited;
   bool has_photon_layout() const { return ph_shells > 0; }
   long long len(int slot) const {
-    return is_photons(slot) ? (has_photon_layout() ? HL.total : 0) : is_products(slot) ? PL.total : slot == n_slots - 1 ? E.it_total : E.sp_total;
+    return has_photon_vector(slot) ? (has_photon_layout() ? HL.total : 0) : is_products(slot) ? PL.total : slot == n_slots - 1 ? E.it_total : E.sp_total;
   }
   bool has_window() const { return !x_log_h.empty(); }
 };
@@ -749,6 +780,10 @@ int leave(mcs_ens* e, hipStream_t st) {
 // mean / m2 are null for a products slot that was never sampled (n is then 0).
 struct SlotRef { long long n; double* mean; double* m2; };
 int slot_ref(const mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
+  if (is_photons_all(slot)) {
+    *out = SlotRef{e->an, e->amean.get(), e->am2.get()};
+    return 0;
+  }
   if (is_photons(slot)) {
     const int s = slot ^ PHOTONS_BIT;
     if (s >= e->n_slots - 1)
@@ -799,10 +834,10 @@ void photon_layout_take(mcs_ens* e, int n_shells, const int n[3], const int star
   for (int p = 0; p < 3; ++p) { e->ph_n[p] = n[p]; e->ph_start[p] = start[p]; }
   photons_layout(n_shells, n, n_pts, &e->HL);
 }
-// room for the two vectors of species slot s's photons slot, zeroed on st when they are new
+// room for the two vectors of species slot s's photons slot (s < 0: of the source slot), zeroed on st when they are new
 int photons_reserve(mcs_ens* e, const std::string& who, int s, hipStream_t st) {
-  DevBuf<double>& m = e->hmean[(size_t)s];
-  DevBuf<double>& q = e->hm2[(size_t)s];
+  DevBuf<double>& m = s < 0 ? e->amean : e->hmean[(size_t)s];
+  DevBuf<double>& q = s < 0 ? e->am2 : e->hm2[(size_t)s];
   if (m.get() && q.get()) return 0;
   hipError_t a = m.reserve(e->HL.total);
   if (a == hipSuccess) a = q.reserve(e->HL.total);
@@ -1074,8 +1109,8 @@ int mcs_ens_set_photon_layout(mcs_ens* e, int n_shells, int n_synch, int n_ic, i
   return 0;
 }
 
-int mcs_ens_add_photons(mcs_ens* e, mcs_ctx* src, int slot) {
-  const std::string who = "mcs_ens_add_photons";
+// mcs_ens_add_photons (deposit false) and mcs_ens_add_photons_deposit: one launch either way
+static int add_photons(mcs_ens* e, mcs_ctx* src, int slot, const std::string& who, bool deposit) {
   if (!e || !src) return fail(who + ": null argument");
   if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
   if (slot == e->n_slots - 1) return fail(who + ": slot " + std::to_string(slot) + " is the iteration slot; only a species slot has a photons slot");
@@ -1096,16 +1131,55 @@ int mcs_ens_add_photons(mcs_ens* e, mcs_ctx* src, int slot) {
   if (!any) return fail(who + ": the context holds no mcs_photon_observe result since its last mcs_begin_species, tally write or photons sample");
   S.off[0] = e->HL.synch; S.off[1] = e->HL.ic; S.off[2] = e->HL.pion; S.off[3] = e->HL.total_section;
   S.n_shells = e->ph_shells; S.n_pts = e->ph_npts; S.total = e->HL.total;
+  if (deposit) {
+    for (int s : e->deposited)
+      if (s == slot) return fail(who + ": species slot " + std::to_string(slot) + " has been deposited since the last mcs_ens_add_photons_all");
+    const hipError_t a = e->pending.reserve(e->HL.total);
+    if (a != hipSuccess) return fail(who + ": hipMalloc: " + hipGetErrorString(a));
+  }
   if (enter(e, v.stream)) return 1;
   if (photons_reserve(e, who, slot, v.stream)) return 1;
   const long long n = e->hn[(size_t)slot] + 1;
-  hipLaunchKernelGGL(mcs_k_ens_add_photons, dim3(grid_for(S.total)), dim3(ENS_THREADS), 0, v.stream, e->hmean[(size_t)slot].get(), e->hm2[(size_t)slot].get(), S,
-                     (double)n);
+  if (deposit)
+    hipLaunchKernelGGL(mcs_k_ens_add_photons_deposit, dim3(grid_for(S.total)), dim3(ENS_THREADS), 0, v.stream, e->hmean[(size_t)slot].get(),
+                       e->hm2[(size_t)slot].get(), S, (double)n, e->pending.get(), e->deposited.empty() ? 1 : 0);
+  else
+    hipLaunchKernelGGL(mcs_k_ens_add_photons, dim3(grid_for(S.total)), dim3(ENS_THREADS), 0, v.stream, e->hmean[(size_t)slot].get(),
+                       e->hm2[(size_t)slot].get(), S, (double)n);
   ENSCHK(hipGetLastError());
   e->hn[(size_t)slot] = n;
   e->photons_sampled = true;
+  if (deposit) e->deposited.push_back(slot);
   mcs_ctx_view_photons_taken(src);
   return leave(e, v.stream);
+}
+
+int mcs_ens_add_photons(mcs_ens* e, mcs_ctx* src, int slot) { return add_photons(e, src, slot, "mcs_ens_add_photons", false); }
+
+int mcs_ens_add_photons_deposit(mcs_ens* e, mcs_ctx* src, int slot) { return add_photons(e, src, slot, "mcs_ens_add_photons_deposit", true); }
+
+int mcs_ens_add_photons_all(mcs_ens* e) {
+  const std::string who = "mcs_ens_add_photons_all";
+  if (!e) return fail(who + ": null argument");
+  if (e->deposited.empty()) return fail(who + ": no deposit pending (mcs_ens_add_photons_deposit)");
+  McsCtxView v;
+  if (mcs_ctx_view_get(e->home, &v)) return 1;
+  if (enter(e, v.stream)) return 1;
+  if (photons_reserve(e, who, -1, v.stream)) return 1;
+  const long long n = e->an + 1;
+  hipLaunchKernelGGL(mcs_k_ens_add_vector, dim3(grid_for(e->HL.total)), dim3(ENS_THREADS), 0, v.stream, e->amean.get(), e->am2.get(), e->pending.get(),
+                     (long long)e->HL.total, (double)n);
+  ENSCHK(hipGetLastError());
+  e->an = n;
+  e->photons_sampled = true;
+  e->deposited.clear();
+  return leave(e, v.stream);
+}
+
+int mcs_ens_drop_pending_photons(mcs_ens* e) {
+  if (!e) return fail("mcs_ens_drop_pending_photons: null argument");
+  e->deposited.clear();
+  return 0;
 }
 
 int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
@@ -1165,6 +1239,23 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
     dst->hn[(size_t)s] = na + nb;
     dst->photons_sampled = true;
   }
+  if (src->an > 0) {      // the source slot, like a photons slot; what is pending on either side stays where it is
+    const long long na = dst->an, nb = src->an;
+    if (!dst->has_photon_layout()) photon_layout_take(dst, src->ph_shells, src->ph_n, src->ph_start, src->ph_npts);
+    const long long len = dst->HL.total;
+    if (photons_reserve(dst, "mcs_ens_merge", -1, v.stream)) return 1;
+    if (na == 0) {
+      ENSCHK(hipMemcpyAsync(dst->amean, src->amean, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
+      ENSCHK(hipMemcpyAsync(dst->am2, src->am2, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
+    } else {
+      const double n = (double)(na + nb);
+      hipLaunchKernelGGL(mcs_k_ens_merge, dim3(grid_for(len)), dim3(ENS_THREADS), 0, v.stream, dst->amean.get(), dst->am2.get(), src->amean.get(),
+                         src->am2.get(), len, (double)nb / n, (double)na * (double)nb / n);
+      ENSCHK(hipGetLastError());
+    }
+    dst->an = na + nb;
+    dst->photons_sampled = true;
+  }
   for (int s = 0; s < dst->n_slots; ++s) {
     const long long na = dst->n[(size_t)s], nb = src->n[(size_t)s], len = dst->len(s);
     if (nb == 0) continue;
@@ -1200,6 +1291,7 @@ int mcs_ens_read(mcs_ens* e, int slot, int what, int64_t first, int64_t count, d
   const long long n = r.n;
   if (is_products(slot) && n == 0) return fail("mcs_ens_read: the products slot has never taken a sample");
   if (is_photons(slot) && n == 0) return fail("mcs_ens_read: the photons slot has never taken a sample");
+  if (is_photons_all(slot) && n == 0) return fail("mcs_ens_read: the source slot has never taken a sample");
   if (what == 2 && n < 2) return fail("mcs_ens_read: the standard error needs at least two samples; the slot has " + std::to_string(n));
   McsCtxView v;
   if (mcs_ctx_view_get(e->home, &v)) return 1;
@@ -1255,7 +1347,7 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
       for (int j = 0; j < k; ++j)
         if (windows_differ(ens[j], ens[k])) return fail(who + ": the accumulators' slope windows differ");
   long long len = a->len(slot);
-  if (is_photons(slot))
+  if (has_photon_vector(slot))
     for (int k = 1; k < n_ens; ++k) {
       for (int j = 0; j < k; ++j)
         if (photon_layouts_differ(ens[j], ens[k])) return fail(who + ": the accumulators' photon layouts differ");
@@ -1308,8 +1400,10 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
       a->P.n_ions != b->P.n_ions || a->P.n_itrs != b->P.n_itrs || a->P.num_psd_mom_bins != b->P.num_psd_mom_bins ||
       a->P.num_psd_tht_bins != b->P.num_psd_tht_bins)
     return fail(who + ": the accumulators' layouts differ");
-  // species slot, iteration slot or products slot
-  const auto kind = [](const mcs_ens* e, int slot) { return is_photons(slot) ? 3 : is_products(slot) ? 2 : slot == e->n_slots - 1 ? 1 : 0; };
+  // species slot, iteration slot, products slot, photons slot or source slot
+  const auto kind = [](const mcs_ens* e, int slot) {
+    return is_photons_all(slot) ? 4 : is_photons(slot) ? 3 : is_products(slot) ? 2 : slot == e->n_slots - 1 ? 1 : 0;
+  };
   const long long len = a->len(slot_a);
   if (kind(a, slot_a) != kind(b, slot_b) || len != b->len(slot_b)) return fail(who + ": the two slots differ in kind or length");
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
@@ -1319,7 +1413,7 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
     if (ra.n == 0 || rb.n == 0) return fail(who + ": a products slot has never taken a sample");
     if (windows_differ(a, b)) return fail(who + ": the accumulators' slope windows differ");
   }
-  if (is_photons(slot_a)) {
+  if (has_photon_vector(slot_a)) {
     if (ra.n == 0 || rb.n == 0) return fail(who + ": a photons slot has never taken a sample");
     if (photon_layouts_differ(a, b)) return fail(who + ": the accumulators' photon layouts differ");
   }

@@ -578,6 +578,16 @@ def _check_trigger_args(have_ensemble, pass_what, min_iterations, check_every):
         raise ValueError(f"triggers: check_every {check_every} < 1")
 
 
+def _check_photon_triggers(triggers, photons):
+    """run and run_overlapped refuse a trigger on a photons slot or on the source slot when no spectra are made."""
+    if photons is not None:
+        return
+    if any(ens.Ensemble.is_photons(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on a photons slot needs photons= (a consumers.PhotonSetup; no sample would ever arrive)")
+    if any(ens.Ensemble.is_photons_all(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on the source slot needs photons= (a consumers.PhotonSetup; no sample would ever arrive)")
+
+
 def _add_products(ensemble, prob, backend, ion_fin):
     """The products sample of the iteration whose last species' ion_finalize has just run on `backend` (ensemble.py, "Products"):
     slot n_species - 1, from what the consumers left on the device (a HIP backend) or from ion_fin (the numpy ensemble).  An ensemble
@@ -609,15 +619,22 @@ def _check_triggers(ensemble, triggers, others=()):
 def _species_photons(rs, i_iter, i_ion):
     """The photon spectra at Earth of the species that has just ended on the primary context (run(photons=...)): one ion_finalize of
     ITS tallies (K4; the last species' is the one the iteration's finalize step needs, and is kept for it), its folds and the observed
-    shell spectra (consumers.observed_spectra: K5-K7 and K9 on a HIP backend), and one photons sample of the ensemble."""
-    prob, be = rs.prob, rs.backend
-    ion_fin = consumers.ion_finalize(prob, be, i_ion)
-    if i_ion == len(prob.cfg.species):
+    shell spectra (consumers.observed_spectra: K5-K7 and K9 on a HIP backend), and one photons sample of the ensemble, which also
+    deposits it for the iteration's source sample."""
+    ion_fin, obs = _photons_of_species(rs.prob, rs.backend, i_ion, rs.photons, rs.ensemble)
+    if i_ion == len(rs.prob.cfg.species):
         rs.last_ion_fin = ion_fin
-    obs = consumers.observed_spectra(prob, be, i_ion, rs.photons, ion_fin)
     rs.photon_spectra[i_ion - 1] = obs
-    if rs.ensemble is not None:
-        rs.ensemble.add_photons(be, i_ion - 1, obs)
+
+
+def _photons_of_species(prob, be, i_ion, setup, ensemble):
+    """ion_finalize and the observed spectra of species i_ion from the tallies on `be`; with an ensemble, its photons sample and the
+    deposit into the pending source sample (ensemble.py, "The source") -> (IonFinal, ObservedSpectra)."""
+    ion_fin = consumers.ion_finalize(prob, be, i_ion)
+    obs = consumers.observed_spectra(prob, be, i_ion, setup, ion_fin)
+    if ensemble is not None:
+        ensemble.add_photons(be, i_ion - 1, obs, deposit=True)
+    return ion_fin, obs
 
 
 def _iteration_species(rs, i_iter, before_pcut):
@@ -730,8 +747,12 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     per species and iteration goes into Ensemble.photons_slot(i_ion - 1) (ensemble.py, "Photons"); an ensemble without a photon layout
     first gets consumers.stock_photon_layout(photons.n_shells); triggers may name its parts (zones= shell rows, bins= an energy window
     of one row).  Refused: a trigger on a photons slot without photons=, photons with species_backends, with an enabled communicator,
-    or without finalize.  Error bars of sums across species are left out: means add on the host, variances do not without the
-    covariance.
+    or without finalize.  The spectrum an observer sees is the sum over species, and the species of an iteration are correlated (one
+    profile, one energy-transfer pool), so its error bars do not follow from the species': every species' sample is also deposited
+    into a pending vector (Ensemble.add_photons(deposit=True)), and after the last species of an iteration, before the iteration
+    sample, the ensemble takes that vector as one SOURCE sample into Ensemble.photons_all_slot (ensemble.py, "The source"; same parts,
+    zones= and bins= as a photons slot).  Deposits left by an iteration that raised are dropped at the top of the next.  Triggers may
+    name the source slot; without photons= they are refused like triggers on a photons slot.
     """
     import torch
     comm = comm or Comm(False)
@@ -777,8 +798,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         if ensemble.n_species < len(cfg.species):
             raise ValueError(f"ensemble: {ensemble.n_species} species slots for {len(cfg.species)} species")
     triggers = list(triggers or [])
-    if photons is None and any(ens.Ensemble.is_photons(t.slot) for t in triggers):
-        raise ValueError("triggers: a trigger on a photons slot needs photons= (a consumers.PhotonSetup; no sample would ever arrive)")
+    _check_photon_triggers(triggers, photons)
     if photons is not None:
         if secondaries:
             raise ValueError("photons: not with species_backends (the spectra are made on the context that ran the species, one at a time)")
@@ -822,6 +842,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         backend.begin_iteration(i_iter)
         if ensemble is not None:
             ensemble.begin_iteration(backend)
+            if photons is not None:
+                ensemble.drop_pending_photons()      # (an iteration that raised after a deposit must not reach into this one)
         if multi and not rs.is_root:
             if rs.dev_t is not None:
                 rs.dev_t[0].zero_()
@@ -830,6 +852,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                 f[:] = 0.0
                 backend.write_tallies(f, i)
         _iteration_species(rs, i_iter, before_pcut)
+        if photons is not None and ensemble is not None:
+            ensemble.add_photons_all()               # the source sample: the sum of the species' spectra of this iteration
         if finalize:
             # ion_finalize of the last species (quirk Q2: only its fluxes and pressures reach iter_finalize) and
             # iter_finalize, on rank 0, whose device buffers hold the merged tallies
@@ -899,7 +923,7 @@ ACCUMULATED_OVER_ITERATIONS = ("esc_flux", "px_esc_feb", "energy_esc_feb", "esc_
 def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pcuts: Optional[int] = None,
                    on_iteration_end: Optional[Callable] = None, first_iter: int = 1,
                    blocks_per_launch: Optional[int] = None, ensemble: bool = False, triggers: Optional[list] = None,
-                   min_iterations: int = 2, check_every: int = 1) -> RunResult:
+                   min_iterations: int = 2, check_every: int = 1, photons=None) -> RunResult:
     """The iterations of a run with a FIXED shock profile (smooth-shocks = false -- the stock mc_in.toml, BASELINE
     config[1]) are independent Monte-Carlo realisations: nothing an iteration computes enters the next one's transport
     (src/main_loops.jl:52-121: every tally the transport reads is reset at the top; the RNG keys carry i_iter).  Their
@@ -938,7 +962,13 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     the per-iteration ion_finalize of the last species (ensemble.FINALIZE_NAMES), in iteration order.  Every context's ensemble also
     takes the products sample of run(finalize=True, ensemble=...) right after that ion_finalize, inside the iteration's job, so that
     triggers on a products slot work through the rounds and the merged summary like any other.
-    The photon spectra of run(photons=...) are not made here: run_overlapped(photons=) is left out."""
+    photons: a consumers.PhotonSetup, as in run(photons=...): every iteration's job makes each species' spectra at its species end, on
+    the job's context (one ion_finalize per species; the last species' is the one handed to iter_finalize, it is not run a second
+    time), and with ensemble=True feeds that context's ensemble -- one photons sample per species, deposited, and the source sample
+    taken inside the job where the products sample is taken.  Rounds, checks and the final merge then cover the photons slots and the
+    source slot like every other; an ensemble gets consumers.stock_photon_layout(photons.n_shells).  RunResult.photons holds the
+    spectra of the last iteration consumed.  Refused: a trigger on a photons slot or on the source slot without photons=.  None:
+    no spectra are made."""
     cfg, P = prob.cfg, prob.params
     n_itrs = n_itrs if n_itrs is not None else cfg.num_iterations
     K = len(backends)
@@ -948,12 +978,16 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     triggers = list(triggers or [])
     if triggers:
         _check_trigger_args(bool(ensemble), "ensemble=True", min_iterations, check_every)
+    _check_photon_triggers(triggers, photons)
     enss = [ens.Ensemble.for_backend(be, len(cfg.species)) for be in backends] if ensemble else [None] * K
     try:
+        if photons is not None and ensemble:
+            for e in enss:
+                e.set_photon_layout(consumers.stock_photon_layout(photons.n_shells))
         for t in triggers:
             enss[0].check_trigger(t)
         return _overlapped_rounds(prob, backends, enss, n_itrs, max_pcuts, on_iteration_end, first_iter, blocks_per_launch, triggers,
-                                  min_iterations, check_every)
+                                  min_iterations, check_every, photons)
     except BaseException:       # (a refused trigger, or whatever an iteration, a hook or a check raised: the run's accumulators go with it)
         for e in enss:
             if e is not None:
@@ -962,9 +996,10 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
 
 
 def _overlapped_rounds(prob, backends, enss, n_itrs, max_pcuts, on_iteration_end, first_iter, blocks_per_launch, triggers, min_iterations,
-                       check_every) -> RunResult:
+                       check_every, photons=None) -> RunResult:
     """run_overlapped once its arguments have passed: the rounds, the checks and the end of the run.  enss: one ensemble per context,
     or None each."""
+    n_sp = len(prob.cfg.species)
     cfg, P = prob.cfg, prob.params
     K, L = len(backends), backends[0].layout
     ensemble = enss[0] is not None
@@ -977,16 +1012,27 @@ def _overlapped_rounds(prob, backends, enss, n_itrs, max_pcuts, on_iteration_end
         k = (i_iter - first_iter) % K
         with locks[k]:                       # a context carries one iteration at a time
             be = backends[k]
+            spectra, fins, at_species_end = [None] * n_sp, {}, None
+            if photons is not None:
+                if enss[k] is not None:
+                    enss[k].drop_pending_photons()      # (an iteration that raised after a deposit must not reach into this one)
+
+                def at_species_end(it, i_ion, G_f, G_i):
+                    # run(photons=)'s species end, on this context: the spectra, the photons sample and its deposit
+                    fins[i_ion], spectra[i_ion - 1] = _photons_of_species(prob, be, i_ion, photons, enss[k])
             busy.enter()
             with busy.geometry(be, lambda n: blocks_per_launch if n > 1 else 0, bool(blocks_per_launch) and K > 1) as geometry:
                 # (long_draws=0: the pcuts are not pipelined here -- the other iterations' launches are what fills this one's tails, and
                 # the per-pcut hook needs the per-pcut loop; MCS_LONG_DRAWS does not reach this call)
                 res = run(prob, be, None, n_itrs=1, max_pcuts=max_pcuts, first_iter=i_iter, species_tallies="light", final_full_read=False,
-                          before_pcut=geometry, long_draws=0, ensemble=enss[k])
-                ion_fin = consumers.ion_finalize(prob, be, len(cfg.species))     # K4, before the context is reused
+                          before_pcut=geometry, long_draws=0, ensemble=enss[k], on_species_end=at_species_end)
+                # K4, before the context is reused (with photons the last species end has made it already)
+                ion_fin = fins[n_sp] if photons is not None else consumers.ion_finalize(prob, be, n_sp)
                 if enss[k] is not None:
+                    if photons is not None:
+                        enss[k].add_photons_all()               # the source sample of this iteration
                     _add_products(enss[k], prob, be, ion_fin)
-        return k, res, ion_fin
+        return k, res, ion_fin, spectra
 
     stats, per_species, iter_finals, local_steps = [], [], [], []
     last = {}                                 # context -> its latest result (running totals of the never-reset tallies)
@@ -1001,7 +1047,7 @@ def _overlapped_rounds(prob, backends, enss, n_itrs, max_pcuts, on_iteration_end
         for rnd in rounds:
             futs = [pool.submit(one, i) for i in rnd]
             for i_iter, fu in zip(rnd, futs):      # consumed in iteration order
-                k, res, ion_fin = fu.result()
+                k, res, ion_fin, last_spectra = fu.result()
                 fin = itf.iter_finalize(prob, st, sm, i_iter, res.tallies_f64, L, ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
                 local_steps.append((i_iter, len(cfg.species), res.steps_helix + res.steps_retro - total[k]))
                 total[k] = res.steps_helix + res.steps_retro
@@ -1036,4 +1082,5 @@ def _overlapped_rounds(prob, backends, enss, n_itrs, max_pcuts, on_iteration_end
             enss[0].finalize_mean[name], enss[0].finalize_stderr[name], enss[0].finalize_count = ens.stats_over(
                 [getattr(ion_fin, name) for _, _, ion_fin in iter_finals])
     return RunResult(f, i64, per_species, stats, *_steps(i64, ng), iter_finals, st, local_steps, ensemble=enss[0],
-                     convergence=Convergence(checks, first_iter + n_done - 1, satisfied) if triggers else None)
+                     convergence=Convergence(checks, first_iter + n_done - 1, satisfied) if triggers else None,
+                     photons=list(last_spectra) if photons is not None else None)

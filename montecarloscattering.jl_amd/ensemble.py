@@ -57,6 +57,12 @@ sample.  `set_photon_layout` (a consumers.PhotonLayout) fixes the vector before 
 
 zones= of a `Request` or `Trigger` selects shell rows of one of these parts, bins= an energy window of one row.
 
+The source (include/mcs.h, "source sample"): an observer sees one spectrum, summed over species, and the species of an iteration are
+correlated, so the sum is sampled itself.  `Ensemble.photons_all_slot`, one per ensemble, has the photons layout and names.  A species'
+sample taken with `add_photons(..., deposit=True)` also joins a pending vector -- per word 1e-99, or what earlier deposits left, plus
+the word where it is above 1e-99 -- and `add_photons_all` takes that vector as one sample and forgets the deposits
+(`pending_photons`, `drop_pending_photons`).  A species slot deposits once between two takes.
+
 A summary range can be restricted in momentum: `Request` / `Trigger(bins=(l_lo, l_hi))` together with a single zone, zones=(z, z+1),
 on a part of shape [zone][bins] (the three dNdp_* and the six marginals) is the word range off + z * per + l_lo of l_hi - l_lo
 words.  dN/dp spans a dozen decades: without it the floor_frac selection keeps the thermal peak and drops the tail.  Several zones
@@ -124,6 +130,7 @@ PHOTON_NAMES = ("synch", "ic", "pion", "total")
 ZONE_PARTS = ZONE_PARTS + PHOTON_NAMES
 BIN_PARTS = BIN_PARTS + PHOTON_NAMES
 PHOTONS_BIT = capi.ENS_PHOTONS_BIT        # photons slot of species slot s: s | PHOTONS_BIT (MCS_ENS_PHOTONS)
+PHOTONS_ALL = capi.ENS_PHOTONS_ALL        # the source slot: the photon spectrum summed over species (MCS_ENS_PHOTONS_ALL)
 
 
 class EnsLayout:
@@ -569,6 +576,7 @@ class Ensemble:
         self.finalize_count = 0
         self.window = None             # (l_lo, l_hi, x_log) of set_slope_window
         self.photon_layout = None      # consumers.PhotonLayout of set_photon_layout
+        self._deposited: List[int] = []      # species slots deposited since the last add_photons_all, in deposit order
 
     @staticmethod
     def for_backend(backend, n_species: int) -> "Ensemble":
@@ -597,6 +605,22 @@ class Ensemble:
     def is_photons(slot: int) -> bool:
         return slot >= 0 and not slot & PRODUCTS_BIT and bool(slot & PHOTONS_BIT)
 
+    photons_all_slot = PHOTONS_ALL     # the source slot, one per ensemble (MCS_ENS_PHOTONS_ALL)
+
+    @staticmethod
+    def is_photons_all(slot: int) -> bool:
+        return slot == PHOTONS_ALL
+
+    @classmethod
+    def _has_photon_vector(cls, slot: int) -> bool:
+        """A photons slot or the source slot: the sample vector is that of the photon layout."""
+        return cls.is_photons(slot) or cls.is_photons_all(slot)
+
+    @property
+    def pending_photons(self) -> Tuple[int, ...]:
+        """The species slots deposited (add_photons(deposit=True)) since the last add_photons_all, in deposit order."""
+        return tuple(self._deposited)
+
     def set_photon_layout(self, layout):
         """The shells, the energy words of every process and their offsets on the common grid (a consumers.PhotonLayout;
         consumers.stock_photon_layout(n_shells) is that of the stock energy grids).  Before the first photons sample; refused afterwards."""
@@ -613,13 +637,15 @@ class Ensemble:
 
     def names(self, slot: int):
         self._check_slot(slot)
-        if self.is_photons(slot):
+        if self._has_photon_vector(slot):
             return PHOTON_NAMES
         if self.is_products(slot):
             return PRODUCT_NAMES
         return ITERATION_NAMES if slot == self.iteration_slot else SPECIES_NAMES
 
     def _check_slot(self, slot: int):
+        if self.is_photons_all(slot):
+            return
         if self.is_photons(slot):
             if not 0 <= slot ^ PHOTONS_BIT < self.n_species:
                 raise ValueError(f"ensemble: photons slot of slot {slot ^ PHOTONS_BIT}, which is no species slot (0..{self.n_species - 1})")
@@ -630,7 +656,7 @@ class Ensemble:
             raise ValueError(f"ensemble: slot {slot} outside 0..{self.n_species}")
 
     def _len(self, slot: int) -> int:
-        if self.is_photons(slot):
+        if self._has_photon_vector(slot):
             return 0 if self.photon_layout is None else self.photon_layout.offsets()["_total"]
         if self.is_products(slot):
             return self.layout.products_total
@@ -638,8 +664,8 @@ class Ensemble:
 
     def _where(self, slot: int, name: str):
         self._check_slot(slot)
-        if self.is_photons(slot):
-            kind = f"the photons slot of species slot {slot ^ PHOTONS_BIT}"
+        if self._has_photon_vector(slot):
+            kind = "the source slot" if self.is_photons_all(slot) else f"the photons slot of species slot {slot ^ PHOTONS_BIT}"
             if self.photon_layout is None:
                 raise ValueError(f"ensemble: {kind} has no layout yet (set_photon_layout)")
             rows = self.photon_layout.rows
@@ -730,7 +756,7 @@ class Ensemble:
                 raise ValueError("ensemble: a merged summary needs ensembles of the same kind, slots and layout")
 
     def _kind(self, slot: int) -> str:
-        return "photons" if self.is_photons(slot) else "products" if self.is_products(slot) else "iteration" if slot == self.iteration_slot else "species"
+        return "source" if self.is_photons_all(slot) else "photons" if self.is_photons(slot) else "products" if self.is_products(slot) else "iteration" if slot == self.iteration_slot else "species"
 
     def compare(self, other: "Ensemble", slot: int, requests: Sequence[CompareRequest], other_slot: Optional[int] = None) -> List[Difference]:
         """One Difference per request (at most MAX_RANGES; they may overlap): slot `slot` of this ensemble, A, against slot
@@ -799,18 +825,30 @@ class HostEnsemble(Ensemble):
         self._hmean: Dict[int, np.ndarray] = {}
         self._hm2: Dict[int, np.ndarray] = {}
         self._hn = [0] * self.n_species
+        # the source slot, from its first sample or merge on, and the pending vector, from the first deposit on
+        self._amean: Optional[np.ndarray] = None
+        self._am2: Optional[np.ndarray] = None
+        self._an = 0
+        self._pending: Optional[np.ndarray] = None
 
     def _set_photon_layout(self, layout):
-        if any(self._hn):
+        if any(self._hn) or self._an:
             raise ValueError("ensemble: a photons slot has taken a sample; the photon layout stays as it is")
 
-    def add_photons(self, backend, slot: int, observed):
+    def add_photons(self, backend, slot: int, observed=None, deposit: bool = False):
         """One photons sample of species slot `slot` from an `ObservedSpectra` (consumers.observed_spectra on `backend`): the observed
-        processes as they are, the others 1e-99, the total rebuilt on this ensemble's layout."""
+        processes as they are, the others 1e-99, the total rebuilt on this ensemble's layout.  deposit: the sample also joins the pending
+        vector of the source slot (include/mcs.h, "source sample"): per word 1e-99 (the first deposit since the last take) or the word
+        as it stands (a later one) plus the sample's word where that is above 1e-99.  Refused, with nothing changed, for a species slot
+        already deposited since the last take."""
         from .consumers import PHOTON_PROCESSES, photon_total
         self._check_slot(slot)
-        if self.is_photons(slot) or self.is_products(slot) or slot == self.iteration_slot:
+        if self._has_photon_vector(slot) or self.is_products(slot) or slot == self.iteration_slot:
             raise ValueError(f"ensemble: slot {slot} is no species slot; only a species slot has a photons slot")
+        if observed is None:
+            raise ValueError("ensemble: the numpy ensemble takes its photons sample from an ObservedSpectra")
+        if deposit and slot in self._deposited:
+            raise ValueError(f"ensemble: species slot {slot} has been deposited since the last add_photons_all")
         lay = self.photon_layout
         if lay is None:
             raise ValueError("ensemble: no photon layout (set_photon_layout)")
@@ -825,13 +863,33 @@ class HostEnsemble(Ensemble):
         if slot not in self._hmean:
             self._hmean[slot], self._hm2[slot] = np.zeros(x.size), np.zeros(x.size)
         self._hn[slot] = welford_update(self._hmean[slot], self._hm2[slot], self._hn[slot], x)
+        if deposit:
+            lit = np.where(x > 1.0e-99, x, 0.0)
+            self._pending = (self._pending if self._deposited else 1.0e-99) + lit
+            self._deposited.append(slot)
+
+    def add_photons_all(self):
+        """The take: one sample of the source slot, the pending vector as it stands; the deposits are then forgotten.  Refused with
+        no deposit pending."""
+        if not self._deposited:
+            raise ValueError("ensemble: no deposit pending (add_photons(deposit=True))")
+        if self._amean is None:
+            self._amean, self._am2 = np.zeros(self._pending.size), np.zeros(self._pending.size)
+        self._an = welford_update(self._amean, self._am2, self._an, self._pending)
+        self._deposited.clear()
+
+    def drop_pending_photons(self):
+        """Forgets the deposits since the last take (the next first deposit starts the pending vector anew)."""
+        self._deposited.clear()
 
     @staticmethod
     def _photon_layouts_differ(a, b) -> bool:
         return a.photon_layout is not None and b.photon_layout is not None and a.photon_layout.args() != b.photon_layout.args()
 
     def _vectors(self, slot: int):
-        """(mean, M2, n) of a slot; (None, None, 0) for a products slot that was never sampled."""
+        """(mean, M2, n) of a slot; (None, None, 0) for a products, photons or source slot that was never sampled."""
+        if self.is_photons_all(slot):
+            return self._amean, self._am2, self._an
         if self.is_photons(slot):
             s = slot ^ PHOTONS_BIT
             return self._hmean.get(s), self._hm2.get(s), self._hn[s]
@@ -898,8 +956,18 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: merge of ensembles whose slope windows differ")
         if self._photon_layouts_differ(self, other):
             raise ValueError("ensemble: merge of ensembles whose photon layouts differ")
-        if any(other._hn) and self.photon_layout is None:
+        if (any(other._hn) or other._an) and self.photon_layout is None:
             self.photon_layout = other.photon_layout
+        if other._an:         # the source slot, like a photons slot; what is pending on either side stays where it is
+            na, nb = self._an, other._an
+            if na == 0:
+                self._amean, self._am2 = other._amean.copy(), other._am2.copy()
+            else:
+                n = float(na + nb)
+                d = other._amean - self._amean
+                self._amean = self._amean + d * (float(nb) / n)
+                self._am2 = (self._am2 + other._am2) + (d * d) * (float(na) * float(nb) / n)
+            self._an = na + nb
         for s in range(self.n_species):
             na, nb = self._hn[s], other._hn[s]
             if nb == 0:
@@ -947,6 +1015,8 @@ class HostEnsemble(Ensemble):
 
     def _read(self, slot, what, first, count):
         mean, m2, n = self._vectors(slot)
+        if mean is None and self.is_photons_all(slot):
+            raise ValueError("ensemble: the source slot has never taken a sample")
         if mean is None and self.is_photons(slot):
             raise ValueError(f"ensemble: the photons slot of species slot {slot ^ PHOTONS_BIT} has never taken a sample")
         if mean is None:
@@ -967,7 +1037,7 @@ class HostEnsemble(Ensemble):
         es = [self] + others
         if self.is_products(slot) and any(self._windows_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose slope windows differ")
-        if self.is_photons(slot) and any(self._photon_layouts_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
+        if self._has_photon_vector(slot) and any(self._photon_layouts_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose photon layouts differ")
         for first, count, floor_frac, tol in ranges:
             m, q, na = None, None, 0
@@ -991,7 +1061,7 @@ class HostEnsemble(Ensemble):
     def _compare(self, other, slot, other_slot, n_a, n_b, ranges):
         if self.is_products(slot) and self._windows_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose slope windows differ")
-        if self.is_photons(slot) and self._photon_layouts_differ(self, other):
+        if self._has_photon_vector(slot) and self._photon_layouts_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose photon layouts differ")
         (ma, qa, _), (mb, qb, _) = self._vectors(slot), other._vectors(other_slot)
         return [difference_of(ma[first:first + count], qa[first:first + count], n_a, mb[first:first + count], qb[first:first + count], n_b,
@@ -1002,6 +1072,8 @@ class HostEnsemble(Ensemble):
         self._check_slot(slot)
         if slot == self.iteration_slot:
             raise ValueError(f"ensemble: slot {slot} is the iteration slot; only a species slot has histograms")
+        if self.is_photons_all(slot):
+            raise ValueError("ensemble: the source slot is no species slot; only a species slot has histograms")
         L, o = self.layout.tally, self.layout.tally.offsets
         f, i = backend.read_tallies()
         m = self._mean[slot]
@@ -1052,16 +1124,31 @@ class HipEnsemble(Ensemble):
     def _set_photon_layout(self, layout):
         self._chk(self.lib.mcs_ens_set_photon_layout(self.h, *layout.args()))
 
-    def add_photons(self, backend: HipBackend, slot: int, observed=None):
+    def add_photons(self, backend: HipBackend, slot: int, observed=None, deposit: bool = False):
         """One photons sample of species slot `slot` from what mcs_photon_observe (consumers.observed_spectra) left on the backend's
-        device (mcs_ens_add_photons); nothing crosses to the host, `observed` is not read."""
-        self._chk(self.lib.mcs_ens_add_photons(self.h, backend.h, int(slot)))
+        device (mcs_ens_add_photons); nothing crosses to the host, `observed` is not read.  deposit: the same launch also adds the
+        sample to the pending vector of the source slot (mcs_ens_add_photons_deposit)."""
+        if not deposit:
+            self._chk(self.lib.mcs_ens_add_photons(self.h, backend.h, int(slot)))
+            return
+        self._chk(self.lib.mcs_ens_add_photons_deposit(self.h, backend.h, int(slot)))
+        self._deposited.append(int(slot))      # (what the library keeps, mirrored: it has refused a second deposit of the slot)
+
+    def add_photons_all(self):
+        """The take: one sample of the source slot from the pending vector on the device (mcs_ens_add_photons_all)."""
+        self._chk(self.lib.mcs_ens_add_photons_all(self.h))
+        self._deposited.clear()
+
+    def drop_pending_photons(self):
+        self._chk(self.lib.mcs_ens_drop_pending_photons(self.h))
+        self._deposited.clear()
 
     def merge(self, other: "HipEnsemble"):
         if not isinstance(other, HipEnsemble):
             raise ValueError("ensemble: merge needs an ensemble of the same kind, slots and layout")
         self._chk(self.lib.mcs_ens_merge(self.h, other.h))
-        if self.photon_layout is None and other.photon_layout is not None and any(other.count(other.photons_slot(s)) for s in range(other.n_species)):
+        if self.photon_layout is None and other.photon_layout is not None and (
+                other.count(PHOTONS_ALL) or any(other.count(other.photons_slot(s)) for s in range(other.n_species))):
             self.photon_layout = other.photon_layout      # (as the library does)
         if self.window is None and other.window is not None and any(other.count(other.products_slot(s)) for s in range(other.n_species)):
             self.window = other.window      # (as the library does: an accumulator without a window takes the one its samples were made with)
