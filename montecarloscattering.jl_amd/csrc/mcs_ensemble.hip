@@ -11,7 +11,11 @@
 // largest |mean|, then the relative errors of the words that pass the floor it sets -- each thread over its words in ascending
 // order, then per wave by shuffles, per block through LDS, one partial per block into a scratch buffer of the accumulator, and a
 // last kernel that folds a range's partials in index order.  No atomics: the same state gives the same bits.
-// The comparison of two slots (mcs_ens_compare) is the same walk over the (mean, M2) pairs of both with a record of its own.
+// The comparison of two slots (mcs_ens_compare) is the same walk over the (mean, M2) pairs of both with a record of its own: the
+// four sweep kernels share one routine, walk, for which words a thread sees and in which order.
+// Host side: every slot of every kind -- species, iteration, products, photons, source -- is one Slot (count, mean, M2); decode reads
+// a slot number's bits, slot_ref finds its Slot, reserve allocates it, merge_slot merges it, and plan_ranges checks the ranges of a
+// summary or comparison and lays out their blocks in one pass.
 // A context is seen through mcs_ctx_view.h; its stream carries the work, an event of the accumulator orders successive operations
 // that were queued on different streams.
 #include <hip/hip_runtime.h>
@@ -316,7 +320,7 @@ __device__ inline SumSpan span_of(const SumRange& R, int blk, int n_blk) {
 }
 
 // Where the sweeps take a word's (mean, M2) from.  A source says how many pairs a thread loads before it looks at them (LOADS);
-// which words a thread sees, and in which order, is span_of's business alone, the same for every source.
+// which words a thread sees, and in which order, is the business of span_of and walk alone, the same for every source.
 //   SrcOne         the two vectors of one accumulator
 //   SrcMerged<N>   the Chan merge of N >= 2 accumulators, folded per word in registers in list order with the factors of every
 //                  step (f_mean[k] = nb / n, f_m2[k] = na * nb / n, host doubles as in mcs_k_ens_merge); nothing is written back
@@ -382,26 +386,60 @@ struct SrcMerged {
   }
 };
 
+// The one walk of a thread over its words of a span, which all four sweeps take: the odd word in front, U pairs at a time (all
+// loaded before any is looked at), the pairs that are left, the odd word at the end.  rd reads a single word (at) or a 16-byte pair
+// of every vector it covers (pair; lo / hi: its two words); see(i, word) gets every word with its index i in the range.
+template <int U, class Reader, class See>
+__device__ inline void walk(const SumSpan& s, const Reader& rd, See&& see) {
+  const long long i0 = 2 * s.pair0 - s.first;        // word index - first of pair 0's first word
+  if (s.ends && (s.first & 1)) see(0, rd.at(s.first));
+  long long j = s.j0;
+  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
+    typename Reader::Pair p[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) p[u] = rd.pair(s.pair0 + j + u * s.stride);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long ju = j + u * s.stride;
+      see(i0 + 2 * ju, rd.lo(p[u])); see(i0 + 2 * ju + 1, rd.hi(p[u]));
+    }
+  }
+  for (; j < s.n_pairs; j += s.stride) {
+    const typename Reader::Pair p = rd.pair(s.pair0 + j);
+    see(i0 + 2 * j, rd.lo(p)); see(i0 + 2 * j + 1, rd.hi(p));
+  }
+  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(s.count - 1, rd.at(s.first + s.count - 1));
+}
+
+// the readers of a summary's source: the means alone (sweep 1), mean and M2 (sweep 2)
+template <class Src>
+struct ReadMean {
+  using Pair = double2;
+  const Src& src;
+  __device__ double at(long long w) const { return src.mean_at(w); }
+  __device__ double2 pair(long long p) const { return src.mean_pair(p); }
+  __device__ double lo(const double2& p) const { return p.x; }
+  __device__ double hi(const double2& p) const { return p.y; }
+};
+struct MeanM2 { double m, q; };
+template <class Src>
+struct ReadBoth {
+  struct Pair { double2 m, q; };
+  const Src& src;
+  __device__ MeanM2 at(long long w) const { MeanM2 r; src.at(w, r.m, r.q); return r; }
+  __device__ Pair pair(long long p) const { Pair r; src.pair(p, r.m, r.q); return r; }
+  __device__ MeanM2 lo(const Pair& p) const { return MeanM2{p.m.x, p.q.x}; }
+  __device__ MeanM2 hi(const Pair& p) const { return MeanM2{p.m.y, p.q.y}; }
+};
+
 // sweep 1: the largest |mean| over the words whose mean is finite, per block
 template <class Src>
 __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_amax(const Src src, const SumParams* __restrict__ P, double* __restrict__ pmax) {
   __shared__ double tmp[SUM_WAVES];
   const int r = range_of_block(P, blockIdx.x), o0 = P->off[r];
   const SumSpan s = span_of(P->r[r], blockIdx.x - o0, P->off[r + 1] - o0);
-  constexpr int U = Src::LOADS;
   double a = 0.0;
-  auto see = [&](double m) { const double x = fabs(m); if (finite_(m) && x > a) a = x; };
-  if (s.ends && (s.first & 1)) see(src.mean_at(s.first));
-  long long j = s.j0;
-  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
-    double2 p[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) p[u] = src.mean_pair(s.pair0 + j + u * s.stride);
-#pragma unroll
-    for (int u = 0; u < U; ++u) { see(p[u].x); see(p[u].y); }
-  }
-  for (; j < s.n_pairs; j += s.stride) { const double2 p = src.mean_pair(s.pair0 + j); see(p.x); see(p.y); }
-  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(src.mean_at(s.first + s.count - 1));
+  walk<Src::LOADS>(s, ReadMean<Src>{src}, [&](long long, double m) { const double x = fabs(m); if (finite_(m) && x > a) a = x; });
   a = block_max(a, tmp);
   if (threadIdx.x == 0) pmax[blockIdx.x] = a;
 }
@@ -415,13 +453,13 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_stats(const Src src
   const int r = range_of_block(P, blockIdx.x), o0 = P->off[r], n_blk = P->off[r + 1] - o0;
   const SumRange R = P->r[r];
   const SumSpan s = span_of(R, blockIdx.x - o0, n_blk);
-  constexpr int U = Src::LOADS;
   double a = 0.0;
   for (int k = threadIdx.x; k < n_blk; k += ENS_THREADS) { const double x = pmax[o0 + k]; a = x > a ? x : a; }
   const double amax_used = block_max(a, tmp);
   const double floor_abs = R.floor_frac * amax_used, tol = R.tol;
   SumRec v = rec_empty(amax_used);
-  auto see = [&](long long idx, double m, double q) {
+  walk<Src::LOADS>(s, ReadBoth<Src>{src}, [&](long long idx, const MeanM2& w) {
+    const double m = w.m, q = w.q;
     if (!finite_(m) || !finite_(q)) { v.n_nonf += 1; return; }
     const double x = fabs(m);
     v.amax = x > v.amax ? x : v.amax;
@@ -435,30 +473,7 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_sum_stats(const Src src
       v.sum_rel2 = v.sum_rel2 + rel * rel;
       if (rel > v.max_rel || (rel == v.max_rel && idx < v.arg)) { v.max_rel = rel; v.arg = idx; }
     }
-  };
-  const long long i0 = 2 * s.pair0 - s.first;        // word index - first of pair 0's first word
-  if (s.ends && (s.first & 1)) { double m, q; src.at(s.first, m, q); see(0, m, q); }
-  long long j = s.j0;
-  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
-    double2 m[U], q[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) src.pair(s.pair0 + j + u * s.stride, m[u], q[u]);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long long ju = j + u * s.stride;
-      see(i0 + 2 * ju, m[u].x, q[u].x); see(i0 + 2 * ju + 1, m[u].y, q[u].y);
-    }
-  }
-  for (; j < s.n_pairs; j += s.stride) {
-    double2 m, q;
-    src.pair(s.pair0 + j, m, q);
-    see(i0 + 2 * j, m.x, q.x); see(i0 + 2 * j + 1, m.y, q.y);
-  }
-  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) {
-    double m, q;
-    src.at(s.first + s.count - 1, m, q);
-    see(s.count - 1, m, q);
-  }
+  });
   rec_block_join(v, rtmp);
   if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
@@ -532,11 +547,15 @@ struct SrcCmp {
     w.finite = finite_(xa) && finite_(ya) && finite_(xb) && finite_(yb) && finite_(w.d) && finite_(w.s2);
     return w;
   }
+  // (its own reader for walk)
+  struct Pair { double2 xa, ya, xb, yb; };
   __device__ CmpWord at(long long i) const { return word(ma[i], qa[i], mb[i], qb[i]); }
-  __device__ void pair(long long p, double2& xa, double2& ya, double2& xb, double2& yb) const {
-    xa = reinterpret_cast<const double2*>(ma)[p]; ya = reinterpret_cast<const double2*>(qa)[p];
-    xb = reinterpret_cast<const double2*>(mb)[p]; yb = reinterpret_cast<const double2*>(qb)[p];
+  __device__ Pair pair(long long p) const {
+    return Pair{reinterpret_cast<const double2*>(ma)[p], reinterpret_cast<const double2*>(qa)[p], reinterpret_cast<const double2*>(mb)[p],
+                reinterpret_cast<const double2*>(qb)[p]};
   }
+  __device__ CmpWord lo(const Pair& p) const { return word(p.xa.x, p.ya.x, p.xb.x, p.yb.x); }
+  __device__ CmpWord hi(const Pair& p) const { return word(p.xa.y, p.ya.y, p.xb.y, p.yb.y); }
 };
 
 // sweep 1: the largest scale = max(|ma|, |mb|) over the finite words, per block
@@ -544,24 +563,8 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_cmp_amax(const SrcCmp s
   __shared__ double tmp[SUM_WAVES];
   const int r = range_of_block(P, blockIdx.x), o0 = P->off[r];
   const SumSpan s = span_of(P->r[r], blockIdx.x - o0, P->off[r + 1] - o0);
-  constexpr int U = SrcCmp::LOADS;
   double a = 0.0;
-  auto see = [&](const CmpWord& w) { if (w.finite && w.scale > a) a = w.scale; };
-  if (s.ends && (s.first & 1)) see(src.at(s.first));
-  long long j = s.j0;
-  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
-    double2 xa[U], ya[U], xb[U], yb[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) src.pair(s.pair0 + j + u * s.stride, xa[u], ya[u], xb[u], yb[u]);
-#pragma unroll
-    for (int u = 0; u < U; ++u) { see(src.word(xa[u].x, ya[u].x, xb[u].x, yb[u].x)); see(src.word(xa[u].y, ya[u].y, xb[u].y, yb[u].y)); }
-  }
-  for (; j < s.n_pairs; j += s.stride) {
-    double2 xa, ya, xb, yb;
-    src.pair(s.pair0 + j, xa, ya, xb, yb);
-    see(src.word(xa.x, ya.x, xb.x, yb.x)); see(src.word(xa.y, ya.y, xb.y, yb.y));
-  }
-  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(src.at(s.first + s.count - 1));
+  walk<SrcCmp::LOADS>(s, src, [&](long long, const CmpWord& w) { if (w.finite && w.scale > a) a = w.scale; });
   a = block_max(a, tmp);
   if (threadIdx.x == 0) pmax[blockIdx.x] = a;
 }
@@ -574,13 +577,12 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_cmp_stats(const SrcCmp 
   const int r = range_of_block(P, blockIdx.x), o0 = P->off[r], n_blk = P->off[r + 1] - o0;
   const SumRange R = P->r[r];
   const SumSpan s = span_of(R, blockIdx.x - o0, n_blk);
-  constexpr int U = SrcCmp::LOADS;
   double a = 0.0;
   for (int k = threadIdx.x; k < n_blk; k += ENS_THREADS) { const double x = pmax[o0 + k]; a = x > a ? x : a; }
   const double amax = block_max(a, tmp);
   const double floor_abs = R.floor_frac * amax, zcut = R.tol;
   CmpRec v = cmp_empty(amax);
-  auto see = [&](long long idx, const CmpWord& w) {
+  walk<SrcCmp::LOADS>(s, src, [&](long long idx, const CmpWord& w) {
     if (!w.finite) { v.n_nonf += 1; return; }
     if (w.scale > 0.0 && w.scale >= floor_abs) {
       v.n_sel += 1;
@@ -595,26 +597,7 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_cmp_stats(const SrcCmp 
       v.sum_z2 = v.sum_z2 + z * z;
       if (az > v.max_z || (az == v.max_z && idx < v.arg)) { v.max_z = az; v.arg = idx; }
     }
-  };
-  const long long i0 = 2 * s.pair0 - s.first;        // word index - first of pair 0's first word
-  if (s.ends && (s.first & 1)) see(0, src.at(s.first));
-  long long j = s.j0;
-  for (; j + (U - 1) * s.stride < s.n_pairs; j += U * s.stride) {
-    double2 xa[U], ya[U], xb[U], yb[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) src.pair(s.pair0 + j + u * s.stride, xa[u], ya[u], xb[u], yb[u]);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long long ju = j + u * s.stride;
-      see(i0 + 2 * ju, src.word(xa[u].x, ya[u].x, xb[u].x, yb[u].x)); see(i0 + 2 * ju + 1, src.word(xa[u].y, ya[u].y, xb[u].y, yb[u].y));
-    }
-  }
-  for (; j < s.n_pairs; j += s.stride) {
-    double2 xa, ya, xb, yb;
-    src.pair(s.pair0 + j, xa, ya, xb, yb);
-    see(i0 + 2 * j, src.word(xa.x, ya.x, xb.x, yb.x)); see(i0 + 2 * j + 1, src.word(xa.y, ya.y, xb.y, yb.y));
-  }
-  if (s.ends && ((s.first + s.count) & 1) && s.count > (s.first & 1)) see(s.count - 1, src.at(s.first + s.count - 1));
+  });
   rec_block_join(v, rtmp);
   if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
@@ -694,12 +677,25 @@ const char* photons_layout_error(int n_shells, const int n[3], const int start[3
 constexpr int PRODUCTS_BIT = 1 << 30;      // MCS_ENS_PRODUCTS
 constexpr int PHOTONS_BIT = 1 << 29;       // MCS_ENS_PHOTONS
 constexpr int PHOTONS_ALL = 1 << 28;       // MCS_ENS_PHOTONS_ALL
-bool is_photons(int slot) { return slot >= 0 && (slot & PRODUCTS_BIT) == 0 && (slot & PHOTONS_BIT) != 0; }
-bool is_photons_all(int slot) { return slot == PHOTONS_ALL; }
-// (the source slot has the photons slots' vector and layout rules; it is a kind of its own in a comparison)
-bool has_photon_vector(int slot) { return is_photons(slot) || is_photons_all(slot); }
-// (a negative slot has every high bit set: it is no products slot, and is refused as it always was)
-bool is_products(int slot) { return slot >= 0 && (slot & PRODUCTS_BIT) != 0; }
+
+// The five kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
+// to (s; not yet held against the accumulator's species slots, slot_ref does that; -1 for the iteration and the source slot).
+// A negative number has every high bit set: it is no companion slot, and is refused as a species slot outside the range.
+// The source slot has the photons slots' vector and layout rules; it is a kind of its own in a comparison.
+enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE };
+const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source"};
+struct SlotId { Kind kind; int s; };
+SlotId decode(int slot, int n_slots) {
+  if (slot == PHOTONS_ALL) return SlotId{SOURCE, -1};
+  if (slot >= 0 && (slot & PRODUCTS_BIT) != 0) return SlotId{PRODUCTS, slot ^ PRODUCTS_BIT};
+  if (slot >= 0 && (slot & PHOTONS_BIT) != 0) return SlotId{PHOTONS, slot ^ PHOTONS_BIT};
+  return slot == n_slots - 1 ? SlotId{ITERATION, -1} : SlotId{SPECIES, slot};
+}
+bool has_photon_vector(Kind k) { return k == PHOTONS || k == SOURCE; }
+
+// What every slot is: the samples it has taken and its two vectors (those of a products, photons or source slot from its first
+// sample or merge on, nothing before)
+struct Slot { long long n = 0; DevBuf<double> mean, m2; };
 
 }  // namespace
 
@@ -711,8 +707,7 @@ struct mcs_ens {
   mcs_ens_layout E;
   IncRanges inc;
   int n_slots = 0;                            // the species slots and, last, the iteration slot
-  std::vector<long long> n;                   // samples of every slot
-  std::vector<DevBuf<double>> mean, m2;       // per slot: sp_total (it_total for the last) doubles each
+  std::vector<Slot> main;                     // those: sp_total (it_total for the last) doubles per vector
   DevBuf<double> marg;                        // the marginals of the sample being added (part 4)
   DevBuf<double> snap;                        // [esc_flux, energy_recv_pool) of snap_of at the last begin-iteration call
   mcs_ctx* snap_of = nullptr;                 // (null: no snapshot since the last iteration sample)
@@ -725,30 +720,41 @@ struct mcs_ens {
   DevBuf<double> sum_pmax;        DevBuf<SumRec> sum_part;
   // mcs_ens_compare with this accumulator as A shares sum_par and sum_pmax with it; its records are another type
   PinnedBuf<CmpRec> cmp_out_h;    DevBuf<CmpRec> cmp_out, cmp_part;
-  // the products slots, one beside every species slot (include/mcs.h, "products sample"): vectors allocated at the first sample
+  // the products slots, one beside every species slot (include/mcs.h, "products sample"): PL.total doubles per vector
   mcs_ens_products_layout PL;
-  std::vector<long long> pn;
-  std::vector<DevBuf<double>> pmean, pm2;     // per species slot: PL.total doubles each, or nothing
+  std::vector<Slot> products;
   int win_lo = 0, win_hi = 0;                 // the slope window; none while x_log_h is empty
   std::vector<double> x_log_h;                // [nmom+1]
   DevBuf<double> x_log, slope;                // its device copy; the slopes of the sample being added [3][n_grid]
   bool products_sampled = false;              // some products slot has taken a sample (or a merge): the window is fixed
-  // the photons slots, likewise (include/mcs.h, "photons sample"); no layout while ph_shells is 0
+  // the photons slots, likewise (include/mcs.h, "photons sample"): HL.total doubles per vector; no layout while ph_shells is 0
   mcs_ens_photons_layout HL{};
   int ph_shells = 0, ph_n[3] = {0, 0, 0}, ph_start[3] = {0, 0, 0}, ph_npts = 0;
-  std::vector<long long> hn;
-  std::vector<DevBuf<double>> hmean, hm2;     // per species slot: HL.total doubles each, or nothing
+  std::vector<Slot> photons;
   bool photons_sampled = false;               // some photons slot has taken a sample (or a merge): the layout is fixed
-  // the source slot MCS_ENS_PHOTONS_ALL (include/mcs.h, "source sample"): its two vectors from its first sample or merge on; the
-  // pending vector from the first deposit on; the species slots deposited since the last take, in call order (host bookkeeping)
-  long long an = 0;
-  DevBuf<double> amean, am2, pending;
+  // the source slot MCS_ENS_PHOTONS_ALL (include/mcs.h, "source sample"), of the photons layout; the pending vector from the first
+  // deposit on; the species slots deposited since the last take, in call order (host bookkeeping)
+  Slot source;
+  DevBuf<double> pending;
   std::vector<int> deposited;
   bool has_photon_layout() const { return ph_shells > 0; }
-  long long len(int slot) const {
-    return has_photon_vector(slot) ? (has_photon_layout() ? HL.total : 0) : is_products(slot) ? PL.total : slot == n_slots - 1 ? E.it_total : E.sp_total;
-  }
   bool has_window() const { return !x_log_h.empty(); }
+  // the one way from a (checked) slot number to its record, and the length of the vectors of a kind
+  Slot& at(SlotId id) {
+    return id.kind == SOURCE ? source : id.kind == PHOTONS ? photons[(size_t)id.s] : id.kind == PRODUCTS ? products[(size_t)id.s]
+           : main[(size_t)(id.kind == ITERATION ? n_slots - 1 : id.s)];
+  }
+  long long len(Kind k) const {
+    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ITERATION ? E.it_total : E.sp_total;
+  }
+  // every slot number the accumulator has
+  std::vector<int> slot_numbers() const {
+    std::vector<int> all;
+    for (int s = 0; s < n_slots; ++s) all.push_back(s);
+    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); }
+    all.push_back(PHOTONS_ALL);
+    return all;
+  }
 };
 
 namespace {
@@ -776,31 +782,30 @@ int leave(mcs_ens* e, hipStream_t st) {
   return 0;
 }
 
-// What a count, read or summary call works on: a species slot, the iteration slot, or the products slot of a species slot.
-// mean / m2 are null for a products slot that was never sampled (n is then 0).
-struct SlotRef { long long n; double* mean; double* m2; };
-int slot_ref(const mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
-  if (is_photons_all(slot)) {
-    *out = SlotRef{e->an, e->amean.get(), e->am2.get()};
-    return 0;
-  }
-  if (is_photons(slot)) {
-    const int s = slot ^ PHOTONS_BIT;
-    if (s >= e->n_slots - 1)
-      return fail(who + ": photons slot of slot " + std::to_string(s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
-    *out = SlotRef{e->hn[(size_t)s], e->hmean[(size_t)s].get(), e->hm2[(size_t)s].get()};
-    return 0;
-  }
-  if (is_products(slot)) {
-    const int s = slot ^ PRODUCTS_BIT;
-    if (s >= e->n_slots - 1)
-      return fail(who + ": products slot of slot " + std::to_string(s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
-    *out = SlotRef{e->pn[(size_t)s], e->pmean[(size_t)s].get(), e->pm2[(size_t)s].get()};
-    return 0;
-  }
-  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
-  *out = SlotRef{e->n[(size_t)slot], e->mean[(size_t)slot].get(), e->m2[(size_t)slot].get()};
+// What a count, read, summary or comparison call works on: the slot of that number, its kind and the length of its vectors
+// (which are null for a products, photons or source slot that was never sampled; n is then 0).
+struct SlotRef { Kind kind; Slot* slot; long long len; };
+int slot_ref(mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
+  const SlotId id = decode(slot, e->n_slots);
+  if ((id.kind == PRODUCTS || id.kind == PHOTONS) && id.s >= e->n_slots - 1)
+    return fail(who + ": " + KIND_NAME[id.kind] + " slot of slot " + std::to_string(id.s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
+  if (id.kind == SPECIES && (slot < 0 || slot >= e->n_slots)) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  *out = SlotRef{id.kind, &e->at(id), e->len(id.kind)};
   return 0;
+}
+
+// slot is a species slot, where a call takes nothing else; tail: what the caller says of the iteration slot
+int species_slot(const mcs_ens* e, const std::string& who, int slot, const char* tail) {
+  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
+  if (slot == e->n_slots - 1) return fail(who + ": slot " + std::to_string(slot) + " is the iteration slot; " + tail);
+  return 0;
+}
+
+// the two accumulators have the same tally, binning and sample layout (whether they have as many slots is the caller's question)
+bool same_layout(const mcs_ens* a, const mcs_ens* b) {
+  return a->E.sp_total == b->E.sp_total && a->E.it_total == b->E.it_total && a->L.total == b->L.total && a->P.n_grid == b->P.n_grid &&
+         a->P.n_ions == b->P.n_ions && a->P.n_itrs == b->P.n_itrs && a->P.num_psd_mom_bins == b->P.num_psd_mom_bins &&
+         a->P.num_psd_tht_bins == b->P.num_psd_tht_bins;
 }
 
 // both have a slope window, and the two differ in a bound or in the bits of an x_log word
@@ -808,19 +813,6 @@ bool windows_differ(const mcs_ens* a, const mcs_ens* b) {
   if (!a->has_window() || !b->has_window()) return false;
   return a->win_lo != b->win_lo || a->win_hi != b->win_hi || a->x_log_h.size() != b->x_log_h.size() ||
          memcmp(a->x_log_h.data(), b->x_log_h.data(), a->x_log_h.size() * sizeof(double)) != 0;
-}
-
-// room for the two vectors of species slot s's products slot, zeroed on st when they are new
-int products_reserve(mcs_ens* e, const std::string& who, int s, hipStream_t st) {
-  DevBuf<double>& m = e->pmean[(size_t)s];
-  DevBuf<double>& q = e->pm2[(size_t)s];
-  if (m.get() && q.get()) return 0;
-  hipError_t a = m.reserve(e->PL.total);
-  if (a == hipSuccess) a = q.reserve(e->PL.total);
-  if (a != hipSuccess) { m.reset(); q.reset(); return fail(who + ": hipMalloc: " + hipGetErrorString(a)); }
-  ENSCHK(hipMemsetAsync(m.get(), 0, (size_t)e->PL.total * sizeof(double), st));
-  ENSCHK(hipMemsetAsync(q.get(), 0, (size_t)e->PL.total * sizeof(double), st));
-  return 0;
 }
 
 // both have a photon layout, and the two differ
@@ -834,36 +826,69 @@ void photon_layout_take(mcs_ens* e, int n_shells, const int n[3], const int star
   for (int p = 0; p < 3; ++p) { e->ph_n[p] = n[p]; e->ph_start[p] = start[p]; }
   photons_layout(n_shells, n, n_pts, &e->HL);
 }
-// room for the two vectors of species slot s's photons slot (s < 0: of the source slot), zeroed on st when they are new
-int photons_reserve(mcs_ens* e, const std::string& who, int s, hipStream_t st) {
-  DevBuf<double>& m = s < 0 ? e->amean : e->hmean[(size_t)s];
-  DevBuf<double>& q = s < 0 ? e->am2 : e->hm2[(size_t)s];
-  if (m.get() && q.get()) return 0;
-  hipError_t a = m.reserve(e->HL.total);
-  if (a == hipSuccess) a = q.reserve(e->HL.total);
-  if (a != hipSuccess) { m.reset(); q.reset(); return fail(who + ": hipMalloc: " + hipGetErrorString(a)); }
-  ENSCHK(hipMemsetAsync(m.get(), 0, (size_t)e->HL.total * sizeof(double), st));
-  ENSCHK(hipMemsetAsync(q.get(), 0, (size_t)e->HL.total * sizeof(double), st));
+
+// room for the two vectors of a slot, len doubles each, zeroed on st when they are new
+int reserve(Slot& s, long long len, const std::string& who, hipStream_t st) {
+  if (s.mean.get() && s.m2.get()) return 0;
+  hipError_t a = s.mean.reserve(len);
+  if (a == hipSuccess) a = s.m2.reserve(len);
+  if (a != hipSuccess) { s.mean.reset(); s.m2.reset(); return fail(who + ": hipMalloc: " + hipGetErrorString(a)); }
+  ENSCHK(hipMemsetAsync(s.mean.get(), 0, (size_t)len * sizeof(double), st));
+  ENSCHK(hipMemsetAsync(s.m2.get(), 0, (size_t)len * sizeof(double), st));
   return 0;
 }
 
-// one range of a summary or a comparison against a vector of len words; cut: its tol or zcut, by that name -> its blocks added
-int check_range(const std::string& which, long long len, long long first, long long count, double floor_frac, double cut, const char* cut_name,
+// Chan's merge of slot b into slot a, both of len words, on st: nothing for an empty b, a copy into an empty a, else one launch
+int merge_slot(Slot& a, const Slot& b, long long len, hipStream_t st) {
+  if (b.n == 0) return 0;
+  if (reserve(a, len, "mcs_ens_merge", st)) return 1;
+  if (a.n == 0) {
+    ENSCHK(hipMemcpyAsync(a.mean, b.mean, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, st));
+    ENSCHK(hipMemcpyAsync(a.m2, b.m2, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, st));
+  } else {
+    const double n = (double)(a.n + b.n);
+    hipLaunchKernelGGL(mcs_k_ens_merge, dim3(grid_for(len)), dim3(ENS_THREADS), 0, st, a.mean.get(), a.m2.get(), b.mean.get(), b.m2.get(), len,
+                       (double)b.n / n, (double)a.n * (double)b.n / n);
+    ENSCHK(hipGetLastError());
+  }
+  a.n += b.n;
+  return 0;
+}
+
+// The ranges of a summary (cut: their tol) or of a comparison (their zcut; cut_name says which) against a vector of len words:
+// checked and, in the same pass, written with their block offsets into e's pinned SumParams -> the blocks they take
+// (every earlier call has waited for its copies: the pinned block is free)
+template <class Range>
+int plan_ranges(const std::string& who, mcs_ens* e, long long len, int n_ranges, const Range* ranges, double Range::*cut, const char* cut_name,
                 long long* n_blocks) {
-  if (first < 0 || count < 0 || first > len || count > len - first) return fail(which + " lies outside the slot's sample vector");
-  if (!(floor_frac >= 0.0 && floor_frac <= 1.0)) return fail(which + ": floor_frac outside [0, 1]");
-  if (!(cut >= 0.0)) return fail(which + ": " + cut_name + " is negative or not a number");
-  const long long b = (count + SUM_CHUNK - 1) / SUM_CHUNK;
-  *n_blocks += b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b;
+  const hipError_t a = e->sum_par_h.reserve(1);
+  if (a != hipSuccess) return fail(who + ": scratch allocation: " + hipGetErrorString(a));
+  SumParams* P = e->sum_par_h.get();
+  P->n_ranges = n_ranges;
+  P->off[0] = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    const Range& R = ranges[r];
+    const std::string which = who + ": range " + std::to_string(r);
+    if (R.first < 0 || R.count < 0 || R.first > len || R.count > len - R.first) return fail(which + " lies outside the slot's sample vector");
+    if (!(R.floor_frac >= 0.0 && R.floor_frac <= 1.0)) return fail(which + ": floor_frac outside [0, 1]");
+    if (!(R.*cut >= 0.0)) return fail(which + ": " + cut_name + " is negative or not a number");
+    P->r[r] = SumRange{R.first, R.count, R.floor_frac, R.*cut};
+    const long long b = (R.count + SUM_CHUNK - 1) / SUM_CHUNK;
+    P->off[r + 1] = P->off[r] + (int)(b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b);
+  }
+  *n_blocks = P->off[n_ranges];
   return 0;
 }
 
-// the ranges of a summary call against a vector of len words -> the blocks they take
-int check_ranges(const std::string& who, long long len, int n_ranges, const mcs_ens_range* ranges, long long* n_blocks) {
-  *n_blocks = 0;
-  for (int r = 0; r < n_ranges; ++r)
-    if (check_range(who + ": range " + std::to_string(r), len, ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].tol, "tol", n_blocks))
-      return 1;
+// the rest of e's scratch for a planned call of n_blocks blocks whose records are Rec
+template <class Rec>
+int reserve_scratch(const std::string& who, mcs_ens* e, PinnedBuf<Rec>& out_h, DevBuf<Rec>& out, DevBuf<Rec>& part, long long n_blocks) {
+  hipError_t a = e->sum_par.reserve(1);
+  if (a == hipSuccess) a = out_h.reserve(SUM_MAX_RANGES);
+  if (a == hipSuccess) a = out.reserve(SUM_MAX_RANGES);
+  if (a == hipSuccess) a = e->sum_pmax.reserve(n_blocks);
+  if (a == hipSuccess) a = part.reserve(n_blocks);
+  if (a != hipSuccess) return fail(who + ": scratch allocation: " + hipGetErrorString(a));
   return 0;
 }
 
@@ -874,34 +899,20 @@ SrcMerged<N> merged_src(const double* const* mean, const double* const* m2, cons
   return s;
 }
 
-// The checked ranges summarised from the word source src with the count n: on the stream of list[0]'s home context, after what
-// every accumulator of the list queued last, with list[0]'s scratch; waits for the device.
+// The ranges that plan_ranges has left in list[0]'s pinned SumParams, n_blocks blocks, summarised from the word source src with
+// the count n: on the stream of list[0]'s home context, after what every accumulator of the list queued last, with list[0]'s
+// scratch; waits for the device.
 template <class Src>
-int sum_run(const std::string& who, mcs_ens* const* list, int n_list, const Src& src, long long n, int n_ranges, const mcs_ens_range* ranges,
-            long long n_blocks, mcs_ens_summary* out) {
+int sum_run(const std::string& who, mcs_ens* const* list, int n_list, const Src& src, long long n, int n_ranges, long long n_blocks,
+            mcs_ens_summary* out) {
   mcs_ens* e = list[0];
   McsCtxView v;
   if (mcs_ctx_view_get(e->home, &v)) return 1;
-  hipError_t a = e->sum_par_h.reserve(1);
-  if (a == hipSuccess) a = e->sum_par.reserve(1);
-  if (a == hipSuccess) a = e->sum_out_h.reserve(SUM_MAX_RANGES);
-  if (a == hipSuccess) a = e->sum_out.reserve(SUM_MAX_RANGES);
-  if (a == hipSuccess) a = e->sum_pmax.reserve(n_blocks);
-  if (a == hipSuccess) a = e->sum_part.reserve(n_blocks);
-  if (a != hipSuccess) return fail(who + ": scratch allocation: " + hipGetErrorString(a));
-  // (every earlier call has waited for its copies: the pinned blocks are free)
-  SumParams* P = e->sum_par_h.get();
-  P->n_ranges = n_ranges;
-  P->off[0] = 0;
-  for (int r = 0; r < n_ranges; ++r) {
-    P->r[r] = SumRange{ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].tol};
-    const long long b = (ranges[r].count + SUM_CHUNK - 1) / SUM_CHUNK;
-    P->off[r + 1] = P->off[r] + (int)(b > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : b);
-  }
+  if (reserve_scratch(who, e, e->sum_out_h, e->sum_out, e->sum_part, n_blocks)) return 1;
   for (int k = 0; k < n_list; ++k)
     if (enter(list[k], v.stream)) return 1;
   const double denom = (double)n * (double)(n - 1);
-  ENSCHK(hipMemcpyAsync(e->sum_par.get(), P, sizeof(SumParams), hipMemcpyHostToDevice, v.stream));
+  ENSCHK(hipMemcpyAsync(e->sum_par.get(), e->sum_par_h.get(), sizeof(SumParams), hipMemcpyHostToDevice, v.stream));
   if (n_blocks > 0) {
     hipLaunchKernelGGL(mcs_k_ens_sum_amax<Src>, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, src, e->sum_par.get(), e->sum_pmax.get());
     ENSCHK(hipGetLastError());
@@ -957,23 +968,14 @@ int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   e->device = v.device; e->home = home; e->P = v.P; e->L = v.L;
   ens_layout(&v.P, &e->E);
   products_layout(&v.P, &e->PL);
-  e->pn.assign((size_t)n_species_slots, 0);
-  e->pmean.resize((size_t)n_species_slots); e->pm2.resize((size_t)n_species_slots);
-  e->hn.assign((size_t)n_species_slots, 0);
-  e->hmean.resize((size_t)n_species_slots); e->hm2.resize((size_t)n_species_slots);
+  e->products.resize((size_t)n_species_slots);
+  e->photons.resize((size_t)n_species_slots);
   const mcs_layout& L = v.L;
   e->inc = IncRanges{{L.esc_flux, L.esc_energy_eff, L.spectra_coupled}, {L.px_esc_feb, L.weight_coupled, L.energy_transfer_pool}};
   e->n_slots = n_species_slots + 1;
-  e->n.assign((size_t)e->n_slots, 0);
-  e->mean.resize((size_t)e->n_slots); e->m2.resize((size_t)e->n_slots);
-  for (int s = 0; s < e->n_slots; ++s) {
-    const long long len = e->len(s);
-    for (DevBuf<double>* b : {&e->mean[(size_t)s], &e->m2[(size_t)s]}) {
-      const hipError_t a = b->reserve(len);
-      if (a != hipSuccess) return fail(std::string("mcs_ens_create: hipMalloc: ") + hipGetErrorString(a));
-      ENSCHK(hipMemsetAsync(b->get(), 0, (size_t)len * sizeof(double), v.stream));
-    }
-  }
+  e->main.resize((size_t)e->n_slots);
+  for (int s = 0; s < e->n_slots; ++s)
+    if (reserve(e->main[(size_t)s], e->len(s == e->n_slots - 1 ? ITERATION : SPECIES), "mcs_ens_create", v.stream)) return 1;
   hipError_t a = e->marg.reserve(e->E.sp_total - e->E.sp_psd_mom);
   if (a == hipSuccess) a = e->snap.reserve(e->E.it_sums_n);
   if (a != hipSuccess) return fail(std::string("mcs_ens_create: hipMalloc: ") + hipGetErrorString(a));
@@ -1003,8 +1005,7 @@ int mcs_ens_begin_iteration(mcs_ens* e, mcs_ctx* src) {
 
 int mcs_ens_add_species(mcs_ens* e, mcs_ctx* src, int slot) {
   if (!e || !src) return fail("mcs_ens_add_species: null argument");
-  if (slot < 0 || slot >= e->n_slots) return fail("mcs_ens_add_species: slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
-  if (slot == e->n_slots - 1) return fail("mcs_ens_add_species: slot " + std::to_string(slot) + " is the iteration slot; it takes no species sample");
+  if (species_slot(e, "mcs_ens_add_species", slot, "it takes no species sample")) return 1;
   McsCtxView v;
   if (view_of(e, src, "mcs_ens_add_species", &v)) return 1;
   if (enter(e, v.stream)) return 1;
@@ -1016,11 +1017,11 @@ int mcs_ens_add_species(mcs_ens* e, mcs_ctx* src, int slot) {
   ENSCHK(hipGetLastError());
   hipLaunchKernelGGL(mcs_k_ens_marg_tht, dim3((unsigned)ng, 3), dim3(MARG_ROWS), 0, v.stream, v.T + e->L.psd, e->marg.get(), ng, nm, nt, marg_stride);
   ENSCHK(hipGetLastError());
-  const long long n = e->n[(size_t)slot] + 1;
-  hipLaunchKernelGGL(mcs_k_ens_add_species, dim3(grid_for(E.sp_total)), dim3(ENS_THREADS), 0, v.stream, e->mean[(size_t)slot].get(), e->m2[(size_t)slot].get(),
-                     v.T, v.I, e->marg.get(), E, (double)n);
+  Slot& sl = e->main[(size_t)slot];
+  hipLaunchKernelGGL(mcs_k_ens_add_species, dim3(grid_for(E.sp_total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), v.T, v.I,
+                     e->marg.get(), E, (double)(sl.n + 1));
   ENSCHK(hipGetLastError());
-  e->n[(size_t)slot] = n;
+  sl.n += 1;
   return leave(e, v.stream);
 }
 
@@ -1030,12 +1031,11 @@ int mcs_ens_add_iteration(mcs_ens* e, mcs_ctx* src) {
   if (view_of(e, src, "mcs_ens_add_iteration", &v)) return 1;
   if (e->snap_of != src) return fail("mcs_ens_add_iteration: no mcs_ens_begin_iteration snapshot of this context since the last iteration sample");
   if (enter(e, v.stream)) return 1;
-  const int slot = e->n_slots - 1;
-  const long long n = e->n[(size_t)slot] + 1;
-  hipLaunchKernelGGL(mcs_k_ens_add_iteration, dim3(grid_for(e->E.it_total)), dim3(ENS_THREADS), 0, v.stream, e->mean[(size_t)slot].get(),
-                     e->m2[(size_t)slot].get(), v.T, e->snap.get(), e->E, e->inc, (double)n);
+  Slot& sl = e->main.back();
+  hipLaunchKernelGGL(mcs_k_ens_add_iteration, dim3(grid_for(e->E.it_total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), v.T,
+                     e->snap.get(), e->E, e->inc, (double)(sl.n + 1));
   ENSCHK(hipGetLastError());
-  e->n[(size_t)slot] = n;
+  sl.n += 1;
   e->snap_of = nullptr;
   return leave(e, v.stream);
 }
@@ -1066,25 +1066,24 @@ int mcs_ens_set_slope_window(mcs_ens* e, int l_lo, int l_hi, const double* x_log
 int mcs_ens_add_products(mcs_ens* e, mcs_ctx* src, int slot) {
   const std::string who = "mcs_ens_add_products";
   if (!e || !src) return fail(who + ": null argument");
-  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
-  if (slot == e->n_slots - 1) return fail(who + ": slot " + std::to_string(slot) + " is the iteration slot; only a species slot has a products slot");
+  if (species_slot(e, who, slot, "only a species slot has a products slot")) return 1;
   if (!e->has_window()) return fail(who + ": no slope window (mcs_ens_set_slope_window)");
   McsCtxView v;
   if (view_of(e, src, who.c_str(), &v)) return 1;
   if (!v.have_dndp_cr || !v.have_thermo || !v.cout)
     return fail(who + ": the context needs an mcs_dndp_cr and an mcs_thermo_calcs since its last mcs_begin_species and its last products sample");
   if (enter(e, v.stream)) return 1;
-  if (products_reserve(e, who, slot, v.stream)) return 1;
+  Slot& sl = e->products[(size_t)slot];
+  if (reserve(sl, e->PL.total, who, v.stream)) return 1;
   const long long ng = e->P.n_grid, n_cout = e->PL.slope_sf;
   const int nm = e->P.num_psd_mom_bins + 2;
   hipLaunchKernelGGL(mcs_k_ens_slope, dim3(grid_for(3 * ng)), dim3(ENS_THREADS), 0, v.stream, v.cout, e->x_log.get(), e->slope.get(), 3 * ng, nm,
                      e->win_lo, e->win_hi);
   ENSCHK(hipGetLastError());
-  const long long n = e->pn[(size_t)slot] + 1;
-  hipLaunchKernelGGL(mcs_k_ens_add_products, dim3(grid_for(e->PL.total)), dim3(ENS_THREADS), 0, v.stream, e->pmean[(size_t)slot].get(),
-                     e->pm2[(size_t)slot].get(), v.cout, e->slope.get(), n_cout, (long long)e->PL.total, (double)n);
+  hipLaunchKernelGGL(mcs_k_ens_add_products, dim3(grid_for(e->PL.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), v.cout,
+                     e->slope.get(), n_cout, (long long)e->PL.total, (double)(sl.n + 1));
   ENSCHK(hipGetLastError());
-  e->pn[(size_t)slot] = n;
+  sl.n += 1;
   e->products_sampled = true;
   mcs_ctx_view_products_taken(src);
   return leave(e, v.stream);
@@ -1112,8 +1111,7 @@ int mcs_ens_set_photon_layout(mcs_ens* e, int n_shells, int n_synch, int n_ic, i
 // mcs_ens_add_photons (deposit false) and mcs_ens_add_photons_deposit: one launch either way
 static int add_photons(mcs_ens* e, mcs_ctx* src, int slot, const std::string& who, bool deposit) {
   if (!e || !src) return fail(who + ": null argument");
-  if (slot < 0 || slot >= e->n_slots) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
-  if (slot == e->n_slots - 1) return fail(who + ": slot " + std::to_string(slot) + " is the iteration slot; only a species slot has a photons slot");
+  if (species_slot(e, who, slot, "only a species slot has a photons slot")) return 1;
   if (!e->has_photon_layout()) return fail(who + ": no photon layout (mcs_ens_set_photon_layout)");
   McsCtxView v;
   if (view_of(e, src, who.c_str(), &v)) return 1;
@@ -1138,16 +1136,15 @@ static int add_photons(mcs_ens* e, mcs_ctx* src, int slot, const std::string& wh
     if (a != hipSuccess) return fail(who + ": hipMalloc: " + hipGetErrorString(a));
   }
   if (enter(e, v.stream)) return 1;
-  if (photons_reserve(e, who, slot, v.stream)) return 1;
-  const long long n = e->hn[(size_t)slot] + 1;
+  Slot& sl = e->photons[(size_t)slot];
+  if (reserve(sl, e->HL.total, who, v.stream)) return 1;
   if (deposit)
-    hipLaunchKernelGGL(mcs_k_ens_add_photons_deposit, dim3(grid_for(S.total)), dim3(ENS_THREADS), 0, v.stream, e->hmean[(size_t)slot].get(),
-                       e->hm2[(size_t)slot].get(), S, (double)n, e->pending.get(), e->deposited.empty() ? 1 : 0);
+    hipLaunchKernelGGL(mcs_k_ens_add_photons_deposit, dim3(grid_for(S.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), S,
+                       (double)(sl.n + 1), e->pending.get(), e->deposited.empty() ? 1 : 0);
   else
-    hipLaunchKernelGGL(mcs_k_ens_add_photons, dim3(grid_for(S.total)), dim3(ENS_THREADS), 0, v.stream, e->hmean[(size_t)slot].get(),
-                       e->hm2[(size_t)slot].get(), S, (double)n);
+    hipLaunchKernelGGL(mcs_k_ens_add_photons, dim3(grid_for(S.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), S, (double)(sl.n + 1));
   ENSCHK(hipGetLastError());
-  e->hn[(size_t)slot] = n;
+  sl.n += 1;
   e->photons_sampled = true;
   if (deposit) e->deposited.push_back(slot);
   mcs_ctx_view_photons_taken(src);
@@ -1165,12 +1162,12 @@ int mcs_ens_add_photons_all(mcs_ens* e) {
   McsCtxView v;
   if (mcs_ctx_view_get(e->home, &v)) return 1;
   if (enter(e, v.stream)) return 1;
-  if (photons_reserve(e, who, -1, v.stream)) return 1;
-  const long long n = e->an + 1;
-  hipLaunchKernelGGL(mcs_k_ens_add_vector, dim3(grid_for(e->HL.total)), dim3(ENS_THREADS), 0, v.stream, e->amean.get(), e->am2.get(), e->pending.get(),
-                     (long long)e->HL.total, (double)n);
+  Slot& sl = e->source;
+  if (reserve(sl, e->HL.total, who, v.stream)) return 1;
+  hipLaunchKernelGGL(mcs_k_ens_add_vector, dim3(grid_for(e->HL.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), e->pending.get(),
+                     (long long)e->HL.total, (double)(sl.n + 1));
   ENSCHK(hipGetLastError());
-  e->an = n;
+  sl.n += 1;
   e->photons_sampled = true;
   e->deposited.clear();
   return leave(e, v.stream);
@@ -1186,90 +1183,37 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (!dst || !src) return fail("mcs_ens_merge: null argument");
   if (dst == src) return fail("mcs_ens_merge: dst and src are the same accumulator");
   if (dst->device != src->device) return fail("mcs_ens_merge: the accumulators are on different devices");
-  if (dst->n_slots != src->n_slots || dst->E.sp_total != src->E.sp_total || dst->E.it_total != src->E.it_total || dst->L.total != src->L.total ||
-      dst->P.n_grid != src->P.n_grid || dst->P.n_ions != src->P.n_ions || dst->P.n_itrs != src->P.n_itrs)
-    return fail("mcs_ens_merge: the accumulators' slots or layouts differ");
+  if (dst->n_slots != src->n_slots || !same_layout(dst, src)) return fail("mcs_ens_merge: the accumulators' slots or layouts differ");
   if (windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' slope windows differ");
   if (photon_layouts_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' photon layouts differ");
   McsCtxView v;
   if (mcs_ctx_view_get(dst->home, &v)) return 1;
-  bool any_products = false;
-  for (int s = 0; s < src->n_slots - 1; ++s) any_products = any_products || src->pn[(size_t)s] > 0;
+  const std::vector<int> slots = dst->slot_numbers();
+  bool any[5] = {false, false, false, false, false};      // per kind: src has samples in a slot of it
+  for (int slot : slots) {
+    const SlotId id = decode(slot, src->n_slots);
+    any[id.kind] = any[id.kind] || src->at(id).n > 0;
+  }
+  const bool any_products = any[PRODUCTS], any_photons = any[PHOTONS] || any[SOURCE];
   if (any_products && !dst->has_window()) {
     hipError_t a = dst->x_log.reserve((long long)src->x_log_h.size());
     if (a == hipSuccess) a = dst->slope.reserve(3LL * dst->P.n_grid);
     if (a != hipSuccess) return fail(std::string("mcs_ens_merge: hipMalloc: ") + hipGetErrorString(a));
   }
   if (enter(dst, v.stream) || enter(src, v.stream)) return 1;
-  if (any_products && !dst->has_window()) {      // an accumulator without a window takes the one its samples were made with
+  // an accumulator without a window or a photon layout takes the one its samples were made with
+  if (any_products && !dst->has_window()) {
     ENSCHK(hipMemcpyAsync(dst->x_log.get(), src->x_log.get(), src->x_log_h.size() * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
     dst->x_log_h = src->x_log_h; dst->win_lo = src->win_lo; dst->win_hi = src->win_hi;
   }
-  for (int s = 0; s < src->n_slots - 1; ++s) {
-    const long long na = dst->pn[(size_t)s], nb = src->pn[(size_t)s], len = dst->PL.total;
-    if (nb == 0) continue;
-    if (products_reserve(dst, "mcs_ens_merge", s, v.stream)) return 1;
-    if (na == 0) {
-      ENSCHK(hipMemcpyAsync(dst->pmean[(size_t)s], src->pmean[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-      ENSCHK(hipMemcpyAsync(dst->pm2[(size_t)s], src->pm2[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-    } else {
-      const double n = (double)(na + nb);
-      hipLaunchKernelGGL(mcs_k_ens_merge, dim3(grid_for(len)), dim3(ENS_THREADS), 0, v.stream, dst->pmean[(size_t)s].get(), dst->pm2[(size_t)s].get(),
-                         src->pmean[(size_t)s].get(), src->pm2[(size_t)s].get(), len, (double)nb / n, (double)na * (double)nb / n);
-      ENSCHK(hipGetLastError());
-    }
-    dst->pn[(size_t)s] = na + nb;
-    dst->products_sampled = true;
+  if (any_photons && !dst->has_photon_layout()) photon_layout_take(dst, src->ph_shells, src->ph_n, src->ph_start, src->ph_npts);
+  // (the source slot merges like a photons slot; what is pending on either side stays where it is)
+  for (int slot : slots) {
+    const SlotId id = decode(slot, dst->n_slots);
+    if (merge_slot(dst->at(id), src->at(id), dst->len(id.kind), v.stream)) return 1;
   }
-  for (int s = 0; s < src->n_slots - 1; ++s) {
-    const long long na = dst->hn[(size_t)s], nb = src->hn[(size_t)s];
-    if (nb == 0) continue;
-    if (!dst->has_photon_layout()) photon_layout_take(dst, src->ph_shells, src->ph_n, src->ph_start, src->ph_npts);
-    const long long len = dst->HL.total;
-    if (photons_reserve(dst, "mcs_ens_merge", s, v.stream)) return 1;
-    if (na == 0) {
-      ENSCHK(hipMemcpyAsync(dst->hmean[(size_t)s], src->hmean[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-      ENSCHK(hipMemcpyAsync(dst->hm2[(size_t)s], src->hm2[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-    } else {
-      const double n = (double)(na + nb);
-      hipLaunchKernelGGL(mcs_k_ens_merge, dim3(grid_for(len)), dim3(ENS_THREADS), 0, v.stream, dst->hmean[(size_t)s].get(), dst->hm2[(size_t)s].get(),
-                         src->hmean[(size_t)s].get(), src->hm2[(size_t)s].get(), len, (double)nb / n, (double)na * (double)nb / n);
-      ENSCHK(hipGetLastError());
-    }
-    dst->hn[(size_t)s] = na + nb;
-    dst->photons_sampled = true;
-  }
-  if (src->an > 0) {      // the source slot, like a photons slot; what is pending on either side stays where it is
-    const long long na = dst->an, nb = src->an;
-    if (!dst->has_photon_layout()) photon_layout_take(dst, src->ph_shells, src->ph_n, src->ph_start, src->ph_npts);
-    const long long len = dst->HL.total;
-    if (photons_reserve(dst, "mcs_ens_merge", -1, v.stream)) return 1;
-    if (na == 0) {
-      ENSCHK(hipMemcpyAsync(dst->amean, src->amean, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-      ENSCHK(hipMemcpyAsync(dst->am2, src->am2, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-    } else {
-      const double n = (double)(na + nb);
-      hipLaunchKernelGGL(mcs_k_ens_merge, dim3(grid_for(len)), dim3(ENS_THREADS), 0, v.stream, dst->amean.get(), dst->am2.get(), src->amean.get(),
-                         src->am2.get(), len, (double)nb / n, (double)na * (double)nb / n);
-      ENSCHK(hipGetLastError());
-    }
-    dst->an = na + nb;
-    dst->photons_sampled = true;
-  }
-  for (int s = 0; s < dst->n_slots; ++s) {
-    const long long na = dst->n[(size_t)s], nb = src->n[(size_t)s], len = dst->len(s);
-    if (nb == 0) continue;
-    if (na == 0) {
-      ENSCHK(hipMemcpyAsync(dst->mean[(size_t)s], src->mean[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-      ENSCHK(hipMemcpyAsync(dst->m2[(size_t)s], src->m2[(size_t)s], (size_t)len * sizeof(double), hipMemcpyDeviceToDevice, v.stream));
-    } else {
-      const double n = (double)(na + nb);
-      hipLaunchKernelGGL(mcs_k_ens_merge, dim3(grid_for(len)), dim3(ENS_THREADS), 0, v.stream, dst->mean[(size_t)s].get(), dst->m2[(size_t)s].get(),
-                         src->mean[(size_t)s].get(), src->m2[(size_t)s].get(), len, (double)nb / n, (double)na * (double)nb / n);
-      ENSCHK(hipGetLastError());
-    }
-    dst->n[(size_t)s] = na + nb;
-  }
+  dst->products_sampled = dst->products_sampled || any_products;
+  dst->photons_sampled = dst->photons_sampled || any_photons;
   if (leave(dst, v.stream)) return 1;
   return leave(src, v.stream);
 }
@@ -1278,7 +1222,7 @@ int mcs_ens_count(mcs_ens* e, int slot, int64_t* n) {
   if (!e || !n) return fail("mcs_ens_count: null argument");
   SlotRef r;
   if (slot_ref(e, "mcs_ens_count", slot, &r)) return 1;
-  *n = r.n;
+  *n = r.slot->n;
   return 0;
 }
 
@@ -1287,16 +1231,14 @@ int mcs_ens_read(mcs_ens* e, int slot, int what, int64_t first, int64_t count, d
   SlotRef r;
   if (slot_ref(e, "mcs_ens_read", slot, &r)) return 1;
   if (what < 0 || what > 2) return fail("mcs_ens_read: what must be 0 (mean), 1 (M2) or 2 (standard error)");
-  if (first < 0 || count < 0 || first + count > e->len(slot)) return fail("mcs_ens_read: range outside the slot's sample vector");
-  const long long n = r.n;
-  if (is_products(slot) && n == 0) return fail("mcs_ens_read: the products slot has never taken a sample");
-  if (is_photons(slot) && n == 0) return fail("mcs_ens_read: the photons slot has never taken a sample");
-  if (is_photons_all(slot) && n == 0) return fail("mcs_ens_read: the source slot has never taken a sample");
+  if (first < 0 || count < 0 || first + count > r.len) return fail("mcs_ens_read: range outside the slot's sample vector");
+  const long long n = r.slot->n;
+  if (r.kind >= PRODUCTS && n == 0) return fail(std::string("mcs_ens_read: the ") + KIND_NAME[r.kind] + " slot has never taken a sample");
   if (what == 2 && n < 2) return fail("mcs_ens_read: the standard error needs at least two samples; the slot has " + std::to_string(n));
   McsCtxView v;
   if (mcs_ctx_view_get(e->home, &v)) return 1;
   if (enter(e, v.stream)) return 1;
-  const double* from = what == 0 ? r.mean : r.m2;
+  const double* from = what == 0 ? r.slot->mean.get() : r.slot->m2.get();
   if (count > 0) ENSCHK(hipMemcpyAsync(host, from + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, v.stream));
   ENSCHK(hipStreamSynchronize(v.stream));
   if (what == 2) {
@@ -1314,12 +1256,12 @@ int mcs_ens_summarize(mcs_ens* e, int slot, int n_ranges, const mcs_ens_range* r
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges == 0) return 0;
   if (!ranges || !out) return fail(who + ": null argument");
-  const long long n = sr.n;
+  const long long n = sr.slot->n;
   if (n < 2) return fail(who + ": the standard error needs at least two samples; the slot has " + std::to_string(n));
   long long n_blocks = 0;
-  if (check_ranges(who, e->len(slot), n_ranges, ranges, &n_blocks)) return 1;
+  if (plan_ranges(who, e, sr.len, n_ranges, ranges, &mcs_ens_range::tol, "tol", &n_blocks)) return 1;
   mcs_ens* list[1] = {e};
-  return sum_run(who, list, 1, SrcOne{sr.mean, sr.m2}, n, n_ranges, ranges, n_blocks, out);
+  return sum_run(who, list, 1, SrcOne{sr.slot->mean, sr.slot->m2}, n, n_ranges, n_blocks, out);
 }
 
 int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ranges, const mcs_ens_range* ranges, mcs_ens_summary* out,
@@ -1332,26 +1274,24 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
     for (int j = 0; j < k; ++j)
       if (ens[j] == ens[k]) return fail(who + ": accumulators " + std::to_string(j) + " and " + std::to_string(k) + " of the list are the same one");
   }
-  const mcs_ens* a = ens[0];
+  mcs_ens* a = ens[0];
   for (int k = 1; k < n_ens; ++k) {
     const mcs_ens* b = ens[k];
     if (a->device != b->device) return fail(who + ": the accumulators are on different devices");
-    if (a->n_slots != b->n_slots || a->E.sp_total != b->E.sp_total || a->E.it_total != b->E.it_total || a->L.total != b->L.total ||
-        a->P.n_grid != b->P.n_grid || a->P.n_ions != b->P.n_ions || a->P.n_itrs != b->P.n_itrs)
-      return fail(who + ": the accumulators' slots or layouts differ");
+    if (a->n_slots != b->n_slots || !same_layout(a, b)) return fail(who + ": the accumulators' slots or layouts differ");
   }
   SlotRef sr;
   if (slot_ref(a, who, slot, &sr)) return 1;
-  if (is_products(slot))
+  if (sr.kind == PRODUCTS)
     for (int k = 1; k < n_ens; ++k)
       for (int j = 0; j < k; ++j)
         if (windows_differ(ens[j], ens[k])) return fail(who + ": the accumulators' slope windows differ");
-  long long len = a->len(slot);
-  if (has_photon_vector(slot))
+  long long len = sr.len;
+  if (has_photon_vector(sr.kind))
     for (int k = 1; k < n_ens; ++k) {
       for (int j = 0; j < k; ++j)
         if (photon_layouts_differ(ens[j], ens[k])) return fail(who + ": the accumulators' photon layouts differ");
-      if (ens[k]->len(slot) > len) len = ens[k]->len(slot);      // (an accumulator without a layout has no photons sample)
+      if (ens[k]->len(sr.kind) > len) len = ens[k]->len(sr.kind);      // (an accumulator without a layout has no photons sample)
     }
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges > 0 && (!ranges || !out)) return fail(who + ": null argument");
@@ -1364,28 +1304,28 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
   for (int k = 0; k < n_ens; ++k) {
     list[k] = ens[k];
     (void)slot_ref(ens[k], who, slot, &sr);      // (the slot exists in every accumulator: their slots are the same)
-    const long long nb = sr.n;
+    const long long nb = sr.slot->n;
     if (nb == 0) continue;
     const double nn = (double)(n + nb);
     f_mean[m] = m ? (double)nb / nn : 0.0;
     f_m2[m] = m ? (double)n * (double)nb / nn : 0.0;
-    mean[m] = sr.mean; m2[m] = sr.m2;
+    mean[m] = sr.slot->mean; m2[m] = sr.slot->m2;
     n += nb; ++m;
   }
   if (n < 2) return fail(who + ": the standard error needs at least two samples; the slot has " + std::to_string(n) + " over the list");
   long long n_blocks = 0;
-  if (check_ranges(who, len, n_ranges, ranges, &n_blocks)) return 1;
+  if (plan_ranges(who, a, len, n_ranges, ranges, &mcs_ens_range::tol, "tol", &n_blocks)) return 1;
   *n_total = n;
   if (n_ranges == 0) return 0;
   switch (m) {
-    case 1: return sum_run(who, list, n_ens, SrcOne{mean[0], m2[0]}, n, n_ranges, ranges, n_blocks, out);
-    case 2: return sum_run(who, list, n_ens, merged_src<2>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
-    case 3: return sum_run(who, list, n_ens, merged_src<3>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
-    case 4: return sum_run(who, list, n_ens, merged_src<4>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
-    case 5: return sum_run(who, list, n_ens, merged_src<5>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
-    case 6: return sum_run(who, list, n_ens, merged_src<6>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
-    case 7: return sum_run(who, list, n_ens, merged_src<7>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
-    default: return sum_run(who, list, n_ens, merged_src<8>(mean, m2, f_mean, f_m2), n, n_ranges, ranges, n_blocks, out);
+    case 1: return sum_run(who, list, n_ens, SrcOne{mean[0], m2[0]}, n, n_ranges, n_blocks, out);
+    case 2: return sum_run(who, list, n_ens, merged_src<2>(mean, m2, f_mean, f_m2), n, n_ranges, n_blocks, out);
+    case 3: return sum_run(who, list, n_ens, merged_src<3>(mean, m2, f_mean, f_m2), n, n_ranges, n_blocks, out);
+    case 4: return sum_run(who, list, n_ens, merged_src<4>(mean, m2, f_mean, f_m2), n, n_ranges, n_blocks, out);
+    case 5: return sum_run(who, list, n_ens, merged_src<5>(mean, m2, f_mean, f_m2), n, n_ranges, n_blocks, out);
+    case 6: return sum_run(who, list, n_ens, merged_src<6>(mean, m2, f_mean, f_m2), n, n_ranges, n_blocks, out);
+    case 7: return sum_run(who, list, n_ens, merged_src<7>(mean, m2, f_mean, f_m2), n, n_ranges, n_blocks, out);
+    default: return sum_run(who, list, n_ens, merged_src<8>(mean, m2, f_mean, f_m2), n, n_ranges, n_blocks, out);
   }
 }
 
@@ -1396,54 +1336,31 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   if (slot_ref(a, who + " (A)", slot_a, &ra) || slot_ref(b, who + " (B)", slot_b, &rb)) return 1;
   if (a == b && slot_a == slot_b) return fail(who + ": A and B are the same slot of the same accumulator");
   if (a->device != b->device) return fail(who + ": the accumulators are on different devices");
-  if (a->E.sp_total != b->E.sp_total || a->E.it_total != b->E.it_total || a->L.total != b->L.total || a->P.n_grid != b->P.n_grid ||
-      a->P.n_ions != b->P.n_ions || a->P.n_itrs != b->P.n_itrs || a->P.num_psd_mom_bins != b->P.num_psd_mom_bins ||
-      a->P.num_psd_tht_bins != b->P.num_psd_tht_bins)
-    return fail(who + ": the accumulators' layouts differ");
-  // species slot, iteration slot, products slot, photons slot or source slot
-  const auto kind = [](const mcs_ens* e, int slot) {
-    return is_photons_all(slot) ? 4 : is_photons(slot) ? 3 : is_products(slot) ? 2 : slot == e->n_slots - 1 ? 1 : 0;
-  };
-  const long long len = a->len(slot_a);
-  if (kind(a, slot_a) != kind(b, slot_b) || len != b->len(slot_b)) return fail(who + ": the two slots differ in kind or length");
+  if (!same_layout(a, b)) return fail(who + ": the accumulators' layouts differ");
+  const Slot &sa = *ra.slot, &sb = *rb.slot;
+  const long long len = ra.len;
+  if (ra.kind != rb.kind || len != rb.len) return fail(who + ": the two slots differ in kind or length");
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges == 0) return 0;
   if (!ranges || !out) return fail(who + ": null argument");
-  if (is_products(slot_a)) {
-    if (ra.n == 0 || rb.n == 0) return fail(who + ": a products slot has never taken a sample");
+  if (ra.kind == PRODUCTS) {
+    if (sa.n == 0 || sb.n == 0) return fail(who + ": a products slot has never taken a sample");
     if (windows_differ(a, b)) return fail(who + ": the accumulators' slope windows differ");
   }
-  if (has_photon_vector(slot_a)) {
-    if (ra.n == 0 || rb.n == 0) return fail(who + ": a photons slot has never taken a sample");
+  if (has_photon_vector(ra.kind)) {
+    if (sa.n == 0 || sb.n == 0) return fail(who + ": a photons slot has never taken a sample");
     if (photon_layouts_differ(a, b)) return fail(who + ": the accumulators' photon layouts differ");
   }
-  if (ra.n < 2 || rb.n < 2)
-    return fail(who + ": a standard error needs at least two samples; A has " + std::to_string(ra.n) + ", B has " + std::to_string(rb.n));
+  if (sa.n < 2 || sb.n < 2)
+    return fail(who + ": a standard error needs at least two samples; A has " + std::to_string(sa.n) + ", B has " + std::to_string(sb.n));
   long long n_blocks = 0;
-  for (int r = 0; r < n_ranges; ++r)
-    if (check_range(who + ": range " + std::to_string(r), len, ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].zcut, "zcut", &n_blocks))
-      return 1;
+  if (plan_ranges(who, a, len, n_ranges, ranges, &mcs_ens_cmp_range::zcut, "zcut", &n_blocks)) return 1;
   McsCtxView v;
   if (mcs_ctx_view_get(a->home, &v)) return 1;
-  hipError_t h = a->sum_par_h.reserve(1);
-  if (h == hipSuccess) h = a->sum_par.reserve(1);
-  if (h == hipSuccess) h = a->cmp_out_h.reserve(SUM_MAX_RANGES);
-  if (h == hipSuccess) h = a->cmp_out.reserve(SUM_MAX_RANGES);
-  if (h == hipSuccess) h = a->sum_pmax.reserve(n_blocks);
-  if (h == hipSuccess) h = a->cmp_part.reserve(n_blocks);
-  if (h != hipSuccess) return fail(who + ": scratch allocation: " + hipGetErrorString(h));
-  // (every earlier call has waited for its copies: the pinned blocks are free)
-  SumParams* P = a->sum_par_h.get();
-  P->n_ranges = n_ranges;
-  P->off[0] = 0;
-  for (int r = 0; r < n_ranges; ++r) {
-    P->r[r] = SumRange{ranges[r].first, ranges[r].count, ranges[r].floor_frac, ranges[r].zcut};
-    const long long nb = (ranges[r].count + SUM_CHUNK - 1) / SUM_CHUNK;
-    P->off[r + 1] = P->off[r] + (int)(nb > SUM_MAX_BLOCKS ? SUM_MAX_BLOCKS : nb);
-  }
+  if (reserve_scratch(who, a, a->cmp_out_h, a->cmp_out, a->cmp_part, n_blocks)) return 1;
   if (enter(a, v.stream) || (b != a && enter(b, v.stream))) return 1;
-  const SrcCmp src{ra.mean, ra.m2, rb.mean, rb.m2, (double)ra.n * (double)(ra.n - 1), (double)rb.n * (double)(rb.n - 1)};
-  ENSCHK(hipMemcpyAsync(a->sum_par.get(), P, sizeof(SumParams), hipMemcpyHostToDevice, v.stream));
+  const SrcCmp src{sa.mean, sa.m2, sb.mean, sb.m2, (double)sa.n * (double)(sa.n - 1), (double)sb.n * (double)(sb.n - 1)};
+  ENSCHK(hipMemcpyAsync(a->sum_par.get(), a->sum_par_h.get(), sizeof(SumParams), hipMemcpyHostToDevice, v.stream));
   if (n_blocks > 0) {
     hipLaunchKernelGGL(mcs_k_ens_cmp_amax, dim3((unsigned)n_blocks), dim3(ENS_THREADS), 0, v.stream, src, a->sum_par.get(), a->sum_pmax.get());
     ENSCHK(hipGetLastError());
@@ -1465,12 +1382,11 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
 
 int mcs_ens_load_mean(mcs_ens* e, int slot, mcs_ctx* dst) {
   if (!e || !dst) return fail("mcs_ens_load_mean: null argument");
-  if (slot < 0 || slot >= e->n_slots) return fail("mcs_ens_load_mean: slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
-  if (slot == e->n_slots - 1) return fail("mcs_ens_load_mean: slot " + std::to_string(slot) + " is the iteration slot; only a species slot has histograms");
+  if (species_slot(e, "mcs_ens_load_mean", slot, "only a species slot has histograms")) return 1;
   McsCtxView v;
   if (view_of(e, dst, "mcs_ens_load_mean", &v)) return 1;
   if (enter(e, v.stream)) return 1;
-  hipLaunchKernelGGL(mcs_k_ens_load_mean, dim3(grid_for(e->E.sp_psd_mom)), dim3(ENS_THREADS), 0, v.stream, e->mean[(size_t)slot].get(), v.T, v.I, e->E);
+  hipLaunchKernelGGL(mcs_k_ens_load_mean, dim3(grid_for(e->E.sp_psd_mom)), dim3(ENS_THREADS), 0, v.stream, e->main[(size_t)slot].mean.get(), v.T, v.I, e->E);
   ENSCHK(hipGetLastError());
   mcs_ctx_view_tallies_written(dst);
   return leave(e, v.stream);

@@ -219,6 +219,27 @@ def welford_update(mean: np.ndarray, m2: np.ndarray, n: int, x: np.ndarray) -> i
     return n
 
 
+def _chan(m, q, na: int, mb, qb, nb: int):
+    """Chan's merge of (mean m, M2 q, na samples) with (mb, qb, nb) -> the merged (mean, M2), new arrays: the one place where the
+    formula stands.  A merge that is not finite is counted by a summary, not an error."""
+    n = float(na + nb)
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = mb - m
+        return m + d * (float(nb) / n), (q + qb) + (d * d) * (float(na) * float(nb) / n)
+
+
+class _Slot:
+    """The mean, the M2 and the sample count of one slot."""
+
+    def __init__(self, size: int):
+        self.mean, self.m2, self.n = np.zeros(size), np.zeros(size), 0
+
+    def copy(self) -> "_Slot":
+        c = _Slot(0)
+        c.mean, c.m2, c.n = self.mean.copy(), self.m2.copy(), self.n
+        return c
+
+
 def stats_over(samples):
     """(mean, standard error of the mean, count) of a list of equally shaped arrays, by the update above, in list order."""
     mean, m2, n = np.zeros_like(samples[0], dtype=np.float64), np.zeros_like(samples[0], dtype=np.float64), 0
@@ -635,50 +656,56 @@ class Ensemble:
         self._set_photon_layout(layout)
         self.photon_layout = layout
 
+    def _decode(self, slot: int) -> Tuple[str, Optional[int]]:
+        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons" or "source" -- the one place where
+        its bits are read; the index is None for the iteration and the source slot, and not yet checked (`_check_slot`)."""
+        if self.is_photons_all(slot):
+            return "source", None
+        if self.is_products(slot):
+            return "products", slot ^ PRODUCTS_BIT
+        if self.is_photons(slot):
+            return "photons", slot ^ PHOTONS_BIT
+        return ("iteration", None) if slot == self.iteration_slot else ("species", slot)
+
+    def _kind(self, slot: int) -> str:
+        return self._decode(slot)[0]
+
+    def _describe(self, slot: int) -> str:
+        kind, s = self._decode(slot)
+        if kind in ("products", "photons"):
+            return f"the {kind} slot of species slot {s}"
+        return f"species slot {s}" if kind == "species" else f"the {kind} slot"
+
     def names(self, slot: int):
         self._check_slot(slot)
-        if self._has_photon_vector(slot):
-            return PHOTON_NAMES
-        if self.is_products(slot):
-            return PRODUCT_NAMES
-        return ITERATION_NAMES if slot == self.iteration_slot else SPECIES_NAMES
+        return {"species": SPECIES_NAMES, "iteration": ITERATION_NAMES, "products": PRODUCT_NAMES}.get(self._kind(slot), PHOTON_NAMES)
 
     def _check_slot(self, slot: int):
-        if self.is_photons_all(slot):
-            return
-        if self.is_photons(slot):
-            if not 0 <= slot ^ PHOTONS_BIT < self.n_species:
-                raise ValueError(f"ensemble: photons slot of slot {slot ^ PHOTONS_BIT}, which is no species slot (0..{self.n_species - 1})")
-        elif self.is_products(slot):
-            if not 0 <= slot ^ PRODUCTS_BIT < self.n_species:
-                raise ValueError(f"ensemble: products slot of slot {slot ^ PRODUCTS_BIT}, which is no species slot (0..{self.n_species - 1})")
-        elif not 0 <= slot <= self.n_species:
+        kind, s = self._decode(slot)
+        if kind in ("products", "photons") and not 0 <= s < self.n_species:
+            raise ValueError(f"ensemble: {kind} slot of slot {s}, which is no species slot (0..{self.n_species - 1})")
+        if kind == "species" and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: slot {slot} outside 0..{self.n_species}")
 
     def _len(self, slot: int) -> int:
-        if self._has_photon_vector(slot):
+        kind = self._kind(slot)
+        if kind in ("photons", "source"):
             return 0 if self.photon_layout is None else self.photon_layout.offsets()["_total"]
-        if self.is_products(slot):
-            return self.layout.products_total
-        return self.layout.iteration_total if slot == self.iteration_slot else self.layout.species_total
+        return {"species": self.layout.species_total, "iteration": self.layout.iteration_total, "products": self.layout.products_total}[kind]
 
     def _where(self, slot: int, name: str):
         self._check_slot(slot)
-        if self._has_photon_vector(slot):
-            kind = "the source slot" if self.is_photons_all(slot) else f"the photons slot of species slot {slot ^ PHOTONS_BIT}"
+        kind = self._kind(slot)
+        if kind in ("photons", "source"):
             if self.photon_layout is None:
-                raise ValueError(f"ensemble: {kind} has no layout yet (set_photon_layout)")
+                raise ValueError(f"ensemble: {self._describe(slot)} has no layout yet (set_photon_layout)")
             rows = self.photon_layout.rows
             offs = self.photon_layout.offsets()
             table = {part: (offs[part][0], (rows, offs[part][1])) for part in PHOTON_NAMES}
-        elif self.is_products(slot):
-            table, kind = self.layout.products, f"the products slot of species slot {slot ^ PRODUCTS_BIT}"
-        elif slot == self.iteration_slot:
-            table, kind = self.layout.iteration, "the iteration slot"
         else:
-            table, kind = self.layout.species, f"species slot {slot}"
+            table = {"species": self.layout.species, "iteration": self.layout.iteration, "products": self.layout.products}[kind]
         if name not in self.names(slot):
-            raise KeyError(f"ensemble: {kind} has no {name!r}; it has: {', '.join(self.names(slot))}")
+            raise KeyError(f"ensemble: {self._describe(slot)} has no {name!r}; it has: {', '.join(self.names(slot))}")
         return table[name]
 
     def _named(self, slot: int, what: int, name: str) -> np.ndarray:
@@ -755,9 +782,6 @@ class Ensemble:
             if type(o) is not type(self) or o.n_species != self.n_species or o.layout.fields != self.layout.fields:
                 raise ValueError("ensemble: a merged summary needs ensembles of the same kind, slots and layout")
 
-    def _kind(self, slot: int) -> str:
-        return "source" if self.is_photons_all(slot) else "photons" if self.is_photons(slot) else "products" if self.is_products(slot) else "iteration" if slot == self.iteration_slot else "species"
-
     def compare(self, other: "Ensemble", slot: int, requests: Sequence[CompareRequest], other_slot: Optional[int] = None) -> List[Difference]:
         """One Difference per request (at most MAX_RANGES; they may overlap): slot `slot` of this ensemble, A, against slot
         `other_slot` (default: the same number) of `other`, B -- two slots of one kind of ensembles of one kind and layout, each with
@@ -812,27 +836,31 @@ class HostEnsemble(Ensemble):
 
     def __init__(self, P: capi.McsParams, n_species: int):
         super().__init__(P, n_species)
-        lens = [self.layout.species_total] * self.n_species + [self.layout.iteration_total]
-        self._mean = [np.zeros(n) for n in lens]
-        self._m2 = [np.zeros(n) for n in lens]
-        self._n = [0] * len(lens)
+        # slot number -> _Slot: the species and the iteration slots from the start; a products, photons or source slot from its first
+        # sample or merge on (absent: never sampled)
+        self._slots: Dict[int, _Slot] = {s: _Slot(self._len(s)) for s in range(self.n_species + 1)}
         self._snapshot = None          # (backend, words [esc_flux, energy_recv_pool))
-        # the products slots: species slot -> vector, from the first sample on
-        self._pmean: Dict[int, np.ndarray] = {}
-        self._pm2: Dict[int, np.ndarray] = {}
-        self._pn = [0] * self.n_species
-        # the photons slots, likewise
-        self._hmean: Dict[int, np.ndarray] = {}
-        self._hm2: Dict[int, np.ndarray] = {}
-        self._hn = [0] * self.n_species
-        # the source slot, from its first sample or merge on, and the pending vector, from the first deposit on
-        self._amean: Optional[np.ndarray] = None
-        self._am2: Optional[np.ndarray] = None
-        self._an = 0
-        self._pending: Optional[np.ndarray] = None
+        self._pending: Optional[np.ndarray] = None      # the pending vector of the source slot, from the first deposit on
+
+    def _sampled(self, *kinds) -> bool:
+        """Some slot of one of these kinds has taken a sample (or a merge)."""
+        return any(s.n > 0 and self._kind(k) in kinds for k, s in self._slots.items())
+
+    def _sample(self, slot: int, x: np.ndarray):
+        """One sample more of a slot, which is allocated at its first."""
+        s = self._slots.get(slot)
+        if s is None:
+            s = self._slots[slot] = _Slot(x.size)
+        s.n = welford_update(s.mean, s.m2, s.n, x)
+
+    def _species_slot(self, slot: int, has: str):
+        """The refusal of a slot that is no species slot where only one will do; has: what only a species slot has."""
+        self._check_slot(slot)
+        if self._kind(slot) != "species":
+            raise ValueError(f"ensemble: slot {slot} is no species slot; only a species slot has {has}")
 
     def _set_photon_layout(self, layout):
-        if any(self._hn) or self._an:
+        if self._sampled("photons", "source"):
             raise ValueError("ensemble: a photons slot has taken a sample; the photon layout stays as it is")
 
     def add_photons(self, backend, slot: int, observed=None, deposit: bool = False):
@@ -842,9 +870,7 @@ class HostEnsemble(Ensemble):
         as it stands (a later one) plus the sample's word where that is above 1e-99.  Refused, with nothing changed, for a species slot
         already deposited since the last take."""
         from .consumers import PHOTON_PROCESSES, photon_total
-        self._check_slot(slot)
-        if self._has_photon_vector(slot) or self.is_products(slot) or slot == self.iteration_slot:
-            raise ValueError(f"ensemble: slot {slot} is no species slot; only a species slot has a photons slot")
+        self._species_slot(slot, "a photons slot")
         if observed is None:
             raise ValueError("ensemble: the numpy ensemble takes its photons sample from an ObservedSpectra")
         if deposit and slot in self._deposited:
@@ -860,9 +886,7 @@ class HostEnsemble(Ensemble):
                 raise ValueError(f"ensemble: {p!r} was observed as {a.shape}; the layout has {(lay.rows, lay.n[p])}")
         parts = [(per[p] if p in per else np.full((lay.rows, lay.n[p]), 1.0e-99)).ravel() for p in PHOTON_PROCESSES]
         x = np.concatenate(parts + [photon_total(per, lay).ravel()])
-        if slot not in self._hmean:
-            self._hmean[slot], self._hm2[slot] = np.zeros(x.size), np.zeros(x.size)
-        self._hn[slot] = welford_update(self._hmean[slot], self._hm2[slot], self._hn[slot], x)
+        self._sample(self.photons_slot(slot), x)
         if deposit:
             lit = np.where(x > 1.0e-99, x, 0.0)
             self._pending = (self._pending if self._deposited else 1.0e-99) + lit
@@ -873,9 +897,7 @@ class HostEnsemble(Ensemble):
         no deposit pending."""
         if not self._deposited:
             raise ValueError("ensemble: no deposit pending (add_photons(deposit=True))")
-        if self._amean is None:
-            self._amean, self._am2 = np.zeros(self._pending.size), np.zeros(self._pending.size)
-        self._an = welford_update(self._amean, self._am2, self._an, self._pending)
+        self._sample(PHOTONS_ALL, self._pending)
         self._deposited.clear()
 
     def drop_pending_photons(self):
@@ -888,26 +910,17 @@ class HostEnsemble(Ensemble):
 
     def _vectors(self, slot: int):
         """(mean, M2, n) of a slot; (None, None, 0) for a products, photons or source slot that was never sampled."""
-        if self.is_photons_all(slot):
-            return self._amean, self._am2, self._an
-        if self.is_photons(slot):
-            s = slot ^ PHOTONS_BIT
-            return self._hmean.get(s), self._hm2.get(s), self._hn[s]
-        if self.is_products(slot):
-            s = slot ^ PRODUCTS_BIT
-            return self._pmean.get(s), self._pm2.get(s), self._pn[s]
-        return self._mean[slot], self._m2[slot], self._n[slot]
+        s = self._slots.get(slot)
+        return (None, None, 0) if s is None else (s.mean, s.m2, s.n)
 
     def _set_slope_window(self, l_lo, l_hi, x_log):
-        if any(self._pn):
+        if self._sampled("products"):
             raise ValueError("ensemble: a products slot has taken a sample; the slope window stays as it is")
 
     def add_products(self, backend, slot: int, ion_final):
         """One products sample of species slot `slot` from an `IonFinal` (consumers.ion_finalize on `backend`), the slopes by the
         backend's deterministic log10."""
-        self._check_slot(slot)
-        if self.is_products(slot) or slot == self.iteration_slot:
-            raise ValueError(f"ensemble: slot {slot} is no species slot; only a species slot has a products slot")
+        self._species_slot(slot, "a products slot")
         if self.window is None:
             raise ValueError("ensemble: no slope window (set_slope_window)")
         l_lo, l_hi, x_log = self.window
@@ -916,10 +929,8 @@ class HostEnsemble(Ensemble):
                             np.asarray(ion_final.energy_density_psd, dtype=np.float64), slopes_of(dndp, l_lo, l_hi, x_log, _det_log10(backend)).ravel()])
         if x.size != self.layout.products_total:
             raise ValueError(f"ensemble: the IonFinal holds {x.size} words; a products sample has {self.layout.products_total}")
-        if slot not in self._pmean:
-            self._pmean[slot], self._pm2[slot] = np.zeros(x.size), np.zeros(x.size)
         with np.errstate(invalid="ignore"):          # (a NaN slope stays NaN)
-            self._pn[slot] = welford_update(self._pmean[slot], self._pm2[slot], self._pn[slot], x)
+            self._sample(self.products_slot(slot), x)
 
     @staticmethod
     def _windows_differ(a, b) -> bool:
@@ -933,18 +944,17 @@ class HostEnsemble(Ensemble):
         self._snapshot = (backend, f[o["esc_flux"]:o["energy_recv_pool"]].copy())
 
     def add_species(self, backend, slot: int):
-        self._check_slot(slot)
         if slot == self.iteration_slot:
             raise ValueError(f"ensemble: slot {slot} is the iteration slot; it takes no species sample")
+        self._species_slot(slot, "a species sample")
         f, i = backend.read_tallies()
-        self._n[slot] = welford_update(self._mean[slot], self._m2[slot], self._n[slot], self.layout.species_sample(f, i))
+        self._sample(slot, self.layout.species_sample(f, i))
 
     def add_iteration(self, backend):
         if self._snapshot is None or self._snapshot[0] is not backend:
             raise ValueError("ensemble: add_iteration without a begin_iteration of this backend since the last iteration sample")
         f, _ = backend.read_tallies()
-        s = self.iteration_slot
-        self._n[s] = welford_update(self._mean[s], self._m2[s], self._n[s], self.layout.iteration_sample(f, self._snapshot[1]))
+        self._sample(self.iteration_slot, self.layout.iteration_sample(f, self._snapshot[1]))
         self._snapshot = None
 
     def merge(self, other: "HostEnsemble"):
@@ -956,58 +966,20 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: merge of ensembles whose slope windows differ")
         if self._photon_layouts_differ(self, other):
             raise ValueError("ensemble: merge of ensembles whose photon layouts differ")
-        if (any(other._hn) or other._an) and self.photon_layout is None:
+        # an ensemble without a photon layout or a slope window takes the one its samples were made with
+        if other._sampled("photons", "source") and self.photon_layout is None:
             self.photon_layout = other.photon_layout
-        if other._an:         # the source slot, like a photons slot; what is pending on either side stays where it is
-            na, nb = self._an, other._an
-            if na == 0:
-                self._amean, self._am2 = other._amean.copy(), other._am2.copy()
-            else:
-                n = float(na + nb)
-                d = other._amean - self._amean
-                self._amean = self._amean + d * (float(nb) / n)
-                self._am2 = (self._am2 + other._am2) + (d * d) * (float(na) * float(nb) / n)
-            self._an = na + nb
-        for s in range(self.n_species):
-            na, nb = self._hn[s], other._hn[s]
-            if nb == 0:
-                continue
-            if na == 0:
-                self._hmean[s], self._hm2[s] = other._hmean[s].copy(), other._hm2[s].copy()
-            else:
-                n = float(na + nb)
-                d = other._hmean[s] - self._hmean[s]
-                self._hmean[s] = self._hmean[s] + d * (float(nb) / n)
-                self._hm2[s] = (self._hm2[s] + other._hm2[s]) + (d * d) * (float(na) * float(nb) / n)
-            self._hn[s] = na + nb
-        for s in range(self.n_species + 1):
-            na, nb = self._n[s], other._n[s]
-            if nb == 0:
-                continue
-            if na == 0:
-                self._mean[s][...] = other._mean[s]
-                self._m2[s][...] = other._m2[s]
-            else:
-                n = float(na + nb)
-                d = other._mean[s] - self._mean[s]
-                self._mean[s][...] = self._mean[s] + d * (float(nb) / n)
-                self._m2[s][...] = (self._m2[s] + other._m2[s]) + (d * d) * (float(na) * float(nb) / n)
-            self._n[s] = na + nb
-        if any(other._pn) and self.window is None:      # an ensemble without a window takes the one its samples were made with
+        if other._sampled("products") and self.window is None:
             self.window = other.window
-        for s in range(self.n_species):
-            na, nb = self._pn[s], other._pn[s]
-            if nb == 0:
+        for k, b in other._slots.items():      # (what is pending for the source slot on either side stays where it is)
+            if b.n == 0:
                 continue
-            if na == 0:
-                self._pmean[s], self._pm2[s] = other._pmean[s].copy(), other._pm2[s].copy()
+            a = self._slots.get(k)
+            if a is None or a.n == 0:
+                self._slots[k] = b.copy()
             else:
-                n = float(na + nb)
-                with np.errstate(invalid="ignore"):
-                    d = other._pmean[s] - self._pmean[s]
-                    self._pmean[s] = self._pmean[s] + d * (float(nb) / n)
-                    self._pm2[s] = (self._pm2[s] + other._pm2[s]) + (d * d) * (float(na) * float(nb) / n)
-            self._pn[s] = na + nb
+                a.mean, a.m2 = _chan(a.mean, a.m2, a.n, b.mean, b.m2, b.n)
+                a.n += b.n
 
     def count(self, slot: int) -> int:
         self._check_slot(slot)
@@ -1015,12 +987,8 @@ class HostEnsemble(Ensemble):
 
     def _read(self, slot, what, first, count):
         mean, m2, n = self._vectors(slot)
-        if mean is None and self.is_photons_all(slot):
-            raise ValueError("ensemble: the source slot has never taken a sample")
-        if mean is None and self.is_photons(slot):
-            raise ValueError(f"ensemble: the photons slot of species slot {slot ^ PHOTONS_BIT} has never taken a sample")
         if mean is None:
-            raise ValueError(f"ensemble: the products slot of species slot {slot ^ PRODUCTS_BIT} has never taken a sample")
+            raise ValueError(f"ensemble: {self._describe(slot)} has never taken a sample")
         if what == 2:
             if n < 2:
                 raise ValueError(f"ensemble: the standard error needs at least two samples; slot {slot} has {n}")
@@ -1046,14 +1014,7 @@ class HostEnsemble(Ensemble):
                 if nb == 0:
                     continue
                 mb, qb = mean_e[first:first + count], m2_e[first:first + count]
-                if na == 0:
-                    m, q = mb, qb
-                else:
-                    nn = float(na + nb)
-                    with np.errstate(over="ignore", invalid="ignore"):      # (a merge that is not finite is counted, not an error)
-                        d = mb - m
-                        m = m + d * (float(nb) / nn)
-                        q = (q + qb) + (d * d) * (float(na) * float(nb) / nn)
+                m, q = (mb, qb) if na == 0 else _chan(m, q, na, mb, qb, nb)
                 na += nb
             out.append(summary_of(m, q, n, floor_frac, tol))
         return out
@@ -1069,14 +1030,14 @@ class HostEnsemble(Ensemble):
 
     def load_mean(self, slot: int, backend):
         """The mean of a species slot written into the backend's per-species sections (num_crossings rounded to nearest)."""
-        self._check_slot(slot)
         if slot == self.iteration_slot:
             raise ValueError(f"ensemble: slot {slot} is the iteration slot; only a species slot has histograms")
         if self.is_photons_all(slot):
             raise ValueError("ensemble: the source slot is no species slot; only a species slot has histograms")
+        self._species_slot(slot, "histograms")
         L, o = self.layout.tally, self.layout.tally.offsets
         f, i = backend.read_tallies()
-        m = self._mean[slot]
+        m = self._slots[slot].mean
         n1 = o["esc_flux"] - o["psd"]
         f[o["psd"]:o["esc_flux"]] = m[:n1]
         L.view(f, "energy_recv_pool")[...] = m[n1:n1 + L.n_grid]

@@ -20,6 +20,15 @@ def bits_equal(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
+def same_words(a, b):
+    """Bit-equal, where a NaN equals a NaN (the bits of a NaN that went through an update are nobody's promise)."""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
+        return False
+    ok = ~np.isnan(a)
+    return np.array_equal(a[ok].view(np.uint64), b[ok].view(np.uint64))
+
+
 def marginals(hist):
     """hist [n_grid][ntht+2][nmom+2] -> (momentum marginal [n_grid][nmom+2], angle marginal [n_grid][ntht+2]): serial sums in
     ascending index order, starting from the first term (np.sum is pairwise and would round differently)."""
@@ -89,6 +98,36 @@ def stat_of(samples):
     for p in samples:
         s.add(p)
     return s
+
+
+def check_one_merge_of_every_kind(a, b, lens, only_b):
+    """a.merge(b), once, of two ensembles of either implementation that hold samples in slots of every kind -- the keys of lens, slot ->
+    length of its vectors; only_b: the slots that only b has sampled.  Every slot of a is then, bit for bit, Chan's formula restated
+    here on the vectors read before the merge (a copy of b's where a had none), the counts add, and b is what it was."""
+    read = lambda e, s: (e._read(s, 0, 0, lens[s]), e._read(s, 1, 0, lens[s]))
+    na = {s: a.count(s) for s in lens}
+    nb = {s: b.count(s) for s in lens}
+    assert all(lens[s] % THREADS != 0 for s in lens), "a vector length is a multiple of the block size: the grid-stride tail would not run"
+    assert all(nb[s] > 0 for s in lens) and sorted(s for s in lens if na[s] == 0) == sorted(only_b) and len({na[s] for s in lens}) == 2
+    assert all(na[s] != nb[s] for s in lens)
+    va = {s: read(a, s) for s in lens if na[s]}
+    vb = {s: read(b, s) for s in lens}
+    a.merge(b)
+    for s in lens:
+        assert a.count(s) == na[s] + nb[s] and b.count(s) == nb[s], s
+        (mb, qb), got, still = vb[s], read(a, s), read(b, s)
+        assert same_words(still[0], mb) and same_words(still[1], qb), f"slot {s}: the source of a merge is unchanged"
+        if na[s] == 0:
+            assert same_words(got[0], mb) and same_words(got[1], qb), f"slot {s}: a slot that only the source had is a copy"
+            continue
+        ma, qa = va[s]
+        n = float(na[s] + nb[s])
+        with np.errstate(invalid="ignore"):
+            d = mb - ma
+            mean, m2 = ma + d * (float(nb[s]) / n), (qa + qb) + (d * d) * (float(na[s]) * float(nb[s]) / n)
+        assert np.isfinite(m2).any() and np.nanmax(m2) > 0 and not bits_equal(mean, ma), s
+        assert same_words(got[0], mean), f"slot {s}: merged mean"
+        assert same_words(got[1], m2), f"slot {s}: merged M2"
 
 
 def crafted_buffers(L, n=5, seed=0):

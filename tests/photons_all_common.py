@@ -12,6 +12,12 @@ N_WORDS = LAYOUT.offsets()["_total"]
 # the processes of the three crafted species: every process is lit in one species, in two, or (a word on the floor in all) in none
 SPECIES_PROCESSES = (("pion",), ("synch", "ic"), ("pion", "synch"))
 FLOOR = 1.0e-99
+# a layout of two shells and a handful of energy words, for tests of the bookkeeping; its two species; what mcs_photon_observe takes
+# for it: the emission words per process (one more than the spectrum has) and the shell ends
+SMALL_LAYOUT = cons.PhotonLayout(2, {"synch": 7, "ic": 5, "pion": 3}, {"synch": 0, "ic": 2, "pion": 6}, 9)
+SMALL_PROCESSES = (("synch", "pion"), ("ic",))
+SMALL_N_PHOTON = {p: n + 1 for p, n in SMALL_LAYOUT.n.items()}
+SMALL_ENDS = [1, 9, 30]
 
 
 def crafted_species(it, seed=0, layout=LAYOUT, species_processes=SPECIES_PROCESSES):

@@ -50,8 +50,11 @@ def fresh(prob, layout=LAYOUT):
 def state_of(e):
     """Everything a refused call must leave as it was."""
     vec = lambda a: None if a is None else a.copy()
-    return dict(hmean={s: a.copy() for s, a in e._hmean.items()}, hm2={s: a.copy() for s, a in e._hm2.items()}, hn=list(e._hn),
-                amean=vec(e._amean), am2=vec(e._am2), an=e._an, pending=vec(e._pending), deposited=e.pending_photons, layout=e.photon_layout)
+    hs = {s: e._slots[e.photons_slot(s)] for s in range(e.n_species) if e.photons_slot(s) in e._slots}      # (absent: never allocated)
+    src = e._slots.get(ALL)
+    return dict(hmean={s: x.mean.copy() for s, x in hs.items()}, hm2={s: x.m2.copy() for s, x in hs.items()},
+                hn=[e.count(e.photons_slot(s)) for s in range(e.n_species)], amean=vec(src and src.mean), am2=vec(src and src.m2), an=e.count(ALL),
+                pending=vec(e._pending), deposited=e.pending_photons, layout=e.photon_layout)
 
 
 def same_state(a, b):
@@ -85,7 +88,7 @@ def test_the_source_slot_is_the_deposit_rule_then_welford():
         a, b = slot_words(e, hs), slot_words(plain, hs)
         assert e.count(hs) == plain.count(hs) == 5
         assert bits_equal(a[0], b[0]) and bits_equal(a[1], b[1]) and bits_equal(a[0], want[0]) and bits_equal(a[1], want[1]), s
-    assert plain.count(ALL) == 0 and plain._pending is None and plain._amean is None
+    assert plain.count(ALL) == 0 and plain._pending is None and ALL not in plain._slots
     # names, ranges, summaries and a trigger work on it as on a photons slot
     off = LAYOUT.offsets()
     assert e.word_range(ALL, "total", (3, 4), (5, 12)) == (off["total"][0] + 3 * 31 + 5, 7) == e.word_range(e.photons_slot(1), "total", (3, 4), (5, 12))
@@ -205,7 +208,7 @@ def test_merge_is_chans_and_a_destination_without_a_layout_takes_it():
         assert into.count(into.photons_slot(s)) == 5 + (s == 1)
     # a source slot alone carries the layout over, too
     only = fresh(prob)
-    only._amean, only._am2, only._an = a._amean.copy(), a._am2.copy(), a._an
+    only._slots[ALL] = a._slots[ALL].copy()
     into2 = fresh(prob, None)
     into2.merge(only)
     assert into2.photon_layout is LAYOUT and into2.count(ALL) == 2
@@ -236,7 +239,7 @@ def test_an_ensemble_that_never_deposits_is_what_it_was():
             e.add_products(be, 2, fin)
             e.add_iteration(be)
         prev = f
-    assert today.count(ALL) == 0 and today._amean is None and today._pending is None and both.count(ALL) == 3
+    assert today.count(ALL) == 0 and ALL not in today._slots and today._pending is None and both.count(ALL) == 3
     slots = [0, 1, 2, 3, today.products_slot(2)] + [today.photons_slot(s) for s in range(3)]
     for slot in slots:
         n = today._len(slot)

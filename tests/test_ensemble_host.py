@@ -2,13 +2,15 @@
 ensemble_common.py bit for bit, the layout of the sample vectors, the exported symbols, and driver.run(ensemble=...) through the
 CPU oracle."""
 import ctypes as ct
+import types
 
 import numpy as np
 import pytest
 
 from conftest import mcs, make_problem, oracle_backend
-from ensemble_common import (AS_IS, HISTS, INCREMENTS, SPECIES_TALLIES, assert_tail_is_exercised, bits_equal, crafted_buffers,
-                             iteration_parts, species_parts, stat_of)
+from ensemble_common import (AS_IS, HISTS, INCREMENTS, SPECIES_TALLIES, assert_tail_is_exercised, bits_equal, check_one_merge_of_every_kind,
+                             crafted_buffers, iteration_parts, species_parts, stat_of)
+from photons_all_common import SMALL_LAYOUT, SMALL_PROCESSES, crafted_species
 
 ens = mcs.ensemble
 
@@ -106,6 +108,43 @@ def test_host_ensemble_equals_the_restatement(crafted):
         e.mean(1, "spectra_sf")
     with pytest.raises(KeyError):
         e.mean(2, "px_esc_feb")                  # indexed by iteration: not exposed
+
+
+def test_one_merge_sends_every_kind_through(crafted):
+    """Two ensembles of two species slots with samples in slot 0, the iteration slot, products_slot(0), photons_slot(0) and the source
+    slot -- two on one side, three on the other -- and in photons_slot(1) of the second alone: one merge call, every kind."""
+    prob, L, bufs, parts = crafted
+    be = oracle_backend(prob)
+    x_log = ens.bin_centres_log10(prob)
+    ng, nm = prob.params.n_grid, prob.params.num_psd_mom_bins + 2
+
+    def products_of(k):      # (what add_products reads of an IonFinal; the merge does not care where a sample came from)
+        rng = np.random.default_rng(500 + k)
+        dndp = np.where(rng.random((3, ng, nm)) < 0.8, 10.0 ** rng.uniform(-30, 5, (3, ng, nm)), 1e-99)
+        return types.SimpleNamespace(dNdp_cr=dndp, P_psd_par=rng.uniform(1, 2, ng), P_psd_perp=rng.uniform(1, 2, ng), energy_density_psd=rng.uniform(1, 2, ng))
+
+    a, b = ens.HostEnsemble(prob.params, 2), ens.HostEnsemble(prob.params, 2)
+    for e, ks in ((a, (1, 2)), (b, (3, 4, 0))):
+        e.set_slope_window(0, prob.params.num_psd_mom_bins + 1, x_log)
+        e.set_photon_layout(SMALL_LAYOUT)
+        for k in ks:
+            f, i = bufs[k]
+            obs = crafted_species(k, 0, SMALL_LAYOUT, SMALL_PROCESSES)
+            be.write_tallies(bufs[k - 1][0], i)
+            e.begin_iteration(be)
+            be.write_tallies(f, i)
+            e.add_species(be, 0)
+            e.add_products(be, 0, products_of(k))
+            e.add_photons(None, 0, obs[0], deposit=True)
+            if e is b:
+                e.add_photons(None, 1, obs[1])
+            e.add_photons_all()
+            e.add_iteration(be)
+    slots = [0, a.iteration_slot, a.products_slot(0), a.photons_slot(0), a.photons_slot(1), a.photons_all_slot]
+    assert [a._kind(s) for s in slots] == ["species", "iteration", "products", "photons", "photons", "source"]
+    check_one_merge_of_every_kind(a, b, {s: b._len(s) for s in slots}, only_b=[b.photons_slot(1)])
+    assert a.count(1) == 0 and a.count(a.products_slot(1)) == 0 and a.pending_photons == () and b.pending_photons == ()
+    be.destroy()
 
 
 def test_layout_agrees_with_the_library_and_the_tally_layout():

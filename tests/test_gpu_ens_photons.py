@@ -21,14 +21,14 @@ ENDS = [1, 4, 9, 30]
 PLAN = (("synch", "ic"), ("pion",), ("synch", "ic", "pion"), ("ic",), ("pion", "synch"))
 
 
-def observe(hb, processes, seed):
+def observe(hb, processes, seed, n_photon=N_PHOTON, ends=ENDS):
     """mcs_photon_observe of seeded random emission for the named processes -> process -> the device's own words on the host."""
     ng = hb.P.n_grid
     rng = np.random.default_rng(seed)
     out = {}
     for p in processes:
-        tabs = tables(p, ng, N_PHOTON[p], BETAS, ENDS)
-        flux = np.where(rng.random((ng, N_PHOTON[p])) < 0.7, 10.0 ** rng.uniform(-14, -2, (ng, N_PHOTON[p])), 1e-99)
+        tabs = tables(p, ng, n_photon[p], BETAS, ends)
+        flux = np.where(rng.random((ng, n_photon[p])) < 0.7, 10.0 ** rng.uniform(-14, -2, (ng, n_photon[p])), 1e-99)
         emis = flux * tabs["energy_div"][None, :] * (cons.MEV_ERG if p == "ic" else tabs["area"] * (cons.MEV_ERG if p == "synch" else 1.0))
         out[p] = hb.photon_observe(p, emis=emis, **tabs)
     return out

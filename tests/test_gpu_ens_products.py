@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import mcs, make_problem, hip_backend
-from ensemble_common import bits_equal, crafted_buffers, species_parts, stat_of
+from ensemble_common import bits_equal, crafted_buffers, same_words, species_parts, stat_of
 from ens_summary_common import as_dict, assert_exact, assert_sums, restate, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -18,15 +18,6 @@ DNDP = ("dNdp_sf", "dNdp_pf", "dNdp_isf")
 SCALARS = ("P_psd_par", "P_psd_perp", "energy_density_psd")
 SLOPES = ("slope_sf", "slope_pf", "slope_isf")
 NAMES = DNDP + SCALARS + SLOPES
-
-
-def same_words(a, b):
-    """Bit-equal, where a NaN equals a NaN (the bits of a NaN that went through an update are nobody's promise)."""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
-        return False
-    ok = ~np.isnan(a)
-    return np.array_equal(a[ok].view(np.uint64), b[ok].view(np.uint64))
 
 
 def slopes_restated(hb, dndp, l_lo, l_hi, x_log):

@@ -5,8 +5,11 @@ import numpy as np
 import pytest
 
 from conftest import mcs, make_problem, hip_backend, oracle_backend
-from ensemble_common import (AS_IS, INCREMENTS, SPECIES_TALLIES, assert_tail_is_exercised, bits_equal, crafted_buffers, iteration_parts,
-                             species_parts, stat_of)
+from ensemble_common import (AS_IS, INCREMENTS, SPECIES_TALLIES, assert_tail_is_exercised, bits_equal, check_one_merge_of_every_kind,
+                             crafted_buffers, iteration_parts, species_parts, stat_of)
+from photons_all_common import SMALL_ENDS, SMALL_LAYOUT, SMALL_N_PHOTON, SMALL_PROCESSES
+from test_gpu_ens_photons import observe
+from test_gpu_ens_products import consume
 
 pytestmark = pytest.mark.gpu
 
@@ -120,6 +123,40 @@ def test_merge_is_chans_and_close_to_one_accumulator(crafted):
     _assert_slot(b, 0, wb, parts[0], "an empty source changes nothing:")
     for e in (a, b, c, d):
         e.destroy()
+    ha.destroy(); hb.destroy()
+
+
+def test_one_merge_sends_every_kind_through(crafted):
+    """Two accumulators of two species slots with samples in slot 0, the iteration slot, products_slot(0), photons_slot(0) and the
+    source slot -- two on one side, three on the other -- and in photons_slot(1) of the second alone: one mcs_ens_merge, every kind."""
+    prob, L, bufs, parts, want = crafted
+    ha, hb = hip_backend(prob), hip_backend(prob)
+    tabs = mcs.consumers.consumer_tables(prob, 1)
+    x_log = ens.bin_centres_log10(prob)
+    a, b = ens.HipEnsemble(ha, 2), ens.HipEnsemble(hb, 2)
+    for be, e, ks in ((ha, a, (1, 2)), (hb, b, (3, 4, 0))):
+        e.set_slope_window(0, prob.params.num_psd_mom_bins + 1, x_log)
+        e.set_photon_layout(SMALL_LAYOUT)
+        for k in ks:
+            f, i = bufs[k]
+            be.write_tallies(bufs[k - 1][0], i)
+            e.begin_iteration(be)
+            be.write_tallies(f, i)
+            e.add_species(be, 0)
+            consume(be, tabs)
+            e.add_products(be, 0)
+            observe(be, SMALL_PROCESSES[0], k, SMALL_N_PHOTON, SMALL_ENDS)
+            e.add_photons(be, 0, deposit=True)
+            if e is b:
+                observe(be, SMALL_PROCESSES[1], 50 + k, SMALL_N_PHOTON, SMALL_ENDS)
+                e.add_photons(be, 1)
+            e.add_photons_all()
+            e.add_iteration(be)
+    slots = [0, a.iteration_slot, a.products_slot(0), a.photons_slot(0), a.photons_slot(1), a.photons_all_slot]
+    assert [a._kind(s) for s in slots] == ["species", "iteration", "products", "photons", "photons", "source"]
+    check_one_merge_of_every_kind(a, b, {s: b._len(s) for s in slots}, only_b=[b.photons_slot(1)])
+    assert a.count(1) == 0 and a.count(a.products_slot(1)) == 0 and a.pending_photons == () and b.pending_photons == ()
+    a.destroy(); b.destroy()
     ha.destroy(); hb.destroy()
 
 

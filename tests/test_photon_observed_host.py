@@ -184,7 +184,7 @@ def test_host_ensemble_photons_slot():
     other.set_photon_layout(lay)
     for o in crafted_observations(lay, 4, seed=50):
         other.add_photons(None, 0, o)
-    mb, qb = other._hmean[0], other._hm2[0]
+    mb, qb = (other._read(other.photons_slot(0), what, 0, mean.size) for what in (0, 1))
     creqs = [ens.CompareRequest("total", (0, 3), 1e-9, 2.0), ens.CompareRequest("ic", (3, 4), 0.0, 1.0, (2, 15))]
     for q, d in zip(creqs, e.compare(other, hs, creqs, other.photons_slot(0))):
         first, count = e.word_range(hs, q.name, q.zones, q.bins)
