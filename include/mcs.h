@@ -828,6 +828,29 @@ typedef struct mcs_pcut_eval {
   int64_t pd[4], pd_next[4];
 } mcs_pcut_eval;
 int mcs_eval_pcut_split(mcs_ctx* ctx, mcs_pcut_eval* io);
+/* The step where a particle event becomes numbers in the tally buffer, on the CALLER's records: the transport kernel's own flux_tally,
+ * particle_finish, tcut_track, record stack, tally replicas and block flush, in a kernel inside its translation unit
+ * (mcs_k_eval_tally in csrc/mcs_transport.hip), between block_prologue and block_flush as transport_body runs them.  Called after
+ * mcs_begin_iteration / mcs_begin_species on a context with an empty population; the launch constants are the context's own (those of
+ * a transport launch of pcut 1), the replicas are marked as a transport launch marks them, and the results are read with
+ * mcs_read_tallies.  n_pass x n_thread records, record (pass, thread) at index pass * n_thread + thread; thread t is lane t % 64 of
+ * wave (t % 256) / 64 of block t / 256 (blocks of 256 threads), and a pass is one round in which every thread handles its record.
+ *   rec [n][8]  pb_pf, p_perp, ptot_pf, gam_pf, phi, weight, x, x_old   (form 2: in the fp32 kernels' normalised units, every value an
+ *               exact float: momenta in m_p c, lengths in rg0 = gam0 beta0 m_p c^2 / (e B[0]); the tally sees (double) f * unit)
+ *   word [n]    i_grid | i_grid_old << 8 | ig3 << 16 | inj << 24 | aux << 32 | kind << 40
+ *               kind 0 idle (the thread sits the pass out), 1 zone crossing (flux_tally), 2 finished particle (particle_finish; aux =
+ *               i_reason 1..4), 3 time cut (tcut_track; aux = the index of the cut, 1..n_tcuts)
+ * form 0  direct: every thread calls the tally function on its record (the DIRECT sites of the loop, and a lane's third event);
+ *      1  the stack: per pass a wave drains when 64 records are pending, then the threads with a record of kind 1 or 2 push it
+ *         (push_record; an idle thread takes no part in the ballot); drain_events(all) after the last pass.  Kind 3 is called directly.
+ *      2  the fp32 kernels' stack: the same through push_record_k / drain_events_k (which drains at 32).  The fp32 kernels are part of
+ *         every build, so the context need not be an fp32-state one.
+ * Refused with a message, nothing queued: a null or negative argument, a form outside 0..2, a kind outside 0..3, a non-finite value, a
+ * zone index outside [0, n_grid + 1], a crossing that would tally outside zones 1..n_grid, i_reason outside 1..4, a cut outside
+ * [1, n_tcuts], form 2 with a value that is no float, a population, and a layout whose pending records would exceed a wave's stack (with one push per
+ * lane and pass between two drain checks none does: the stack's capacity rests on at most two; the check guards the invariant). */
+#define MCS_TALLY_REC_F64 8
+int mcs_eval_tally(mcs_ctx* ctx, int form, int64_t n_pass, int64_t n_thread, const double* rec, const uint64_t* word);
 /* per-particle end state of the last mcs_run_pcut (bit-parity tests): i_reason
  * (0 = saved), helix_count, retro step count, final ptot_pf and x. Any pointer may be NULL.
  * The kernel records them only after mcs_set_debug_finals(ctx, 1) (24 B of stores per particle

@@ -1310,6 +1310,78 @@ int mcs_eval_scatter(mcs_ctx* c, int form, int64_t n, const double* in, double* 
   return 0;
 }
 
+// The caller's tally records through K1's own tally code (include/mcs.h): launch constants from fill_kargs, as a transport launch of
+// pcut 1 over an empty population has them; the replicas marked as such a launch marks them.  Every record is checked before anything
+// is queued: the kernel indexes LDS tables and the tally buffer with what the words say.
+int mcs_eval_tally(mcs_ctx* c, int form, int64_t n_pass, int64_t n_thread, const double* rec, const uint64_t* word) {
+  MCS_ENTER(c);
+  const std::string w = "mcs_eval_tally: ";
+  if (n_pass < 0 || n_thread < 0 || (n_pass > 0 && n_thread > 0 && (!rec || !word))) return fail(w + "null argument or negative count");
+  if (form < 0 || form > 2) return fail(w + "unknown form " + std::to_string(form) + " (0, 1 or 2: include/mcs.h)");
+  if (!c->have_grid || !c->have_cuts) return fail(w + "grid/cuts not set");
+  if (c->n != 0) return fail(w + "the context holds a population (the launch constants are those of an empty one)");
+  if (n_pass > 0 && n_thread > INT64_MAX / n_pass / (MCS_TALLY_REC_F64 + 1)) return fail(w + "n_pass * n_thread is too large");
+  const int64_t n = n_pass * n_thread;
+  const int ng = c->P.n_grid;
+  for (int64_t e = 0; e < n; ++e) {
+    const uint64_t u = word[e];
+    const int kind = (int)((u >> 40) & 0xffu), aux = (int)((u >> 32) & 0xffu);
+    const int i_grid = (int)(u & 0xffu), i_grid_old = (int)((u >> 8) & 0xffu), ig3 = (int)((u >> 16) & 0xffu);
+    const std::string at = w + "record " + std::to_string(e) + ": ";
+    if ((u >> 48) != 0 || ((u >> 25) & 0x7fu) != 0 || kind > 3) return fail(at + "unknown kind or stray bits in the word (include/mcs.h)");
+    if (kind == 0) continue;
+    const double* r = rec + MCS_TALLY_REC_F64 * e;
+    for (int j = 0; j < MCS_TALLY_REC_F64; ++j) {
+      if (!std::isfinite(r[j])) return fail(at + "value " + std::to_string(j) + " is not finite");
+      if (form == 2 && (double)(float)r[j] != r[j]) return fail(at + "value " + std::to_string(j) + " is no float (form 2 takes fp32 values)");
+    }
+    if (i_grid > ng + 1 || i_grid_old > ng + 1 || ig3 > ng + 1) return fail(at + "zone index outside [0, n_grid + 1]");
+    if (kind == 1) {
+      // F_stream! walks zones i_grid_old + 1 .. i_grid (x > x_old) or i_grid_old .. i_grid + 1 (else): all_flux! leaves both in [0, n_grid]
+      const double x = form == 2 ? (double)(float)r[6] : r[6], x_old = form == 2 ? (double)(float)r[7] : r[7];
+      const bool down = x > x_old;
+      const int lo = down ? i_grid_old + 1 : i_grid + 1, hi = down ? i_grid : i_grid_old;
+      if (lo <= hi && (lo < 1 || hi > ng)) return fail(at + "the crossing would tally outside zones 1 .. n_grid");
+    } else if (kind == 2) {
+      if (aux < 1 || aux > 4) return fail(at + "i_reason outside 1 .. 4");
+    } else {
+      if (aux < 1 || aux > c->tb.n_tcuts) return fail(at + "time cut outside [1, n_tcuts]");
+    }
+  }
+  if (form != 0) {
+    // A wave's stack: drained to below `drain_at` at the top of a pass, then one record per pushing lane.  The capacity rests on at most
+    // two passes' worth of pushes between drains (MCS_EV_CAP, mcs_device.h); this layout keeps to it by construction, and the walk below
+    // refuses whatever would not.
+    int cap = 0, drain_at = 0;
+    if (mcs_eval_tally_stack(form, &cap, &drain_at)) return fail(w + "no stack for this form");
+    const int64_t n_wave = (n_thread + 63) / 64;
+    std::vector<int> height((size_t)n_wave, 0);
+    for (int64_t p = 0; p < n_pass; ++p)
+      for (int64_t t = 0; t < n_thread; ++t) {
+        int& h = height[(size_t)(t / 64)];
+        if (t % 64 == 0) while (h >= drain_at) h -= std::min(h, 64);
+        const int kind = (int)((word[p * n_thread + t] >> 40) & 0xffu);
+        if (kind == 1 || kind == 2) {
+          if (++h > cap) return fail(w + "pass " + std::to_string(p) + ": more records pending than a wave's stack holds");
+        }
+      }
+  }
+  if (n == 0) return 0;
+  if (reserve(c->d_stage, (MCS_TALLY_REC_F64 + 1) * n + 2) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1)) return 1;
+  HIPCHK(hipStreamSynchronize(c->stream));         // (nothing queued may still read the launch constants)
+  KArgs& a = *c->h_args_pin;
+  fill_kargs(c, a, 1, 0, 0, 1, nullptr, 0);
+  double* drec = c->d_stage;
+  unsigned long long* dword = (unsigned long long*)(c->d_stage + MCS_TALLY_REC_F64 * n);
+  HIPCHK(hipMemcpyAsync(c->d_args, c->h_args_pin, sizeof(KArgs), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(drec, rec, (size_t)n * MCS_TALLY_REC_F64 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dword, word, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(mcs_launch_eval_tally(c->d_args, form, n_pass, n_thread, drec, dword, c->stream));
+  c->rep_dirty = true;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // K2 on the caller's status bytes and saved states (include/mcs.h): the launchers mcs_run_pcut / mcs_new_pcut / mcs_saved_export (form 0),
 // mcs_run_pcuts_fused (form 1) and pipelined_pcuts (form 2) call, with their grids, on the context's own saved arrays, status bytes,
 // scan scratch and counter words; the target is the spare buffer between two guards.  Everything is checked before anything is

@@ -2565,6 +2565,79 @@ extern "C" __global__ void __launch_bounds__(256) mcs_k_eval_scatter(const KArgs
   o[0] = p.pb_pf; o[1] = p.p_perp; o[2] = p.phi; o[3] = p.gyro_period; o[4] = p.cm_val;
 }
 
+// Caller-given tally records through the tally code of the kernels above (mcs_eval_tally, include/mcs.h; tests/test_gpu_tally_records.py),
+// in transport_body's frame: block_prologue, barrier, the records, barrier, block_flush.  Record (pass, thread) is at index
+// pass * n_thread + thread; a thread whose record is idle sits the pass out, so that the ballots of the pushes are ragged.
+//   form 0  flux_tally / particle_finish / tcut_track called by the lane itself (the DIRECT sites, and npush >= 2)
+//   form 1  per pass: the wave drains once 64 records are pending, then the lanes with a record push it; drain_events(all) at the end
+//   form 2  the same through the fp32 kernels' stack (push_record_k / drain_events_k, which drain at 32); the record's values are
+//           floats in the units of F32Units (set up as transport_f32k_body sets them up)
+// A time cut (kind 3) is tallied on the spot in every form, as in the kernels.  The host has checked every index (mcs_eval_tally).
+extern "C" __global__ void __launch_bounds__(256) mcs_k_eval_tally(const KArgs* __restrict__ ka, int form, long long n_pass, long long n_thread,
+                                                                   const double* __restrict__ rec, const unsigned long long* __restrict__ word) {
+  CK* a = (CK*)ka;
+  block_prologue(a);
+  if (threadIdx.x < 4) F_evcur[threadIdx.x] = 0u;
+  __syncthreads();
+  const unsigned wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  F32Units U;
+  U.L0 = a->P.gam0 * a->P.beta0 * MCS_MP * MCS_C * MCS_C / (MCS_QCGS * S_bt[0]);
+  U.P0 = MCS_MP * MCS_C; U.T0 = U.L0 / MCS_C; U.invL0 = 1.0 / U.L0;
+  unsigned ev_unused = 0u;
+  for (long long pass = 0; pass < n_pass; ++pass) {
+    if (form == 1) { if (S_evcur[wv] >= 64u) drain_events(a, wv, lane, false); }
+    else if (form == 2) { if (F_evcur[wv] >= 32u) drain_events_k(a, U, wv, lane, false); }
+    const long long e = pass * n_thread + t;
+    const unsigned long long w = t < n_thread ? word[e] : 0ull;
+    const int kind = (int)((w >> 40) & 3ull);
+    const double* r = rec + MCS_TALLY_REC_F64 * (kind != 0 ? e : 0);
+    const int i_grid = (int)(w & 0xffull), i_grid_old = (int)((w >> 8) & 0xffull), ig3 = (int)((w >> 16) & 0xffull), aux = (int)((w >> 32) & 0xffull);
+    const bool inj = ((w >> 24) & 1ull) != 0ull;
+    if (kind == 3) {
+      if (form == 2) tcut_track(a, aux, (double)(float)r[5], (double)(float)r[2] * U.P0);
+      else tcut_track(a, aux, r[5], r[2]);
+    } else if (kind == 0) {      // idle: the lane is not among those the pushes below ballot
+    } else if (form == 0) {
+      if (kind == 1) flux_tally(a, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], i_grid, i_grid_old, ig3, inj);
+      else particle_finish(a, aux, r[0], r[1], r[3], r[4], r[5], ig3);
+    } else {
+      const uint32_t tag = kind == 2 ? ((1u << 28) | ((uint32_t)aux << 25)) : 0u;
+      if (form == 1) {
+        Pt p{};
+        p.pb_pf = r[0]; p.p_perp = r[1]; p.ptot_pf = r[2]; p.gam_pf = r[3]; p.phi = r[4]; p.weight = r[5]; p.x = r[6]; p.x_old = r[7];
+        p.i_grid = i_grid; p.i_grid_old = i_grid_old; p.inj = inj;
+        push_record(p, ig3, -1, tag);
+      } else {
+        Pk p{};
+        p.pb = (float)r[0]; p.pperp = (float)r[1]; p.ptot = (float)r[2]; p.gam = (float)r[3]; p.phi = (float)r[4]; p.w = (float)r[5];
+        p.x = (float)r[6]; p.x_old = (float)r[7];
+        p.i_grid = i_grid; p.i_grid_old = i_grid_old; p.inj = inj;
+        push_record_k(p, ig3, tag, ev_unused);
+      }
+    }
+  }
+  if (form == 1) drain_events(a, wv, lane, true);
+  else if (form == 2) drain_events_k(a, U, wv, lane, true);
+  __syncthreads();
+  block_flush(a);
+}
+
+// the stack a form of mcs_k_eval_tally pushes to: records a wave's stack holds, and the height at which a pass drains it first
+extern "C" int mcs_eval_tally_stack(int form, int* cap, int* drain_at) {
+  if (form == 1) { *cap = MCS_EV_CAP; *drain_at = 64; return 0; }
+  if (form == 2) { *cap = F32_EV_CAP; *drain_at = 32; return 0; }
+  return 1;
+}
+
+extern "C" hipError_t mcs_launch_eval_tally(const KArgs* a_dev, int form, long long n_pass, long long n_thread, const double* rec,
+                                            const unsigned long long* word, hipStream_t st) {
+  if (form < 0 || form > 2) return hipErrorInvalidValue;
+  if (n_pass <= 0 || n_thread <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcs_k_eval_tally, dim3((unsigned)((n_thread + 255) / 256)), dim3(256), 0, st, a_dev, form, n_pass, n_thread, rec, word);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t mcs_launch_eval_hot(int fn, long long n, const double* a, const double* b, double* out, hipStream_t st) {
   if (fn < MCS_FN_SQRT_FAST || fn >= MCS_FN_COUNT) return hipErrorInvalidValue;
   if (n <= 0) return hipSuccess;

@@ -436,6 +436,16 @@ class HipBackend:
         self._chk(self.lib.mcs_eval_scatter(self.h, int(form), len(s), _dp(s), _dp(out)))
         return out
 
+    def eval_tally(self, form: int, rec, word):
+        """Caller-given tally records through the transport kernel's own tally code (mcs_eval_tally in include/mcs.h: form 0 direct,
+        1 the record stack, 2 the fp32 kernels' stack).  rec [n_pass][n_thread][8]: pb_pf, p_perp, ptot_pf, gam_pf, phi, weight, x,
+        x_old; word [n_pass][n_thread] uint64: i_grid | i_grid_old << 8 | ig3 << 16 | inj << 24 | aux << 32 | kind << 40.  The
+        deposits land in the context's tallies: read them with read_tallies()."""
+        r = np.ascontiguousarray(rec, dtype=np.float64)
+        w = np.ascontiguousarray(word, dtype=np.uint64)
+        assert w.ndim == 2 and r.shape == w.shape + (8,)
+        self._chk(self.lib.mcs_eval_tally(self.h, int(form), w.shape[0], w.shape[1], _dp(r), w.ctypes.data_as(ct.POINTER(ct.c_uint64))))
+
     def eval_pcut_split(self, form: int, l_save, saved: Population, n=None, *, match=1, i_mult=1, n_target=1, ctr_work=0, ctr_saved=0,
                         n_main_next=0, src_fill=0, guard=64, out_cap=0, export_mode=0, exp_cap=0, exp_first=0, exp_stride=1, exp_gin=None):
         """The pcut bookkeeping kernels on the caller's status bytes and saved states (mcs_eval_pcut_split in include/mcs.h: form 0

@@ -59,6 +59,8 @@ def load(math: str = "det", capi=None):
         "orc_eval_fn": (i32, [i32, i64, dp, dp, dp]),
         "orc_scattering": (None, [vp, ct.c_uint64, dbl, dbl, dbl, dbl, dbl, dp, dp, dp, dp]),
         "orc_eval_scatter": (i32, [vp, i64, dp, dp]),
+        "orc_eval_tally": (i32, [vp, i32, i64, dp, ct.POINTER(ct.c_uint64), i32]),
+        "orc_tally_log": (i64, [vp, i64, i64p, i64p, i64p, dp]),
         "orc_transform_p_PS": (None, [dbl] * 11 + [dp]),
         "orc_transform_p_PSP": (None, [vp] + [dbl] * 5 + [dp, dp, dp]),
         "orc_set_long_draws": (i32, [vp, i64]),
@@ -360,3 +362,19 @@ class OracleBackend:
         out = np.zeros((len(s), 5))
         self._chk(self.lib.orc_eval_scatter(self.h, len(s), _dp(s), _dp(out)))
         return out
+
+    def eval_tally(self, rec, word, f32_units=False, log=True):
+        """The tally records of HipBackend.eval_tally, walked serially in index order through the oracle's own all_flux tally part,
+        particle_finish and tcut_track (the oracle has one spelling, so no `form`; f32_units: the rows of form 2).  With log, returns
+        every deposit of the walk as arrays (record index, buffer: 0 fp64 tallies / 1 int64 tallies, offset, value), in the order made."""
+        r = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, 8)
+        w = np.ascontiguousarray(word, dtype=np.uint64).reshape(-1)
+        assert len(r) == len(w)
+        self._chk(self.lib.orc_eval_tally(self.h, int(bool(f32_units)), len(w), _dp(r), w.ctypes.data_as(ct.POINTER(ct.c_uint64)), int(bool(log))))
+        if not log:
+            return None
+        n = int(self.lib.orc_tally_log(self.h, 0, None, None, None, None))
+        i64p = ct.POINTER(ct.c_int64)
+        lr, lb, lo, lv = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n)
+        self.lib.orc_tally_log(self.h, n, lr.ctypes.data_as(i64p), lb.ctypes.data_as(i64p), lo.ctypes.data_as(i64p), _dp(lv))
+        return lr, lb, lo, lv

@@ -284,6 +284,13 @@ class Twin:
         n_xspec = len(self.x_spec)
         if i_grid == i_grid_old and i_grid > P.i_grid_feb and n_xspec == 0:
             return i_grid, i_grid_old
+        self.flux_tally(pb_pf, p_perp, ptot_pf, gam_pf, phi, weight, i_grid, i_grid_old, ux, gsf, bcos, bsin, x, x_old, inj)
+        return i_grid, i_grid_old
+
+    # -- the tally part of all_flux!, all_flux.jl:84-259: the move ended in zone i_grid, coming from i_grid_old
+    def flux_tally(self, pb_pf, p_perp, ptot_pf, gam_pf, phi, weight, i_grid, i_grid_old, ux, gsf, bcos, bsin, x, x_old, inj):
+        P = self.P
+        n_xspec = len(self.x_spec)
         ptot_sk, (px, py, pz), gam_sk = self.transform_p_PS(pb_pf, p_perp, gam_pf, phi, ux, gsf, bcos, bsin)
         m = self.aa * MP
         if ptot_sk > abs(px * SPIKE_AWAY):
@@ -341,7 +348,6 @@ class Twin:
         if inj and x < P.feb_upstream and x_old >= P.feb_upstream:      # Q1: kept (the reference drops these by value)
             self.T["scalars"][3] += e_add * g0u0
             self.T["scalars"][2] -= px * weight * g0u0
-        return i_grid, i_grid_old
 
     # -- particle_loop.jl:652-723
     def do_energy_transfer(self, i_grid, i_grid_old, ptot_pf, pb_pf, p_perp, gam_pf, weight):
