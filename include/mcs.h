@@ -851,6 +851,35 @@ int mcs_eval_pcut_split(mcs_ctx* ctx, mcs_pcut_eval* io);
  * lane and pass between two drain checks none does: the stack's capacity rests on at most two; the check guards the invariant). */
 #define MCS_TALLY_REC_F64 8
 int mcs_eval_tally(mcs_ctx* ctx, int form, int64_t n_pass, int64_t n_thread, const double* rec, const uint64_t* word);
+/* The move of Code Block 2 and the decision what that move triggers, on the CALLER's states: the transport kernel's own
+ * load_particle, refresh_move / refresh_time / refresh_dtest, one of the four spellings of the move, then slow_post or plain_crossing,
+ * in a kernel inside its translation unit (mcs_k_eval_move in csrc/mcs_transport.hip), between block_prologue and block_flush as
+ * transport_body runs them.  The states are the context's population (mcs_pop_upload after mcs_begin_iteration / mcs_begin_species),
+ * one state per thread, n = the population's size: weight, ptot_pf, pb_pf, x, xn_per, prp, acctime, phi, grid, tcut, downstream, inj
+ * as the move sees them, i.e. AFTER the scatter and the clock of a pass; gam_pf, gyro_denom, gyro_rad_tot, gyro_period (that of the
+ * prologue: 2 pi gam m c / (Z e B)), p_perp and the zone's properties and edges are the kernel's own derivation.  The launch constants
+ * are those of a transport launch of pcut i_pcut over this population (which fixes pcut_prev, and the RNG key of state k: that of
+ * particle k + 1).  Neither the population nor the saved arrays are written; tallies are read with mcs_read_tallies.
+ * form 0  move_and_detect: the exact one, as Code Block 1 passes and the rare region use it
+ *      1  refresh_thr then move_and_detect_thr: the common pass
+ *      2  form 1 with the tail loop's literals (mod2pi_k, whose domain is that of mod2pi: |phi + 2 pi / xn_per| < 1e5)
+ *      3  the lossy kernel: refresh_dtest_k, refresh_thr without the fine / coarse switch, move_and_detect_thr(xn_is_threshold = false)
+ *      In forms 1-3 the two thresholds are computed with the position set to x_thr[k] (the lane's last visit to the rare region),
+ *      the state otherwise its own; then the move is made from the state's own x.  x_thr = x is the ordinary case.  Form 0 ignores
+ *      x_thr (may be NULL).
+ * post 0  nothing follows the move          1  slow_post, its record pushed and drained          2  slow_post tallying directly
+ *      3  plain_crossing, its record pushed and drained                                          4  plain_crossing tallying directly
+ *      Posts 1-4 run on the moved state whether or not the move reported an event.
+ * out [n][MCS_MOVE_OUT_F64]  x, x_old, phi, pb_pf, p_perp, ptot_pf, gam_pf, prp, acctime, t_hi, t_lo, x_dt, z_lo, z_hi, z_ux, z_gsf,
+ *      z_bcos, z_gef   (t_hi, t_lo: 0 in form 0)
+ * word [n]  i_grid | i_grid_old << 8 | ig3 << 16 | tcut << 24 | downstream << 32 | inj << 33 | end << 34 (3 bits: slow_post's end code
+ *      1..4, 7 = goes on / no slow_post) | F_B1 << 37 | F_CROSSED << 38 | F_ZONE << 39 | the move's returned event bit << 40 |
+ *      its ev_cross << 41 | plain_crossing's return value << 42 | records pushed << 43 (2 bits) | min(n_retro, 511) << 45 |
+ *      min(draws taken, 1023) << 54
+ * Refused with a message, nothing queued: a null or negative argument, form outside 0..3, post outside 0..4, i_pcut outside
+ * [1, n_pcuts], n other than the population's size, a non-finite x_thr, a context with fp32 state. */
+#define MCS_MOVE_OUT_F64 18
+int mcs_eval_move(mcs_ctx* ctx, int form, int post, int i_pcut, int64_t n, const double* x_thr, double* out, uint64_t* word);
 /* per-particle end state of the last mcs_run_pcut (bit-parity tests): i_reason
  * (0 = saved), helix_count, retro step count, final ptot_pf and x. Any pointer may be NULL.
  * The kernel records them only after mcs_set_debug_finals(ctx, 1) (24 B of stores per particle

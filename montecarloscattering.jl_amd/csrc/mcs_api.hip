@@ -1382,6 +1382,43 @@ int mcs_eval_tally(mcs_ctx* c, int form, int64_t n_pass, int64_t n_thread, const
   return 0;
 }
 
+// One move of Code Block 2 per state of the context's population through K1's own move and post-move code (include/mcs.h): launch
+// constants from fill_kargs, as a transport launch of pcut i_pcut over this population has them; the replicas marked as such a launch
+// marks them.  The states' indices were checked by mcs_pop_upload; the kernel writes only `out`, `word` and the tallies.
+int mcs_eval_move(mcs_ctx* c, int form, int post, int i_pcut, int64_t n, const double* x_thr, double* out, uint64_t* word) {
+  MCS_ENTER(c);
+  const std::string w = "mcs_eval_move: ";
+  if (n < 0 || (n > 0 && (!out || !word))) return fail(w + "null argument or negative count");
+  if (form < 0 || form > 3) return fail(w + "unknown form " + std::to_string(form) + " (0 .. 3: include/mcs.h)");
+  if (post < 0 || post > 4) return fail(w + "unknown post " + std::to_string(post) + " (0 .. 4: include/mcs.h)");
+  if (form != 0 && n > 0 && !x_thr) return fail(w + "null argument (forms 1 .. 3 take x_thr)");
+  if (!c->have_grid || !c->have_cuts) return fail(w + "grid/cuts not set");
+  if (i_pcut < 1 || i_pcut > c->tb.n_pcuts) return fail(w + "i_pcut outside [1, n_pcuts]");
+  if (c->P.state_fp32) return fail(w + "the context holds fp32 state (the move of the fp32 kernels is another function)");
+  if (n != c->n) return fail(w + "n is not the size of the context's population (mcs_pop_upload)");
+  if (form != 0)
+    for (int64_t k = 0; k < n; ++k)
+      if (!std::isfinite(x_thr[k])) return fail(w + "x_thr[" + std::to_string(k) + "] is not finite");
+  if (n == 0) return 0;
+  if (n > INT64_MAX / (MCS_MOVE_OUT_F64 + 2)) return fail(w + "n is too large");
+  if (reserve(c->d_stage, (MCS_MOVE_OUT_F64 + 2) * n) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1)) return 1;
+  HIPCHK(hipStreamSynchronize(c->stream));         // (nothing queued may still read the launch constants)
+  KArgs& a = *c->h_args_pin;
+  fill_kargs(c, a, i_pcut, n, 0, 1, nullptr, 0);
+  a.f_reason = nullptr; a.f_helix = nullptr; a.f_retro = nullptr; a.f_ptot = nullptr; a.f_x = nullptr;
+  double* dthr = c->d_stage;
+  double* dout = c->d_stage + n;
+  unsigned long long* dword = (unsigned long long*)(c->d_stage + (MCS_MOVE_OUT_F64 + 1) * n);
+  HIPCHK(hipMemcpyAsync(c->d_args, c->h_args_pin, sizeof(KArgs), hipMemcpyHostToDevice, c->stream));
+  if (form != 0) HIPCHK(hipMemcpyAsync(dthr, x_thr, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(mcs_launch_eval_move(c->d_args, form, post, n, dthr, dout, dword, c->stream));
+  c->rep_dirty = true;
+  HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * MCS_MOVE_OUT_F64 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(word, dword, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // K2 on the caller's status bytes and saved states (include/mcs.h): the launchers mcs_run_pcut / mcs_new_pcut / mcs_saved_export (form 0),
 // mcs_run_pcuts_fused (form 1) and pipelined_pcuts (form 2) call, with their grids, on the context's own saved arrays, status bytes,
 // scan scratch and counter words; the target is the spare buffer between two guards.  Everything is checked before anything is

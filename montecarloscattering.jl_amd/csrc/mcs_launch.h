@@ -40,6 +40,8 @@ hipError_t mcs_launch_eval_scatter(const KArgs* a_dev, int form, long long n, co
 hipError_t mcs_launch_eval_tally(const KArgs* a_dev, int form, long long n_pass, long long n_thread, const double* rec,
                                  const unsigned long long* word, hipStream_t st);
 int mcs_eval_tally_stack(int form, int* cap, int* drain_at);
+hipError_t mcs_launch_eval_move(const KArgs* a_dev, int form, int post, long long n, const double* x_thr, double* out,
+                                unsigned long long* word, hipStream_t st);
 hipError_t mcs_launch_dndp_cr(const mcs_params* P, const double* psd, const double* gam_sf, const double* ux, const double* tabs,
                               double rest_energy, double n0, double gam0, double* out_dndp, unsigned long long* diag, hipStream_t st);
 hipError_t mcs_launch_dndp_2d(const mcs_params* P, const double* psd, const double* therm_sf, const unsigned long long* num_crossings, const double* tabs,

@@ -1717,7 +1717,7 @@ __device__ __forceinline__ void transport_body(const KArgs* __restrict__ ka) {
   // Hot-loop constants are parked in VGPRs behind an opaque move: the compiler can then
   // neither re-load them from the constant buffer inside the loop (s_load + s_waitcnt) nor
   // spill them as SGPRs.
-  Hot h;
+  Hot h;      // (mcs_k_eval_move, at the end of this file, repeats these statements for the general kernel: keep the two alike)
   h.m = vconst(a->m); h.x_grid_stop = vconst(a->P.x_grid_stop); h.xn_coarse = vconst(a->P.xn_per_coarse);
   h.u2 = sconst(a->P.u2); h.eta = sconst(a->P.eta_mfp); h.zzq = sconst(a->zzq); h.mc = sconst(a->mc);
   h.feb_down = sconst(a->P.feb_downstream); h.pcut = sconst(a->pcut); h.pmax_cutoff = sconst(a->pmax_cutoff);
@@ -2635,6 +2635,103 @@ extern "C" hipError_t mcs_launch_eval_tally(const KArgs* a_dev, int form, long l
   if (form < 0 || form > 2) return hipErrorInvalidValue;
   if (n_pass <= 0 || n_thread <= 0) return hipSuccess;
   hipLaunchKernelGGL(mcs_k_eval_tally, dim3((unsigned)((n_thread + 255) / 256)), dim3(256), 0, st, a_dev, form, n_pass, n_thread, rec, word);
+  return hipGetLastError();
+}
+
+// One move of Code Block 2 per state of the context's population, and what that move triggers (mcs_eval_move, include/mcs.h;
+// tests/test_gpu_move_events.py), in transport_body's frame: block_prologue, barrier, the Hot constants, the states, barrier, block_flush.
+// One state per thread: load_particle (the prologue of particle_loop), refresh_move / refresh_time / refresh_dtest as slow_pre leaves
+// them, then
+//   form 0  move_and_detect                                             (block1_step, the rare region)
+//        1  refresh_thr<false> at x_thr[i], then move_and_detect_thr    (the common pass)
+//        2  the same with the tail loop's literals (TailK: mod2pi_k)
+//        3  refresh_dtest_k, refresh_thr<true> at x_thr[i], move_and_detect_thr(xn_is_threshold = false)   (the lossy kernel)
+//   post 0  nothing more        1  slow_post<false>, drained at the end        2  slow_post<true>
+//        3  plain_crossing<false>, drained at the end                          4  plain_crossing<true>
+// Posts 1-4 run on the moved state whether or not the move reported an event (the reference runs the tail of Code Block 2 after
+// every move).  The population and the saved arrays are only read.  out [n][MCS_MOVE_OUT_F64] and word [n]: include/mcs.h.
+// The host has checked every index the state carries (mcs_pop_upload) and the forms (mcs_eval_move).
+extern "C" __global__ void __launch_bounds__(256) mcs_k_eval_move(const KArgs* __restrict__ ka, int form, int post, long long n,
+                                                                  const double* __restrict__ x_thr, double* __restrict__ out,
+                                                                  unsigned long long* __restrict__ word) {
+  CK* a = (CK*)ka;
+  const int ne = a->P.n_grid + 2, ng = a->P.n_grid, ntc = a->tb.n_tcuts;
+  block_prologue(a);
+  __syncthreads();
+  // Hot as transport_body fills it for the general kernel (PLAIN = LOSSY = false): the statements are repeated here because moving them
+  // into a function both call changed the register allocation of a shipping kernel; keep the two alike.
+  Hot h;
+  h.m = vconst(a->m); h.x_grid_stop = vconst(a->P.x_grid_stop); h.xn_coarse = vconst(a->P.xn_per_coarse);
+  h.u2 = sconst(a->P.u2); h.eta = sconst(a->P.eta_mfp); h.zzq = sconst(a->zzq); h.mc = sconst(a->mc);
+  h.feb_down = sconst(a->P.feb_downstream); h.pcut = sconst(a->pcut); h.pmax_cutoff = sconst(a->pmax_cutoff);
+  h.feb_up = sconst(a->P.feb_upstream); h.age_max = sconst(a->P.age_max); h.inj_frac = sconst(a->inj_frac);
+  h.xn_fine = sconst(a->P.xn_per_fine); h.aa = sconst(a->aa);
+  h.n_grid = sconsti(ng); h.i_grid_feb = sconsti(a->P.i_grid_feb); h.n_tcuts = sconsti(ntc); h.n_xspec = sconsti(a->tb.n_xspec);
+  // uniform flags stay scalar (s_cbranch): whole code regions are skipped for free
+  h.custom_epsB = a->P.use_custom_epsB != 0; h.etf = a->P.energy_transfer_frac > 0;
+  h.dont_scatter = a->P.dont_scatter != 0; h.rad_losses = a->P.do_rad_losses != 0;
+  h.do_tcuts = a->P.do_tcuts != 0; h.dont_DSA = a->P.dont_DSA != 0;
+  {
+    int ob = 0;
+    for (int i = threadIdx.x; i < ne; i += blockDim.x) ob |= S_bsin[i] != 0.0;
+    h.oblique = __builtin_amdgcn_readfirstlane(__syncthreads_or(ob)) != 0;     // scalar: a uniform branch, not an exec mask
+  }
+  h.every_pass = h.custom_epsB || (h.rad_losses && h.aa < 1) || h.dont_scatter;
+  h.odd_cfg = h.feb_down > 0 || h.dont_DSA || h.inj_frac < 1 || h.aa < 1 || h.n_xspec != 0;
+  TailK K;
+  tail_k_init(K);
+  const unsigned wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {      // (no early return: the drain and the flush below are the whole wave's and the whole block's)
+    Pt p{};
+    Rng rng;
+    load_particle(a, h, i, p, rng);
+    p.helix = 1;      // (the pass that makes this move is the particle's first, and is counted before the move)
+    refresh_move(a, h, p);
+    if (form == 3) refresh_dtest_k(h, p, a->P.pe_crit, a->P.game_crit); else refresh_dtest(a, h, p);
+    if (form != 0) {
+      // the thresholds as the lane's last visit to the rare region left them, at x_thr; everything else is the state's own
+      const double x_own = p.x;
+      p.x = x_thr[i];
+      if (form == 3) refresh_thr<true>(h, p); else refresh_thr<false>(h, p);
+      p.x = x_own;
+    }
+    double phi_old = 0.0;
+    bool ev_cross = false, ev = false;
+    if (form == 0) ev = move_and_detect(a, h, p, phi_old, ev_cross);
+    else if (form == 1) ev = move_and_detect_thr(a, h, p, phi_old, ev_cross, true, nullptr);
+    else if (form == 2) ev = move_and_detect_thr(a, h, p, phi_old, ev_cross, true, &K);
+    else ev = move_and_detect_thr(a, h, p, phi_old, ev_cross, false, nullptr);
+    int end = -1;
+    bool plain = false;
+    if (post == 1) end = slow_post<false>(a, h, rng, p, phi_old);
+    else if (post == 2) end = slow_post<true>(a, h, rng, p, phi_old);
+    else if (post == 3) plain = plain_crossing<false>(a, h, p, 0u);      // (the wave's stack is empty: the height a pass's first push site knows)
+    else if (post == 4) plain = plain_crossing<true>(a, h, p, 0u);
+    double* o = out + (long long)MCS_MOVE_OUT_F64 * i;
+    o[0] = p.x; o[1] = p.x_old; o[2] = p.phi; o[3] = p.pb_pf; o[4] = p.p_perp; o[5] = p.ptot_pf; o[6] = p.gam_pf; o[7] = p.prp;
+    o[8] = p.acctime; o[9] = p.t_hi; o[10] = p.t_lo; o[11] = p.x_dt;
+    o[12] = p.z_lo; o[13] = p.z_hi; o[14] = p.z_ux; o[15] = p.z_gsf; o[16] = p.z_bcos; o[17] = p.z_gef;
+    const unsigned long long n_retro = (unsigned long long)(p.n_retro > 511 ? 511 : p.n_retro);
+    const unsigned long long draws = rng.n > 1023u ? 1023ull : (unsigned long long)rng.n;
+    word[i] = (unsigned long long)(p.i_grid & 0xff) | ((unsigned long long)(p.i_grid_old & 0xff) << 8) | ((unsigned long long)(p.ig3 & 0xff) << 16) |
+              ((unsigned long long)(p.tcut & 0xff) << 24) | ((unsigned long long)(p.downstream ? 1 : 0) << 32) |
+              ((unsigned long long)(p.inj ? 1 : 0) << 33) | ((unsigned long long)(end < 0 ? 7 : end) << 34) |
+              ((unsigned long long)((p.flags & F_B1) ? 1 : 0) << 37) | ((unsigned long long)((p.flags & F_CROSSED) ? 1 : 0) << 38) |
+              ((unsigned long long)((p.flags & F_ZONE) ? 1 : 0) << 39) | ((unsigned long long)(ev ? 1 : 0) << 40) |
+              ((unsigned long long)(ev_cross ? 1 : 0) << 41) | ((unsigned long long)(plain ? 1 : 0) << 42) |
+              ((unsigned long long)(p.npush & 3) << 43) | (n_retro << 45) | (draws << 54);
+  }
+  if (post == 1 || post == 3) drain_events(a, wv, lane, true);
+  __syncthreads();
+  block_flush(a);
+}
+
+extern "C" hipError_t mcs_launch_eval_move(const KArgs* a_dev, int form, int post, long long n, const double* x_thr, double* out,
+                                           unsigned long long* word, hipStream_t st) {
+  if (form < 0 || form > 3 || post < 0 || post > 4) return hipErrorInvalidValue;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcs_k_eval_move, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a_dev, form, post, n, x_thr, out, word);
   return hipGetLastError();
 }
 

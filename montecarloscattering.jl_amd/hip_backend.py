@@ -446,6 +446,23 @@ class HipBackend:
         assert w.ndim == 2 and r.shape == w.shape + (8,)
         self._chk(self.lib.mcs_eval_tally(self.h, int(form), w.shape[0], w.shape[1], _dp(r), w.ctypes.data_as(ct.POINTER(ct.c_uint64))))
 
+    def eval_move(self, form: int, post: int, i_pcut: int = 1, x_thr=None):
+        """One move of Code Block 2 per state of the context's population (set_population), and what follows it, through the
+        transport kernel's own code (mcs_eval_move in include/mcs.h: form 0 move_and_detect, 1 the thresholds of the common pass,
+        2 the tail loop's literals, 3 the lossy kernel's thresholds; post 0 nothing, 1 / 2 slow_post pushed / direct, 3 / 4
+        plain_crossing pushed / direct).  x_thr: the position at which forms 1-3 compute their thresholds (default: the state's own).
+        Returns out [n][18] and the packed word [n] of include/mcs.h; the deposits land in the context's tallies."""
+        n = self.pop_size()
+        thr = None if x_thr is None else np.ascontiguousarray(x_thr, dtype=np.float64)
+        if thr is None and form != 0:
+            thr = np.ascontiguousarray(self.get_population().x_PT_cm[:n], dtype=np.float64)
+        assert thr is None or thr.shape == (n,)
+        out = np.zeros((n, 18))
+        word = np.zeros(n, dtype=np.uint64)
+        self._chk(self.lib.mcs_eval_move(self.h, int(form), int(post), int(i_pcut), n, None if thr is None else _dp(thr), _dp(out),
+                                         word.ctypes.data_as(ct.POINTER(ct.c_uint64))))
+        return out, word
+
     def eval_pcut_split(self, form: int, l_save, saved: Population, n=None, *, match=1, i_mult=1, n_target=1, ctr_work=0, ctr_saved=0,
                         n_main_next=0, src_fill=0, guard=64, out_cap=0, export_mode=0, exp_cap=0, exp_first=0, exp_stride=1, exp_gin=None):
         """The pcut bookkeeping kernels on the caller's status bytes and saved states (mcs_eval_pcut_split in include/mcs.h: form 0

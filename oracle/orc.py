@@ -61,6 +61,8 @@ def load(math: str = "det", capi=None):
         "orc_eval_scatter": (i32, [vp, i64, dp, dp]),
         "orc_eval_tally": (i32, [vp, i32, i64, dp, ct.POINTER(ct.c_uint64), i32]),
         "orc_tally_log": (i64, [vp, i64, i64p, i64p, i64p, dp]),
+        "orc_eval_move": (i32, [vp, i32, i64, soa_p, dp, ct.POINTER(ct.c_uint64), i32]),
+        "orc_zone_search": (i32, [vp, i64, dp, u8p, i32p, i32p]),
         "orc_transform_p_PS": (None, [dbl] * 11 + [dp]),
         "orc_transform_p_PSP": (None, [vp] + [dbl] * 5 + [dp, dp, dp]),
         "orc_set_long_draws": (i32, [vp, i64]),
@@ -378,3 +380,35 @@ class OracleBackend:
         lr, lb, lo, lv = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n)
         self.lib.orc_tally_log(self.h, n, lr.ctypes.data_as(i64p), lb.ctypes.data_as(i64p), lo.ctypes.data_as(i64p), _dp(lv))
         return lr, lb, lo, lv
+
+    def eval_move(self, pop, i_pcut=1, log=True):
+        """One pass's Code Block 2 per state of `pop` (HipBackend.eval_move's states): the prologue of particle_loop, the time cut of
+        the pass on the given acctime, then the oracle's code_block_2 once, with the RNG key of particle k + 1 of pcut i_pcut.
+        Returns out [n][18], the packed word [n] (include/mcs.h, mcs_eval_move; the device's own fields stay 0) and, with log, every
+        deposit of the walk as arrays (state index, buffer: 0 fp64 tallies / 1 int64 tallies, offset, value), in the order made."""
+        n = pop.n
+        out = np.zeros((n, 18))
+        word = np.zeros(n, dtype=np.uint64)
+        s = pop.soa()
+        self._chk(self.lib.orc_eval_move(self.h, int(i_pcut), n, ct.byref(s), _dp(out), word.ctypes.data_as(ct.POINTER(ct.c_uint64)),
+                                         int(bool(log))))
+        if not log:
+            return out, word, None
+        m = int(self.lib.orc_tally_log(self.h, 0, None, None, None, None))
+        i64p = ct.POINTER(ct.c_int64)
+        lr, lb, lo, lv = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64), np.zeros(m)
+        self.lib.orc_tally_log(self.h, m, lr.ctypes.data_as(i64p), lb.ctypes.data_as(i64p), lo.ctypes.data_as(i64p), _dp(lv))
+        return out, word, (lr, lb, lo, lv)
+
+    def zone_search(self, x, fwd, i_grid):
+        """The bare zone search of all_flux! as the reference states it: forward findnext(>(x)) - 1, backward findprev(<=(x)), -1 off
+        the grid (zero-based indices into the n_grid + 2 grid entries)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        f = np.ascontiguousarray(fwd, dtype=np.uint8)
+        g = np.ascontiguousarray(i_grid, dtype=np.int32)
+        assert x.shape == f.shape == g.shape and x.ndim == 1
+        found = np.zeros(len(x), dtype=np.int32)
+        i32p = ct.POINTER(ct.c_int32)
+        self._chk(self.lib.orc_zone_search(self.h, len(x), _dp(x), f.ctypes.data_as(ct.POINTER(ct.c_uint8)), g.ctypes.data_as(i32p),
+                                           found.ctypes.data_as(i32p)))
+        return found
