@@ -430,6 +430,28 @@ int mcs_dndp_cr(mcs_ctx* ctx, const mcs_consumer_in* in, double* dNdp, int64_t* 
 /* thermo_calcs (src/thermo_calcs.jl:30-352) on the resident psd / therm_pf / num_crossings.
  * Outputs: host [n_grid] each. */
 int mcs_thermo_calcs(mcs_ctx* ctx, const mcs_consumer_in* in, double* P_par, double* P_perp, double* energy_density);
+/* K10: dN/dp of the particles that LEAVE the shock, from the two escape slabs of the tallies (the reference's print_dNdp_esc call at
+ * src/ion_finalize.jl:65-68 has no body; the slabs are binned and weighted as psd is, so this is get_dNdp_cr of one zone whose slab
+ * is a door's, up to and including dN -> dN/dp, particle_counter.jl:295-304, without the zone normalisation: a door has no volume).
+ *   door 0: esc_psd_up (upstream free-escape boundary and p_max), door 1: esc_psd_down (the downstream end);
+ *   frame 0: the shock frame, frame 1: the plasma frame of the door, Lorentz factor gam_pf[door] (beta by the rule of
+ *   transformers.jl:639, 0 below 1.000001), frame 2: the ISM frame, in->gam0.
+ * It reads mom_log_cgs, mom_edge_cgs, cos_edge, rest_energy and gam0 of `in`; gam_pf: host [2], each >= 1.
+ * dNdp: host [2][3][nmom+2] (door, frame); entry nmom+1 of every row is 1e-99, a bin whose dN is below 1e-66 is 1e-99.
+ * number: host [2][3], the row's dN summed over the bins 0..nmom in ascending order, before the division by the bin widths.
+ * diag: host [2][2] or null, per door the cells skipped on identify_corners error paths and the bin searches that left the table,
+ * both frames 1 and 2 counted, as mcs_dndp_cr counts them.
+ * A slab is [201][201] with the momentum index fastest, whatever the binning; only ip < nmom+2, jtheta < ntht+2 are ever written,
+ * and nothing else is read.  Cells, thresholds and the spreading of a cell over the bins are those of mcs_dndp_cr.
+ * ORDER OF THE ADDS (normative; no floating-point atomics, so every call on the same tallies gives the same bits):
+ *   frames 1, 2: every angle row j = 0..ntht has a partial histogram R_j[l] that starts at 0.0 and takes the parts of its lit cells
+ *   with ip ascending (a cell's parts in the order triangular_distribution! makes them);
+ *   dN[l] = ((0.0 + R_0[l]) + R_1[l]) + ... + R_ntht[l];
+ *   frame 0: dN[l] = the cells > 0 of column l added to 0.0 with jtheta = 0..ntht+1 ascending;
+ *   number = ((0.0 + dN[0]) + dN[1]) + ... + dN[nmom].
+ * The result also stays on the device, in a buffer that no other call writes, for the escape sample of the ensemble statistics
+ * (below); mcs_begin_species and that sample invalidate it. */
+int mcs_dndp_esc(mcs_ctx* ctx, const mcs_consumer_in* in, const double* gam_pf, double* dNdp, double* number, int64_t* diag);
 
 /* ---- photon post-processing: the synchrotron fold of src/synch_emission.jl:27-171 over the plasma-frame
  * dN/dp of an electron species (frame 2 of mcs_dndp_cr), for every grid zone with the zone's field of the grid tables.
@@ -667,6 +689,27 @@ typedef struct mcs_ens_products_layout {
 int mcs_ens_products_get_layout(const mcs_params* p, mcs_ens_products_layout* out);      /* needs no GPU */
 int mcs_ens_set_slope_window(mcs_ens* ens, int l_lo, int l_hi, const double* x_log);
 int mcs_ens_add_products(mcs_ens* ens, mcs_ctx* src, int species_slot);
+
+/* ---- escape sample: error bars of the spectra of the escaping particles.  Every species slot s has a third companion, the ESCAPE
+ * slot MCS_ENS_ESCAPE(s), which behaves as its products slot does in the count, read, merge, summarize, summarize-merged and compare
+ * calls (vectors allocated at the first sample; reads of a slot that never took one are refused).  The sample holds
+ * 6 NM + 12 doubles (NM = nmom + 2), mcs_ens_escape_layout:
+ *   dNdp    [2][3][NM]  door, frame: the last mcs_dndp_esc on the context, as that call left it on the device
+ *   number  [2][3]      likewise
+ *   slope   [2][3]      the slope of each dNdp row over the accumulator's slope window, by the rule of the products sample
+ *                       (valid bin: dN/dp > 1e-99; fewer than three valid bins: NaN)
+ * mcs_ens_add_escape: refused unless mcs_dndp_esc has run on src since its last mcs_begin_species and since the last escape sample
+ * taken from it, without a slope window, and for what mcs_ens_add_species refuses.  Queued on src's stream behind the accumulator's
+ * event, no host synchronisation.  The slope window is fixed from the first products OR escape sample on, and the window rules of
+ * merge, merged summary and comparison hold for escape slots as for products slots. */
+#define MCS_ENS_ESCAPE(s) ((s) | (1 << 27))
+typedef struct mcs_ens_escape_layout {
+  int64_t dNdp, number, slope;                              /* offsets, in doubles */
+  int64_t row_n;                                            /* nmom + 2: the length of a dNdp row; number and slope have 6 words */
+  int64_t total;
+} mcs_ens_escape_layout;
+int mcs_ens_escape_get_layout(const mcs_params* p, mcs_ens_escape_layout* out);      /* needs no GPU */
+int mcs_ens_add_escape(mcs_ens* ens, mcs_ctx* src, int species_slot);
 
 /* ---- photons sample: error bars of the photon spectra at Earth.  A shell spectrum is a sum over zones, slices and processes: its
  * variance does not follow from per-cell variances, so the spectrum itself is sampled once per iteration, from what

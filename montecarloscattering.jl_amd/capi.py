@@ -103,6 +103,13 @@ class McsEnsPhotonsLayout(ct.Structure):
     _fields_ = [(name, ct.c_int64) for name in ("synch", "ic", "pion", "total_section", "n_synch", "n_ic", "n_pion", "n_pts", "rows", "total")]
 
 
+class McsEnsEscapeLayout(ct.Structure):
+    """`mcs_ens_escape_layout`: offsets of the three parts of an escape sample and the length of a dN/dp row (include/mcs.h,
+    "escape sample")."""
+    _fields_ = [(name, ct.c_int64) for name in ("dNdp", "number", "slope", "row_n", "total")]
+
+
+ENS_ESCAPE_BIT = 1 << 27        # MCS_ENS_ESCAPE(s) = s | ENS_ESCAPE_BIT
 ENS_PHOTONS_BIT = 1 << 29       # MCS_ENS_PHOTONS(s) = s | ENS_PHOTONS_BIT
 ENS_PHOTONS_ALL = 1 << 28       # MCS_ENS_PHOTONS_ALL: the source slot, one per accumulator
 
@@ -344,6 +351,7 @@ def load_library() -> ct.CDLL:
         "mcs_get_layout": (i32, [ct.POINTER(McsParams), c_int64_p]),
         "mcs_dndp_cr": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_int64_p]),
         "mcs_thermo_calcs": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_double_p, c_double_p]),
+        "mcs_dndp_esc": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_double_p, c_double_p, c_int64_p]),
         "mcs_photon_synch": (i32, [vp, c_double_p, c_double_p, dbl, i32, dbl, dbl, c_double_p, c_double_p]),
         "mcs_run_pcuts_fused": (i32, [vp, i32, i32, c_int64_p, c_int64_p, c_int64_p, c_int64_p, c_double_p]),
         "mcs_run_pcuts_pipelined": (i32, [vp, i32, i32, c_int64_p, ct.c_int64, ct.c_int64, c_int64_p, c_int64_p, c_int64_p, c_double_p, c_int64_p]),
@@ -381,6 +389,8 @@ def load_library() -> ct.CDLL:
         "mcs_ens_add_photons_all": (i32, [vp]),
         "mcs_ens_drop_pending_photons": (i32, [vp]),
         "mcs_ens_compare": (i32, [vp, i32, vp, i32, i32, ct.POINTER(McsEnsCmpRange), ct.POINTER(McsEnsDifference)]),
+        "mcs_ens_escape_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsEnsEscapeLayout)]),
+        "mcs_ens_add_escape": (i32, [vp, vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -438,4 +448,6 @@ EXPORTED_SYMBOLS += [
 EXPORTED_SYMBOLS += ["mcs_photon_observe", "mcs_ens_photons_get_layout", "mcs_ens_set_photon_layout", "mcs_ens_add_photons"]
 # the source sample: the photon spectrum summed over species
 EXPORTED_SYMBOLS += ["mcs_ens_add_photons_deposit", "mcs_ens_add_photons_all", "mcs_ens_drop_pending_photons"]
+# the spectra of the escaping particles (K10) and their sample
+EXPORTED_SYMBOLS += ["mcs_dndp_esc", "mcs_ens_escape_get_layout", "mcs_ens_add_escape"]
 PHOTON_PROCESS = {"synch": 0, "ic": 1, "pion": 2}      # MCS_PHOTON_SYNCH, _IC, _PION

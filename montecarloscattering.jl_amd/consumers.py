@@ -161,6 +161,34 @@ def ion_finalize(prob, backend, i_ion: int, therm_from_hist: bool = True) -> Ion
     return IonFinal(dndp, tabs.zone_pop, ppar, pperp, edens, diag)
 
 
+@dataclasses.dataclass
+class EscapeSpectra:
+    """dN/dp of the particles that leave the shock, per door (0: the upstream free-escape boundary and p_max, 1: the downstream end)
+    and frame (0: shock, 1: the door's plasma frame, 2: ISM).  Not normalised to a volume: a door has none."""
+    dndp: np.ndarray             # [2][3][nmom+2]; entry nmom+1 and every empty bin 1e-99
+    number: np.ndarray           # [2][3]: the summed weight of each row, before the division by the bin widths
+    diag: np.ndarray             # [2][2]: per door, cells skipped on identify_corners error paths and bin searches that left the table
+    gam_pf: np.ndarray           # [2]: the Lorentz factor of each door's plasma frame
+    mom_edge_cgs: np.ndarray     # [nmom+2]
+
+
+def escape_gam_pf(prob) -> np.ndarray:
+    """The flow the escaping particles leave behind: at the upstream free-escape boundary and far downstream."""
+    P = prob.params
+    return np.array([prob.gam_sf[P.i_grid_feb], prob.gam_sf[P.n_grid]], dtype=np.float64)
+
+
+def escape_spectra(prob, backend, i_ion: int, gam_pf=None) -> EscapeSpectra:
+    """The escape slabs of the backend's resident tallies through get_dNdp_cr's rebinning (the reference's print_dNdp_esc,
+    src/ion_finalize.jl:65-68, which has no body there)."""
+    if not hasattr(backend, "dndp_esc"):
+        raise ValueError("escape_spectra: the backend has no dndp_esc (the escape spectra are made on the device, K10; there is no host twin)")
+    tabs = consumer_tables(prob, i_ion)
+    g = escape_gam_pf(prob) if gam_pf is None else np.ascontiguousarray(gam_pf, dtype=np.float64)
+    dndp, number, diag = backend.dndp_esc(tabs, g)
+    return EscapeSpectra(dndp, number, diag, g, tabs.mom_edge_cgs)
+
+
 # ---- photon post-processing (SURVEY.md 8(f-4)) -------------------------------------------------------------------------
 # photon_calcs.jl:11-19: the common energy grid of the emission spectra
 PHOTON_E_MIN_MEV = 1.0e-13

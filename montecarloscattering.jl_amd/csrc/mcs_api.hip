@@ -171,6 +171,10 @@ struct mcs_ctx {
   // d_cscratch and d_c2d (consumers_ready only sizes d_cout, whose size never changes), the photon folds stage their inputs in d_stage and
   // write d_pemis (below).
   bool have_cout_dndp = false, have_cout_thermo = false;
+  // K10: what the last mcs_dndp_esc left, dNdp [2][3][nmom+2] then number [2][3]; have_esc: a whole result since the last
+  // mcs_begin_species and the last escape sample of the ensemble statistics.  Only that call writes it, its row scratch and its counts.
+  DevBuf<double> d_esc_out, d_esc_rows; DevBuf<unsigned int> d_esc_rowdiag; DevBuf<unsigned long long> d_esc_diag;
+  bool have_esc = false;
   DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
   // K9, per process (MCS_PHOTON_SYNCH / _IC / _PION): d_pemis the emis[n_grid][n_photon] its fold left (pemis_n: that n_photon, 0 =
   // nothing), d_pobs the [n_shells+1][n] of the last mcs_photon_observe (pobs_n: its n, 0 = nothing; pobs_shells).  Only those calls
@@ -449,6 +453,7 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
   c->i_iter = i_iter; c->i_ion = i_ion; c->aa = aa; c->zzq = zz * MCS_QCGS; c->m = aa * MCS_MP; c->mc = c->m * MCS_C;
   c->pmax_cutoff = pmax_cutoff; c->density = density; c->ewf = ewf;
   c->have_cout_dndp = c->have_cout_thermo = false;
+  c->have_esc = false;
   c->photon_flags_clear();
   if (fold_replicas(c)) return 1;      // (the previous species' replicas, before its histograms are cleared)
   const long long npsd = c->L.psd_stride_zone * P.n_grid;
@@ -1583,6 +1588,38 @@ int mcs_dndp_cr(mcs_ctx* c, const mcs_consumer_in* in, double* dNdp, int64_t* di
   return 0;
 }
 
+int mcs_dndp_esc(mcs_ctx* c, const mcs_consumer_in* in, const double* gam_pf, double* dNdp, double* number, int64_t* diag) {
+  MCS_ENTER(c);
+  if (consumers_ready(c, in, "mcs_dndp_esc")) return 1;
+  if (fold_replicas(c)) return 1;
+  if (!in->mom_log_cgs || !in->mom_edge_cgs || !in->cos_edge || !gam_pf || !dNdp || !number) return fail("mcs_dndp_esc: null table");
+  const int NM = c->P.num_psd_mom_bins + 2, NT = c->P.num_psd_tht_bins + 2;
+  if (NM > MCS_PSD_MAX + 1 || NT > MCS_PSD_MAX + 1) return fail("mcs_dndp_esc: more PSD bins than an escape slab holds");
+  if (!(gam_pf[0] >= 1) || !(gam_pf[1] >= 1) || !(in->gam0 >= 1)) return fail("mcs_dndp_esc: a Lorentz factor below 1");
+  c->have_esc = false;
+  const size_t n_out = (size_t)6 * NM + 6;
+  if (reserve(c->d_esc_out, (long long)n_out) || reserve(c->d_esc_rows, 4LL * NT * NM) || reserve(c->d_esc_rowdiag, 8LL * NT) ||
+      reserve(c->d_esc_diag, 4))
+    return 1;
+  std::vector<double> h((size_t)(2 * NM + NT));
+  memcpy(h.data(), in->mom_log_cgs, sizeof(double) * NM);
+  memcpy(h.data() + NM, in->mom_edge_cgs, sizeof(double) * NM);
+  memcpy(h.data() + 2 * NM, in->cos_edge, sizeof(double) * NT);
+  HIPCHK(hipMemcpyAsync(c->d_ctab, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(mcs_launch_dndp_esc(&c->P, c->d_T + c->L.esc_psd_up, c->d_ctab, in->rest_energy, gam_pf, in->gam0, c->d_esc_rows, c->d_esc_rowdiag,
+                             c->d_esc_out, c->d_esc_diag, c->stream));
+  std::vector<double> o(n_out);
+  unsigned long long hd[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(o.data(), c->d_esc_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hd, c->d_esc_diag, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  memcpy(dNdp, o.data(), sizeof(double) * 6 * NM);
+  memcpy(number, o.data() + 6 * NM, sizeof(double) * 6);
+  if (diag) for (int q = 0; q < 4; ++q) diag[q] = (int64_t)hd[q];
+  c->have_esc = true;
+  return 0;
+}
+
 int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, double* P_perp, double* energy_density) {
   MCS_ENTER(c);
   if (consumers_ready(c, in, "mcs_thermo_calcs")) return 1;
@@ -1781,13 +1818,15 @@ int mcs_photon_observe(mcs_ctx* c, int process, int n_photon, const double* emis
 int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
   MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
-  *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo, {}, {}, {}};
+  *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo, {}, {}, {},
+                    c->d_esc_out, c->have_esc};
   for (int p = 0; p < 3; ++p) { out->pobs[p] = c->d_pobs[p]; out->pobs_n[p] = c->pobs_n[p]; out->pobs_shells[p] = c->pobs_shells[p]; }
   return 0;
 }
 void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; c->photon_flags_clear(); }
 void mcs_ctx_view_products_taken(mcs_ctx* c) { c->have_cout_dndp = c->have_cout_thermo = false; }
 void mcs_ctx_view_photons_taken(mcs_ctx* c) { c->photon_flags_clear(); }
+void mcs_ctx_view_escape_taken(mcs_ctx* c) { c->have_esc = false; }
 int mcs_ctx_view_fail(const char* msg) { return fail(msg); }
 
 }  // extern "C"

@@ -99,9 +99,10 @@ typedef __attribute__((address_space(1))) double gdbl;
 __device__ __forceinline__ void c_ladd(double* p, double v) { (void)__builtin_amdgcn_ds_atomic_fadd_f64((ldbl*)p, v); }
 __device__ __forceinline__ void c_gadd(double* p, double v) { (void)__builtin_amdgcn_global_atomic_fadd_f64((gdbl*)p, v); }
 
-// triangular_distribution! with i_approx = 2 (src/transformers.jl:209-312), adds into LDS dN
-__device__ void c_triangular(double* dN, double p_hi, double p_lo, double clo_pt, double chi_pt, double w, int l_lo, int l_hi,
-                             const double* lb, int nmax1) {
+// triangular_distribution! with i_approx = 2 (src/transformers.jl:209-312); add(&dN[l], part) is how a part joins its bin
+template <class Add>
+__device__ __forceinline__ void c_triangular_to(Add add, double* dN, double p_hi, double p_lo, double clo_pt, double chi_pt, double w, int l_lo,
+                                                int l_hi, const double* lb, int nmax1) {
   const double length_tot = 1 / (p_hi - p_lo);
   const double ct_height = 2 * w / length_tot;
   double p_bottom = p_lo;
@@ -111,14 +112,14 @@ __device__ void c_triangular(double* dN, double p_hi, double p_lo, double clo_pt
   double fractional_area = 0;
   for (int l = l_lo; l <= l_hi; ++l) {
     if (l + 1 > nmax1) break;
-    if (p_hi < lb[l_lo + 1]) { c_ladd(&dN[l], w); break; }
+    if (p_hi < lb[l_lo + 1]) { add(&dN[l], w); break; }
     const double top = lb[l + 1];
     if (top <= p_peak) {
       const double p_base = top - p_bottom;
       const double rh = (top - p_lo) * p_denom_lo * ct_height;
       const double lh = p_bottom == p_lo ? 0.0 : (p_bottom - p_lo) * p_denom_lo * ct_height;
       const double part = p_base / 2 * (lh + rh);
-      c_ladd(&dN[l], part);
+      add(&dN[l], part);
       p_bottom = top;
       fractional_area += part;
       continue;
@@ -128,14 +129,20 @@ __device__ void c_triangular(double* dN, double p_hi, double p_lo, double clo_pt
       const double lh = p_base * p_denom_hi * ct_height;
       const double missing = p_base / 2 * lh;
       const double part = (w - fractional_area) - missing;
-      c_ladd(&dN[l], part);
+      add(&dN[l], part);
       p_bottom = top;
       fractional_area += part;
       continue;
     }
-    c_ladd(&dN[l], w - fractional_area);
+    add(&dN[l], w - fractional_area);
     break;
   }
+}
+
+// ... into the LDS histogram of a workgroup (ds_add_f64)
+__device__ void c_triangular(double* dN, double p_hi, double p_lo, double clo_pt, double chi_pt, double w, int l_lo, int l_hi,
+                             const double* lb, int nmax1) {
+  c_triangular_to([](double* p, double v) { c_ladd(p, v); }, dN, p_hi, p_lo, clo_pt, chi_pt, w, l_lo, l_hi, lb, nmax1);
 }
 
 struct ConsArgs {
@@ -429,6 +436,113 @@ __global__ void __launch_bounds__(256) mcs_k_photon_ic(const double* __restrict_
   }
 }
 
+// ---- K10: dN/dp of the escaping particles (the reference's print_dNdp_esc call, src/ion_finalize.jl:65-68, has no body; its slabs
+// are binned and weighted as psd is, so this is get_dNdp_cr, particle_counter.jl:29-304, of one "zone" whose slab is a door's) -----
+// A door's slab is esc[ip + ESC_STRIDE * jtheta]; only ip < nmom+2, jtheta < ntht+2 are ever written.  Door 0: esc_psd_up, door 1:
+// esc_psd_down, which follows it in the tally buffer.  Two launches, no floating-point atomics, one fixed order of the adds
+// (include/mcs.h): the results are the same bits in every call.
+#define ESC_STRIDE (MCS_PSD_MAX + 1)
+#define ESC_ROWS_THREADS 64
+
+struct EscArgs {
+  const double* esc;        // tallies + L.esc_psd_up: [2][ESC_STRIDE][ESC_STRIDE]
+  const double *mom_log, *mom_edge, *cos_edge;
+  double rest_energy;
+  double gam[2][2];         // [door][frame - 1]: the door's plasma frame, the ISM frame
+  int nm, nt;
+  double* rows;             // scratch [2 doors][2 frames][nt+2][nm+2]: R_j of the header
+  unsigned int* row_diag;   // scratch [2][2][nt+2][2]
+  double* out;              // dNdp [2][3][nm+2] | number [2][3]
+  unsigned long long* diag; // [2][2]
+};
+
+// One lane per (door, frame 1 or 2, angle row j <= nt): it walks the row's cells with i ascending and adds their parts into its own
+// row of the scratch, which it zeroes first.  The transformed right corners of cell i are the left corners of cell i + 1 (the same
+// operations on the same edges: the same bits), so a lit cell behind a lit cell costs two corners instead of four.
+__global__ void __launch_bounds__(ESC_ROWS_THREADS) mcs_k_dndp_esc_rows(EscArgs a) {
+  __shared__ double s_lb[KC_MAXB], s_pe[KC_MAXB], s_ce[KC_MAXB];
+  const int nm = a.nm, nt = a.nt, NM = nm + 2, NT = nt + 2;
+  for (int i = threadIdx.x; i < NM; i += blockDim.x) { s_lb[i] = a.mom_log[i]; s_pe[i] = a.mom_edge[i]; }
+  for (int i = threadIdx.x; i < NT; i += blockDim.x) s_ce[i] = a.cos_edge[i];
+  __syncthreads();
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= 4 * (nt + 1)) return;
+  const int j = q % (nt + 1), df = q / (nt + 1), door = df >> 1, f = df & 1;
+  const double* slab = a.esc + (long long)door * ESC_STRIDE * ESC_STRIDE + (long long)ESC_STRIDE * j;
+  double* R = a.rows + ((long long)df * NT + j) * NM;
+  for (int l = 0; l < NM; ++l) R[l] = 0.0;
+  const double gam = a.gam[door][f];
+  const double beta = gam >= 1.000001 ? __builtin_sqrt(1 - 1 / (gam * gam)) : 0.0;
+  unsigned int n_skip = 0, n_clamp = 0;
+  double pts[4], cts[4];
+  int i_right = -1;                               // pts / cts [1] and [3] hold the corners at momentum edge i_right
+  for (int i = 0; i <= nm; ++i) {
+    const double v = slab[i];
+    if (v < 1.0e-66) continue;
+    const double w = v / gam;
+    if (i_right == i) { pts[0] = pts[1]; cts[0] = cts[1]; pts[2] = pts[3]; cts[2] = cts[3]; }
+    else {
+      c_corner(gam, beta, a.rest_energy, s_pe[i], s_ce[j], pts[0], cts[0]);
+      c_corner(gam, beta, a.rest_energy, s_pe[i], s_ce[j + 1], pts[2], cts[2]);
+    }
+    c_corner(gam, beta, a.rest_energy, s_pe[i + 1], s_ce[j], pts[1], cts[1]);
+    c_corner(gam, beta, a.rest_energy, s_pe[i + 1], s_ce[j + 1], pts[3], cts[3]);
+    i_right = i + 1;
+    double p_lo, p_hi, clo, chi;
+    if (!c_identify(pts, cts, p_lo, p_hi, clo, chi)) { ++n_skip; continue; }
+    int l_lo = -1;
+    {
+      int lo = 0, hi = NM;                        // smallest l in [0, NM) with s_lb[l] > p_lo, NM if there is none
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (s_lb[mid] > p_lo) hi = mid; else lo = mid + 1; }
+      if (lo < NM) l_lo = lo - 1;
+    }
+    if (l_lo < 0) { l_lo = nm; ++n_clamp; }
+    int l_hi = -1;
+    for (int l = l_lo; l < NM; ++l) if (s_lb[l] >= p_hi) { l_hi = l; break; }
+    if (l_hi < 0) { l_hi = nm; ++n_clamp; }
+    c_triangular_to([](double* p, double x) { *p = *p + x; }, R, p_hi, p_lo, clo, chi, w, l_lo, l_hi, s_lb, nm + 1);
+  }
+  a.row_diag[((long long)df * NT + j) * 2] = n_skip;
+  a.row_diag[((long long)df * NT + j) * 2 + 1] = n_clamp;
+}
+
+// One workgroup: per door and frame the rows join per bin with j ascending (frame 0: the theta-ascending column sum of the slab's
+// written rows, as mcs_k_dndp_cr has it), the number is the serial sum of the bins, then dN -> dN/dp (particle_counter.jl:295-304).
+__global__ void __launch_bounds__(256) mcs_k_dndp_esc_join(EscArgs a) {
+  __shared__ double s_dn[6][KC_MAXB];
+  const int nm = a.nm, nt = a.nt, NM = nm + 2, NT = nt + 2;
+  for (int q = threadIdx.x; q < 6 * NM; q += blockDim.x) {
+    const int l = q % NM, dm = q / NM, door = dm / 3, m = dm % 3;
+    double acc = 0.0;
+    if (m == 0) {
+      const double* slab = a.esc + (long long)door * ESC_STRIDE * ESC_STRIDE;
+      for (int j = 0; j < NT; ++j) { const double v = slab[l + ESC_STRIDE * j]; if (v > 0) acc += v; }
+    } else {
+      const double* rows = a.rows + (long long)(door * 2 + (m - 1)) * NT * NM;
+      for (int j = 0; j <= nt; ++j) acc = acc + rows[(long long)j * NM + l];
+    }
+    s_dn[dm][l] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    double n = 0.0;
+    for (int l = 0; l <= nm; ++l) n = n + s_dn[threadIdx.x][l];
+    a.out[6 * NM + threadIdx.x] = n;
+  }
+  if (threadIdx.x >= 64 && threadIdx.x < 68) {
+    const int q = threadIdx.x - 64, door = q >> 1, which = q & 1;
+    unsigned long long n = 0ull;
+    for (int f = 0; f < 2; ++f)
+      for (int j = 0; j <= nt; ++j) n += a.row_diag[((long long)(door * 2 + f) * NT + j) * 2 + which];
+    a.diag[q] = n;
+  }
+  for (int q = threadIdx.x; q < 6 * NM; q += blockDim.x) {
+    const int l = q % NM, dm = q / NM;
+    const double d = s_dn[dm][l];
+    a.out[q] = (l > nm || d < 1.0e-66) ? 1.0e-99 : d / (a.mom_edge[l + 1] - a.mom_edge[l]);
+  }
+}
+
 }  // namespace
 
 // Host-callable launchers (pointers are device pointers; tables were uploaded by the caller)
@@ -460,6 +574,24 @@ extern "C" hipError_t mcs_launch_thermo(const mcs_params* P, const double* psd, 
   a.rest_energy = rest_energy; a.mc = mc; a.n0 = n0; a.therm_from_hist = therm_from_hist;
   a.scratch = scratch; a.out_par = out3; a.out_perp = out3 + ng; a.out_edens = out3 + 2 * ng;
   hipLaunchKernelGGL(mcs_k_thermo, dim3(P->n_grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t mcs_launch_dndp_esc(const mcs_params* P, const double* esc, const double* tabs /*mom_log|mom_edge|cos_edge*/,
+                                          double rest_energy, const double gam_pf[2], double gam0, double* rows, unsigned int* row_diag,
+                                          double* out, unsigned long long* diag, hipStream_t st) {
+  EscArgs a{};
+  const int NM = P->num_psd_mom_bins + 2;
+  a.esc = esc; a.mom_log = tabs; a.mom_edge = tabs + NM; a.cos_edge = tabs + 2 * NM;
+  a.rest_energy = rest_energy;
+  for (int d = 0; d < 2; ++d) { a.gam[d][0] = gam_pf[d]; a.gam[d][1] = gam0; }
+  a.nm = P->num_psd_mom_bins; a.nt = P->num_psd_tht_bins;
+  a.rows = rows; a.row_diag = row_diag; a.out = out; a.diag = diag;
+  const int lanes = 4 * (a.nt + 1);
+  hipLaunchKernelGGL(mcs_k_dndp_esc_rows, dim3((lanes + ESC_ROWS_THREADS - 1) / ESC_ROWS_THREADS), dim3(ESC_ROWS_THREADS), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mcs_k_dndp_esc_join, dim3(1), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

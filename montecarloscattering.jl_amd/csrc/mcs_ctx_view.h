@@ -21,6 +21,10 @@ struct McsCtxView {
   // (pobs_n: that n, 0 = nothing since the last mcs_begin_species, tally write or photons sample)
   const double* pobs[3];
   int pobs_n[3], pobs_shells[3];
+  // what the last mcs_dndp_esc left on the device, dNdp [2][3][nmom+2] then number [2][3] (null before the first call), and whether
+  // it is a whole result since the last mcs_begin_species / escape sample
+  const double* esc_out;
+  bool have_esc;
 };
 
 extern "C" {
@@ -35,6 +39,8 @@ void mcs_ctx_view_tallies_written(mcs_ctx* ctx);
 void mcs_ctx_view_products_taken(mcs_ctx* ctx);
 // A photons sample has been queued from ctx's observed spectra: the folds and mcs_photon_observe have to run again before the next.
 void mcs_ctx_view_photons_taken(mcs_ctx* ctx);
+// An escape sample has been queued from ctx's mcs_dndp_esc result: that call has to run again before the next.
+void mcs_ctx_view_escape_taken(mcs_ctx* ctx);
 // Sets the message of the calling thread's last error (what the ABI's error call returns); returns 1.
 int mcs_ctx_view_fail(const char* msg);
 }

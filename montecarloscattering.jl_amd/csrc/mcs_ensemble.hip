@@ -13,7 +13,7 @@
 // last kernel that folds a range's partials in index order.  No atomics: the same state gives the same bits.
 // The comparison of two slots (mcs_ens_compare) is the same walk over the (mean, M2) pairs of both with a record of its own: the
 // four sweep kernels share one routine, walk, for which words a thread sees and in which order.
-// Host side: every slot of every kind -- species, iteration, products, photons, source -- is one Slot (count, mean, M2); decode reads
+// Host side: every slot of every kind -- species, iteration, products, photons, source, escape -- is one Slot (count, mean, M2); decode reads
 // a slot number's bits, slot_ref finds its Slot, reserve allocates it, merge_slot merges it, and plan_ranges checks the ranges of a
 // summary or comparison and lays out their blocks in one pass.
 // A context is seen through mcs_ctx_view.h; its stream carries the work, an event of the accumulator orders successive operations
@@ -660,6 +660,13 @@ void products_layout(const mcs_params* p, mcs_ens_products_layout* PL) {
   PL->total = o;
 }
 
+void escape_layout(const mcs_params* p, mcs_ens_escape_layout* XL) {
+  const int64_t nm = p->num_psd_mom_bins + 2;
+  XL->row_n = nm;
+  XL->dNdp = 0; XL->number = 6 * nm; XL->slope = 6 * nm + 6;
+  XL->total = 6 * nm + 12;
+}
+
 void photons_layout(int n_shells, const int n[3], int n_pts, mcs_ens_photons_layout* HL) {
   const int64_t rows = (int64_t)n_shells + 1;
   HL->rows = rows; HL->n_synch = n[0]; HL->n_ic = n[1]; HL->n_pion = n[2]; HL->n_pts = n_pts;
@@ -677,23 +684,26 @@ const char* photons_layout_error(int n_shells, const int n[3], const int start[3
 constexpr int PRODUCTS_BIT = 1 << 30;      // MCS_ENS_PRODUCTS
 constexpr int PHOTONS_BIT = 1 << 29;       // MCS_ENS_PHOTONS
 constexpr int PHOTONS_ALL = 1 << 28;       // MCS_ENS_PHOTONS_ALL
+constexpr int ESCAPE_BIT = 1 << 27;        // MCS_ENS_ESCAPE
 
-// The five kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
+// The six kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
 // to (s; not yet held against the accumulator's species slots, slot_ref does that; -1 for the iteration and the source slot).
 // A negative number has every high bit set: it is no companion slot, and is refused as a species slot outside the range.
 // The source slot has the photons slots' vector and layout rules; it is a kind of its own in a comparison.
-enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE };
-const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source"};
+enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, N_KINDS };
+const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape"};
 struct SlotId { Kind kind; int s; };
 SlotId decode(int slot, int n_slots) {
   if (slot == PHOTONS_ALL) return SlotId{SOURCE, -1};
   if (slot >= 0 && (slot & PRODUCTS_BIT) != 0) return SlotId{PRODUCTS, slot ^ PRODUCTS_BIT};
   if (slot >= 0 && (slot & PHOTONS_BIT) != 0) return SlotId{PHOTONS, slot ^ PHOTONS_BIT};
+  if (slot >= 0 && (slot & ESCAPE_BIT) != 0) return SlotId{ESCAPE, slot ^ ESCAPE_BIT};
   return slot == n_slots - 1 ? SlotId{ITERATION, -1} : SlotId{SPECIES, slot};
 }
 bool has_photon_vector(Kind k) { return k == PHOTONS || k == SOURCE; }
+bool has_window_vector(Kind k) { return k == PRODUCTS || k == ESCAPE; }      // (its sample holds slopes over the slope window)
 
-// What every slot is: the samples it has taken and its two vectors (those of a products, photons or source slot from its first
+// What every slot is: the samples it has taken and its two vectors (those of a products, photons, source or escape slot from its first
 // sample or merge on, nothing before)
 struct Slot { long long n = 0; DevBuf<double> mean, m2; };
 
@@ -726,7 +736,11 @@ struct mcs_ens {
   int win_lo = 0, win_hi = 0;                 // the slope window; none while x_log_h is empty
   std::vector<double> x_log_h;                // [nmom+1]
   DevBuf<double> x_log, slope;                // its device copy; the slopes of the sample being added [3][n_grid]
-  bool products_sampled = false;              // some products slot has taken a sample (or a merge): the window is fixed
+  bool products_sampled = false;              // some products or escape slot has taken a sample (or a merge): the window is fixed
+  // the escape slots, likewise (include/mcs.h, "escape sample"): XL.total doubles per vector; the slopes of the sample being added
+  mcs_ens_escape_layout XL;
+  std::vector<Slot> escape;
+  DevBuf<double> esc_slope;                   // [2][3]
   // the photons slots, likewise (include/mcs.h, "photons sample"): HL.total doubles per vector; no layout while ph_shells is 0
   mcs_ens_photons_layout HL{};
   int ph_shells = 0, ph_n[3] = {0, 0, 0}, ph_start[3] = {0, 0, 0}, ph_npts = 0;
@@ -742,16 +756,17 @@ struct mcs_ens {
   // the one way from a (checked) slot number to its record, and the length of the vectors of a kind
   Slot& at(SlotId id) {
     return id.kind == SOURCE ? source : id.kind == PHOTONS ? photons[(size_t)id.s] : id.kind == PRODUCTS ? products[(size_t)id.s]
+           : id.kind == ESCAPE ? escape[(size_t)id.s]
            : main[(size_t)(id.kind == ITERATION ? n_slots - 1 : id.s)];
   }
   long long len(Kind k) const {
-    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ITERATION ? E.it_total : E.sp_total;
+    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ITERATION ? E.it_total : E.sp_total;
   }
   // every slot number the accumulator has
   std::vector<int> slot_numbers() const {
     std::vector<int> all;
     for (int s = 0; s < n_slots; ++s) all.push_back(s);
-    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); }
+    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); all.push_back(s | ESCAPE_BIT); }
     all.push_back(PHOTONS_ALL);
     return all;
   }
@@ -783,11 +798,11 @@ int leave(mcs_ens* e, hipStream_t st) {
 }
 
 // What a count, read, summary or comparison call works on: the slot of that number, its kind and the length of its vectors
-// (which are null for a products, photons or source slot that was never sampled; n is then 0).
+// (which are null for a products, photons, source or escape slot that was never sampled; n is then 0).
 struct SlotRef { Kind kind; Slot* slot; long long len; };
 int slot_ref(mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
   const SlotId id = decode(slot, e->n_slots);
-  if ((id.kind == PRODUCTS || id.kind == PHOTONS) && id.s >= e->n_slots - 1)
+  if ((id.kind == PRODUCTS || id.kind == PHOTONS || id.kind == ESCAPE) && id.s >= e->n_slots - 1)
     return fail(who + ": " + KIND_NAME[id.kind] + " slot of slot " + std::to_string(id.s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
   if (id.kind == SPECIES && (slot < 0 || slot >= e->n_slots)) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
   *out = SlotRef{id.kind, &e->at(id), e->len(id.kind)};
@@ -958,6 +973,12 @@ int mcs_ens_products_get_layout(const mcs_params* p, mcs_ens_products_layout* ou
   return 0;
 }
 
+int mcs_ens_escape_get_layout(const mcs_params* p, mcs_ens_escape_layout* out) {
+  if (!p || !out) return fail("mcs_ens_escape_get_layout: null argument");
+  escape_layout(p, out);
+  return 0;
+}
+
 int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   if (!home || !out) return fail("mcs_ens_create: null argument");
   if (n_species_slots < 0 || n_species_slots > 4096) return fail("mcs_ens_create: n_species_slots outside 0..4096");
@@ -970,6 +991,8 @@ int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   products_layout(&v.P, &e->PL);
   e->products.resize((size_t)n_species_slots);
   e->photons.resize((size_t)n_species_slots);
+  escape_layout(&v.P, &e->XL);
+  e->escape.resize((size_t)n_species_slots);
   const mcs_layout& L = v.L;
   e->inc = IncRanges{{L.esc_flux, L.esc_energy_eff, L.spectra_coupled}, {L.px_esc_feb, L.weight_coupled, L.energy_transfer_pool}};
   e->n_slots = n_species_slots + 1;
@@ -1043,7 +1066,7 @@ int mcs_ens_add_iteration(mcs_ens* e, mcs_ctx* src) {
 int mcs_ens_set_slope_window(mcs_ens* e, int l_lo, int l_hi, const double* x_log) {
   const std::string who = "mcs_ens_set_slope_window";
   if (!e || !x_log) return fail(who + ": null argument");
-  if (e->products_sampled) return fail(who + ": a products slot has taken a sample; the window stays as it is");
+  if (e->products_sampled) return fail(who + ": a products or escape slot has taken a sample; the window stays as it is");
   const int nx = e->P.num_psd_mom_bins + 1;
   if (l_lo < 0 || l_hi > nx || l_hi - l_lo < 3)
     return fail(who + ": window [" + std::to_string(l_lo) + ", " + std::to_string(l_hi) + ") needs 0 <= l_lo, l_hi <= " + std::to_string(nx) +
@@ -1086,6 +1109,33 @@ int mcs_ens_add_products(mcs_ens* e, mcs_ctx* src, int slot) {
   sl.n += 1;
   e->products_sampled = true;
   mcs_ctx_view_products_taken(src);
+  return leave(e, v.stream);
+}
+
+int mcs_ens_add_escape(mcs_ens* e, mcs_ctx* src, int slot) {
+  const std::string who = "mcs_ens_add_escape";
+  if (!e || !src) return fail(who + ": null argument");
+  if (species_slot(e, who, slot, "only a species slot has an escape slot")) return 1;
+  if (!e->has_window()) return fail(who + ": no slope window (mcs_ens_set_slope_window)");
+  McsCtxView v;
+  if (view_of(e, src, who.c_str(), &v)) return 1;
+  if (!v.have_esc || !v.esc_out)
+    return fail(who + ": the context needs an mcs_dndp_esc since its last mcs_begin_species and its last escape sample");
+  const hipError_t a = e->esc_slope.reserve(6);
+  if (a != hipSuccess) return fail(who + ": hipMalloc: " + hipGetErrorString(a));
+  if (enter(e, v.stream)) return 1;
+  Slot& sl = e->escape[(size_t)slot];
+  if (reserve(sl, e->XL.total, who, v.stream)) return 1;
+  // the sample is the call's result (dNdp | number) as it lies on the device, then the six slopes of its rows
+  hipLaunchKernelGGL(mcs_k_ens_slope, dim3(1), dim3(ENS_THREADS), 0, v.stream, v.esc_out, e->x_log.get(), e->esc_slope.get(), 6LL, (int)e->XL.row_n,
+                     e->win_lo, e->win_hi);
+  ENSCHK(hipGetLastError());
+  hipLaunchKernelGGL(mcs_k_ens_add_products, dim3(grid_for(e->XL.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), v.esc_out,
+                     e->esc_slope.get(), (long long)e->XL.slope, (long long)e->XL.total, (double)(sl.n + 1));
+  ENSCHK(hipGetLastError());
+  sl.n += 1;
+  e->products_sampled = true;
+  mcs_ctx_view_escape_taken(src);
   return leave(e, v.stream);
 }
 
@@ -1189,12 +1239,12 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   McsCtxView v;
   if (mcs_ctx_view_get(dst->home, &v)) return 1;
   const std::vector<int> slots = dst->slot_numbers();
-  bool any[5] = {false, false, false, false, false};      // per kind: src has samples in a slot of it
+  bool any[N_KINDS] = {};      // per kind: src has samples in a slot of it
   for (int slot : slots) {
     const SlotId id = decode(slot, src->n_slots);
     any[id.kind] = any[id.kind] || src->at(id).n > 0;
   }
-  const bool any_products = any[PRODUCTS], any_photons = any[PHOTONS] || any[SOURCE];
+  const bool any_products = any[PRODUCTS] || any[ESCAPE], any_photons = any[PHOTONS] || any[SOURCE];
   if (any_products && !dst->has_window()) {
     hipError_t a = dst->x_log.reserve((long long)src->x_log_h.size());
     if (a == hipSuccess) a = dst->slope.reserve(3LL * dst->P.n_grid);
@@ -1282,7 +1332,7 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
   }
   SlotRef sr;
   if (slot_ref(a, who, slot, &sr)) return 1;
-  if (sr.kind == PRODUCTS)
+  if (has_window_vector(sr.kind))
     for (int k = 1; k < n_ens; ++k)
       for (int j = 0; j < k; ++j)
         if (windows_differ(ens[j], ens[k])) return fail(who + ": the accumulators' slope windows differ");
@@ -1343,8 +1393,8 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges == 0) return 0;
   if (!ranges || !out) return fail(who + ": null argument");
-  if (ra.kind == PRODUCTS) {
-    if (sa.n == 0 || sb.n == 0) return fail(who + ": a products slot has never taken a sample");
+  if (has_window_vector(ra.kind)) {
+    if (sa.n == 0 || sb.n == 0) return fail(who + (ra.kind == ESCAPE ? ": an escape" : ": a products") + " slot has never taken a sample");
     if (windows_differ(a, b)) return fail(who + ": the accumulators' slope windows differ");
   }
   if (has_photon_vector(ra.kind)) {

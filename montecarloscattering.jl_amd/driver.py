@@ -82,6 +82,7 @@ class RunResult:
     ensemble: object = None       # the ensemble statistics the run fed (run(ensemble=...), run_overlapped(ensemble=True)); ensemble.py
     convergence: object = None    # a Convergence: what run / run_overlapped(triggers=...) checked and where it stopped; None without triggers
     photons: object = None        # [consumers.ObservedSpectra], one per species, of the last iteration (run(photons=...)); None without
+    escape: object = None         # [(i_iter, i_ion, consumers.EscapeSpectra)] of every species end (run(escape=True)); None without
 
 
 @dataclasses.dataclass
@@ -637,6 +638,20 @@ def _photons_of_species(prob, be, i_ion, setup, ensemble):
     return ion_fin, obs
 
 
+def _species_escape(rs, be, i_iter, i_ion):
+    """The spectra of the particles that left the shock while species i_ion ran on `be` (run(escape=True); K10 on a HIP backend): from
+    the escape slabs of ITS tallies, which are per-species sections -- before the context's next begin_species clears them.  With an
+    ensemble, one escape sample into Ensemble.escape_slot(i_ion - 1)."""
+    if not rs.is_root:
+        return
+    spec = consumers.escape_spectra(rs.prob, be, i_ion)
+    rs.escape.append((i_iter, i_ion, spec))
+    if rs.ensemble is not None:
+        if not rs.ensemble.has_slope_window():
+            rs.ensemble.set_slope_window(0, rs.prob.params.num_psd_mom_bins + 1, ens.bin_centres_log10(rs.prob))
+        rs.ensemble.add_escape(be, i_ion - 1, spec)
+
+
 def _iteration_species(rs, i_iter, before_pcut):
     """The species of iteration i_iter in order: its transport (here, or with secondaries on the pool's threads as the
     scheduler places it), its merge into the primary if it ran on a secondary, its species end."""
@@ -645,6 +660,8 @@ def _iteration_species(rs, i_iter, before_pcut):
         for i_ion in range(1, n_sp + 1):
             _species_transport(rs, rs.backend, i_iter, i_ion, before_pcut, rs.stats, rs.empty_launches)
             _species_end(rs, 0, i_iter, i_ion)
+            if rs.do_escape:
+                _species_escape(rs, rs.backend, i_iter, i_ion)      # (after the ranks' merge: rank 0 holds the whole slabs)
             if rs.photons is not None:
                 _species_photons(rs, i_iter, i_ion)
         return
@@ -652,6 +669,8 @@ def _iteration_species(rs, i_iter, before_pcut):
         sched = _SpeciesScheduler(rs, pool, i_iter)
         for i_ion in range(1, n_sp + 1):
             k, out_stats, out_empty, t0, t1 = sched.result(i_ion)
+            if rs.do_escape:
+                _species_escape(rs, rs.ctxs[k], i_iter, i_ion)      # (the slabs do not travel with the running sums)
             if k > 0 and hasattr(rs.backend, "accumulate_tallies_from") and type(rs.ctxs[k]) is type(rs.backend):
                 rs.backend.accumulate_tallies_from(rs.ctxs[k])      # its running sums added to the primary's and cleared
             elif k > 0:
@@ -670,7 +689,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         first_iter: int = 1, iter_state=None, species_tallies: str = "full", final_full_read: bool = True,
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
         long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None,
-        ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1, photons=None) -> RunResult:
+        ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1, photons=None,
+        escape: bool = False) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -753,6 +773,13 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     sample, the ensemble takes that vector as one SOURCE sample into Ensemble.photons_all_slot (ensemble.py, "The source"; same parts,
     zones= and bins= as a photons slot).  Deposits left by an iteration that raised are dropped at the top of the next.  Triggers may
     name the source slot; without photons= they are refused like triggers on a photons slot.
+    escape: after every species' last pcut, on the context that transported it, consumers.escape_spectra: dN/dp of the particles that
+    left through the upstream free-escape boundary or p_max and through the downstream end, in the shock frame, the plasma frame at
+    that boundary and the ISM frame (K10 on a HIP backend).  RunResult.escape holds [(i_iter, i_ion, EscapeSpectra)].  With ensemble,
+    one ESCAPE sample per species and iteration goes into Ensemble.escape_slot(i_ion - 1) (ensemble.py, "Escape": dNdp, number,
+    slope; an ensemble without a slope window first gets one over all bins); triggers may name its parts, with
+    zones=Ensemble.escape_row(door, frame) for one door and frame and bins= for a momentum window of that row.
+    Refused: escape without finalize, a trigger on an escape slot without escape.
     """
     import torch
     comm = comm or Comm(False)
@@ -781,7 +808,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         n_pcuts=len(prob.pcuts) if max_pcuts is None else min(max_pcuts, len(prob.pcuts)), last_iter=first_iter + n_itrs - 1,
         verbose=verbose, gather_max=gather_max, skew_max=skew_max, fused_pcuts=fused_pcuts, fused_chunk=fused_chunk,
         long_draws=long_draws, long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
-        photons=photons, photon_spectra=[None] * len(cfg.species), last_ion_fin=None,
+        photons=photons, photon_spectra=[None] * len(cfg.species), last_ion_fin=None, do_escape=bool(escape), escape=[],
         G_f=None, G_i=None, G_pool=None, stats=[], per_species=[], local_steps=[], empty_launches=[], species_spans=[], iter_finals=[])
     # the step counters are never reset: this rank's running total.  A context that has run before (run() called again with
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
@@ -829,6 +856,10 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             if getattr(be, "device", None) != getattr(backend, "device", None):
                 raise ValueError("species_backends: every context must be on the primary's device")
     finalize = finalize or smoothing is not None
+    if escape and not finalize:
+        raise ValueError("escape: needs finalize=True (the escape spectra belong to the iteration's finalize step)")
+    if not escape and any(ens.Ensemble.is_escape(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on an escape slot needs escape=True (no sample would ever arrive)")
     if not finalize and any(ens.Ensemble.is_products(t.slot) for t in triggers):
         raise ValueError("triggers: a trigger on a products slot needs finalize=True (ion_finalize makes the products; no sample would ever arrive)")
     it_state = None
@@ -911,7 +942,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     return RunResult(rs.G_f, rs.G_i, rs.per_species, rs.stats, *_steps(rs.G_i, P.n_grid), rs.iter_finals, it_state,
                      rs.local_steps, rs.empty_launches, rs.species_spans, options, ensemble,
                      Convergence(checks, stopped_at, satisfied) if triggers else None,
-                     list(rs.photon_spectra) if photons is not None else None)
+                     list(rs.photon_spectra) if photons is not None else None, rs.escape if escape else None)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over
@@ -923,7 +954,7 @@ ACCUMULATED_OVER_ITERATIONS = ("esc_flux", "px_esc_feb", "energy_esc_feb", "esc_
 def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pcuts: Optional[int] = None,
                    on_iteration_end: Optional[Callable] = None, first_iter: int = 1,
                    blocks_per_launch: Optional[int] = None, ensemble: bool = False, triggers: Optional[list] = None,
-                   min_iterations: int = 2, check_every: int = 1, photons=None) -> RunResult:
+                   min_iterations: int = 2, check_every: int = 1, photons=None, escape: bool = False) -> RunResult:
     """The iterations of a run with a FIXED shock profile (smooth-shocks = false -- the stock mc_in.toml, BASELINE
     config[1]) are independent Monte-Carlo realisations: nothing an iteration computes enters the next one's transport
     (src/main_loops.jl:52-121: every tally the transport reads is reset at the top; the RNG keys carry i_iter).  Their
@@ -968,7 +999,10 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     taken inside the job where the products sample is taken.  Rounds, checks and the final merge then cover the photons slots and the
     source slot like every other; an ensemble gets consumers.stock_photon_layout(photons.n_shells).  RunResult.photons holds the
     spectra of the last iteration consumed.  Refused: a trigger on a photons slot or on the source slot without photons=.  None:
-    no spectra are made."""
+    no spectra are made.
+    escape: refused -- the escape spectra of run(escape=True) are left out of the overlapped path."""
+    if escape or any(ens.Ensemble.is_escape(t.slot) for t in (triggers or [])):
+        raise ValueError("escape: the overlapped run leaves the escape spectra out; use run(finalize=True, escape=True)")
     cfg, P = prob.cfg, prob.params
     n_itrs = n_itrs if n_itrs is not None else cfg.num_iterations
     K = len(backends)

@@ -46,6 +46,18 @@ vectors exist from its first sample on:
       counts it in n_nonfinite and a trigger over it is never met -- a slope trigger belongs on zones that the accelerated
       population reaches.  It is the slope of dN/dp, about -2.2 behind a strong shock, not the index of f(p).
 
+Escape (include/mcs.h, "escape sample"): the spectra of the particles that leave the shock, consumers.escape_spectra, sampled once per
+species and iteration by driver.run(finalize=True, escape=True, ensemble=...).  Every species slot s has a third companion, the escape
+slot `Ensemble.escape_slot(s)`, whose vectors exist from its first sample on.  Its parts have as first axis the row 3 * door + frame
+(door 0: upstream, 1: downstream; frame 0: shock, 1: the door's plasma frame, 2: ISM):
+
+  dNdp     [6][nmom+2]: dN/dp of the row
+  number   [6]: the row's summed weight
+  slope    [6]: the slope of the row over the slope window, by the products sample's rule
+
+zones=Ensemble.escape_row(door, frame) of a `Request` or `Trigger` selects one door and frame, bins= a momentum window of that dNdp
+row.  The slope window is shared with the products slots: it is fixed from the first products or escape sample on.
+
 Photons (include/mcs.h, "photons sample"): the photon spectra at Earth per photon shell, consumers.observed_spectra.  A shell spectrum is
 a sum over zones, slices in cos(theta) and processes, so its variance does not follow from per-cell variances either: every species
 slot s has a second companion, `Ensemble.photons_slot(s)`, sampled once per iteration (`add_photons`) and allocated at its first
@@ -131,6 +143,13 @@ ZONE_PARTS = ZONE_PARTS + PHOTON_NAMES
 BIN_PARTS = BIN_PARTS + PHOTON_NAMES
 PHOTONS_BIT = capi.ENS_PHOTONS_BIT        # photons slot of species slot s: s | PHOTONS_BIT (MCS_ENS_PHOTONS)
 PHOTONS_ALL = capi.ENS_PHOTONS_ALL        # the source slot: the photon spectrum summed over species (MCS_ENS_PHOTONS_ALL)
+# the parts of an escape slot, in the order of mcs_ens_escape_layout: first axis the row 3 * door + frame (zones=; Ensemble.escape_row),
+# dNdp's second the momentum bin (bins=)
+ESCAPE_NAMES = ("dNdp", "number", "slope")
+ESCAPE_ROWS = 6
+ZONE_PARTS = ZONE_PARTS + ESCAPE_NAMES
+BIN_PARTS = BIN_PARTS + ("dNdp",)
+ESCAPE_BIT = capi.ENS_ESCAPE_BIT          # escape slot of species slot s: s | ESCAPE_BIT (MCS_ENS_ESCAPE)
 
 
 class EnsLayout:
@@ -173,6 +192,11 @@ class EnsLayout:
         self.products_total = w
         self.products_fields = {name: off for name, (off, _) in self.products.items()}
         self.products_fields.update(dNdp_n=ng * nm, zone_n=ng, total=w)
+        # the escape sample: mirror of `mcs_ens_escape_get_layout`
+        self.escape: Dict[str, Tuple[int, tuple]] = {"dNdp": (0, (ESCAPE_ROWS, nm)), "number": (ESCAPE_ROWS * nm, (ESCAPE_ROWS,)),
+                                                     "slope": (ESCAPE_ROWS * nm + ESCAPE_ROWS, (ESCAPE_ROWS,))}
+        self.escape_total = ESCAPE_ROWS * nm + 2 * ESCAPE_ROWS
+        self.escape_fields = dict(dNdp=0, number=ESCAPE_ROWS * nm, slope=ESCAPE_ROWS * nm + ESCAPE_ROWS, row_n=nm, total=self.escape_total)
 
     def species_sample(self, f: np.ndarray, i: np.ndarray) -> np.ndarray:
         """The species sample of the tally buffers (f, i).  The marginals are serial sums in ascending index order, one index
@@ -252,9 +276,10 @@ def stats_over(samples):
 def _check_part(name: str, zones, bins=None):
     """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis, a bins
     window is a pair, comes with a single zone and the part has a bins axis."""
-    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES:
+    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES:
         raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}; "
-                         f"a products slot: {', '.join(PRODUCT_NAMES)}; a photons slot: {', '.join(PHOTON_NAMES)}")
+                         f"a products slot: {', '.join(PRODUCT_NAMES)}; a photons slot: {', '.join(PHOTON_NAMES)}; "
+                         f"an escape slot: {', '.join(ESCAPE_NAMES)}")
     if bins is not None:
         if name not in BIN_PARTS:
             raise ValueError(f"ensemble: {name!r} has no [zone][bins] shape; a bins window fits: {', '.join(BIN_PARTS)}")
@@ -626,6 +651,24 @@ class Ensemble:
     def is_photons(slot: int) -> bool:
         return slot >= 0 and not slot & PRODUCTS_BIT and bool(slot & PHOTONS_BIT)
 
+    def escape_slot(self, s: int) -> int:
+        """The slot number of the escape spectra of species slot s (MCS_ENS_ESCAPE)."""
+        if not 0 <= s < self.n_species:
+            raise ValueError(f"ensemble: slot {s} is no species slot (0..{self.n_species - 1}); only a species slot has an escape slot")
+        return int(s) | ESCAPE_BIT
+
+    @staticmethod
+    def is_escape(slot: int) -> bool:
+        return slot >= 0 and slot != PHOTONS_ALL and not slot & (PRODUCTS_BIT | PHOTONS_BIT) and bool(slot & ESCAPE_BIT)
+
+    @staticmethod
+    def escape_row(door: int, frame: int) -> Tuple[int, int]:
+        """zones= of one door (0: upstream, 1: downstream) and frame (0: shock, 1: the door's plasma frame, 2: ISM) of an escape
+        slot's parts: the row 3 * door + frame."""
+        if door not in (0, 1) or frame not in (0, 1, 2):
+            raise ValueError(f"ensemble: an escape slot has doors 0, 1 and frames 0, 1, 2, not door {door!r}, frame {frame!r}")
+        return 3 * door + frame, 3 * door + frame + 1
+
     photons_all_slot = PHOTONS_ALL     # the source slot, one per ensemble (MCS_ENS_PHOTONS_ALL)
 
     @staticmethod
@@ -657,7 +700,7 @@ class Ensemble:
         self.photon_layout = layout
 
     def _decode(self, slot: int) -> Tuple[str, Optional[int]]:
-        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons" or "source" -- the one place where
+        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source" or "escape" -- the one place where
         its bits are read; the index is None for the iteration and the source slot, and not yet checked (`_check_slot`)."""
         if self.is_photons_all(slot):
             return "source", None
@@ -665,6 +708,8 @@ class Ensemble:
             return "products", slot ^ PRODUCTS_BIT
         if self.is_photons(slot):
             return "photons", slot ^ PHOTONS_BIT
+        if self.is_escape(slot):
+            return "escape", slot ^ ESCAPE_BIT
         return ("iteration", None) if slot == self.iteration_slot else ("species", slot)
 
     def _kind(self, slot: int) -> str:
@@ -672,17 +717,17 @@ class Ensemble:
 
     def _describe(self, slot: int) -> str:
         kind, s = self._decode(slot)
-        if kind in ("products", "photons"):
+        if kind in ("products", "photons", "escape"):
             return f"the {kind} slot of species slot {s}"
         return f"species slot {s}" if kind == "species" else f"the {kind} slot"
 
     def names(self, slot: int):
         self._check_slot(slot)
-        return {"species": SPECIES_NAMES, "iteration": ITERATION_NAMES, "products": PRODUCT_NAMES}.get(self._kind(slot), PHOTON_NAMES)
+        return {"species": SPECIES_NAMES, "iteration": ITERATION_NAMES, "products": PRODUCT_NAMES, "escape": ESCAPE_NAMES}.get(self._kind(slot), PHOTON_NAMES)
 
     def _check_slot(self, slot: int):
         kind, s = self._decode(slot)
-        if kind in ("products", "photons") and not 0 <= s < self.n_species:
+        if kind in ("products", "photons", "escape") and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: {kind} slot of slot {s}, which is no species slot (0..{self.n_species - 1})")
         if kind == "species" and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: slot {slot} outside 0..{self.n_species}")
@@ -691,7 +736,8 @@ class Ensemble:
         kind = self._kind(slot)
         if kind in ("photons", "source"):
             return 0 if self.photon_layout is None else self.photon_layout.offsets()["_total"]
-        return {"species": self.layout.species_total, "iteration": self.layout.iteration_total, "products": self.layout.products_total}[kind]
+        return {"species": self.layout.species_total, "iteration": self.layout.iteration_total, "products": self.layout.products_total,
+                "escape": self.layout.escape_total}[kind]
 
     def _where(self, slot: int, name: str):
         self._check_slot(slot)
@@ -703,7 +749,8 @@ class Ensemble:
             offs = self.photon_layout.offsets()
             table = {part: (offs[part][0], (rows, offs[part][1])) for part in PHOTON_NAMES}
         else:
-            table = {"species": self.layout.species, "iteration": self.layout.iteration, "products": self.layout.products}[kind]
+            table = {"species": self.layout.species, "iteration": self.layout.iteration, "products": self.layout.products,
+                     "escape": self.layout.escape}[kind]
         if name not in self.names(slot):
             raise KeyError(f"ensemble: {self._describe(slot)} has no {name!r}; it has: {', '.join(self.names(slot))}")
         return table[name]
@@ -914,8 +961,25 @@ class HostEnsemble(Ensemble):
         return (None, None, 0) if s is None else (s.mean, s.m2, s.n)
 
     def _set_slope_window(self, l_lo, l_hi, x_log):
-        if self._sampled("products"):
-            raise ValueError("ensemble: a products slot has taken a sample; the slope window stays as it is")
+        if self._sampled("products", "escape"):
+            raise ValueError("ensemble: a products or escape slot has taken a sample; the slope window stays as it is")
+
+    def add_escape(self, backend, slot: int, spectra):
+        """One escape sample of species slot `slot` from an `EscapeSpectra` (consumers.escape_spectra on `backend`), the slopes of its
+        six rows by the backend's deterministic log10."""
+        self._species_slot(slot, "an escape slot")
+        if self.window is None:
+            raise ValueError("ensemble: no slope window (set_slope_window)")
+        if spectra is None:
+            raise ValueError("ensemble: the numpy ensemble takes its escape sample from an EscapeSpectra")
+        l_lo, l_hi, x_log = self.window
+        dndp = np.asarray(spectra.dndp, dtype=np.float64)
+        x = np.concatenate([dndp.ravel(), np.asarray(spectra.number, dtype=np.float64).ravel(),
+                            slopes_of(dndp, l_lo, l_hi, x_log, _det_log10(backend)).ravel()])
+        if x.size != self.layout.escape_total:
+            raise ValueError(f"ensemble: the EscapeSpectra holds {x.size} words; an escape sample has {self.layout.escape_total}")
+        with np.errstate(invalid="ignore"):          # (a NaN slope stays NaN)
+            self._sample(self.escape_slot(slot), x)
 
     def add_products(self, backend, slot: int, ion_final):
         """One products sample of species slot `slot` from an `IonFinal` (consumers.ion_finalize on `backend`), the slopes by the
@@ -969,7 +1033,7 @@ class HostEnsemble(Ensemble):
         # an ensemble without a photon layout or a slope window takes the one its samples were made with
         if other._sampled("photons", "source") and self.photon_layout is None:
             self.photon_layout = other.photon_layout
-        if other._sampled("products") and self.window is None:
+        if other._sampled("products", "escape") and self.window is None:
             self.window = other.window
         for k, b in other._slots.items():      # (what is pending for the source slot on either side stays where it is)
             if b.n == 0:
@@ -1003,7 +1067,7 @@ class HostEnsemble(Ensemble):
     def _summarize_merged(self, others, slot, n, ranges):
         out = []
         es = [self] + others
-        if self.is_products(slot) and any(self._windows_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
+        if (self.is_products(slot) or self.is_escape(slot)) and any(self._windows_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose slope windows differ")
         if self._has_photon_vector(slot) and any(self._photon_layouts_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose photon layouts differ")
@@ -1020,7 +1084,7 @@ class HostEnsemble(Ensemble):
         return out
 
     def _compare(self, other, slot, other_slot, n_a, n_b, ranges):
-        if self.is_products(slot) and self._windows_differ(self, other):
+        if (self.is_products(slot) or self.is_escape(slot)) and self._windows_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose slope windows differ")
         if self._has_photon_vector(slot) and self._photon_layouts_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose photon layouts differ")
@@ -1082,6 +1146,11 @@ class HipEnsemble(Ensemble):
         the backend's device (mcs_ens_add_products); nothing crosses to the host, ion_final is not read."""
         self._chk(self.lib.mcs_ens_add_products(self.h, backend.h, int(slot)))
 
+    def add_escape(self, backend: HipBackend, slot: int, spectra=None):
+        """One escape sample of species slot `slot` from what mcs_dndp_esc (consumers.escape_spectra) left on the backend's device
+        (mcs_ens_add_escape); nothing crosses to the host, `spectra` is not read."""
+        self._chk(self.lib.mcs_ens_add_escape(self.h, backend.h, int(slot)))
+
     def _set_photon_layout(self, layout):
         self._chk(self.lib.mcs_ens_set_photon_layout(self.h, *layout.args()))
 
@@ -1111,7 +1180,8 @@ class HipEnsemble(Ensemble):
         if self.photon_layout is None and other.photon_layout is not None and (
                 other.count(PHOTONS_ALL) or any(other.count(other.photons_slot(s)) for s in range(other.n_species))):
             self.photon_layout = other.photon_layout      # (as the library does)
-        if self.window is None and other.window is not None and any(other.count(other.products_slot(s)) for s in range(other.n_species)):
+        if self.window is None and other.window is not None and any(
+                other.count(other.products_slot(s)) or other.count(other.escape_slot(s)) for s in range(other.n_species)):
             self.window = other.window      # (as the library does: an accumulator without a window takes the one its samples were made with)
 
     def count(self, slot: int) -> int:

@@ -356,6 +356,19 @@ class HipBackend:
         self._chk(self.lib.mcs_thermo_calcs(self.h, ct.byref(s), _dp(a), _dp(b), _dp(c)))
         return a, b, c
 
+    def dndp_esc(self, tabs, gam_pf):
+        """K10: dN/dp of the escaping particles from the resident escape slabs -> (dNdp [2][3][nmom+2], number [2][3], diag [2][2]);
+        door (upstream, downstream) x frame (shock, the door's plasma frame of Lorentz factor gam_pf[door], ISM)."""
+        out = np.zeros((2, 3, self.P.num_psd_mom_bins + 2))
+        number = np.zeros((2, 3))
+        diag = np.zeros((2, 2), dtype=np.int64)
+        g = np.ascontiguousarray(gam_pf, dtype=np.float64)
+        if g.shape != (2,):
+            raise ValueError("dndp_esc: gam_pf holds one Lorentz factor per door")
+        s = tabs.as_struct()
+        self._chk(self.lib.mcs_dndp_esc(self.h, ct.byref(s), _dp(g), _dp(out), _dp(number), diag.ctypes.data_as(c_int64_p)))
+        return out, number, diag
+
     def photon_synch(self, dndp_pf, mom_edge_cgs, mc, n_photon, emin_mev, bins_per_dec):
         """K5: synchrotron emission dP/d(ln E) [erg/s] per zone from the plasma-frame electron dN/dp -> (E_erg[n_photon], emis[n_grid][n_photon])."""
         d = np.ascontiguousarray(dndp_pf, dtype=np.float64); pe = np.ascontiguousarray(mom_edge_cgs, dtype=np.float64)
