@@ -923,6 +923,33 @@ int mcs_eval_tally(mcs_ctx* ctx, int form, int64_t n_pass, int64_t n_thread, con
  * [1, n_pcuts], n other than the population's size, a non-finite x_thr, a context with fp32 state. */
 #define MCS_MOVE_OUT_F64 18
 int mcs_eval_move(mcs_ctx* ctx, int form, int post, int i_pcut, int64_t n, const double* x_thr, double* out, uint64_t* word);
+/* One pass boundary on the CALLER's states: the move of Code Block 2 with what it triggers (as mcs_eval_move, form 0, post 2), then the
+ * head of Code Block 3 -- everything between the end of one move and the next scatter -- through the transport kernel's own slow_pre,
+ * in a kernel inside its translation unit (mcs_k_eval_pass in csrc/mcs_transport.hip).  The states are the context's population, one
+ * per thread, n = its size, as mcs_eval_move reads them (the row AFTER the scatter and the clock of the pass that moves); helix[k] is
+ * the count of that pass (the particle's first: 1), which load_particle's value is overridden with.  Before the move the derived
+ * quantities and flags are those the slow_pre of that pass left: cos_max, 1/ptot and the gyro period of the scatter's statements with
+ * the state's xn_per, t_step, 2 pi / xn_per, 1/(gam m), x_dt; F_NEARP and F_SAVE by their predicates; no refresh pending.  What the
+ * pass head then recomputes is what a flag raised by the move's events or by the head's own branches asks for.
+ * form 0  slow_pre (the general kernel), t_clock = the move's t_step
+ *      1  the LOSSY kernel's in-line radiative loss (lossy_inline_loss) with the constants as that kernel holds them, on the state as
+ *         slow_post left it.  Species with aa < 1 only, do_rad_losses set, no custom eps_B, no dont_scatter: the LOSSY kernel's domain.
+ * The head runs if the particle goes on after the move and its next pass is no Code Block 1 pass (no PRP return).
+ * out [n][MCS_PASS_OUT_F64]
+ *       0 pb_pf   1 p_perp   2 ptot_pf   3 gam_pf   4 phi   5 x   6 x_old   7 prp   8 acctime
+ *       9 gyro_denom   10 gyro_rad   11 gyro_rad_tot   12 gyro_period   13 cm_val (cos_max)   14 rp_val (1/ptot_pf)   15 xn_per
+ *      16 dphi   17 t_step   18 rg_val (1/(gam_pf m))   19 x_dt   20 t_hi   21 t_lo (form 1 only, else 0)
+ *      22 z_lo   23 z_hi   24 z_ux   25 z_gsf   26 z_bcos   27 z_gef
+ * word [n]  i_grid | i_grid_old << 8 | ig3 << 16 | tcut << 24 | downstream << 32 | inj << 33 | slow_post's end code << 34 (3 bits: 1..4,
+ *      7 = goes on) | (the head's end code + 1) << 37 (3 bits: 0 = goes on to the scatter, 1 = saved for the next pcut, 2..5 = i_reason
+ *      1..4, 7 = the head did not run) | F_SAVE << 40 | F_NEARP << 41 | helix after << 42 (14 bits) | min(draws taken, 7) << 56 |
+ *      min(n_retro, 7) << 59 | the move's event bit << 62 | its ev_cross << 63
+ * Neither the population nor the saved arrays are written; the tallies (the time cuts' sums, MCS_IC_HELIX_CAP, MCS_IC_PSP_CLAMP, the
+ * receivers' energy pool) stay in the context for mcs_read_tallies.
+ * Refused with a message, nothing queued: a null or negative argument, form outside 0..1, form 1 outside the LOSSY kernel's domain,
+ * i_pcut outside [1, n_pcuts], n other than the population's size, helix[k] outside [1, 16000], a context with fp32 state. */
+#define MCS_PASS_OUT_F64 28
+int mcs_eval_pass(mcs_ctx* ctx, int form, int i_pcut, int64_t n, const int32_t* helix, double* out, uint64_t* word);
 /* per-particle end state of the last mcs_run_pcut (bit-parity tests): i_reason
  * (0 = saved), helix_count, retro step count, final ptot_pf and x. Any pointer may be NULL.
  * The kernel records them only after mcs_set_debug_finals(ctx, 1) (24 B of stores per particle

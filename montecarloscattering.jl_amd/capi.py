@@ -342,6 +342,7 @@ def load_library() -> ct.CDLL:
         "mcs_eval_pcut_split": (i32, [vp, ct.POINTER(McsPcutEval)]),
         "mcs_eval_tally": (i32, [vp, i32, i64, i64, c_double_p, ct.POINTER(ct.c_uint64)]),
         "mcs_eval_move": (i32, [vp, i32, i32, i32, i64, c_double_p, c_double_p, ct.POINTER(ct.c_uint64)]),
+        "mcs_eval_pass": (i32, [vp, i32, i32, i64, c_int32_p, c_double_p, ct.POINTER(ct.c_uint64)]),
         "mcs_final_download": (i32, [vp, i64, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p]),
         "mcs_last_kernel_ms": (dbl, [vp]),
         "mcs_set_launch": (i32, [vp, i32, i32]),
@@ -429,7 +430,7 @@ EXPORTED_SYMBOLS = [
     "mcs_tallies_f64_devptr", "mcs_tallies_i64_devptr", "mcs_set_grid", "mcs_set_cuts", "mcs_begin_iteration",
     "mcs_begin_species", "mcs_set_fluxes", "mcs_pop_upload", "mcs_pop_download", "mcs_saved_download",
     "mcs_pop_size", "mcs_init_pop", "mcs_init_pop_binned", "mcs_run_pcut", "mcs_new_pcut", "mcs_run_pcut_host", "mcs_read_tallies", "mcs_read_tallies_part", "mcs_num_cus",
-    "mcs_write_tallies", "mcs_eval_fn", "mcs_eval_scatter", "mcs_eval_pcut_split", "mcs_eval_tally", "mcs_eval_move", "mcs_final_download", "mcs_last_kernel_ms", "mcs_set_launch",
+    "mcs_write_tallies", "mcs_eval_fn", "mcs_eval_scatter", "mcs_eval_pcut_split", "mcs_eval_tally", "mcs_eval_move", "mcs_eval_pass", "mcs_final_download", "mcs_last_kernel_ms", "mcs_set_launch",
     "mcs_get_layout", "mcs_dndp_cr", "mcs_thermo_calcs",
     "mcs_run_pcut_strided", "mcs_run_pcut_indexed", "mcs_saved_gidx", "mcs_init_pop_binned_strided", "mcs_saved_export", "mcs_split_import", "mcs_set_debug_finals", "mcs_set_retro_cap",
     "mcs_set_tail_slicing", "mcs_last_launches", "mcs_last_kernel", "mcs_write_tallies_part", "mcs_photon_synch",

@@ -1424,6 +1424,42 @@ int mcs_eval_move(mcs_ctx* c, int form, int post, int i_pcut, int64_t n, const d
   return 0;
 }
 
+// One pass boundary per state of the context's population through K1's own move, slow_post and slow_pre (include/mcs.h): launch
+// constants and replicas as in mcs_eval_move.  The kernel writes only `out`, `word` and the tallies.
+int mcs_eval_pass(mcs_ctx* c, int form, int i_pcut, int64_t n, const int32_t* helix, double* out, uint64_t* word) {
+  MCS_ENTER(c);
+  const std::string w = "mcs_eval_pass: ";
+  if (n < 0 || (n > 0 && (!helix || !out || !word))) return fail(w + "null argument or negative count");
+  if (form < 0 || form > 1) return fail(w + "unknown form " + std::to_string(form) + " (0 .. 1: include/mcs.h)");
+  if (!c->have_grid || !c->have_cuts) return fail(w + "grid/cuts not set");
+  if (i_pcut < 1 || i_pcut > c->tb.n_pcuts) return fail(w + "i_pcut outside [1, n_pcuts]");
+  if (c->P.state_fp32) return fail(w + "the context holds fp32 state (the pass head of the fp32 kernels is another function)");
+  if (form == 1 && !(c->aa < 1 && c->P.do_rad_losses && !c->P.use_custom_epsB && !c->P.dont_scatter))
+    return fail(w + "form 1 is the LOSSY kernel's: a species with aa < 1, do_rad_losses, no custom eps_B, no dont_scatter");
+  if (n != c->n) return fail(w + "n is not the size of the context's population (mcs_pop_upload)");
+  for (int64_t k = 0; k < n; ++k)
+    if (helix[k] < 1 || helix[k] > 16000) return fail(w + "helix[" + std::to_string(k) + "] outside [1, 16000]");
+  if (n == 0) return 0;
+  if (n > INT64_MAX / (MCS_PASS_OUT_F64 + 2)) return fail(w + "n is too large");
+  if (reserve(c->d_stage, (MCS_PASS_OUT_F64 + 2) * n) || reserve(c->d_args, 1) || reserve(c->h_args_pin, 1)) return 1;
+  HIPCHK(hipStreamSynchronize(c->stream));         // (nothing queued may still read the launch constants)
+  KArgs& a = *c->h_args_pin;
+  fill_kargs(c, a, i_pcut, n, 0, 1, nullptr, 0);
+  a.f_reason = nullptr; a.f_helix = nullptr; a.f_retro = nullptr; a.f_ptot = nullptr; a.f_x = nullptr;
+  double* dstage = c->d_stage;
+  int* dhelix = (int*)dstage;                      // (n ints in the first n doubles)
+  double* dout = dstage + n;
+  unsigned long long* dword = (unsigned long long*)(dstage + (MCS_PASS_OUT_F64 + 1) * n);
+  HIPCHK(hipMemcpyAsync(c->d_args, c->h_args_pin, sizeof(KArgs), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dhelix, helix, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(mcs_launch_eval_pass(c->d_args, form, n, dhelix, dout, dword, c->stream));
+  c->rep_dirty = true;
+  HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * MCS_PASS_OUT_F64 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(word, dword, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // K2 on the caller's status bytes and saved states (include/mcs.h): the launchers mcs_run_pcut / mcs_new_pcut / mcs_saved_export (form 0),
 // mcs_run_pcuts_fused (form 1) and pipelined_pcuts (form 2) call, with their grids, on the context's own saved arrays, status bytes,
 // scan scratch and counter words; the target is the spare buffer between two guards.  Everything is checked before anything is

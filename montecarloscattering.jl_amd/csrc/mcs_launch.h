@@ -42,6 +42,8 @@ hipError_t mcs_launch_eval_tally(const KArgs* a_dev, int form, long long n_pass,
 int mcs_eval_tally_stack(int form, int* cap, int* drain_at);
 hipError_t mcs_launch_eval_move(const KArgs* a_dev, int form, int post, long long n, const double* x_thr, double* out,
                                 unsigned long long* word, hipStream_t st);
+hipError_t mcs_launch_eval_pass(const KArgs* a_dev, int form, long long n, const int* helix, double* out, unsigned long long* word,
+                                hipStream_t st);
 hipError_t mcs_launch_dndp_cr(const mcs_params* P, const double* psd, const double* gam_sf, const double* ux, const double* tabs,
                               double rest_energy, double n0, double gam0, double* out_dndp, unsigned long long* diag, hipStream_t st);
 hipError_t mcs_launch_dndp_esc(const mcs_params* P, const double* esc, const double* tabs, double rest_energy, const double gam_pf[2], double gam0,

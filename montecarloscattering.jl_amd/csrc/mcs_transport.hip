@@ -2360,6 +2360,8 @@ __device__ __forceinline__ void transport_body(const KArgs* __restrict__ ka) {
         // pending from the last move (the clock and the position thresholds -- the upstream FEB among them -- stop a lane before this).  The
         // momentum only decreases here, so F_NEARP / F_SAVE stay clear; the cone is refreshed with the xn_per of before this
         // pass's fine / coarse decision, as slow_pre does; t_clock is the time step of the previous move.
+        // (mcs_k_eval_pass, at the end of this file, repeats these statements as lossy_inline_loss for its form 1 -- one function
+        // called from both places changed the register allocation of a shipping kernel --: keep the two alike)
         if (run && !(rep == 0 && loss_done)) {
           const double bmag = S_bt[p.ig3];
           const double ptot_old = p.ptot_pf;
@@ -2732,6 +2734,140 @@ extern "C" hipError_t mcs_launch_eval_move(const KArgs* a_dev, int form, int pos
   if (form < 0 || form > 3 || post < 0 || post > 4) return hipErrorInvalidValue;
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(mcs_k_eval_move, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a_dev, form, post, n, x_thr, out, word);
+  return hipGetLastError();
+}
+
+// The LOSSY kernel's in-line radiative loss, REPEATED from the common pass of transport_body (`if constexpr (LOSSY)` there, which
+// says for which lanes it runs) for form 1 of mcs_k_eval_pass: one function called from both places changed a shipping kernel
+// (mcs_k_transport_lossy_sliced: scratch 84 -> 92 B/lane), so the statements stand twice; keep the two alike.  They are slow_pre's
+// from `rad_losses` to refresh_move in the forms of the common pass -- fdiv and div_r for `/`, refresh_scatter_k and refresh_dtest_k,
+// the fine / coarse step decided in line, refresh_thr<true> --, bit-identical to them: tests/test_gpu_pass_head.py compares form 1
+// with form 0 (slow_pre) state by state.  t_clock is the time step of the previous move.  Returns true when no momentum is left:
+// floors as in slow_pre, the pass counted, F_LOST set (slow_pre returns 4 at the next header).
+__device__ __forceinline__ bool lossy_inline_loss(const Hot& h, const mcsm::HotCoef& kc, Pt& p, double t_clock, double l_bcmb,
+                                                  double l_pe_crit, double l_game_crit) {
+  const double bmag = S_bt[p.ig3];
+  const double ptot_old = p.ptot_pf;
+  const double B_CMB_loc = l_bcmb * p.z_gef;
+  double pn;
+  {   // radiation_loss (particle_loop.jl:578-592)
+    const double dlnp = MCS_RAD_LOSS_FAC * (bmag * bmag + B_CMB_loc * B_CMB_loc) * ptot_old * t_clock;
+    if (dlnp > 1.0e-2) pn = fdiv(ptot_old, 1 + dlnp); else pn = ptot_old * (1 - dlnp);
+  }
+  if (MCS_UNLIKELY(pn <= 0)) {
+    p.ptot_pf = MCS_FLOOR; p.pb_pf = MCS_FLOOR; p.p_perp = MCS_FLOOR; p.gam_pf = 1;
+    p.helix += 1;
+    p.flags |= F_LOST;
+    return true;
+  }
+  p.ptot_pf = pn;
+  p.gam_pf = mcsm::hypot1(fdiv(p.ptot_pf, h.mc));
+  const double ratio = fdiv(p.ptot_pf, ptot_old);
+  p.pb_pf *= ratio;
+  p.p_perp *= ratio;
+  p.gyro_rad_tot = p.ptot_pf * CC_ * p.gyro_denom;
+  p.gyro_rad = p.p_perp * CC_ * p.gyro_denom;
+  refresh_scatter_k(p, kc, h.aa, h.aa * MP_ * CC_, h.eta, l_pe_crit, l_game_crit);
+  refresh_dtest_k(h, p, l_pe_crit, l_game_crit);
+  p.xn_per = p.x > p.gyro_rad_tot ? h.xn_coarse : h.xn_fine;
+  {   // refresh_move
+    const double rx = rcp_refined(p.xn_per);
+    p.dphi = div_r(TWOPI_, p.xn_per, rx);
+    p.t_step = div_r(p.gyro_period, p.xn_per, rx);
+    p.rg_val = rcp_refined(p.gam_pf * (h.aa * MP_));
+  }
+  refresh_thr<true>(h, p);
+  return false;
+}
+
+// One pass boundary per state of the context's population (mcs_eval_pass, include/mcs.h; tests/test_gpu_pass_head.py): the move of
+// Code Block 2 with what it triggers, then everything before the next scatter, in transport_body's frame.  One state per thread:
+//   load_particle, helix = the caller's count of the pass that moves; the derived quantities and flags as the slow_pre of that pass
+//   left them (refresh_scatter with the state's xn_per, refresh_move, refresh_time, refresh_dtest; F_NEARP / F_SAVE by their
+//   predicates, F_RS / F_RM / F_NOPARK clear: slow_pre below refreshes only what a flag raised since then asks for);
+//   move_and_detect; slow_post<true>; then, if the particle goes on and F_B1 is clear,
+//   form 0  slow_pre(a, h, kc, rng, p, t_clock = the move's t_step, false)                          (the general kernel)
+//        1  lossy_inline_loss(...), with Hot as the LOSSY kernel fills it                            (the LOSSY kernel's common pass)
+// The population and the saved arrays are only read.  out [n][MCS_PASS_OUT_F64] and word [n]: include/mcs.h.
+// The host has checked every index the state carries (mcs_pop_upload), the helix counts and the form (mcs_eval_pass).
+extern "C" __global__ void __launch_bounds__(256) mcs_k_eval_pass(const KArgs* __restrict__ ka, int form, long long n,
+                                                                  const int* __restrict__ helix, double* __restrict__ out,
+                                                                  unsigned long long* __restrict__ word) {
+  CK* a = (CK*)ka;
+  const int ne = a->P.n_grid + 2, ng = a->P.n_grid, ntc = a->tb.n_tcuts;
+  block_prologue(a);
+  __syncthreads();
+  // Hot as transport_body fills it (PLAIN = false; LOSSY in form 1): the statements are repeated here, as in mcs_k_eval_move, because
+  // moving them into a function both call changed the register allocation of a shipping kernel; keep them alike.
+  Hot h;
+  h.m = vconst(a->m); h.x_grid_stop = vconst(a->P.x_grid_stop); h.xn_coarse = vconst(a->P.xn_per_coarse);
+  h.u2 = sconst(a->P.u2); h.eta = sconst(a->P.eta_mfp); h.zzq = sconst(a->zzq); h.mc = sconst(a->mc);
+  h.feb_down = sconst(a->P.feb_downstream); h.pcut = sconst(a->pcut); h.pmax_cutoff = sconst(a->pmax_cutoff);
+  h.feb_up = sconst(a->P.feb_upstream); h.age_max = sconst(a->P.age_max); h.inj_frac = sconst(a->inj_frac);
+  h.xn_fine = sconst(a->P.xn_per_fine); h.aa = sconst(a->aa);
+  h.n_grid = sconsti(ng); h.i_grid_feb = sconsti(a->P.i_grid_feb); h.n_tcuts = sconsti(ntc); h.n_xspec = sconsti(a->tb.n_xspec);
+  h.custom_epsB = a->P.use_custom_epsB != 0; h.etf = a->P.energy_transfer_frac > 0;
+  h.dont_scatter = a->P.dont_scatter != 0; h.rad_losses = a->P.do_rad_losses != 0;
+  h.do_tcuts = a->P.do_tcuts != 0; h.dont_DSA = a->P.dont_DSA != 0;
+  {
+    int ob = 0;
+    for (int i = threadIdx.x; i < ne; i += blockDim.x) ob |= S_bsin[i] != 0.0;
+    h.oblique = __builtin_amdgcn_readfirstlane(__syncthreads_or(ob)) != 0;
+  }
+  h.every_pass = h.custom_epsB || (h.rad_losses && h.aa < 1) || h.dont_scatter;
+  h.odd_cfg = h.feb_down > 0 || h.dont_DSA || h.inj_frac < 1 || h.aa < 1 || h.n_xspec != 0;
+  double l_bcmb = 0, l_pe_crit = 0, l_game_crit = 0;
+  if (form == 1) {
+    h.every_pass = false; h.custom_epsB = false; h.dont_scatter = false; h.rad_losses = true;
+    l_bcmb = sconst(a->P.B_CMBz); l_pe_crit = sconst(a->P.pe_crit); l_game_crit = sconst(a->P.game_crit);
+  }
+  mcsm::HotCoef kc;
+  hot_coef_init(kc);
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {      // (no early return: the flush below is the whole block's)
+    Pt p{};
+    Rng rng;
+    load_particle(a, h, i, p, rng);
+    p.helix = helix[i];
+    if (!h.dont_scatter) refresh_scatter(a, p, h.aa, h.aa * MP_ * CC_, h.eta);
+    refresh_move(a, h, p);
+    refresh_dtest(a, h, p);
+    p.t_hi = 0.0; p.t_lo = 0.0;
+    p.flags = (p.flags & F_INJCHK) | (p.ptot_pf > h.pmax_cutoff ? F_NEARP : 0) | ((p.downstream && p.ptot_pf > h.pcut) ? F_SAVE : 0);
+    double phi_old = 0.0;
+    bool ev_cross = false;
+    const bool ev = move_and_detect(a, h, p, phi_old, ev_cross);
+    const double t_clock = p.t_step;
+    const int end_post = slow_post<true>(a, h, rng, p, phi_old);
+    int end_pre = -2;      // (-2: slow_pre did not run)
+    if (end_post < 0 && !(p.flags & F_B1)) {
+      if (form == 0) end_pre = slow_pre(a, h, kc, rng, p, t_clock, false);
+      else end_pre = lossy_inline_loss(h, kc, p, t_clock, l_bcmb, l_pe_crit, l_game_crit) ? 4 : -1;
+    }
+    if (p.n_ovr) cnt(a, MCS_IC_TCUT_OVERRUN, p.n_ovr);      // (D4: counted per pass, flushed where a particle ends in transport_body)
+    double* o = out + (long long)MCS_PASS_OUT_F64 * i;
+    o[0] = p.pb_pf; o[1] = p.p_perp; o[2] = p.ptot_pf; o[3] = p.gam_pf; o[4] = p.phi; o[5] = p.x; o[6] = p.x_old; o[7] = p.prp;
+    o[8] = p.acctime; o[9] = p.gyro_denom; o[10] = p.gyro_rad; o[11] = p.gyro_rad_tot; o[12] = p.gyro_period; o[13] = p.cm_val;
+    o[14] = p.rp_val; o[15] = p.xn_per; o[16] = p.dphi; o[17] = p.t_step; o[18] = p.rg_val; o[19] = p.x_dt; o[20] = p.t_hi; o[21] = p.t_lo;
+    o[22] = p.z_lo; o[23] = p.z_hi; o[24] = p.z_ux; o[25] = p.z_gsf; o[26] = p.z_bcos; o[27] = p.z_gef;
+    const unsigned long long n_retro = (unsigned long long)(p.n_retro > 7 ? 7 : p.n_retro);
+    const unsigned long long draws = rng.n > 7u ? 7ull : (unsigned long long)rng.n;
+    word[i] = (unsigned long long)(p.i_grid & 0xff) | ((unsigned long long)(p.i_grid_old & 0xff) << 8) | ((unsigned long long)(p.ig3 & 0xff) << 16) |
+              ((unsigned long long)(p.tcut & 0xff) << 24) | ((unsigned long long)(p.downstream ? 1 : 0) << 32) |
+              ((unsigned long long)(p.inj ? 1 : 0) << 33) | ((unsigned long long)(end_post < 0 ? 7 : end_post) << 34) |
+              ((unsigned long long)(end_pre == -2 ? 7 : end_pre + 1) << 37) | ((unsigned long long)((p.flags & F_SAVE) ? 1 : 0) << 40) |
+              ((unsigned long long)((p.flags & F_NEARP) ? 1 : 0) << 41) | ((unsigned long long)(p.helix & 0x3fff) << 42) | (draws << 56) |
+              (n_retro << 59) | ((unsigned long long)(ev ? 1 : 0) << 62) | ((unsigned long long)(ev_cross ? 1 : 0) << 63);
+  }
+  __syncthreads();
+  block_flush(a);
+}
+
+extern "C" hipError_t mcs_launch_eval_pass(const KArgs* a_dev, int form, long long n, const int* helix, double* out,
+                                           unsigned long long* word, hipStream_t st) {
+  if (form < 0 || form > 1) return hipErrorInvalidValue;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcs_k_eval_pass, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a_dev, form, n, helix, out, word);
   return hipGetLastError();
 }
 

@@ -476,6 +476,20 @@ class HipBackend:
                                          word.ctypes.data_as(ct.POINTER(ct.c_uint64))))
         return out, word
 
+    def eval_pass(self, form: int, helix, i_pcut: int = 1):
+        """One pass boundary per state of the context's population (set_population): the move of Code Block 2 with what it triggers,
+        then the head of Code Block 3 through the transport kernel's own slow_pre (form 0) or the LOSSY kernel's in-line loss (form 1);
+        helix: the count of the pass that moves, per state (mcs_eval_pass in include/mcs.h).  Returns out [n][28] and the packed word
+        [n]; the deposits land in the context's tallies."""
+        n = self.pop_size()
+        hx = np.ascontiguousarray(helix, dtype=np.int32)
+        assert hx.shape == (n,)
+        out = np.zeros((n, 28))
+        word = np.zeros(n, dtype=np.uint64)
+        self._chk(self.lib.mcs_eval_pass(self.h, int(form), int(i_pcut), n, hx.ctypes.data_as(ct.POINTER(ct.c_int32)), _dp(out),
+                                         word.ctypes.data_as(ct.POINTER(ct.c_uint64))))
+        return out, word
+
     def eval_pcut_split(self, form: int, l_save, saved: Population, n=None, *, match=1, i_mult=1, n_target=1, ctr_work=0, ctr_saved=0,
                         n_main_next=0, src_fill=0, guard=64, out_cap=0, export_mode=0, exp_cap=0, exp_first=0, exp_stride=1, exp_gin=None):
         """The pcut bookkeeping kernels on the caller's status bytes and saved states (mcs_eval_pcut_split in include/mcs.h: form 0

@@ -62,6 +62,7 @@ def load(math: str = "det", capi=None):
         "orc_eval_tally": (i32, [vp, i32, i64, dp, ct.POINTER(ct.c_uint64), i32]),
         "orc_tally_log": (i64, [vp, i64, i64p, i64p, i64p, dp]),
         "orc_eval_move": (i32, [vp, i32, i64, soa_p, dp, ct.POINTER(ct.c_uint64), i32]),
+        "orc_eval_pass": (i32, [vp, i32, i64, soa_p, i32p, i32, dp, ct.POINTER(ct.c_uint64), i32]),
         "orc_zone_search": (i32, [vp, i64, dp, u8p, i32p, i32p]),
         "orc_transform_p_PS": (None, [dbl] * 11 + [dp]),
         "orc_transform_p_PSP": (None, [vp] + [dbl] * 5 + [dp, dp, dp]),
@@ -392,6 +393,29 @@ class OracleBackend:
         s = pop.soa()
         self._chk(self.lib.orc_eval_move(self.h, int(i_pcut), n, ct.byref(s), _dp(out), word.ctypes.data_as(ct.POINTER(ct.c_uint64)),
                                          int(bool(log))))
+        if not log:
+            return out, word, None
+        m = int(self.lib.orc_tally_log(self.h, 0, None, None, None, None))
+        i64p = ct.POINTER(ct.c_int64)
+        lr, lb, lo, lv = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64), np.zeros(m)
+        self.lib.orc_tally_log(self.h, m, lr.ctypes.data_as(i64p), lb.ctypes.data_as(i64p), lo.ctypes.data_as(i64p), _dp(lv))
+        return out, word, (lr, lb, lo, lv)
+
+    def eval_pass(self, pop, helix, i_pcut=1, head=True, log=True):
+        """One pass boundary per state of `pop` (HipBackend.eval_pass's states and helix counts): the prologue of particle_loop, the
+        oracle's code_block_2 once with the caller's helix_count, then the next pass up to its scatter (the helix cap, code_block_3_head,
+        and code_block_3_rest for a particle saved there).  head=0: the move alone with the prologue's gyro period, as eval_move; head=2:
+        the move alone as the full call makes it (the state the head sees).
+        Returns out [n][28], the packed word [n] (include/mcs.h, mcs_eval_pass; the device's own fields stay 0) and, with log, every
+        deposit of the walk as arrays (state index, buffer: 0 fp64 tallies / 1 int64 tallies, offset, value), in the order made."""
+        n = pop.n
+        hx = np.ascontiguousarray(helix, dtype=np.int32)
+        assert hx.shape == (n,)
+        out = np.zeros((n, 28))
+        word = np.zeros(n, dtype=np.uint64)
+        s = pop.soa()
+        self._chk(self.lib.orc_eval_pass(self.h, int(i_pcut), n, ct.byref(s), hx.ctypes.data_as(ct.POINTER(ct.c_int32)), int(head),
+                                         _dp(out), word.ctypes.data_as(ct.POINTER(ct.c_uint64)), int(bool(log))))
         if not log:
             return out, word, None
         m = int(self.lib.orc_tally_log(self.h, 0, None, None, None, None))

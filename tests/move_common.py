@@ -28,8 +28,8 @@ no code with oracle/mcs_oracle.cpp (gam_pf and mod2pi come through orc_eval_fn).
 only: with an oblique field the gyro term needs the library's cos, and first_move() then asks the oracle.
 
 Not reached here, on purpose: prob_return's `helix_count % 1000 == 0` branch of the electrons (a state is a particle's first pass,
-helix_count 1: the branch stays with the whole-run tests), and the inline dispatch of the rare region (full / light path / waiting) in
-transport_body, mcs_transport_ws.inc and the tail loop -- calling that from a test kernel needs a refactor of the body, which is a
+helix_count 1: mcs_eval_pass takes the count from the caller, and tests/pass_common.py builds electrons beyond x_grid_stop with 999, 1000 and
+2000 passes behind them), and the inline dispatch of the rare region (full / light path / waiting) in transport_body, mcs_transport_ws.inc and the tail loop -- calling that from a test kernel needs a refactor of the body, which is a
 pull request of its own, with a bench.  The fp32 kernels keep their whole-run check.
 """
 import ctypes as ct
