@@ -452,6 +452,39 @@ int mcs_thermo_calcs(mcs_ctx* ctx, const mcs_consumer_in* in, double* P_par, dou
  * The result also stays on the device, in a buffer that no other call writes, for the escape sample of the ensemble statistics
  * (below); mcs_begin_species and that sample invalidate it. */
 int mcs_dndp_esc(mcs_ctx* ctx, const mcs_consumer_in* in, const double* gam_pf, double* dNdp, double* number, int64_t* diag);
+/* K11: the pitch-angle distribution of every grid zone over up to MCS_ANGLE_MAX_WINDOWS momentum windows, in three frames, from the
+ * resident psd, therm_sf and num_crossings and the grid tables (gam_sf).  Of `in` it reads pt_center, cos_center, cos_edge,
+ * rest_energy, gam0 and therm_from_hist.
+ *   frame 0: the shock frame; frame 1: the plasma frame of the zone, Lorentz factor gam_sf[zone] as mcs_dndp_cr takes it;
+ *   frame 2: the ISM frame, in->gam0.  beta by the rule of transformers.jl:639 (0 below 1.000001).
+ * Window m is the momentum bins l_lo[m] <= kX < l_hi[m] OF THE TARGET FRAME; 0 <= l_lo < l_hi <= nmom + 1, 1 <= n_win <=
+ * MCS_ANGLE_MAX_WINDOWS; windows may overlap.  Anything else is refused with a message and nothing is changed.
+ * CELLS: with NM = nmom + 2, NT = ntht + 2, the cells j <= ntht, k <= nmom of psd[z][j][k] (momentum fastest).  A cell's weight:
+ *   v = 0.0;  if therm_from_hist and num_crossings[z] != 0: v = v + therm_sf[z][j][k];  if psd[z][j][k] > 1e-66: v = v + psd[z][j][k];
+ * the cell is lit if v > 1e-66 (a NaN cell is not lit).
+ * IMAGE of cell (j, k): itself in frame 0 (nothing is computed); in frames 1 and 2 the centre-point rebin of mcs_dndp_2d, every
+ * operation rounded separately:
+ *   px = pt_center[k] * cos_center[j];  pc = pt_center[k] * c;  et = sqrt(pc*pc + E0*E0);
+ *   pxX = gam * (px - beta * et / c);   ptX = sqrt(pt*pt - px*px + pxX*pxX);
+ *   kX = the momentum bin of ptX, jX = the angle bin of (pxX, ptX), as mcs_dndp_2d finds them; both clamped into 0..nmom, 0..ntht.
+ * OUTPUTS (host; each may be null): dist [3][n_grid][n_win][NT], number [3][n_grid][n_win], moments [3][n_grid][n_win][2].
+ * ORDER OF THE ADDS (normative; no floating-point atomics, so every call on the same tallies gives the same bits):
+ *   A[jX] = the weights of the lit cells whose image lies in row jX and in the window, added to 0.0 with j ascending and, within
+ *   a row, k ascending;
+ *   number = ((0.0 + A[0]) + A[1]) + ... + A[ntht];
+ *   dist[j] = (A[j] / number) / (cos_edge[j+1] - cos_edge[j]) where A[j] > 0, else 1e-99;  dist[ntht+1] = 1e-99;
+ *   a window that no cell reaches has number = 0.0 and all of dist at 1e-99;
+ *   moments[0] = <mu> = s1 / number, s1 the serial sum from 0.0 over j = 0..ntht of t_j = A[j] * cos_center[j];
+ *   moments[1] = <mu^2> = s2 / number, s2 the serial sum of t_j * cos_center[j];
+ *   with number == 0 both moments are a quiet NaN -- the convention of the slope words of the products sample: a summary counts
+ *   such a word in n_nonfinite, no trigger on it is met, and ONE empty sample keeps the word's mean non-finite.  Windows belong on
+ *   zones and momenta that the population reaches.
+ * The result also stays on the device, in a buffer that no other call writes, for the angles sample of the ensemble statistics
+ * (below); mcs_begin_species, a write of the tallies and that sample invalidate it.  The call changes neither the tallies nor what
+ * mcs_dndp_cr, mcs_thermo_calcs, mcs_dndp_2d and mcs_dndp_esc left on the device. */
+#define MCS_ANGLE_MAX_WINDOWS 8
+int mcs_angle_dist(mcs_ctx* ctx, const mcs_consumer_in* in, int n_win, const int32_t* l_lo, const int32_t* l_hi,
+                   double* dist, double* number, double* moments);
 
 /* ---- photon post-processing: the synchrotron fold of src/synch_emission.jl:27-171 over the plasma-frame
  * dN/dp of an electron species (frame 2 of mcs_dndp_cr), for every grid zone with the zone's field of the grid tables.
@@ -710,6 +743,32 @@ typedef struct mcs_ens_escape_layout {
 } mcs_ens_escape_layout;
 int mcs_ens_escape_get_layout(const mcs_params* p, mcs_ens_escape_layout* out);      /* needs no GPU */
 int mcs_ens_add_escape(mcs_ens* ens, mcs_ctx* src, int species_slot);
+
+/* ---- angles sample: error bars of the pitch-angle distributions.  Every species slot s has a fourth companion, the ANGLES slot
+ * MCS_ENS_ANGLES(s), which behaves as its escape slot does in the count, read, merge, summarize, summarize-merged and compare calls
+ * (vectors allocated at the first sample; reads of a slot that never took one are refused).  The accumulator holds the momentum
+ * windows of its angles samples, mcs_ens_set_angle_windows (the rules of mcs_angle_dist): they may be set again until the first
+ * angles sample of any slot and are fixed from then on.  With rows = 3 * n_grid * n_win and row = (frame * n_grid + zone) * n_win +
+ * window, the sample holds rows * (ntht + 5) doubles, mcs_ens_angles_layout:
+ *   dist     [rows][ntht+2]   the last mcs_angle_dist on the context, as that call left it on the device
+ *   number   [rows]           likewise
+ *   mean_mu  [rows]           moments[.][0] of that call
+ *   mean_mu2 [rows]           moments[.][1]
+ * mcs_ens_add_angles: refused unless mcs_angle_dist has run on src since its last mcs_begin_species and since the last angles
+ * sample taken from it, without windows, where that call's windows differ from the accumulator's, and for what
+ * mcs_ens_add_species refuses.  Queued on src's stream behind the accumulator's event, no host synchronisation.
+ * A merge, a merged summary or a comparison of accumulators whose windows differ is refused; a destination without windows takes
+ * the source's.  mcs_ens_load_mean takes species slots only. */
+#define MCS_ENS_ANGLES(s) ((s) | (1 << 26))
+typedef struct mcs_ens_angles_layout {
+  int64_t dist, number, mean_mu, mean_mu2;                  /* offsets, in doubles */
+  int64_t row_n;                                            /* ntht + 2: the length of a dist row */
+  int64_t rows;                                             /* 3 * n_grid * n_win */
+  int64_t total;
+} mcs_ens_angles_layout;
+int mcs_ens_angles_get_layout(const mcs_params* p, int n_win, mcs_ens_angles_layout* out);   /* needs no GPU */
+int mcs_ens_set_angle_windows(mcs_ens* ens, int n_win, const int32_t* l_lo, const int32_t* l_hi);
+int mcs_ens_add_angles(mcs_ens* ens, mcs_ctx* src, int species_slot);
 
 /* ---- photons sample: error bars of the photon spectra at Earth.  A shell spectrum is a sum over zones, slices and processes: its
  * variance does not follow from per-cell variances, so the spectrum itself is sampled once per iteration, from what

@@ -109,7 +109,14 @@ class McsEnsEscapeLayout(ct.Structure):
     _fields_ = [(name, ct.c_int64) for name in ("dNdp", "number", "slope", "row_n", "total")]
 
 
+class McsEnsAnglesLayout(ct.Structure):
+    """`mcs_ens_angles_layout`: offsets of the four parts of an angles sample, the length of a dist row and the number of rows
+    (include/mcs.h, "angles sample")."""
+    _fields_ = [(name, ct.c_int64) for name in ("dist", "number", "mean_mu", "mean_mu2", "row_n", "rows", "total")]
+
+
 ENS_ESCAPE_BIT = 1 << 27        # MCS_ENS_ESCAPE(s) = s | ENS_ESCAPE_BIT
+ENS_ANGLES_BIT = 1 << 26        # MCS_ENS_ANGLES(s) = s | ENS_ANGLES_BIT
 ENS_PHOTONS_BIT = 1 << 29       # MCS_ENS_PHOTONS(s) = s | ENS_PHOTONS_BIT
 ENS_PHOTONS_ALL = 1 << 28       # MCS_ENS_PHOTONS_ALL: the source slot, one per accumulator
 
@@ -353,6 +360,7 @@ def load_library() -> ct.CDLL:
         "mcs_dndp_cr": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_int64_p]),
         "mcs_thermo_calcs": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_double_p, c_double_p]),
         "mcs_dndp_esc": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_double_p, c_double_p, c_int64_p]),
+        "mcs_angle_dist": (i32, [vp, ct.POINTER(McsConsumerIn), i32, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
         "mcs_photon_synch": (i32, [vp, c_double_p, c_double_p, dbl, i32, dbl, dbl, c_double_p, c_double_p]),
         "mcs_run_pcuts_fused": (i32, [vp, i32, i32, c_int64_p, c_int64_p, c_int64_p, c_int64_p, c_double_p]),
         "mcs_run_pcuts_pipelined": (i32, [vp, i32, i32, c_int64_p, ct.c_int64, ct.c_int64, c_int64_p, c_int64_p, c_int64_p, c_double_p, c_int64_p]),
@@ -392,6 +400,9 @@ def load_library() -> ct.CDLL:
         "mcs_ens_compare": (i32, [vp, i32, vp, i32, i32, ct.POINTER(McsEnsCmpRange), ct.POINTER(McsEnsDifference)]),
         "mcs_ens_escape_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsEnsEscapeLayout)]),
         "mcs_ens_add_escape": (i32, [vp, vp, i32]),
+        "mcs_ens_angles_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsEnsAnglesLayout)]),
+        "mcs_ens_set_angle_windows": (i32, [vp, i32, c_int32_p, c_int32_p]),
+        "mcs_ens_add_angles": (i32, [vp, vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -451,4 +462,6 @@ EXPORTED_SYMBOLS += ["mcs_photon_observe", "mcs_ens_photons_get_layout", "mcs_en
 EXPORTED_SYMBOLS += ["mcs_ens_add_photons_deposit", "mcs_ens_add_photons_all", "mcs_ens_drop_pending_photons"]
 # the spectra of the escaping particles (K10) and their sample
 EXPORTED_SYMBOLS += ["mcs_dndp_esc", "mcs_ens_escape_get_layout", "mcs_ens_add_escape"]
+# the pitch-angle distributions (K11) and their sample
+EXPORTED_SYMBOLS += ["mcs_angle_dist", "mcs_ens_angles_get_layout", "mcs_ens_set_angle_windows", "mcs_ens_add_angles"]
 PHOTON_PROCESS = {"synch": 0, "ic": 1, "pion": 2}      # MCS_PHOTON_SYNCH, _IC, _PION

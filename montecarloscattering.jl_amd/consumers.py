@@ -189,6 +189,52 @@ def escape_spectra(prob, backend, i_ion: int, gam_pf=None) -> EscapeSpectra:
     return EscapeSpectra(dndp, number, diag, g, tabs.mom_edge_cgs)
 
 
+@dataclasses.dataclass
+class AngleDistributions:
+    """The pitch-angle distribution of every grid zone over momentum windows (K11, include/mcs.h mcs_angle_dist), per frame (0: shock,
+    1: the zone's plasma frame, 2: ISM), zone (0-based) and window.  The windows select momentum bins OF THE TARGET FRAME."""
+    dist: np.ndarray             # [3][n_grid][n_win][ntht+2]: (share of the window's weight in the angle bin) / (cos_edge[j+1] - cos_edge[j]); empty: 1e-99
+    number: np.ndarray           # [3][n_grid][n_win]: the summed weight of the window
+    mean_mu: np.ndarray          # [3][n_grid][n_win]: <mu> over cos_center; NaN where number is 0
+    mean_mu2: np.ndarray         # [3][n_grid][n_win]: <mu^2>; NaN where number is 0
+    windows: tuple               # ((l_lo, l_hi), ...): momentum bins l_lo <= k < l_hi
+    cos_edge: np.ndarray         # [ntht+2]
+    cos_center: np.ndarray       # [ntht+1]
+
+
+def momentum_windows(prob, windows) -> tuple:
+    """((l_lo, l_hi), ...) of `angle_distributions` from momenta [(p_lo, p_hi), ...] in cgs: the bins whose centre lies in
+    [p_lo, p_hi], by the bin centres of ensemble.slope_window.  An empty window, or more than eight, raises ValueError."""
+    from . import ensemble as ens
+    x_log = ens.bin_centres_log10(prob)
+    windows = list(windows)
+    if not 1 <= len(windows) <= ens.ANGLE_MAX_WINDOWS:
+        raise ValueError(f"momentum_windows: 1..{ens.ANGLE_MAX_WINDOWS} windows, not {len(windows)}")
+    out = []
+    for p_lo, p_hi in windows:
+        if not 0 < p_lo < p_hi:
+            raise ValueError(f"momentum_windows: a window needs momenta 0 < p_lo < p_hi, not {p_lo!r}, {p_hi!r}")
+        inside = np.flatnonzero((x_log >= math.log10(p_lo)) & (x_log <= math.log10(p_hi)))
+        if inside.size == 0:
+            raise ValueError(f"momentum_windows: no momentum bin has its centre in [{p_lo!r}, {p_hi!r}]")
+        out.append((int(inside[0]), int(inside[-1]) + 1))
+    return tuple(out)
+
+
+def angle_distributions(prob, backend, i_ion: int, windows, therm_from_hist: bool = True) -> AngleDistributions:
+    """The pitch-angle distributions of the backend's resident tallies over the momentum-bin windows ((l_lo, l_hi), ...)
+    (`momentum_windows` makes them from cgs momenta)."""
+    if not hasattr(backend, "angle_dist"):
+        raise ValueError("angle_distributions: the backend has no angle_dist (the distributions are made on the device, K11; there is no host twin)")
+    from . import ensemble as ens
+    windows = tuple((int(a), int(b)) for a, b in windows)
+    lo, hi = ens.check_angle_windows(prob.params.num_psd_mom_bins, [w[0] for w in windows], [w[1] for w in windows])
+    tabs = consumer_tables(prob, i_ion, therm_from_hist=therm_from_hist)
+    dist, number, moments = backend.angle_dist(tabs, lo, hi)
+    return AngleDistributions(dist, number, np.ascontiguousarray(moments[..., 0]), np.ascontiguousarray(moments[..., 1]), windows,
+                              np.asarray(tabs.cos_edge), np.asarray(tabs.cos_center))
+
+
 # ---- photon post-processing (SURVEY.md 8(f-4)) -------------------------------------------------------------------------
 # photon_calcs.jl:11-19: the common energy grid of the emission spectra
 PHOTON_E_MIN_MEV = 1.0e-13

@@ -175,6 +175,12 @@ struct mcs_ctx {
   // mcs_begin_species and the last escape sample of the ensemble statistics.  Only that call writes it, its row scratch and its counts.
   DevBuf<double> d_esc_out, d_esc_rows; DevBuf<unsigned int> d_esc_rowdiag; DevBuf<unsigned long long> d_esc_diag;
   bool have_esc = false;
+  // K11: what the last mcs_angle_dist left, in the layout of an angles sample (dist | number | mean_mu | mean_mu2), its tables and
+  // its windows; have_ang: a whole result since the last mcs_begin_species, tally write and angles sample.  Only that call writes them.
+  DevBuf<double> d_ang_out, d_ang_tab;
+  bool have_ang = false;
+  int ang_n_win = 0;
+  int32_t ang_lo[MCS_ANGLE_MAX_WINDOWS] = {}, ang_hi[MCS_ANGLE_MAX_WINDOWS] = {};
   DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
   // K9, per process (MCS_PHOTON_SYNCH / _IC / _PION): d_pemis the emis[n_grid][n_photon] its fold left (pemis_n: that n_photon, 0 =
   // nothing), d_pobs the [n_shells+1][n] of the last mcs_photon_observe (pobs_n: its n, 0 = nothing; pobs_shells).  Only those calls
@@ -454,6 +460,7 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
   c->pmax_cutoff = pmax_cutoff; c->density = density; c->ewf = ewf;
   c->have_cout_dndp = c->have_cout_thermo = false;
   c->have_esc = false;
+  c->have_ang = false;
   c->photon_flags_clear();
   if (fold_replicas(c)) return 1;      // (the previous species' replicas, before its histograms are cleared)
   const long long npsd = c->L.psd_stride_zone * P.n_grid;
@@ -1244,6 +1251,7 @@ int mcs_write_tallies_part(mcs_ctx* c, int64_t first, int64_t count, const doubl
   if (first < 0 || count < 0 || first + count > c->L.total || (count > 0 && !host_f64)) return fail("mcs_write_tallies_part: range outside the tally buffer");
   if (fold_replicas(c)) return 1;
   c->photon_flags_clear();
+  c->have_ang = false;
   if (count > 0) HIPCHK(hipMemcpyAsync(c->d_T + first, host_f64, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -1252,6 +1260,7 @@ int mcs_write_tallies(mcs_ctx* c, const double* host_f64, const int64_t* host_i6
   MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
   c->photon_flags_clear();
+  c->have_ang = false;
   if (host_f64) HIPCHK(hipMemcpyAsync(c->d_T, host_f64, (size_t)c->L.total * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (host_i64) HIPCHK(hipMemcpyAsync(c->d_I, host_i64, (size_t)mcs_i64_total(&c->P) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1656,6 +1665,47 @@ int mcs_dndp_esc(mcs_ctx* c, const mcs_consumer_in* in, const double* gam_pf, do
   return 0;
 }
 
+int mcs_angle_dist(mcs_ctx* c, const mcs_consumer_in* in, int n_win, const int32_t* l_lo, const int32_t* l_hi, double* dist, double* number,
+                   double* moments) {
+  MCS_ENTER(c);
+  const std::string who = "mcs_angle_dist";
+  if (!in || !l_lo || !l_hi) return fail(who + ": null argument");
+  if (!c->have_grid) return fail(who + ": grid not set");
+  const int nm = c->P.num_psd_mom_bins, nt = c->P.num_psd_tht_bins, ng = c->P.n_grid;
+  const int NM = nm + 2, NT = nt + 2;
+  if (NM > 208 || NT > 208) return fail(who + ": too many PSD bins");
+  if (!in->pt_center || !in->cos_center || !in->cos_edge) return fail(who + ": null table");
+  if (!(in->gam0 >= 1)) return fail(who + ": a Lorentz factor below 1");
+  if (n_win < 1 || n_win > MCS_ANGLE_MAX_WINDOWS) return fail(who + ": n_win outside 1.." + std::to_string(MCS_ANGLE_MAX_WINDOWS));
+  for (int m = 0; m < n_win; ++m)
+    if (l_lo[m] < 0 || l_lo[m] >= l_hi[m] || l_hi[m] > nm + 1)
+      return fail(who + ": window " + std::to_string(m) + " [" + std::to_string(l_lo[m]) + ", " + std::to_string(l_hi[m]) +
+                  ") needs 0 <= l_lo < l_hi <= " + std::to_string(nm + 1));
+  if (fold_replicas(c)) return 1;
+  const long long rows = 3LL * ng * n_win, n_out = rows * (NT + 3);
+  if (reserve(c->d_ang_out, 3LL * ng * MCS_ANGLE_MAX_WINDOWS * (NT + 3)) || reserve(c->d_ang_tab, NM + 2 * NT)) return 1;
+  c->have_ang = false;
+  std::vector<double> h((size_t)(NM + 2 * NT), 0.0);
+  memcpy(h.data(), in->pt_center, sizeof(double) * (NM - 1));
+  memcpy(h.data() + NM, in->cos_center, sizeof(double) * (NT - 1));
+  memcpy(h.data() + NM + NT, in->cos_edge, sizeof(double) * NT);
+  HIPCHK(hipMemcpyAsync(c->d_ang_tab, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(mcs_launch_angle_dist(&c->P, c->d_T + c->L.psd, c->d_T + c->L.therm_sf, c->d_I + MCS_I_NUM_CROSSINGS, c->tb.gsf, c->d_ang_tab,
+                               in->rest_energy, in->gam0, in->therm_from_hist, n_win, l_lo, l_hi, c->d_ang_out, c->stream));
+  std::vector<double> o((size_t)n_out);
+  HIPCHK(hipMemcpyAsync(o.data(), c->d_ang_out, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (dist) memcpy(dist, o.data(), sizeof(double) * (size_t)(rows * NT));
+  const double* tail = o.data() + rows * NT;      // number | mean_mu | mean_mu2
+  if (number) memcpy(number, tail, sizeof(double) * (size_t)rows);
+  if (moments)
+    for (long long r = 0; r < rows; ++r) { moments[2 * r] = tail[rows + r]; moments[2 * r + 1] = tail[2 * rows + r]; }
+  c->ang_n_win = n_win;
+  for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) { c->ang_lo[m] = m < n_win ? l_lo[m] : 0; c->ang_hi[m] = m < n_win ? l_hi[m] : 0; }
+  c->have_ang = true;
+  return 0;
+}
+
 int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, double* P_perp, double* energy_density) {
   MCS_ENTER(c);
   if (consumers_ready(c, in, "mcs_thermo_calcs")) return 1;
@@ -1855,14 +1905,16 @@ int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
   MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
   *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo, {}, {}, {},
-                    c->d_esc_out, c->have_esc};
+                    c->d_esc_out, c->have_esc, c->d_ang_out, c->have_ang, c->ang_n_win, {}, {}};
+  for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) { out->ang_lo[m] = c->ang_lo[m]; out->ang_hi[m] = c->ang_hi[m]; }
   for (int p = 0; p < 3; ++p) { out->pobs[p] = c->d_pobs[p]; out->pobs_n[p] = c->pobs_n[p]; out->pobs_shells[p] = c->pobs_shells[p]; }
   return 0;
 }
-void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; c->photon_flags_clear(); }
+void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; c->have_ang = false; c->photon_flags_clear(); }
 void mcs_ctx_view_products_taken(mcs_ctx* c) { c->have_cout_dndp = c->have_cout_thermo = false; }
 void mcs_ctx_view_photons_taken(mcs_ctx* c) { c->photon_flags_clear(); }
 void mcs_ctx_view_escape_taken(mcs_ctx* c) { c->have_esc = false; }
+void mcs_ctx_view_angles_taken(mcs_ctx* c) { c->have_ang = false; }
 int mcs_ctx_view_fail(const char* msg) { return fail(msg); }
 
 }  // extern "C"

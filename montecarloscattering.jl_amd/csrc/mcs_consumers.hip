@@ -543,6 +543,143 @@ __global__ void __launch_bounds__(256) mcs_k_dndp_esc_join(EscArgs a) {
   }
 }
 
+// ---- K11: the pitch-angle distribution of every zone over momentum windows, in the shock frame, the zone's plasma frame and the
+// ISM frame (include/mcs.h, mcs_angle_dist).  The cells are K6's (thermal crossings + psd above 1e-66) and so is the image of a cell
+// in a moving frame, the centre-point rebin; what is kept is the angle, not the momentum.  No floating-point atomics: the header
+// fixes the order of every add, so the same tallies give the same bits.
+// One workgroup per (zone, frame).  The cells are taken in their order, ANG_CHUNK at a time: first every thread makes the weight
+// and the image of its cells of the chunk into LDS, one transform per cell -- the image as jX | mask << 8, bit m of the mask set
+// where window m holds kX; ANG_DARK, a row that no thread owns, for a cell that is not lit or lies in no window --; then thread j,
+// the owner of target row j, walks the chunk in cell order, ANG_STEP cells per step (their images and weights read from LDS
+// together: all lanes read the same words, a broadcast), and adds the weights whose image lies in its row to its accumulators of
+// the windows in the mask.  A wave none of whose rows is hit skips the adds.
+#define ANG_CHUNK 2048
+#define ANG_STEP 8
+#define ANG_DARK 0x00FFu
+
+struct AngArgs {
+  mcs_params P;
+  const double *psd, *therm_sf;                   // tallies + L.psd, + L.therm_sf
+  const unsigned long long* num_crossings;
+  const double* gam_sf;                           // device grid table, n_grid+2
+  const double *pt_center, *cos_center, *cos_edge;
+  double rest_energy, gam0;
+  int therm_from_hist, n_win;
+  int l_lo[MCS_ANGLE_MAX_WINDOWS], l_hi[MCS_ANGLE_MAX_WINDOWS];      // (unused windows: 0, 0 -- they hold no bin)
+  double* out;                                    // dist [rows][NT] | number [rows] | mean_mu [rows] | mean_mu2 [rows]
+};
+
+__global__ void __launch_bounds__(256) mcs_k_angle_dist(AngArgs a) {
+  __shared__ __attribute__((aligned(16))) double s_v[ANG_CHUNK];
+  __shared__ __attribute__((aligned(16))) unsigned short s_im[ANG_CHUNK];
+  __shared__ double s_A[MCS_ANGLE_MAX_WINDOWS][KC_MAXB];
+  __shared__ double s_num[MCS_ANGLE_MAX_WINDOWS];
+  __shared__ double s_pt[KC_MAXB], s_cc[KC_MAXB];
+  const mcs_params& P = a.P;
+  const int nm = P.num_psd_mom_bins, nt = P.num_psd_tht_bins, ng = P.n_grid;
+  const int NM = nm + 2, NT = nt + 2;
+  const int z = blockIdx.x, f = blockIdx.y;       // zone (0-based), frame
+  const long long slab = (long long)NM * NT;
+  const double* psd = a.psd + slab * z;
+  const double* ths = a.therm_sf + slab * z;
+  const bool with_therm = a.therm_from_hist && a.num_crossings[z] != 0ull;
+  const double E0 = a.rest_energy;
+  const double gam = f == 1 ? a.gam_sf[z + 1] : a.gam0;
+  const double beta = gam >= 1.000001 ? __builtin_sqrt(1 - 1 / (gam * gam)) : 0.0;      // transformers.jl:639
+  for (int i = threadIdx.x; i <= nm; i += blockDim.x) s_pt[i] = a.pt_center[i];
+  for (int i = threadIdx.x; i <= nt; i += blockDim.x) s_cc[i] = a.cos_center[i];
+  const int row = threadIdx.x;                    // the target row this thread owns, if row <= nt
+  double acc[MCS_ANGLE_MAX_WINDOWS];
+#pragma unroll
+  for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) acc[m] = 0.0;
+  const int ncell = (nm + 1) * (nt + 1);
+  for (int c0 = 0; c0 < ncell; c0 += ANG_CHUNK) {
+    const int n = ncell - c0 < ANG_CHUNK ? ncell - c0 : ANG_CHUNK;
+    __syncthreads();                              // (the tables are there; the last chunk has been walked)
+    const int n_pad = (n + ANG_STEP - 1) / ANG_STEP * ANG_STEP;      // (<= ANG_CHUNK, a multiple of ANG_STEP)
+    for (int i = threadIdx.x; i < n_pad; i += blockDim.x) {
+      if (i >= n) { s_v[i] = 0.0; s_im[i] = (unsigned short)ANG_DARK; continue; }
+      const int q = c0 + i, k = q % (nm + 1), j = q / (nm + 1);
+      const int at = k + NM * j;
+      double v = 0.0;
+      if (with_therm) v = v + ths[at];
+      const double w = psd[at];
+      if (w > 1.0e-66) v = v + w;
+      unsigned int im = ANG_DARK;
+      if (v > 1.0e-66) {
+        int kX = k, jX = j;
+        if (f != 0) {
+          const double pt = s_pt[k], cs = s_cc[j];
+          const double px = pt * cs;
+          const double pc = pt * MCS_C;
+          const double et = __builtin_sqrt(pc * pc + E0 * E0);
+          const double pxX = gam * (px - beta * et / MCS_C);
+          const double ptX = __builtin_sqrt(pt * pt - px * px + pxX * pxX);
+          kX = c_bin_mom(P, ptX); jX = c_bin_ang(P, pxX, ptX);
+          kX = kX < 0 ? 0 : (kX > nm ? nm : kX);
+          jX = jX < 0 ? 0 : (jX > nt ? nt : jX);
+        }
+        unsigned int mask = 0u;
+#pragma unroll
+        for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) mask |= (kX >= a.l_lo[m] && kX < a.l_hi[m]) ? (1u << m) : 0u;
+        if (mask != 0u) im = (unsigned int)jX | (mask << 8);
+      }
+      s_v[i] = v;
+      s_im[i] = (unsigned short)im;
+    }
+    __syncthreads();
+    if (row <= nt) {
+      for (int i0 = 0; i0 < n_pad; i0 += ANG_STEP) {
+        const uint4 w = *reinterpret_cast<const uint4*>(&s_im[i0]);
+        const unsigned int ws[4] = {w.x, w.y, w.z, w.w};
+        double v[ANG_STEP];
+#pragma unroll
+        for (int u = 0; u < ANG_STEP; ++u) v[u] = s_v[i0 + u];
+#pragma unroll
+        for (int u = 0; u < ANG_STEP; ++u) {
+          const unsigned int im = (ws[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
+          if ((int)(im & 255u) != row) continue;
+#pragma unroll
+          for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) acc[m] = ((im >> (8 + m)) & 1u) ? acc[m] + v[u] : acc[m];
+        }
+      }
+    }
+  }
+  if (row <= nt) {
+#pragma unroll
+    for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) s_A[m][row] = acc[m];
+  }
+  __syncthreads();
+  const long long rows = 3LL * ng * a.n_win, row0 = ((long long)f * ng + z) * a.n_win;
+  double* o_dist = a.out;
+  double* o_num = a.out + rows * NT;
+  if ((int)threadIdx.x < a.n_win) {
+    const int m = threadIdx.x;
+    double num = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int j = 0; j <= nt; ++j) {
+      const double A = s_A[m][j];
+      const double t = A * s_cc[j];
+      num = num + A;
+      s1 = s1 + t;
+      s2 = s2 + t * s_cc[j];
+    }
+    s_num[m] = num;
+    o_num[row0 + m] = num;
+    o_num[rows + row0 + m] = num == 0.0 ? __builtin_nan("") : s1 / num;
+    o_num[2 * rows + row0 + m] = num == 0.0 ? __builtin_nan("") : s2 / num;
+  }
+  __syncthreads();
+  for (int q = threadIdx.x; q < a.n_win * NT; q += blockDim.x) {
+    const int m = q / NT, j = q % NT;
+    double d = 1.0e-99;
+    if (j <= nt) {
+      const double A = s_A[m][j];
+      if (A > 0) d = (A / s_num[m]) / (a.cos_edge[j + 1] - a.cos_edge[j]);
+    }
+    o_dist[(row0 + m) * NT + j] = d;
+  }
+}
+
 }  // namespace
 
 // Host-callable launchers (pointers are device pointers; tables were uploaded by the caller)
@@ -592,6 +729,22 @@ extern "C" hipError_t mcs_launch_dndp_esc(const mcs_params* P, const double* esc
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(mcs_k_dndp_esc_join, dim3(1), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t mcs_launch_angle_dist(const mcs_params* P, const double* psd, const double* therm_sf, const unsigned long long* num_crossings,
+                                            const double* gam_sf, const double* tabs /*pt_center|cos_center|cos_edge*/, double rest_energy,
+                                            double gam0, int therm_from_hist, int n_win, const int32_t* l_lo, const int32_t* l_hi, double* out,
+                                            hipStream_t st) {
+  AngArgs a{};
+  a.P = *P;
+  const int NM = P->num_psd_mom_bins + 2, NT = P->num_psd_tht_bins + 2;
+  a.psd = psd; a.therm_sf = therm_sf; a.num_crossings = num_crossings; a.gam_sf = gam_sf;
+  a.pt_center = tabs; a.cos_center = tabs + NM; a.cos_edge = tabs + NM + NT;
+  a.rest_energy = rest_energy; a.gam0 = gam0; a.therm_from_hist = therm_from_hist; a.n_win = n_win;
+  for (int m = 0; m < n_win; ++m) { a.l_lo[m] = l_lo[m]; a.l_hi[m] = l_hi[m]; }
+  a.out = out;
+  hipLaunchKernelGGL(mcs_k_angle_dist, dim3(P->n_grid, 3), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -25,6 +25,12 @@ struct McsCtxView {
   // it is a whole result since the last mcs_begin_species / escape sample
   const double* esc_out;
   bool have_esc;
+  // what the last mcs_angle_dist left on the device, in the layout of an angles sample (mcs_ens_angles_layout; null before the first
+  // call), whether it is a whole result since the last mcs_begin_species / tally write / angles sample, and that call's windows
+  const double* ang_out;
+  bool have_ang;
+  int ang_n_win;
+  int32_t ang_lo[MCS_ANGLE_MAX_WINDOWS], ang_hi[MCS_ANGLE_MAX_WINDOWS];
 };
 
 extern "C" {
@@ -41,6 +47,8 @@ void mcs_ctx_view_products_taken(mcs_ctx* ctx);
 void mcs_ctx_view_photons_taken(mcs_ctx* ctx);
 // An escape sample has been queued from ctx's mcs_dndp_esc result: that call has to run again before the next.
 void mcs_ctx_view_escape_taken(mcs_ctx* ctx);
+// An angles sample has been queued from ctx's mcs_angle_dist result: that call has to run again before the next.
+void mcs_ctx_view_angles_taken(mcs_ctx* ctx);
 // Sets the message of the calling thread's last error (what the ABI's error call returns); returns 1.
 int mcs_ctx_view_fail(const char* msg);
 }

@@ -13,7 +13,7 @@
 // last kernel that folds a range's partials in index order.  No atomics: the same state gives the same bits.
 // The comparison of two slots (mcs_ens_compare) is the same walk over the (mean, M2) pairs of both with a record of its own: the
 // four sweep kernels share one routine, walk, for which words a thread sees and in which order.
-// Host side: every slot of every kind -- species, iteration, products, photons, source, escape -- is one Slot (count, mean, M2); decode reads
+// Host side: every slot of every kind -- species, iteration, products, photons, source, escape, angles -- is one Slot (count, mean, M2); decode reads
 // a slot number's bits, slot_ref finds its Slot, reserve allocates it, merge_slot merges it, and plan_ranges checks the ranges of a
 // summary or comparison and lays out their blocks in one pass.
 // A context is seen through mcs_ctx_view.h; its stream carries the work, an event of the accumulator orders successive operations
@@ -667,6 +667,20 @@ void escape_layout(const mcs_params* p, mcs_ens_escape_layout* XL) {
   XL->total = 6 * nm + 12;
 }
 
+void angles_layout(const mcs_params* p, int n_win, mcs_ens_angles_layout* AL) {
+  const int64_t nt = p->num_psd_tht_bins + 2, rows = 3 * (int64_t)p->n_grid * n_win;
+  AL->row_n = nt; AL->rows = rows;
+  AL->dist = 0; AL->number = rows * nt; AL->mean_mu = rows * nt + rows; AL->mean_mu2 = rows * nt + 2 * rows;
+  AL->total = rows * nt + 3 * rows;
+}
+// the windows of an angles sample by the rules of mcs_angle_dist: null if they are good
+const char* angle_windows_error(const mcs_params* p, int n_win, const int32_t* l_lo, const int32_t* l_hi) {
+  if (n_win < 1 || n_win > MCS_ANGLE_MAX_WINDOWS) return "n_win outside 1..MCS_ANGLE_MAX_WINDOWS";
+  for (int m = 0; m < n_win; ++m)
+    if (l_lo[m] < 0 || l_lo[m] >= l_hi[m] || l_hi[m] > p->num_psd_mom_bins + 1) return "a window needs 0 <= l_lo < l_hi <= nmom + 1";
+  return nullptr;
+}
+
 void photons_layout(int n_shells, const int n[3], int n_pts, mcs_ens_photons_layout* HL) {
   const int64_t rows = (int64_t)n_shells + 1;
   HL->rows = rows; HL->n_synch = n[0]; HL->n_ic = n[1]; HL->n_pion = n[2]; HL->n_pts = n_pts;
@@ -685,25 +699,27 @@ constexpr int PRODUCTS_BIT = 1 << 30;      // MCS_ENS_PRODUCTS
 constexpr int PHOTONS_BIT = 1 << 29;       // MCS_ENS_PHOTONS
 constexpr int PHOTONS_ALL = 1 << 28;       // MCS_ENS_PHOTONS_ALL
 constexpr int ESCAPE_BIT = 1 << 27;        // MCS_ENS_ESCAPE
+constexpr int ANGLES_BIT = 1 << 26;        // MCS_ENS_ANGLES
 
-// The six kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
+// The seven kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
 // to (s; not yet held against the accumulator's species slots, slot_ref does that; -1 for the iteration and the source slot).
 // A negative number has every high bit set: it is no companion slot, and is refused as a species slot outside the range.
 // The source slot has the photons slots' vector and layout rules; it is a kind of its own in a comparison.
-enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, N_KINDS };
-const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape"};
+enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, ANGLES, N_KINDS };
+const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape", "angles"};
 struct SlotId { Kind kind; int s; };
 SlotId decode(int slot, int n_slots) {
   if (slot == PHOTONS_ALL) return SlotId{SOURCE, -1};
   if (slot >= 0 && (slot & PRODUCTS_BIT) != 0) return SlotId{PRODUCTS, slot ^ PRODUCTS_BIT};
   if (slot >= 0 && (slot & PHOTONS_BIT) != 0) return SlotId{PHOTONS, slot ^ PHOTONS_BIT};
   if (slot >= 0 && (slot & ESCAPE_BIT) != 0) return SlotId{ESCAPE, slot ^ ESCAPE_BIT};
+  if (slot >= 0 && (slot & ANGLES_BIT) != 0) return SlotId{ANGLES, slot ^ ANGLES_BIT};
   return slot == n_slots - 1 ? SlotId{ITERATION, -1} : SlotId{SPECIES, slot};
 }
 bool has_photon_vector(Kind k) { return k == PHOTONS || k == SOURCE; }
 bool has_window_vector(Kind k) { return k == PRODUCTS || k == ESCAPE; }      // (its sample holds slopes over the slope window)
 
-// What every slot is: the samples it has taken and its two vectors (those of a products, photons, source or escape slot from its first
+// What every slot is: the samples it has taken and its two vectors (those of a products, photons, source, escape or angles slot from its first
 // sample or merge on, nothing before)
 struct Slot { long long n = 0; DevBuf<double> mean, m2; };
 
@@ -741,6 +757,12 @@ struct mcs_ens {
   mcs_ens_escape_layout XL;
   std::vector<Slot> escape;
   DevBuf<double> esc_slope;                   // [2][3]
+  // the angles slots, likewise (include/mcs.h, "angles sample"): AL.total doubles per vector; no windows while ang_n_win is 0
+  mcs_ens_angles_layout AL{};
+  int ang_n_win = 0;
+  int32_t ang_lo[MCS_ANGLE_MAX_WINDOWS] = {}, ang_hi[MCS_ANGLE_MAX_WINDOWS] = {};
+  std::vector<Slot> angles;
+  bool angles_sampled = false;                // some angles slot has taken a sample (or a merge): the windows are fixed
   // the photons slots, likewise (include/mcs.h, "photons sample"): HL.total doubles per vector; no layout while ph_shells is 0
   mcs_ens_photons_layout HL{};
   int ph_shells = 0, ph_n[3] = {0, 0, 0}, ph_start[3] = {0, 0, 0}, ph_npts = 0;
@@ -753,20 +775,21 @@ struct mcs_ens {
   std::vector<int> deposited;
   bool has_photon_layout() const { return ph_shells > 0; }
   bool has_window() const { return !x_log_h.empty(); }
+  bool has_angle_windows() const { return ang_n_win > 0; }
   // the one way from a (checked) slot number to its record, and the length of the vectors of a kind
   Slot& at(SlotId id) {
     return id.kind == SOURCE ? source : id.kind == PHOTONS ? photons[(size_t)id.s] : id.kind == PRODUCTS ? products[(size_t)id.s]
-           : id.kind == ESCAPE ? escape[(size_t)id.s]
+           : id.kind == ESCAPE ? escape[(size_t)id.s] : id.kind == ANGLES ? angles[(size_t)id.s]
            : main[(size_t)(id.kind == ITERATION ? n_slots - 1 : id.s)];
   }
   long long len(Kind k) const {
-    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ITERATION ? E.it_total : E.sp_total;
+    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ANGLES ? (has_angle_windows() ? AL.total : 0) : k == ITERATION ? E.it_total : E.sp_total;
   }
   // every slot number the accumulator has
   std::vector<int> slot_numbers() const {
     std::vector<int> all;
     for (int s = 0; s < n_slots; ++s) all.push_back(s);
-    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); all.push_back(s | ESCAPE_BIT); }
+    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); all.push_back(s | ESCAPE_BIT); all.push_back(s | ANGLES_BIT); }
     all.push_back(PHOTONS_ALL);
     return all;
   }
@@ -798,11 +821,11 @@ int leave(mcs_ens* e, hipStream_t st) {
 }
 
 // What a count, read, summary or comparison call works on: the slot of that number, its kind and the length of its vectors
-// (which are null for a products, photons, source or escape slot that was never sampled; n is then 0).
+// (which are null for a products, photons, source, escape or angles slot that was never sampled; n is then 0).
 struct SlotRef { Kind kind; Slot* slot; long long len; };
 int slot_ref(mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
   const SlotId id = decode(slot, e->n_slots);
-  if ((id.kind == PRODUCTS || id.kind == PHOTONS || id.kind == ESCAPE) && id.s >= e->n_slots - 1)
+  if ((id.kind == PRODUCTS || id.kind == PHOTONS || id.kind == ESCAPE || id.kind == ANGLES) && id.s >= e->n_slots - 1)
     return fail(who + ": " + KIND_NAME[id.kind] + " slot of slot " + std::to_string(id.s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
   if (id.kind == SPECIES && (slot < 0 || slot >= e->n_slots)) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
   *out = SlotRef{id.kind, &e->at(id), e->len(id.kind)};
@@ -828,6 +851,17 @@ bool windows_differ(const mcs_ens* a, const mcs_ens* b) {
   if (!a->has_window() || !b->has_window()) return false;
   return a->win_lo != b->win_lo || a->win_hi != b->win_hi || a->x_log_h.size() != b->x_log_h.size() ||
          memcmp(a->x_log_h.data(), b->x_log_h.data(), a->x_log_h.size() * sizeof(double)) != 0;
+}
+
+// both have angle windows, and the two differ
+bool angle_windows_differ(const mcs_ens* a, const mcs_ens* b) {
+  if (!a->has_angle_windows() || !b->has_angle_windows()) return false;
+  return a->ang_n_win != b->ang_n_win || memcmp(a->ang_lo, b->ang_lo, sizeof a->ang_lo) != 0 || memcmp(a->ang_hi, b->ang_hi, sizeof a->ang_hi) != 0;
+}
+void angle_windows_take(mcs_ens* e, int n_win, const int32_t* l_lo, const int32_t* l_hi) {
+  e->ang_n_win = n_win;
+  for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) { e->ang_lo[m] = m < n_win ? l_lo[m] : 0; e->ang_hi[m] = m < n_win ? l_hi[m] : 0; }
+  angles_layout(&e->P, n_win, &e->AL);
 }
 
 // both have a photon layout, and the two differ
@@ -993,6 +1027,7 @@ int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   e->photons.resize((size_t)n_species_slots);
   escape_layout(&v.P, &e->XL);
   e->escape.resize((size_t)n_species_slots);
+  e->angles.resize((size_t)n_species_slots);
   const mcs_layout& L = v.L;
   e->inc = IncRanges{{L.esc_flux, L.esc_energy_eff, L.spectra_coupled}, {L.px_esc_feb, L.weight_coupled, L.energy_transfer_pool}};
   e->n_slots = n_species_slots + 1;
@@ -1139,6 +1174,46 @@ int mcs_ens_add_escape(mcs_ens* e, mcs_ctx* src, int slot) {
   return leave(e, v.stream);
 }
 
+int mcs_ens_angles_get_layout(const mcs_params* p, int n_win, mcs_ens_angles_layout* out) {
+  if (!p || !out) return fail("mcs_ens_angles_get_layout: null argument");
+  if (n_win < 1 || n_win > MCS_ANGLE_MAX_WINDOWS) return fail("mcs_ens_angles_get_layout: n_win outside 1.." + std::to_string(MCS_ANGLE_MAX_WINDOWS));
+  angles_layout(p, n_win, out);
+  return 0;
+}
+
+int mcs_ens_set_angle_windows(mcs_ens* e, int n_win, const int32_t* l_lo, const int32_t* l_hi) {
+  const std::string who = "mcs_ens_set_angle_windows";
+  if (!e || !l_lo || !l_hi) return fail(who + ": null argument");
+  if (e->angles_sampled) return fail(who + ": an angles slot has taken a sample; the windows stay as they are");
+  if (const char* msg = angle_windows_error(&e->P, n_win, l_lo, l_hi)) return fail(who + ": " + msg);
+  angle_windows_take(e, n_win, l_lo, l_hi);
+  return 0;
+}
+
+int mcs_ens_add_angles(mcs_ens* e, mcs_ctx* src, int slot) {
+  const std::string who = "mcs_ens_add_angles";
+  if (!e || !src) return fail(who + ": null argument");
+  if (species_slot(e, who, slot, "only a species slot has an angles slot")) return 1;
+  if (!e->has_angle_windows()) return fail(who + ": no angle windows (mcs_ens_set_angle_windows)");
+  McsCtxView v;
+  if (view_of(e, src, who.c_str(), &v)) return 1;
+  if (!v.have_ang || !v.ang_out)
+    return fail(who + ": the context needs an mcs_angle_dist since its last mcs_begin_species, tally write and angles sample");
+  if (v.ang_n_win != e->ang_n_win || memcmp(v.ang_lo, e->ang_lo, sizeof e->ang_lo) != 0 || memcmp(v.ang_hi, e->ang_hi, sizeof e->ang_hi) != 0)
+    return fail(who + ": the windows of the context's mcs_angle_dist differ from the accumulator's");
+  if (enter(e, v.stream)) return 1;
+  Slot& sl = e->angles[(size_t)slot];
+  if (reserve(sl, e->AL.total, who, v.stream)) return 1;
+  // the sample is the call's result as it lies on the device
+  hipLaunchKernelGGL(mcs_k_ens_add_vector, dim3(grid_for(e->AL.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), v.ang_out,
+                     (long long)e->AL.total, (double)(sl.n + 1));
+  ENSCHK(hipGetLastError());
+  sl.n += 1;
+  e->angles_sampled = true;
+  mcs_ctx_view_angles_taken(src);
+  return leave(e, v.stream);
+}
+
 int mcs_ens_photons_get_layout(int n_shells, int n_synch, int n_ic, int n_pion, int n_pts, mcs_ens_photons_layout* out) {
   if (!out) return fail("mcs_ens_photons_get_layout: null argument");
   const int n[3] = {n_synch, n_ic, n_pion}, start[3] = {0, 0, 0};
@@ -1236,6 +1311,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (dst->n_slots != src->n_slots || !same_layout(dst, src)) return fail("mcs_ens_merge: the accumulators' slots or layouts differ");
   if (windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' slope windows differ");
   if (photon_layouts_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' photon layouts differ");
+  if (angle_windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' angle windows differ");
   McsCtxView v;
   if (mcs_ctx_view_get(dst->home, &v)) return 1;
   const std::vector<int> slots = dst->slot_numbers();
@@ -1257,6 +1333,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
     dst->x_log_h = src->x_log_h; dst->win_lo = src->win_lo; dst->win_hi = src->win_hi;
   }
   if (any_photons && !dst->has_photon_layout()) photon_layout_take(dst, src->ph_shells, src->ph_n, src->ph_start, src->ph_npts);
+  if (any[ANGLES] && !dst->has_angle_windows()) angle_windows_take(dst, src->ang_n_win, src->ang_lo, src->ang_hi);
   // (the source slot merges like a photons slot; what is pending on either side stays where it is)
   for (int slot : slots) {
     const SlotId id = decode(slot, dst->n_slots);
@@ -1264,6 +1341,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   }
   dst->products_sampled = dst->products_sampled || any_products;
   dst->photons_sampled = dst->photons_sampled || any_photons;
+  dst->angles_sampled = dst->angles_sampled || any[ANGLES];
   if (leave(dst, v.stream)) return 1;
   return leave(src, v.stream);
 }
@@ -1337,6 +1415,12 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
       for (int j = 0; j < k; ++j)
         if (windows_differ(ens[j], ens[k])) return fail(who + ": the accumulators' slope windows differ");
   long long len = sr.len;
+  if (sr.kind == ANGLES)
+    for (int k = 1; k < n_ens; ++k) {
+      for (int j = 0; j < k; ++j)
+        if (angle_windows_differ(ens[j], ens[k])) return fail(who + ": the accumulators' angle windows differ");
+      if (ens[k]->len(sr.kind) > len) len = ens[k]->len(sr.kind);      // (an accumulator without windows has no angles sample)
+    }
   if (has_photon_vector(sr.kind))
     for (int k = 1; k < n_ens; ++k) {
       for (int j = 0; j < k; ++j)
@@ -1396,6 +1480,10 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   if (has_window_vector(ra.kind)) {
     if (sa.n == 0 || sb.n == 0) return fail(who + (ra.kind == ESCAPE ? ": an escape" : ": a products") + " slot has never taken a sample");
     if (windows_differ(a, b)) return fail(who + ": the accumulators' slope windows differ");
+  }
+  if (ra.kind == ANGLES) {
+    if (sa.n == 0 || sb.n == 0) return fail(who + ": an angles slot has never taken a sample");
+    if (angle_windows_differ(a, b)) return fail(who + ": the accumulators' angle windows differ");
   }
   if (has_photon_vector(ra.kind)) {
     if (sa.n == 0 || sb.n == 0) return fail(who + ": a photons slot has never taken a sample");

@@ -48,6 +48,9 @@ hipError_t mcs_launch_dndp_cr(const mcs_params* P, const double* psd, const doub
                               double rest_energy, double n0, double gam0, double* out_dndp, unsigned long long* diag, hipStream_t st);
 hipError_t mcs_launch_dndp_esc(const mcs_params* P, const double* esc, const double* tabs, double rest_energy, const double gam_pf[2], double gam0,
                                double* rows, unsigned int* row_diag, double* out, unsigned long long* diag, hipStream_t st);
+hipError_t mcs_launch_angle_dist(const mcs_params* P, const double* psd, const double* therm_sf, const unsigned long long* num_crossings,
+                                 const double* gam_sf, const double* tabs, double rest_energy, double gam0, int therm_from_hist, int n_win,
+                                 const int32_t* l_lo, const int32_t* l_hi, double* out, hipStream_t st);
 hipError_t mcs_launch_dndp_2d(const mcs_params* P, const double* psd, const double* therm_sf, const unsigned long long* num_crossings, const double* tabs,
                               double rest_energy, double n0, int therm_from_hist, double gam_x, double beta_x, double* scratch, double* ef, hipStream_t st);
 hipError_t mcs_launch_photon_ic(const double* ef, const double* p_edge, const double* field, int n_grid, int NM, int NT, int j_max, int n_nu, int n_photon,

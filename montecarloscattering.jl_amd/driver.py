@@ -83,6 +83,7 @@ class RunResult:
     convergence: object = None    # a Convergence: what run / run_overlapped(triggers=...) checked and where it stopped; None without triggers
     photons: object = None        # [consumers.ObservedSpectra], one per species, of the last iteration (run(photons=...)); None without
     escape: object = None         # [(i_iter, i_ion, consumers.EscapeSpectra)] of every species end (run(escape=True)); None without
+    angles: object = None         # [(i_iter, i_ion, consumers.AngleDistributions)] of every species end (run(angles=[...])); None without
 
 
 @dataclasses.dataclass
@@ -652,6 +653,20 @@ def _species_escape(rs, be, i_iter, i_ion):
         rs.ensemble.add_escape(be, i_ion - 1, spec)
 
 
+def _species_angles(rs, be, i_iter, i_ion):
+    """The pitch-angle distributions of species i_ion over the run's momentum windows (run(angles=[...]); K11 on a HIP backend), from
+    the psd and thermal tallies of the context that transported it -- per-species sections, before the context's next begin_species
+    clears them.  With an ensemble, one angles sample into Ensemble.angles_slot(i_ion - 1)."""
+    if not rs.is_root:
+        return
+    dist = consumers.angle_distributions(rs.prob, be, i_ion, rs.angle_windows)
+    rs.angles.append((i_iter, i_ion, dist))
+    if rs.ensemble is not None:
+        if not rs.ensemble.has_angle_windows():
+            rs.ensemble.set_angle_windows([w[0] for w in rs.angle_windows], [w[1] for w in rs.angle_windows])
+        rs.ensemble.add_angles(be, i_ion - 1, dist)
+
+
 def _iteration_species(rs, i_iter, before_pcut):
     """The species of iteration i_iter in order: its transport (here, or with secondaries on the pool's threads as the
     scheduler places it), its merge into the primary if it ran on a secondary, its species end."""
@@ -662,6 +677,8 @@ def _iteration_species(rs, i_iter, before_pcut):
             _species_end(rs, 0, i_iter, i_ion)
             if rs.do_escape:
                 _species_escape(rs, rs.backend, i_iter, i_ion)      # (after the ranks' merge: rank 0 holds the whole slabs)
+            if rs.angle_windows is not None:
+                _species_angles(rs, rs.backend, i_iter, i_ion)
             if rs.photons is not None:
                 _species_photons(rs, i_iter, i_ion)
         return
@@ -671,6 +688,8 @@ def _iteration_species(rs, i_iter, before_pcut):
             k, out_stats, out_empty, t0, t1 = sched.result(i_ion)
             if rs.do_escape:
                 _species_escape(rs, rs.ctxs[k], i_iter, i_ion)      # (the slabs do not travel with the running sums)
+            if rs.angle_windows is not None:
+                _species_angles(rs, rs.ctxs[k], i_iter, i_ion)      # (nor do the histograms)
             if k > 0 and hasattr(rs.backend, "accumulate_tallies_from") and type(rs.ctxs[k]) is type(rs.backend):
                 rs.backend.accumulate_tallies_from(rs.ctxs[k])      # its running sums added to the primary's and cleared
             elif k > 0:
@@ -690,7 +709,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
         long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None,
         ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1, photons=None,
-        escape: bool = False) -> RunResult:
+        escape: bool = False, angles=None) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -780,6 +799,13 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     slope; an ensemble without a slope window first gets one over all bins); triggers may name its parts, with
     zones=Ensemble.escape_row(door, frame) for one door and frame and bins= for a momentum window of that row.
     Refused: escape without finalize, a trigger on an escape slot without escape.
+    angles: [(p_lo, p_hi), ...], up to eight momentum windows in cgs (consumers.momentum_windows).  After every species' last pcut, on
+    the context that transported it, consumers.angle_distributions: the pitch-angle distribution of every grid zone over every window
+    in the shock frame, the zone's plasma frame and the ISM frame, with <mu> and <mu^2> (K11 on a HIP backend).  RunResult.angles holds
+    [(i_iter, i_ion, AngleDistributions)].  With ensemble, one ANGLES sample per species and iteration goes into
+    Ensemble.angles_slot(i_ion - 1) (ensemble.py, "Angles": dist, number, mean_mu, mean_mu2; an ensemble without angle windows first
+    gets the run's); triggers may name its parts, with zones=ensemble.angles_row(frame, zone, window) for one row and bins= for angle
+    bins of that dist row.  Refused: angles without finalize, a trigger on an angles slot without angles.  None: nothing of this runs.
     """
     import torch
     comm = comm or Comm(False)
@@ -809,6 +835,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         verbose=verbose, gather_max=gather_max, skew_max=skew_max, fused_pcuts=fused_pcuts, fused_chunk=fused_chunk,
         long_draws=long_draws, long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
         photons=photons, photon_spectra=[None] * len(cfg.species), last_ion_fin=None, do_escape=bool(escape), escape=[],
+        angle_windows=None, angles=[],
         G_f=None, G_i=None, G_pool=None, stats=[], per_species=[], local_steps=[], empty_launches=[], species_spans=[], iter_finals=[])
     # the step counters are never reset: this rank's running total.  A context that has run before (run() called again with
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
@@ -835,6 +862,14 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             raise ValueError("photons: needs finalize=True (the spectra are made from ion_finalize's dN/dp)")
         if ensemble is not None and ensemble.photon_layout is None:
             ensemble.set_photon_layout(consumers.stock_photon_layout(photons.n_shells))
+    if angles is not None:
+        if not (finalize or smoothing is not None):
+            raise ValueError("angles: needs finalize=True (the pitch-angle distributions belong to the iteration's finalize step)")
+        rs.angle_windows = consumers.momentum_windows(prob, angles)
+        if ensemble is not None and not ensemble.has_angle_windows():      # (before the triggers are held against the ensemble's parts)
+            ensemble.set_angle_windows([w[0] for w in rs.angle_windows], [w[1] for w in rs.angle_windows])
+    elif any(ens.Ensemble.is_angles(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on an angles slot needs angles=[...] (no sample would ever arrive)")
     if triggers:
         _check_trigger_args(ensemble is not None, "ensemble=", min_iterations, check_every)
         for t in triggers:
@@ -942,7 +977,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     return RunResult(rs.G_f, rs.G_i, rs.per_species, rs.stats, *_steps(rs.G_i, P.n_grid), rs.iter_finals, it_state,
                      rs.local_steps, rs.empty_launches, rs.species_spans, options, ensemble,
                      Convergence(checks, stopped_at, satisfied) if triggers else None,
-                     list(rs.photon_spectra) if photons is not None else None, rs.escape if escape else None)
+                     list(rs.photon_spectra) if photons is not None else None, rs.escape if escape else None,
+                     rs.angles if angles is not None else None)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over
@@ -954,7 +990,7 @@ ACCUMULATED_OVER_ITERATIONS = ("esc_flux", "px_esc_feb", "energy_esc_feb", "esc_
 def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pcuts: Optional[int] = None,
                    on_iteration_end: Optional[Callable] = None, first_iter: int = 1,
                    blocks_per_launch: Optional[int] = None, ensemble: bool = False, triggers: Optional[list] = None,
-                   min_iterations: int = 2, check_every: int = 1, photons=None, escape: bool = False) -> RunResult:
+                   min_iterations: int = 2, check_every: int = 1, photons=None, escape: bool = False, angles=None) -> RunResult:
     """The iterations of a run with a FIXED shock profile (smooth-shocks = false -- the stock mc_in.toml, BASELINE
     config[1]) are independent Monte-Carlo realisations: nothing an iteration computes enters the next one's transport
     (src/main_loops.jl:52-121: every tally the transport reads is reset at the top; the RNG keys carry i_iter).  Their
@@ -1000,7 +1036,10 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     source slot like every other; an ensemble gets consumers.stock_photon_layout(photons.n_shells).  RunResult.photons holds the
     spectra of the last iteration consumed.  Refused: a trigger on a photons slot or on the source slot without photons=.  None:
     no spectra are made.
-    escape: refused -- the escape spectra of run(escape=True) are left out of the overlapped path."""
+    escape: refused -- the escape spectra of run(escape=True) are left out of the overlapped path.
+    angles: refused likewise -- the pitch-angle distributions of run(angles=[...]) are left out of the overlapped path."""
+    if angles is not None or any(ens.Ensemble.is_angles(t.slot) for t in (triggers or [])):
+        raise ValueError("angles: the overlapped run leaves the pitch-angle distributions out; use run(finalize=True, angles=[...])")
     if escape or any(ens.Ensemble.is_escape(t.slot) for t in (triggers or [])):
         raise ValueError("escape: the overlapped run leaves the escape spectra out; use run(finalize=True, escape=True)")
     cfg, P = prob.cfg, prob.params

@@ -58,6 +58,23 @@ slot `Ensemble.escape_slot(s)`, whose vectors exist from its first sample on.  I
 zones=Ensemble.escape_row(door, frame) of a `Request` or `Trigger` selects one door and frame, bins= a momentum window of that dNdp
 row.  The slope window is shared with the products slots: it is fixed from the first products or escape sample on.
 
+Angles (include/mcs.h, "angles sample"): the pitch-angle distributions of consumers.angle_distributions (K11), sampled once per species
+and iteration by driver.run(finalize=True, angles=[(p_lo, p_hi), ...], ensemble=...).  Every species slot s has a fourth companion, the
+angles slot `Ensemble.angles_slot(s)`, whose vectors exist from its first sample on.  The ensemble holds the momentum windows of its
+angles samples (`set_angle_windows`; consumers.momentum_windows makes them from cgs momenta): they may be set again until the first
+angles sample and are fixed from then on; merge, summarize_merged and compare refuse ensembles whose windows differ, and a merge
+into an ensemble without windows gives it the source's.  Its parts have as first axis the row (frame * n_grid + zone) * n_win + window
+(frame 0: shock, 1: the zone's plasma frame, 2: ISM; zone 0-based):
+
+  dist      [rows][ntht+2]: the normalised distribution over the angle bins, 1e-99 in an empty bin
+  number    [rows]: the summed weight of the window
+  mean_mu   [rows]: <mu>
+  mean_mu2  [rows]: <mu^2>
+
+zones=Ensemble.angles_row(frame, zone, window) of a `Request`, `Trigger`, `CompareRequest` or `Agreement` selects one row, bins= angle
+bins of that dist row.  A window that no particle reached has NaN moments in that sample: the word's mean stays non-finite, a summary
+counts it in n_nonfinite and a trigger over it is never met -- windows belong on zones and momenta that the population reaches.
+
 Photons (include/mcs.h, "photons sample"): the photon spectra at Earth per photon shell, consumers.observed_spectra.  A shell spectrum is
 a sum over zones, slices in cos(theta) and processes, so its variance does not follow from per-cell variances either: every species
 slot s has a second companion, `Ensemble.photons_slot(s)`, sampled once per iteration (`add_photons`) and allocated at its first
@@ -150,6 +167,13 @@ ESCAPE_ROWS = 6
 ZONE_PARTS = ZONE_PARTS + ESCAPE_NAMES
 BIN_PARTS = BIN_PARTS + ("dNdp",)
 ESCAPE_BIT = capi.ENS_ESCAPE_BIT          # escape slot of species slot s: s | ESCAPE_BIT (MCS_ENS_ESCAPE)
+# the parts of an angles slot, in the order of mcs_ens_angles_layout: first axis the row (frame * n_grid + zone) * n_win + window
+# (zones=; Ensemble.angles_row), dist's second the angle bin (bins=)
+ANGLES_NAMES = ("dist", "number", "mean_mu", "mean_mu2")
+ANGLE_MAX_WINDOWS = 8                     # MCS_ANGLE_MAX_WINDOWS
+ZONE_PARTS = ZONE_PARTS + tuple(n for n in ANGLES_NAMES if n not in ZONE_PARTS)
+BIN_PARTS = BIN_PARTS + ("dist",)
+ANGLES_BIT = capi.ENS_ANGLES_BIT          # angles slot of species slot s: s | ANGLES_BIT (MCS_ENS_ANGLES)
 
 
 class EnsLayout:
@@ -197,6 +221,18 @@ class EnsLayout:
                                                      "slope": (ESCAPE_ROWS * nm + ESCAPE_ROWS, (ESCAPE_ROWS,))}
         self.escape_total = ESCAPE_ROWS * nm + 2 * ESCAPE_ROWS
         self.escape_fields = dict(dNdp=0, number=ESCAPE_ROWS * nm, slope=ESCAPE_ROWS * nm + ESCAPE_ROWS, row_n=nm, total=self.escape_total)
+
+    def angles(self, n_win: int) -> Dict[str, Tuple[int, tuple]]:
+        """The angles sample of n_win windows: mirror of `mcs_ens_angles_get_layout` (the one layout that depends on a setting)."""
+        nt = self.tally.shapes["psd"][1]
+        rows = 3 * self.tally.n_grid * int(n_win)
+        return {"dist": (0, (rows, nt)), "number": (rows * nt, (rows,)), "mean_mu": (rows * nt + rows, (rows,)),
+                "mean_mu2": (rows * nt + 2 * rows, (rows,))}
+
+    def angles_fields(self, n_win: int) -> Dict[str, int]:
+        t = self.angles(n_win)
+        rows, nt = t["dist"][1]
+        return dict(dist=0, number=t["number"][0], mean_mu=t["mean_mu"][0], mean_mu2=t["mean_mu2"][0], row_n=nt, rows=rows, total=rows * (nt + 3))
 
     def species_sample(self, f: np.ndarray, i: np.ndarray) -> np.ndarray:
         """The species sample of the tally buffers (f, i).  The marginals are serial sums in ascending index order, one index
@@ -276,10 +312,10 @@ def stats_over(samples):
 def _check_part(name: str, zones, bins=None):
     """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis, a bins
     window is a pair, comes with a single zone and the part has a bins axis."""
-    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES:
+    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES + ANGLES_NAMES:
         raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}; "
                          f"a products slot: {', '.join(PRODUCT_NAMES)}; a photons slot: {', '.join(PHOTON_NAMES)}; "
-                         f"an escape slot: {', '.join(ESCAPE_NAMES)}")
+                         f"an escape slot: {', '.join(ESCAPE_NAMES)}; an angles slot: {', '.join(ANGLES_NAMES)}")
     if bins is not None:
         if name not in BIN_PARTS:
             raise ValueError(f"ensemble: {name!r} has no [zone][bins] shape; a bins window fits: {', '.join(BIN_PARTS)}")
@@ -609,6 +645,18 @@ def slopes_of(dndp: np.ndarray, l_lo: int, l_hi: int, x_log: np.ndarray, log10) 
     return slope.reshape(d.shape[:-1])
 
 
+def check_angle_windows(nmom: int, l_lo, l_hi) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """The momentum windows of mcs_angle_dist as two tuples of ints, or the ValueError that says which rule they break: 1..8 windows,
+    0 <= l_lo < l_hi <= nmom + 1."""
+    lo, hi = list(l_lo), list(l_hi)
+    if len(lo) != len(hi) or not 1 <= len(lo) <= ANGLE_MAX_WINDOWS:
+        raise ValueError(f"ensemble: 1..{ANGLE_MAX_WINDOWS} angle windows, each with its l_lo and l_hi, not {len(lo)} and {len(hi)}")
+    for a, b in zip(lo, hi):
+        if int(a) != a or int(b) != b or not 0 <= a < b <= nmom + 1:
+            raise ValueError(f"ensemble: angle window ({a}, {b}) needs integers 0 <= l_lo < l_hi <= {nmom + 1}")
+    return tuple(int(a) for a in lo), tuple(int(b) for b in hi)
+
+
 class Ensemble:
     """What both kinds have in common: the slots, the named views of a slot's vectors."""
 
@@ -622,6 +670,7 @@ class Ensemble:
         self.finalize_count = 0
         self.window = None             # (l_lo, l_hi, x_log) of set_slope_window
         self.photon_layout = None      # consumers.PhotonLayout of set_photon_layout
+        self.angle_windows = None      # ((l_lo, ...), (l_hi, ...)) of set_angle_windows
         self._deposited: List[int] = []      # species slots deposited since the last add_photons_all, in deposit order
 
     @staticmethod
@@ -669,6 +718,43 @@ class Ensemble:
             raise ValueError(f"ensemble: an escape slot has doors 0, 1 and frames 0, 1, 2, not door {door!r}, frame {frame!r}")
         return 3 * door + frame, 3 * door + frame + 1
 
+    def angles_slot(self, s: int) -> int:
+        """The slot number of the pitch-angle distributions of species slot s (MCS_ENS_ANGLES)."""
+        if not 0 <= s < self.n_species:
+            raise ValueError(f"ensemble: slot {s} is no species slot (0..{self.n_species - 1}); only a species slot has an angles slot")
+        return int(s) | ANGLES_BIT
+
+    @staticmethod
+    def is_angles(slot: int) -> bool:
+        return slot >= 0 and slot != PHOTONS_ALL and not slot & (PRODUCTS_BIT | PHOTONS_BIT | ESCAPE_BIT) and bool(slot & ANGLES_BIT)
+
+    def angles_row(self, frame: int, zone: int, window: int) -> Tuple[int, int]:
+        """zones= of one frame (0: shock, 1: the zone's plasma frame, 2: ISM), grid zone (0-based) and momentum window of an angles
+        slot's parts: the row (frame * n_grid + zone) * n_win + window."""
+        if self.angle_windows is None:
+            raise ValueError("ensemble: no angle windows (set_angle_windows)")
+        ng, n_win = self.layout.tally.n_grid, len(self.angle_windows[0])
+        if frame not in (0, 1, 2) or not 0 <= zone < ng or not 0 <= window < n_win or int(zone) != zone or int(window) != window:
+            raise ValueError(f"ensemble: an angles slot has frames 0, 1, 2, zones 0..{ng - 1} and windows 0..{n_win - 1}, not frame {frame!r}, "
+                             f"zone {zone!r}, window {window!r}")
+        r = (int(frame) * ng + int(zone)) * n_win + int(window)
+        return r, r + 1
+
+    def set_angle_windows(self, l_lo, l_hi):
+        """The momentum windows l_lo[m] <= k < l_hi[m] of the angles samples (consumers.momentum_windows builds them; the rules of
+        mcs_angle_dist: 1..8 windows, 0 <= l_lo < l_hi <= nmom + 1, they may overlap).  May be repeated until the first angles sample;
+        refused afterwards."""
+        lo, hi = check_angle_windows(self.layout.tally.shapes["psd"][2] - 2, l_lo, l_hi)
+        self._set_angle_windows(lo, hi)
+        self.angle_windows = (lo, hi)
+
+    def has_angle_windows(self) -> bool:
+        return self.angle_windows is not None
+
+    @staticmethod
+    def _angle_windows_differ(a, b) -> bool:
+        return a.angle_windows is not None and b.angle_windows is not None and a.angle_windows != b.angle_windows
+
     photons_all_slot = PHOTONS_ALL     # the source slot, one per ensemble (MCS_ENS_PHOTONS_ALL)
 
     @staticmethod
@@ -700,7 +786,7 @@ class Ensemble:
         self.photon_layout = layout
 
     def _decode(self, slot: int) -> Tuple[str, Optional[int]]:
-        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source" or "escape" -- the one place where
+        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source", "escape" or "angles" -- the one place where
         its bits are read; the index is None for the iteration and the source slot, and not yet checked (`_check_slot`)."""
         if self.is_photons_all(slot):
             return "source", None
@@ -710,6 +796,8 @@ class Ensemble:
             return "photons", slot ^ PHOTONS_BIT
         if self.is_escape(slot):
             return "escape", slot ^ ESCAPE_BIT
+        if self.is_angles(slot):
+            return "angles", slot ^ ANGLES_BIT
         return ("iteration", None) if slot == self.iteration_slot else ("species", slot)
 
     def _kind(self, slot: int) -> str:
@@ -717,17 +805,18 @@ class Ensemble:
 
     def _describe(self, slot: int) -> str:
         kind, s = self._decode(slot)
-        if kind in ("products", "photons", "escape"):
+        if kind in ("products", "photons", "escape", "angles"):
             return f"the {kind} slot of species slot {s}"
         return f"species slot {s}" if kind == "species" else f"the {kind} slot"
 
     def names(self, slot: int):
         self._check_slot(slot)
-        return {"species": SPECIES_NAMES, "iteration": ITERATION_NAMES, "products": PRODUCT_NAMES, "escape": ESCAPE_NAMES}.get(self._kind(slot), PHOTON_NAMES)
+        return {"species": SPECIES_NAMES, "iteration": ITERATION_NAMES, "products": PRODUCT_NAMES, "escape": ESCAPE_NAMES,
+                "angles": ANGLES_NAMES}.get(self._kind(slot), PHOTON_NAMES)
 
     def _check_slot(self, slot: int):
         kind, s = self._decode(slot)
-        if kind in ("products", "photons", "escape") and not 0 <= s < self.n_species:
+        if kind in ("products", "photons", "escape", "angles") and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: {kind} slot of slot {s}, which is no species slot (0..{self.n_species - 1})")
         if kind == "species" and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: slot {slot} outside 0..{self.n_species}")
@@ -736,6 +825,8 @@ class Ensemble:
         kind = self._kind(slot)
         if kind in ("photons", "source"):
             return 0 if self.photon_layout is None else self.photon_layout.offsets()["_total"]
+        if kind == "angles":
+            return 0 if self.angle_windows is None else self.layout.angles_fields(len(self.angle_windows[0]))["total"]
         return {"species": self.layout.species_total, "iteration": self.layout.iteration_total, "products": self.layout.products_total,
                 "escape": self.layout.escape_total}[kind]
 
@@ -748,6 +839,10 @@ class Ensemble:
             rows = self.photon_layout.rows
             offs = self.photon_layout.offsets()
             table = {part: (offs[part][0], (rows, offs[part][1])) for part in PHOTON_NAMES}
+        elif kind == "angles":
+            if self.angle_windows is None:
+                raise ValueError(f"ensemble: {self._describe(slot)} has no windows yet (set_angle_windows)")
+            table = self.layout.angles(len(self.angle_windows[0]))
         else:
             table = {"species": self.layout.species, "iteration": self.layout.iteration, "products": self.layout.products,
                      "escape": self.layout.escape}[kind]
@@ -964,6 +1059,26 @@ class HostEnsemble(Ensemble):
         if self._sampled("products", "escape"):
             raise ValueError("ensemble: a products or escape slot has taken a sample; the slope window stays as it is")
 
+    def _set_angle_windows(self, l_lo, l_hi):
+        if self._sampled("angles"):
+            raise ValueError("ensemble: an angles slot has taken a sample; the angle windows stay as they are")
+
+    def add_angles(self, backend, slot: int, angles):
+        """One angles sample of species slot `slot` from an `AngleDistributions` (consumers.angle_distributions) made with this
+        ensemble's windows."""
+        self._species_slot(slot, "an angles slot")
+        if self.angle_windows is None:
+            raise ValueError("ensemble: no angle windows (set_angle_windows)")
+        if angles is None:
+            raise ValueError("ensemble: the numpy ensemble takes its angles sample from an AngleDistributions")
+        if tuple(tuple(int(v) for v in w) for w in angles.windows) != tuple(zip(*self.angle_windows)):
+            raise ValueError("ensemble: the windows of the AngleDistributions differ from the ensemble's")
+        x = np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in (angles.dist, angles.number, angles.mean_mu, angles.mean_mu2)])
+        if x.size != self._len(self.angles_slot(slot)):
+            raise ValueError(f"ensemble: the AngleDistributions holds {x.size} words; an angles sample has {self._len(self.angles_slot(slot))}")
+        with np.errstate(invalid="ignore"):          # (a NaN moment stays NaN)
+            self._sample(self.angles_slot(slot), x)
+
     def add_escape(self, backend, slot: int, spectra):
         """One escape sample of species slot `slot` from an `EscapeSpectra` (consumers.escape_spectra on `backend`), the slopes of its
         six rows by the backend's deterministic log10."""
@@ -1030,11 +1145,15 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: merge of ensembles whose slope windows differ")
         if self._photon_layouts_differ(self, other):
             raise ValueError("ensemble: merge of ensembles whose photon layouts differ")
+        if self._angle_windows_differ(self, other):
+            raise ValueError("ensemble: merge of ensembles whose angle windows differ")
         # an ensemble without a photon layout or a slope window takes the one its samples were made with
         if other._sampled("photons", "source") and self.photon_layout is None:
             self.photon_layout = other.photon_layout
         if other._sampled("products", "escape") and self.window is None:
             self.window = other.window
+        if other._sampled("angles") and self.angle_windows is None:
+            self.angle_windows = other.angle_windows
         for k, b in other._slots.items():      # (what is pending for the source slot on either side stays where it is)
             if b.n == 0:
                 continue
@@ -1071,6 +1190,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: a merged summary of ensembles whose slope windows differ")
         if self._has_photon_vector(slot) and any(self._photon_layouts_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose photon layouts differ")
+        if self.is_angles(slot) and any(self._angle_windows_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
+            raise ValueError("ensemble: a merged summary of ensembles whose angle windows differ")
         for first, count, floor_frac, tol in ranges:
             m, q, na = None, None, 0
             for e in [self] + others:
@@ -1088,6 +1209,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: a comparison of ensembles whose slope windows differ")
         if self._has_photon_vector(slot) and self._photon_layouts_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose photon layouts differ")
+        if self.is_angles(slot) and self._angle_windows_differ(self, other):
+            raise ValueError("ensemble: a comparison of ensembles whose angle windows differ")
         (ma, qa, _), (mb, qb, _) = self._vectors(slot), other._vectors(other_slot)
         return [difference_of(ma[first:first + count], qa[first:first + count], n_a, mb[first:first + count], qb[first:first + count], n_b,
                               floor_frac, zcut) for first, count, floor_frac, zcut in ranges]
@@ -1151,6 +1274,15 @@ class HipEnsemble(Ensemble):
         (mcs_ens_add_escape); nothing crosses to the host, `spectra` is not read."""
         self._chk(self.lib.mcs_ens_add_escape(self.h, backend.h, int(slot)))
 
+    def _set_angle_windows(self, l_lo, l_hi):
+        lo, hi = np.asarray(l_lo, dtype=np.int32), np.asarray(l_hi, dtype=np.int32)
+        self._chk(self.lib.mcs_ens_set_angle_windows(self.h, len(lo), lo.ctypes.data_as(capi.c_int32_p), hi.ctypes.data_as(capi.c_int32_p)))
+
+    def add_angles(self, backend: HipBackend, slot: int, angles=None):
+        """One angles sample of species slot `slot` from what mcs_angle_dist (consumers.angle_distributions) left on the backend's
+        device (mcs_ens_add_angles); nothing crosses to the host, `angles` is not read."""
+        self._chk(self.lib.mcs_ens_add_angles(self.h, backend.h, int(slot)))
+
     def _set_photon_layout(self, layout):
         self._chk(self.lib.mcs_ens_set_photon_layout(self.h, *layout.args()))
 
@@ -1183,6 +1315,8 @@ class HipEnsemble(Ensemble):
         if self.window is None and other.window is not None and any(
                 other.count(other.products_slot(s)) or other.count(other.escape_slot(s)) for s in range(other.n_species)):
             self.window = other.window      # (as the library does: an accumulator without a window takes the one its samples were made with)
+        if self.angle_windows is None and other.angle_windows is not None and any(other.count(other.angles_slot(s)) for s in range(other.n_species)):
+            self.angle_windows = other.angle_windows      # (likewise)
 
     def count(self, slot: int) -> int:
         n = ct.c_int64(0)

@@ -369,6 +369,22 @@ class HipBackend:
         self._chk(self.lib.mcs_dndp_esc(self.h, ct.byref(s), _dp(g), _dp(out), _dp(number), diag.ctypes.data_as(c_int64_p)))
         return out, number, diag
 
+    def angle_dist(self, tabs, l_lo, l_hi):
+        """K11: the pitch-angle distributions of every zone over the momentum windows l_lo[m] <= k < l_hi[m], from the resident
+        tallies -> (dist [3][n_grid][n_win][ntht+2], number [3][n_grid][n_win], moments [3][n_grid][n_win][2]); frame (shock, the
+        zone's plasma frame, ISM)."""
+        lo = np.ascontiguousarray(l_lo, dtype=np.int32); hi = np.ascontiguousarray(l_hi, dtype=np.int32)
+        if lo.ndim != 1 or lo.shape != hi.shape:
+            raise ValueError("angle_dist: l_lo and l_hi hold one bin index per window")
+        n_win, ng = len(lo), self.P.n_grid
+        dist = np.zeros((3, ng, max(n_win, 1), self.P.num_psd_tht_bins + 2))
+        number = np.zeros((3, ng, max(n_win, 1)))
+        moments = np.zeros((3, ng, max(n_win, 1), 2))
+        s = tabs.as_struct()
+        self._chk(self.lib.mcs_angle_dist(self.h, ct.byref(s), n_win, lo.ctypes.data_as(c_int32_p), hi.ctypes.data_as(c_int32_p), _dp(dist),
+                                          _dp(number), _dp(moments)))
+        return dist, number, moments
+
     def photon_synch(self, dndp_pf, mom_edge_cgs, mc, n_photon, emin_mev, bins_per_dec):
         """K5: synchrotron emission dP/d(ln E) [erg/s] per zone from the plasma-frame electron dN/dp -> (E_erg[n_photon], emis[n_grid][n_photon])."""
         d = np.ascontiguousarray(dndp_pf, dtype=np.float64); pe = np.ascontiguousarray(mom_edge_cgs, dtype=np.float64)
