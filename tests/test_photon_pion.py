@@ -13,6 +13,7 @@ import math
 import numpy as np
 import pytest
 
+import photon_fold_common as pf
 from conftest import mcs, make_problem, oracle_backend
 
 C, MP = mcs.constants.C, mcs.constants.MP
@@ -270,9 +271,13 @@ def test_gpu_pion_matches_cpu_twin():
         assert np.allclose(Eg, Eo, rtol=1e-14)
         assert o.max() > 1e-30
         edge = np.abs(np.log(np.maximum(g, 1e-99) / np.maximum(o, 1e-99))) > 1e-6
-        # a photon energy within one ulp of a bin's kinematic limit may fall on either side of it: at most a handful, and tiny
-        assert np.array_equal(g > 1e-99, o > 1e-99) or edge.sum() <= 3
+        # a photon energy within an ulp or so of a bin's kinematic limit may fall on either side of it: every such output must be one
+        # the mpmath reference cannot decide either (X within its running bound of 1 in some lit bin: photon_fold_common.py)
+        with pf.libm(pf.DEVICE):
+            for z, j in zip(*np.nonzero(edge)):
+                assert pf.pion_point_undecidable(d[z], pe, mc, aa, i_data, target[z], scaling, Eg[j]), (aa, i_data, z, j, g[z, j], o[z, j])
         ok = ~edge
+        assert np.array_equal((g > 1e-99 * scaling)[ok], (o > 1e-99 * scaling)[ok])
         assert np.allclose(g[ok], o[ok], rtol=1e-11, atol=0), float(np.max(np.abs(g[ok] / o[ok] - 1)))
     with pytest.raises(RuntimeError):
         hb.photon_pion(d, pe, MP * C, 1.0, target, 1.0, 120, 1.0, 10, i_data=5)
