@@ -298,7 +298,10 @@ int mcs_set_cuts(mcs_ctx* ctx, int n_pcuts, const double* pcuts, int n_tcuts, co
 /* resets of src/main_loops.jl:59-86 (fluxes, weight_coupled := 1e-99; pools := 0; scalars := 1e-99) */
 int mcs_begin_iteration(mcs_ctx* ctx, int i_iter);
 /* src/main_loops.jl:97-121,164 + clear_psd! (src/ion_init.jl:1-16): psd/esc_psd := 1e-99,
- * num_crossings/therm := 0, fluxes := 0 (quirk Q2), recv_pool := transfer_pool. */
+ * num_crossings/therm := 0, fluxes := 0 (quirk Q2), recv_pool := transfer_pool.
+ * With do_tcuts it also queues, on the context's stream, one device-to-device copy of the species' block
+ * spectra_coupled[i_ion][0..MCS_NA_C)[0..201) into a base buffer that the context owns (mcs_tcut_spectra, K12, reads it); without
+ * do_tcuts nothing is queued. */
 int mcs_begin_species(mcs_ctx* ctx, int i_iter, int i_ion, double aa, double zz,
                       double pmax_cutoff, double density, double electron_weight_fac);
 /* analytic fast-push fluxes of init_pop/F_update! (src/initializers.jl:1054-1068,1156) */
@@ -485,6 +488,50 @@ int mcs_dndp_esc(mcs_ctx* ctx, const mcs_consumer_in* in, const double* gam_pf, 
 #define MCS_ANGLE_MAX_WINDOWS 8
 int mcs_angle_dist(mcs_ctx* ctx, const mcs_consumer_in* in, int n_win, const int32_t* l_lo, const int32_t* l_hi,
                    double* dist, double* number, double* moments);
+/* K12: the spectra of the time cuts, "how far has acceleration got after time t" (the reference's tcut_print, src/io.jl:21-76,
+ * called at src/main_loops.jl:383-389), for the context's CURRENT species and the n_tcuts (nt) cuts of mcs_set_cuts, from the
+ * resident weight_coupled and spectra_coupled.  Of `in` it reads only mom_log_cgs (e[l], NM = nmom + 2 edges).
+ * BASE.  spectra_coupled is never reset, so a species' contribution in one iteration is the growth of its row block over the
+ * base that mcs_begin_species took: independent of earlier iterations, of tcut_print's rewrite and of mcs_accumulate_tallies.
+ * All deposits are positive and fl(base + w) >= base, so the growth g = now - base (one subtraction per word) is never negative,
+ * and exactly 0.0 where nothing was deposited.
+ * out: host, laid out as mcs_tcut_get_layout says (it needs no GPU; 1 <= n_tcuts < MCS_NA_C):
+ *   spectrum [nt][NM] | weight [nt] | number [nt] | mean_log_p [nt] | quantile [3][nt] | index [3];  total nt (NM + 6) + 3.
+ * Every operation is a separate fp64 rounding; there are no floating-point atomics, so every call on the same buffers gives the
+ * same bits.
+ *   BINS: a row has the bins l = 0..nmom, with edges e[l] and e[l+1].  Entry nmom+1 of spectrum is 1e-99.  Words with l > nmom of
+ *   the 201-wide tally row, and rows k >= nt, are never read.
+ *   GROWTH AND NUMBER: g[l] = now[l] - base[l];  number[k] = ((0.0 + g[0]) + g[1]) + ... + g[nmom], serial and ascending.
+ *   WEIGHT: weight[k] is weight_coupled[i_ion][k] as it stands, or 1e-99 where it is below 1e-60 (tcut_print's floor).
+ *   LIVE AND DEAD ROWS: a row is live if number[k] > 1e-99.
+ *     live: spectrum[k][l] = g[l] / number[k], or 1e-99 where that is below 1e-60 (tcut_print's normalisation and floor);
+ *     dead: spectrum all 1e-99, number 0.0, mean_log_p and the three quantiles a quiet NaN -- the convention of the slope words of
+ *     the products sample: a summary counts them in n_nonfinite and no trigger on them is ever met.  Triggers belong on cuts below
+ *     age_max: the last cut must lie above 10 x age_max and stays dead.
+ *   MEAN: mean_log_p[k] = (sum_l g[l] * c_l) / number[k] with c_l = 0.5 * (e[l] + e[l+1]); the sum serial and ascending from 0.0.
+ *   QUANTILES: MCS_TCUT_Q, q = 0.5, 0.9, 0.99.  T = q * number[k];  C_0 = 0.0, C_{l+1} = C_l + g[l];  l* is the first l with
+ *     g[l] > 0 and C_{l+1} >= T;  f = (T - C_{l*}) / g[l*].  If the last lit bin's C falls short of T through rounding, l* is that
+ *     bin and f is 1.0.  quantile = e[l*] + f * (e[l*+1] - e[l*]): log10 of the momentum below which the fraction q of the
+ *     still-coupled weight lies, "p reached by time t".
+ *   INDEX: index[j] is the least-squares slope of quantile[j][k] against log10(tcuts[k]) (the deterministic log10 of
+ *     include/mcs_math.h) over the live rows, k ascending, exactly by the rule of the products slope below ("Slope of frame m":
+ *     a live row is a valid bin, x = log10 tcuts[k], y = quantile[j][k]); fewer than three live rows give a quiet NaN.
+ * diag: host [2] or null: the number of live rows, and the number of words read with now < base.  The second must be 0; it is
+ * there so that a caller who overwrote the tallies sees it.
+ * The result also stays on the device, in a buffer that no other call writes, for the tcuts sample of the ensemble statistics
+ * (below); mcs_begin_species and that sample invalidate it.
+ * Refused, with a message: a context without do_tcuts, before mcs_set_cuts (or with no time cut set), before the first
+ * mcs_begin_species, a null table or output. */
+#define MCS_TCUT_NQ 3
+#define MCS_TCUT_Q {0.5, 0.9, 0.99}
+typedef struct mcs_tcut_layout {
+  int64_t spectrum, weight, number, mean_log_p, quantile, index;   /* offsets, in doubles */
+  int64_t row_n;                                            /* nmom + 2: the length of a spectrum row */
+  int64_t n_tcuts;                                          /* the length of weight, number, mean_log_p and of a quantile row */
+  int64_t total;
+} mcs_tcut_layout;
+int mcs_tcut_get_layout(const mcs_params* p, int n_tcuts, mcs_tcut_layout* out);     /* needs no GPU */
+int mcs_tcut_spectra(mcs_ctx* ctx, const mcs_consumer_in* in, double* out, int64_t* diag);
 
 /* ---- photon post-processing: the synchrotron fold of src/synch_emission.jl:27-171 over the plasma-frame
  * dN/dp of an electron species (frame 2 of mcs_dndp_cr), for every grid zone with the zone's field of the grid tables.
@@ -769,6 +816,21 @@ typedef struct mcs_ens_angles_layout {
 int mcs_ens_angles_get_layout(const mcs_params* p, int n_win, mcs_ens_angles_layout* out);   /* needs no GPU */
 int mcs_ens_set_angle_windows(mcs_ens* ens, int n_win, const int32_t* l_lo, const int32_t* l_hi);
 int mcs_ens_add_angles(mcs_ens* ens, mcs_ctx* src, int species_slot);
+
+/* ---- tcuts sample: error bars of the time-cut spectra.  Every species slot s has a fifth companion, the TCUTS slot
+ * MCS_ENS_TCUTS(s), which behaves as its escape slot does in the count, read, merge, summarize, summarize-merged and compare calls
+ * (vectors allocated at the first sample; reads of a slot that never took one are refused).  The sample is the last
+ * mcs_tcut_spectra on the context as that call left it on the device, in its layout (mcs_ens_tcuts_get_layout gives that of
+ * mcs_tcut_get_layout): spectrum [nt][nmom+2], weight, number, mean_log_p [nt], quantile [3][nt], index [3].
+ * n_tcuts is fixed by the accumulator's first tcuts sample (or by a merge into an accumulator that has none): a later sample,
+ * merge, merged summary or comparison with another n_tcuts is refused.
+ * mcs_ens_add_tcuts: refused unless mcs_tcut_spectra has run on src since its last mcs_begin_species and since the last tcuts
+ * sample taken from it, and for what mcs_ens_add_species refuses.  Queued on src's stream behind the accumulator's event, no host
+ * synchronisation.  mcs_ens_load_mean takes species slots only. */
+#define MCS_ENS_TCUTS(s) ((s) | (1 << 25))
+typedef mcs_tcut_layout mcs_ens_tcuts_layout;
+int mcs_ens_tcuts_get_layout(const mcs_params* p, int n_tcuts, mcs_ens_tcuts_layout* out);    /* needs no GPU */
+int mcs_ens_add_tcuts(mcs_ens* ens, mcs_ctx* src, int species_slot);
 
 /* ---- photons sample: error bars of the photon spectra at Earth.  A shell spectrum is a sum over zones, slices and processes: its
  * variance does not follow from per-cell variances, so the spectrum itself is sampled once per iteration, from what

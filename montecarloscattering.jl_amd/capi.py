@@ -115,8 +115,16 @@ class McsEnsAnglesLayout(ct.Structure):
     _fields_ = [(name, ct.c_int64) for name in ("dist", "number", "mean_mu", "mean_mu2", "row_n", "rows", "total")]
 
 
+class McsTcutLayout(ct.Structure):
+    """`mcs_tcut_layout` (= `mcs_ens_tcuts_layout`): offsets of the six parts of a time-cut result, the length of a spectrum row and the
+    number of cuts (include/mcs.h, mcs_tcut_spectra and "tcuts sample")."""
+    _fields_ = [(name, ct.c_int64) for name in ("spectrum", "weight", "number", "mean_log_p", "quantile", "index", "row_n", "n_tcuts", "total")]
+
+
+TCUT_Q = (0.5, 0.9, 0.99)       # MCS_TCUT_Q
 ENS_ESCAPE_BIT = 1 << 27        # MCS_ENS_ESCAPE(s) = s | ENS_ESCAPE_BIT
 ENS_ANGLES_BIT = 1 << 26        # MCS_ENS_ANGLES(s) = s | ENS_ANGLES_BIT
+ENS_TCUTS_BIT = 1 << 25         # MCS_ENS_TCUTS(s) = s | ENS_TCUTS_BIT
 ENS_PHOTONS_BIT = 1 << 29       # MCS_ENS_PHOTONS(s) = s | ENS_PHOTONS_BIT
 ENS_PHOTONS_ALL = 1 << 28       # MCS_ENS_PHOTONS_ALL: the source slot, one per accumulator
 
@@ -361,6 +369,8 @@ def load_library() -> ct.CDLL:
         "mcs_thermo_calcs": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_double_p, c_double_p]),
         "mcs_dndp_esc": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_double_p, c_double_p, c_int64_p]),
         "mcs_angle_dist": (i32, [vp, ct.POINTER(McsConsumerIn), i32, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
+        "mcs_tcut_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsTcutLayout)]),
+        "mcs_tcut_spectra": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_int64_p]),
         "mcs_photon_synch": (i32, [vp, c_double_p, c_double_p, dbl, i32, dbl, dbl, c_double_p, c_double_p]),
         "mcs_run_pcuts_fused": (i32, [vp, i32, i32, c_int64_p, c_int64_p, c_int64_p, c_int64_p, c_double_p]),
         "mcs_run_pcuts_pipelined": (i32, [vp, i32, i32, c_int64_p, ct.c_int64, ct.c_int64, c_int64_p, c_int64_p, c_int64_p, c_double_p, c_int64_p]),
@@ -403,6 +413,8 @@ def load_library() -> ct.CDLL:
         "mcs_ens_angles_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsEnsAnglesLayout)]),
         "mcs_ens_set_angle_windows": (i32, [vp, i32, c_int32_p, c_int32_p]),
         "mcs_ens_add_angles": (i32, [vp, vp, i32]),
+        "mcs_ens_tcuts_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsTcutLayout)]),
+        "mcs_ens_add_tcuts": (i32, [vp, vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -420,6 +432,16 @@ def load_library() -> ct.CDLL:
 
 
 _OPTIONS: Dict[str, dict] = {}
+
+
+def tcut_layout(P: McsParams, n_tcuts: int) -> McsTcutLayout:
+    """`mcs_tcut_get_layout`: where the parts of a time-cut result of n_tcuts cuts lie (needs no GPU).  ValueError with the library's
+    message for an n_tcuts outside 1..99."""
+    out = McsTcutLayout()
+    lib = load_library()
+    if lib.mcs_tcut_get_layout(ct.byref(P), int(n_tcuts), ct.byref(out)) != 0:
+        raise ValueError(lib.mcs_last_error().decode())
+    return out
 
 
 def option_table() -> Dict[str, dict]:
@@ -464,4 +486,6 @@ EXPORTED_SYMBOLS += ["mcs_ens_add_photons_deposit", "mcs_ens_add_photons_all", "
 EXPORTED_SYMBOLS += ["mcs_dndp_esc", "mcs_ens_escape_get_layout", "mcs_ens_add_escape"]
 # the pitch-angle distributions (K11) and their sample
 EXPORTED_SYMBOLS += ["mcs_angle_dist", "mcs_ens_angles_get_layout", "mcs_ens_set_angle_windows", "mcs_ens_add_angles"]
+# the time-cut spectra (K12) and their sample
+EXPORTED_SYMBOLS += ["mcs_tcut_spectra", "mcs_tcut_get_layout", "mcs_ens_tcuts_get_layout", "mcs_ens_add_tcuts"]
 PHOTON_PROCESS = {"synch": 0, "ic": 1, "pion": 2}      # MCS_PHOTON_SYNCH, _IC, _PION

@@ -235,6 +235,114 @@ def angle_distributions(prob, backend, i_ion: int, windows, therm_from_hist: boo
                               np.asarray(tabs.cos_edge), np.asarray(tabs.cos_center))
 
 
+@dataclasses.dataclass
+class TcutSpectra:
+    """The spectra of the time cuts of one species in one iteration (K12, include/mcs.h mcs_tcut_spectra): of the weight still
+    coupled to the shock at the cut's time, per cut k.  A cut that no particle reached is a DEAD row: spectrum all 1e-99, number 0.0,
+    mean_log_p and the quantiles NaN."""
+    spectrum: np.ndarray         # [nt][nmom+2]: the growth of spectra_coupled over the species, normalised to its sum; empty: 1e-99
+    weight: np.ndarray           # [nt]: weight_coupled as it stands, floored as tcut_print floors it
+    number: np.ndarray           # [nt]: the sum the spectrum was normalised with; 0.0 in a dead row
+    mean_log_p: np.ndarray       # [nt]: the mean of log10 p (cgs) over the spectrum
+    quantile: np.ndarray         # [3][nt]: log10 of the momentum below which the share TCUT_Q[j] of the weight lies
+    index: np.ndarray            # [3]: d quantile / d log10 t over the live rows; NaN with fewer than three
+    diag: np.ndarray             # [2]: live rows, words with now < base (must be 0)
+    tcuts: np.ndarray            # [nt]: the times of the cuts
+    mom_log_cgs: np.ndarray      # [nmom+2]: log10 of the momentum bin edges (cgs)
+
+    def words(self) -> np.ndarray:
+        """The result as one vector in mcs_tcut_layout, the tcuts sample of the ensemble statistics."""
+        return np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in
+                               (self.spectrum, self.weight, self.number, self.mean_log_p, self.quantile, self.index)])
+
+
+TCUT_Q = capi.TCUT_Q
+
+
+def _tcut_from_words(out, diag, nt, NM, tcuts, mom_log) -> TcutSpectra:
+    o = np.asarray(out, dtype=np.float64)
+    a = nt * NM
+    return TcutSpectra(o[:a].reshape(nt, NM).copy(), o[a:a + nt].copy(), o[a + nt:a + 2 * nt].copy(), o[a + 2 * nt:a + 3 * nt].copy(),
+                       o[a + 3 * nt:a + 6 * nt].reshape(3, nt).copy(), o[a + 6 * nt:a + 6 * nt + 3].copy(), np.asarray(diag, dtype=np.int64),
+                       np.array(tcuts, dtype=np.float64), np.array(mom_log, dtype=np.float64))
+
+
+def tcut_spectra_host(now, base, weight, mom_log, tcuts, nmom: int, log10) -> TcutSpectra:
+    """The rules of mcs_tcut_spectra (include/mcs.h) in numpy, the cuts side by side and the bins of a row one after the other, so
+    that every sum is the serial one.  now, base: [>= nt][>= nmom+1] rows of spectra_coupled of the species and what they held at
+    its start; weight: [>= nt] of weight_coupled; log10: the deterministic one (ensemble._det_log10)."""
+    from . import ensemble as ens
+    tcuts = np.asarray(tcuts, dtype=np.float64)
+    nt, nm, NM = len(tcuts), int(nmom), int(nmom) + 2
+    e = np.asarray(mom_log, dtype=np.float64)[:NM]
+    now = np.asarray(now, dtype=np.float64)[:nt, :nm + 1]
+    base = np.asarray(base, dtype=np.float64)[:nt, :nm + 1]
+    with np.errstate(all="ignore"):
+        g = now - base
+        n_neg = int(np.count_nonzero(now < base))
+        num = np.zeros(nt)
+        for l in range(nm + 1):
+            num = num + g[:, l]
+        live = num > 1.0e-99
+        w = np.asarray(weight, dtype=np.float64)[:nt]
+        weight_out = np.where(w < 1.0e-60, 1.0e-99, w)
+        spectrum = np.full((nt, NM), 1.0e-99)
+        s = g / np.where(live, num, 1.0)[:, None]
+        spectrum[:, :nm + 1] = np.where(live[:, None], np.where(s < 1.0e-60, 1.0e-99, s), 1.0e-99)
+        c = 0.5 * (e[:-1] + e[1:])
+        sm = np.zeros(nt)
+        for l in range(nm + 1):
+            sm = sm + g[:, l] * c[l]
+        mean = np.where(live, sm / num, np.nan)
+        quant = np.full((3, nt), np.nan)
+        for j, q in enumerate(TCUT_Q):
+            T = q * num
+            C = np.zeros(nt)
+            found = np.zeros(nt, dtype=bool)
+            last = np.full(nt, -1)
+            val = np.full(nt, np.nan)
+            for l in range(nm + 1):
+                gl = g[:, l]
+                Cn = C + gl
+                lit = (gl > 0) & ~found
+                hit = lit & (Cn >= T)
+                f = (T - C) / np.where(hit, gl, 1.0)
+                val = np.where(hit, e[l] + f * (e[l + 1] - e[l]), val)
+                found = found | hit
+                last = np.where(lit & ~hit, l, last)
+                C = Cn
+            short = ~found & (last >= 0)
+            lz = np.where(short, last, 0)
+            val = np.where(short, e[lz] + 1.0 * (e[lz + 1] - e[lz]), val)
+            quant[j] = np.where(live, val, np.nan)
+        x = log10(np.ascontiguousarray(tcuts))
+        index = ens.slopes_xy(x, quant, np.broadcast_to(live, quant.shape))
+    number = np.where(live, num, 0.0)
+    return TcutSpectra(spectrum, weight_out, number, mean, quant, index, np.array([int(live.sum()), n_neg], dtype=np.int64),
+                       tcuts.copy(), e.copy())
+
+
+def tcut_spectra(prob, backend, i_ion: int, base=None) -> TcutSpectra:
+    """The time-cut spectra of species i_ion from the backend's resident weight_coupled and spectra_coupled: on a HIP backend the
+    device call (K12; the base is the one its begin_species took), on a backend without it the numpy statement of the same rules on
+    the tallies read back and on `base`, the species' [100][201] block of spectra_coupled as it stood at the species' start."""
+    P = prob.params
+    if not P.do_tcuts or len(prob.tcuts) < 1:
+        raise ValueError("tcut_spectra: the problem tracks no time cuts")
+    tabs = consumer_tables(prob, i_ion)
+    nt, NM = len(prob.tcuts), P.num_psd_mom_bins + 2
+    if hasattr(backend, "tcut_spectra"):
+        out, diag = backend.tcut_spectra(tabs)
+        return _tcut_from_words(out, diag, nt, NM, prob.tcuts, tabs.mom_log_cgs)
+    if base is None:
+        raise ValueError("tcut_spectra: a backend without tcut_spectra needs the base, spectra_coupled of the species as it stood at its start")
+    from . import ensemble as ens
+    L = backend.layout
+    f, _ = backend.read_tallies()
+    return tcut_spectra_host(L.view(f, "spectra_coupled")[i_ion - 1], base, L.view(f, "weight_coupled")[i_ion - 1], tabs.mom_log_cgs,
+                             prob.tcuts, P.num_psd_mom_bins, ens._det_log10(backend))
+
+
 # ---- photon post-processing (SURVEY.md 8(f-4)) -------------------------------------------------------------------------
 # photon_calcs.jl:11-19: the common energy grid of the emission spectra
 PHOTON_E_MIN_MEV = 1.0e-13

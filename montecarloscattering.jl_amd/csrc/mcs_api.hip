@@ -181,6 +181,12 @@ struct mcs_ctx {
   bool have_ang = false;
   int ang_n_win = 0;
   int32_t ang_lo[MCS_ANGLE_MAX_WINDOWS] = {}, ang_hi[MCS_ANGLE_MAX_WINDOWS] = {};
+  // K12: d_tcut_base, the current species' block of spectra_coupled as mcs_begin_species found it ([MCS_NA_C][201]; taken only with
+  // do_tcuts); what the last mcs_tcut_spectra left, in mcs_tcut_layout, its n_tcuts and its counts; have_tcut: a whole result since the
+  // last mcs_begin_species and the last tcuts sample.  Only those two calls write them.  species_begun: mcs_begin_species has run.
+  DevBuf<double> d_tcut_base, d_tcut_out; DevBuf<unsigned int> d_tcut_rowneg; DevBuf<unsigned long long> d_tcut_diag;
+  bool have_tcut = false, species_begun = false;
+  int tcut_n = 0;
   DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
   // K9, per process (MCS_PHOTON_SYNCH / _IC / _PION): d_pemis the emis[n_grid][n_photon] its fold left (pemis_n: that n_photon, 0 =
   // nothing), d_pobs the [n_shells+1][n] of the last mcs_photon_observe (pobs_n: its n, 0 = nothing; pobs_shells).  Only those calls
@@ -461,8 +467,16 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
   c->have_cout_dndp = c->have_cout_thermo = false;
   c->have_esc = false;
   c->have_ang = false;
+  c->have_tcut = false;
   c->photon_flags_clear();
   if (fold_replicas(c)) return 1;      // (the previous species' replicas, before its histograms are cleared)
+  if (P.do_tcuts) {      // K12's base: the species' block of spectra_coupled as it stands now
+    const long long nb = (long long)MCS_NA_C * (MCS_PSD_MAX + 1);
+    if (reserve(c->d_tcut_base, nb)) return 1;
+    HIPCHK(hipMemcpyAsync(c->d_tcut_base, c->d_T + c->L.spectra_coupled + nb * (i_ion - 1), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice,
+                          c->stream));
+  }
+  c->species_begun = true;
   const long long npsd = c->L.psd_stride_zone * P.n_grid;
   const long long pm = MCS_PSD_MAX + 1;
   if (fill(c, c->L.psd, npsd, MCS_FLOOR) || fill(c, c->L.therm_sf, 2 * npsd, 0.0) ||
@@ -1706,6 +1720,50 @@ int mcs_angle_dist(mcs_ctx* c, const mcs_consumer_in* in, int n_win, const int32
   return 0;
 }
 
+int mcs_tcut_get_layout(const mcs_params* p, int n_tcuts, mcs_tcut_layout* out) {
+  if (!p || !out) return fail("mcs_tcut_get_layout: null argument");
+  if (n_tcuts < 1 || n_tcuts >= MCS_NA_C) return fail("mcs_tcut_get_layout: n_tcuts outside 1.." + std::to_string(MCS_NA_C - 1));
+  const int64_t nm = p->num_psd_mom_bins + 2, nt = n_tcuts;
+  out->row_n = nm; out->n_tcuts = nt;
+  out->spectrum = 0; out->weight = nt * nm; out->number = nt * nm + nt; out->mean_log_p = nt * nm + 2 * nt;
+  out->quantile = nt * nm + 3 * nt; out->index = nt * nm + (3 + MCS_TCUT_NQ) * nt;
+  out->total = nt * nm + (3 + MCS_TCUT_NQ) * nt + MCS_TCUT_NQ;
+  return 0;
+}
+
+int mcs_tcut_spectra(mcs_ctx* c, const mcs_consumer_in* in, double* out, int64_t* diag) {
+  MCS_ENTER(c);
+  const std::string who = "mcs_tcut_spectra";
+  if (!in || !out) return fail(who + ": null argument");
+  if (!c->P.do_tcuts) return fail(who + ": the context tracks no time cuts (do_tcuts)");
+  if (!c->have_cuts) return fail(who + ": cuts not set (mcs_set_cuts)");
+  if (c->tb.n_tcuts < 1) return fail(who + ": no time cut is set");
+  if (!c->species_begun) return fail(who + ": no species has begun (mcs_begin_species takes the base)");
+  if (!in->mom_log_cgs) return fail(who + ": null table");
+  const int NM = c->P.num_psd_mom_bins + 2, nt = c->tb.n_tcuts;
+  if (NM > MCS_PSD_MAX + 1) return fail(who + ": more PSD bins than a row of spectra_coupled holds");
+  if (fold_replicas(c)) return 1;
+  mcs_tcut_layout TL;
+  if (mcs_tcut_get_layout(&c->P, nt, &TL)) return 1;
+  c->have_tcut = false;
+  if (reserve(c->d_tcut_out, TL.total) || reserve(c->d_ctab, NM) || reserve(c->d_tcut_rowneg, nt) || reserve(c->d_tcut_diag, 2)) return 1;
+  HIPCHK(hipMemcpyAsync(c->d_ctab, in->mom_log_cgs, sizeof(double) * NM, hipMemcpyHostToDevice, c->stream));
+  const long long nb = (long long)MCS_NA_C * (MCS_PSD_MAX + 1);
+  HIPCHK(mcs_launch_tcut_spectra(&c->P, c->d_T + c->L.spectra_coupled + nb * (c->i_ion - 1), c->d_tcut_base,
+                                 c->d_T + c->L.weight_coupled + (long long)MCS_NA_C * (c->i_ion - 1), c->d_ctab, c->tb.tcuts, nt, c->d_tcut_out,
+                                 c->d_tcut_rowneg, c->d_tcut_diag, c->stream));
+  std::vector<double> o((size_t)TL.total);
+  unsigned long long hd[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(o.data(), c->d_tcut_out, sizeof(double) * o.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hd, c->d_tcut_diag, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  memcpy(out, o.data(), sizeof(double) * o.size());
+  if (diag) { diag[0] = (int64_t)hd[0]; diag[1] = (int64_t)hd[1]; }
+  c->tcut_n = nt;
+  c->have_tcut = true;
+  return 0;
+}
+
 int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, double* P_perp, double* energy_density) {
   MCS_ENTER(c);
   if (consumers_ready(c, in, "mcs_thermo_calcs")) return 1;
@@ -1905,7 +1963,8 @@ int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
   MCS_ENTER(c);
   if (fold_replicas(c)) return 1;
   *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo, {}, {}, {},
-                    c->d_esc_out, c->have_esc, c->d_ang_out, c->have_ang, c->ang_n_win, {}, {}};
+                    c->d_esc_out, c->have_esc, c->d_ang_out, c->have_ang, c->ang_n_win, {}, {},
+                    c->d_tcut_out, c->have_tcut, c->tcut_n};
   for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) { out->ang_lo[m] = c->ang_lo[m]; out->ang_hi[m] = c->ang_hi[m]; }
   for (int p = 0; p < 3; ++p) { out->pobs[p] = c->d_pobs[p]; out->pobs_n[p] = c->pobs_n[p]; out->pobs_shells[p] = c->pobs_shells[p]; }
   return 0;
@@ -1915,6 +1974,7 @@ void mcs_ctx_view_products_taken(mcs_ctx* c) { c->have_cout_dndp = c->have_cout_
 void mcs_ctx_view_photons_taken(mcs_ctx* c) { c->photon_flags_clear(); }
 void mcs_ctx_view_escape_taken(mcs_ctx* c) { c->have_esc = false; }
 void mcs_ctx_view_angles_taken(mcs_ctx* c) { c->have_ang = false; }
+void mcs_ctx_view_tcuts_taken(mcs_ctx* c) { c->have_tcut = false; }
 int mcs_ctx_view_fail(const char* msg) { return fail(msg); }
 
 }  // extern "C"

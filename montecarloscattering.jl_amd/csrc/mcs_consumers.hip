@@ -14,6 +14,7 @@
 // The reference's consumer quirks C1-C6 are handled as DESIGN.md section 3b says.
 #include "mcs_device.h"
 #include "mcs_launch.h"
+#include "mcs_slope.h"
 #include "../../include/mcs_math.h"
 #include "../../include/mcs_synch.h"
 #include "../../include/mcs_ic.h"
@@ -680,6 +681,115 @@ __global__ void __launch_bounds__(256) mcs_k_angle_dist(AngArgs a) {
   }
 }
 
+// ---- K12: the spectra of the time cuts (include/mcs.h, mcs_tcut_spectra; the reference's tcut_print, src/io.jl:21-76) --------------
+// now: the current species' block of spectra_coupled, [MCS_NA_C][TCUT_STRIDE] with the momentum index fastest; base: what
+// mcs_begin_species copied of it; only rows k < nt and words l <= nm are read.  Two launches, no floating-point atomics, one
+// fixed order of the adds (include/mcs.h): the same bits in every call.
+#define TCUT_STRIDE (MCS_PSD_MAX + 1)
+
+struct TcutArgs {
+  const double *now, *base;
+  const double* weight;     // weight_coupled of the species: [MCS_NA_C]
+  const double* mom_log;    // e[l], [nm+2]
+  const double* tcuts;      // [nt]
+  int nm, nt;
+  double* out;              // mcs_tcut_layout: spectrum [nt][nm+2] | weight | number | mean_log_p [nt] | quantile [3][nt] | index [3]
+  unsigned int* row_neg;    // scratch [nt]: the words of a row with now < base
+  unsigned long long* diag; // [2]
+};
+
+// log10 of the momentum below which the share T / number of a live row's growth lies (include/mcs.h, QUANTILES)
+__device__ double tcut_quantile(const double* g, const double* e, int nm, double T) {
+  double C = 0.0;
+  int last = -1;
+  for (int l = 0; l <= nm; ++l) {
+    const double gl = g[l];
+    const double Cn = C + gl;
+    if (gl > 0) {
+      if (Cn >= T) {
+        const double f = (T - C) / gl;
+        return e[l] + f * (e[l + 1] - e[l]);
+      }
+      last = l;
+    }
+    C = Cn;
+  }
+  if (last < 0) return __builtin_nan("");
+  return e[last] + 1.0 * (e[last + 1] - e[last]);      // (the last lit bin's C fell short of T through rounding: f = 1)
+}
+
+// One wave per cut: the lanes stride the row for the loads, the subtraction and the stores; the ordered sums are lane 0's, out of LDS.
+__global__ void __launch_bounds__(64) mcs_k_tcut_rows(TcutArgs a) {
+  __shared__ double s_g[KC_MAXB], s_e[KC_MAXB];
+  __shared__ unsigned int s_neg[64];
+  __shared__ double s_num;
+  const int nm = a.nm, NM = nm + 2, nt = a.nt, k = blockIdx.x;
+  const double* now = a.now + (long long)TCUT_STRIDE * k;
+  const double* base = a.base + (long long)TCUT_STRIDE * k;
+  unsigned int neg = 0;
+  for (int l = threadIdx.x; l < NM; l += 64) s_e[l] = a.mom_log[l];
+  for (int l = threadIdx.x; l <= nm; l += 64) {
+    const double n = now[l], b = base[l];
+    if (n < b) ++neg;
+    s_g[l] = n - b;
+  }
+  s_neg[threadIdx.x] = neg;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double num = 0.0;
+    for (int l = 0; l <= nm; ++l) num = num + s_g[l];
+    const bool live = num > 1.0e-99;
+    const double nan = __builtin_nan("");
+    double* o = a.out + (long long)nt * NM;      // weight | number | mean_log_p | quantile [3]
+    const double w = a.weight[k];
+    o[k] = w < 1.0e-60 ? 1.0e-99 : w;
+    o[nt + k] = live ? num : 0.0;
+    double mean = nan;
+    if (live) {
+      double s = 0.0;
+      for (int l = 0; l <= nm; ++l) {
+        const double c = 0.5 * (s_e[l] + s_e[l + 1]);
+        s = s + s_g[l] * c;
+      }
+      mean = s / num;
+    }
+    o[2 * nt + k] = mean;
+    const double q[MCS_TCUT_NQ] = MCS_TCUT_Q;
+    for (int j = 0; j < MCS_TCUT_NQ; ++j) o[(3 + j) * nt + k] = live ? tcut_quantile(s_g, s_e, nm, q[j] * num) : nan;
+    unsigned int t = 0;
+    for (int i = 0; i < 64; ++i) t += s_neg[i];
+    a.row_neg[k] = t;
+    s_num = live ? num : 0.0;
+  }
+  __syncthreads();
+  const double num = s_num;
+  for (int l = threadIdx.x; l < NM; l += 64) {
+    double d = 1.0e-99;
+    if (num > 0 && l <= nm) {
+      const double s = s_g[l] / num;
+      d = s < 1.0e-60 ? 1.0e-99 : s;
+    }
+    a.out[(long long)k * NM + l] = d;
+  }
+}
+
+// One wave: lanes 0..2 the index of a quantile each (the slope rule of the products sample over the live rows), lane 3 the counts.
+__global__ void __launch_bounds__(64) mcs_k_tcut_index(TcutArgs a) {
+  const int nt = a.nt, NM = a.nm + 2;
+  const double* number = a.out + (long long)nt * NM + nt;
+  const double* quant = a.out + (long long)nt * NM + 3 * nt;
+  if (threadIdx.x < MCS_TCUT_NQ) {
+    const double* y = quant + (long long)threadIdx.x * nt;
+    a.out[(long long)nt * (NM + 6) + threadIdx.x] =
+        mcs_slope_rule(0, nt, [&](int k) { return number[k] > 1.0e-99; }, [&](int k) { return mcsm::log10(a.tcuts[k]); }, [&](int k) { return y[k]; });
+  }
+  if (threadIdx.x == MCS_TCUT_NQ) {
+    unsigned long long live = 0ull, neg = 0ull;
+    for (int k = 0; k < nt; ++k) { if (number[k] > 1.0e-99) ++live; neg += a.row_neg[k]; }
+    a.diag[0] = live; a.diag[1] = neg;
+  }
+}
+
 }  // namespace
 
 // Host-callable launchers (pointers are device pointers; tables were uploaded by the caller)
@@ -745,6 +855,20 @@ extern "C" hipError_t mcs_launch_angle_dist(const mcs_params* P, const double* p
   for (int m = 0; m < n_win; ++m) { a.l_lo[m] = l_lo[m]; a.l_hi[m] = l_hi[m]; }
   a.out = out;
   hipLaunchKernelGGL(mcs_k_angle_dist, dim3(P->n_grid, 3), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t mcs_launch_tcut_spectra(const mcs_params* P, const double* now, const double* base, const double* weight,
+                                              const double* mom_log, const double* tcuts, int n_tcuts, double* out, unsigned int* row_neg,
+                                              unsigned long long* diag, hipStream_t st) {
+  TcutArgs a{};
+  a.now = now; a.base = base; a.weight = weight; a.mom_log = mom_log; a.tcuts = tcuts;
+  a.nm = P->num_psd_mom_bins; a.nt = n_tcuts;
+  a.out = out; a.row_neg = row_neg; a.diag = diag;
+  hipLaunchKernelGGL(mcs_k_tcut_rows, dim3(n_tcuts), dim3(64), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mcs_k_tcut_index, dim3(1), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

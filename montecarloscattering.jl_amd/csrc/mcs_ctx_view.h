@@ -31,6 +31,11 @@ struct McsCtxView {
   bool have_ang;
   int ang_n_win;
   int32_t ang_lo[MCS_ANGLE_MAX_WINDOWS], ang_hi[MCS_ANGLE_MAX_WINDOWS];
+  // what the last mcs_tcut_spectra left on the device, in mcs_tcut_layout (null before the first call), whether it is a whole result
+  // since the last mcs_begin_species / tcuts sample, and that call's n_tcuts
+  const double* tcut_out;
+  bool have_tcut;
+  int tcut_n;
 };
 
 extern "C" {
@@ -49,6 +54,8 @@ void mcs_ctx_view_photons_taken(mcs_ctx* ctx);
 void mcs_ctx_view_escape_taken(mcs_ctx* ctx);
 // An angles sample has been queued from ctx's mcs_angle_dist result: that call has to run again before the next.
 void mcs_ctx_view_angles_taken(mcs_ctx* ctx);
+// A tcuts sample has been queued from ctx's mcs_tcut_spectra result: that call has to run again before the next.
+void mcs_ctx_view_tcuts_taken(mcs_ctx* ctx);
 // Sets the message of the calling thread's last error (what the ABI's error call returns); returns 1.
 int mcs_ctx_view_fail(const char* msg);
 }

@@ -13,7 +13,7 @@
 // last kernel that folds a range's partials in index order.  No atomics: the same state gives the same bits.
 // The comparison of two slots (mcs_ens_compare) is the same walk over the (mean, M2) pairs of both with a record of its own: the
 // four sweep kernels share one routine, walk, for which words a thread sees and in which order.
-// Host side: every slot of every kind -- species, iteration, products, photons, source, escape, angles -- is one Slot (count, mean, M2); decode reads
+// Host side: every slot of every kind -- species, iteration, products, photons, source, escape, angles, tcuts -- is one Slot (count, mean, M2); decode reads
 // a slot number's bits, slot_ref finds its Slot, reserve allocates it, merge_slot merges it, and plan_ranges checks the ranges of a
 // summary or comparison and lays out their blocks in one pass.
 // A context is seen through mcs_ctx_view.h; its stream carries the work, an event of the accumulator orders successive operations
@@ -22,6 +22,7 @@
 
 #include "mcs_ctx_view.h"
 #include "mcs_hip_owned.h"
+#include "mcs_slope.h"
 #include "../../include/mcs_math.h"
 
 #include <climits>
@@ -131,27 +132,8 @@ __global__ void __launch_bounds__(ENS_THREADS) mcs_k_ens_slope(const double* __r
                                                                double* __restrict__ slope, long long rows, int nm, int l_lo, int l_hi) {
   for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long long)gridDim.x * blockDim.x) {
     const double* row = dndp + r * nm;
-    int k = 0;
-    double sx = 0.0, sy = 0.0;
-    for (int l = l_lo; l < l_hi; ++l) {
-      const double d = row[l];
-      if (d > 1.0e-99) { sx = sx + x_log[l]; sy = sy + mcsm::log10(d); ++k; }
-    }
-    double out = __builtin_nan("");
-    if (k >= 3) {
-      const double xbar = sx / (double)k, ybar = sy / (double)k;
-      double sxx = 0.0, sxy = 0.0;
-      for (int l = l_lo; l < l_hi; ++l) {
-        const double d = row[l];
-        if (d > 1.0e-99) {
-          const double dx = x_log[l] - xbar;
-          sxx = sxx + dx * dx;
-          sxy = sxy + dx * (mcsm::log10(d) - ybar);
-        }
-      }
-      out = sxy / sxx;
-    }
-    slope[r] = out;
+    slope[r] = mcs_slope_rule(l_lo, l_hi, [&](int l) { return row[l] > 1.0e-99; }, [&](int l) { return x_log[l]; },
+                              [&](int l) { return mcsm::log10(row[l]); });
   }
 }
 
@@ -700,13 +682,14 @@ constexpr int PHOTONS_BIT = 1 << 29;       // MCS_ENS_PHOTONS
 constexpr int PHOTONS_ALL = 1 << 28;       // MCS_ENS_PHOTONS_ALL
 constexpr int ESCAPE_BIT = 1 << 27;        // MCS_ENS_ESCAPE
 constexpr int ANGLES_BIT = 1 << 26;        // MCS_ENS_ANGLES
+constexpr int TCUTS_BIT = 1 << 25;         // MCS_ENS_TCUTS
 
-// The seven kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
+// The eight kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
 // to (s; not yet held against the accumulator's species slots, slot_ref does that; -1 for the iteration and the source slot).
 // A negative number has every high bit set: it is no companion slot, and is refused as a species slot outside the range.
 // The source slot has the photons slots' vector and layout rules; it is a kind of its own in a comparison.
-enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, ANGLES, N_KINDS };
-const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape", "angles"};
+enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, ANGLES, TCUTS, N_KINDS };
+const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape", "angles", "tcuts"};
 struct SlotId { Kind kind; int s; };
 SlotId decode(int slot, int n_slots) {
   if (slot == PHOTONS_ALL) return SlotId{SOURCE, -1};
@@ -714,12 +697,13 @@ SlotId decode(int slot, int n_slots) {
   if (slot >= 0 && (slot & PHOTONS_BIT) != 0) return SlotId{PHOTONS, slot ^ PHOTONS_BIT};
   if (slot >= 0 && (slot & ESCAPE_BIT) != 0) return SlotId{ESCAPE, slot ^ ESCAPE_BIT};
   if (slot >= 0 && (slot & ANGLES_BIT) != 0) return SlotId{ANGLES, slot ^ ANGLES_BIT};
+  if (slot >= 0 && (slot & TCUTS_BIT) != 0) return SlotId{TCUTS, slot ^ TCUTS_BIT};
   return slot == n_slots - 1 ? SlotId{ITERATION, -1} : SlotId{SPECIES, slot};
 }
 bool has_photon_vector(Kind k) { return k == PHOTONS || k == SOURCE; }
 bool has_window_vector(Kind k) { return k == PRODUCTS || k == ESCAPE; }      // (its sample holds slopes over the slope window)
 
-// What every slot is: the samples it has taken and its two vectors (those of a products, photons, source, escape or angles slot from its first
+// What every slot is: the samples it has taken and its two vectors (those of a products, photons, source, escape, angles or tcuts slot from its first
 // sample or merge on, nothing before)
 struct Slot { long long n = 0; DevBuf<double> mean, m2; };
 
@@ -763,6 +747,11 @@ struct mcs_ens {
   int32_t ang_lo[MCS_ANGLE_MAX_WINDOWS] = {}, ang_hi[MCS_ANGLE_MAX_WINDOWS] = {};
   std::vector<Slot> angles;
   bool angles_sampled = false;                // some angles slot has taken a sample (or a merge): the windows are fixed
+  // the tcuts slots, likewise (include/mcs.h, "tcuts sample"): TL.total doubles per vector; tc_n, the n_tcuts of the first tcuts sample
+  // (or merge), is fixed from then on; 0: none yet
+  mcs_ens_tcuts_layout TL{};
+  int tc_n = 0;
+  std::vector<Slot> tcuts;
   // the photons slots, likewise (include/mcs.h, "photons sample"): HL.total doubles per vector; no layout while ph_shells is 0
   mcs_ens_photons_layout HL{};
   int ph_shells = 0, ph_n[3] = {0, 0, 0}, ph_start[3] = {0, 0, 0}, ph_npts = 0;
@@ -776,20 +765,22 @@ struct mcs_ens {
   bool has_photon_layout() const { return ph_shells > 0; }
   bool has_window() const { return !x_log_h.empty(); }
   bool has_angle_windows() const { return ang_n_win > 0; }
+  bool has_tcuts() const { return tc_n > 0; }
   // the one way from a (checked) slot number to its record, and the length of the vectors of a kind
   Slot& at(SlotId id) {
     return id.kind == SOURCE ? source : id.kind == PHOTONS ? photons[(size_t)id.s] : id.kind == PRODUCTS ? products[(size_t)id.s]
            : id.kind == ESCAPE ? escape[(size_t)id.s] : id.kind == ANGLES ? angles[(size_t)id.s]
+           : id.kind == TCUTS ? tcuts[(size_t)id.s]
            : main[(size_t)(id.kind == ITERATION ? n_slots - 1 : id.s)];
   }
   long long len(Kind k) const {
-    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ANGLES ? (has_angle_windows() ? AL.total : 0) : k == ITERATION ? E.it_total : E.sp_total;
+    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ANGLES ? (has_angle_windows() ? AL.total : 0) : k == TCUTS ? (has_tcuts() ? TL.total : 0) : k == ITERATION ? E.it_total : E.sp_total;
   }
   // every slot number the accumulator has
   std::vector<int> slot_numbers() const {
     std::vector<int> all;
     for (int s = 0; s < n_slots; ++s) all.push_back(s);
-    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); all.push_back(s | ESCAPE_BIT); all.push_back(s | ANGLES_BIT); }
+    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); all.push_back(s | ESCAPE_BIT); all.push_back(s | ANGLES_BIT); all.push_back(s | TCUTS_BIT); }
     all.push_back(PHOTONS_ALL);
     return all;
   }
@@ -821,11 +812,11 @@ int leave(mcs_ens* e, hipStream_t st) {
 }
 
 // What a count, read, summary or comparison call works on: the slot of that number, its kind and the length of its vectors
-// (which are null for a products, photons, source, escape or angles slot that was never sampled; n is then 0).
+// (which are null for a products, photons, source, escape, angles or tcuts slot that was never sampled; n is then 0).
 struct SlotRef { Kind kind; Slot* slot; long long len; };
 int slot_ref(mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
   const SlotId id = decode(slot, e->n_slots);
-  if ((id.kind == PRODUCTS || id.kind == PHOTONS || id.kind == ESCAPE || id.kind == ANGLES) && id.s >= e->n_slots - 1)
+  if ((id.kind == PRODUCTS || id.kind == PHOTONS || id.kind == ESCAPE || id.kind == ANGLES || id.kind == TCUTS) && id.s >= e->n_slots - 1)
     return fail(who + ": " + KIND_NAME[id.kind] + " slot of slot " + std::to_string(id.s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
   if (id.kind == SPECIES && (slot < 0 || slot >= e->n_slots)) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
   *out = SlotRef{id.kind, &e->at(id), e->len(id.kind)};
@@ -862,6 +853,13 @@ void angle_windows_take(mcs_ens* e, int n_win, const int32_t* l_lo, const int32_
   e->ang_n_win = n_win;
   for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) { e->ang_lo[m] = m < n_win ? l_lo[m] : 0; e->ang_hi[m] = m < n_win ? l_hi[m] : 0; }
   angles_layout(&e->P, n_win, &e->AL);
+}
+
+// both have taken tcuts samples, and their n_tcuts differ
+bool tcuts_differ(const mcs_ens* a, const mcs_ens* b) { return a->has_tcuts() && b->has_tcuts() && a->tc_n != b->tc_n; }
+void tcuts_take(mcs_ens* e, int n_tcuts) {
+  e->tc_n = n_tcuts;
+  mcs_tcut_get_layout(&e->P, n_tcuts, &e->TL);
 }
 
 // both have a photon layout, and the two differ
@@ -1028,6 +1026,7 @@ int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   escape_layout(&v.P, &e->XL);
   e->escape.resize((size_t)n_species_slots);
   e->angles.resize((size_t)n_species_slots);
+  e->tcuts.resize((size_t)n_species_slots);
   const mcs_layout& L = v.L;
   e->inc = IncRanges{{L.esc_flux, L.esc_energy_eff, L.spectra_coupled}, {L.px_esc_feb, L.weight_coupled, L.energy_transfer_pool}};
   e->n_slots = n_species_slots + 1;
@@ -1214,6 +1213,35 @@ int mcs_ens_add_angles(mcs_ens* e, mcs_ctx* src, int slot) {
   return leave(e, v.stream);
 }
 
+int mcs_ens_tcuts_get_layout(const mcs_params* p, int n_tcuts, mcs_ens_tcuts_layout* out) {
+  if (!p || !out) return fail("mcs_ens_tcuts_get_layout: null argument");
+  return mcs_tcut_get_layout(p, n_tcuts, out);
+}
+
+int mcs_ens_add_tcuts(mcs_ens* e, mcs_ctx* src, int slot) {
+  const std::string who = "mcs_ens_add_tcuts";
+  if (!e || !src) return fail(who + ": null argument");
+  if (species_slot(e, who, slot, "only a species slot has a tcuts slot")) return 1;
+  McsCtxView v;
+  if (view_of(e, src, who.c_str(), &v)) return 1;
+  if (!v.have_tcut || !v.tcut_out)
+    return fail(who + ": the context needs an mcs_tcut_spectra since its last mcs_begin_species and its last tcuts sample");
+  if (e->has_tcuts() && v.tcut_n != e->tc_n)
+    return fail(who + ": the context's mcs_tcut_spectra had " + std::to_string(v.tcut_n) + " time cuts, the accumulator's tcuts samples have " +
+                std::to_string(e->tc_n));
+  if (enter(e, v.stream)) return 1;
+  if (!e->has_tcuts()) tcuts_take(e, v.tcut_n);
+  Slot& sl = e->tcuts[(size_t)slot];
+  if (reserve(sl, e->TL.total, who, v.stream)) return 1;
+  // the sample is the call's result as it lies on the device
+  hipLaunchKernelGGL(mcs_k_ens_add_vector, dim3(grid_for(e->TL.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), v.tcut_out,
+                     (long long)e->TL.total, (double)(sl.n + 1));
+  ENSCHK(hipGetLastError());
+  sl.n += 1;
+  mcs_ctx_view_tcuts_taken(src);
+  return leave(e, v.stream);
+}
+
 int mcs_ens_photons_get_layout(int n_shells, int n_synch, int n_ic, int n_pion, int n_pts, mcs_ens_photons_layout* out) {
   if (!out) return fail("mcs_ens_photons_get_layout: null argument");
   const int n[3] = {n_synch, n_ic, n_pion}, start[3] = {0, 0, 0};
@@ -1312,6 +1340,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' slope windows differ");
   if (photon_layouts_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' photon layouts differ");
   if (angle_windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' angle windows differ");
+  if (tcuts_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' tcuts samples differ in n_tcuts");
   McsCtxView v;
   if (mcs_ctx_view_get(dst->home, &v)) return 1;
   const std::vector<int> slots = dst->slot_numbers();
@@ -1334,6 +1363,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   }
   if (any_photons && !dst->has_photon_layout()) photon_layout_take(dst, src->ph_shells, src->ph_n, src->ph_start, src->ph_npts);
   if (any[ANGLES] && !dst->has_angle_windows()) angle_windows_take(dst, src->ang_n_win, src->ang_lo, src->ang_hi);
+  if (any[TCUTS] && !dst->has_tcuts()) tcuts_take(dst, src->tc_n);
   // (the source slot merges like a photons slot; what is pending on either side stays where it is)
   for (int slot : slots) {
     const SlotId id = decode(slot, dst->n_slots);
@@ -1421,6 +1451,12 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
         if (angle_windows_differ(ens[j], ens[k])) return fail(who + ": the accumulators' angle windows differ");
       if (ens[k]->len(sr.kind) > len) len = ens[k]->len(sr.kind);      // (an accumulator without windows has no angles sample)
     }
+  if (sr.kind == TCUTS)
+    for (int k = 1; k < n_ens; ++k) {
+      for (int j = 0; j < k; ++j)
+        if (tcuts_differ(ens[j], ens[k])) return fail(who + ": the accumulators' tcuts samples differ in n_tcuts");
+      if (ens[k]->len(sr.kind) > len) len = ens[k]->len(sr.kind);      // (an accumulator that took no tcuts sample has no length)
+    }
   if (has_photon_vector(sr.kind))
     for (int k = 1; k < n_ens; ++k) {
       for (int j = 0; j < k; ++j)
@@ -1473,6 +1509,7 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   if (!same_layout(a, b)) return fail(who + ": the accumulators' layouts differ");
   const Slot &sa = *ra.slot, &sb = *rb.slot;
   const long long len = ra.len;
+  if (ra.kind == TCUTS && rb.kind == TCUTS && tcuts_differ(a, b)) return fail(who + ": the accumulators' tcuts samples differ in n_tcuts");
   if (ra.kind != rb.kind || len != rb.len) return fail(who + ": the two slots differ in kind or length");
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges == 0) return 0;
@@ -1484,6 +1521,9 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   if (ra.kind == ANGLES) {
     if (sa.n == 0 || sb.n == 0) return fail(who + ": an angles slot has never taken a sample");
     if (angle_windows_differ(a, b)) return fail(who + ": the accumulators' angle windows differ");
+  }
+  if (ra.kind == TCUTS) {
+    if (sa.n == 0 || sb.n == 0) return fail(who + ": a tcuts slot has never taken a sample");
   }
   if (has_photon_vector(ra.kind)) {
     if (sa.n == 0 || sb.n == 0) return fail(who + ": a photons slot has never taken a sample");

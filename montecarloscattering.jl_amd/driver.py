@@ -83,6 +83,7 @@ class RunResult:
     convergence: object = None    # a Convergence: what run / run_overlapped(triggers=...) checked and where it stopped; None without triggers
     photons: object = None        # [consumers.ObservedSpectra], one per species, of the last iteration (run(photons=...)); None without
     escape: object = None         # [(i_iter, i_ion, consumers.EscapeSpectra)] of every species end (run(escape=True)); None without
+    tcuts: object = None          # [(i_iter, i_ion, consumers.TcutSpectra)] of every species end (run(tcuts=True)); None without
     angles: object = None         # [(i_iter, i_ion, consumers.AngleDistributions)] of every species end (run(angles=[...])); None without
 
 
@@ -389,6 +390,9 @@ def _species_transport(rs, be, i_iter, i_ion, hook, out_stats, out_empty):
     zz = abs(sp.zz) if cfg.abs_charge else sp.zz
     ewf = 1.0 / cfg.species[-1].density if cfg.species[-1].density != 0 else float("inf")
     be.begin_species(i_iter, i_ion, sp.aa, zz, pmax_cutoff, sp.density, ewf)
+    if rs.do_tcuts and not hasattr(be, "tcut_spectra"):
+        # (a backend without K12: the base its numpy statement needs, the species' coupled spectra as they stand now)
+        rs.tcut_base[id(be)] = L.view(be.read_tallies()[0], "spectra_coupled")[i_ion - 1].copy()
     if rs.is_root:
         be.set_fluxes(inj.pxx_flux, inj.pxz_flux, inj.energy_flux)
     if rs.multi:
@@ -667,6 +671,18 @@ def _species_angles(rs, be, i_iter, i_ion):
         rs.ensemble.add_angles(be, i_ion - 1, dist)
 
 
+def _species_tcuts(rs, be, i_iter, i_ion):
+    """The time-cut spectra of species i_ion (run(tcuts=True); K12 on a HIP backend): the growth of ITS block of spectra_coupled on
+    the context that transported it since that context's begin_species, before the running sums travel to the primary.  With an
+    ensemble, one tcuts sample into Ensemble.tcuts_slot(i_ion - 1)."""
+    if not rs.is_root:
+        return
+    spec = consumers.tcut_spectra(rs.prob, be, i_ion, base=rs.tcut_base.get(id(be)))
+    rs.tcuts.append((i_iter, i_ion, spec))
+    if rs.ensemble is not None:
+        rs.ensemble.add_tcuts(be, i_ion - 1, spec)
+
+
 def _iteration_species(rs, i_iter, before_pcut):
     """The species of iteration i_iter in order: its transport (here, or with secondaries on the pool's threads as the
     scheduler places it), its merge into the primary if it ran on a secondary, its species end."""
@@ -679,6 +695,8 @@ def _iteration_species(rs, i_iter, before_pcut):
                 _species_escape(rs, rs.backend, i_iter, i_ion)      # (after the ranks' merge: rank 0 holds the whole slabs)
             if rs.angle_windows is not None:
                 _species_angles(rs, rs.backend, i_iter, i_ion)
+            if rs.do_tcuts:
+                _species_tcuts(rs, rs.backend, i_iter, i_ion)
             if rs.photons is not None:
                 _species_photons(rs, i_iter, i_ion)
         return
@@ -690,6 +708,8 @@ def _iteration_species(rs, i_iter, before_pcut):
                 _species_escape(rs, rs.ctxs[k], i_iter, i_ion)      # (the slabs do not travel with the running sums)
             if rs.angle_windows is not None:
                 _species_angles(rs, rs.ctxs[k], i_iter, i_ion)      # (nor do the histograms)
+            if rs.do_tcuts:
+                _species_tcuts(rs, rs.ctxs[k], i_iter, i_ion)       # (the growth is that of the context's own running sums)
             if k > 0 and hasattr(rs.backend, "accumulate_tallies_from") and type(rs.ctxs[k]) is type(rs.backend):
                 rs.backend.accumulate_tallies_from(rs.ctxs[k])      # its running sums added to the primary's and cleared
             elif k > 0:
@@ -709,7 +729,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
         long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None,
         ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1, photons=None,
-        escape: bool = False, angles=None) -> RunResult:
+        escape: bool = False, angles=None, tcuts: bool = False) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -806,6 +826,13 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     Ensemble.angles_slot(i_ion - 1) (ensemble.py, "Angles": dist, number, mean_mu, mean_mu2; an ensemble without angle windows first
     gets the run's); triggers may name its parts, with zones=ensemble.angles_row(frame, zone, window) for one row and bins= for angle
     bins of that dist row.  Refused: angles without finalize, a trigger on an angles slot without angles.  None: nothing of this runs.
+    tcuts: after every species' last pcut, on the context that transported it, consumers.tcut_spectra: per time cut the normalised
+    spectrum of the weight still coupled at that time, its sum, the mean and three quantiles of log10 p ("p reached by time t") and
+    their slopes against log10 t (K12 on a HIP backend; on another backend the numpy statement of the same rules).  It is what the
+    tcut_print rewrite published, made from the species' own growth of spectra_coupled, so the tallies stay sums and an ensemble may
+    sample it.  RunResult.tcuts holds [(i_iter, i_ion, TcutSpectra)].  With ensemble, one TCUTS sample per species and iteration goes
+    into Ensemble.tcuts_slot(i_ion - 1) (ensemble.py, "Tcuts").  Refused: tcuts without finalize, on a problem without time cuts,
+    together with tcut_print, with a communicator, a trigger on a tcuts slot without tcuts.  False: no new call is made.
     """
     import torch
     comm = comm or Comm(False)
@@ -835,7 +862,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         verbose=verbose, gather_max=gather_max, skew_max=skew_max, fused_pcuts=fused_pcuts, fused_chunk=fused_chunk,
         long_draws=long_draws, long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
         photons=photons, photon_spectra=[None] * len(cfg.species), last_ion_fin=None, do_escape=bool(escape), escape=[],
-        angle_windows=None, angles=[],
+        angle_windows=None, angles=[], do_tcuts=bool(tcuts), tcuts=[], tcut_base={},
         G_f=None, G_i=None, G_pool=None, stats=[], per_species=[], local_steps=[], empty_launches=[], species_spans=[], iter_finals=[])
     # the step counters are never reset: this rank's running total.  A context that has run before (run() called again with
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
@@ -870,6 +897,19 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             ensemble.set_angle_windows([w[0] for w in rs.angle_windows], [w[1] for w in rs.angle_windows])
     elif any(ens.Ensemble.is_angles(t.slot) for t in triggers):
         raise ValueError("triggers: a trigger on an angles slot needs angles=[...] (no sample would ever arrive)")
+    if tcuts:
+        if not (finalize or smoothing is not None):
+            raise ValueError("tcuts: needs finalize=True (the time-cut spectra belong to the iteration's finalize step)")
+        if not P.do_tcuts or len(prob.tcuts) < 1:
+            raise ValueError("tcuts: the problem tracks no time cuts")
+        if tcut_print:
+            raise ValueError("tcuts: not with tcut_print (its in-place rewrite is what the time-cut spectra replace)")
+        if comm.enabled:
+            raise ValueError("tcuts: one process without a communicator (the multi-rank case is left out)")
+        if ensemble is not None:      # (before the triggers are held against the ensemble's parts)
+            ensemble.expect_tcuts(len(prob.tcuts))
+    elif any(ens.Ensemble.is_tcuts(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on a tcuts slot needs tcuts=True (no sample would ever arrive)")
     if triggers:
         _check_trigger_args(ensemble is not None, "ensemble=", min_iterations, check_every)
         for t in triggers:
@@ -978,7 +1018,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                      rs.local_steps, rs.empty_launches, rs.species_spans, options, ensemble,
                      Convergence(checks, stopped_at, satisfied) if triggers else None,
                      list(rs.photon_spectra) if photons is not None else None, rs.escape if escape else None,
-                     rs.angles if angles is not None else None)
+                     tcuts=rs.tcuts if tcuts else None, angles=rs.angles if angles is not None else None)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over
@@ -990,7 +1030,8 @@ ACCUMULATED_OVER_ITERATIONS = ("esc_flux", "px_esc_feb", "energy_esc_feb", "esc_
 def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pcuts: Optional[int] = None,
                    on_iteration_end: Optional[Callable] = None, first_iter: int = 1,
                    blocks_per_launch: Optional[int] = None, ensemble: bool = False, triggers: Optional[list] = None,
-                   min_iterations: int = 2, check_every: int = 1, photons=None, escape: bool = False, angles=None) -> RunResult:
+                   min_iterations: int = 2, check_every: int = 1, photons=None, escape: bool = False, angles=None,
+                   tcuts: bool = False) -> RunResult:
     """The iterations of a run with a FIXED shock profile (smooth-shocks = false -- the stock mc_in.toml, BASELINE
     config[1]) are independent Monte-Carlo realisations: nothing an iteration computes enters the next one's transport
     (src/main_loops.jl:52-121: every tally the transport reads is reset at the top; the RNG keys carry i_iter).  Their
@@ -1037,7 +1078,10 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     spectra of the last iteration consumed.  Refused: a trigger on a photons slot or on the source slot without photons=.  None:
     no spectra are made.
     escape: refused -- the escape spectra of run(escape=True) are left out of the overlapped path.
-    angles: refused likewise -- the pitch-angle distributions of run(angles=[...]) are left out of the overlapped path."""
+    angles: refused likewise -- the pitch-angle distributions of run(angles=[...]) are left out of the overlapped path.
+    tcuts: refused likewise -- the time-cut spectra of run(tcuts=True) are left out of the overlapped path."""
+    if tcuts or any(ens.Ensemble.is_tcuts(t.slot) for t in (triggers or [])):
+        raise ValueError("tcuts: the overlapped run leaves the time-cut spectra out; use run(finalize=True, tcuts=True)")
     if angles is not None or any(ens.Ensemble.is_angles(t.slot) for t in (triggers or [])):
         raise ValueError("angles: the overlapped run leaves the pitch-angle distributions out; use run(finalize=True, angles=[...])")
     if escape or any(ens.Ensemble.is_escape(t.slot) for t in (triggers or [])):

@@ -75,6 +75,24 @@ zones=Ensemble.angles_row(frame, zone, window) of a `Request`, `Trigger`, `Compa
 bins of that dist row.  A window that no particle reached has NaN moments in that sample: the word's mean stays non-finite, a summary
 counts it in n_nonfinite and a trigger over it is never met -- windows belong on zones and momenta that the population reaches.
 
+Tcuts (include/mcs.h, "tcuts sample"): the time-cut spectra of consumers.tcut_spectra (K12), sampled once per species and iteration by
+driver.run(finalize=True, tcuts=True, ensemble=...).  Every species slot s has a fifth companion, the tcuts slot
+`Ensemble.tcuts_slot(s)`, whose vectors exist from its first sample on.  The number of time cuts nt is fixed by the ensemble's first
+tcuts sample; a later sample, merge, summarize_merged or compare with another nt is refused.  Its parts:
+
+  spectrum    [nt][nmom+2]: the species' growth of spectra_coupled in the iteration, normalised per cut; 1e-99 in an empty bin
+  weight      [nt]: weight_coupled, floored as tcut_print floors it
+  number      [nt]: the sum a spectrum row was normalised with
+  mean_log_p  [nt]: the mean of log10 p over the row
+  quantile    [3][nt]: log10 of the momentum below which 50, 90, 99 % of the still-coupled weight lies, "p reached by time t"
+  index       [3]: the slope of each quantile against log10 t over the live cuts
+
+zones=Ensemble.tcuts_row(k) of a `Request`, `Trigger` or `CompareRequest` selects cut k of spectrum, weight, number and mean_log_p,
+bins= a momentum window of that spectrum row; of quantile, zones=(j, j + 1) selects the quantile and bins=Ensemble.tcuts_row(k) the
+cut.  A cut that no particle reached is a dead row: its mean_log_p and quantiles are NaN in that sample, the word's mean stays
+non-finite, a summary counts it in n_nonfinite and a trigger over it is never met -- triggers belong on cuts below age_max (the last
+cut lies above 10 age_max and is always dead).
+
 Photons (include/mcs.h, "photons sample"): the photon spectra at Earth per photon shell, consumers.observed_spectra.  A shell spectrum is
 a sum over zones, slices in cos(theta) and processes, so its variance does not follow from per-cell variances either: every species
 slot s has a second companion, `Ensemble.photons_slot(s)`, sampled once per iteration (`add_photons`) and allocated at its first
@@ -174,6 +192,12 @@ ANGLE_MAX_WINDOWS = 8                     # MCS_ANGLE_MAX_WINDOWS
 ZONE_PARTS = ZONE_PARTS + tuple(n for n in ANGLES_NAMES if n not in ZONE_PARTS)
 BIN_PARTS = BIN_PARTS + ("dist",)
 ANGLES_BIT = capi.ENS_ANGLES_BIT          # angles slot of species slot s: s | ANGLES_BIT (MCS_ENS_ANGLES)
+# the parts of a tcuts slot, in the order of mcs_tcut_layout: first axis the cut (zones=; Ensemble.tcuts_row), spectrum's second the
+# momentum bin (bins=); quantile is [quantile][cut]
+TCUTS_NAMES = ("spectrum", "weight", "number", "mean_log_p", "quantile", "index")
+ZONE_PARTS = ZONE_PARTS + tuple(n for n in TCUTS_NAMES if n not in ZONE_PARTS)
+BIN_PARTS = BIN_PARTS + ("spectrum", "quantile")
+TCUTS_BIT = capi.ENS_TCUTS_BIT            # tcuts slot of species slot s: s | TCUTS_BIT (MCS_ENS_TCUTS)
 
 
 class EnsLayout:
@@ -233,6 +257,18 @@ class EnsLayout:
         t = self.angles(n_win)
         rows, nt = t["dist"][1]
         return dict(dist=0, number=t["number"][0], mean_mu=t["mean_mu"][0], mean_mu2=t["mean_mu2"][0], row_n=nt, rows=rows, total=rows * (nt + 3))
+
+    def tcuts(self, n_tcuts: int) -> Dict[str, Tuple[int, tuple]]:
+        """The tcuts sample of n_tcuts cuts: mirror of `mcs_ens_tcuts_get_layout`."""
+        nm, nt = self.tally.shapes["psd"][2], int(n_tcuts)
+        a = nt * nm
+        return {"spectrum": (0, (nt, nm)), "weight": (a, (nt,)), "number": (a + nt, (nt,)), "mean_log_p": (a + 2 * nt, (nt,)),
+                "quantile": (a + 3 * nt, (3, nt)), "index": (a + 6 * nt, (3,))}
+
+    def tcuts_fields(self, n_tcuts: int) -> Dict[str, int]:
+        t = self.tcuts(n_tcuts)
+        nt, nm = t["spectrum"][1]
+        return dict({name: off for name, (off, _) in t.items()}, row_n=nm, n_tcuts=nt, total=nt * (nm + 6) + 3)
 
     def species_sample(self, f: np.ndarray, i: np.ndarray) -> np.ndarray:
         """The species sample of the tally buffers (f, i).  The marginals are serial sums in ascending index order, one index
@@ -312,10 +348,11 @@ def stats_over(samples):
 def _check_part(name: str, zones, bins=None):
     """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis, a bins
     window is a pair, comes with a single zone and the part has a bins axis."""
-    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES + ANGLES_NAMES:
+    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES + ANGLES_NAMES + TCUTS_NAMES:
         raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}; "
                          f"a products slot: {', '.join(PRODUCT_NAMES)}; a photons slot: {', '.join(PHOTON_NAMES)}; "
-                         f"an escape slot: {', '.join(ESCAPE_NAMES)}; an angles slot: {', '.join(ANGLES_NAMES)}")
+                         f"an escape slot: {', '.join(ESCAPE_NAMES)}; an angles slot: {', '.join(ANGLES_NAMES)}; "
+                         f"a tcuts slot: {', '.join(TCUTS_NAMES)}")
     if bins is not None:
         if name not in BIN_PARTS:
             raise ValueError(f"ensemble: {name!r} has no [zone][bins] shape; a bins window fits: {', '.join(BIN_PARTS)}")
@@ -621,14 +658,23 @@ def _det_log10(backend):
 
 
 def slopes_of(dndp: np.ndarray, l_lo: int, l_hi: int, x_log: np.ndarray, log10) -> np.ndarray:
-    """The slope definition of the module docstring for every row of dndp [...][nmom+2] -> [...]: the rows side by side in numpy,
-    the bins of a row one after the other, so that every sum is the serial one."""
+    """The slope definition of the module docstring for every row of dndp [...][nmom+2] -> [...]."""
     d = np.asarray(dndp, dtype=np.float64)
     rows = d.reshape(-1, d.shape[-1])[:, l_lo:l_hi]
     valid = rows > DNDP_FLOOR
     y = np.zeros_like(rows)
     y[valid] = log10(np.ascontiguousarray(rows[valid]))
-    x = np.asarray(x_log, dtype=np.float64)[l_lo:l_hi]
+    return slopes_xy(np.asarray(x_log, dtype=np.float64)[l_lo:l_hi], y, valid).reshape(d.shape[:-1])
+
+
+def slopes_xy(x: np.ndarray, y: np.ndarray, valid: np.ndarray) -> np.ndarray:
+    """The least-squares slope rule of the module docstring for every row of y [rows][n] against x [n] over the entries that
+    valid [rows][n] admits -> [rows]: the rows side by side in numpy, the entries of a row one after the other, so that every sum is
+    the serial one.  Fewer than three valid entries: NaN."""
+    rows = np.asarray(y, dtype=np.float64)
+    valid = np.asarray(valid, dtype=bool)
+    y = np.where(valid, rows, 0.0)
+    x = np.asarray(x, dtype=np.float64)
     k = valid.sum(axis=1).astype(np.float64)
     sx, sy = np.zeros(len(rows)), np.zeros(len(rows))
     for l in range(rows.shape[1]):
@@ -642,7 +688,7 @@ def slopes_of(dndp: np.ndarray, l_lo: int, l_hi: int, x_log: np.ndarray, log10) 
             sxx = np.where(valid[:, l], sxx + dx * dx, sxx)
             sxy = np.where(valid[:, l], sxy + dx * (y[:, l] - ybar), sxy)
         slope = np.where(k >= 3, sxy / sxx, np.nan)
-    return slope.reshape(d.shape[:-1])
+    return slope
 
 
 def check_angle_windows(nmom: int, l_lo, l_hi) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
@@ -671,6 +717,7 @@ class Ensemble:
         self.window = None             # (l_lo, l_hi, x_log) of set_slope_window
         self.photon_layout = None      # consumers.PhotonLayout of set_photon_layout
         self.angle_windows = None      # ((l_lo, ...), (l_hi, ...)) of set_angle_windows
+        self.tcuts_n = None            # the number of time cuts of the tcuts samples, fixed by the first
         self._deposited: List[int] = []      # species slots deposited since the last add_photons_all, in deposit order
 
     @staticmethod
@@ -755,6 +802,37 @@ class Ensemble:
     def _angle_windows_differ(a, b) -> bool:
         return a.angle_windows is not None and b.angle_windows is not None and a.angle_windows != b.angle_windows
 
+    def tcuts_slot(self, s: int) -> int:
+        """The slot number of the time-cut spectra of species slot s (MCS_ENS_TCUTS)."""
+        if not 0 <= s < self.n_species:
+            raise ValueError(f"ensemble: slot {s} is no species slot (0..{self.n_species - 1}); only a species slot has a tcuts slot")
+        return int(s) | TCUTS_BIT
+
+    @staticmethod
+    def is_tcuts(slot: int) -> bool:
+        return (slot >= 0 and slot != PHOTONS_ALL and not slot & (PRODUCTS_BIT | PHOTONS_BIT | ESCAPE_BIT | ANGLES_BIT)
+                and bool(slot & TCUTS_BIT))
+
+    @staticmethod
+    def tcuts_row(k: int) -> Tuple[int, int]:
+        """zones= of time cut k (0-based) of a tcuts slot's spectrum, weight, number and mean_log_p; bins= of cut k of a quantile."""
+        if int(k) != k or k < 0:
+            raise ValueError(f"ensemble: a time cut is an index 0, 1, ..., not {k!r}")
+        return int(k), int(k) + 1
+
+    def expect_tcuts(self, n_tcuts: int):
+        """The number of time cuts the tcuts samples will have, so that requests and triggers can name their parts before the first
+        sample arrives (which fixes it for good).  Refused where the ensemble's tcuts samples have another."""
+        if self.tcuts_n is not None and self.tcuts_n != int(n_tcuts):
+            raise ValueError(f"ensemble: {n_tcuts} time cuts, but the ensemble's tcuts samples have {self.tcuts_n}")
+        if not 1 <= int(n_tcuts) <= 99:
+            raise ValueError(f"ensemble: a tcuts sample has 1..99 time cuts, not {n_tcuts!r}")
+        self.tcuts_n = int(n_tcuts)
+
+    @staticmethod
+    def _tcuts_differ(a, b) -> bool:
+        return a.tcuts_n is not None and b.tcuts_n is not None and a.tcuts_n != b.tcuts_n
+
     photons_all_slot = PHOTONS_ALL     # the source slot, one per ensemble (MCS_ENS_PHOTONS_ALL)
 
     @staticmethod
@@ -786,7 +864,7 @@ class Ensemble:
         self.photon_layout = layout
 
     def _decode(self, slot: int) -> Tuple[str, Optional[int]]:
-        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source", "escape" or "angles" -- the one place where
+        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source", "escape", "angles" or "tcuts" -- the one place where
         its bits are read; the index is None for the iteration and the source slot, and not yet checked (`_check_slot`)."""
         if self.is_photons_all(slot):
             return "source", None
@@ -798,6 +876,8 @@ class Ensemble:
             return "escape", slot ^ ESCAPE_BIT
         if self.is_angles(slot):
             return "angles", slot ^ ANGLES_BIT
+        if self.is_tcuts(slot):
+            return "tcuts", slot ^ TCUTS_BIT
         return ("iteration", None) if slot == self.iteration_slot else ("species", slot)
 
     def _kind(self, slot: int) -> str:
@@ -805,18 +885,18 @@ class Ensemble:
 
     def _describe(self, slot: int) -> str:
         kind, s = self._decode(slot)
-        if kind in ("products", "photons", "escape", "angles"):
+        if kind in ("products", "photons", "escape", "angles", "tcuts"):
             return f"the {kind} slot of species slot {s}"
         return f"species slot {s}" if kind == "species" else f"the {kind} slot"
 
     def names(self, slot: int):
         self._check_slot(slot)
         return {"species": SPECIES_NAMES, "iteration": ITERATION_NAMES, "products": PRODUCT_NAMES, "escape": ESCAPE_NAMES,
-                "angles": ANGLES_NAMES}.get(self._kind(slot), PHOTON_NAMES)
+                "angles": ANGLES_NAMES, "tcuts": TCUTS_NAMES}.get(self._kind(slot), PHOTON_NAMES)
 
     def _check_slot(self, slot: int):
         kind, s = self._decode(slot)
-        if kind in ("products", "photons", "escape", "angles") and not 0 <= s < self.n_species:
+        if kind in ("products", "photons", "escape", "angles", "tcuts") and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: {kind} slot of slot {s}, which is no species slot (0..{self.n_species - 1})")
         if kind == "species" and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: slot {slot} outside 0..{self.n_species}")
@@ -827,6 +907,8 @@ class Ensemble:
             return 0 if self.photon_layout is None else self.photon_layout.offsets()["_total"]
         if kind == "angles":
             return 0 if self.angle_windows is None else self.layout.angles_fields(len(self.angle_windows[0]))["total"]
+        if kind == "tcuts":
+            return 0 if self.tcuts_n is None else self.layout.tcuts_fields(self.tcuts_n)["total"]
         return {"species": self.layout.species_total, "iteration": self.layout.iteration_total, "products": self.layout.products_total,
                 "escape": self.layout.escape_total}[kind]
 
@@ -843,6 +925,10 @@ class Ensemble:
             if self.angle_windows is None:
                 raise ValueError(f"ensemble: {self._describe(slot)} has no windows yet (set_angle_windows)")
             table = self.layout.angles(len(self.angle_windows[0]))
+        elif kind == "tcuts":
+            if self.tcuts_n is None:
+                raise ValueError(f"ensemble: {self._describe(slot)} has taken no sample yet (its first fixes the number of time cuts)")
+            table = self.layout.tcuts(self.tcuts_n)
         else:
             table = {"species": self.layout.species, "iteration": self.layout.iteration, "products": self.layout.products,
                      "escape": self.layout.escape}[kind]
@@ -1079,6 +1165,22 @@ class HostEnsemble(Ensemble):
         with np.errstate(invalid="ignore"):          # (a NaN moment stays NaN)
             self._sample(self.angles_slot(slot), x)
 
+    def add_tcuts(self, backend, slot: int, spectra):
+        """One tcuts sample of species slot `slot` from a `TcutSpectra` (consumers.tcut_spectra); the ensemble's first fixes the
+        number of time cuts."""
+        self._species_slot(slot, "a tcuts slot")
+        if spectra is None:
+            raise ValueError("ensemble: the numpy ensemble takes its tcuts sample from a TcutSpectra")
+        nt = len(spectra.number)
+        if self.tcuts_n is not None and nt != self.tcuts_n:
+            raise ValueError(f"ensemble: the TcutSpectra has {nt} time cuts, the ensemble's tcuts samples have {self.tcuts_n}")
+        x = spectra.words()
+        if x.size != self.layout.tcuts_fields(nt)["total"]:
+            raise ValueError(f"ensemble: the TcutSpectra holds {x.size} words; a tcuts sample of {nt} cuts has {self.layout.tcuts_fields(nt)['total']}")
+        self.tcuts_n = nt
+        with np.errstate(invalid="ignore"):          # (a NaN of a dead row stays NaN)
+            self._sample(self.tcuts_slot(slot), x)
+
     def add_escape(self, backend, slot: int, spectra):
         """One escape sample of species slot `slot` from an `EscapeSpectra` (consumers.escape_spectra on `backend`), the slopes of its
         six rows by the backend's deterministic log10."""
@@ -1147,6 +1249,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: merge of ensembles whose photon layouts differ")
         if self._angle_windows_differ(self, other):
             raise ValueError("ensemble: merge of ensembles whose angle windows differ")
+        if self._tcuts_differ(self, other):
+            raise ValueError("ensemble: merge of ensembles whose tcuts samples differ in the number of time cuts")
         # an ensemble without a photon layout or a slope window takes the one its samples were made with
         if other._sampled("photons", "source") and self.photon_layout is None:
             self.photon_layout = other.photon_layout
@@ -1154,6 +1258,8 @@ class HostEnsemble(Ensemble):
             self.window = other.window
         if other._sampled("angles") and self.angle_windows is None:
             self.angle_windows = other.angle_windows
+        if other._sampled("tcuts") and self.tcuts_n is None:
+            self.tcuts_n = other.tcuts_n
         for k, b in other._slots.items():      # (what is pending for the source slot on either side stays where it is)
             if b.n == 0:
                 continue
@@ -1192,6 +1298,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: a merged summary of ensembles whose photon layouts differ")
         if self.is_angles(slot) and any(self._angle_windows_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose angle windows differ")
+        if self.is_tcuts(slot) and any(self._tcuts_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
+            raise ValueError("ensemble: a merged summary of ensembles whose tcuts samples differ in the number of time cuts")
         for first, count, floor_frac, tol in ranges:
             m, q, na = None, None, 0
             for e in [self] + others:
@@ -1211,6 +1319,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: a comparison of ensembles whose photon layouts differ")
         if self.is_angles(slot) and self._angle_windows_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose angle windows differ")
+        if self.is_tcuts(slot) and self._tcuts_differ(self, other):
+            raise ValueError("ensemble: a comparison of ensembles whose tcuts samples differ in the number of time cuts")
         (ma, qa, _), (mb, qb, _) = self._vectors(slot), other._vectors(other_slot)
         return [difference_of(ma[first:first + count], qa[first:first + count], n_a, mb[first:first + count], qb[first:first + count], n_b,
                               floor_frac, zcut) for first, count, floor_frac, zcut in ranges]
@@ -1283,6 +1393,13 @@ class HipEnsemble(Ensemble):
         device (mcs_ens_add_angles); nothing crosses to the host, `angles` is not read."""
         self._chk(self.lib.mcs_ens_add_angles(self.h, backend.h, int(slot)))
 
+    def add_tcuts(self, backend: HipBackend, slot: int, spectra=None):
+        """One tcuts sample of species slot `slot` from what mcs_tcut_spectra (consumers.tcut_spectra) left on the backend's device
+        (mcs_ens_add_tcuts); nothing crosses to the host, `spectra` is not read."""
+        self._chk(self.lib.mcs_ens_add_tcuts(self.h, backend.h, int(slot)))
+        if self.tcuts_n is None:
+            self.tcuts_n = int(backend.n_tcuts)      # (as the library does: the first sample fixes it)
+
     def _set_photon_layout(self, layout):
         self._chk(self.lib.mcs_ens_set_photon_layout(self.h, *layout.args()))
 
@@ -1317,6 +1434,8 @@ class HipEnsemble(Ensemble):
             self.window = other.window      # (as the library does: an accumulator without a window takes the one its samples were made with)
         if self.angle_windows is None and other.angle_windows is not None and any(other.count(other.angles_slot(s)) for s in range(other.n_species)):
             self.angle_windows = other.angle_windows      # (likewise)
+        if self.tcuts_n is None and other.tcuts_n is not None and any(other.count(other.tcuts_slot(s)) for s in range(other.n_species)):
+            self.tcuts_n = other.tcuts_n      # (likewise)
 
     def count(self, slot: int) -> int:
         n = ct.c_int64(0)

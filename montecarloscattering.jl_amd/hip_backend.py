@@ -81,6 +81,7 @@ class HipBackend:
         pc, tc, xs, inj, eps = (np.ascontiguousarray(a, dtype=np.float64) for a in
                                 (prob.pcuts, prob.tcuts, prob.x_spec, prob.inj_fracs, prob.eps_target))
         self._chk(self.lib.mcs_set_cuts(self.h, len(pc), _dp(pc), len(tc), _dp(tc), len(xs), _dp(xs), _dp(inj), _dp(eps)))
+        self.n_tcuts = len(tc)
 
     def destroy(self):
         if self.h:
@@ -384,6 +385,18 @@ class HipBackend:
         self._chk(self.lib.mcs_angle_dist(self.h, ct.byref(s), n_win, lo.ctypes.data_as(c_int32_p), hi.ctypes.data_as(c_int32_p), _dp(dist),
                                           _dp(number), _dp(moments)))
         return dist, number, moments
+
+    def tcut_spectra(self, tabs):
+        """K12: the spectra of the time cuts of the context's current species from the resident weight_coupled and spectra_coupled and
+        the base taken at begin_species -> (out, diag [2]); `out` in mcs_tcut_layout (capi.tcut_layout), diag = (live rows, words with
+        now < base)."""
+        if self.n_tcuts < 1:
+            raise ValueError("tcut_spectra: the context has no time cuts")
+        out = np.zeros(capi.tcut_layout(self.P, self.n_tcuts).total)
+        diag = np.zeros(2, dtype=np.int64)
+        s = tabs.as_struct()
+        self._chk(self.lib.mcs_tcut_spectra(self.h, ct.byref(s), _dp(out), diag.ctypes.data_as(c_int64_p)))
+        return out, diag
 
     def photon_synch(self, dndp_pf, mom_edge_cgs, mc, n_photon, emin_mev, bins_per_dec):
         """K5: synchrotron emission dP/d(ln E) [erg/s] per zone from the plasma-frame electron dN/dp -> (E_erg[n_photon], emis[n_grid][n_photon])."""
