@@ -533,6 +533,90 @@ typedef struct mcs_tcut_layout {
 int mcs_tcut_get_layout(const mcs_params* p, int n_tcuts, mcs_tcut_layout* out);     /* needs no GPU */
 int mcs_tcut_spectra(mcs_ctx* ctx, const mcs_consumer_in* in, double* out, int64_t* diag);
 
+/* K13: the shock-profile update, "which profile would smooth_grid_par write from this iteration" (the reference's iter_finalize,
+ * src/iter_finalize.jl:1-110, with smooth_grid_par / new_velocity_profile / smooth_profile!, src/smoothers.jl:54-604, as the host's
+ * iter_finalize.py restates them), up to and including ux_new = (ux_new + w ux) / (1 + w).  The refresh of the grid tables that
+ * follows (gam_sf, beta_ef, btot ...) is not part of it, and nothing on the context but the result buffer is written.
+ * READ WHERE IT LIES: pxx_flux, energy_flux [n_grid] and scalars [4] of the resident tallies; ux, gam_sf, x_grid_cm of mcs_set_grid
+ * (entries 1..n_grid); P_par | P_perp | energy_density [n_grid] each as the last mcs_thermo_calcs left them on the device -- or,
+ * with a non-null `pressures`, 3 n_grid host doubles in that order in their place (crafted inputs; pressures made elsewhere).  No
+ * other tally word is read.  u0, beta0, gam0, n_grid, i_shock are the context's parameters.
+ * PASSED BY THE HOST in a mcs_profile_in, none of which depends on the iteration's tallies: the upstream fluxes, the species sums P0 = kB sum
+ * n T and rho0 = sum n m of q_esc_calcs, n0_aa = sum n aa, r_comp, r_RH, u2, beta2, gam2, SMMOE, SMPFP, the old-profile weight w AFTER
+ * the increase_old_profile_weighting rule, i_trans (the Julia zone number at which the artificial arctangent section starts; 0 = no
+ * artificial smoothing), n_hist <= 3 earlier (q_px, q_en) pairs oldest first, and three tables of n_grid doubles for zones 1..n_grid:
+ * pxx_EM, en_EM (the electromagnetic fluxes of the current profile and field) and atan_x = atan(x_grid_rg).
+ * ARITHMETIC: fp64, every operation rounded separately, in the order of the Python expressions of iter_finalize.py as Python
+ * evaluates them, with their parentheses; the numpy lines elementwise.  Only + - * /, sqrt_ (mcs_math.h), rint, copysign, fabs and
+ * comparisons; no transcendental is evaluated on the device.  POWERS ARE PRODUCTS: a**2 is a*a, a**3 is (a*a)*a.  This is a
+ * deliberate difference from iter_finalize.py: CPython's x**2 is pow(x, 2), which differs from x*x in about 1 of 1200 doubles (x**3
+ * from (x*x)*x in 26 %), so this statement is NOT bit-equal to the host file; it agrees with it to rounding.
+ * NaN and infinity propagate as IEEE gives them (arr[0] == avg is a division by zero); max(a, 1e-99) is (1e-99 > a ? 1e-99 : a).
+ * With c = MCS_C, mp = MCS_MP, zone j = 0..n-1 (table entry j + 1), sc = scalars:
+ *   SCALARS  px_esc = sc[2] / F_px_upstream; en_esc = sc[3] / F_energy_upstream; gamma_down = 1 + sc[0] / sc[1].
+ *   Q  (q_esc_calcs; its two returns bound to (q_px, q_en) in the reference's order)  r_comp == r_RH: both 0.  Else Gf = G / (G - 1)
+ *     with G = gamma_down, rho2 = ((rho0 gam0) beta0) / (gam2 beta2), and for beta0 >= 0.02 (the RELATIVISTIC branch, also below):
+ *       q_fac = c sqrt_((1 + beta0) / 2); e = rho0 (c c) + 2.5 P0; Fp = ((gam0 gam0)(beta0 beta0)) e + P0; Fe = ((gam0 gam0) u0) e;
+ *       aux = (gam2 gam2)(q_fac (beta2 beta2) - u2); P2 = ((q_fac Fp - Fe) - (aux rho2)(c c)) / (q_fac + Gf aux); t = gam2 beta2;
+ *       Qp = (Fp - (t t)(rho2 (c c) + Gf P2)) - P2; q_px = (Qp q_fac) / (Fe - ((gam0 u0) rho0)(c c)); q_en = Qp / Fp
+ *     otherwise (CLASSICAL): Fp = rho0 (u0 u0) + P0; Fe = (rho0 ((u0 u0) u0)) / 2 + (2.5 P0) u0; P2 = Fp - rho2 (u2 u2);
+ *       q_px = ((Fe - ((rho0 u0)(u2 u2)) / 2) - (P2 u2) Gf) / Fe; q_en = 0.
+ *     AVERAGE: q_avg = (((h0 + h1) + h2) + q) / k over the n_hist history values in their order and then this iteration's, k = n_hist + 1
+ *     (the sum starts with its first term).
+ *   ROUNDING  pxx[j] = rint(pxx_flux[j] 1e13) / 1e13, en[j] likewise (np.round(x, 13)); rows flux_px = pxx / F_px_upstream, flux_en.
+ *   GAMMA  Ptot = P_par + P_perp; G[j] = 1 + Ptot / e_dens, but 1e-99 where e_dens == 1e-99; Xi = G / (G - 1).
+ *   Qpx = q_px_avg pxx[0] (relativistic; 0.0 classical); Qen = q_en_avg en[0]; u = ux[j]; b = u / c; g = gam_sf[j].
+ *   RELATIVISTIC ZONE  gb = g b; gb2 = gb gb; dens = ((gam0 beta0) / (g b)) n0_aa; p_px = (pxx - ((gb2 dens) mp)(c c)) / (1 + gb2 Xi);
+ *     p_loc = (1 - SMPFP) p_px + SMPFP Ptot; y = (((F_px - Qpx) - pxx_EM) - p_loc) / (((gam0 beta0) n0_aa)(mp (c c) + (p_loc Xi) / dens));
+ *     ux_px = (y / sqrt_(1 + y y)) c; K = ((F_en - Qen) - en_EM) / (c ((dens mp)(c c) + Xi p_loc)); z = (-1 + sqrt_(1 + (4 K) K)) / 2;
+ *     y = copysign(sqrt_(z), K); ux_en = (y / sqrt_(1 + y y)) c.
+ *   CLASSICAL ZONE  rm = n0_aa mp; p_px = (pxx - ((rm u0) u)(1 + b b)) / (1 + (b b) Xi); p_loc as above; A = (F_px - Qpx) - pxx_EM;
+ *     B = (F_en - Qen) - en_EM.  NEWTON: x from x0, at most 10000 times { dx = f / f'; x = x - dx; stop when |dx| <= 1e-14 |x| } (a NaN
+ *     never passes: such a zone runs all its steps).  Momentum, x0 = (u0 / c) 1e-4: f = (A - ((rm u0)(x c))(1 + x x)) - (1 + (x x) Xi) p_loc,
+ *     f' = -(((rm u0) c)(1 + (3 x) x) + ((2 x) Xi) p_loc); ux_px = x c.  Energy, x0 = u0 1e-4, t = x / c, t2 = t t:
+ *     f = (B - ((((0.5 rm) u0) x) x)(1 + 1.25 t2)) - ((Xi p_loc) x)(1 + t2), f' = -(((rm u0) x)(1 + 2.5 t2) + (Xi p_loc)(1 + 3 t2)); ux_en = x.
+ *   LAST TEN  avg = (0.0 + a[n-10] + ... + a[n-1]) / 10 for a = ux_px and ux_en, ascending from zone max(0, n - 10), before any smoothing,
+ *     divided by 10 whatever n_grid.
+ *   SMOOTH (smooth_profile!)  for i = n-1 down to 1: if a[i-1] < a[i] then a[i-1] = a[i].  Then from the row as that pass left it:
+ *     d[1] = ((2 a[0] + a[1]) + a[2]) / 4; d[i] = ((a[i-1] + a[i]) + a[i+1]) / 3 for 2 <= i <= n-3; d[n-2] = ((a[n-3] + a[n-2]) + 2 a[n-1]) / 4
+ *     (in this order, a later one replacing an earlier); a[1..n-2] = d[1..n-2].
+ *   RESCALE  s = (u0 - u2) / (a[0] - avg); a[j] = s (a[j] - avg) + u2 for every j, from the a[0] before it; then zones with
+ *     x_grid_cm >= 0 are pinned to u2.  Relativistic: smooth, then rescale; classical: rescale, then smooth.
+ *   BLEND  ux_pred = (1 - SMMOE) ux_px + SMMOE ux_en (the return of new_velocity_profile).
+ *   ARTIFICIAL (i_trans > 0)  s = -(ux_pred[i_trans-1] - ux_pred[n-1]) / atan_x[i_trans-1]; zones i_trans..i_shock (j = i_trans-1 .. i_shock-1):
+ *     v[j] = (-atan_x[j]) s + ux_pred[n-1]; elsewhere v = ux_pred.
+ *   WEIGHT  ux_next = (v + w u) / (1 + w).  SHIFT  shift = (ux_pred - u) / u0; shift_rms = sqrt_(S / n), S = 0.0 + shift[0]^2 + ..., ascending.
+ * out: host, laid out as mcs_profile_get_layout says (it needs no GPU): ten rows of n_grid doubles -- flux_px, flux_en, gamma_ad (G),
+ *   p_flux (p_px), p_used (p_loc), ux_px, ux_en (after rescale and smooth), ux_pred, ux_next, shift -- then the eight scalars gamma_down,
+ *   px_esc_up, en_esc_up (= max(., 1e-99), as the host floors them last), q_px, q_en, q_px_avg, q_en_avg, shift_rms.  Total 10 n_grid + 8.
+ * diag: host [3] or null: the number of non-finite words of out; the number of zones in which a Newton iteration ran out of steps;
+ *   the largest Newton step count (0 in the relativistic branch).
+ * One launch of one workgroup, no atomics: every call on the same inputs gives the same bits.  The result also stays on the device, in
+ * a buffer that no other call writes, for the profile sample of the ensemble statistics (below); mcs_begin_species, a tally write and
+ * that sample invalidate it.
+ * Refused, with a message: before mcs_set_grid, before the first mcs_begin_species, pressures == NULL on a context whose
+ * mcs_thermo_calcs result is not whole (never run, or taken by a products sample), i_trans outside [0, i_shock], n_hist outside
+ * [0, 3], n_grid < 3, a null table or output. */
+#define MCS_PROFILE_ROWS 10
+#define MCS_PROFILE_SCALARS 8
+#define MCS_PROFILE_MAX_HIST 3
+#define MCS_PROFILE_NEWTON_MAX 10000
+typedef struct mcs_profile_in {
+  double F_px_upstream, F_energy_upstream, P0, rho0, n0_aa, r_comp, r_RH, u2, beta2, gam2, SMMOE, SMPFP, w;
+  int32_t i_trans;                       /* the settings end here: an ensemble keeps the fields above and this one */
+  int32_t n_hist;
+  double hist_q_px[MCS_PROFILE_MAX_HIST], hist_q_en[MCS_PROFILE_MAX_HIST];
+  const double *pxx_EM, *en_EM, *atan_x; /* host [n_grid] each */
+} mcs_profile_in;
+typedef struct mcs_profile_layout {
+  int64_t flux_px, flux_en, gamma_ad, p_flux, p_used, ux_px, ux_en, ux_pred, ux_next, shift, scalars;   /* offsets, in doubles */
+  int64_t row_n;                                            /* n_grid: the length of each of the ten rows */
+  int64_t n_scalars;                                        /* 8 */
+  int64_t total;
+} mcs_profile_layout;
+int mcs_profile_get_layout(const mcs_params* p, mcs_profile_layout* out);     /* needs no GPU */
+int mcs_profile_update(mcs_ctx* ctx, const mcs_profile_in* in, const double* pressures_or_null, double* out, int64_t* diag);
+
 /* ---- photon post-processing: the synchrotron fold of src/synch_emission.jl:27-171 over the plasma-frame
  * dN/dp of an electron species (frame 2 of mcs_dndp_cr), for every grid zone with the zone's field of the grid tables.
  * dNdp_pf: host [n_grid][nmom+2]; mom_edge_cgs: host [nmom+2]; mc of the species; photon energies
@@ -831,6 +915,22 @@ int mcs_ens_add_angles(mcs_ens* ens, mcs_ctx* src, int species_slot);
 typedef mcs_tcut_layout mcs_ens_tcuts_layout;
 int mcs_ens_tcuts_get_layout(const mcs_params* p, int n_tcuts, mcs_ens_tcuts_layout* out);    /* needs no GPU */
 int mcs_ens_add_tcuts(mcs_ens* ens, mcs_ctx* src, int species_slot);
+
+/* ---- profile sample: error bars of the predicted shock profile.  With a FIXED profile every iteration's mcs_profile_update is an
+ * independent sample of the profile that smooth_grid_par would write; its mean and standard error say how far the current profile is
+ * from self-consistency.  The PROFILE slot MCS_ENS_PROFILE, one per accumulator like the source slot, behaves as the source slot does
+ * in the count, read, merge, summarize, summarize-merged and compare calls (vectors allocated at the first sample; reads of a slot
+ * that never took one are refused).  The sample is the last mcs_profile_update on the context as that call left it on the device, in
+ * its layout (mcs_ens_profile_get_layout gives that of mcs_profile_get_layout): ten rows of n_grid doubles, then eight scalars.
+ * The accumulator keeps the SETTINGS of its first sample's mcs_profile_in -- the fields F_px_upstream .. i_trans; the q history and
+ * the tables are not kept -- (or takes them in a merge into an accumulator that has none): a later sample, merge, merged summary or
+ * comparison whose settings differ in any bit is refused.
+ * mcs_ens_add_profile: refused unless mcs_profile_update has run on src since its last mcs_begin_species, tally write and profile
+ * sample.  Queued on src's stream behind the accumulator's event, no host synchronisation.  mcs_ens_load_mean takes species slots only. */
+#define MCS_ENS_PROFILE (1 << 24)
+typedef mcs_profile_layout mcs_ens_profile_layout;
+int mcs_ens_profile_get_layout(const mcs_params* p, mcs_ens_profile_layout* out);    /* needs no GPU */
+int mcs_ens_add_profile(mcs_ens* ens, mcs_ctx* src);
 
 /* ---- photons sample: error bars of the photon spectra at Earth.  A shell spectrum is a sum over zones, slices and processes: its
  * variance does not follow from per-cell variances, so the spectrum itself is sampled once per iteration, from what

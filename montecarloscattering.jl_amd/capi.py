@@ -121,7 +121,24 @@ class McsTcutLayout(ct.Structure):
     _fields_ = [(name, ct.c_int64) for name in ("spectrum", "weight", "number", "mean_log_p", "quantile", "index", "row_n", "n_tcuts", "total")]
 
 
+class McsProfileIn(ct.Structure):
+    """`mcs_profile_in`: what the host hands to the profile update (include/mcs.h, mcs_profile_update); the fields up to i_trans are
+    the settings an ensemble keeps of its first profile sample."""
+    _fields_ = [(name, ct.c_double) for name in ("F_px_upstream", "F_energy_upstream", "P0", "rho0", "n0_aa", "r_comp", "r_RH", "u2", "beta2",
+                                                 "gam2", "SMMOE", "SMPFP", "w")] + \
+               [("i_trans", ct.c_int32), ("n_hist", ct.c_int32), ("hist_q_px", ct.c_double * 3), ("hist_q_en", ct.c_double * 3)] + \
+               [(name, ct.POINTER(ct.c_double)) for name in ("pxx_EM", "en_EM", "atan_x")]
+
+
+class McsProfileLayout(ct.Structure):
+    """`mcs_profile_layout` (= `mcs_ens_profile_layout`): offsets of the ten rows and of the scalars of a profile update, the length of a
+    row and the number of scalars (include/mcs.h, mcs_profile_update and "profile sample")."""
+    _fields_ = [(name, ct.c_int64) for name in ("flux_px", "flux_en", "gamma_ad", "p_flux", "p_used", "ux_px", "ux_en", "ux_pred", "ux_next",
+                                                "shift", "scalars", "row_n", "n_scalars", "total")]
+
+
 TCUT_Q = (0.5, 0.9, 0.99)       # MCS_TCUT_Q
+ENS_PROFILE = 1 << 24           # MCS_ENS_PROFILE: the profile slot, one per accumulator
 ENS_ESCAPE_BIT = 1 << 27        # MCS_ENS_ESCAPE(s) = s | ENS_ESCAPE_BIT
 ENS_ANGLES_BIT = 1 << 26        # MCS_ENS_ANGLES(s) = s | ENS_ANGLES_BIT
 ENS_TCUTS_BIT = 1 << 25         # MCS_ENS_TCUTS(s) = s | ENS_TCUTS_BIT
@@ -371,6 +388,8 @@ def load_library() -> ct.CDLL:
         "mcs_angle_dist": (i32, [vp, ct.POINTER(McsConsumerIn), i32, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
         "mcs_tcut_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsTcutLayout)]),
         "mcs_tcut_spectra": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_int64_p]),
+        "mcs_profile_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsProfileLayout)]),
+        "mcs_profile_update": (i32, [vp, ct.POINTER(McsProfileIn), c_double_p, c_double_p, c_int64_p]),
         "mcs_photon_synch": (i32, [vp, c_double_p, c_double_p, dbl, i32, dbl, dbl, c_double_p, c_double_p]),
         "mcs_run_pcuts_fused": (i32, [vp, i32, i32, c_int64_p, c_int64_p, c_int64_p, c_int64_p, c_double_p]),
         "mcs_run_pcuts_pipelined": (i32, [vp, i32, i32, c_int64_p, ct.c_int64, ct.c_int64, c_int64_p, c_int64_p, c_int64_p, c_double_p, c_int64_p]),
@@ -415,6 +434,8 @@ def load_library() -> ct.CDLL:
         "mcs_ens_add_angles": (i32, [vp, vp, i32]),
         "mcs_ens_tcuts_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsTcutLayout)]),
         "mcs_ens_add_tcuts": (i32, [vp, vp, i32]),
+        "mcs_ens_profile_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsProfileLayout)]),
+        "mcs_ens_add_profile": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -440,6 +461,15 @@ def tcut_layout(P: McsParams, n_tcuts: int) -> McsTcutLayout:
     out = McsTcutLayout()
     lib = load_library()
     if lib.mcs_tcut_get_layout(ct.byref(P), int(n_tcuts), ct.byref(out)) != 0:
+        raise ValueError(lib.mcs_last_error().decode())
+    return out
+
+
+def profile_layout(P: McsParams) -> McsProfileLayout:
+    """`mcs_profile_get_layout`: where the rows and scalars of a profile update lie (needs no GPU)."""
+    out = McsProfileLayout()
+    lib = load_library()
+    if lib.mcs_profile_get_layout(ct.byref(P), ct.byref(out)) != 0:
         raise ValueError(lib.mcs_last_error().decode())
     return out
 
@@ -488,4 +518,6 @@ EXPORTED_SYMBOLS += ["mcs_dndp_esc", "mcs_ens_escape_get_layout", "mcs_ens_add_e
 EXPORTED_SYMBOLS += ["mcs_angle_dist", "mcs_ens_angles_get_layout", "mcs_ens_set_angle_windows", "mcs_ens_add_angles"]
 # the time-cut spectra (K12) and their sample
 EXPORTED_SYMBOLS += ["mcs_tcut_spectra", "mcs_tcut_get_layout", "mcs_ens_tcuts_get_layout", "mcs_ens_add_tcuts"]
+# the shock-profile update (K13) and its sample
+EXPORTED_SYMBOLS += ["mcs_profile_update", "mcs_profile_get_layout", "mcs_ens_profile_get_layout", "mcs_ens_add_profile"]
 PHOTON_PROCESS = {"synch": 0, "ic": 1, "pion": 2}      # MCS_PHOTON_SYNCH, _IC, _PION

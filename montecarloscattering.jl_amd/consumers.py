@@ -343,6 +343,301 @@ def tcut_spectra(prob, backend, i_ion: int, base=None) -> TcutSpectra:
                              prob.tcuts, P.num_psd_mom_bins, ens._det_log10(backend))
 
 
+# ---- K13: the shock-profile update (include/mcs.h, mcs_profile_update) ----------------------------------------------------------
+PROFILE_ROWS = ("flux_px", "flux_en", "gamma_ad", "p_flux", "p_used", "ux_px", "ux_en", "ux_pred", "ux_next", "shift")
+PROFILE_SCALARS = ("gamma_down", "px_esc_up", "en_esc_up", "q_px", "q_en", "q_px_avg", "q_en_avg", "shift_rms")
+PROFILE_SETTINGS = ("F_px_upstream", "F_energy_upstream", "P0", "rho0", "n0_aa", "r_comp", "r_RH", "u2", "beta2", "gam2", "SMMOE",
+                    "SMPFP", "w", "i_trans")
+PROFILE_MAX_HIST = 3
+PROFILE_NEWTON_TOL = 1.0e-14
+PROFILE_NEWTON_MAX = 10_000
+BETA_REL_FL = 0.02          # src/parameters.jl:30 (iter_finalize.BETA_REL_FL)
+
+
+@dataclasses.dataclass
+class ProfileIn:
+    """`mcs_profile_in`: what the host hands to the profile update; nothing in it depends on the iteration's tallies.  The first
+    fourteen fields (PROFILE_SETTINGS) are the settings an ensemble keeps of its first profile sample."""
+    F_px_upstream: float
+    F_energy_upstream: float
+    P0: float                    # kB sum(n0 T0): the species sum of q_esc_calcs
+    rho0: float                  # sum(n0 m)
+    n0_aa: float                 # sum(n0 aa)
+    r_comp: float
+    r_RH: float
+    u2: float
+    beta2: float
+    gam2: float
+    SMMOE: float
+    SMPFP: float
+    w: float                     # the old-profile weight AFTER the increase_old_profile_weighting rule
+    i_trans: int                 # first zone of the artificial arctangent section (Julia zone number); 0: none
+    hist_q_px: tuple = ()        # the q of up to three earlier iterations, oldest first
+    hist_q_en: tuple = ()
+    pxx_EM: np.ndarray = None    # [n_grid]: the electromagnetic momentum flux of the current profile and field
+    en_EM: np.ndarray = None     # [n_grid]
+    atan_x: np.ndarray = None    # [n_grid]: atan(x_grid_rg) of zones 1..n_grid
+
+    def settings(self) -> np.ndarray:
+        return np.array([float(getattr(self, k)) for k in PROFILE_SETTINGS], dtype=np.float64)
+
+    def as_struct(self) -> "capi.McsProfileIn":
+        self._keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (self.pxx_EM, self.en_EM, self.atan_x)]
+        s = capi.McsProfileIn()
+        for k in PROFILE_SETTINGS[:-1]:
+            setattr(s, k, float(getattr(self, k)))
+        s.i_trans = int(self.i_trans)
+        s.n_hist = len(self.hist_q_px)
+        for k in range(min(len(self.hist_q_px), PROFILE_MAX_HIST)):
+            s.hist_q_px[k] = float(self.hist_q_px[k]); s.hist_q_en[k] = float(self.hist_q_en[k])
+        dp = ct.POINTER(ct.c_double)
+        s.pxx_EM, s.en_EM, s.atan_x = (a.ctypes.data_as(dp) for a in self._keep)
+        return s
+
+
+@dataclasses.dataclass
+class ProfileUpdate:
+    """The profile that smooth_grid_par WOULD write from one iteration's fluxes and pressures (K13, include/mcs.h
+    mcs_profile_update), with the intermediate rows.  Rows are zones 1..n_grid."""
+    rows: np.ndarray             # [10][n_grid], PROFILE_ROWS
+    scalars: np.ndarray          # [8], PROFILE_SCALARS
+    diag: np.ndarray             # [3]: non-finite output words, zones whose Newton ran out of steps, the largest Newton step count
+    settings: np.ndarray         # ProfileIn.settings() of the call
+
+    def __getattr__(self, name):
+        if name in PROFILE_ROWS:
+            return self.rows[PROFILE_ROWS.index(name)]
+        if name in PROFILE_SCALARS:
+            return float(self.scalars[PROFILE_SCALARS.index(name)])
+        raise AttributeError(name)
+
+    def words(self) -> np.ndarray:
+        """The result as one vector in mcs_profile_layout, the profile sample of the ensemble statistics."""
+        return np.concatenate([np.asarray(self.rows, dtype=np.float64).ravel(), np.asarray(self.scalars, dtype=np.float64)])
+
+
+def _profile_from_words(out, diag, n, settings) -> ProfileUpdate:
+    o = np.asarray(out, dtype=np.float64)
+    return ProfileUpdate(o[:10 * n].reshape(10, n).copy(), o[10 * n:10 * n + 8].copy(), np.asarray(diag, dtype=np.int64).copy(),
+                         np.asarray(settings, dtype=np.float64))
+
+
+def _profile_smooth(y):
+    """`smooth_profile!` on a numpy row: the descending `<` pass, then the 1-2-1 / three-point filter."""
+    n = len(y)
+    for i in range(n - 1, 0, -1):
+        if y[i - 1] < y[i]:
+            y[i - 1] = y[i]
+    d = y.copy()
+    d[1] = (2 * y[0] + y[1] + y[2]) / 4
+    for i in range(2, n - 2):
+        d[i] = (y[i - 1] + y[i] + y[i + 1]) / 3
+    d[n - 2] = (y[n - 3] + y[n - 2] + 2 * y[n - 1]) / 4
+    y[1:n - 1] = d[1:n - 1]
+
+
+def _profile_newton(f_df, x0):
+    x, steps = np.float64(x0), 0
+    for _ in range(PROFILE_NEWTON_MAX):
+        f, df = f_df(x)
+        dx = f / df
+        x = x - dx
+        steps += 1
+        if abs(dx) <= PROFILE_NEWTON_TOL * abs(x):
+            return x, steps, False
+    return x, steps, True
+
+
+def profile_update_host(pin: ProfileIn, params, ux_tab, gam_sf_tab, x_grid_cm, pxx_flux, energy_flux, scalars, P_par, P_perp,
+                        e_dens) -> ProfileUpdate:
+    """The rules of mcs_profile_update (include/mcs.h) in numpy: the elementwise lines side by side over the zones, the ordered
+    ones zone after zone; powers are products.  params: u0, beta0, gam0, n_grid, i_shock; the three tables have n_grid + 2 entries,
+    the tallies and pressures n_grid."""
+    f8 = np.float64
+    n, i_shock = int(params.n_grid), int(params.i_shock)
+    if n < 3:
+        raise ValueError("profile_update: a profile has at least three zones")
+    if not 0 <= int(pin.i_trans) <= i_shock:
+        raise ValueError(f"profile_update: i_trans {pin.i_trans} outside 0..i_shock ({i_shock})")
+    if len(pin.hist_q_px) > PROFILE_MAX_HIST or len(pin.hist_q_px) != len(pin.hist_q_en):
+        raise ValueError(f"profile_update: at most {PROFILE_MAX_HIST} earlier (q_px, q_en) pairs")
+    u0, b0, g0 = f8(params.u0), f8(params.beta0), f8(params.gam0)
+    c, mp = f8(C), f8(MP)
+    F_px, F_en, P0, rho0, n0 = f8(pin.F_px_upstream), f8(pin.F_energy_upstream), f8(pin.P0), f8(pin.rho0), f8(pin.n0_aa)
+    u2, b2, g2 = f8(pin.u2), f8(pin.beta2), f8(pin.gam2)
+    rel = bool(b0 >= BETA_REL_FL)
+    arr = lambda a: np.array(a, dtype=np.float64)[:n].copy()
+    sc = np.asarray(scalars, dtype=np.float64)
+    ux, g = np.asarray(ux_tab, dtype=np.float64)[1:n + 1], np.asarray(gam_sf_tab, dtype=np.float64)[1:n + 1]
+    down = np.asarray(x_grid_cm, dtype=np.float64)[1:n + 1] >= 0
+    Ppar, Pperp, ed = arr(P_par), arr(P_perp), arr(e_dens)
+    pxx_EM, en_EM, atan_x = arr(pin.pxx_EM), arr(pin.en_EM), arr(pin.atan_x)
+    with np.errstate(all="ignore"):
+        px_esc, en_esc = sc[2] / F_px, sc[3] / F_en
+        gam_down = 1 + sc[0] / sc[1]
+        # q_esc_calcs
+        if f8(pin.r_comp) == f8(pin.r_RH):
+            q_px, q_en = f8(0.0), f8(0.0)
+        else:
+            Gf = gam_down / (gam_down - 1)
+            rho2 = ((rho0 * g0) * b0) / (g2 * b2)
+            if rel:
+                q_fac = c * np.sqrt((1 + b0) / 2)
+                e = rho0 * (c * c) + 2.5 * P0
+                Fp = ((g0 * g0) * (b0 * b0)) * e + P0
+                Fe = ((g0 * g0) * u0) * e
+                aux = (g2 * g2) * (q_fac * (b2 * b2) - u2)
+                P2 = ((q_fac * Fp - Fe) - (aux * rho2) * (c * c)) / (q_fac + Gf * aux)
+                t = g2 * b2
+                Q_px = (Fp - (t * t) * (rho2 * (c * c) + Gf * P2)) - P2
+                Q_en = Q_px * q_fac
+                q_px, q_en = Q_en / (Fe - ((g0 * u0) * rho0) * (c * c)), Q_px / Fp
+            else:
+                Fp = rho0 * (u0 * u0) + P0
+                Fe = (rho0 * ((u0 * u0) * u0)) / 2 + (2.5 * P0) * u0
+                P2 = Fp - rho2 * (u2 * u2)
+                Q_en = (Fe - ((rho0 * u0) * (u2 * u2)) / 2) - (P2 * u2) * Gf
+                q_px, q_en = Q_en / Fe, f8(0.0)
+        k = len(pin.hist_q_px) + 1
+        s_px, s_en = None, None
+        for a, b in list(zip(pin.hist_q_px, pin.hist_q_en)) + [(q_px, q_en)]:
+            s_px = f8(a) if s_px is None else s_px + f8(a)
+            s_en = f8(b) if s_en is None else s_en + f8(b)
+        q_px_avg, q_en_avg = s_px / k, s_en / k
+        pxx = np.rint(arr(pxx_flux) * 1.0e13) / 1.0e13
+        en = np.rint(arr(energy_flux) * 1.0e13) / 1.0e13
+        G = 1 + (Ppar + Pperp) / ed
+        G[ed == 1.0e-99] = 1.0e-99
+        Xi = G / (G - 1)
+        Ptot = Ppar + Pperp
+        wp = f8(pin.SMPFP)
+        Qpx = q_px_avg * pxx[0] if rel else f8(0.0)
+        Qen = q_en_avg * en[0]
+        bux = ux / c
+        steps_max, n_out = 0, 0
+        if rel:
+            gb = g * bux
+            gb2 = gb * gb
+            dens = ((g0 * b0) / (g * bux)) * n0
+            p_px = (pxx - ((gb2 * dens) * mp) * (c * c)) / (1 + gb2 * Xi)
+            p_loc = (1 - wp) * p_px + wp * Ptot
+            gbn = (((F_px - Qpx) - pxx_EM) - p_loc) / (((g0 * b0) * n0) * (mp * (c * c) + (p_loc * Xi) / dens))
+            ux_px = (gbn / np.sqrt(1 + gbn * gbn)) * c
+            K = ((F_en - Qen) - en_EM) / (c * ((dens * mp) * (c * c) + Xi * p_loc))
+            y = (-1 + np.sqrt(1 + (4 * K) * K)) / 2
+            gbn = np.copysign(np.sqrt(y), K)
+            ux_en = (gbn / np.sqrt(1 + gbn * gbn)) * c
+        else:
+            rm = n0 * mp
+            b2x = bux * bux
+            p_px = (pxx - ((rm * u0) * ux) * (1 + b2x)) / (1 + b2x * Xi)
+            p_loc = (1 - wp) * p_px + wp * Ptot
+            ux_px, ux_en = np.zeros(n), np.zeros(n)
+            for j in range(n):
+                X, pl = Xi[j], p_loc[j]
+                A = (F_px - Qpx) - pxx_EM[j]
+                B = (F_en - Qen) - en_EM[j]
+
+                def f_px(b):
+                    return ((A - ((rm * u0) * (b * c)) * (1 + b * b)) - (1 + (b * b) * X) * pl,
+                            -(((rm * u0) * c) * (1 + (3 * b) * b) + ((2 * b) * X) * pl))
+
+                def f_en(u):
+                    t = u / c
+                    t2 = t * t
+                    return ((B - ((((0.5 * rm) * u0) * u) * u) * (1 + 1.25 * t2)) - ((X * pl) * u) * (1 + t2),
+                            -(((rm * u0) * u) * (1 + 2.5 * t2) + (X * pl) * (1 + 3 * t2)))
+                x, s1, o1 = _profile_newton(f_px, (u0 / c) * 1.0e-4)
+                ux_px[j] = x * c
+                ux_en[j], s2, o2 = _profile_newton(f_en, u0 * 1.0e-4)
+                steps_max = max(steps_max, s1, s2)
+                n_out += int(o1 or o2)
+        avg_px, avg_en = f8(0.0), f8(0.0)
+        for j in range(max(0, n - 10), n):
+            avg_px = avg_px + ux_px[j]; avg_en = avg_en + ux_en[j]
+        avg_px, avg_en = avg_px / 10, avg_en / 10
+        if rel:
+            _profile_smooth(ux_px); _profile_smooth(ux_en)
+        for a, avg in ((ux_px, avg_px), (ux_en, avg_en)):
+            s = (u0 - u2) / (a[0] - avg)
+            a[:] = s * (a - avg) + u2
+            a[down] = u2
+        if not rel:
+            _profile_smooth(ux_px); _profile_smooth(ux_en)
+        mo = f8(pin.SMMOE)
+        ux_pred = (1 - mo) * ux_px + mo * ux_en
+        ux_new = ux_pred.copy()
+        it = int(pin.i_trans)
+        if it > 0:
+            last = ux_pred[n - 1]
+            s = -(ux_pred[it - 1] - last) / atan_x[it - 1]
+            ux_new[it - 1:i_shock] = (-atan_x[it - 1:i_shock]) * s + last
+        w = f8(pin.w)
+        ux_next = (ux_new + w * ux) / (1 + w)
+        shift = (ux_pred - ux) / u0
+        s = f8(0.0)
+        for j in range(n):
+            s = s + shift[j] * shift[j]
+        rms = np.sqrt(s / n)
+        px_esc = f8(1.0e-99) if 1.0e-99 > px_esc else px_esc
+        en_esc = f8(1.0e-99) if 1.0e-99 > en_esc else en_esc
+    rows = np.stack([pxx / F_px, en / F_en, G, p_px, p_loc, ux_px, ux_en, ux_pred, ux_next, shift])
+    svec = np.array([gam_down, px_esc, en_esc, q_px, q_en, q_px_avg, q_en_avg, rms], dtype=np.float64)
+    bad = int(np.count_nonzero(~np.isfinite(rows))) + int(np.count_nonzero(~np.isfinite(svec)))
+    return ProfileUpdate(rows, svec, np.array([bad, n_out, steps_max], dtype=np.int64), pin.settings())
+
+
+def profile_in(prob, it_state, sm, i_iter: int, history=None) -> ProfileIn:
+    """The `mcs_profile_in` of iteration i_iter from the quantities iter_finalize uses: the upstream fluxes of `it_state`, the
+    species sums, the weight after the increase_old_profile_weighting rule, the start of the artificial section, the
+    electromagnetic fluxes of the current profile.  history: [(q_px, q_en)] of earlier iterations, oldest first (the last three
+    count); None: none, the samples of a fixed profile stay independent."""
+    P, cfg = prob.params, prob.cfg
+    n = P.n_grid
+    n0 = np.array([s.density for s in cfg.species]); T0 = np.array([s.temperature for s in cfg.species])
+    m = np.array([s.mass for s in cfg.species])
+    w = sm.old_profile_weight
+    if sm.increase_old_profile_weighting and i_iter != 1:
+        w = max(10.0, w * (1.15 if i_iter < 6 else 1.5))
+    xs = sm.artificial_smoothing_start_rg
+    i_trans = 0
+    if xs < 0:
+        i_trans = int(np.argmax(prob.x_grid_rg > xs)) - 1
+        if not 1 <= i_trans <= P.i_shock:
+            raise ValueError(f"profile_update: the artificial section would start at zone {i_trans}, outside 1..i_shock")
+    ux = np.asarray(prob.ux, dtype=np.float64)[1:n + 1]; g = np.asarray(prob.gam_sf, dtype=np.float64)[1:n + 1]
+    B = np.asarray(prob.btot, dtype=np.float64)[1:n + 1]; th = np.asarray(prob.theta, dtype=np.float64)[1:n + 1]
+    bux = ux / C
+    gb, g2_ = g * bux, g * g
+    Bx, Bz = B * np.cos(th), B * np.sin(th)
+    pxx_EM = gb ** 2 / (8 * math.pi) * B ** 2 + g2_ / (8 * math.pi) * (Bz ** 2 - Bx ** 2)
+    en_EM = g2_ / (4 * math.pi) * bux * Bz ** 2
+    hist = list(history or [])[-PROFILE_MAX_HIST:]
+    return ProfileIn(it_state.F_px_upstream, it_state.F_energy_upstream, float(np.dot(n0, T0)) * KB, float(np.dot(n0, m)),
+                     float(sum(s.density * s.aa for s in cfg.species)), prob.r_comp, it_state.r_RH, P.u2, prob.beta2, prob.gam2,
+                     sm.SMMOE, sm.SMPFP, w, i_trans, tuple(h[0] for h in hist), tuple(h[1] for h in hist), pxx_EM, en_EM,
+                     np.arctan(np.asarray(prob.x_grid_rg, dtype=np.float64)[1:n + 1]))
+
+
+def profile_update(prob, backend, it_state, sm, i_iter: int, history=None, pressures=None) -> ProfileUpdate:
+    """The profile update of iteration i_iter from the backend's resident fluxes and running scalars and the pressures of the last
+    ion_finalize: on a HIP backend the device call (K13; the pressures are those mcs_thermo_calcs left on the device, or
+    `pressures` = (P_par, P_perp, energy_density) in their place), on a backend without it the numpy statement of the same rules
+    on the tallies read back, with `pressures` or, without them, those of a thermo_calcs of the last species.  Nothing of `prob`,
+    `it_state` or the tallies is changed."""
+    pin = profile_in(prob, it_state, sm, i_iter, history)
+    n = prob.params.n_grid
+    if hasattr(backend, "profile_update"):
+        out, diag = backend.profile_update(pin, pressures)
+        return _profile_from_words(out, diag, n, pin.settings())
+    if pressures is None:
+        pressures = backend.thermo_calcs(consumer_tables(prob, len(prob.cfg.species)))
+    L = backend.layout
+    f, _ = backend.read_tallies()
+    return profile_update_host(pin, prob.params, prob.ux, prob.gam_sf, prob.x_grid_cm, L.view(f, "pxx_flux"), L.view(f, "energy_flux"),
+                               L.view(f, "scalars"), *pressures)
+
+
 # ---- photon post-processing (SURVEY.md 8(f-4)) -------------------------------------------------------------------------
 # photon_calcs.jl:11-19: the common energy grid of the emission spectra
 PHOTON_E_MIN_MEV = 1.0e-13

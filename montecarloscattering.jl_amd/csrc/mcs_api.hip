@@ -187,6 +187,12 @@ struct mcs_ctx {
   DevBuf<double> d_tcut_base, d_tcut_out; DevBuf<unsigned int> d_tcut_rowneg; DevBuf<unsigned long long> d_tcut_diag;
   bool have_tcut = false, species_begun = false;
   int tcut_n = 0;
+  // K13: what the last mcs_profile_update left, in mcs_profile_layout, its counts, its tables (pxx_EM | en_EM | atan_x, then the caller's
+  // pressures when it passed some) and the settings of its mcs_profile_in; have_prof: a whole result since the last mcs_begin_species,
+  // tally write and profile sample.  Only that call writes them.
+  DevBuf<double> d_prof_out, d_prof_tab; DevBuf<unsigned long long> d_prof_diag;
+  bool have_prof = false;
+  mcs_profile_in prof_in{};
   DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
   // K9, per process (MCS_PHOTON_SYNCH / _IC / _PION): d_pemis the emis[n_grid][n_photon] its fold left (pemis_n: that n_photon, 0 =
   // nothing), d_pobs the [n_shells+1][n] of the last mcs_photon_observe (pobs_n: its n, 0 = nothing; pobs_shells).  Only those calls
@@ -468,6 +474,7 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
   c->have_esc = false;
   c->have_ang = false;
   c->have_tcut = false;
+  c->have_prof = false;
   c->photon_flags_clear();
   if (fold_replicas(c)) return 1;      // (the previous species' replicas, before its histograms are cleared)
   if (P.do_tcuts) {      // K12's base: the species' block of spectra_coupled as it stands now
@@ -1266,6 +1273,7 @@ int mcs_write_tallies_part(mcs_ctx* c, int64_t first, int64_t count, const doubl
   if (fold_replicas(c)) return 1;
   c->photon_flags_clear();
   c->have_ang = false;
+  c->have_prof = false;
   if (count > 0) HIPCHK(hipMemcpyAsync(c->d_T + first, host_f64, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -1275,6 +1283,7 @@ int mcs_write_tallies(mcs_ctx* c, const double* host_f64, const int64_t* host_i6
   if (fold_replicas(c)) return 1;
   c->photon_flags_clear();
   c->have_ang = false;
+  c->have_prof = false;
   if (host_f64) HIPCHK(hipMemcpyAsync(c->d_T, host_f64, (size_t)c->L.total * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (host_i64) HIPCHK(hipMemcpyAsync(c->d_I, host_i64, (size_t)mcs_i64_total(&c->P) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1764,6 +1773,64 @@ int mcs_tcut_spectra(mcs_ctx* c, const mcs_consumer_in* in, double* out, int64_t
   return 0;
 }
 
+int mcs_profile_get_layout(const mcs_params* p, mcs_profile_layout* out) {
+  if (!p || !out) return fail("mcs_profile_get_layout: null argument");
+  if (p->n_grid < 3) return fail("mcs_profile_get_layout: a profile has at least three zones");
+  const int64_t n = p->n_grid;
+  out->flux_px = 0; out->flux_en = n; out->gamma_ad = 2 * n; out->p_flux = 3 * n; out->p_used = 4 * n; out->ux_px = 5 * n; out->ux_en = 6 * n;
+  out->ux_pred = 7 * n; out->ux_next = 8 * n; out->shift = 9 * n; out->scalars = MCS_PROFILE_ROWS * n;
+  out->row_n = n; out->n_scalars = MCS_PROFILE_SCALARS; out->total = MCS_PROFILE_ROWS * n + MCS_PROFILE_SCALARS;
+  return 0;
+}
+
+int mcs_profile_update(mcs_ctx* c, const mcs_profile_in* in, const double* pressures, double* out, int64_t* diag) {
+  MCS_ENTER(c);
+  const std::string who = "mcs_profile_update";
+  if (!in || !out) return fail(who + ": null argument");
+  if (!in->pxx_EM || !in->en_EM || !in->atan_x) return fail(who + ": null table");
+  if (!c->have_grid) return fail(who + ": grid not set (mcs_set_grid)");
+  if (!c->species_begun) return fail(who + ": no species has begun (the fluxes and running scalars are those of a species' transport)");
+  const int n = c->P.n_grid;
+  if (in->i_trans < 0 || in->i_trans > c->P.i_shock || in->i_trans > n)
+    return fail(who + ": i_trans " + std::to_string(in->i_trans) + " outside 0..i_shock (" + std::to_string(c->P.i_shock) + ")");
+  if (c->P.i_shock > n) return fail(who + ": i_shock beyond the grid");
+  if (in->n_hist < 0 || in->n_hist > MCS_PROFILE_MAX_HIST)
+    return fail(who + ": " + std::to_string(in->n_hist) + " earlier (q_px, q_en) pairs; at most " + std::to_string(MCS_PROFILE_MAX_HIST));
+  if (!pressures && !c->have_cout_thermo)
+    return fail(who + ": no pressures on the context (mcs_thermo_calcs has not run since the last mcs_begin_species or products sample) and none passed");
+  mcs_profile_layout PL;
+  if (mcs_profile_get_layout(&c->P, &PL)) return 1;
+  if ((size_t)4 * n * sizeof(double) > (size_t)48 * 1024) return fail(who + ": n_grid too large for the kernel's rows (4 n_grid doubles of LDS, 48 KB)");
+  if (fold_replicas(c)) return 1;
+  c->have_prof = false;
+  if (reserve(c->d_prof_out, PL.total) || reserve(c->d_prof_tab, 6 * (long long)n) || reserve(c->d_prof_diag, 3)) return 1;
+  std::vector<double> h((size_t)(pressures ? 6 : 3) * n);
+  memcpy(h.data(), in->pxx_EM, sizeof(double) * n);
+  memcpy(h.data() + n, in->en_EM, sizeof(double) * n);
+  memcpy(h.data() + 2 * (size_t)n, in->atan_x, sizeof(double) * n);
+  if (pressures) memcpy(h.data() + 3 * (size_t)n, pressures, sizeof(double) * 3 * n);
+  HIPCHK(hipMemcpyAsync(c->d_prof_tab, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  const double* pres = c->d_prof_tab + 3 * (size_t)n;
+  if (!pressures) {
+    pres = c->d_cout + (size_t)3 * n * (c->P.num_psd_mom_bins + 2);
+  }
+  HIPCHK(mcs_launch_profile_update(&c->P, in, c->d_T + c->L.pxx_flux, c->d_T + c->L.energy_flux, c->d_T + c->L.scalars, c->tb.ux, c->tb.gsf,
+                                   c->tb.x_grid, pres, c->d_prof_tab, c->d_prof_out, c->d_prof_diag, c->stream));
+  std::vector<double> o((size_t)PL.total);
+  unsigned long long hd[3] = {0, 0, 0};
+  HIPCHK(hipMemcpyAsync(o.data(), c->d_prof_out, sizeof(double) * o.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hd, c->d_prof_diag, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  memcpy(out, o.data(), sizeof(double) * o.size());
+  if (diag) for (int k = 0; k < 3; ++k) diag[k] = (int64_t)hd[k];
+  c->prof_in = *in;
+  c->prof_in.pxx_EM = c->prof_in.en_EM = c->prof_in.atan_x = nullptr;
+  c->prof_in.n_hist = 0;
+  for (int k = 0; k < MCS_PROFILE_MAX_HIST; ++k) c->prof_in.hist_q_px[k] = c->prof_in.hist_q_en[k] = 0.0;
+  c->have_prof = true;
+  return 0;
+}
+
 int mcs_thermo_calcs(mcs_ctx* c, const mcs_consumer_in* in, double* P_par, double* P_perp, double* energy_density) {
   MCS_ENTER(c);
   if (consumers_ready(c, in, "mcs_thermo_calcs")) return 1;
@@ -1964,17 +2031,19 @@ int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
   if (fold_replicas(c)) return 1;
   *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo, {}, {}, {},
                     c->d_esc_out, c->have_esc, c->d_ang_out, c->have_ang, c->ang_n_win, {}, {},
-                    c->d_tcut_out, c->have_tcut, c->tcut_n};
+                    c->d_tcut_out, c->have_tcut, c->tcut_n, c->d_prof_out, c->have_prof, c->prof_in};
+  out->prof_in.pxx_EM = out->prof_in.en_EM = out->prof_in.atan_x = nullptr;      // (the caller's tables are not kept)
   for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) { out->ang_lo[m] = c->ang_lo[m]; out->ang_hi[m] = c->ang_hi[m]; }
   for (int p = 0; p < 3; ++p) { out->pobs[p] = c->d_pobs[p]; out->pobs_n[p] = c->pobs_n[p]; out->pobs_shells[p] = c->pobs_shells[p]; }
   return 0;
 }
-void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; c->have_ang = false; c->photon_flags_clear(); }
+void mcs_ctx_view_tallies_written(mcs_ctx* c) { c->have_c2d = false; c->have_ang = false; c->have_prof = false; c->photon_flags_clear(); }
 void mcs_ctx_view_products_taken(mcs_ctx* c) { c->have_cout_dndp = c->have_cout_thermo = false; }
 void mcs_ctx_view_photons_taken(mcs_ctx* c) { c->photon_flags_clear(); }
 void mcs_ctx_view_escape_taken(mcs_ctx* c) { c->have_esc = false; }
 void mcs_ctx_view_angles_taken(mcs_ctx* c) { c->have_ang = false; }
 void mcs_ctx_view_tcuts_taken(mcs_ctx* c) { c->have_tcut = false; }
+void mcs_ctx_view_profile_taken(mcs_ctx* c) { c->have_prof = false; }
 int mcs_ctx_view_fail(const char* msg) { return fail(msg); }
 
 }  // extern "C"

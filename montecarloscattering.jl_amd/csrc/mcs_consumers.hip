@@ -790,6 +790,230 @@ __global__ void __launch_bounds__(64) mcs_k_tcut_index(TcutArgs a) {
   }
 }
 
+// ---- K13: the shock-profile update (include/mcs.h, mcs_profile_update; iter_finalize / smooth_grid_par / new_velocity_profile) -------
+// One workgroup, no atomics.  Phase A: thread 0 the scalars and the q; then a lane per zone (striding) the rounding, Gamma, the two
+// pressures and the two roots into LDS rows.  Phase B, the order-dependent parts out of LDS: thread 0 the momentum row, the first lane of
+// the second wave the energy row (last-ten sum, monotone pass, filter, rescale).  Phase C: a lane per zone the blend, the artificial section,
+// the weighting and the shift; thread 0 the serial rms and the counts.  Every expression is the header's, operation by operation.
+#define PROF_THREADS 256
+
+struct ProfArgs {
+  mcs_profile_in in;                          // (its three table pointers are not read: tab below)
+  const double *pxx_flux, *energy_flux, *scalars;
+  const double *ux, *gsf, *xg;                // grid tables, entry 0 first
+  const double* pres;                         // P_par | P_perp | e_dens, [n] each
+  const double* tab;                          // pxx_EM | en_EM | atan_x, [n] each
+  double u0, beta0, gam0;
+  int n, i_shock;
+  double* out;                                // mcs_profile_layout
+  unsigned long long* diag;                   // [3]
+};
+
+__device__ double prof_newton_px(double A, double rmu0, double Xi, double pl, double x, int* steps, int* ran_out) {
+  const double c = MCS_C;
+  int k = 0;
+  bool done = false;
+  while (k < MCS_PROFILE_NEWTON_MAX && !done) {
+    const double xx = x * x;
+    const double f = (A - (rmu0 * (x * c)) * (1.0 + xx)) - (1.0 + xx * Xi) * pl;
+    const double df = -((rmu0 * c) * (1.0 + (3.0 * x) * x) + ((2.0 * x) * Xi) * pl);
+    const double dx = f / df;
+    x = x - dx;
+    ++k;
+    done = __builtin_fabs(dx) <= 1.0e-14 * __builtin_fabs(x);
+  }
+  if (k > *steps) *steps = k;
+  if (!done) *ran_out = 1;
+  return x;
+}
+
+__device__ double prof_newton_en(double B, double rm, double u0, double Xi, double pl, double x, int* steps, int* ran_out) {
+  const double c = MCS_C;
+  int k = 0;
+  bool done = false;
+  while (k < MCS_PROFILE_NEWTON_MAX && !done) {
+    const double t = x / c;
+    const double t2 = t * t;
+    const double f = (B - ((((0.5 * rm) * u0) * x) * x) * (1.0 + 1.25 * t2)) - ((Xi * pl) * x) * (1.0 + t2);
+    const double df = -(((rm * u0) * x) * (1.0 + 2.5 * t2) + (Xi * pl) * (1.0 + 3.0 * t2));
+    const double dx = f / df;
+    x = x - dx;
+    ++k;
+    done = __builtin_fabs(dx) <= 1.0e-14 * __builtin_fabs(x);
+  }
+  if (k > *steps) *steps = k;
+  if (!done) *ran_out = 1;
+  return x;
+}
+
+// smooth_profile! on an LDS row a[n] with scratch d[n]
+__device__ void prof_smooth(double* a, double* d, int n) {
+  for (int i = n - 1; i >= 1; --i)
+    if (a[i - 1] < a[i]) a[i - 1] = a[i];
+  for (int i = 0; i < n; ++i) d[i] = a[i];
+  d[1] = ((2.0 * a[0] + a[1]) + a[2]) / 4.0;
+  for (int i = 2; i <= n - 3; ++i) d[i] = ((a[i - 1] + a[i]) + a[i + 1]) / 3.0;
+  d[n - 2] = ((a[n - 3] + a[n - 2]) + 2.0 * a[n - 1]) / 4.0;
+  for (int i = 1; i <= n - 2; ++i) a[i] = d[i];
+}
+
+__device__ void prof_rescale(double* a, int n, double avg, double u0, double u2, const double* xg) {
+  const double s = (u0 - u2) / (a[0] - avg);
+  for (int j = 0; j < n; ++j) {
+    const double v = s * (a[j] - avg) + u2;
+    a[j] = xg[j + 1] >= 0.0 ? u2 : v;
+  }
+}
+
+__global__ void __launch_bounds__(PROF_THREADS) mcs_k_profile_update(ProfArgs a) {
+  extern __shared__ double s_prof[];          // row_px [n] | row_en [n] | d_px [n] | d_en [n]
+  __shared__ double s_sc[8];                  // the eight output scalars (shift_rms last)
+  __shared__ int s_steps[PROF_THREADS], s_out[PROF_THREADS];
+  const int n = a.n, tid = threadIdx.x;
+  const mcs_profile_in& I = a.in;
+  const double c = MCS_C, mp = MCS_MP;
+  const double u0 = a.u0, b0 = a.beta0, g0 = a.gam0, u2 = I.u2;
+  const bool rel = b0 >= 0.02;
+  double* row_px = s_prof;
+  double* row_en = s_prof + n;
+  double* o = a.out;
+  if (tid == 0) {
+    const double* sc = a.scalars;
+    const double px_esc = sc[2] / I.F_px_upstream, en_esc = sc[3] / I.F_energy_upstream;
+    const double G = 1.0 + sc[0] / sc[1];
+    double q_px = 0.0, q_en = 0.0;
+    if (!(I.r_comp == I.r_RH)) {
+      const double Gf = G / (G - 1.0);
+      const double rho0 = I.rho0, P0 = I.P0, g2 = I.gam2, b2 = I.beta2;
+      const double rho2 = ((rho0 * g0) * b0) / (g2 * b2);
+      if (rel) {
+        const double q_fac = c * mcsm::sqrt_((1.0 + b0) / 2.0);
+        const double e = rho0 * (c * c) + 2.5 * P0;
+        const double Fp = ((g0 * g0) * (b0 * b0)) * e + P0;
+        const double Fe = ((g0 * g0) * u0) * e;
+        const double aux = (g2 * g2) * (q_fac * (b2 * b2) - u2);
+        const double P2 = ((q_fac * Fp - Fe) - (aux * rho2) * (c * c)) / (q_fac + Gf * aux);
+        const double t = g2 * b2;
+        const double Qp = (Fp - (t * t) * (rho2 * (c * c) + Gf * P2)) - P2;
+        const double Qe = Qp * q_fac;
+        q_px = Qe / (Fe - ((g0 * u0) * rho0) * (c * c));
+        q_en = Qp / Fp;
+      } else {
+        const double Fp = rho0 * (u0 * u0) + P0;
+        const double Fe = (rho0 * ((u0 * u0) * u0)) / 2.0 + (2.5 * P0) * u0;
+        const double P2 = Fp - rho2 * (u2 * u2);
+        const double Qe = (Fe - ((rho0 * u0) * (u2 * u2)) / 2.0) - (P2 * u2) * Gf;
+        q_px = Qe / Fe;
+        q_en = 0.0;
+      }
+    }
+    double s_px = q_px, s_en = q_en;
+    if (I.n_hist > 0) {
+      s_px = I.hist_q_px[0]; s_en = I.hist_q_en[0];
+      for (int k = 1; k < I.n_hist; ++k) { s_px = s_px + I.hist_q_px[k]; s_en = s_en + I.hist_q_en[k]; }
+      s_px = s_px + q_px; s_en = s_en + q_en;
+    }
+    const double kk = (double)(I.n_hist + 1);
+    s_sc[0] = G;
+    s_sc[1] = 1.0e-99 > px_esc ? 1.0e-99 : px_esc;
+    s_sc[2] = 1.0e-99 > en_esc ? 1.0e-99 : en_esc;
+    s_sc[3] = q_px; s_sc[4] = q_en;
+    s_sc[5] = s_px / kk; s_sc[6] = s_en / kk;
+  }
+  __syncthreads();
+  // ---- phase A
+  const double pxx0 = __builtin_rint(a.pxx_flux[0] * 1.0e13) / 1.0e13, en0 = __builtin_rint(a.energy_flux[0] * 1.0e13) / 1.0e13;
+  const double Qpx = rel ? s_sc[5] * pxx0 : 0.0;
+  const double Qen = s_sc[6] * en0;
+  int steps = 0, ran_out = 0;
+  for (int j = tid; j < n; j += PROF_THREADS) {
+    const double pxx = __builtin_rint(a.pxx_flux[j] * 1.0e13) / 1.0e13, en = __builtin_rint(a.energy_flux[j] * 1.0e13) / 1.0e13;
+    const double Ptot = a.pres[j] + a.pres[n + j], ed = a.pres[2 * n + j];
+    double G = 1.0 + Ptot / ed;
+    if (ed == 1.0e-99) G = 1.0e-99;
+    const double Xi = G / (G - 1.0);
+    const double u = a.ux[j + 1], g = a.gsf[j + 1];
+    const double b = u / c;
+    const double pxx_EM = a.tab[j], en_EM = a.tab[n + j];
+    double p_px, p_loc, v_px, v_en;
+    if (rel) {
+      const double gb = g * b;
+      const double gb2 = gb * gb;
+      const double dens = ((g0 * b0) / (g * b)) * I.n0_aa;
+      p_px = (pxx - ((gb2 * dens) * mp) * (c * c)) / (1.0 + gb2 * Xi);
+      p_loc = (1.0 - I.SMPFP) * p_px + I.SMPFP * Ptot;
+      double y = (((I.F_px_upstream - Qpx) - pxx_EM) - p_loc) / (((g0 * b0) * I.n0_aa) * (mp * (c * c) + (p_loc * Xi) / dens));
+      v_px = (y / mcsm::sqrt_(1.0 + y * y)) * c;
+      const double K = ((I.F_energy_upstream - Qen) - en_EM) / (c * ((dens * mp) * (c * c) + Xi * p_loc));
+      const double z = (-1.0 + mcsm::sqrt_(1.0 + (4.0 * K) * K)) / 2.0;
+      y = __builtin_copysign(mcsm::sqrt_(z), K);
+      v_en = (y / mcsm::sqrt_(1.0 + y * y)) * c;
+    } else {
+      const double rm = I.n0_aa * mp;
+      const double bb = b * b;
+      p_px = (pxx - ((rm * u0) * u) * (1.0 + bb)) / (1.0 + bb * Xi);
+      p_loc = (1.0 - I.SMPFP) * p_px + I.SMPFP * Ptot;
+      const double A = (I.F_px_upstream - Qpx) - pxx_EM;
+      const double B = (I.F_energy_upstream - Qen) - en_EM;
+      int zone_out = 0;
+      v_px = prof_newton_px(A, rm * u0, Xi, p_loc, (u0 / c) * 1.0e-4, &steps, &zone_out) * c;
+      v_en = prof_newton_en(B, rm, u0, Xi, p_loc, u0 * 1.0e-4, &steps, &zone_out);
+      ran_out += zone_out;
+    }
+    o[j] = pxx / I.F_px_upstream;
+    o[n + j] = en / I.F_energy_upstream;
+    o[2 * n + j] = G;
+    o[3 * n + j] = p_px;
+    o[4 * n + j] = p_loc;
+    row_px[j] = v_px;
+    row_en[j] = v_en;
+  }
+  s_steps[tid] = steps; s_out[tid] = ran_out;      // (ran_out: the lane's zones in which either iteration ran out of steps)
+  __syncthreads();
+  // ---- phase B: thread 0 the momentum row, the second wave's first lane the energy row
+  if (tid == 0 || tid == 64) {
+    double* row = tid == 0 ? row_px : row_en;
+    double* d = s_prof + (tid == 0 ? 2 : 3) * n;
+    double avg = 0.0;
+    for (int j = n > 10 ? n - 10 : 0; j < n; ++j) avg = avg + row[j];
+    avg = avg / 10.0;
+    if (rel) { prof_smooth(row, d, n); prof_rescale(row, n, avg, u0, u2, a.xg); }
+    else { prof_rescale(row, n, avg, u0, u2, a.xg); prof_smooth(row, d, n); }
+  }
+  __syncthreads();
+  // ---- phase C
+  const int it = I.i_trans;
+  const double last = (1.0 - I.SMMOE) * row_px[n - 1] + I.SMMOE * row_en[n - 1];
+  double s_art = 0.0;
+  if (it > 0) {
+    const double at = (1.0 - I.SMMOE) * row_px[it - 1] + I.SMMOE * row_en[it - 1];
+    s_art = -(at - last) / a.tab[2 * n + it - 1];
+  }
+  for (int j = tid; j < n; j += PROF_THREADS) {
+    const double u = a.ux[j + 1];
+    const double pred = (1.0 - I.SMMOE) * row_px[j] + I.SMMOE * row_en[j];
+    double v = pred;
+    if (it > 0 && j >= it - 1 && j <= a.i_shock - 1) v = (-a.tab[2 * n + j]) * s_art + last;
+    o[5 * n + j] = row_px[j];
+    o[6 * n + j] = row_en[j];
+    o[7 * n + j] = pred;
+    o[8 * n + j] = (v + I.w * u) / (1.0 + I.w);
+    o[9 * n + j] = (pred - u) / u0;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double S = 0.0;
+    for (int j = 0; j < n; ++j) { const double sh = o[9 * n + j]; S = S + sh * sh; }
+    s_sc[7] = mcsm::sqrt_(S / (double)n);
+    unsigned long long bad = 0ull, outs = 0ull;
+    int smax = 0;
+    for (int k = 0; k < 8; ++k) { o[10 * n + k] = s_sc[k]; if (!__builtin_isfinite(s_sc[k])) ++bad; }
+    for (long long k = 0; k < 10ll * n; ++k) if (!__builtin_isfinite(o[k])) ++bad;
+    for (int k = 0; k < PROF_THREADS; ++k) { outs += (unsigned long long)s_out[k]; if (s_steps[k] > smax) smax = s_steps[k]; }
+    a.diag[0] = bad; a.diag[1] = outs; a.diag[2] = (unsigned long long)smax;
+  }
+}
+
 }  // namespace
 
 // Host-callable launchers (pointers are device pointers; tables were uploaded by the caller)
@@ -869,6 +1093,21 @@ extern "C" hipError_t mcs_launch_tcut_spectra(const mcs_params* P, const double*
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(mcs_k_tcut_index, dim3(1), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+// tab: pxx_EM | en_EM | atan_x; pres: P_par | P_perp | e_dens; the LDS rows take 4 n_grid doubles (the caller has checked that they fit)
+extern "C" hipError_t mcs_launch_profile_update(const mcs_params* P, const mcs_profile_in* in, const double* pxx_flux, const double* energy_flux,
+                                                const double* scalars, const double* ux, const double* gam_sf, const double* x_grid,
+                                                const double* pres, const double* tab, double* out, unsigned long long* diag, hipStream_t st) {
+  ProfArgs a{};
+  a.in = *in;
+  a.in.pxx_EM = a.in.en_EM = a.in.atan_x = nullptr;
+  a.pxx_flux = pxx_flux; a.energy_flux = energy_flux; a.scalars = scalars;
+  a.ux = ux; a.gsf = gam_sf; a.xg = x_grid; a.pres = pres; a.tab = tab;
+  a.u0 = P->u0; a.beta0 = P->beta0; a.gam0 = P->gam0; a.n = P->n_grid; a.i_shock = P->i_shock;
+  a.out = out; a.diag = diag;
+  hipLaunchKernelGGL(mcs_k_profile_update, dim3(1), dim3(PROF_THREADS), sizeof(double) * 4 * (size_t)P->n_grid, st, a);
   return hipGetLastError();
 }
 

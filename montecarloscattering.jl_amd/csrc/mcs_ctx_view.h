@@ -36,6 +36,12 @@ struct McsCtxView {
   const double* tcut_out;
   bool have_tcut;
   int tcut_n;
+  // what the last mcs_profile_update left on the device, in mcs_profile_layout (null before the first call), whether it is a whole result
+  // since the last mcs_begin_species / tally write / profile sample, and the settings of that call's mcs_profile_in (F_px_upstream ..
+  // i_trans; no history, null tables)
+  const double* prof_out;
+  bool have_prof;
+  mcs_profile_in prof_in;
 };
 
 extern "C" {
@@ -56,6 +62,8 @@ void mcs_ctx_view_escape_taken(mcs_ctx* ctx);
 void mcs_ctx_view_angles_taken(mcs_ctx* ctx);
 // A tcuts sample has been queued from ctx's mcs_tcut_spectra result: that call has to run again before the next.
 void mcs_ctx_view_tcuts_taken(mcs_ctx* ctx);
+// A profile sample has been queued from ctx's mcs_profile_update result: that call has to run again before the next.
+void mcs_ctx_view_profile_taken(mcs_ctx* ctx);
 // Sets the message of the calling thread's last error (what the ABI's error call returns); returns 1.
 int mcs_ctx_view_fail(const char* msg);
 }

@@ -13,7 +13,7 @@
 // last kernel that folds a range's partials in index order.  No atomics: the same state gives the same bits.
 // The comparison of two slots (mcs_ens_compare) is the same walk over the (mean, M2) pairs of both with a record of its own: the
 // four sweep kernels share one routine, walk, for which words a thread sees and in which order.
-// Host side: every slot of every kind -- species, iteration, products, photons, source, escape, angles, tcuts -- is one Slot (count, mean, M2); decode reads
+// Host side: every slot of every kind -- species, iteration, products, photons, source, escape, angles, tcuts, profile -- is one Slot (count, mean, M2); decode reads
 // a slot number's bits, slot_ref finds its Slot, reserve allocates it, merge_slot merges it, and plan_ranges checks the ranges of a
 // summary or comparison and lays out their blocks in one pass.
 // A context is seen through mcs_ctx_view.h; its stream carries the work, an event of the accumulator orders successive operations
@@ -26,6 +26,7 @@
 #include "../../include/mcs_math.h"
 
 #include <climits>
+#include <cstddef>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -683,16 +684,18 @@ constexpr int PHOTONS_ALL = 1 << 28;       // MCS_ENS_PHOTONS_ALL
 constexpr int ESCAPE_BIT = 1 << 27;        // MCS_ENS_ESCAPE
 constexpr int ANGLES_BIT = 1 << 26;        // MCS_ENS_ANGLES
 constexpr int TCUTS_BIT = 1 << 25;         // MCS_ENS_TCUTS
+constexpr int PROFILE_SLOT = 1 << 24;      // MCS_ENS_PROFILE
 
-// The eight kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
-// to (s; not yet held against the accumulator's species slots, slot_ref does that; -1 for the iteration and the source slot).
+// The nine kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
+// to (s; not yet held against the accumulator's species slots, slot_ref does that; -1 for the iteration, the source and the profile slot).
 // A negative number has every high bit set: it is no companion slot, and is refused as a species slot outside the range.
 // The source slot has the photons slots' vector and layout rules; it is a kind of its own in a comparison.
-enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, ANGLES, TCUTS, N_KINDS };
-const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape", "angles", "tcuts"};
+enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, ANGLES, TCUTS, PROFILE, N_KINDS };
+const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape", "angles", "tcuts", "profile"};
 struct SlotId { Kind kind; int s; };
 SlotId decode(int slot, int n_slots) {
   if (slot == PHOTONS_ALL) return SlotId{SOURCE, -1};
+  if (slot == PROFILE_SLOT) return SlotId{PROFILE, -1};
   if (slot >= 0 && (slot & PRODUCTS_BIT) != 0) return SlotId{PRODUCTS, slot ^ PRODUCTS_BIT};
   if (slot >= 0 && (slot & PHOTONS_BIT) != 0) return SlotId{PHOTONS, slot ^ PHOTONS_BIT};
   if (slot >= 0 && (slot & ESCAPE_BIT) != 0) return SlotId{ESCAPE, slot ^ ESCAPE_BIT};
@@ -752,6 +755,12 @@ struct mcs_ens {
   mcs_ens_tcuts_layout TL{};
   int tc_n = 0;
   std::vector<Slot> tcuts;
+  // the profile slot MCS_ENS_PROFILE (include/mcs.h, "profile sample"): FL.total doubles per vector; prof_set, the settings of the first
+  // profile sample's mcs_profile_in (F_px_upstream .. i_trans), is fixed from then on; prof_taken: there is one
+  mcs_ens_profile_layout FL{};
+  mcs_profile_in prof_set{};
+  bool prof_taken = false;
+  Slot profile;
   // the photons slots, likewise (include/mcs.h, "photons sample"): HL.total doubles per vector; no layout while ph_shells is 0
   mcs_ens_photons_layout HL{};
   int ph_shells = 0, ph_n[3] = {0, 0, 0}, ph_start[3] = {0, 0, 0}, ph_npts = 0;
@@ -766,15 +775,16 @@ struct mcs_ens {
   bool has_window() const { return !x_log_h.empty(); }
   bool has_angle_windows() const { return ang_n_win > 0; }
   bool has_tcuts() const { return tc_n > 0; }
+  bool has_profile() const { return prof_taken; }
   // the one way from a (checked) slot number to its record, and the length of the vectors of a kind
   Slot& at(SlotId id) {
     return id.kind == SOURCE ? source : id.kind == PHOTONS ? photons[(size_t)id.s] : id.kind == PRODUCTS ? products[(size_t)id.s]
            : id.kind == ESCAPE ? escape[(size_t)id.s] : id.kind == ANGLES ? angles[(size_t)id.s]
-           : id.kind == TCUTS ? tcuts[(size_t)id.s]
+           : id.kind == TCUTS ? tcuts[(size_t)id.s] : id.kind == PROFILE ? profile
            : main[(size_t)(id.kind == ITERATION ? n_slots - 1 : id.s)];
   }
   long long len(Kind k) const {
-    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ANGLES ? (has_angle_windows() ? AL.total : 0) : k == TCUTS ? (has_tcuts() ? TL.total : 0) : k == ITERATION ? E.it_total : E.sp_total;
+    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ANGLES ? (has_angle_windows() ? AL.total : 0) : k == TCUTS ? (has_tcuts() ? TL.total : 0) : k == PROFILE ? (has_profile() ? FL.total : 0) : k == ITERATION ? E.it_total : E.sp_total;
   }
   // every slot number the accumulator has
   std::vector<int> slot_numbers() const {
@@ -782,6 +792,7 @@ struct mcs_ens {
     for (int s = 0; s < n_slots; ++s) all.push_back(s);
     for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); all.push_back(s | ESCAPE_BIT); all.push_back(s | ANGLES_BIT); all.push_back(s | TCUTS_BIT); }
     all.push_back(PHOTONS_ALL);
+    all.push_back(PROFILE_SLOT);
     return all;
   }
 };
@@ -860,6 +871,15 @@ bool tcuts_differ(const mcs_ens* a, const mcs_ens* b) { return a->has_tcuts() &&
 void tcuts_take(mcs_ens* e, int n_tcuts) {
   e->tc_n = n_tcuts;
   mcs_tcut_get_layout(&e->P, n_tcuts, &e->TL);
+}
+
+// both have taken profile samples, and the settings of their mcs_profile_in (the bytes up to n_hist) differ in some bit
+bool profile_settings_differ(const mcs_profile_in& a, const mcs_profile_in& b) { return std::memcmp(&a, &b, offsetof(mcs_profile_in, n_hist)) != 0; }
+bool profiles_differ(const mcs_ens* a, const mcs_ens* b) { return a->has_profile() && b->has_profile() && profile_settings_differ(a->prof_set, b->prof_set); }
+void profile_take(mcs_ens* e, const mcs_profile_in& in) {
+  e->prof_set = in;
+  e->prof_taken = true;
+  mcs_profile_get_layout(&e->P, &e->FL);
 }
 
 // both have a photon layout, and the two differ
@@ -1242,6 +1262,33 @@ int mcs_ens_add_tcuts(mcs_ens* e, mcs_ctx* src, int slot) {
   return leave(e, v.stream);
 }
 
+int mcs_ens_profile_get_layout(const mcs_params* p, mcs_ens_profile_layout* out) {
+  if (!p || !out) return fail("mcs_ens_profile_get_layout: null argument");
+  return mcs_profile_get_layout(p, out);
+}
+
+int mcs_ens_add_profile(mcs_ens* e, mcs_ctx* src) {
+  const std::string who = "mcs_ens_add_profile";
+  if (!e || !src) return fail(who + ": null argument");
+  McsCtxView v;
+  if (view_of(e, src, who.c_str(), &v)) return 1;
+  if (!v.have_prof || !v.prof_out)
+    return fail(who + ": the context needs an mcs_profile_update since its last mcs_begin_species, tally write and profile sample");
+  if (e->has_profile() && profile_settings_differ(e->prof_set, v.prof_in))
+    return fail(who + ": the settings of the context's mcs_profile_update differ from those of the accumulator's profile samples");
+  if (enter(e, v.stream)) return 1;
+  if (!e->has_profile()) profile_take(e, v.prof_in);
+  Slot& sl = e->profile;
+  if (reserve(sl, e->FL.total, who, v.stream)) return 1;
+  // the sample is the call's result as it lies on the device
+  hipLaunchKernelGGL(mcs_k_ens_add_vector, dim3(grid_for(e->FL.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), v.prof_out,
+                     (long long)e->FL.total, (double)(sl.n + 1));
+  ENSCHK(hipGetLastError());
+  sl.n += 1;
+  mcs_ctx_view_profile_taken(src);
+  return leave(e, v.stream);
+}
+
 int mcs_ens_photons_get_layout(int n_shells, int n_synch, int n_ic, int n_pion, int n_pts, mcs_ens_photons_layout* out) {
   if (!out) return fail("mcs_ens_photons_get_layout: null argument");
   const int n[3] = {n_synch, n_ic, n_pion}, start[3] = {0, 0, 0};
@@ -1341,6 +1388,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (photon_layouts_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' photon layouts differ");
   if (angle_windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' angle windows differ");
   if (tcuts_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' tcuts samples differ in n_tcuts");
+  if (profiles_differ(dst, src)) return fail("mcs_ens_merge: the settings of the accumulators' profile samples differ");
   McsCtxView v;
   if (mcs_ctx_view_get(dst->home, &v)) return 1;
   const std::vector<int> slots = dst->slot_numbers();
@@ -1364,6 +1412,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (any_photons && !dst->has_photon_layout()) photon_layout_take(dst, src->ph_shells, src->ph_n, src->ph_start, src->ph_npts);
   if (any[ANGLES] && !dst->has_angle_windows()) angle_windows_take(dst, src->ang_n_win, src->ang_lo, src->ang_hi);
   if (any[TCUTS] && !dst->has_tcuts()) tcuts_take(dst, src->tc_n);
+  if (any[PROFILE] && !dst->has_profile()) profile_take(dst, src->prof_set);
   // (the source slot merges like a photons slot; what is pending on either side stays where it is)
   for (int slot : slots) {
     const SlotId id = decode(slot, dst->n_slots);
@@ -1457,6 +1506,12 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
         if (tcuts_differ(ens[j], ens[k])) return fail(who + ": the accumulators' tcuts samples differ in n_tcuts");
       if (ens[k]->len(sr.kind) > len) len = ens[k]->len(sr.kind);      // (an accumulator that took no tcuts sample has no length)
     }
+  if (sr.kind == PROFILE)
+    for (int k = 1; k < n_ens; ++k) {
+      for (int j = 0; j < k; ++j)
+        if (profiles_differ(ens[j], ens[k])) return fail(who + ": the settings of the accumulators' profile samples differ");
+      if (ens[k]->len(sr.kind) > len) len = ens[k]->len(sr.kind);      // (an accumulator that took no profile sample has no length)
+    }
   if (has_photon_vector(sr.kind))
     for (int k = 1; k < n_ens; ++k) {
       for (int j = 0; j < k; ++j)
@@ -1510,6 +1565,7 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   const Slot &sa = *ra.slot, &sb = *rb.slot;
   const long long len = ra.len;
   if (ra.kind == TCUTS && rb.kind == TCUTS && tcuts_differ(a, b)) return fail(who + ": the accumulators' tcuts samples differ in n_tcuts");
+  if (ra.kind == PROFILE && rb.kind == PROFILE && profiles_differ(a, b)) return fail(who + ": the settings of the accumulators' profile samples differ");
   if (ra.kind != rb.kind || len != rb.len) return fail(who + ": the two slots differ in kind or length");
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges == 0) return 0;
@@ -1524,6 +1580,9 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   }
   if (ra.kind == TCUTS) {
     if (sa.n == 0 || sb.n == 0) return fail(who + ": a tcuts slot has never taken a sample");
+  }
+  if (ra.kind == PROFILE) {
+    if (sa.n == 0 || sb.n == 0) return fail(who + ": a profile slot has never taken a sample");
   }
   if (has_photon_vector(ra.kind)) {
     if (sa.n == 0 || sb.n == 0) return fail(who + ": a photons slot has never taken a sample");

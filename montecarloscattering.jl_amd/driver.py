@@ -84,6 +84,7 @@ class RunResult:
     photons: object = None        # [consumers.ObservedSpectra], one per species, of the last iteration (run(photons=...)); None without
     escape: object = None         # [(i_iter, i_ion, consumers.EscapeSpectra)] of every species end (run(escape=True)); None without
     tcuts: object = None          # [(i_iter, i_ion, consumers.TcutSpectra)] of every species end (run(tcuts=True)); None without
+    profile: object = None        # [(i_iter, consumers.ProfileUpdate)] of every iteration's finalize step (run(profile=True)); None without
     angles: object = None         # [(i_iter, i_ion, consumers.AngleDistributions)] of every species end (run(angles=[...])); None without
 
 
@@ -683,6 +684,22 @@ def _species_tcuts(rs, be, i_iter, i_ion):
         rs.ensemble.add_tcuts(be, i_ion - 1, spec)
 
 
+def _iteration_profile(rs, be, it_state, sm, i_iter, ion_fin):
+    """The profile update of iteration i_iter (run(profile=True); K13 on a HIP backend) from the tallies and pressures of the last
+    species on the primary context, before iter_finalize touches `prob`.  With smooth_shocks the q of up to three earlier iterations
+    -- what iter_finalize averages with this iteration's -- go with it; with a fixed profile none.  With an ensemble, one profile
+    sample."""
+    history = None
+    if sm.smooth_shocks:
+        n_avg = min(i_iter, 4)
+        history = list(zip(it_state.q_esc_cal_px[i_iter - n_avg:i_iter - 1], it_state.q_esc_cal_energy[i_iter - n_avg:i_iter - 1]))
+    pressures = None if hasattr(be, "profile_update") else (ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
+    upd = consumers.profile_update(rs.prob, be, it_state, sm, i_iter, history=history, pressures=pressures)
+    rs.profile.append((i_iter, upd))
+    if rs.ensemble is not None:
+        rs.ensemble.add_profile(be, upd)
+
+
 def _iteration_species(rs, i_iter, before_pcut):
     """The species of iteration i_iter in order: its transport (here, or with secondaries on the pool's threads as the
     scheduler places it), its merge into the primary if it ran on a secondary, its species end."""
@@ -729,7 +746,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
         long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None,
         ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1, photons=None,
-        escape: bool = False, angles=None, tcuts: bool = False) -> RunResult:
+        escape: bool = False, angles=None, tcuts: bool = False, profile: bool = False) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -833,6 +850,14 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     sample it.  RunResult.tcuts holds [(i_iter, i_ion, TcutSpectra)].  With ensemble, one TCUTS sample per species and iteration goes
     into Ensemble.tcuts_slot(i_ion - 1) (ensemble.py, "Tcuts").  Refused: tcuts without finalize, on a problem without time cuts,
     together with tcut_print, with a communicator, a trigger on a tcuts slot without tcuts.  False: no new call is made.
+    profile: in every iteration's finalize step, on the primary context, after the last species' ion_finalize and before the products
+    sample, consumers.profile_update: the shock profile that smooth_grid_par WOULD write from this iteration's fluxes and pressures,
+    with its intermediate rows (K13 on a HIP backend; on another backend the numpy statement of the same rules).  Nothing is applied:
+    the host iter_finalize and what it writes into `prob` are unchanged.  RunResult.profile holds [(i_iter, ProfileUpdate)].  With
+    smoothing= and smooth_shocks it is handed the q of the earlier iterations that iter_finalize averages; in a run with a fixed
+    profile none, so that its samples stay independent, and with ensemble one PROFILE sample per iteration goes into
+    Ensemble.profile_slot (ensemble.py, "Profile"; ensemble.profile_consistency reads it).  Refused: profile without finalize, with
+    a communicator, a trigger on the profile slot without profile.  False: no new call is made.
     """
     import torch
     comm = comm or Comm(False)
@@ -862,7 +887,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         verbose=verbose, gather_max=gather_max, skew_max=skew_max, fused_pcuts=fused_pcuts, fused_chunk=fused_chunk,
         long_draws=long_draws, long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
         photons=photons, photon_spectra=[None] * len(cfg.species), last_ion_fin=None, do_escape=bool(escape), escape=[],
-        angle_windows=None, angles=[], do_tcuts=bool(tcuts), tcuts=[], tcut_base={},
+        angle_windows=None, angles=[], do_tcuts=bool(tcuts), tcuts=[], tcut_base={}, profile=[],
         G_f=None, G_i=None, G_pool=None, stats=[], per_species=[], local_steps=[], empty_launches=[], species_spans=[], iter_finals=[])
     # the step counters are never reset: this rank's running total.  A context that has run before (run() called again with
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
@@ -910,6 +935,13 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             ensemble.expect_tcuts(len(prob.tcuts))
     elif any(ens.Ensemble.is_tcuts(t.slot) for t in triggers):
         raise ValueError("triggers: a trigger on a tcuts slot needs tcuts=True (no sample would ever arrive)")
+    if profile:
+        if not (finalize or smoothing is not None):
+            raise ValueError("profile: needs finalize=True (the profile update belongs to the iteration's finalize step)")
+        if comm.enabled:
+            raise ValueError("profile: one process without a communicator (the multi-rank case is left out)")
+    elif any(ens.Ensemble.is_profile(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on the profile slot needs profile=True (no sample would ever arrive)")
     if triggers:
         _check_trigger_args(ensemble is not None, "ensemble=", min_iterations, check_every)
         for t in triggers:
@@ -967,6 +999,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             if rs.is_root:
                 # (with photons= the last species end has made it already)
                 ion_fin = rs.last_ion_fin if photons is not None else consumers.ion_finalize(prob, backend, len(cfg.species))
+                if profile:      # (before the products sample, which takes the pressures ion_finalize left on the device)
+                    _iteration_profile(rs, backend, it_state, sm, i_iter, ion_fin)
                 if ensemble is not None:
                     _add_products(ensemble, prob, backend, ion_fin)
                 fin = itf.iter_finalize(prob, it_state, sm, i_iter, rs.G_f, L, ion_fin.P_psd_par, ion_fin.P_psd_perp, ion_fin.energy_density_psd)
@@ -1018,7 +1052,8 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                      rs.local_steps, rs.empty_launches, rs.species_spans, options, ensemble,
                      Convergence(checks, stopped_at, satisfied) if triggers else None,
                      list(rs.photon_spectra) if photons is not None else None, rs.escape if escape else None,
-                     tcuts=rs.tcuts if tcuts else None, angles=rs.angles if angles is not None else None)
+                     tcuts=rs.tcuts if tcuts else None, profile=rs.profile if profile else None,
+                     angles=rs.angles if angles is not None else None)
 
 
 # The never-reset tallies of the reference (esc_flux, esc_*_eff, spectra_coupled, spectra_sf / _pf accumulate over
@@ -1031,7 +1066,7 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
                    on_iteration_end: Optional[Callable] = None, first_iter: int = 1,
                    blocks_per_launch: Optional[int] = None, ensemble: bool = False, triggers: Optional[list] = None,
                    min_iterations: int = 2, check_every: int = 1, photons=None, escape: bool = False, angles=None,
-                   tcuts: bool = False) -> RunResult:
+                   tcuts: bool = False, profile: bool = False) -> RunResult:
     """The iterations of a run with a FIXED shock profile (smooth-shocks = false -- the stock mc_in.toml, BASELINE
     config[1]) are independent Monte-Carlo realisations: nothing an iteration computes enters the next one's transport
     (src/main_loops.jl:52-121: every tally the transport reads is reset at the top; the RNG keys carry i_iter).  Their
@@ -1079,7 +1114,10 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     no spectra are made.
     escape: refused -- the escape spectra of run(escape=True) are left out of the overlapped path.
     angles: refused likewise -- the pitch-angle distributions of run(angles=[...]) are left out of the overlapped path.
-    tcuts: refused likewise -- the time-cut spectra of run(tcuts=True) are left out of the overlapped path."""
+    tcuts: refused likewise -- the time-cut spectra of run(tcuts=True) are left out of the overlapped path.
+    profile: refused likewise -- the profile update of run(profile=True) is left out of the overlapped path."""
+    if profile or any(ens.Ensemble.is_profile(t.slot) for t in (triggers or [])):
+        raise ValueError("profile: the overlapped run leaves the profile update out; use run(finalize=True, profile=True)")
     if tcuts or any(ens.Ensemble.is_tcuts(t.slot) for t in (triggers or [])):
         raise ValueError("tcuts: the overlapped run leaves the time-cut spectra out; use run(finalize=True, tcuts=True)")
     if angles is not None or any(ens.Ensemble.is_angles(t.slot) for t in (triggers or [])):

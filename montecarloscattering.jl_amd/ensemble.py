@@ -93,6 +93,16 @@ cut.  A cut that no particle reached is a dead row: its mean_log_p and quantiles
 non-finite, a summary counts it in n_nonfinite and a trigger over it is never met -- triggers belong on cuts below age_max (the last
 cut lies above 10 age_max and is always dead).
 
+Profile (include/mcs.h, "profile sample"): the shock profile that smooth_grid_par WOULD write from an iteration's fluxes and pressures,
+consumers.profile_update (K13), sampled once per iteration by driver.run(finalize=True, profile=True, ensemble=...) of a run with a
+FIXED profile: the mean and standard error of that prediction say how far the current profile is from self-consistency.  One slot
+per ensemble, `Ensemble.profile_slot`, whose vectors exist from its first sample on.  The ensemble keeps the settings of its first
+sample's ProfileIn (upstream fluxes, species sums, compression ratios, SMMOE, SMPFP, the old-profile weight, i_trans); a later sample,
+merge, summarize_merged or compare whose settings differ in any bit is refused.  Its parts are ten rows [n_grid] -- flux_px, flux_en,
+gamma_ad, p_flux, p_used, ux_px, ux_en, ux_pred, ux_next, shift -- of which zones=(a, b) selects zones, and scalars [8] (gamma_down,
+px_esc_up, en_esc_up, q_px, q_en, q_px_avg, q_en_avg, shift_rms).  `profile_consistency(ens)` turns mean and M2 of `shift` into
+per-zone z-scores and their chi-square over the upstream zones.
+
 Photons (include/mcs.h, "photons sample"): the photon spectra at Earth per photon shell, consumers.observed_spectra.  A shell spectrum is
 a sum over zones, slices in cos(theta) and processes, so its variance does not follow from per-cell variances either: every species
 slot s has a second companion, `Ensemble.photons_slot(s)`, sampled once per iteration (`add_photons`) and allocated at its first
@@ -198,6 +208,12 @@ TCUTS_NAMES = ("spectrum", "weight", "number", "mean_log_p", "quantile", "index"
 ZONE_PARTS = ZONE_PARTS + tuple(n for n in TCUTS_NAMES if n not in ZONE_PARTS)
 BIN_PARTS = BIN_PARTS + ("spectrum", "quantile")
 TCUTS_BIT = capi.ENS_TCUTS_BIT            # tcuts slot of species slot s: s | TCUTS_BIT (MCS_ENS_TCUTS)
+# the parts of the profile slot, in the order of mcs_profile_layout: ten rows over the zones (zones=), then the scalars
+PROFILE_ROW_NAMES = ("flux_px", "flux_en", "gamma_ad", "p_flux", "p_used", "ux_px", "ux_en", "ux_pred", "ux_next", "shift")
+PROFILE_SCALAR_NAMES = ("gamma_down", "px_esc_up", "en_esc_up", "q_px", "q_en", "q_px_avg", "q_en_avg", "shift_rms")
+PROFILE_NAMES = PROFILE_ROW_NAMES + ("scalars",)
+ZONE_PARTS = ZONE_PARTS + tuple(n for n in PROFILE_ROW_NAMES if n not in ZONE_PARTS)
+PROFILE_SLOT = capi.ENS_PROFILE           # the profile slot, one per ensemble (MCS_ENS_PROFILE)
 
 
 class EnsLayout:
@@ -269,6 +285,19 @@ class EnsLayout:
         t = self.tcuts(n_tcuts)
         nt, nm = t["spectrum"][1]
         return dict({name: off for name, (off, _) in t.items()}, row_n=nm, n_tcuts=nt, total=nt * (nm + 6) + 3)
+
+    def profile(self) -> Dict[str, Tuple[int, tuple]]:
+        """The profile sample: mirror of `mcs_ens_profile_get_layout`."""
+        n = self.tally.shapes["pxx_flux"][0]
+        t = {name: (k * n, (n,)) for k, name in enumerate(PROFILE_ROW_NAMES)}
+        t["scalars"] = (len(PROFILE_ROW_NAMES) * n, (len(PROFILE_SCALAR_NAMES),))
+        return t
+
+    def profile_fields(self) -> Dict[str, int]:
+        t = self.profile()
+        n = t["shift"][1][0]
+        return dict({name: off for name, (off, _) in t.items()}, row_n=n, n_scalars=len(PROFILE_SCALAR_NAMES),
+                    total=len(PROFILE_ROW_NAMES) * n + len(PROFILE_SCALAR_NAMES))
 
     def species_sample(self, f: np.ndarray, i: np.ndarray) -> np.ndarray:
         """The species sample of the tally buffers (f, i).  The marginals are serial sums in ascending index order, one index
@@ -348,11 +377,11 @@ def stats_over(samples):
 def _check_part(name: str, zones, bins=None):
     """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis, a bins
     window is a pair, comes with a single zone and the part has a bins axis."""
-    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES + ANGLES_NAMES + TCUTS_NAMES:
+    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES + ANGLES_NAMES + TCUTS_NAMES + PROFILE_NAMES:
         raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}; "
                          f"a products slot: {', '.join(PRODUCT_NAMES)}; a photons slot: {', '.join(PHOTON_NAMES)}; "
                          f"an escape slot: {', '.join(ESCAPE_NAMES)}; an angles slot: {', '.join(ANGLES_NAMES)}; "
-                         f"a tcuts slot: {', '.join(TCUTS_NAMES)}")
+                         f"a tcuts slot: {', '.join(TCUTS_NAMES)}; the profile slot: {', '.join(PROFILE_NAMES)}")
     if bins is not None:
         if name not in BIN_PARTS:
             raise ValueError(f"ensemble: {name!r} has no [zone][bins] shape; a bins window fits: {', '.join(BIN_PARTS)}")
@@ -710,6 +739,7 @@ class Ensemble:
         self.layout = EnsLayout(P)
         self.n_species = int(n_species)
         self.iteration_slot = self.n_species
+        self.i_shock = int(P.i_shock)      # the last upstream zone (profile_consistency)
         # run_overlapped(ensemble=True): mean / standard error / count over the iterations of ion_finalize's FINALIZE_NAMES
         self.finalize_mean: Dict[str, np.ndarray] = {}
         self.finalize_stderr: Dict[str, np.ndarray] = {}
@@ -718,6 +748,7 @@ class Ensemble:
         self.photon_layout = None      # consumers.PhotonLayout of set_photon_layout
         self.angle_windows = None      # ((l_lo, ...), (l_hi, ...)) of set_angle_windows
         self.tcuts_n = None            # the number of time cuts of the tcuts samples, fixed by the first
+        self.profile_settings = None   # ProfileIn.settings() of the first profile sample, fixed by it
         self._deposited: List[int] = []      # species slots deposited since the last add_photons_all, in deposit order
 
     @staticmethod
@@ -833,6 +864,21 @@ class Ensemble:
     def _tcuts_differ(a, b) -> bool:
         return a.tcuts_n is not None and b.tcuts_n is not None and a.tcuts_n != b.tcuts_n
 
+    profile_slot = PROFILE_SLOT        # the profile slot, one per ensemble (MCS_ENS_PROFILE)
+
+    @staticmethod
+    def is_profile(slot: int) -> bool:
+        return slot == PROFILE_SLOT
+
+    @staticmethod
+    def _settings_differ(a, b) -> bool:
+        """Two ProfileIn.settings() vectors (or None) that are both there and differ in some bit."""
+        return a is not None and b is not None and np.asarray(a, dtype=np.float64).tobytes() != np.asarray(b, dtype=np.float64).tobytes()
+
+    @classmethod
+    def _profiles_differ(cls, a, b) -> bool:
+        return cls._settings_differ(a.profile_settings, b.profile_settings)
+
     photons_all_slot = PHOTONS_ALL     # the source slot, one per ensemble (MCS_ENS_PHOTONS_ALL)
 
     @staticmethod
@@ -864,10 +910,12 @@ class Ensemble:
         self.photon_layout = layout
 
     def _decode(self, slot: int) -> Tuple[str, Optional[int]]:
-        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source", "escape", "angles" or "tcuts" -- the one place where
-        its bits are read; the index is None for the iteration and the source slot, and not yet checked (`_check_slot`)."""
+        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source", "escape", "angles", "tcuts" or "profile" -- the one place where
+        its bits are read; the index is None for the iteration, the source and the profile slot, and not yet checked (`_check_slot`)."""
         if self.is_photons_all(slot):
             return "source", None
+        if self.is_profile(slot):
+            return "profile", None
         if self.is_products(slot):
             return "products", slot ^ PRODUCTS_BIT
         if self.is_photons(slot):
@@ -892,7 +940,7 @@ class Ensemble:
     def names(self, slot: int):
         self._check_slot(slot)
         return {"species": SPECIES_NAMES, "iteration": ITERATION_NAMES, "products": PRODUCT_NAMES, "escape": ESCAPE_NAMES,
-                "angles": ANGLES_NAMES, "tcuts": TCUTS_NAMES}.get(self._kind(slot), PHOTON_NAMES)
+                "angles": ANGLES_NAMES, "tcuts": TCUTS_NAMES, "profile": PROFILE_NAMES}.get(self._kind(slot), PHOTON_NAMES)
 
     def _check_slot(self, slot: int):
         kind, s = self._decode(slot)
@@ -909,6 +957,8 @@ class Ensemble:
             return 0 if self.angle_windows is None else self.layout.angles_fields(len(self.angle_windows[0]))["total"]
         if kind == "tcuts":
             return 0 if self.tcuts_n is None else self.layout.tcuts_fields(self.tcuts_n)["total"]
+        if kind == "profile":
+            return self.layout.profile_fields()["total"]
         return {"species": self.layout.species_total, "iteration": self.layout.iteration_total, "products": self.layout.products_total,
                 "escape": self.layout.escape_total}[kind]
 
@@ -929,6 +979,8 @@ class Ensemble:
             if self.tcuts_n is None:
                 raise ValueError(f"ensemble: {self._describe(slot)} has taken no sample yet (its first fixes the number of time cuts)")
             table = self.layout.tcuts(self.tcuts_n)
+        elif kind == "profile":
+            table = self.layout.profile()
         else:
             table = {"species": self.layout.species, "iteration": self.layout.iteration, "products": self.layout.products,
                      "escape": self.layout.escape}[kind]
@@ -1181,6 +1233,20 @@ class HostEnsemble(Ensemble):
         with np.errstate(invalid="ignore"):          # (a NaN of a dead row stays NaN)
             self._sample(self.tcuts_slot(slot), x)
 
+    def add_profile(self, backend, update):
+        """One profile sample from a `ProfileUpdate` (consumers.profile_update); the ensemble's first fixes the settings."""
+        if update is None:
+            raise ValueError("ensemble: the numpy ensemble takes its profile sample from a ProfileUpdate")
+        if self._settings_differ(self.profile_settings, update.settings):
+            raise ValueError("ensemble: the settings of the ProfileUpdate differ from those of the ensemble's profile samples")
+        x = update.words()
+        if x.size != self.layout.profile_fields()["total"]:
+            raise ValueError(f"ensemble: the ProfileUpdate holds {x.size} words; a profile sample has {self.layout.profile_fields()['total']}")
+        if self.profile_settings is None:
+            self.profile_settings = np.array(update.settings, dtype=np.float64)
+        with np.errstate(invalid="ignore"):          # (a non-finite word stays non-finite)
+            self._sample(PROFILE_SLOT, x)
+
     def add_escape(self, backend, slot: int, spectra):
         """One escape sample of species slot `slot` from an `EscapeSpectra` (consumers.escape_spectra on `backend`), the slopes of its
         six rows by the backend's deterministic log10."""
@@ -1251,6 +1317,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: merge of ensembles whose angle windows differ")
         if self._tcuts_differ(self, other):
             raise ValueError("ensemble: merge of ensembles whose tcuts samples differ in the number of time cuts")
+        if self._profiles_differ(self, other):
+            raise ValueError("ensemble: merge of ensembles whose profile samples differ in their settings")
         # an ensemble without a photon layout or a slope window takes the one its samples were made with
         if other._sampled("photons", "source") and self.photon_layout is None:
             self.photon_layout = other.photon_layout
@@ -1260,6 +1328,8 @@ class HostEnsemble(Ensemble):
             self.angle_windows = other.angle_windows
         if other._sampled("tcuts") and self.tcuts_n is None:
             self.tcuts_n = other.tcuts_n
+        if other._sampled("profile") and self.profile_settings is None:
+            self.profile_settings = other.profile_settings
         for k, b in other._slots.items():      # (what is pending for the source slot on either side stays where it is)
             if b.n == 0:
                 continue
@@ -1300,6 +1370,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: a merged summary of ensembles whose angle windows differ")
         if self.is_tcuts(slot) and any(self._tcuts_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose tcuts samples differ in the number of time cuts")
+        if self.is_profile(slot) and any(self._profiles_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
+            raise ValueError("ensemble: a merged summary of ensembles whose profile samples differ in their settings")
         for first, count, floor_frac, tol in ranges:
             m, q, na = None, None, 0
             for e in [self] + others:
@@ -1321,6 +1393,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: a comparison of ensembles whose angle windows differ")
         if self.is_tcuts(slot) and self._tcuts_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose tcuts samples differ in the number of time cuts")
+        if self.is_profile(slot) and self._profiles_differ(self, other):
+            raise ValueError("ensemble: a comparison of ensembles whose profile samples differ in their settings")
         (ma, qa, _), (mb, qb, _) = self._vectors(slot), other._vectors(other_slot)
         return [difference_of(ma[first:first + count], qa[first:first + count], n_a, mb[first:first + count], qb[first:first + count], n_b,
                               floor_frac, zcut) for first, count, floor_frac, zcut in ranges]
@@ -1400,6 +1474,13 @@ class HipEnsemble(Ensemble):
         if self.tcuts_n is None:
             self.tcuts_n = int(backend.n_tcuts)      # (as the library does: the first sample fixes it)
 
+    def add_profile(self, backend: HipBackend, update=None):
+        """One profile sample from what mcs_profile_update (consumers.profile_update) left on the backend's device
+        (mcs_ens_add_profile); nothing crosses to the host, of `update` only the settings are noted."""
+        self._chk(self.lib.mcs_ens_add_profile(self.h, backend.h))
+        if self.profile_settings is None and update is not None:
+            self.profile_settings = np.array(update.settings, dtype=np.float64)      # (as the library does: the first sample fixes them)
+
     def _set_photon_layout(self, layout):
         self._chk(self.lib.mcs_ens_set_photon_layout(self.h, *layout.args()))
 
@@ -1436,6 +1517,8 @@ class HipEnsemble(Ensemble):
             self.angle_windows = other.angle_windows      # (likewise)
         if self.tcuts_n is None and other.tcuts_n is not None and any(other.count(other.tcuts_slot(s)) for s in range(other.n_species)):
             self.tcuts_n = other.tcuts_n      # (likewise)
+        if self.profile_settings is None and other.profile_settings is not None and other.count(PROFILE_SLOT):
+            self.profile_settings = other.profile_settings      # (likewise)
 
     def count(self, slot: int) -> int:
         n = ct.c_int64(0)
@@ -1479,3 +1562,32 @@ class HipEnsemble(Ensemble):
 
     def load_mean(self, slot: int, backend: HipBackend):
         self._chk(self.lib.mcs_ens_load_mean(self.h, int(slot), backend.h))
+
+
+@dataclasses.dataclass
+class ProfileConsistency:
+    """How far the current profile is from the one its own fluxes predict (profile_consistency)."""
+    n: int                   # samples
+    z: np.ndarray            # [n_grid]: mean(shift) / stderr(shift); 0 where both vanish (a pinned zone), inf where only the error does
+    chi2_upstream: float     # sum of z^2 over the upstream zones that have a finite z and a positive error
+    n_upstream: int          # how many zones that sum has
+
+
+def profile_consistency(ens: Ensemble, x_grid_cm=None, i_shock: Optional[int] = None) -> ProfileConsistency:
+    """Per zone z = mean(shift) / stderr(shift) of the ensemble's profile slot, from its mean and M2 on the host (no new reduction),
+    and the sum of z^2 over the upstream zones -- those with x_grid_cm[1..n_grid] < 0, or zones 1..i_shock (default: the i_shock of
+    the ensemble's parameters).  A self-consistent profile has z of order one; refused below two samples."""
+    n = ens.count(PROFILE_SLOT)
+    if n < 2:
+        raise ValueError(f"ensemble: profile_consistency needs at least two profile samples; the slot has {n}")
+    mean, m2 = ens.mean(PROFILE_SLOT, "shift"), ens.m2(PROFILE_SLOT, "shift")
+    ng = mean.size
+    if x_grid_cm is not None:
+        up = np.asarray(x_grid_cm, dtype=np.float64)[1:ng + 1] < 0
+    else:
+        up = np.arange(ng) < int(ens.i_shock if i_shock is None else i_shock)
+    with np.errstate(all="ignore"):
+        se = np.sqrt(m2 / (float(n) * float(n - 1)))
+        z = np.where((mean == 0) & (se == 0), 0.0, mean / se)
+    used = up & np.isfinite(z) & (se > 0)
+    return ProfileConsistency(n, z, float(np.sum(z[used] * z[used])), int(np.count_nonzero(used)))

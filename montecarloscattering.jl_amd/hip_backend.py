@@ -398,6 +398,24 @@ class HipBackend:
         self._chk(self.lib.mcs_tcut_spectra(self.h, ct.byref(s), _dp(out), diag.ctypes.data_as(c_int64_p)))
         return out, diag
 
+    def profile_update(self, pin, pressures=None):
+        """K13: the shock-profile update from the resident fluxes and running scalars, the grid tables of set_grid and the pressures
+        mcs_thermo_calcs left on the device -- or `pressures` = (P_par, P_perp, energy_density), host [n_grid] each, in their place
+        -> (out, diag [3]); `out` in mcs_profile_layout (capi.profile_layout), diag = (non-finite output words, zones whose Newton ran
+        out of steps, the largest Newton step count).  pin: a consumers.ProfileIn."""
+        n = self.P.n_grid
+        out = np.zeros(capi.profile_layout(self.P).total)
+        diag = np.zeros(3, dtype=np.int64)
+        s = pin.as_struct()
+        pr = None
+        if pressures is not None:
+            pr = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64).ravel()[:n] for a in pressures]))
+            if pr.size != 3 * n:
+                raise ValueError("profile_update: the pressures are three arrays of n_grid doubles")
+        self._chk(self.lib.mcs_profile_update(self.h, ct.byref(s), _dp(pr) if pr is not None else None, _dp(out),
+                                              diag.ctypes.data_as(c_int64_p)))
+        return out, diag
+
     def photon_synch(self, dndp_pf, mom_edge_cgs, mc, n_photon, emin_mev, bins_per_dec):
         """K5: synchrotron emission dP/d(ln E) [erg/s] per zone from the plasma-frame electron dN/dp -> (E_erg[n_photon], emis[n_grid][n_photon])."""
         d = np.ascontiguousarray(dndp_pf, dtype=np.float64); pe = np.ascontiguousarray(mom_edge_cgs, dtype=np.float64)
