@@ -301,7 +301,8 @@ int mcs_begin_iteration(mcs_ctx* ctx, int i_iter);
  * num_crossings/therm := 0, fluxes := 0 (quirk Q2), recv_pool := transfer_pool.
  * With do_tcuts it also queues, on the context's stream, one device-to-device copy of the species' block
  * spectra_coupled[i_ion][0..MCS_NA_C)[0..201) into a base buffer that the context owns (mcs_tcut_spectra, K12, reads it); without
- * do_tcuts nothing is queued. */
+ * do_tcuts nothing is queued.  With cuts set and n_xspec >= 1 it queues likewise one copy of rows 0..n_xspec-1 of spectra_sf and
+ * spectra_pf (mcs_detector_spectra, K14, reads it); with no detector nothing is queued. */
 int mcs_begin_species(mcs_ctx* ctx, int i_iter, int i_ion, double aa, double zz,
                       double pmax_cutoff, double density, double electron_weight_fac);
 /* analytic fast-push fluxes of init_pop/F_update! (src/initializers.jl:1054-1068,1156) */
@@ -532,6 +533,62 @@ typedef struct mcs_tcut_layout {
 } mcs_tcut_layout;
 int mcs_tcut_get_layout(const mcs_params* p, int n_tcuts, mcs_tcut_layout* out);     /* needs no GPU */
 int mcs_tcut_spectra(mcs_ctx* ctx, const mcs_consumer_in* in, double* out, int64_t* diag);
+
+/* K14: the spectra at the detectors, "what does a detector at a fixed place see" (the reference's calculate_x_spec_spectra!,
+ * src/all_flux.jl:164-190, fills spectra_sf and spectra_pf at every crossing of an XSPEC position; nothing in the reference reads
+ * them), for the context's CURRENT species and the nd = n_xspec detectors of mcs_set_cuts, from the resident spectra_sf (frame
+ * f = 0, shock frame) and spectra_pf (f = 1, plasma frame).  Of `in` it reads mom_log_cgs (e[l]) and mom_edge_cgs (E[l]), NM = nmom + 2
+ * edges each.
+ * BASE.  Both sections are shared by all species and never reset.  With cuts set and n_xspec >= 1, mcs_begin_species queues, on the
+ * context's stream, ONE device-to-device copy of rows 0..nd-1 of both sections into a base buffer that the context owns
+ * ([2][nd][201]); with no detector nothing is queued.  A species' contribution in one iteration is the growth of the rows over that
+ * base: g = now - base, one subtraction per word, exactly 0.0 where nothing was deposited.  The deposits of spectra_pf are positive
+ * (weight |p / p_x| F), so g[1] is never negative.  Those of spectra_sf are SIGNED as in the reference (weight p / p_x in the shock
+ * frame, negative for a crossing towards upstream): a row of frame 0 is the NET flux-weighted count, its number is close to the
+ * injected flux at every upstream detector, and in a real run single bins of it may come out negative.  The rules below take such
+ * a word as it is: it enters number, mean and the cumulative sums, its spectrum word falls to the floor, its dndp is negative, and it
+ * is no valid bin of a slope or of the gradient (which need g > 0).  mcs_set_cuts drops the base.  Because the rows are not per species, anything else that adds
+ * into them between mcs_begin_species and this call -- another species, mcs_accumulate_tallies of a secondary context -- is counted
+ * as the current species' growth: one context, one species at a time.
+ * out: host, laid out as mcs_detector_get_layout says (it needs no GPU; 1 <= n_det <= n_grid):
+ *   spectrum [2][nd][NM] | dndp [2][nd][NM] | number [2][nd] | mean_log_p [2][nd] | quantile [3][2][nd] | slope [2][nd] | gradient [NM];
+ *   total 2 nd (2 NM + 6) + NM.
+ * Every operation is a separate fp64 rounding; sums are serial and ascending from 0.0; there are no floating-point atomics, so
+ * every call on the same buffers gives the same bits.
+ *   BINS: a row has the bins l = 0..nmom.  Words with l > nmom of the 201-wide tally row, and rows >= nd, are never read.
+ *   GROWTH AND NUMBER: g[f][d][l] = now - base;  number[f][d] = ((0.0 + g[0]) + g[1]) + ... + g[nmom].
+ *   LIVE AND DEAD ROWS: a row is live if number > 1e-99.  A dead row has spectrum and dndp all 1e-99, number 0.0, and mean_log_p,
+ *     the three quantiles and slope a quiet NaN (K12's convention: a summary counts them in n_nonfinite, no trigger on them is met).
+ *   SPECTRUM, MEAN, QUANTILES: K12's rules word for word (mcs_tcut_spectra above: spectrum[l] = g[l] / number or 1e-99 where that
+ *     is below 1e-60, entry nmom+1 1e-99; MEAN; QUANTILES with MCS_TCUT_Q and the f = 1 fall-back).
+ *   DNDP: on a live row dndp[l] = g[l] / (E[l+1] - E[l]), or 1e-99 where g[l] is 0.0; entry nmom+1 is 1e-99.  A table whose E is
+ *     not strictly ascending is refused.
+ *   SLOPE: slope[f][d] is the least-squares slope ("Slope of frame m" below) over the window l_lo <= l < l_hi of a live row: a bin
+ *     is valid if g[l] > 0, x = 0.5 (e[l] + e[l+1]), y = log10(dndp[l]) (the deterministic log10 of include/mcs_math.h); fewer than
+ *     three valid bins give a quiet NaN.  The window needs 0 <= l_lo, l_hi <= nmom + 1, l_hi - l_lo >= 3.
+ *   GRADIENT: frame 0 only, for l = 0..nmom: the same slope rule over the detectors d = 0..nd-1 in index order (whatever their
+ *     order in x).  A detector is valid if x_spec[d] < 0.0 (upstream; one at exactly 0.0 is not) and g[0][d][l] > 0;
+ *     x = x_spec[d] / x_unit, y = log10(g[0][d][l]).  Fewer than three valid detectors give a quiet NaN; gradient[nmom+1] is a quiet
+ *     NaN.  x_unit must be finite and positive; a driver passes rg0.  DSA predicts n(x, p) ~ exp(u0 x / D(p)) upstream, so
+ *     ln 10 * gradient[l] is u0 / D(p_l) in units of 1 / x_unit: the inverse e-fold length of the precursor at that momentum.  Bins
+ *     that few particles reach are NOISY -- three points through counts of a few -- which is what the error bar of the detectors
+ *     sample is for.
+ * diag: host [3] or null: the number of live rows (of 2 nd); the number of words read with now < base (0 on rows that took only
+ *   positive deposits, so a caller who overwrote such tallies sees it; in a real run the signed frame-0 bins described under BASE
+ *   are counted here); the number of finite gradient words.
+ * The result also stays on the device, in a buffer that no other call writes, for the detectors sample of the ensemble statistics
+ * (below); mcs_begin_species, mcs_set_cuts and that sample invalidate it.
+ * Refused, with a message and nothing written: a null argument or table, before mcs_set_cuts, with no detector set, before the
+ * first mcs_begin_species, without a base (cuts set after the species began), a bad window, a bad x_unit, a table E that does not
+ * ascend. */
+typedef struct mcs_detector_layout {
+  int64_t spectrum, dndp, number, mean_log_p, quantile, slope, gradient;   /* offsets, in doubles */
+  int64_t row_n;                                            /* nmom + 2: the length of a spectrum or dndp row and of gradient */
+  int64_t n_det;                                            /* nd */
+  int64_t total;
+} mcs_detector_layout;
+int mcs_detector_get_layout(const mcs_params* p, int n_det, mcs_detector_layout* out);     /* needs no GPU; 1 <= n_det <= n_grid */
+int mcs_detector_spectra(mcs_ctx* ctx, const mcs_consumer_in* in, int l_lo, int l_hi, double x_unit, double* out, int64_t* diag);
 
 /* K13: the shock-profile update, "which profile would smooth_grid_par write from this iteration" (the reference's iter_finalize,
  * src/iter_finalize.jl:1-110, with smooth_grid_par / new_velocity_profile / smooth_profile!, src/smoothers.jl:54-604, as the host's
@@ -931,6 +988,23 @@ int mcs_ens_add_tcuts(mcs_ens* ens, mcs_ctx* src, int species_slot);
 typedef mcs_profile_layout mcs_ens_profile_layout;
 int mcs_ens_profile_get_layout(const mcs_params* p, mcs_ens_profile_layout* out);    /* needs no GPU */
 int mcs_ens_add_profile(mcs_ens* ens, mcs_ctx* src);
+
+/* ---- detectors sample: error bars of the detector spectra.  Every species slot s has a sixth companion, the DETECTORS slot
+ * MCS_ENS_DETECTORS(s), which behaves as its tcuts slot does in the count, read, merge, summarize, summarize-merged and compare
+ * calls (vectors allocated at the first sample; reads of a slot that never took one are refused).  The sample is the last
+ * mcs_detector_spectra on the context as that call left it on the device, in its layout (mcs_ens_detectors_get_layout gives that of
+ * mcs_detector_get_layout): spectrum, dndp [2][nd][nmom+2], number, mean_log_p [2][nd], quantile [3][2][nd], slope [2][nd],
+ * gradient [nmom+2].
+ * The accumulator keeps the SETTINGS of its first detectors sample -- nd, the window l_lo, l_hi, and the bits of x_unit and of
+ * x_spec[0..nd) -- (or takes them in a merge into an accumulator that has none): a later sample, merge, merged summary or comparison
+ * whose settings differ is refused.
+ * mcs_ens_add_detectors: refused unless mcs_detector_spectra has run on src since its last mcs_begin_species and since the last
+ * detectors sample taken from it, and for what mcs_ens_add_species refuses.  Queued on src's stream behind the accumulator's event,
+ * no host synchronisation.  mcs_ens_load_mean takes species slots only. */
+#define MCS_ENS_DETECTORS(s) ((s) | (1 << 23))
+typedef mcs_detector_layout mcs_ens_detectors_layout;
+int mcs_ens_detectors_get_layout(const mcs_params* p, int n_det, mcs_ens_detectors_layout* out);    /* needs no GPU */
+int mcs_ens_add_detectors(mcs_ens* ens, mcs_ctx* src, int species_slot);
 
 /* ---- photons sample: error bars of the photon spectra at Earth.  A shell spectrum is a sum over zones, slices and processes: its
  * variance does not follow from per-cell variances, so the spectrum itself is sampled once per iteration, from what

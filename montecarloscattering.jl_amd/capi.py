@@ -137,7 +137,14 @@ class McsProfileLayout(ct.Structure):
                                                 "shift", "scalars", "row_n", "n_scalars", "total")]
 
 
+class McsDetectorLayout(ct.Structure):
+    """`mcs_detector_layout` (= `mcs_ens_detectors_layout`): offsets of the seven parts of a detector result, the length of a row and the
+    number of detectors (include/mcs.h, mcs_detector_spectra and "detectors sample")."""
+    _fields_ = [(name, ct.c_int64) for name in ("spectrum", "dndp", "number", "mean_log_p", "quantile", "slope", "gradient", "row_n", "n_det", "total")]
+
+
 TCUT_Q = (0.5, 0.9, 0.99)       # MCS_TCUT_Q
+ENS_DETECTORS_BIT = 1 << 23     # MCS_ENS_DETECTORS(s) = s | ENS_DETECTORS_BIT
 ENS_PROFILE = 1 << 24           # MCS_ENS_PROFILE: the profile slot, one per accumulator
 ENS_ESCAPE_BIT = 1 << 27        # MCS_ENS_ESCAPE(s) = s | ENS_ESCAPE_BIT
 ENS_ANGLES_BIT = 1 << 26        # MCS_ENS_ANGLES(s) = s | ENS_ANGLES_BIT
@@ -388,6 +395,8 @@ def load_library() -> ct.CDLL:
         "mcs_angle_dist": (i32, [vp, ct.POINTER(McsConsumerIn), i32, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
         "mcs_tcut_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsTcutLayout)]),
         "mcs_tcut_spectra": (i32, [vp, ct.POINTER(McsConsumerIn), c_double_p, c_int64_p]),
+        "mcs_detector_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsDetectorLayout)]),
+        "mcs_detector_spectra": (i32, [vp, ct.POINTER(McsConsumerIn), i32, i32, dbl, c_double_p, c_int64_p]),
         "mcs_profile_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsProfileLayout)]),
         "mcs_profile_update": (i32, [vp, ct.POINTER(McsProfileIn), c_double_p, c_double_p, c_int64_p]),
         "mcs_photon_synch": (i32, [vp, c_double_p, c_double_p, dbl, i32, dbl, dbl, c_double_p, c_double_p]),
@@ -436,6 +445,8 @@ def load_library() -> ct.CDLL:
         "mcs_ens_add_tcuts": (i32, [vp, vp, i32]),
         "mcs_ens_profile_get_layout": (i32, [ct.POINTER(McsParams), ct.POINTER(McsProfileLayout)]),
         "mcs_ens_add_profile": (i32, [vp, vp]),
+        "mcs_ens_detectors_get_layout": (i32, [ct.POINTER(McsParams), i32, ct.POINTER(McsDetectorLayout)]),
+        "mcs_ens_add_detectors": (i32, [vp, vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing: fail loudly
@@ -461,6 +472,16 @@ def tcut_layout(P: McsParams, n_tcuts: int) -> McsTcutLayout:
     out = McsTcutLayout()
     lib = load_library()
     if lib.mcs_tcut_get_layout(ct.byref(P), int(n_tcuts), ct.byref(out)) != 0:
+        raise ValueError(lib.mcs_last_error().decode())
+    return out
+
+
+def detector_layout(P: McsParams, n_det: int) -> McsDetectorLayout:
+    """`mcs_detector_get_layout`: where the parts of a detector result of n_det detectors lie (needs no GPU).  ValueError with the
+    library's message for an n_det outside 1..n_grid."""
+    out = McsDetectorLayout()
+    lib = load_library()
+    if lib.mcs_detector_get_layout(ct.byref(P), int(n_det), ct.byref(out)) != 0:
         raise ValueError(lib.mcs_last_error().decode())
     return out
 
@@ -520,4 +541,6 @@ EXPORTED_SYMBOLS += ["mcs_angle_dist", "mcs_ens_angles_get_layout", "mcs_ens_set
 EXPORTED_SYMBOLS += ["mcs_tcut_spectra", "mcs_tcut_get_layout", "mcs_ens_tcuts_get_layout", "mcs_ens_add_tcuts"]
 # the shock-profile update (K13) and its sample
 EXPORTED_SYMBOLS += ["mcs_profile_update", "mcs_profile_get_layout", "mcs_ens_profile_get_layout", "mcs_ens_add_profile"]
+# the detector spectra (K14) and their sample
+EXPORTED_SYMBOLS += ["mcs_detector_spectra", "mcs_detector_get_layout", "mcs_ens_detectors_get_layout", "mcs_ens_add_detectors"]
 PHOTON_PROCESS = {"synch": 0, "ic": 1, "pion": 2}      # MCS_PHOTON_SYNCH, _IC, _PION

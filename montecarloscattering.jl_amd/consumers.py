@@ -267,6 +267,49 @@ def _tcut_from_words(out, diag, nt, NM, tcuts, mom_log) -> TcutSpectra:
                        np.array(tcuts, dtype=np.float64), np.array(mom_log, dtype=np.float64))
 
 
+def _growth_rows_host(now, base, e, nm: int):
+    """The row rules that K12 and K14 share (include/mcs.h, mcs_tcut_spectra: GROWTH AND NUMBER, LIVE AND DEAD ROWS, the spectrum's
+    normalisation and floor, MEAN, QUANTILES) for rows side by side: now, base [rows][nm+1], e [nm+2] ->
+    (g, n_neg, num, live, spectrum [rows][nm+2], mean [rows], quant [3][rows]).  To be called under np.errstate(all="ignore")."""
+    nt, NM = now.shape[0], nm + 2
+    g = now - base
+    n_neg = int(np.count_nonzero(now < base))
+    num = np.zeros(nt)
+    for l in range(nm + 1):
+        num = num + g[:, l]
+    live = num > 1.0e-99
+    spectrum = np.full((nt, NM), 1.0e-99)
+    s = g / np.where(live, num, 1.0)[:, None]
+    spectrum[:, :nm + 1] = np.where(live[:, None], np.where(s < 1.0e-60, 1.0e-99, s), 1.0e-99)
+    c = 0.5 * (e[:-1] + e[1:])
+    sm = np.zeros(nt)
+    for l in range(nm + 1):
+        sm = sm + g[:, l] * c[l]
+    mean = np.where(live, sm / num, np.nan)
+    quant = np.full((3, nt), np.nan)
+    for j, q in enumerate(TCUT_Q):
+        T = q * num
+        C = np.zeros(nt)
+        found = np.zeros(nt, dtype=bool)
+        last = np.full(nt, -1)
+        val = np.full(nt, np.nan)
+        for l in range(nm + 1):
+            gl = g[:, l]
+            Cn = C + gl
+            lit = (gl > 0) & ~found
+            hit = lit & (Cn >= T)
+            f = (T - C) / np.where(hit, gl, 1.0)
+            val = np.where(hit, e[l] + f * (e[l + 1] - e[l]), val)
+            found = found | hit
+            last = np.where(lit & ~hit, l, last)
+            C = Cn
+        short = ~found & (last >= 0)
+        lz = np.where(short, last, 0)
+        val = np.where(short, e[lz] + 1.0 * (e[lz + 1] - e[lz]), val)
+        quant[j] = np.where(live, val, np.nan)
+    return g, n_neg, num, live, spectrum, mean, quant
+
+
 def tcut_spectra_host(now, base, weight, mom_log, tcuts, nmom: int, log10) -> TcutSpectra:
     """The rules of mcs_tcut_spectra (include/mcs.h) in numpy, the cuts side by side and the bins of a row one after the other, so
     that every sum is the serial one.  now, base: [>= nt][>= nmom+1] rows of spectra_coupled of the species and what they held at
@@ -278,43 +321,9 @@ def tcut_spectra_host(now, base, weight, mom_log, tcuts, nmom: int, log10) -> Tc
     now = np.asarray(now, dtype=np.float64)[:nt, :nm + 1]
     base = np.asarray(base, dtype=np.float64)[:nt, :nm + 1]
     with np.errstate(all="ignore"):
-        g = now - base
-        n_neg = int(np.count_nonzero(now < base))
-        num = np.zeros(nt)
-        for l in range(nm + 1):
-            num = num + g[:, l]
-        live = num > 1.0e-99
+        g, n_neg, num, live, spectrum, mean, quant = _growth_rows_host(now, base, e, nm)
         w = np.asarray(weight, dtype=np.float64)[:nt]
         weight_out = np.where(w < 1.0e-60, 1.0e-99, w)
-        spectrum = np.full((nt, NM), 1.0e-99)
-        s = g / np.where(live, num, 1.0)[:, None]
-        spectrum[:, :nm + 1] = np.where(live[:, None], np.where(s < 1.0e-60, 1.0e-99, s), 1.0e-99)
-        c = 0.5 * (e[:-1] + e[1:])
-        sm = np.zeros(nt)
-        for l in range(nm + 1):
-            sm = sm + g[:, l] * c[l]
-        mean = np.where(live, sm / num, np.nan)
-        quant = np.full((3, nt), np.nan)
-        for j, q in enumerate(TCUT_Q):
-            T = q * num
-            C = np.zeros(nt)
-            found = np.zeros(nt, dtype=bool)
-            last = np.full(nt, -1)
-            val = np.full(nt, np.nan)
-            for l in range(nm + 1):
-                gl = g[:, l]
-                Cn = C + gl
-                lit = (gl > 0) & ~found
-                hit = lit & (Cn >= T)
-                f = (T - C) / np.where(hit, gl, 1.0)
-                val = np.where(hit, e[l] + f * (e[l + 1] - e[l]), val)
-                found = found | hit
-                last = np.where(lit & ~hit, l, last)
-                C = Cn
-            short = ~found & (last >= 0)
-            lz = np.where(short, last, 0)
-            val = np.where(short, e[lz] + 1.0 * (e[lz + 1] - e[lz]), val)
-            quant[j] = np.where(live, val, np.nan)
         x = log10(np.ascontiguousarray(tcuts))
         index = ens.slopes_xy(x, quant, np.broadcast_to(live, quant.shape))
     number = np.where(live, num, 0.0)
@@ -341,6 +350,128 @@ def tcut_spectra(prob, backend, i_ion: int, base=None) -> TcutSpectra:
     f, _ = backend.read_tallies()
     return tcut_spectra_host(L.view(f, "spectra_coupled")[i_ion - 1], base, L.view(f, "weight_coupled")[i_ion - 1], tabs.mom_log_cgs,
                              prob.tcuts, P.num_psd_mom_bins, ens._det_log10(backend))
+
+
+# ---- K14: the spectra at the detectors (include/mcs.h, mcs_detector_spectra) ------------------------------------------------------
+@dataclasses.dataclass
+class DetectorSpectra:
+    """The spectra that the XSPEC detectors saw of one species in one iteration (K14, include/mcs.h mcs_detector_spectra), per frame
+    f (0: shock frame, spectra_sf; 1: plasma frame, spectra_pf) and detector d.  A detector that no particle crossed is a DEAD row:
+    spectrum and dndp all 1e-99, number 0.0, mean_log_p, the quantiles and slope NaN."""
+    spectrum: np.ndarray         # [2][nd][nmom+2]: the growth of the detector's row over the species, normalised to its sum; empty: 1e-99
+    dndp: np.ndarray             # [2][nd][nmom+2]: the growth per unit momentum (cgs); empty: 1e-99
+    number: np.ndarray           # [2][nd]: the sum the spectrum was normalised with; 0.0 in a dead row
+    mean_log_p: np.ndarray       # [2][nd]: the mean of log10 p (cgs) over the spectrum
+    quantile: np.ndarray         # [3][2][nd]: log10 of the momentum below which the share TCUT_Q[j] of the weight lies
+    slope: np.ndarray            # [2][nd]: d log10 dndp / d log10 p over the window; NaN with fewer than three lit bins
+    gradient: np.ndarray         # [nmom+2]: d log10 g / d (x / x_unit) over the upstream detectors, shock frame; ln 10 times it is u0 / D(p)
+    diag: np.ndarray             # [3]: live rows, words with now < base (must be 0), finite gradient words
+    x_spec: np.ndarray           # [nd]: the detectors' positions (cm)
+    window: tuple                # (l_lo, l_hi) of the slope
+    x_unit: float                # what the gradient's x was divided by (rg0)
+    mom_log_cgs: np.ndarray      # [nmom+2]: log10 of the momentum bin edges (cgs)
+
+    def words(self) -> np.ndarray:
+        """The result as one vector in mcs_detector_layout, the detectors sample of the ensemble statistics."""
+        return np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in
+                               (self.spectrum, self.dndp, self.number, self.mean_log_p, self.quantile, self.slope, self.gradient)])
+
+    def settings(self) -> tuple:
+        """What an ensemble keeps of its first detectors sample: nd, the window, the bits of x_unit and of x_spec."""
+        return (len(self.x_spec), int(self.window[0]), int(self.window[1]), np.float64(self.x_unit).tobytes(),
+                np.ascontiguousarray(self.x_spec, dtype=np.float64).tobytes())
+
+
+def _detector_from_words(out, diag, nd, NM, x_spec, window, x_unit, mom_log) -> DetectorSpectra:
+    o = np.asarray(out, dtype=np.float64)
+    r, a = 2 * nd, 2 * nd * NM
+    return DetectorSpectra(o[:a].reshape(2, nd, NM).copy(), o[a:2 * a].reshape(2, nd, NM).copy(), o[2 * a:2 * a + r].reshape(2, nd).copy(),
+                           o[2 * a + r:2 * a + 2 * r].reshape(2, nd).copy(), o[2 * a + 2 * r:2 * a + 5 * r].reshape(3, 2, nd).copy(),
+                           o[2 * a + 5 * r:2 * a + 6 * r].reshape(2, nd).copy(), o[2 * a + 6 * r:2 * a + 6 * r + NM].copy(),
+                           np.asarray(diag, dtype=np.int64), np.array(x_spec, dtype=np.float64), (int(window[0]), int(window[1])), float(x_unit),
+                           np.array(mom_log, dtype=np.float64))
+
+
+def check_detector_window(nmom: int, window) -> tuple:
+    """(l_lo, l_hi) of a slope window over the bins 0..nmom; None: all bins.  ValueError for what mcs_detector_spectra refuses."""
+    l_lo, l_hi = (0, int(nmom) + 1) if window is None else (int(window[0]), int(window[1]))
+    if l_lo < 0 or l_hi > nmom + 1 or l_hi - l_lo < 3:
+        raise ValueError(f"detector_spectra: window [{l_lo}, {l_hi}) needs 0 <= l_lo, l_hi <= {nmom + 1} and at least three bins")
+    return l_lo, l_hi
+
+
+def detector_spectra_host(now, base, mom_log, mom_edge, x_spec, nmom: int, window, x_unit: float, log10) -> DetectorSpectra:
+    """The rules of mcs_detector_spectra (include/mcs.h) in numpy, the rows side by side and the bins of a row one after the other,
+    so that every sum is the serial one.  now, base: [2][>= nd][>= nmom+1], the rows of spectra_sf and spectra_pf and what they held
+    at the species' start; log10: the deterministic one (ensemble._det_log10)."""
+    from . import ensemble as ens
+    x_spec = np.array(x_spec, dtype=np.float64)
+    nd, nm, NM = len(x_spec), int(nmom), int(nmom) + 2
+    if nd < 1:
+        raise ValueError("detector_spectra: no detector is set")
+    l_lo, l_hi = check_detector_window(nm, window)
+    if not (np.isfinite(x_unit) and x_unit > 0):
+        raise ValueError("detector_spectra: x_unit must be finite and positive")
+    e = np.asarray(mom_log, dtype=np.float64)[:NM]
+    E = np.asarray(mom_edge, dtype=np.float64)[:NM]
+    if not np.all(E[1:] > E[:-1]):
+        raise ValueError("detector_spectra: mom_edge_cgs is not strictly ascending")
+    now = np.asarray(now, dtype=np.float64)[:, :nd, :nm + 1].reshape(2 * nd, nm + 1)
+    base = np.asarray(base, dtype=np.float64)[:, :nd, :nm + 1].reshape(2 * nd, nm + 1)
+    with np.errstate(all="ignore"):
+        g, n_neg, num, live, spectrum, mean, quant = _growth_rows_host(now, base, e, nm)
+        dE = E[1:] - E[:-1]
+        dndp = np.full((2 * nd, NM), 1.0e-99)
+        lit = live[:, None] & (g != 0.0)
+        dndp[:, :nm + 1] = np.where(lit, g / dE[None, :], 1.0e-99)
+        valid = g > 0
+        y = np.zeros_like(g)
+        y[valid] = log10(np.ascontiguousarray(dndp[:, :nm + 1][valid]))
+        xc = 0.5 * (e[:-1] + e[1:])
+        slope = ens.slopes_xy(xc[l_lo:l_hi], y[:, l_lo:l_hi], valid[:, l_lo:l_hi])
+        slope = np.where(live, slope, np.nan)
+        # the gradient: per momentum bin a slope over the detectors, shock frame
+        g0 = g[:nd].T                                           # [nm+1][nd]
+        vg = (g0 > 0) & (x_spec < 0.0)[None, :]
+        yg = np.zeros_like(g0)
+        yg[vg] = log10(np.ascontiguousarray(g0[vg]))
+        gradient = np.full(NM, np.nan)
+        gradient[:nm + 1] = ens.slopes_xy(x_spec / x_unit, yg, vg)
+    number = np.where(live, num, 0.0)
+    diag = np.array([int(live.sum()), n_neg, int(np.isfinite(gradient).sum())], dtype=np.int64)
+    return DetectorSpectra(spectrum.reshape(2, nd, NM), dndp.reshape(2, nd, NM), number.reshape(2, nd), mean.reshape(2, nd),
+                           quant.reshape(3, 2, nd), slope.reshape(2, nd), gradient, diag, x_spec, (l_lo, l_hi), float(x_unit), e.copy())
+
+
+def detector_base(backend, nd: int) -> np.ndarray:
+    """Rows 0..nd-1 of spectra_sf and spectra_pf as the backend holds them now, [2][nd][201]: the base that a backend without the
+    device call needs of the species' start."""
+    L = backend.layout
+    f, _ = backend.read_tallies()
+    return np.stack([L.view(f, "spectra_sf")[:nd], L.view(f, "spectra_pf")[:nd]]).copy()
+
+
+def detector_spectra(prob, backend, i_ion: int, window=None, base=None) -> DetectorSpectra:
+    """The detector spectra of species i_ion from the backend's resident spectra_sf and spectra_pf: on a HIP backend the device call
+    (K14; the base is the one its begin_species took), on a backend without it the numpy statement of the same rules on the tallies
+    read back and on `base` (detector_base at the species' start).  window: (l_lo, l_hi) of the slope, None: all bins.  The gradient's
+    x is in units of rg0."""
+    P = prob.params
+    nd = len(prob.x_spec)
+    if nd < 1:
+        raise ValueError("detector_spectra: the problem has no detector (XSPEC)")
+    tabs = consumer_tables(prob, i_ion)
+    nm, NM = P.num_psd_mom_bins, P.num_psd_mom_bins + 2
+    l_lo, l_hi = check_detector_window(nm, window)
+    x_unit = float(prob.rg0)
+    if hasattr(backend, "detector_spectra"):
+        out, diag = backend.detector_spectra(tabs, l_lo, l_hi, x_unit)
+        return _detector_from_words(out, diag, nd, NM, prob.x_spec, (l_lo, l_hi), x_unit, tabs.mom_log_cgs)
+    if base is None:
+        raise ValueError("detector_spectra: a backend without detector_spectra needs the base, detector_base at the species' start")
+    from . import ensemble as ens
+    return detector_spectra_host(detector_base(backend, nd), base, tabs.mom_log_cgs, tabs.mom_edge_cgs, prob.x_spec, nm, (l_lo, l_hi), x_unit,
+                                 ens._det_log10(backend))
 
 
 # ---- K13: the shock-profile update (include/mcs.h, mcs_profile_update) ----------------------------------------------------------

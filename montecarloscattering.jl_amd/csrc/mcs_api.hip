@@ -193,6 +193,15 @@ struct mcs_ctx {
   DevBuf<double> d_prof_out, d_prof_tab; DevBuf<unsigned long long> d_prof_diag;
   bool have_prof = false;
   mcs_profile_in prof_in{};
+  // K14: d_det_base, rows 0..nd-1 of spectra_sf and spectra_pf as mcs_begin_species found them ([2][nd][201]; taken only with cuts set
+  // and n_xspec >= 1; have_det_base: there is one for the cuts in force); what the last mcs_detector_spectra left, in
+  // mcs_detector_layout, its counts and its settings; have_det: a whole result since the last mcs_begin_species, mcs_set_cuts and
+  // detectors sample.  h_x_spec: the host copy of x_spec.
+  DevBuf<double> d_det_base, d_det_out, d_det_tab; DevBuf<unsigned int> d_det_rowneg; DevBuf<unsigned long long> d_det_diag;
+  bool have_det = false, have_det_base = false;
+  int det_n = 0, det_lo = 0, det_hi = 0;
+  double det_x_unit = 0.0;
+  std::vector<double> h_x_spec;
   DevBuf<double> d_c2d; bool have_c2d = false;    // d2N/dp dcos of the last mcs_dndp_2d ([n_grid][ntht+2][nmom+2]), the input of mcs_photon_ic
   // K9, per process (MCS_PHOTON_SYNCH / _IC / _PION): d_pemis the emis[n_grid][n_photon] its fold left (pemis_n: that n_photon, 0 =
   // nothing), d_pobs the [n_shells+1][n] of the last mcs_photon_observe (pobs_n: its n, 0 = nothing; pobs_shells).  Only those calls
@@ -435,6 +444,7 @@ int mcs_set_cuts(mcs_ctx* c, int n_pcuts, const double* pcuts, int n_tcuts, cons
   h.insert(h.end(), inj_fracs, inj_fracs + ni);
   h.insert(h.end(), eps_target, eps_target + ng);
   c->have_cuts = false;      // (the table pointers of c->tb lead into the block that is replaced)
+  c->have_det = c->have_det_base = false;      // (K14's base and result belong to the detectors that are replaced)
   c->d_cuts.reset();
   if (reserve(c->d_cuts, (long long)h.size())) return 1;
   HIPCHK(hipMemcpyAsync(c->d_cuts, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -445,6 +455,7 @@ int mcs_set_cuts(mcs_ctx* c, int n_pcuts, const double* pcuts, int n_tcuts, cons
   c->tb.n_pcuts = n_pcuts; c->tb.n_tcuts = n_tcuts; c->tb.n_xspec = n_xspec;
   c->h_pcuts.assign(pcuts, pcuts + n_pcuts);
   c->h_inj_fracs.assign(inj_fracs, inj_fracs + ni);
+  c->h_x_spec.assign(x_spec, x_spec + (n_xspec > 0 ? n_xspec : 0));
   c->have_cuts = true;
   return 0;
 }
@@ -475,6 +486,7 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
   c->have_ang = false;
   c->have_tcut = false;
   c->have_prof = false;
+  c->have_det = false;
   c->photon_flags_clear();
   if (fold_replicas(c)) return 1;      // (the previous species' replicas, before its histograms are cleared)
   if (P.do_tcuts) {      // K12's base: the species' block of spectra_coupled as it stands now
@@ -482,6 +494,15 @@ int mcs_begin_species(mcs_ctx* c, int i_iter, int i_ion, double aa, double zz, d
     if (reserve(c->d_tcut_base, nb)) return 1;
     HIPCHK(hipMemcpyAsync(c->d_tcut_base, c->d_T + c->L.spectra_coupled + nb * (i_ion - 1), (size_t)nb * sizeof(double), hipMemcpyDeviceToDevice,
                           c->stream));
+  }
+  if (c->have_cuts && c->tb.n_xspec >= 1) {      // K14's base: rows 0..nd-1 of spectra_sf and of spectra_pf as they stand now, in one copy
+    const long long pm1 = MCS_PSD_MAX + 1, nd = c->tb.n_xspec;
+    c->have_det_base = false;
+    if (reserve(c->d_det_base, 2 * nd * pm1)) return 1;
+    HIPCHK(hipMemcpy2DAsync(c->d_det_base, (size_t)(nd * pm1) * sizeof(double), c->d_T + c->L.spectra_sf,
+                            (size_t)(c->L.spectra_pf - c->L.spectra_sf) * sizeof(double), (size_t)(nd * pm1) * sizeof(double), 2,
+                            hipMemcpyDeviceToDevice, c->stream));
+    c->have_det_base = true;
   }
   c->species_begun = true;
   const long long npsd = c->L.psd_stride_zone * P.n_grid;
@@ -1773,6 +1794,59 @@ int mcs_tcut_spectra(mcs_ctx* c, const mcs_consumer_in* in, double* out, int64_t
   return 0;
 }
 
+int mcs_detector_get_layout(const mcs_params* p, int n_det, mcs_detector_layout* out) {
+  if (!p || !out) return fail("mcs_detector_get_layout: null argument");
+  if (n_det < 1 || n_det > p->n_grid) return fail("mcs_detector_get_layout: n_det outside 1..n_grid (" + std::to_string(p->n_grid) + ")");
+  const int64_t nm = p->num_psd_mom_bins + 2, r = 2 * (int64_t)n_det;
+  out->row_n = nm; out->n_det = n_det;
+  out->spectrum = 0; out->dndp = r * nm; out->number = 2 * r * nm; out->mean_log_p = 2 * r * nm + r; out->quantile = 2 * r * nm + 2 * r;
+  out->slope = 2 * r * nm + (2 + MCS_TCUT_NQ) * r; out->gradient = 2 * r * nm + (3 + MCS_TCUT_NQ) * r;
+  out->total = 2 * r * nm + (3 + MCS_TCUT_NQ) * r + nm;
+  return 0;
+}
+
+int mcs_detector_spectra(mcs_ctx* c, const mcs_consumer_in* in, int l_lo, int l_hi, double x_unit, double* out, int64_t* diag) {
+  MCS_ENTER(c);
+  const std::string who = "mcs_detector_spectra";
+  if (!in || !out) return fail(who + ": null argument");
+  if (!c->have_cuts) return fail(who + ": cuts not set (mcs_set_cuts)");
+  if (c->tb.n_xspec < 1) return fail(who + ": no detector is set (n_xspec of mcs_set_cuts)");
+  if (!c->species_begun) return fail(who + ": no species has begun (mcs_begin_species takes the base)");
+  if (!c->have_det_base) return fail(who + ": no base (the cuts were set after the species began; mcs_begin_species takes the base)");
+  if (!in->mom_log_cgs || !in->mom_edge_cgs) return fail(who + ": null table");
+  const int nm = c->P.num_psd_mom_bins, NM = nm + 2, nd = c->tb.n_xspec;
+  if (NM > MCS_PSD_MAX + 1) return fail(who + ": more PSD bins than a row of spectra_sf holds");
+  if (l_lo < 0 || l_hi > nm + 1 || l_hi - l_lo < 3)
+    return fail(who + ": window [" + std::to_string(l_lo) + ", " + std::to_string(l_hi) + ") needs 0 <= l_lo, l_hi <= " + std::to_string(nm + 1) +
+                " and at least three bins");
+  if (!std::isfinite(x_unit) || !(x_unit > 0)) return fail(who + ": x_unit must be finite and positive");
+  for (int l = 0; l + 1 < NM; ++l)
+    if (!(in->mom_edge_cgs[l + 1] > in->mom_edge_cgs[l])) return fail(who + ": mom_edge_cgs is not strictly ascending at entry " + std::to_string(l + 1));
+  if (fold_replicas(c)) return 1;
+  mcs_detector_layout DL;
+  if (mcs_detector_get_layout(&c->P, nd, &DL)) return 1;
+  c->have_det = false;
+  if (reserve(c->d_det_out, DL.total) || reserve(c->d_det_tab, 2 * (long long)NM) || reserve(c->d_det_rowneg, 2 * (long long)nd) ||
+      reserve(c->d_det_diag, 3))
+    return 1;
+  std::vector<double> h((size_t)2 * NM);
+  memcpy(h.data(), in->mom_log_cgs, sizeof(double) * NM);
+  memcpy(h.data() + NM, in->mom_edge_cgs, sizeof(double) * NM);
+  HIPCHK(hipMemcpyAsync(c->d_det_tab, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(mcs_launch_detector_spectra(&c->P, c->d_T + c->L.spectra_sf, c->d_T + c->L.spectra_pf, c->d_det_base, c->d_det_tab, c->d_det_tab + NM,
+                                     c->tb.x_spec, nd, l_lo, l_hi, x_unit, c->d_det_out, c->d_det_rowneg, c->d_det_diag, c->stream));
+  std::vector<double> o((size_t)DL.total);
+  unsigned long long hd[3] = {0, 0, 0};
+  HIPCHK(hipMemcpyAsync(o.data(), c->d_det_out, sizeof(double) * o.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hd, c->d_det_diag, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));      // (also: h has been read)
+  memcpy(out, o.data(), sizeof(double) * o.size());
+  if (diag) for (int k = 0; k < 3; ++k) diag[k] = (int64_t)hd[k];
+  c->det_n = nd; c->det_lo = l_lo; c->det_hi = l_hi; c->det_x_unit = x_unit;
+  c->have_det = true;
+  return 0;
+}
+
 int mcs_profile_get_layout(const mcs_params* p, mcs_profile_layout* out) {
   if (!p || !out) return fail("mcs_profile_get_layout: null argument");
   if (p->n_grid < 3) return fail("mcs_profile_get_layout: a profile has at least three zones");
@@ -2031,7 +2105,8 @@ int mcs_ctx_view_get(mcs_ctx* c, McsCtxView* out) {
   if (fold_replicas(c)) return 1;
   *out = McsCtxView{c->device, c->stream, c->d_T, c->d_I, c->P, c->L, c->d_cout, c->have_cout_dndp, c->have_cout_thermo, {}, {}, {},
                     c->d_esc_out, c->have_esc, c->d_ang_out, c->have_ang, c->ang_n_win, {}, {},
-                    c->d_tcut_out, c->have_tcut, c->tcut_n, c->d_prof_out, c->have_prof, c->prof_in};
+                    c->d_tcut_out, c->have_tcut, c->tcut_n, c->d_prof_out, c->have_prof, c->prof_in,
+                    c->d_det_out, c->have_det, c->det_n, c->det_lo, c->det_hi, c->det_x_unit, c->h_x_spec.data()};
   out->prof_in.pxx_EM = out->prof_in.en_EM = out->prof_in.atan_x = nullptr;      // (the caller's tables are not kept)
   for (int m = 0; m < MCS_ANGLE_MAX_WINDOWS; ++m) { out->ang_lo[m] = c->ang_lo[m]; out->ang_hi[m] = c->ang_hi[m]; }
   for (int p = 0; p < 3; ++p) { out->pobs[p] = c->d_pobs[p]; out->pobs_n[p] = c->pobs_n[p]; out->pobs_shells[p] = c->pobs_shells[p]; }
@@ -2044,6 +2119,7 @@ void mcs_ctx_view_escape_taken(mcs_ctx* c) { c->have_esc = false; }
 void mcs_ctx_view_angles_taken(mcs_ctx* c) { c->have_ang = false; }
 void mcs_ctx_view_tcuts_taken(mcs_ctx* c) { c->have_tcut = false; }
 void mcs_ctx_view_profile_taken(mcs_ctx* c) { c->have_prof = false; }
+void mcs_ctx_view_detectors_taken(mcs_ctx* c) { c->have_det = false; }
 int mcs_ctx_view_fail(const char* msg) { return fail(msg); }
 
 }  // extern "C"

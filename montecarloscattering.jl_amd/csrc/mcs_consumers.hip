@@ -718,6 +718,40 @@ __device__ double tcut_quantile(const double* g, const double* e, int nm, double
   return e[last] + 1.0 * (e[last + 1] - e[last]);      // (the last lit bin's C fell short of T through rounding: f = 1)
 }
 
+// The ordered part of a row, one lane's work out of LDS (include/mcs.h, GROWTH AND NUMBER, LIVE AND DEAD ROWS, MEAN, QUANTILES): shared by
+// K12 and K14.  number is 0.0, mean and the quantiles a quiet NaN in a dead row.
+struct TcutRowStats { double number, mean, quant[MCS_TCUT_NQ]; };
+__device__ TcutRowStats tcut_row_stats(const double* s_g, const double* s_e, int nm) {
+  TcutRowStats r;
+  double num = 0.0;
+  for (int l = 0; l <= nm; ++l) num = num + s_g[l];
+  const bool live = num > 1.0e-99;
+  const double nan = __builtin_nan("");
+  r.number = live ? num : 0.0;
+  double mean = nan;
+  if (live) {
+    double s = 0.0;
+    for (int l = 0; l <= nm; ++l) {
+      const double c = 0.5 * (s_e[l] + s_e[l + 1]);
+      s = s + s_g[l] * c;
+    }
+    mean = s / num;
+  }
+  r.mean = mean;
+  const double q[MCS_TCUT_NQ] = MCS_TCUT_Q;
+  for (int j = 0; j < MCS_TCUT_NQ; ++j) r.quant[j] = live ? tcut_quantile(s_g, s_e, nm, q[j] * num) : nan;
+  return r;
+}
+// word l of a row's spectrum (num: the row's number, 0.0 in a dead row): the normalisation and floor of tcut_print
+__device__ double tcut_spectrum_word(const double* s_g, int l, int nm, double num) {
+  double d = 1.0e-99;
+  if (num > 0 && l <= nm) {
+    const double s = s_g[l] / num;
+    d = s < 1.0e-60 ? 1.0e-99 : s;
+  }
+  return d;
+}
+
 // One wave per cut: the lanes stride the row for the loads, the subtraction and the stores; the ordered sums are lane 0's, out of LDS.
 __global__ void __launch_bounds__(64) mcs_k_tcut_rows(TcutArgs a) {
   __shared__ double s_g[KC_MAXB], s_e[KC_MAXB];
@@ -736,41 +770,21 @@ __global__ void __launch_bounds__(64) mcs_k_tcut_rows(TcutArgs a) {
   s_neg[threadIdx.x] = neg;
   __syncthreads();
   if (threadIdx.x == 0) {
-    double num = 0.0;
-    for (int l = 0; l <= nm; ++l) num = num + s_g[l];
-    const bool live = num > 1.0e-99;
-    const double nan = __builtin_nan("");
+    const TcutRowStats r = tcut_row_stats(s_g, s_e, nm);
     double* o = a.out + (long long)nt * NM;      // weight | number | mean_log_p | quantile [3]
     const double w = a.weight[k];
     o[k] = w < 1.0e-60 ? 1.0e-99 : w;
-    o[nt + k] = live ? num : 0.0;
-    double mean = nan;
-    if (live) {
-      double s = 0.0;
-      for (int l = 0; l <= nm; ++l) {
-        const double c = 0.5 * (s_e[l] + s_e[l + 1]);
-        s = s + s_g[l] * c;
-      }
-      mean = s / num;
-    }
-    o[2 * nt + k] = mean;
-    const double q[MCS_TCUT_NQ] = MCS_TCUT_Q;
-    for (int j = 0; j < MCS_TCUT_NQ; ++j) o[(3 + j) * nt + k] = live ? tcut_quantile(s_g, s_e, nm, q[j] * num) : nan;
+    o[nt + k] = r.number;
+    o[2 * nt + k] = r.mean;
+    for (int j = 0; j < MCS_TCUT_NQ; ++j) o[(3 + j) * nt + k] = r.quant[j];
     unsigned int t = 0;
     for (int i = 0; i < 64; ++i) t += s_neg[i];
     a.row_neg[k] = t;
-    s_num = live ? num : 0.0;
+    s_num = r.number;
   }
   __syncthreads();
   const double num = s_num;
-  for (int l = threadIdx.x; l < NM; l += 64) {
-    double d = 1.0e-99;
-    if (num > 0 && l <= nm) {
-      const double s = s_g[l] / num;
-      d = s < 1.0e-60 ? 1.0e-99 : s;
-    }
-    a.out[(long long)k * NM + l] = d;
-  }
+  for (int l = threadIdx.x; l < NM; l += 64) a.out[(long long)k * NM + l] = tcut_spectrum_word(s_g, l, nm, num);
 }
 
 // One wave: lanes 0..2 the index of a quantile each (the slope rule of the products sample over the live rows), lane 3 the counts.
@@ -787,6 +801,98 @@ __global__ void __launch_bounds__(64) mcs_k_tcut_index(TcutArgs a) {
     unsigned long long live = 0ull, neg = 0ull;
     for (int k = 0; k < nt; ++k) { if (number[k] > 1.0e-99) ++live; neg += a.row_neg[k]; }
     a.diag[0] = live; a.diag[1] = neg;
+  }
+}
+
+// ---- K14: the spectra at the detectors (include/mcs.h, mcs_detector_spectra; the tallies of src/all_flux.jl:164-190) ---------------
+// now_sf / now_pf: the sections spectra_sf and spectra_pf, [n_grid][TCUT_STRIDE] with the momentum index fastest; base: what
+// mcs_begin_species copied of their rows 0..nd-1, [2][nd][TCUT_STRIDE]; only rows d < nd and words l <= nm are read.  Two launches, no
+// floating-point atomics, one fixed order of the adds: the same bits in every call.
+#define DET_JOIN_THREADS 256
+
+struct DetArgs {
+  const double *now_sf, *now_pf, *base;
+  const double *mom_log, *mom_edge;   // e[l], E[l]: [nm+2] each
+  const double* x_spec;               // [nd]
+  double x_unit;
+  int nm, nd, l_lo, l_hi;
+  double* out;              // mcs_detector_layout
+  unsigned int* row_neg;    // scratch [2 nd]: the words of a row with now < base
+  unsigned long long* diag; // [3]
+};
+
+// One wave per (frame, detector), shaped like mcs_k_tcut_rows: the lanes stride the loads, the subtraction and the stores; lane 0
+// does the ordered sums and the slope out of LDS.
+__global__ void __launch_bounds__(64) mcs_k_detector_rows(DetArgs a) {
+  __shared__ double s_g[KC_MAXB], s_e[KC_MAXB], s_w[KC_MAXB];      // growth, log10 edges, bin widths
+  __shared__ unsigned int s_neg[64];
+  __shared__ double s_num;
+  const int nm = a.nm, NM = nm + 2, nd = a.nd, r = blockIdx.x, f = r / nd, d = r - f * nd;
+  const double* now = (f == 0 ? a.now_sf : a.now_pf) + (long long)TCUT_STRIDE * d;
+  const double* base = a.base + (long long)TCUT_STRIDE * r;
+  unsigned int neg = 0;
+  for (int l = threadIdx.x; l < NM; l += 64) s_e[l] = a.mom_log[l];
+  for (int l = threadIdx.x; l <= nm; l += 64) {
+    const double n = now[l], b = base[l];
+    if (n < b) ++neg;
+    s_g[l] = n - b;
+    s_w[l] = a.mom_edge[l + 1] - a.mom_edge[l];
+  }
+  s_neg[threadIdx.x] = neg;
+  __syncthreads();
+  const long long rows = 2LL * nd;
+  double* o = a.out + 2 * rows * NM;      // number | mean_log_p | quantile [3] | slope, [2][nd] each
+  if (threadIdx.x == 0) {
+    const TcutRowStats st = tcut_row_stats(s_g, s_e, nm);
+    o[r] = st.number;
+    o[rows + r] = st.mean;
+    for (int j = 0; j < MCS_TCUT_NQ; ++j) o[(2 + j) * rows + r] = st.quant[j];
+    double slope = __builtin_nan("");
+    if (st.number > 0)
+      slope = mcs_slope_rule(a.l_lo, a.l_hi, [&](int l) { return s_g[l] > 0; }, [&](int l) { return 0.5 * (s_e[l] + s_e[l + 1]); },
+                             [&](int l) { return mcsm::log10(s_g[l] / s_w[l]); });
+    o[(2 + MCS_TCUT_NQ) * rows + r] = slope;
+    unsigned int t = 0;
+    for (int i = 0; i < 64; ++i) t += s_neg[i];
+    a.row_neg[r] = t;
+    s_num = st.number;
+  }
+  __syncthreads();
+  const double num = s_num;
+  for (int l = threadIdx.x; l < NM; l += 64) {
+    a.out[(long long)r * NM + l] = tcut_spectrum_word(s_g, l, nm, num);
+    double dn = 1.0e-99;
+    if (num > 0 && l <= nm && s_g[l] != 0.0) dn = s_g[l] / s_w[l];
+    a.out[(rows + r) * NM + l] = dn;
+  }
+}
+
+// The join, one block: a lane per momentum bin the gradient over the detectors (frame 0; now - base recomputed, the same bits), then
+// lane 0 the counts.
+__global__ void __launch_bounds__(DET_JOIN_THREADS) mcs_k_detector_join(DetArgs a) {
+  __shared__ unsigned int s_fin[DET_JOIN_THREADS];
+  const int nm = a.nm, NM = nm + 2, nd = a.nd;
+  const long long rows = 2LL * nd;
+  double* grad = a.out + rows * (2 * NM + 3 + MCS_TCUT_NQ);
+  unsigned int fin = 0;
+  for (int l = threadIdx.x; l < NM; l += DET_JOIN_THREADS) {
+    double gr = __builtin_nan("");
+    if (l <= nm) {
+      auto g = [&](int d) { return a.now_sf[(long long)TCUT_STRIDE * d + l] - a.base[(long long)TCUT_STRIDE * d + l]; };
+      gr = mcs_slope_rule(0, nd, [&](int d) { return a.x_spec[d] < 0.0 && g(d) > 0; }, [&](int d) { return a.x_spec[d] / a.x_unit; },
+                          [&](int d) { return mcsm::log10(g(d)); });
+    }
+    grad[l] = gr;
+    if (gr - gr == 0.0) ++fin;      // (finite)
+  }
+  s_fin[threadIdx.x] = fin;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double* number = a.out + 2 * rows * NM;
+    unsigned long long live = 0ull, neg = 0ull, nf = 0ull;
+    for (int r = 0; r < rows; ++r) { if (number[r] > 1.0e-99) ++live; neg += a.row_neg[r]; }
+    for (int i = 0; i < DET_JOIN_THREADS; ++i) nf += s_fin[i];
+    a.diag[0] = live; a.diag[1] = neg; a.diag[2] = nf;
   }
 }
 
@@ -1093,6 +1199,21 @@ extern "C" hipError_t mcs_launch_tcut_spectra(const mcs_params* P, const double*
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(mcs_k_tcut_index, dim3(1), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t mcs_launch_detector_spectra(const mcs_params* P, const double* now_sf, const double* now_pf, const double* base,
+                                                  const double* mom_log, const double* mom_edge, const double* x_spec, int n_det, int l_lo,
+                                                  int l_hi, double x_unit, double* out, unsigned int* row_neg, unsigned long long* diag,
+                                                  hipStream_t st) {
+  DetArgs a{};
+  a.now_sf = now_sf; a.now_pf = now_pf; a.base = base; a.mom_log = mom_log; a.mom_edge = mom_edge; a.x_spec = x_spec; a.x_unit = x_unit;
+  a.nm = P->num_psd_mom_bins; a.nd = n_det; a.l_lo = l_lo; a.l_hi = l_hi;
+  a.out = out; a.row_neg = row_neg; a.diag = diag;
+  hipLaunchKernelGGL(mcs_k_detector_rows, dim3(2 * n_det), dim3(64), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mcs_k_detector_join, dim3(1), dim3(DET_JOIN_THREADS), 0, st, a);
   return hipGetLastError();
 }
 

@@ -42,6 +42,14 @@ struct McsCtxView {
   const double* prof_out;
   bool have_prof;
   mcs_profile_in prof_in;
+  // what the last mcs_detector_spectra left on the device, in mcs_detector_layout (null before the first call), whether it is a whole
+  // result since the last mcs_begin_species / mcs_set_cuts / detectors sample, and that call's settings: nd, window, x_unit and the
+  // host copy of x_spec[0..nd) that the context keeps (valid until its next mcs_set_cuts)
+  const double* det_out;
+  bool have_det;
+  int det_n, det_lo, det_hi;
+  double det_x_unit;
+  const double* det_x_spec;
 };
 
 extern "C" {
@@ -64,6 +72,8 @@ void mcs_ctx_view_angles_taken(mcs_ctx* ctx);
 void mcs_ctx_view_tcuts_taken(mcs_ctx* ctx);
 // A profile sample has been queued from ctx's mcs_profile_update result: that call has to run again before the next.
 void mcs_ctx_view_profile_taken(mcs_ctx* ctx);
+// A detectors sample has been queued from ctx's mcs_detector_spectra result: that call has to run again before the next.
+void mcs_ctx_view_detectors_taken(mcs_ctx* ctx);
 // Sets the message of the calling thread's last error (what the ABI's error call returns); returns 1.
 int mcs_ctx_view_fail(const char* msg);
 }

@@ -13,7 +13,7 @@
 // last kernel that folds a range's partials in index order.  No atomics: the same state gives the same bits.
 // The comparison of two slots (mcs_ens_compare) is the same walk over the (mean, M2) pairs of both with a record of its own: the
 // four sweep kernels share one routine, walk, for which words a thread sees and in which order.
-// Host side: every slot of every kind -- species, iteration, products, photons, source, escape, angles, tcuts, profile -- is one Slot (count, mean, M2); decode reads
+// Host side: every slot of every kind -- species, iteration, products, photons, source, escape, angles, tcuts, profile, detectors -- is one Slot (count, mean, M2); decode reads
 // a slot number's bits, slot_ref finds its Slot, reserve allocates it, merge_slot merges it, and plan_ranges checks the ranges of a
 // summary or comparison and lays out their blocks in one pass.
 // A context is seen through mcs_ctx_view.h; its stream carries the work, an event of the accumulator orders successive operations
@@ -685,13 +685,14 @@ constexpr int ESCAPE_BIT = 1 << 27;        // MCS_ENS_ESCAPE
 constexpr int ANGLES_BIT = 1 << 26;        // MCS_ENS_ANGLES
 constexpr int TCUTS_BIT = 1 << 25;         // MCS_ENS_TCUTS
 constexpr int PROFILE_SLOT = 1 << 24;      // MCS_ENS_PROFILE
+constexpr int DETECTORS_BIT = 1 << 23;     // MCS_ENS_DETECTORS
 
-// The nine kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
+// The ten kinds of slot, and the one place where the bits of a slot number are read: -> its kind and the species slot it belongs
 // to (s; not yet held against the accumulator's species slots, slot_ref does that; -1 for the iteration, the source and the profile slot).
 // A negative number has every high bit set: it is no companion slot, and is refused as a species slot outside the range.
 // The source slot has the photons slots' vector and layout rules; it is a kind of its own in a comparison.
-enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, ANGLES, TCUTS, PROFILE, N_KINDS };
-const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape", "angles", "tcuts", "profile"};
+enum Kind { SPECIES, ITERATION, PRODUCTS, PHOTONS, SOURCE, ESCAPE, ANGLES, TCUTS, PROFILE, DETECTORS, N_KINDS };
+const char* const KIND_NAME[] = {"species", "iteration", "products", "photons", "source", "escape", "angles", "tcuts", "profile", "detectors"};
 struct SlotId { Kind kind; int s; };
 SlotId decode(int slot, int n_slots) {
   if (slot == PHOTONS_ALL) return SlotId{SOURCE, -1};
@@ -701,6 +702,7 @@ SlotId decode(int slot, int n_slots) {
   if (slot >= 0 && (slot & ESCAPE_BIT) != 0) return SlotId{ESCAPE, slot ^ ESCAPE_BIT};
   if (slot >= 0 && (slot & ANGLES_BIT) != 0) return SlotId{ANGLES, slot ^ ANGLES_BIT};
   if (slot >= 0 && (slot & TCUTS_BIT) != 0) return SlotId{TCUTS, slot ^ TCUTS_BIT};
+  if (slot >= 0 && (slot & DETECTORS_BIT) != 0) return SlotId{DETECTORS, slot ^ DETECTORS_BIT};
   return slot == n_slots - 1 ? SlotId{ITERATION, -1} : SlotId{SPECIES, slot};
 }
 bool has_photon_vector(Kind k) { return k == PHOTONS || k == SOURCE; }
@@ -761,6 +763,13 @@ struct mcs_ens {
   mcs_profile_in prof_set{};
   bool prof_taken = false;
   Slot profile;
+  // the detectors slots, like the tcuts slots (include/mcs.h, "detectors sample"): DL.total doubles per vector; the settings of the first
+  // detectors sample (or merge) -- det_n detectors, the window, x_unit and x_spec -- are fixed from then on; det_n 0: none yet
+  mcs_ens_detectors_layout DL{};
+  int det_n = 0, det_lo = 0, det_hi = 0;
+  double det_x_unit = 0.0;
+  std::vector<double> det_x_spec;
+  std::vector<Slot> detectors;
   // the photons slots, likewise (include/mcs.h, "photons sample"): HL.total doubles per vector; no layout while ph_shells is 0
   mcs_ens_photons_layout HL{};
   int ph_shells = 0, ph_n[3] = {0, 0, 0}, ph_start[3] = {0, 0, 0}, ph_npts = 0;
@@ -776,21 +785,23 @@ struct mcs_ens {
   bool has_angle_windows() const { return ang_n_win > 0; }
   bool has_tcuts() const { return tc_n > 0; }
   bool has_profile() const { return prof_taken; }
+  bool has_detectors() const { return det_n > 0; }
   // the one way from a (checked) slot number to its record, and the length of the vectors of a kind
   Slot& at(SlotId id) {
     return id.kind == SOURCE ? source : id.kind == PHOTONS ? photons[(size_t)id.s] : id.kind == PRODUCTS ? products[(size_t)id.s]
            : id.kind == ESCAPE ? escape[(size_t)id.s] : id.kind == ANGLES ? angles[(size_t)id.s]
            : id.kind == TCUTS ? tcuts[(size_t)id.s] : id.kind == PROFILE ? profile
+           : id.kind == DETECTORS ? detectors[(size_t)id.s]
            : main[(size_t)(id.kind == ITERATION ? n_slots - 1 : id.s)];
   }
   long long len(Kind k) const {
-    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ANGLES ? (has_angle_windows() ? AL.total : 0) : k == TCUTS ? (has_tcuts() ? TL.total : 0) : k == PROFILE ? (has_profile() ? FL.total : 0) : k == ITERATION ? E.it_total : E.sp_total;
+    return has_photon_vector(k) ? (has_photon_layout() ? HL.total : 0) : k == PRODUCTS ? PL.total : k == ESCAPE ? XL.total : k == ANGLES ? (has_angle_windows() ? AL.total : 0) : k == TCUTS ? (has_tcuts() ? TL.total : 0) : k == PROFILE ? (has_profile() ? FL.total : 0) : k == DETECTORS ? (has_detectors() ? DL.total : 0) : k == ITERATION ? E.it_total : E.sp_total;
   }
   // every slot number the accumulator has
   std::vector<int> slot_numbers() const {
     std::vector<int> all;
     for (int s = 0; s < n_slots; ++s) all.push_back(s);
-    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); all.push_back(s | ESCAPE_BIT); all.push_back(s | ANGLES_BIT); all.push_back(s | TCUTS_BIT); }
+    for (int s = 0; s < n_slots - 1; ++s) { all.push_back(s | PRODUCTS_BIT); all.push_back(s | PHOTONS_BIT); all.push_back(s | ESCAPE_BIT); all.push_back(s | ANGLES_BIT); all.push_back(s | TCUTS_BIT); all.push_back(s | DETECTORS_BIT); }
     all.push_back(PHOTONS_ALL);
     all.push_back(PROFILE_SLOT);
     return all;
@@ -827,7 +838,7 @@ int leave(mcs_ens* e, hipStream_t st) {
 struct SlotRef { Kind kind; Slot* slot; long long len; };
 int slot_ref(mcs_ens* e, const std::string& who, int slot, SlotRef* out) {
   const SlotId id = decode(slot, e->n_slots);
-  if ((id.kind == PRODUCTS || id.kind == PHOTONS || id.kind == ESCAPE || id.kind == ANGLES || id.kind == TCUTS) && id.s >= e->n_slots - 1)
+  if ((id.kind == PRODUCTS || id.kind == PHOTONS || id.kind == ESCAPE || id.kind == ANGLES || id.kind == TCUTS || id.kind == DETECTORS) && id.s >= e->n_slots - 1)
     return fail(who + ": " + KIND_NAME[id.kind] + " slot of slot " + std::to_string(id.s) + ", which is no species slot (0.." + std::to_string(e->n_slots - 2) + ")");
   if (id.kind == SPECIES && (slot < 0 || slot >= e->n_slots)) return fail(who + ": slot " + std::to_string(slot) + " outside 0.." + std::to_string(e->n_slots - 1));
   *out = SlotRef{id.kind, &e->at(id), e->len(id.kind)};
@@ -880,6 +891,22 @@ void profile_take(mcs_ens* e, const mcs_profile_in& in) {
   e->prof_set = in;
   e->prof_taken = true;
   mcs_profile_get_layout(&e->P, &e->FL);
+}
+
+// both have taken detectors samples, and their settings (nd, window, the bits of x_unit and of x_spec) differ
+bool detector_settings_differ(int na, int lo_a, int hi_a, double xu_a, const double* xs_a, int nb, int lo_b, int hi_b, double xu_b, const double* xs_b) {
+  return na != nb || lo_a != lo_b || hi_a != hi_b || std::memcmp(&xu_a, &xu_b, sizeof(double)) != 0 ||
+         std::memcmp(xs_a, xs_b, sizeof(double) * (size_t)na) != 0;
+}
+bool detectors_differ(const mcs_ens* a, const mcs_ens* b) {
+  return a->has_detectors() && b->has_detectors() &&
+         detector_settings_differ(a->det_n, a->det_lo, a->det_hi, a->det_x_unit, a->det_x_spec.data(), b->det_n, b->det_lo, b->det_hi, b->det_x_unit,
+                                  b->det_x_spec.data());
+}
+void detectors_take(mcs_ens* e, int nd, int l_lo, int l_hi, double x_unit, const double* x_spec) {
+  e->det_n = nd; e->det_lo = l_lo; e->det_hi = l_hi; e->det_x_unit = x_unit;
+  e->det_x_spec.assign(x_spec, x_spec + nd);
+  mcs_detector_get_layout(&e->P, nd, &e->DL);
 }
 
 // both have a photon layout, and the two differ
@@ -1047,6 +1074,7 @@ int mcs_ens_create(mcs_ctx* home, int n_species_slots, mcs_ens** out) {
   e->escape.resize((size_t)n_species_slots);
   e->angles.resize((size_t)n_species_slots);
   e->tcuts.resize((size_t)n_species_slots);
+  e->detectors.resize((size_t)n_species_slots);
   const mcs_layout& L = v.L;
   e->inc = IncRanges{{L.esc_flux, L.esc_energy_eff, L.spectra_coupled}, {L.px_esc_feb, L.weight_coupled, L.energy_transfer_pool}};
   e->n_slots = n_species_slots + 1;
@@ -1289,6 +1317,37 @@ int mcs_ens_add_profile(mcs_ens* e, mcs_ctx* src) {
   return leave(e, v.stream);
 }
 
+int mcs_ens_detectors_get_layout(const mcs_params* p, int n_det, mcs_ens_detectors_layout* out) {
+  if (!p || !out) return fail("mcs_ens_detectors_get_layout: null argument");
+  return mcs_detector_get_layout(p, n_det, out);
+}
+
+int mcs_ens_add_detectors(mcs_ens* e, mcs_ctx* src, int slot) {
+  const std::string who = "mcs_ens_add_detectors";
+  if (!e || !src) return fail(who + ": null argument");
+  if (species_slot(e, who, slot, "only a species slot has a detectors slot")) return 1;
+  McsCtxView v;
+  if (view_of(e, src, who.c_str(), &v)) return 1;
+  if (!v.have_det || !v.det_out || !v.det_x_spec)
+    return fail(who + ": the context needs an mcs_detector_spectra since its last mcs_begin_species and its last detectors sample");
+  if (e->has_detectors() && detector_settings_differ(e->det_n, e->det_lo, e->det_hi, e->det_x_unit, e->det_x_spec.data(), v.det_n, v.det_lo,
+                                                     v.det_hi, v.det_x_unit, v.det_x_spec))
+    return fail(who + ": the settings of the context's mcs_detector_spectra (" + std::to_string(v.det_n) + " detectors, window [" +
+                std::to_string(v.det_lo) + ", " + std::to_string(v.det_hi) + "), x_unit, x_spec) differ from those of the accumulator's detectors samples (" +
+                std::to_string(e->det_n) + " detectors, window [" + std::to_string(e->det_lo) + ", " + std::to_string(e->det_hi) + "))");
+  if (enter(e, v.stream)) return 1;
+  if (!e->has_detectors()) detectors_take(e, v.det_n, v.det_lo, v.det_hi, v.det_x_unit, v.det_x_spec);
+  Slot& sl = e->detectors[(size_t)slot];
+  if (reserve(sl, e->DL.total, who, v.stream)) return 1;
+  // the sample is the call's result as it lies on the device
+  hipLaunchKernelGGL(mcs_k_ens_add_vector, dim3(grid_for(e->DL.total)), dim3(ENS_THREADS), 0, v.stream, sl.mean.get(), sl.m2.get(), v.det_out,
+                     (long long)e->DL.total, (double)(sl.n + 1));
+  ENSCHK(hipGetLastError());
+  sl.n += 1;
+  mcs_ctx_view_detectors_taken(src);
+  return leave(e, v.stream);
+}
+
 int mcs_ens_photons_get_layout(int n_shells, int n_synch, int n_ic, int n_pion, int n_pts, mcs_ens_photons_layout* out) {
   if (!out) return fail("mcs_ens_photons_get_layout: null argument");
   const int n[3] = {n_synch, n_ic, n_pion}, start[3] = {0, 0, 0};
@@ -1389,6 +1448,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (angle_windows_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' angle windows differ");
   if (tcuts_differ(dst, src)) return fail("mcs_ens_merge: the accumulators' tcuts samples differ in n_tcuts");
   if (profiles_differ(dst, src)) return fail("mcs_ens_merge: the settings of the accumulators' profile samples differ");
+  if (detectors_differ(dst, src)) return fail("mcs_ens_merge: the settings of the accumulators' detectors samples differ");
   McsCtxView v;
   if (mcs_ctx_view_get(dst->home, &v)) return 1;
   const std::vector<int> slots = dst->slot_numbers();
@@ -1413,6 +1473,7 @@ int mcs_ens_merge(mcs_ens* dst, mcs_ens* src) {
   if (any[ANGLES] && !dst->has_angle_windows()) angle_windows_take(dst, src->ang_n_win, src->ang_lo, src->ang_hi);
   if (any[TCUTS] && !dst->has_tcuts()) tcuts_take(dst, src->tc_n);
   if (any[PROFILE] && !dst->has_profile()) profile_take(dst, src->prof_set);
+  if (any[DETECTORS] && !dst->has_detectors()) detectors_take(dst, src->det_n, src->det_lo, src->det_hi, src->det_x_unit, src->det_x_spec.data());
   // (the source slot merges like a photons slot; what is pending on either side stays where it is)
   for (int slot : slots) {
     const SlotId id = decode(slot, dst->n_slots);
@@ -1512,6 +1573,12 @@ int mcs_ens_summarize_merged(int n_ens, mcs_ens* const* ens, int slot, int n_ran
         if (profiles_differ(ens[j], ens[k])) return fail(who + ": the settings of the accumulators' profile samples differ");
       if (ens[k]->len(sr.kind) > len) len = ens[k]->len(sr.kind);      // (an accumulator that took no profile sample has no length)
     }
+  if (sr.kind == DETECTORS)
+    for (int k = 1; k < n_ens; ++k) {
+      for (int j = 0; j < k; ++j)
+        if (detectors_differ(ens[j], ens[k])) return fail(who + ": the settings of the accumulators' detectors samples differ");
+      if (ens[k]->len(sr.kind) > len) len = ens[k]->len(sr.kind);      // (an accumulator that took no detectors sample has no length)
+    }
   if (has_photon_vector(sr.kind))
     for (int k = 1; k < n_ens; ++k) {
       for (int j = 0; j < k; ++j)
@@ -1566,6 +1633,7 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   const long long len = ra.len;
   if (ra.kind == TCUTS && rb.kind == TCUTS && tcuts_differ(a, b)) return fail(who + ": the accumulators' tcuts samples differ in n_tcuts");
   if (ra.kind == PROFILE && rb.kind == PROFILE && profiles_differ(a, b)) return fail(who + ": the settings of the accumulators' profile samples differ");
+  if (ra.kind == DETECTORS && rb.kind == DETECTORS && detectors_differ(a, b)) return fail(who + ": the settings of the accumulators' detectors samples differ");
   if (ra.kind != rb.kind || len != rb.len) return fail(who + ": the two slots differ in kind or length");
   if (n_ranges < 0 || n_ranges > SUM_MAX_RANGES) return fail(who + ": n_ranges outside 0.." + std::to_string(SUM_MAX_RANGES));
   if (n_ranges == 0) return 0;
@@ -1583,6 +1651,9 @@ int mcs_ens_compare(mcs_ens* a, int slot_a, mcs_ens* b, int slot_b, int n_ranges
   }
   if (ra.kind == PROFILE) {
     if (sa.n == 0 || sb.n == 0) return fail(who + ": a profile slot has never taken a sample");
+  }
+  if (ra.kind == DETECTORS) {
+    if (sa.n == 0 || sb.n == 0) return fail(who + ": a detectors slot has never taken a sample");
   }
   if (has_photon_vector(ra.kind)) {
     if (sa.n == 0 || sb.n == 0) return fail(who + ": a photons slot has never taken a sample");

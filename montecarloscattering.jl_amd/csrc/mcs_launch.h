@@ -56,6 +56,9 @@ hipError_t mcs_launch_tcut_spectra(const mcs_params* P, const double* now, const
 hipError_t mcs_launch_profile_update(const mcs_params* P, const mcs_profile_in* in, const double* pxx_flux, const double* energy_flux,
                                      const double* scalars, const double* ux, const double* gam_sf, const double* x_grid, const double* pres,
                                      const double* tab, double* out, unsigned long long* diag, hipStream_t st);
+hipError_t mcs_launch_detector_spectra(const mcs_params* P, const double* now_sf, const double* now_pf, const double* base, const double* mom_log,
+                                       const double* mom_edge, const double* x_spec, int n_det, int l_lo, int l_hi, double x_unit, double* out,
+                                       unsigned int* row_neg, unsigned long long* diag, hipStream_t st);
 hipError_t mcs_launch_dndp_2d(const mcs_params* P, const double* psd, const double* therm_sf, const unsigned long long* num_crossings, const double* tabs,
                               double rest_energy, double n0, int therm_from_hist, double gam_x, double beta_x, double* scratch, double* ef, hipStream_t st);
 hipError_t mcs_launch_photon_ic(const double* ef, const double* p_edge, const double* field, int n_grid, int NM, int NT, int j_max, int n_nu, int n_photon,

@@ -85,6 +85,7 @@ class RunResult:
     escape: object = None         # [(i_iter, i_ion, consumers.EscapeSpectra)] of every species end (run(escape=True)); None without
     tcuts: object = None          # [(i_iter, i_ion, consumers.TcutSpectra)] of every species end (run(tcuts=True)); None without
     profile: object = None        # [(i_iter, consumers.ProfileUpdate)] of every iteration's finalize step (run(profile=True)); None without
+    detectors: object = None      # [(i_iter, i_ion, consumers.DetectorSpectra)] of every species end (run(detectors=True)); None without
     angles: object = None         # [(i_iter, i_ion, consumers.AngleDistributions)] of every species end (run(angles=[...])); None without
 
 
@@ -394,6 +395,9 @@ def _species_transport(rs, be, i_iter, i_ion, hook, out_stats, out_empty):
     if rs.do_tcuts and not hasattr(be, "tcut_spectra"):
         # (a backend without K12: the base its numpy statement needs, the species' coupled spectra as they stand now)
         rs.tcut_base[id(be)] = L.view(be.read_tallies()[0], "spectra_coupled")[i_ion - 1].copy()
+    if rs.detector_window is not None and not hasattr(be, "detector_spectra"):
+        # (a backend without K14: the base its numpy statement needs, the detectors' rows as they stand now)
+        rs.detector_base[id(be)] = consumers.detector_base(be, len(rs.prob.x_spec))
     if rs.is_root:
         be.set_fluxes(inj.pxx_flux, inj.pxz_flux, inj.energy_flux)
     if rs.multi:
@@ -684,6 +688,18 @@ def _species_tcuts(rs, be, i_iter, i_ion):
         rs.ensemble.add_tcuts(be, i_ion - 1, spec)
 
 
+def _species_detectors(rs, be, i_iter, i_ion):
+    """The detector spectra of species i_ion (run(detectors=...); K14 on a HIP backend): the growth of the detectors' rows of
+    spectra_sf and spectra_pf on the one context since its begin_species.  With an ensemble, one detectors sample into
+    Ensemble.detectors_slot(i_ion - 1)."""
+    if not rs.is_root:
+        return
+    spec = consumers.detector_spectra(rs.prob, be, i_ion, window=rs.detector_window, base=rs.detector_base.get(id(be)))
+    rs.detectors.append((i_iter, i_ion, spec))
+    if rs.ensemble is not None:
+        rs.ensemble.add_detectors(be, i_ion - 1, spec)
+
+
 def _iteration_profile(rs, be, it_state, sm, i_iter, ion_fin):
     """The profile update of iteration i_iter (run(profile=True); K13 on a HIP backend) from the tallies and pressures of the last
     species on the primary context, before iter_finalize touches `prob`.  With smooth_shocks the q of up to three earlier iterations
@@ -714,6 +730,8 @@ def _iteration_species(rs, i_iter, before_pcut):
                 _species_angles(rs, rs.backend, i_iter, i_ion)
             if rs.do_tcuts:
                 _species_tcuts(rs, rs.backend, i_iter, i_ion)
+            if rs.detector_window is not None:
+                _species_detectors(rs, rs.backend, i_iter, i_ion)
             if rs.photons is not None:
                 _species_photons(rs, i_iter, i_ion)
         return
@@ -746,7 +764,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         before_pcut: Optional[Callable] = None, tcut_print: bool = False, fused_pcuts: Optional[bool] = None, long_draws: Optional[int] = None,
         long_imult_max: Optional[int] = None, species_backends: Optional[list] = None, fused_chunk: Optional[int] = None,
         ensemble=None, triggers: Optional[list] = None, min_iterations: int = 2, check_every: int = 1, photons=None,
-        escape: bool = False, angles=None, tcuts: bool = False, profile: bool = False) -> RunResult:
+        escape: bool = False, angles=None, tcuts: bool = False, profile: bool = False, detectors=False) -> RunResult:
     """Run `n_itrs` iterations of all species through all pcuts.
 
     backend protocol: create/begin_iteration/begin_species/set_fluxes/init_pop/
@@ -858,6 +876,14 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
     profile none, so that its samples stay independent, and with ensemble one PROFILE sample per iteration goes into
     Ensemble.profile_slot (ensemble.py, "Profile"; ensemble.profile_consistency reads it).  Refused: profile without finalize, with
     a communicator, a trigger on the profile slot without profile.  False: no new call is made.
+    detectors: True, or a slope window (l_lo, l_hi) over the momentum bins (True: all bins).  After every species' last pcut,
+    consumers.detector_spectra: per frame and XSPEC detector the normalised spectrum of what crossed it, its dN/dp, sum, mean and three
+    quantiles of log10 p and its spectral slope, and per momentum bin the gradient of log10 of the growth over the upstream detectors
+    in units of 1/rg0 -- ln 10 times it is u0 / D(p), the inverse e-fold length of the precursor (K14 on a HIP backend; on another
+    backend the numpy statement of the same rules, with the base kept here).  RunResult.detectors holds [(i_iter, i_ion,
+    DetectorSpectra)].  With ensemble, one DETECTORS sample per species and iteration goes into Ensemble.detectors_slot(i_ion - 1)
+    (ensemble.py, "Detectors").  Refused: detectors without finalize, on a problem with no XSPEC, with a communicator, with
+    species_backends (see the message), a trigger on a detectors slot without detectors.  False: no new call is made.
     """
     import torch
     comm = comm or Comm(False)
@@ -888,6 +914,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
         long_draws=long_draws, long_imult_max=long_imult_max, species_tallies=species_tallies, final_full_read=final_full_read, on_species_end=on_species_end,
         photons=photons, photon_spectra=[None] * len(cfg.species), last_ion_fin=None, do_escape=bool(escape), escape=[],
         angle_windows=None, angles=[], do_tcuts=bool(tcuts), tcuts=[], tcut_base={}, profile=[],
+        detector_window=None, detectors=[], detector_base={},
         G_f=None, G_i=None, G_pool=None, stats=[], per_species=[], local_steps=[], empty_launches=[], species_spans=[], iter_finals=[])
     # the step counters are never reset: this rank's running total.  A context that has run before (run() called again with
     # first_iter / iter_state, the documented way to step through the loop) starts from what its counters hold now.
@@ -935,6 +962,23 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
             ensemble.expect_tcuts(len(prob.tcuts))
     elif any(ens.Ensemble.is_tcuts(t.slot) for t in triggers):
         raise ValueError("triggers: a trigger on a tcuts slot needs tcuts=True (no sample would ever arrive)")
+    if detectors is not False and detectors is not None:
+        if not (finalize or smoothing is not None):
+            raise ValueError("detectors: needs finalize=True (the detector spectra belong to the iteration's finalize step)")
+        if len(prob.x_spec) < 1:
+            raise ValueError("detectors: the problem has no detector (XSPEC)")
+        if comm.enabled:
+            raise ValueError("detectors: one process without a communicator (the multi-rank case is left out)")
+        if species_backends:
+            raise ValueError("detectors: one context only (no species_backends): spectra_sf and spectra_pf are shared by all species, so "
+                             "accumulate_tallies would add a secondary's species into the primary's rows while another species may be current "
+                             "there, and that species' growth over its base would include it")
+        rs.detector_window = consumers.check_detector_window(P.num_psd_mom_bins, None if detectors is True else detectors)
+        if ensemble is not None:      # (before the triggers are held against the ensemble's parts)
+            ensemble.expect_detectors((len(prob.x_spec), rs.detector_window[0], rs.detector_window[1], np.float64(prob.rg0).tobytes(),
+                                       np.ascontiguousarray(prob.x_spec, dtype=np.float64).tobytes()))
+    elif any(ens.Ensemble.is_detectors(t.slot) for t in triggers):
+        raise ValueError("triggers: a trigger on a detectors slot needs detectors=True (no sample would ever arrive)")
     if profile:
         if not (finalize or smoothing is not None):
             raise ValueError("profile: needs finalize=True (the profile update belongs to the iteration's finalize step)")
@@ -1053,6 +1097,7 @@ def run(prob: Problem, backend, comm: Optional[Comm] = None, n_itrs: Optional[in
                      Convergence(checks, stopped_at, satisfied) if triggers else None,
                      list(rs.photon_spectra) if photons is not None else None, rs.escape if escape else None,
                      tcuts=rs.tcuts if tcuts else None, profile=rs.profile if profile else None,
+                     detectors=rs.detectors if rs.detector_window is not None else None,
                      angles=rs.angles if angles is not None else None)
 
 
@@ -1066,7 +1111,7 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
                    on_iteration_end: Optional[Callable] = None, first_iter: int = 1,
                    blocks_per_launch: Optional[int] = None, ensemble: bool = False, triggers: Optional[list] = None,
                    min_iterations: int = 2, check_every: int = 1, photons=None, escape: bool = False, angles=None,
-                   tcuts: bool = False, profile: bool = False) -> RunResult:
+                   tcuts: bool = False, profile: bool = False, detectors=False) -> RunResult:
     """The iterations of a run with a FIXED shock profile (smooth-shocks = false -- the stock mc_in.toml, BASELINE
     config[1]) are independent Monte-Carlo realisations: nothing an iteration computes enters the next one's transport
     (src/main_loops.jl:52-121: every tally the transport reads is reset at the top; the RNG keys carry i_iter).  Their
@@ -1115,7 +1160,10 @@ def run_overlapped(prob: Problem, backends, n_itrs: Optional[int] = None, max_pc
     escape: refused -- the escape spectra of run(escape=True) are left out of the overlapped path.
     angles: refused likewise -- the pitch-angle distributions of run(angles=[...]) are left out of the overlapped path.
     tcuts: refused likewise -- the time-cut spectra of run(tcuts=True) are left out of the overlapped path.
-    profile: refused likewise -- the profile update of run(profile=True) is left out of the overlapped path."""
+    profile: refused likewise -- the profile update of run(profile=True) is left out of the overlapped path.
+    detectors: refused likewise -- the detector spectra of run(detectors=True) are left out of the overlapped path."""
+    if (detectors is not False and detectors is not None) or any(ens.Ensemble.is_detectors(t.slot) for t in (triggers or [])):
+        raise ValueError("detectors: the overlapped run leaves the detector spectra out; use run(finalize=True, detectors=True)")
     if profile or any(ens.Ensemble.is_profile(t.slot) for t in (triggers or [])):
         raise ValueError("profile: the overlapped run leaves the profile update out; use run(finalize=True, profile=True)")
     if tcuts or any(ens.Ensemble.is_tcuts(t.slot) for t in (triggers or [])):

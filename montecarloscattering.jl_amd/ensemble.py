@@ -93,6 +93,26 @@ cut.  A cut that no particle reached is a dead row: its mean_log_p and quantiles
 non-finite, a summary counts it in n_nonfinite and a trigger over it is never met -- triggers belong on cuts below age_max (the last
 cut lies above 10 age_max and is always dead).
 
+Detectors (include/mcs.h, "detectors sample"): the spectra at the XSPEC detectors, consumers.detector_spectra (K14), sampled once per
+species and iteration by driver.run(finalize=True, detectors=True, ensemble=...).  Every species slot s has a sixth companion, the
+detectors slot `Ensemble.detectors_slot(s)`, whose vectors exist from its first sample on.  The ensemble keeps the settings of its
+first detectors sample -- the number of detectors nd, the slope window, the bits of x_unit and of x_spec; a later sample, merge,
+summarize_merged or compare with other settings is refused.  Its parts, with the row r = frame * nd + d (frame 0: shock, 1: plasma):
+
+  spectrum    [2 nd][nmom+2]: the species' growth of the detector's row in the iteration, normalised per row; 1e-99 in an empty bin
+  dndp        [2 nd][nmom+2]: that growth per unit momentum
+  number      [2 nd]: the sum a spectrum row was normalised with
+  mean_log_p  [2 nd]: the mean of log10 p over the row
+  quantile    [3][2 nd]: log10 of the momentum below which 50, 90, 99 % of the weight lies
+  slope       [2 nd]: d log10 dndp / d log10 p over the window
+  gradient    [nmom+2]: per momentum bin, d log10 g / d (x / x_unit) over the upstream detectors: ln 10 times it is u0 / D(p)
+
+zones=Ensemble.detectors_row(frame, d) of a `Request`, `Trigger` or `CompareRequest` selects one row of spectrum, dndp, number,
+mean_log_p and slope, bins= a momentum window of that spectrum or dndp row; of quantile, zones=(j, j + 1) selects the quantile and
+bins=Ensemble.detectors_row(frame, d) the row; of gradient, zones=(l_lo, l_hi) selects momentum bins.  A detector that no particle
+crossed is a dead row, and a gradient bin lit in fewer than three upstream detectors is NaN in that sample: the word's mean stays
+non-finite, a summary counts it in n_nonfinite and a trigger over it is never met.
+
 Profile (include/mcs.h, "profile sample"): the shock profile that smooth_grid_par WOULD write from an iteration's fluxes and pressures,
 consumers.profile_update (K13), sampled once per iteration by driver.run(finalize=True, profile=True, ensemble=...) of a run with a
 FIXED profile: the mean and standard error of that prediction say how far the current profile is from self-consistency.  One slot
@@ -208,6 +228,12 @@ TCUTS_NAMES = ("spectrum", "weight", "number", "mean_log_p", "quantile", "index"
 ZONE_PARTS = ZONE_PARTS + tuple(n for n in TCUTS_NAMES if n not in ZONE_PARTS)
 BIN_PARTS = BIN_PARTS + ("spectrum", "quantile")
 TCUTS_BIT = capi.ENS_TCUTS_BIT            # tcuts slot of species slot s: s | TCUTS_BIT (MCS_ENS_TCUTS)
+# the parts of a detectors slot, in the order of mcs_detector_layout: first axis the row frame * nd + d (zones=; Ensemble.detectors_row),
+# spectrum's and dndp's second the momentum bin (bins=); quantile is [quantile][row]; gradient's only axis is the momentum bin
+DETECTORS_NAMES = ("spectrum", "dndp", "number", "mean_log_p", "quantile", "slope", "gradient")
+ZONE_PARTS = ZONE_PARTS + tuple(n for n in DETECTORS_NAMES if n not in ZONE_PARTS)
+BIN_PARTS = BIN_PARTS + ("dndp",)
+DETECTORS_BIT = capi.ENS_DETECTORS_BIT    # detectors slot of species slot s: s | DETECTORS_BIT (MCS_ENS_DETECTORS)
 # the parts of the profile slot, in the order of mcs_profile_layout: ten rows over the zones (zones=), then the scalars
 PROFILE_ROW_NAMES = ("flux_px", "flux_en", "gamma_ad", "p_flux", "p_used", "ux_px", "ux_en", "ux_pred", "ux_next", "shift")
 PROFILE_SCALAR_NAMES = ("gamma_down", "px_esc_up", "en_esc_up", "q_px", "q_en", "q_px_avg", "q_en_avg", "shift_rms")
@@ -285,6 +311,18 @@ class EnsLayout:
         t = self.tcuts(n_tcuts)
         nt, nm = t["spectrum"][1]
         return dict({name: off for name, (off, _) in t.items()}, row_n=nm, n_tcuts=nt, total=nt * (nm + 6) + 3)
+
+    def detectors(self, n_det: int) -> Dict[str, Tuple[int, tuple]]:
+        """The detectors sample of n_det detectors: mirror of `mcs_ens_detectors_get_layout`, the frame and the detector as one row axis."""
+        nm, r = self.tally.shapes["psd"][2], 2 * int(n_det)
+        a = r * nm
+        return {"spectrum": (0, (r, nm)), "dndp": (a, (r, nm)), "number": (2 * a, (r,)), "mean_log_p": (2 * a + r, (r,)),
+                "quantile": (2 * a + 2 * r, (3, r)), "slope": (2 * a + 5 * r, (r,)), "gradient": (2 * a + 6 * r, (nm,))}
+
+    def detectors_fields(self, n_det: int) -> Dict[str, int]:
+        t = self.detectors(n_det)
+        r, nm = t["spectrum"][1]
+        return dict({name: off for name, (off, _) in t.items()}, row_n=nm, n_det=r // 2, total=r * (2 * nm + 6) + nm)
 
     def profile(self) -> Dict[str, Tuple[int, tuple]]:
         """The profile sample: mirror of `mcs_ens_profile_get_layout`."""
@@ -377,11 +415,12 @@ def stats_over(samples):
 def _check_part(name: str, zones, bins=None):
     """What can be said of a part without an ensemble: the name exists, a zone slice is a pair and the part has a zone axis, a bins
     window is a pair, comes with a single zone and the part has a bins axis."""
-    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES + ANGLES_NAMES + TCUTS_NAMES + PROFILE_NAMES:
+    if name not in SPECIES_NAMES + ITERATION_NAMES + PRODUCT_NAMES + PHOTON_NAMES + ESCAPE_NAMES + ANGLES_NAMES + TCUTS_NAMES + PROFILE_NAMES + DETECTORS_NAMES:
         raise ValueError(f"ensemble: no part {name!r}; a species slot has: {', '.join(SPECIES_NAMES)}; the iteration slot: {', '.join(ITERATION_NAMES)}; "
                          f"a products slot: {', '.join(PRODUCT_NAMES)}; a photons slot: {', '.join(PHOTON_NAMES)}; "
                          f"an escape slot: {', '.join(ESCAPE_NAMES)}; an angles slot: {', '.join(ANGLES_NAMES)}; "
-                         f"a tcuts slot: {', '.join(TCUTS_NAMES)}; the profile slot: {', '.join(PROFILE_NAMES)}")
+                         f"a tcuts slot: {', '.join(TCUTS_NAMES)}; the profile slot: {', '.join(PROFILE_NAMES)}; "
+                         f"a detectors slot: {', '.join(DETECTORS_NAMES)}")
     if bins is not None:
         if name not in BIN_PARTS:
             raise ValueError(f"ensemble: {name!r} has no [zone][bins] shape; a bins window fits: {', '.join(BIN_PARTS)}")
@@ -749,6 +788,7 @@ class Ensemble:
         self.angle_windows = None      # ((l_lo, ...), (l_hi, ...)) of set_angle_windows
         self.tcuts_n = None            # the number of time cuts of the tcuts samples, fixed by the first
         self.profile_settings = None   # ProfileIn.settings() of the first profile sample, fixed by it
+        self.detectors_settings = None # DetectorSpectra.settings() of the first detectors sample, fixed by it: (nd, l_lo, l_hi, x_unit, x_spec)
         self._deposited: List[int] = []      # species slots deposited since the last add_photons_all, in deposit order
 
     @staticmethod
@@ -864,6 +904,44 @@ class Ensemble:
     def _tcuts_differ(a, b) -> bool:
         return a.tcuts_n is not None and b.tcuts_n is not None and a.tcuts_n != b.tcuts_n
 
+    def detectors_slot(self, s: int) -> int:
+        """The slot number of the detector spectra of species slot s (MCS_ENS_DETECTORS)."""
+        if not 0 <= s < self.n_species:
+            raise ValueError(f"ensemble: slot {s} is no species slot (0..{self.n_species - 1}); only a species slot has a detectors slot")
+        return int(s) | DETECTORS_BIT
+
+    @staticmethod
+    def is_detectors(slot: int) -> bool:
+        return (slot >= 0 and slot != PHOTONS_ALL and not slot & (PRODUCTS_BIT | PHOTONS_BIT | ESCAPE_BIT | ANGLES_BIT | TCUTS_BIT | PROFILE_SLOT)
+                and bool(slot & DETECTORS_BIT))
+
+    def detectors_row(self, frame: int, d: int) -> Tuple[int, int]:
+        """zones= of frame (0: shock, 1: plasma) and detector d (0-based) of a detectors slot's spectrum, dndp, number, mean_log_p and
+        slope; bins= of that row of a quantile: the row frame * nd + d."""
+        if self.detectors_settings is None:
+            raise ValueError("ensemble: the detectors samples have no settings yet (expect_detectors, or the first sample)")
+        nd = self.detectors_settings[0]
+        if frame not in (0, 1) or int(d) != d or not 0 <= d < nd:
+            raise ValueError(f"ensemble: a detectors slot has frames 0, 1 and detectors 0..{nd - 1}, not frame {frame!r}, detector {d!r}")
+        r = int(frame) * nd + int(d)
+        return r, r + 1
+
+    def expect_detectors(self, settings):
+        """The settings the detectors samples will have -- DetectorSpectra.settings(): (nd, l_lo, l_hi, the bits of x_unit, the bits of
+        x_spec) -- so that requests and triggers can name their parts before the first sample arrives (which fixes them for good).
+        Refused where the ensemble's detectors samples have others."""
+        settings = tuple(settings)
+        if self.detectors_settings is not None and self.detectors_settings != settings:
+            raise ValueError("ensemble: these detector settings (number of detectors, window, x_unit, x_spec) differ from those of the ensemble's "
+                             "detectors samples")
+        if not 1 <= settings[0] <= self.layout.tally.n_grid:
+            raise ValueError(f"ensemble: a detectors sample has 1..{self.layout.tally.n_grid} detectors, not {settings[0]!r}")
+        self.detectors_settings = settings
+
+    @staticmethod
+    def _detectors_differ(a, b) -> bool:
+        return a.detectors_settings is not None and b.detectors_settings is not None and a.detectors_settings != b.detectors_settings
+
     profile_slot = PROFILE_SLOT        # the profile slot, one per ensemble (MCS_ENS_PROFILE)
 
     @staticmethod
@@ -910,7 +988,7 @@ class Ensemble:
         self.photon_layout = layout
 
     def _decode(self, slot: int) -> Tuple[str, Optional[int]]:
-        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source", "escape", "angles", "tcuts" or "profile" -- the one place where
+        """(kind, species index) of a slot number -- "species", "iteration", "products", "photons", "source", "escape", "angles", "tcuts", "profile" or "detectors" -- the one place where
         its bits are read; the index is None for the iteration, the source and the profile slot, and not yet checked (`_check_slot`)."""
         if self.is_photons_all(slot):
             return "source", None
@@ -926,6 +1004,8 @@ class Ensemble:
             return "angles", slot ^ ANGLES_BIT
         if self.is_tcuts(slot):
             return "tcuts", slot ^ TCUTS_BIT
+        if self.is_detectors(slot):
+            return "detectors", slot ^ DETECTORS_BIT
         return ("iteration", None) if slot == self.iteration_slot else ("species", slot)
 
     def _kind(self, slot: int) -> str:
@@ -933,18 +1013,18 @@ class Ensemble:
 
     def _describe(self, slot: int) -> str:
         kind, s = self._decode(slot)
-        if kind in ("products", "photons", "escape", "angles", "tcuts"):
+        if kind in ("products", "photons", "escape", "angles", "tcuts", "detectors"):
             return f"the {kind} slot of species slot {s}"
         return f"species slot {s}" if kind == "species" else f"the {kind} slot"
 
     def names(self, slot: int):
         self._check_slot(slot)
         return {"species": SPECIES_NAMES, "iteration": ITERATION_NAMES, "products": PRODUCT_NAMES, "escape": ESCAPE_NAMES,
-                "angles": ANGLES_NAMES, "tcuts": TCUTS_NAMES, "profile": PROFILE_NAMES}.get(self._kind(slot), PHOTON_NAMES)
+                "angles": ANGLES_NAMES, "tcuts": TCUTS_NAMES, "profile": PROFILE_NAMES, "detectors": DETECTORS_NAMES}.get(self._kind(slot), PHOTON_NAMES)
 
     def _check_slot(self, slot: int):
         kind, s = self._decode(slot)
-        if kind in ("products", "photons", "escape", "angles", "tcuts") and not 0 <= s < self.n_species:
+        if kind in ("products", "photons", "escape", "angles", "tcuts", "detectors") and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: {kind} slot of slot {s}, which is no species slot (0..{self.n_species - 1})")
         if kind == "species" and not 0 <= s < self.n_species:
             raise ValueError(f"ensemble: slot {slot} outside 0..{self.n_species}")
@@ -959,6 +1039,8 @@ class Ensemble:
             return 0 if self.tcuts_n is None else self.layout.tcuts_fields(self.tcuts_n)["total"]
         if kind == "profile":
             return self.layout.profile_fields()["total"]
+        if kind == "detectors":
+            return 0 if self.detectors_settings is None else self.layout.detectors_fields(self.detectors_settings[0])["total"]
         return {"species": self.layout.species_total, "iteration": self.layout.iteration_total, "products": self.layout.products_total,
                 "escape": self.layout.escape_total}[kind]
 
@@ -981,6 +1063,10 @@ class Ensemble:
             table = self.layout.tcuts(self.tcuts_n)
         elif kind == "profile":
             table = self.layout.profile()
+        elif kind == "detectors":
+            if self.detectors_settings is None:
+                raise ValueError(f"ensemble: {self._describe(slot)} has taken no sample yet (its first fixes the detectors and the window)")
+            table = self.layout.detectors(self.detectors_settings[0])
         else:
             table = {"species": self.layout.species, "iteration": self.layout.iteration, "products": self.layout.products,
                      "escape": self.layout.escape}[kind]
@@ -1233,6 +1319,24 @@ class HostEnsemble(Ensemble):
         with np.errstate(invalid="ignore"):          # (a NaN of a dead row stays NaN)
             self._sample(self.tcuts_slot(slot), x)
 
+    def add_detectors(self, backend, slot: int, spectra):
+        """One detectors sample of species slot `slot` from a `DetectorSpectra` (consumers.detector_spectra); the ensemble's first
+        fixes the settings."""
+        self._species_slot(slot, "a detectors slot")
+        if spectra is None:
+            raise ValueError("ensemble: the numpy ensemble takes its detectors sample from a DetectorSpectra")
+        st = spectra.settings()
+        if self.detectors_settings is not None and st != self.detectors_settings:
+            raise ValueError("ensemble: the settings of the DetectorSpectra (number of detectors, window, x_unit, x_spec) differ from those of "
+                             "the ensemble's detectors samples")
+        x = spectra.words()
+        if x.size != self.layout.detectors_fields(st[0])["total"]:
+            raise ValueError(f"ensemble: the DetectorSpectra holds {x.size} words; a detectors sample of {st[0]} detectors has "
+                             f"{self.layout.detectors_fields(st[0])['total']}")
+        self.detectors_settings = st
+        with np.errstate(invalid="ignore"):          # (a NaN of a dead row or gradient bin stays NaN)
+            self._sample(self.detectors_slot(slot), x)
+
     def add_profile(self, backend, update):
         """One profile sample from a `ProfileUpdate` (consumers.profile_update); the ensemble's first fixes the settings."""
         if update is None:
@@ -1319,6 +1423,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: merge of ensembles whose tcuts samples differ in the number of time cuts")
         if self._profiles_differ(self, other):
             raise ValueError("ensemble: merge of ensembles whose profile samples differ in their settings")
+        if self._detectors_differ(self, other):
+            raise ValueError("ensemble: merge of ensembles whose detectors samples differ in their settings")
         # an ensemble without a photon layout or a slope window takes the one its samples were made with
         if other._sampled("photons", "source") and self.photon_layout is None:
             self.photon_layout = other.photon_layout
@@ -1330,6 +1436,8 @@ class HostEnsemble(Ensemble):
             self.tcuts_n = other.tcuts_n
         if other._sampled("profile") and self.profile_settings is None:
             self.profile_settings = other.profile_settings
+        if other._sampled("detectors") and self.detectors_settings is None:
+            self.detectors_settings = other.detectors_settings
         for k, b in other._slots.items():      # (what is pending for the source slot on either side stays where it is)
             if b.n == 0:
                 continue
@@ -1372,6 +1480,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: a merged summary of ensembles whose tcuts samples differ in the number of time cuts")
         if self.is_profile(slot) and any(self._profiles_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
             raise ValueError("ensemble: a merged summary of ensembles whose profile samples differ in their settings")
+        if self.is_detectors(slot) and any(self._detectors_differ(a, b) for k, a in enumerate(es) for b in es[:k]):
+            raise ValueError("ensemble: a merged summary of ensembles whose detectors samples differ in their settings")
         for first, count, floor_frac, tol in ranges:
             m, q, na = None, None, 0
             for e in [self] + others:
@@ -1395,6 +1505,8 @@ class HostEnsemble(Ensemble):
             raise ValueError("ensemble: a comparison of ensembles whose tcuts samples differ in the number of time cuts")
         if self.is_profile(slot) and self._profiles_differ(self, other):
             raise ValueError("ensemble: a comparison of ensembles whose profile samples differ in their settings")
+        if self.is_detectors(slot) and self._detectors_differ(self, other):
+            raise ValueError("ensemble: a comparison of ensembles whose detectors samples differ in their settings")
         (ma, qa, _), (mb, qb, _) = self._vectors(slot), other._vectors(other_slot)
         return [difference_of(ma[first:first + count], qa[first:first + count], n_a, mb[first:first + count], qb[first:first + count], n_b,
                               floor_frac, zcut) for first, count, floor_frac, zcut in ranges]
@@ -1474,6 +1586,13 @@ class HipEnsemble(Ensemble):
         if self.tcuts_n is None:
             self.tcuts_n = int(backend.n_tcuts)      # (as the library does: the first sample fixes it)
 
+    def add_detectors(self, backend: HipBackend, slot: int, spectra=None):
+        """One detectors sample of species slot `slot` from what mcs_detector_spectra (consumers.detector_spectra) left on the backend's
+        device (mcs_ens_add_detectors); nothing crosses to the host, of `spectra` only the settings are noted."""
+        self._chk(self.lib.mcs_ens_add_detectors(self.h, backend.h, int(slot)))
+        if self.detectors_settings is None and spectra is not None:
+            self.detectors_settings = spectra.settings()      # (as the library does: the first sample fixes them)
+
     def add_profile(self, backend: HipBackend, update=None):
         """One profile sample from what mcs_profile_update (consumers.profile_update) left on the backend's device
         (mcs_ens_add_profile); nothing crosses to the host, of `update` only the settings are noted."""
@@ -1519,6 +1638,8 @@ class HipEnsemble(Ensemble):
             self.tcuts_n = other.tcuts_n      # (likewise)
         if self.profile_settings is None and other.profile_settings is not None and other.count(PROFILE_SLOT):
             self.profile_settings = other.profile_settings      # (likewise)
+        if self.detectors_settings is None and other.detectors_settings is not None and any(other.count(other.detectors_slot(s)) for s in range(other.n_species)):
+            self.detectors_settings = other.detectors_settings      # (likewise)
 
     def count(self, slot: int) -> int:
         n = ct.c_int64(0)

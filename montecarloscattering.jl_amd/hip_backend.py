@@ -82,6 +82,7 @@ class HipBackend:
                                 (prob.pcuts, prob.tcuts, prob.x_spec, prob.inj_fracs, prob.eps_target))
         self._chk(self.lib.mcs_set_cuts(self.h, len(pc), _dp(pc), len(tc), _dp(tc), len(xs), _dp(xs), _dp(inj), _dp(eps)))
         self.n_tcuts = len(tc)
+        self.n_xspec = len(xs)
 
     def destroy(self):
         if self.h:
@@ -414,6 +415,18 @@ class HipBackend:
                 raise ValueError("profile_update: the pressures are three arrays of n_grid doubles")
         self._chk(self.lib.mcs_profile_update(self.h, ct.byref(s), _dp(pr) if pr is not None else None, _dp(out),
                                               diag.ctypes.data_as(c_int64_p)))
+        return out, diag
+
+    def detector_spectra(self, tabs, l_lo: int, l_hi: int, x_unit: float):
+        """K14: the spectra at the detectors for the context's current species from the resident spectra_sf and spectra_pf and the base
+        taken at begin_species -> (out, diag [3]); `out` in mcs_detector_layout (capi.detector_layout), diag = (live rows, words with
+        now < base, finite gradient words)."""
+        if self.n_xspec < 1:
+            raise ValueError("detector_spectra: the context has no detector")
+        out = np.zeros(capi.detector_layout(self.P, self.n_xspec).total)
+        diag = np.zeros(3, dtype=np.int64)
+        s = tabs.as_struct()
+        self._chk(self.lib.mcs_detector_spectra(self.h, ct.byref(s), int(l_lo), int(l_hi), float(x_unit), _dp(out), diag.ctypes.data_as(c_int64_p)))
         return out, diag
 
     def photon_synch(self, dndp_pf, mom_edge_cgs, mc, n_photon, emin_mev, bins_per_dec):
